@@ -178,6 +178,22 @@ def accumulate(kstats, entries):
             a[k] += ks[k]
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, film):
+    """--dump-outputs: what pt_render hands its caller after the last timed step, the (H, W, 4) float32 film (XYZ sums + weight sum), as
+    out_dir/film.npy. A film above DUMP_MAX_BYTES is written as a fixed sample instead: the rows (pixel index y * W + x, ascending) that a
+    seed-0 generator picks, shape (n, 4), so two runs with the same arguments write the same pixels."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    if film.nbytes > DUMP_MAX_BYTES - 4096:   # (room for the .npy header)
+        flat = film.reshape(-1, film.shape[-1])
+        keep = np.sort(np.random.default_rng(0).choice(len(flat), (DUMP_MAX_BYTES - 4096) // flat[0].nbytes, replace=False))
+        film = flat[keep]
+    np.save(os.path.join(out_dir, "film.npy"), np.ascontiguousarray(film, dtype=np.float32))
+
+
 def measure(pkg, lib, torch, dev, dist, args, config, spp, steps, warmup, devices, in_process, rank, world, want_cpu_baseline, proj_world=0):
     """Build the config's scene, run `warmup` untimed + `steps` timed renders, return the result dict (rank 0) or None."""
     builder_fn, named_spp, workload_desc = pkg.scenes.CONFIG_SCENES[config]
@@ -281,6 +297,8 @@ def measure(pkg, lib, torch, dev, dist, args, config, spp, steps, warmup, device
     if args.dump_film and config == args.config:
         import numpy as np
         np.save(args.dump_film, film.cpu().numpy())
+    if args.dump_outputs and config == args.config:
+        dump_outputs(args.dump_outputs, film.cpu().numpy())
 
     # SURVEY 8(d)'s definition of the metric includes the film read-back: timed apart (pinned host buffer, the 4 x f32 x W x H film of the last step)
     # and reported beside `value`, which stays the device-resident figure the contract asks for
@@ -405,9 +423,12 @@ def main():
     ap.add_argument("--devices", default="", help="one-process form: explicit device ordinals, e.g. 0,1,2,3 (an ordinal may repeat: replicas share the device; default 0..gpus-1)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"], help="launcher form: nccl (= RCCL, one GPU per rank) or gloo (film staged through the host; ranks may share a GPU: rehearsal on a one-GPU box)")
     ap.add_argument("--dump-film", default="", help="rank 0 writes the (merged) film of the last step as .npy")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="rank 0 writes the (merged) film of the last timed step as DIR/film.npy (float32, at most 64 MB: a fixed sample of a larger film)")
     ap.add_argument("--projection", default="auto", choices=["auto", "on", "off"], help="scaling_projection: rank 0's shard of an 8-rank job at the named spp, for the headline and for C4 / C5 (auto: default C2 run on one GPU)")
     ap.add_argument("--other-configs", default="auto", choices=["auto", "on", "off"], help="after the headline, one step (one wavefront pass) each of C3 / C4 / C5 under 'other_configs' (auto: default C2 run on one GPU)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))

@@ -23,17 +23,19 @@ def _write_pfm(path, img):          # img: (h, w, 3), top row first
         f.write(b"PF\n%d %d\n-1\n" % (w, h)); f.write(np.ascontiguousarray(img[::-1], dtype="<f4").tobytes())
 
 
-def _write_ply(path, P, N, UV, faces, binary):
+def _write_ply(path, P, N, UV, faces, binary):     # UV=None: no u v properties
+    rows = [(*p, *n) for p, n in zip(P, N)] if UV is None else [(*p, *n, *uv) for p, n, uv in zip(P, N, UV)]
     with open(path, "wb") as f:
         hdr = ["ply", "format %s 1.0" % ("binary_little_endian" if binary else "ascii"), "element vertex %d" % len(P)]
-        hdr += ["property float x", "property float y", "property float z", "property float nx", "property float ny", "property float nz", "property float u", "property float v"]
+        hdr += ["property float x", "property float y", "property float z", "property float nx", "property float ny", "property float nz"]
+        hdr += [] if UV is None else ["property float u", "property float v"]
         hdr += ["element face %d" % len(faces), "property list uint8 int vertex_indices", "end_header"]
         f.write(("\n".join(hdr) + "\n").encode())
         if binary:
-            for p, n, uv in zip(P, N, UV): f.write(struct.pack("<8f", *p, *n, *uv))
+            for r in rows: f.write(struct.pack("<%df" % len(r), *r))
             for fc in faces: f.write(struct.pack("<B%di" % len(fc), len(fc), *fc))
         else:
-            for p, n, uv in zip(P, N, UV): f.write((" ".join(repr(float(x)) for x in (*p, *n, *uv)) + "\n").encode())
+            for r in rows: f.write((" ".join(repr(float(x)) for x in r) + "\n").encode())
             for fc in faces: f.write(("%d %s\n" % (len(fc), " ".join(str(i) for i in fc))).encode())
 
 
@@ -660,7 +662,64 @@ WorldEnd
     np.testing.assert_allclose(list(mat.kd), 0.5 * np.array([3.240479 - 1.537150 - 0.498535, -0.969256 + 1.875991 + 0.041556, 0.055648 - 0.204043 + 1.057311]), rtol=5e-3)   # (the X and Z integrals of the tables differ from the Y integral by ~0.2 %)
 
 
-_REF_SCENES = "/root/reference/src/scenes"
+# A scene file laid out like the pbrt-v3 scenes exporters write: comments and commented-out alternatives, indented parameter lines, a bare scalar
+# ("float scale" 1.5), bracketed values padded with spaces, an Integrator this renderer does not have (the test swaps that line), a spot light given
+# as a blackbody, and two binary PLY meshes beside it (written by the test: _vase_mesh and a two-triangle slab).
+_EXPORTED_SCENE = """\
+
+#LookAt 3 5 -6   0 1 0   0 1 0
+LookAt 4 6 -7   0.5 1.5 0   0 1 0
+
+Camera "perspective" "float fov" [35]
+
+Film "image"
+    "integer xresolution" [640] "integer yresolution" [900]
+    "float scale" 1.5
+    "string filename" "vase.exr"
+
+Integrator "sppm" "integer numiterations" [64] "float radius" .05
+#Integrator "bdpt" "integer maxdepth" 8
+
+WorldBegin
+
+LightSource "spot" "point from" [1 6 7]
+  "point to" [0 1.5 0] "blackbody I" [4800 60]
+
+AttributeBegin
+LightSource "infinite" "color L" [.08 .08 .1]
+AttributeEnd
+
+AttributeBegin
+    Material "glass"
+            "float index" [ 1.4500000000 ]
+    Shape "plymesh" "string filename" "geometry/vase.ply"
+AttributeEnd
+
+AttributeBegin
+    Material "uber"
+            "float roughness" [ 0.0250000000 ]
+            "float index" [ 1 ]
+            "rgb Kd" [ 0.5500000000 0.5000000000 0.4500000000 ]
+            "rgb Ks" [ 0.1000000000 0.1000000000 0.1000000000 ]
+            "rgb Kt" [ 0 0 0 ]
+            "rgb opacity" [ 1 1 1 ]
+    Shape "plymesh" "string filename" "geometry/slab.ply"
+AttributeEnd
+
+WorldEnd
+"""
+
+
+def _vase_mesh(nu=210, nv=211, h=3.0):
+    """A surface of revolution, radius 0.6 + 0.25 sin(2.5 pi t) at height h t, with its analytic normals: nu x nv vertices, 2 (nu - 1)(nv - 1) = 87 780 triangles."""
+    t, phi = np.linspace(0.0, 1.0, nv)[:, None], np.linspace(0.0, 2.0 * np.pi, nu)[None, :]
+    r, dr = 0.6 + 0.25 * np.sin(2.5 * np.pi * t), 0.625 * np.pi * np.cos(2.5 * np.pi * t)
+    P = np.stack(np.broadcast_arrays(r * np.cos(phi), h * t, r * np.sin(phi)), -1).reshape(-1, 3)
+    N = np.stack(np.broadcast_arrays(h * np.cos(phi), -dr, h * np.sin(phi)), -1).reshape(-1, 3)
+    N /= np.linalg.norm(N, axis=1, keepdims=True)
+    i = (np.arange(nv - 1)[:, None] * nu + np.arange(nu - 1)[None, :]).reshape(-1, 1)
+    tris = np.concatenate([np.hstack([i, i + nu, i + 1]), np.hstack([i + 1, i + nu, i + nu + 1])])
+    return P.astype(np.float32), N.astype(np.float32), tris
 
 
 def _read_ply_numpy(path):
@@ -711,33 +770,34 @@ def _read_ply_numpy(path):
     return P, np.array(tris, np.uint32), N, UV
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(_REF_SCENES, "caustic-glass.pbrt")), reason="the reference's shipped scenes exist in the build container only")
-def test_reference_authored_scene_loads_like_the_mirror(pkg, oracle, tmp_path):
-    """src/scenes/caustic-glass.pbrt (a scene the reference ships; its spot light is given as `"blackbody I" [5500 125]`) read in place
-    by libmi355front.so -- only its Integrator line is swapped for "path" (the file names sppm) and a sampler line added, in memory -- and
-    assembled independently through the Python mirror of api.rs with a numpy PLY reader: the flattened arrays must agree, and the
-    oracle renders both to the same image. Nothing of the file is copied into the repository; the test is skipped where the
-    reference is absent (the GPU box)."""
-    text = open(os.path.join(_REF_SCENES, "caustic-glass.pbrt")).read()
+def test_exported_scene_with_ply_meshes_loads_like_the_mirror(pkg, oracle, tmp_path):
+    """_EXPORTED_SCENE (its spot light is given as `"blackbody I" [4800 60]`) and its two binary PLY meshes read by libmi355front.so --
+    only its Integrator line is swapped for "path" (the file names sppm) and a sampler line added, in memory -- and assembled independently
+    through the Python mirror of api.rs with a numpy PLY reader: the flattened arrays must agree, and the oracle renders both to the same image."""
+    (tmp_path / "geometry").mkdir()
+    P, N, I = _vase_mesh()
+    _write_ply(tmp_path / "geometry" / "vase.ply", P.tolist(), N.tolist(), None, I.tolist(), binary=True)
+    _write_ply(tmp_path / "geometry" / "slab.ply", [(-4.0, 0.0, -4.0), (4.0, 0.0, -4.0), (4.0, 0.0, 4.0), (-4.0, 0.0, 4.0)], [(0.0, 1.0, 0.0)] * 4, None,
+               [(0, 1, 2), (0, 2, 3)], binary=True)
     lines = []
-    for l in text.split("\n"):
+    for l in _EXPORTED_SCENE.split("\n"):
         if l.startswith("Integrator"): lines.append('Integrator "path" "integer maxdepth" [5]\nSampler "sobol" "integer pixelsamples" [1]'); continue
         if l.startswith('    "integer xresolution"'): l = '    "integer xresolution" [70] "integer yresolution" [100]'
         lines.append(l)
-    fs = pkg.frontend.FrontScene(text="\n".join(lines), base_dir=_REF_SCENES)
+    fs = pkg.frontend.FrontScene(text="\n".join(lines), base_dir=str(tmp_path))
     d, rp = fs.desc(), fs.render_params()
     H = pkg.host
     b = H.SceneBuilder()
     b.film.update(xres=70, yres=100, scale=1.5); b.spp = 1
     b.integ.update(maxdepth=5)
-    b.look_at((-5.5, 7.0, -5.5), (-4.75, 2.25, 0.0), (0.0, 1.0, 0.0)); b.camera(fov=30.0)
+    b.look_at((4.0, 6.0, -7.0), (0.5, 1.5, 0.0), (0.0, 1.0, 0.0)); b.camera(fov=35.0)
     b.world_begin()
-    b.light_source("spot", from_=(0.0, 5.0, 9.0), to=(-5.0, 2.75, 0.0), I=tuple(float(x) for x in H.rgb_from_blackbody(5500, 125)))
-    b.attribute_begin(); b.light_source("infinite", L=(0.1, 0.1, 0.1)); b.attribute_end()
-    for fn, (kind, kw) in (("geometry/mesh_00001.ply", ("glass", dict(eta=1.25))),
-                           ("geometry/mesh_00002.ply", ("uber", dict(roughness=0.0104080001, eta=1.0, Kd=(0.6399999857,) * 3, Ks=(0.1000000015,) * 3, Kt=(0.0, 0.0, 0.0), opacity=(1.0, 1.0, 1.0))))):
+    b.light_source("spot", from_=(1.0, 6.0, 7.0), to=(0.0, 1.5, 0.0), I=tuple(float(x) for x in H.rgb_from_blackbody(4800, 60)))
+    b.attribute_begin(); b.light_source("infinite", L=(0.08, 0.08, 0.1)); b.attribute_end()
+    for fn, (kind, kw) in (("geometry/vase.ply", ("glass", dict(eta=1.45))),
+                           ("geometry/slab.ply", ("uber", dict(roughness=0.025, eta=1.0, Kd=(0.55, 0.5, 0.45), Ks=(0.1,) * 3, Kt=(0.0, 0.0, 0.0), opacity=(1.0, 1.0, 1.0))))):
         b.attribute_begin(); b.material(kind, **kw)
-        P, I, N, UV = _read_ply_numpy(os.path.join(_REF_SCENES, fn))
+        P, I, N, UV = _read_ply_numpy(str(tmp_path / fn))
         b.trianglemesh(P, I, N=N, UV=UV); b.attribute_end()
     sd, rp2 = b.world_end()
     d2 = sd.desc()
