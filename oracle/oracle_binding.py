@@ -35,6 +35,8 @@ class Oracle:
         lib.orc_render.argtypes = [C.c_void_p, C.POINTER(A.PtRenderParams), A.fp, C.c_int]
         lib.orc_film_resolve.argtypes = [A.fp, C.c_uint32, C.c_float, A.fp]
         lib.orc_last_render_seconds.restype = C.c_double; lib.orc_last_render_seconds.argtypes = [C.c_void_p]
+        lib.orc_tmax_raises.restype = C.c_uint64; lib.orc_tmax_raises.argtypes = []      # triangle hits that raised t_max (ref_scene.h g_tmax_raises)
+        lib.orc_reset_tmax_raises.restype = None; lib.orc_reset_tmax_raises.argtypes = []
         lib.orc_load_tables.argtypes = [C.c_char_p]
         f = C.c_float
         lib.orc_sobol_sample_float.restype = f; lib.orc_sobol_sample_float.argtypes = [C.c_uint64, C.c_int, C.c_uint32]

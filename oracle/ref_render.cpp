@@ -1137,6 +1137,8 @@ int orc_render(orc_scene *h, const PtRenderParams *rp, float *film_xyzw, int nth
     return overflow ? PT_ERR_SOBOL_DIMENSIONS : PT_OK;
 }
 double orc_last_render_seconds(const orc_scene *h) { return h->last_render_seconds; }
+uint64_t orc_tmax_raises() { return g_tmax_raises.load(); }   // see g_tmax_raises (ref_scene.h)
+void orc_reset_tmax_raises() { g_tmax_raises.store(0); }
 
 int orc_get_counters(const orc_scene *h, PtCounters *o) {
     std::memset(o, 0, sizeof *o);

@@ -4,6 +4,7 @@
 //   shapes/triangle.rs:101-584; core/primitive.rs:126-153; core/scene.rs:54-66;
 //   core/interaction.rs:186-249; core/shape.rs:40-82.
 #pragma once
+#include <atomic>
 #include <memory>
 #include "ref_math.h"
 #include "../include/mi355pt.h"
@@ -327,6 +328,11 @@ inline Bounds3 Scene::prim_world_bound(uint32_t prim) const {
     return sphere_world_bound(s & 0x3fffffffu);
 }
 
+// Accepted triangle hits whose t lies ABOVE the t_max they were tested against (the test is `tscaled < t_max * det` in scaled space, triangle.rs:202-206,
+// then t = tscaled * (1 / det) is rounded, :208-213): each one raises the ray's t_max at `r.t_max = thit`. Test infrastructure: counts over every
+// thread of the process until orc_reset_tmax_raises(); the vertex-aimed render tests assert that their scenes produce such hits.
+inline std::atomic<uint64_t> g_tmax_raises{0};
+
 // GeometricPrimitive::intersect (primitive.rs:126-149)
 inline bool Scene::prim_intersect(uint32_t prim, Ray &r, SurfaceInteraction &si, Counters &c) const {
     uint32_t s = prim_shape[prim], k = s >> 30, i = s & 0x3fffffffu;
@@ -335,6 +341,7 @@ inline bool Scene::prim_intersect(uint32_t prim, Ray &r, SurfaceInteraction &si,
         Float t, b[3];
         if (!tri_intersect(i, r, t, b)) return false;
         if (tri_has_alpha(i) && tri_alpha_rejects(i, b, false)) return false;   // triangle.rs:275-285 (test_alpha_texture = true)
+        if (t > r.t_max) g_tmax_raises.fetch_add(1, std::memory_order_relaxed);
         r.t_max = t;
         si.prim = prim; si.inst = PT_NONE; si.t = t; si.b[0] = b[0]; si.b[1] = b[1]; si.b[2] = b[2];
         return true;
