@@ -9,6 +9,7 @@
 #define MI355FRONT_H
 #include <stddef.h>
 #include "mi355pt.h"
+#include "mi355ao.h"
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -21,6 +22,9 @@ const char *ptf_last_error(void);
 const PtSceneDesc *ptf_scene_desc(const ptf_scene *scene);
 const PtRenderParams *ptf_render_params(const ptf_scene *scene);
 const char *ptf_output_filename(const ptf_scene *scene);   /* Film "string filename" */
+/* The "ambientocclusion" parameters (nsamples, cossample; defaults 64, true) of a scene whose ptf_render_params reports
+ * integrator == PT_INTEGRATOR_AO: render it with pt_ao_render (include/mi355ao.h). PT_OK or PT_ERR_INVALID_ARG. */
+int ptf_ao_params(const ptf_scene *scene, PtAOParams *out);
 void ptf_scene_destroy(ptf_scene *scene);
 /* Film::write_image's PFM branch (core/imageio.rs:288-328): rgb = width*height*3 floats, top row first. */
 int ptf_write_pfm(const char *path, int width, int height, const float *rgb);

@@ -188,7 +188,7 @@ def bind(lib, table=ENTRY_POINTS, prefix_from="pt_", prefix_to="pt_", strict=Tru
         fn = getattr(lib, name.replace(prefix_from, prefix_to, 1), None)
         if fn is None:
             if strict:
-                raise AttributeError(f"{name}: symbol declared in include/mi355pt.h is missing from the library")
+                raise AttributeError(f"{name}: symbol declared in " + ("include/mi355pt.h" if table is ENTRY_POINTS else "its C header") + " is missing from the library")
             continue
         fn.restype = res
         fn.argtypes = args

@@ -3,6 +3,7 @@ import ctypes as C
 import os
 import subprocess
 from . import _abi as A
+from . import _abi_ao as AO
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SAN = bool(os.environ.get("PT_SAN"))   # ASan/UBSan build of the front end (tools/san_cpu_tests.sh)
@@ -34,6 +35,7 @@ def lib():
         L.ptf_scene_desc.restype = C.POINTER(A.PtSceneDesc); L.ptf_scene_desc.argtypes = [C.c_void_p]
         L.ptf_render_params.restype = C.POINTER(A.PtRenderParams); L.ptf_render_params.argtypes = [C.c_void_p]
         L.ptf_output_filename.restype = C.c_char_p; L.ptf_output_filename.argtypes = [C.c_void_p]
+        L.ptf_ao_params.argtypes = [C.c_void_p, C.POINTER(AO.PtAOParams)]
         L.ptf_scene_destroy.argtypes = [C.c_void_p]
         L.ptf_write_pfm.argtypes = [C.c_char_p, C.c_int, C.c_int, A.fp]
         L.ptf_write_image.argtypes = [C.c_char_p, C.c_int, C.c_int, A.fp]
@@ -64,6 +66,12 @@ class FrontScene:
         rp = A.PtRenderParams()
         C.memmove(C.byref(rp), lib().ptf_render_params(self.h), C.sizeof(A.PtRenderParams))
         return rp
+
+    def ao_params(self):
+        """PtAOParams of an `Integrator "ambientocclusion"` scene (render_params().integrator == PT_INTEGRATOR_AO)."""
+        ao = AO.PtAOParams()
+        if lib().ptf_ao_params(self.h, C.byref(ao)) != A.PT_OK: raise ValueError(lib().ptf_last_error().decode(errors="replace"))
+        return ao
 
     def output_filename(self):
         return lib().ptf_output_filename(self.h).decode()

@@ -7,10 +7,11 @@
 //   :1630-1713 (ObjectBegin/End/Instance), :1715-1748 (WorldEnd), core/paramset.rs:500-600 (texture-or-constant lookups),
 //   cameras/perspective.rs:40-86,298-356, core/film.rs:55-112,364-398, filters/*.rs, lights/*.rs create_* functions,
 //   materials/*.rs create_* functions, shapes/{triangle.rs:700-760, sphere.rs:424-431, plymesh.rs}.
-// Out of scope here (an error names the directive): other cameras / samplers / integrators than perspective / sobol, halton / path,
+// Out of scope here (an error names the directive): other cameras / samplers / integrators than perspective / sobol, halton / path, volpath, ambientocclusion,
 // participating media, spectral (non-RGB) parameters, image formats other than PFM, per-shape material parameter
 // overrides, animated transforms (ActiveTransform / TransformTimes are accepted and ignored for static scenes).
 #include "../../include/mi355pt.h"
+#include "../../include/mi355ao.h"
 #include "fe_bssrdf.h"
 #include "fe_image.h"
 #include "fe_imageio.h"
@@ -44,6 +45,7 @@ struct Scene {
     std::vector<PtSphere> spheres;
     std::vector<uint32_t> prim_shape, prim_material, prim_light, prim_med_in, prim_med_out;
     std::vector<PtMedium> media; std::map<std::string, int> named_media; int camera_medium = -1; bool volpath = false;
+    bool ao = false; PtAOParams ao_params{64u, 1u};   // Integrator "ambientocclusion" (include/mi355ao.h)
     std::vector<std::vector<float>> media_density; std::vector<int> media_density_of;   // grid media: density arrays and the medium each belongs to
     std::vector<PtMaterial> materials; std::vector<PtLight> lights;
     std::vector<PtTexture> textures; std::vector<Pyramid> pyramids; std::vector<PtImage> images; std::vector<float> ewa_lut;
@@ -207,9 +209,17 @@ private:
         sc.film_scale = p.one_float("scale", 1.0f); sc.max_lum = p.one_float("maxsampleluminance", INFINITY);
         sc.filename = p.one_string("filename", "pbrt.exr");
     }
-    void integrator(const Token &d, const std::string &name, const ParamSet &p) {   // path.rs:225-253, volpath.rs:188-227 (same parameters)
-        if (name != "path" && name != "volpath") fail(d, "integrator \"" + name + "\": only \"path\" and \"volpath\" run on this back end");
+    void integrator(const Token &d, const std::string &name, const ParamSet &p) {   // path.rs:225-253, volpath.rs:188-227 (same parameters), ao.rs:113-141
+        if (name != "path" && name != "volpath" && name != "ambientocclusion") fail(d, "integrator \"" + name + "\": only \"path\", \"volpath\" and \"ambientocclusion\" run on this back end");
         sc.volpath = name == "volpath";
+        sc.ao = name == "ambientocclusion";
+        if (sc.ao) {   // create_ao_integrator reads these three only (pixelbounds as path.rs does)
+            const int ns = p.one_int("nsamples", 64);
+            if (ns <= 0) fail(d, "integrator \"ambientocclusion\": \"nsamples\" must be > 0");
+            sc.ao_params.nsamples = (uint32_t)ns; sc.ao_params.cos_sample = p.one_bool("cossample", true) ? 1u : 0u;
+            if (const std::vector<float> *pb = p.floats("int", "pixelbounds")) if (pb->size() == 4) { sc.has_pixel_bounds = true; for (int i = 0; i < 4; ++i) sc.pixel_bounds[i] = (int)(*pb)[i]; }
+            return;
+        }
         sc.maxdepth = p.one_int("maxdepth", 5); sc.rr_threshold = p.one_float("rrthreshold", 1.0f);
         sc.strategy = p.one_string("lightsamplestrategy", "spatial");
         if (const std::vector<float> *pb = p.floats("int", "pixelbounds")) if (pb->size() == 4) { sc.has_pixel_bounds = true; for (int i = 0; i < 4; ++i) sc.pixel_bounds[i] = (int)(*pb)[i]; }
@@ -609,7 +619,7 @@ static void finish(Scene &sc, const Api &api) {
     r2c.flat(rp.raster_to_camera); sc.camera_to_world.flat(rp.camera_to_world);
     rp.lens_radius = cp.one_float("lensradius", 0.0f); rp.focal_distance = cp.one_float("focaldistance", 1.0e30f); rp.shutter_open = so; rp.shutter_close = scl;
     rp.max_depth = (uint32_t)sc.maxdepth; rp.rr_threshold = sc.rr_threshold;
-    rp.integrator = sc.volpath ? PT_INTEGRATOR_VOLPATH : PT_INTEGRATOR_PATH; rp.camera_medium = sc.camera_medium < 0 ? PT_NONE : (uint32_t)sc.camera_medium;
+    rp.integrator = sc.ao ? PT_INTEGRATOR_AO : sc.volpath ? PT_INTEGRATOR_VOLPATH : PT_INTEGRATOR_PATH; rp.camera_medium = sc.camera_medium < 0 ? PT_NONE : (uint32_t)sc.camera_medium;
     if (!sc.has_pixel_bounds) for (int i = 0; i < 4; ++i) rp.pixel_bounds[i] = sb[i];
     else { const int *pb = sc.pixel_bounds; rp.pixel_bounds[0] = std::max(pb[0], sb[0]); rp.pixel_bounds[1] = std::max(pb[2], sb[1]); rp.pixel_bounds[2] = std::min(pb[1], sb[2]); rp.pixel_bounds[3] = std::min(pb[3], sb[3]); }   // path.rs:233-246
     rp.light_strategy = sc.strategy == "uniform" ? PT_LS_UNIFORM : sc.strategy == "power" ? PT_LS_POWER : PT_LS_SPATIAL;
@@ -653,6 +663,11 @@ int ptf_parse_string(const char *text, const char *base_dir, ptf_scene **out) {
 const char *ptf_last_error(void) { return fe::g_error.c_str(); }
 const PtSceneDesc *ptf_scene_desc(const ptf_scene *s) { return s ? &s->sc.desc : nullptr; }
 const PtRenderParams *ptf_render_params(const ptf_scene *s) { return s ? &s->sc.rp : nullptr; }
+int ptf_ao_params(const ptf_scene *s, PtAOParams *out) {
+    if (!s || !out) { fe::g_error = "null argument"; return PT_ERR_INVALID_ARG; }
+    *out = s->sc.ao_params;
+    return PT_OK;
+}
 const char *ptf_output_filename(const ptf_scene *s) { return s ? s->sc.filename.c_str() : ""; }
 void ptf_scene_destroy(ptf_scene *s) { delete s; }
 // rgb: width * height * 3 floats, top row first (the layout pt_film_resolve produces)

@@ -1,6 +1,6 @@
 // mi355pbrt -- command-line renderer: the drop-in for `pbrt-rust scene.pbrt` on this back end (main.rs + api.rs:1715-1748).
 //   mi355pbrt scene.pbrt [--outfile out.pfm] [--device N] [--spp N] [--quiet]
-// Parses with libmi355front.so, renders with libmi355pt.so (HIP), writes the film in the format the Film's "filename"
+// Parses with libmi355front.so, renders with libmi355pt.so (HIP; Integrator "ambientocclusion": libmi355ao.so), writes the film in the format the Film's "filename"
 // extension names (exr -- the reference's default "pbrt.exr" -- png, tga, pfm: core/imageio.rs:42-60).
 #include "../../include/mi355front.h"
 #include <chrono>
@@ -35,7 +35,10 @@ int main(int argc, char **argv) {
     const auto t1 = std::chrono::steady_clock::now();
     const int w = rp.cropped_pixel_bounds[2] - rp.cropped_pixel_bounds[0], h = rp.cropped_pixel_bounds[3] - rp.cropped_pixel_bounds[1];
     std::vector<float> film((size_t)w * h * 4, 0.0f), rgb((size_t)w * h * 3);
-    if (pt_render(sc, &rp, film.data(), 0) != PT_OK) { std::fprintf(stderr, "mi355pbrt: %s\n", pt_last_error()); return 1; }
+    int rst;
+    if (rp.integrator == PT_INTEGRATOR_AO) { PtAOParams ao; ptf_ao_params(fs, &ao); rst = pt_ao_render(sc, &rp, &ao, film.data(), 0); }   // Integrator "ambientocclusion" (libmi355ao.so)
+    else rst = pt_render(sc, &rp, film.data(), 0);
+    if (rst != PT_OK) { std::fprintf(stderr, "mi355pbrt: %s\n", pt_last_error()); return 1; }
     const auto t2 = std::chrono::steady_clock::now();
     pt_film_resolve(film.data(), (uint32_t)(w * h), rp.scale, rgb.data());
     if (ptf_write_image(outfile.c_str(), w, h, rgb.data()) != PT_OK) { std::fprintf(stderr, "mi355pbrt: %s\n", ptf_last_error()); return 1; }

@@ -11,6 +11,7 @@ import math
 import sys
 import numpy as np
 from . import _abi as A
+from . import _abi_ao as AO
 
 F = np.float32
 
@@ -198,7 +199,7 @@ class SceneBuilder:
         self.spp = 16
         self.sampler = "sobol"          # "sobol" | "halton" (Sampler directive; the reference's default is halton, api.rs:215-241)
         self.sample_at_pixel_center = False
-        self.integ = dict(maxdepth=5, rrthreshold=1.0, strategy="spatial", pixelbounds=None, kind="path")   # kind: "path" | "volpath"
+        self.integ = dict(maxdepth=5, rrthreshold=1.0, strategy="spatial", pixelbounds=None, kind="path")   # kind: "path" | "volpath" | "ao" (+ nsamples, cossample: ao.rs:113-141)
         # participating media (api.rs:706-722,1219-1253): named homogeneous media, the current MediumInterface, the camera's medium
         self.media = []; self.named_media = {}; self.medium_inside = ""; self.medium_outside = ""; self.camera_medium = None; self._undefined_media = set()
         self._keep = []
@@ -627,7 +628,7 @@ class SceneBuilder:
         rp.lens_radius = self.cam["lensradius"]; rp.focal_distance = self.cam["focaldistance"]
         rp.shutter_open = self.cam["shutteropen"]; rp.shutter_close = self.cam["shutterclose"]
         rp.max_depth = self.integ["maxdepth"]; rp.rr_threshold = self.integ["rrthreshold"]
-        rp.integrator = {"path": A.PT_INTEGRATOR_PATH, "volpath": A.PT_INTEGRATOR_VOLPATH}[self.integ.get("kind", "path")]
+        rp.integrator = {"path": A.PT_INTEGRATOR_PATH, "volpath": A.PT_INTEGRATOR_VOLPATH, "ao": AO.PT_INTEGRATOR_AO}[self.integ.get("kind", "path")]
         rp.camera_medium = A.PT_NONE if self.camera_medium is None else self.camera_medium
         pb = self.integ["pixelbounds"]
         if pb is None: pb = sb
@@ -723,6 +724,7 @@ class SceneData:
         self.env = b.env
         self.media = (A.PtMedium * max(1, len(b.media)))(*b.media); self.n_media = len(b.media); self._keep = b._keep   # (grid media point into numpy arrays)
         self.prim_med_in = c1(b.prim_med_in) if b.media else None; self.prim_med_out = c1(b.prim_med_out) if b.media else None
+        self.integ = dict(b.integ)
         self.max_node_prims = b.max_node_prims
         self.split_method = {"sah": A.PT_SPLIT_SAH, "hlbvh": A.PT_SPLIT_HLBVH}[b.split_method]
         self.nodes = None; self.ordered = None
@@ -759,6 +761,10 @@ class SceneData:
     def set_bvh(self, nodes, ordered):
         """Adopt a prebuilt accelerator (what a Rust host would pass: BVHAccel.nodes / ordered prims)."""
         self.nodes, self.ordered = nodes, np.ascontiguousarray(ordered, dtype=np.uint32)
+
+    def ao_params(self):
+        """PtAOParams of integ["kind"] == "ao" (create_ao_integrator, ao.rs:113-141: nsamples 64, cossample true by default)."""
+        return AO.PtAOParams(int(self.integ.get("nsamples", 64)), 1 if self.integ.get("cossample", True) else 0)
 
     def desc(self):
         d = A.PtSceneDesc()

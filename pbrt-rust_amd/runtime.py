@@ -5,19 +5,22 @@ import os
 import subprocess
 import numpy as np
 from . import _abi as A
+from . import _abi_ao as AO
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PT_LIB_PATH") or os.path.join(_HERE, "csrc", "libmi355pt.so")   # PT_LIB_PATH: kernel-variant experiments
+AO_LIB_PATH = os.path.join(_HERE, "ao", "libmi355ao.so")   # the ambient-occlusion integrator (include/mi355ao.h), linked against libmi355pt.so
 TABLES_PATH = os.path.join(_HERE, "data", "sobol_tables.bin")
 
 
 def build_library(verbose=False):
-    """Compile every HIP source for gfx950 (hipcc cross-compiles without a GPU)."""
-    r = subprocess.run(["make", "-C", os.path.join(_HERE, "csrc"), "-j8"], capture_output=True, text=True)
-    if verbose or r.returncode != 0:
-        print(r.stdout[-4000:]); print(r.stderr[-4000:])
-    if r.returncode != 0:
-        raise RuntimeError("building libmi355pt.so failed")
+    """Compile every HIP source for gfx950 (hipcc cross-compiles without a GPU): libmi355pt.so, then libmi355ao.so, which links against it."""
+    for sub, name in (("csrc", "libmi355pt.so"), ("ao", "libmi355ao.so")):
+        r = subprocess.run(["make", "-C", os.path.join(_HERE, sub), "-j8"], capture_output=True, text=True)
+        if verbose or r.returncode != 0:
+            print(r.stdout[-4000:]); print(r.stderr[-4000:])
+        if r.returncode != 0:
+            raise RuntimeError(f"building {name} failed")
     return LIB_PATH
 
 
@@ -30,6 +33,16 @@ class Library:
         if not os.path.exists(path):
             raise PtError(f"{path} not found: build it with __graft_entry__.build() (no CPU fallback exists)")
         self.lib = A.bind(C.CDLL(path), strict=not os.environ.get("PT_LIB_PATH"))   # (PT_LIB_PATH: a kernel-variant library of an A/B run, possibly built from an older tree)
+        self._ao = None
+
+    @property
+    def ao(self):
+        """libmi355ao.so (include/mi355ao.h), loaded on first use."""
+        if self._ao is None:
+            if not os.path.exists(AO_LIB_PATH):
+                raise PtError(f"{AO_LIB_PATH} not found: build it with __graft_entry__.build() (no CPU fallback exists)")
+            self._ao = A.bind(C.CDLL(AO_LIB_PATH), table=AO.ENTRY_POINTS)
+        return self._ao
 
     def check(self, st, what=""):
         if st != A.PT_OK:
@@ -89,18 +102,33 @@ class Scene:
         self.L.check(self.L.lib.pt_pass_size(self.h, C.byref(rp), C.byref(s)), "pt_pass_size")
         return int(s.value)
 
-    def render(self, rp, film=None, device_ptr=None):
-        """Returns the un-normalised film (H, W, 4) = XYZ sums + weight sum."""
+    def render(self, rp, film=None, device_ptr=None, ao=None):
+        """Returns the un-normalised film (H, W, 4) = XYZ sums + weight sum. rp.integrator == PT_INTEGRATOR_AO renders with
+        pt_ao_render: `ao` (a PtAOParams), else the scene's own (scene_data.ao_params())."""
         cb = rp.cropped_pixel_bounds
         w, h = cb[2] - cb[0], cb[3] - cb[1]
+        if rp.integrator == AO.PT_INTEGRATOR_AO:
+            ao = self.ao_params() if ao is None else ao
+            call, what = (lambda ptr, dev: self.L.ao.pt_ao_render(self.h, C.byref(rp), C.byref(ao), ptr, dev)), "pt_ao_render"
+        else:
+            call, what = (lambda ptr, dev: self.L.lib.pt_render(self.h, C.byref(rp), ptr, dev)), "pt_render"
         if device_ptr is not None:
-            st = self.L.lib.pt_render(self.h, C.byref(rp), C.c_void_p(device_ptr), 1)
-            self.L.check(st, "pt_render"); return None
+            self.L.check(call(C.c_void_p(device_ptr), 1), what); return None
         if film is None:
             film = np.zeros((h, w, 4), dtype=np.float32)
-        st = self.L.lib.pt_render(self.h, C.byref(rp), film.ctypes.data_as(C.c_void_p), 0)
-        self.L.check(st, "pt_render")
+        self.L.check(call(film.ctypes.data_as(C.c_void_p), 0), what)
         return film
+
+    def ao_params(self):
+        """The scene's PtAOParams (SceneBuilder.integ / the front end's "ambientocclusion" parameters)."""
+        return self.data.ao_params()
+
+    def ao_pass_size(self, rp, ao=None):
+        """Samples per pixel per pass pt_ao_render would use for `rp` now."""
+        s = C.c_uint32()
+        ao = self.ao_params() if ao is None else ao
+        self.L.check(self.L.ao.pt_ao_pass_size(self.h, C.byref(rp), C.byref(ao), C.byref(s)), "pt_ao_pass_size")
+        return int(s.value)
 
     def resolve(self, film, scale=1.0):
         film = np.ascontiguousarray(film, dtype=np.float32)

@@ -1,0 +1,130 @@
+"""Host-side pieces of the ambient-occlusion integrator (include/mi355ao.h): the test-side reference on scenes with a known answer,
+the .pbrt front end's "ambientocclusion" parameters against the Python scene builder, and the C header against the ctypes mirror."""
+import math
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from ao_reference import AOReference
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _builder(pkg, nsamples=16, cossample=True, spp=2, res=8):
+    b = pkg.host.SceneBuilder()
+    b.film.update(xres=res, yres=res); b.spp = spp
+    b.integ.update(kind="ao", nsamples=nsamples, cossample=cossample)
+    return b
+
+
+def _all_pixels(rp):
+    pb = list(rp.pixel_bounds)
+    ys, xs = np.mgrid[pb[1]:pb[3], pb[0]:pb[2]]
+    return np.stack([xs.ravel(), ys.ravel()], 1).astype(np.int32)
+
+
+def test_reference_open_quad_gives_pi_per_hit_sample(pkg, oracle):
+    b = _builder(pkg)
+    b.look_at((0, 0, -1), (0, 0, 0), (0, 1, 0)); b.camera(fov=30.0)
+    b.world_begin()
+    b.trianglemesh([(-100, -100, 0), (100, -100, 0), (100, 100, 0), (-100, 100, 0)], [0, 1, 2, 0, 2, 3])
+    sd, rp = b.world_end()
+    ref = AOReference(oracle, pkg._abi, sd, rp, nsamples=16, cos_sample=True)
+    pix = _all_pixels(rp)
+    for s in range(rp.spp):
+        L, _ = ref.li(pix, s)
+        assert np.allclose(L, math.pi, rtol=1e-6, atol=0), (L.min(), L.max())
+    n = len(pix) * rp.spp
+    assert ref.counters["camera_rays"] == ref.counters["intersect_tests"] == n and ref.counters["shadow_tests"] == 16 * n
+
+
+@pytest.mark.parametrize("cossample", [True, False])
+def test_reference_inside_a_closed_box_gives_zero_or_only_escaping_back_rays(pkg, oracle, cossample):
+    b = _builder(pkg, nsamples=8, cossample=cossample)
+    b.look_at((0, 0, 0), (0, 0, 1), (0, 1, 0)); b.camera(fov=60.0)
+    b.world_begin()
+    P = [(x, y, z) for z in (-2, 2) for y in (-2, 2) for x in (-2, 2)]   # cube corners, index = 4z + 2y + x
+    faces = [(0, 1, 3, 2), (4, 6, 7, 5), (0, 4, 5, 1), (2, 3, 7, 6), (0, 2, 6, 4), (1, 5, 7, 3)]
+    b.trianglemesh(P, [i for a, c1, c2, d in faces for i in (a, c1, c2, a, c2, d)])
+    sd, rp = b.world_end()
+    ref = AOReference(oracle, pkg._abi, sd, rp, nsamples=8, cos_sample=cossample)
+    L, _ = ref.li(_all_pixels(rp), 0)
+    if cossample:
+        assert np.all(L == 0.0)
+    else:   # the rays of the outer hemisphere start behind the wall (offset_ray_origin along -n) and escape with dot(wi, n) < 0
+        assert np.all(L < 0.0)
+    assert ref.counters["shadow_tests"] == 8 * len(L)
+
+
+AO_SCENE = """LookAt 0 0 -1  0 0 0  0 1 0
+Camera "perspective" "float fov" 30
+Film "image" "integer xresolution" 24 "integer yresolution" 16
+Sampler "halton" "integer pixelsamples" 4
+Integrator "ambientocclusion" "integer nsamples" 16 "bool cossample" "false" "integer pixelbounds" [2 20 3 12]
+WorldBegin
+Shape "trianglemesh" "integer indices" [0 1 2 0 2 3] "point P" [-100 -100 0 100 -100 0 100 100 0 -100 100 0]
+WorldEnd
+"""
+
+
+def test_front_end_ambientocclusion_matches_the_python_builder(pkg):
+    A = pkg._abi
+    fs = pkg.frontend.FrontScene(text=AO_SCENE)
+    rp = fs.render_params(); ao = fs.ao_params()
+    assert rp.integrator == pkg._abi_ao.PT_INTEGRATOR_AO == 2
+    assert (ao.nsamples, ao.cos_sample) == (16, 0)
+    b = _builder(pkg, nsamples=16, cossample=False, spp=4)
+    b.film.update(xres=24, yres=16); b.sampler = "halton"; b.integ["pixelbounds"] = (2, 20, 3, 12)
+    b.look_at((0, 0, -1), (0, 0, 0), (0, 1, 0)); b.camera(fov=30.0)
+    b.world_begin()
+    b.trianglemesh([(-100, -100, 0), (100, -100, 0), (100, 100, 0), (-100, 100, 0)], [0, 1, 2, 0, 2, 3])
+    sd, rp2 = b.world_end()
+    ao2 = sd.ao_params()
+    assert (ao2.nsamples, ao2.cos_sample) == (ao.nsamples, ao.cos_sample)
+    for f in ("integrator", "spp", "sampler_type", "pixel_bounds", "sample_bounds", "cropped_pixel_bounds", "filter_radius"):
+        a, c = getattr(rp, f), getattr(rp2, f)
+        assert (list(a) if hasattr(a, "__len__") else a) == (list(c) if hasattr(c, "__len__") else c), f
+    assert list(rp.pixel_bounds) == [2, 3, 20, 12]
+    # defaults (ao.rs:138-139)
+    d = pkg.frontend.FrontScene(text=AO_SCENE.replace('"integer nsamples" 16 "bool cossample" "false" ', "")).ao_params()
+    assert (d.nsamples, d.cos_sample) == (64, 1)
+    b = pkg.host.SceneBuilder(); b.integ["kind"] = "ao"
+    d = b.world_end()[0].ao_params()
+    assert (d.nsamples, d.cos_sample) == (64, 1)
+
+
+def test_front_end_path_scenes_are_unchanged_and_others_refused(pkg):
+    A = pkg._abi
+    for name, want in (("path", A.PT_INTEGRATOR_PATH), ("volpath", A.PT_INTEGRATOR_VOLPATH)):
+        fs = pkg.frontend.FrontScene(text=AO_SCENE.replace('"ambientocclusion"', f'"{name}"'))
+        assert fs.render_params().integrator == want
+    for bad in ("bdpt", "whitted", "directlighting"):
+        with pytest.raises(ValueError, match='only "path"'):
+            pkg.frontend.FrontScene(text=f'Integrator "{bad}"\n')
+    with pytest.raises(ValueError, match="nsamples"):
+        pkg.frontend.FrontScene(text='Integrator "ambientocclusion" "integer nsamples" 0\n')
+
+
+def test_mi355ao_header_is_c99_and_matches_the_ctypes_mirror(pkg, tmp_path):
+    import ctypes as C
+    A = pkg._abi_ao
+    src = tmp_path / "probe.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "mi355ao.h"\n'
+                   'int main(void) { printf("%d %d %d %d\\n", (int)sizeof(PtAOParams), (int)offsetof(PtAOParams, nsamples), '
+                   '(int)offsetof(PtAOParams, cos_sample), PT_INTEGRATOR_AO); return 0; }\n')
+    exe = tmp_path / "probe"
+    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    out = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()
+    assert [int(v) for v in out] == [C.sizeof(A.PtAOParams), A.PtAOParams.nsamples.offset, A.PtAOParams.cos_sample.offset, A.PT_INTEGRATOR_AO]
+
+
+def test_ao_library_exports_only_its_entry_points(pkg):
+    path = pkg.runtime.AO_LIB_PATH
+    if not os.path.exists(path):
+        pytest.fail(f"{path} missing: __graft_entry__.build() builds it")
+    r = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True)
+    names = {line.split()[-1] for line in r.stdout.splitlines() if line.strip()}
+    assert names == set(pkg._abi_ao.ENTRY_POINTS)
