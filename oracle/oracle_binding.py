@@ -1,6 +1,7 @@
 """ctypes binding of the CPU oracle (TEST INFRASTRUCTURE: imported only by tests/,
 __graft_entry__.smoke() and bench.py's cpu_baseline leg)."""
 import ctypes as C
+import importlib
 import os
 import subprocess
 import numpy as np
@@ -24,6 +25,7 @@ class Oracle:
         if not os.path.exists(LIB_PATH):
             build()
         self.A = abi
+        self.AO = importlib.import_module("._abi_ao", abi.__package__)   # the ctypes mirror of include/mi355ao.h beside `abi`
         A = abi
         lib = C.CDLL(LIB_PATH)
         table = {k.replace("pt_", "orc_", 1): v for k, v in A.ENTRY_POINTS.items()
@@ -33,6 +35,8 @@ class Oracle:
             fn = getattr(lib, name); fn.restype = res; fn.argtypes = args
         lib.orc_render.restype = C.c_int
         lib.orc_render.argtypes = [C.c_void_p, C.POINTER(A.PtRenderParams), A.fp, C.c_int]
+        lib.orc_ao_render.restype = C.c_int
+        lib.orc_ao_render.argtypes = [C.c_void_p, C.POINTER(A.PtRenderParams), C.POINTER(self.AO.PtAOParams), A.fp, C.c_int]
         lib.orc_film_resolve.argtypes = [A.fp, C.c_uint32, C.c_float, A.fp]
         lib.orc_last_render_seconds.restype = C.c_double; lib.orc_last_render_seconds.argtypes = [C.c_void_p]
         lib.orc_tmax_raises.restype = C.c_uint64; lib.orc_tmax_raises.argtypes = []      # triangle hits that raised t_max (ref_scene.h g_tmax_raises)
@@ -97,11 +101,17 @@ class OracleScene:
         self.O.lib.orc_scene_bvh_read(self.h, nodes, ordered.ctypes.data_as(A.u32p))
         return nodes, ordered
 
-    def render(self, rp, nthreads=1):
+    def render(self, rp, nthreads=1, ao=None):
+        """The un-normalised film (H, W, 4), as runtime.Scene.render: rp.integrator == PT_INTEGRATOR_AO renders with orc_ao_render
+        and `ao` (a PtAOParams), else the scene's own (scene_data.ao_params())."""
         cb = rp.cropped_pixel_bounds
         w, h = cb[2] - cb[0], cb[3] - cb[1]
         film = np.zeros((h, w, 4), dtype=np.float32)
-        st = self.O.lib.orc_render(self.h, C.byref(rp), _fp(self.A, film), nthreads)
+        if rp.integrator == self.O.AO.PT_INTEGRATOR_AO:
+            ao = self.data.ao_params() if ao is None else ao
+            st = self.O.lib.orc_ao_render(self.h, C.byref(rp), C.byref(ao), _fp(self.A, film), nthreads)
+        else:
+            st = self.O.lib.orc_render(self.h, C.byref(rp), _fp(self.A, film), nthreads)
         assert st == 0, st
         return film
 

@@ -1,11 +1,12 @@
 // ORACLE -- TEST INFRASTRUCTURE ONLY (see ref_math.h header).
-// ref_render.cpp: materials -> BSDF, one-light MIS, PathIntegrator::li, perspective camera, film,
+// ref_render.cpp: materials -> BSDF, one-light MIS, PathIntegrator::li, AOIntegrator::li, perspective camera, film,
 // the tile render loop, and the oracle's C ABI (driven from tests/ and bench.py's cpu_baseline leg).
 //   materials/{matte,mirror,glass,plastic,metal,uber,substrate}.rs; core/integrator.rs:81-237,263-403;
-//   integrators/path.rs:79-222; cameras/perspective.rs:120-179; core/film.rs:104-161,217-258,292-331.
+//   integrators/path.rs:79-222; integrators/ao.rs:63-110; cameras/perspective.rs:120-179; core/film.rs:104-161,217-258,292-331.
 #include "ref_bssrdf.h"
 #include "ref_texture.h"
 #include "ref_hlbvh.h"
+#include "../include/mi355ao.h"
 #include <thread>
 #include <atomic>
 #include <chrono>
@@ -499,6 +500,25 @@ static RGB path_li(const RenderCtx &ctx, const PathParams &pp, Ray ray, SobolSam
     return L;
 }
 
+// ---- AOIntegrator::li (integrators/ao.rs:63-110) ----------------------------------------------------
+// compute_scattering_functions (ao.rs:79) changes only the BSDF and the shading geometry, which AO does not read.
+static RGB ao_li(const RenderCtx &ctx, const PtAOParams &ao, Ray ray, SobolSampler &sampler) {
+    RGB L(0.0f);
+    SurfaceInteraction isect;
+    if (!ctx.scene->intersect(ray, isect, *ctx.c)) return L;
+    // the frame of the true geometry, not the shading geometry
+    V3 n = face_forward(isect.n, -ray.d), s = normalize(isect.dpdu), t = cross(isect.n, s);
+    IData it; it.p = isect.p; it.p_error = isect.p_error; it.n = isect.n;
+    for (uint32_t k = 0; k < ao.nsamples; ++k) {
+        V3 wi; Float pdf;
+        if (ao.cos_sample) { wi = cosine_sample_hemisphere(sampler.get_2d_array(k)); pdf = std::fabs(wi.z) * INV_PI; }   // cosine_hemisphere_pdf
+        else { wi = uniform_sample_sphere(sampler.get_2d_array(k)); pdf = INV4_PI; }                                  // uniform_sphere_pdf
+        wi = V3(s.x * wi.x + t.x * wi.y + n.x * wi.z, s.y * wi.x + t.y * wi.y + n.y * wi.z, s.z * wi.x + t.z * wi.y + n.z * wi.z);
+        if (!ctx.scene->intersect_p(spawn_ray(it, wi), *ctx.c)) L += RGB(dot(wi, n) / (pdf * (Float)ao.nsamples));
+    }
+    return L;
+}
+
 
 // ---- VolPathIntegrator (integrators/volpath.rs:76-186) with HomogeneousMedium (media/homogeneous.rs) and the Henyey-Greenstein
 //      phase function (core/medium.rs:149-194). A primitive without a material is a medium-interface shell (api.rs:597): the path
@@ -937,7 +957,7 @@ struct FilmTile {
 };
 
 struct RenderJob {
-    const Scene *scene; LightSampler lights; PtRenderParams rp; Camera cam; FilmParams fp;
+    const Scene *scene; LightSampler lights; PtRenderParams rp; Camera cam; FilmParams fp; PtAOParams ao{};
 };
 
 static void render_tiles(const RenderJob &job, float *film_xyzw, int nthreads, Counters &total, std::atomic<bool> &dim_overflow) {
@@ -960,6 +980,7 @@ static void render_tiles(const RenderJob &job, float *film_xyzw, int nthreads, C
             int64_t tb[4] = {sb[0] + tx * 16, sb[1] + ty * 16, 0, 0};
             tb[2] = std::min<int64_t>(tb[0] + 16, sb[2]); tb[3] = std::min<int64_t>(tb[1] + 16, sb[3]);
             SobolSampler sampler(rp.spp, rp.sample_bounds, rp.sampler_type, rp.sample_at_pixel_center != 0);
+            if (rp.integrator == PT_INTEGRATOR_AO) sampler.request_2d_array(job.ao.nsamples);   // AOIntegrator::preprocess (ao.rs:63-65)
             FilmTile tile(job.fp, tb);
             for (int64_t y = tb[1]; y < tb[3]; ++y)
                 for (int64_t x = tb[0]; x < tb[2]; ++x) {
@@ -972,7 +993,8 @@ static void render_tiles(const RenderJob &job, float *film_xyzw, int nthreads, C
                         RayDiff rdiff;
                         if (job.scene->textures) rdiff = generate_ray_differentials(job.cam, cs, ray, rp.spp);
                         if (rp.integrator == PT_INTEGRATOR_VOLPATH) ray.medium = rp.camera_medium;   // perspective.rs:114
-                        RGB L = rp.integrator == PT_INTEGRATOR_VOLPATH ? volpath_li(ctx, pp, ray, sampler, rdiff) : path_li(ctx, pp, ray, sampler, rdiff);
+                        RGB L = rp.integrator == PT_INTEGRATOR_AO ? ao_li(ctx, job.ao, ray, sampler)
+                              : rp.integrator == PT_INTEGRATOR_VOLPATH ? volpath_li(ctx, pp, ray, sampler, rdiff) : path_li(ctx, pp, ray, sampler, rdiff);
                         if (L.has_nans()) { L = RGB(0.0f); c.san_nan++; }
                         else if (L.y() < -1.0e-5f) { L = RGB(0.0f); c.san_neg++; }
                         else if (std::isinf(L.y())) { L = RGB(0.0f); c.san_inf++; }
@@ -1118,9 +1140,13 @@ int orc_scene_bvh_read(const orc_scene *h, PtBVHNode *nodes, uint32_t *ordered) 
     return PT_OK;
 }
 
-int orc_render(orc_scene *h, const PtRenderParams *rp, float *film_xyzw, int nthreads) {
+// ao == null: pt_render, which renders PT_INTEGRATOR_AO as the path integrator (mi355ao.h); else pt_ao_render, which does not read
+// rp->integrator
+static int render(orc_scene *h, const PtRenderParams *rp, const PtAOParams *ao, float *film_xyzw, int nthreads) {
     RenderJob job;
     job.scene = &h->scene; job.rp = *rp;
+    if (ao) { job.ao = *ao; job.rp.integrator = PT_INTEGRATOR_AO; }
+    else if (rp->integrator == PT_INTEGRATOR_AO) job.rp.integrator = PT_INTEGRATOR_PATH;
     job.lights.init(h->scene, (int)rp->light_strategy);
     job.cam.raster_to_camera = m4_from(rp->raster_to_camera); job.cam.camera_to_world = m4_from(rp->camera_to_world);
     job.cam.lens_radius = rp->lens_radius; job.cam.focal_distance = rp->focal_distance;
@@ -1135,6 +1161,11 @@ int orc_render(orc_scene *h, const PtRenderParams *rp, float *film_xyzw, int nth
     render_tiles(job, film_xyzw, nthreads, h->counters, overflow);
     h->last_render_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return overflow ? PT_ERR_SOBOL_DIMENSIONS : PT_OK;
+}
+int orc_render(orc_scene *h, const PtRenderParams *rp, float *film_xyzw, int nthreads) { return render(h, rp, nullptr, film_xyzw, nthreads); }
+int orc_ao_render(orc_scene *h, const PtRenderParams *rp, const PtAOParams *ao, float *film_xyzw, int nthreads) {
+    if (!ao || ao->nsamples == 0) return PT_ERR_INVALID_ARG;
+    return render(h, rp, ao, film_xyzw, nthreads);
 }
 double orc_last_render_seconds(const orc_scene *h) { return h->last_render_seconds; }
 uint64_t orc_tmax_raises() { return g_tmax_raises.load(); }   // see g_tmax_raises (ref_scene.h)

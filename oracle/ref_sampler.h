@@ -161,7 +161,8 @@ struct SobolSampler {
     uint64_t cur_sample;
     int dimension;
     uint64_t interval_sample_index;
-    int array_end_dim;  // == ARRAY_START_DIM (5): the path integrator requests no arrays
+    int array_end_dim;  // ARRAY_START_DIM (5), 7 once a 2-D array is requested (sampler.rs:275-278)
+    uint64_t array_2d_n = 0;   // size of the one 2-D array the AO integrator requests; the path integrators request none
     bool dim_overflow;
     // HaltonSampler state (halton.rs:54-60); `halton` selects it: the GlobalSampler bookkeeping below is shared
     bool halton = false, at_center = false;
@@ -235,6 +236,15 @@ struct SobolSampler {
         interval_sample_index = get_index_for_sample(n);
         cur_sample = n;
         return cur_sample < spp;
+    }
+    void request_2d_array(uint64_t n) { array_2d_n = n; array_end_dim = 7; }   // sampler.rs:118-124
+    // element k of the current sample's 2-D array: GlobalSampler::start_pixel (sampler.rs:288-302) fills the pixel's whole table
+    // from sample numbers cur_sample * n + k, dimensions 5 and 6 (y first); here each element is computed when it is asked for
+    P2 get_2d_array(uint64_t k) {
+        uint64_t index = get_index_for_sample(cur_sample * array_2d_n + k);
+        Float y = sample_dimension(index, 6);
+        Float x = sample_dimension(index, 5);
+        return P2(x, y);
     }
     Float get_1d() {  // sampler.rs:322-333
         if (dimension >= 5 && dimension < array_end_dim) dimension = array_end_dim;

@@ -1,13 +1,13 @@
-"""Host-side pieces of the ambient-occlusion integrator (include/mi355ao.h): the test-side reference on scenes with a known answer,
-the .pbrt front end's "ambientocclusion" parameters against the Python scene builder, and the C header against the ctypes mirror."""
+"""Host-side pieces of the ambient-occlusion integrator (include/mi355ao.h): the CPU oracle's AO render loop on scenes with a known
+answer, the .pbrt front end's "ambientocclusion" parameters against the Python scene builder, and the C header against the ctypes
+mirror."""
+import ctypes as C
 import math
 import os
 import subprocess
 
 import numpy as np
 import pytest
-
-from ao_reference import AOReference
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -19,43 +19,57 @@ def _builder(pkg, nsamples=16, cossample=True, spp=2, res=8):
     return b
 
 
-def _all_pixels(rp):
-    pb = list(rp.pixel_bounds)
-    ys, xs = np.mgrid[pb[1]:pb[3], pb[0]:pb[2]]
-    return np.stack([xs.ravel(), ys.ravel()], 1).astype(np.int32)
+def _sample_values(oracle, b):
+    """Oracle AO render of builder `b` in which every pixel holds exactly one sample: one Halton sample per pixel at the pixel centre
+    and the box filter of radius 0.5. Returns each sample's y(L) (the film's Y, weight 1) and the render's counters."""
+    b.sampler = "halton"; b.sample_at_pixel_center = True
+    sd, rp = b.world_end()
+    assert rp.spp == 1 and list(rp.filter_radius) == [0.5, 0.5]
+    osc = oracle.scene(sd)
+    film = osc.render(rp)
+    c = osc.counters()
+    assert c["film_splats"] == c["camera_rays"] and np.all(film[..., 3] == 1.0)
+    return film[..., 1], c
 
 
 def test_reference_open_quad_gives_pi_per_hit_sample(pkg, oracle):
-    b = _builder(pkg)
+    b = _builder(pkg, spp=1, res=16)
     b.look_at((0, 0, -1), (0, 0, 0), (0, 1, 0)); b.camera(fov=30.0)
     b.world_begin()
     b.trianglemesh([(-100, -100, 0), (100, -100, 0), (100, 100, 0), (-100, 100, 0)], [0, 1, 2, 0, 2, 3])
-    sd, rp = b.world_end()
-    ref = AOReference(oracle, pkg._abi, sd, rp, nsamples=16, cos_sample=True)
-    pix = _all_pixels(rp)
-    for s in range(rp.spp):
-        L, _ = ref.li(pix, s)
-        assert np.allclose(L, math.pi, rtol=1e-6, atol=0), (L.min(), L.max())
-    n = len(pix) * rp.spp
-    assert ref.counters["camera_rays"] == ref.counters["intersect_tests"] == n and ref.counters["shadow_tests"] == 16 * n
+    L, c = _sample_values(oracle, b)
+    assert np.allclose(L, math.pi, rtol=1e-6, atol=0), (L.min(), L.max())
+    n = L.size
+    assert c["camera_rays"] == c["intersect_tests"] == n and c["shadow_tests"] == 16 * n
+    assert c["sanitized_nan"] == c["sanitized_negative"] == c["sanitized_infinite"] == 0
 
 
 @pytest.mark.parametrize("cossample", [True, False])
 def test_reference_inside_a_closed_box_gives_zero_or_only_escaping_back_rays(pkg, oracle, cossample):
-    b = _builder(pkg, nsamples=8, cossample=cossample)
+    b = _builder(pkg, nsamples=8, cossample=cossample, spp=1)
     b.look_at((0, 0, 0), (0, 0, 1), (0, 1, 0)); b.camera(fov=60.0)
     b.world_begin()
     P = [(x, y, z) for z in (-2, 2) for y in (-2, 2) for x in (-2, 2)]   # cube corners, index = 4z + 2y + x
     faces = [(0, 1, 3, 2), (4, 6, 7, 5), (0, 4, 5, 1), (2, 3, 7, 6), (0, 2, 6, 4), (1, 5, 7, 3)]
     b.trianglemesh(P, [i for a, c1, c2, d in faces for i in (a, c1, c2, a, c2, d)])
-    sd, rp = b.world_end()
-    ref = AOReference(oracle, pkg._abi, sd, rp, nsamples=8, cos_sample=cossample)
-    L, _ = ref.li(_all_pixels(rp), 0)
+    L, c = _sample_values(oracle, b)
     if cossample:
-        assert np.all(L == 0.0)
-    else:   # the rays of the outer hemisphere start behind the wall (offset_ray_origin along -n) and escape with dot(wi, n) < 0
-        assert np.all(L < 0.0)
-    assert ref.counters["shadow_tests"] == 8 * len(L)
+        assert np.all(L == 0.0) and c["sanitized_nan"] == c["sanitized_negative"] == c["sanitized_infinite"] == 0
+    else:   # the rays of the outer hemisphere start behind the wall (offset_ray_origin along -n) and escape with dot(wi, n) < 0:
+        # every sample's sum is negative, and the film's sanitiser zeroes it
+        assert c["sanitized_negative"] == L.size and np.all(L == 0.0)
+    assert c["camera_rays"] == c["intersect_tests"] == L.size and c["shadow_tests"] == 8 * L.size
+
+
+def test_oracle_ao_render_rejects_zero_nsamples_and_null_params(pkg, oracle):
+    A = pkg._abi
+    sd, rp = _builder(pkg).world_end()
+    osc = oracle.scene(sd)
+    film = np.zeros((8, 8, 4), np.float32)
+    fp = film.ctypes.data_as(A.fp)
+    assert oracle.lib.orc_ao_render(osc.h, C.byref(rp), C.byref(pkg._abi_ao.PtAOParams(0, 1)), fp, 1) == A.PT_ERR_INVALID_ARG
+    assert oracle.lib.orc_ao_render(osc.h, C.byref(rp), None, fp, 1) == A.PT_ERR_INVALID_ARG
+    assert not film.any()
 
 
 AO_SCENE = """LookAt 0 0 -1  0 0 0  0 1 0
@@ -108,7 +122,6 @@ def test_front_end_path_scenes_are_unchanged_and_others_refused(pkg):
 
 
 def test_mi355ao_header_is_c99_and_matches_the_ctypes_mirror(pkg, tmp_path):
-    import ctypes as C
     A = pkg._abi_ao
     src = tmp_path / "probe.c"
     src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "mi355ao.h"\n'

@@ -1,13 +1,11 @@
-"""The ambient-occlusion integrator on the GPU (libmi355ao.so, include/mi355ao.h) against the test-side reference of
-tests/ao_reference.py (built from the CPU oracle's exports) and against what can be derived analytically."""
+"""The ambient-occlusion integrator on the GPU (libmi355ao.so, include/mi355ao.h) against the CPU oracle's render loop
+(orc_ao_render) and against what can be derived analytically."""
 import math
 import subprocess
 
 import numpy as np
 import pytest
 from conftest import ckeys, trace_env
-
-from ao_reference import AOReference
 
 pytestmark = pytest.mark.gpu
 CKEYS = ("camera_rays", "intersect_tests", "shadow_tests", "bvh_nodes_visited", "triangle_tests", "sphere_tests", "film_splats",
@@ -42,6 +40,10 @@ CASES = {
     "sobol_sphere": dict(builder="ganesha_scale", sampler="sobol", cossample=False, kw=dict(n=12, xres=32, yres=24, spp=2)),
     "normals": dict(builder="ganesha_scale", sampler="sobol", cossample=True, kw=dict(n=12, xres=32, yres=24, spp=1, with_normals=True)),
     "alpha": dict(builder="alpha_foliage", sampler="halton", cossample=False, kw=dict(xres=32, yres=24, spp=1, instanced=False)),
+    "spheres": dict(builder="spheres_c1", sampler="sobol", cossample=True, kw=dict(xres=32, yres=24, spp=2)),
+    "disks": dict(builder="disk_scene", sampler="halton", cossample=False, kw=dict(xres=32, yres=24, spp=2)),
+    "instances": dict(builder="instanced_garden", sampler="sobol", cossample=True, kw=dict(xres=32, yres=24, spp=1, flatten=False)),
+    "max_lum": dict(builder="ganesha_scale", sampler="halton", cossample=True, kw=dict(n=12, xres=32, yres=24, spp=2), max_lum=1.0),
 }
 
 
@@ -51,17 +53,22 @@ def test_ao_film_and_counters_match_the_reference(pkg, gpu, oracle, case):
     ns = 8
     sd, rp = ao_scene(pkg, getattr(pkg.scenes, c["builder"]), ns, c["cossample"], c["sampler"], **c["kw"])
     assert rp.integrator == pkg._abi_ao.PT_INTEGRATOR_AO
+    if "max_lum" in c:
+        rp.max_sample_luminance = c["max_lum"]
     sc, film = render_ao(pkg, gpu, sd, rp)
-    ref = AOReference(oracle, pkg._abi, sd, rp, ns, c["cossample"])
-    want = ref.render()
-    got = sc.counters()
+    osc = oracle.scene(sd)
+    want = osc.render(rp, nthreads=4)
+    got, ref = sc.counters(), osc.counters()
     for k in ckeys(CKEYS):
-        assert got[k] == ref.counters[k], (k, got[k], ref.counters[k])
+        assert got[k] == ref[k], (k, got[k], ref[k])
     for k in ZERO_KEYS:
         assert not np.any(got[k]), k
     if not c["cossample"] and case == "sobol_sphere":
         assert got["sanitized_negative"] > 0   # uniform sphere sampling: some sample's sum is negative
     assert_film_close(film, want)
+    if "max_lum" in c:   # the clamp fires: the unclamped film is another one
+        rp.max_sample_luminance = float("inf")
+        assert not np.allclose(osc.render(rp, nthreads=4), want, rtol=1e-3)
 
 
 def _plane_scene(pkg, kind, inside_sphere=False, nsamples=16, cossample=True, spp=2, res=16):
@@ -111,7 +118,7 @@ def test_ao_instances_match_the_flattened_reference(pkg, gpu, oracle):
     sd, rp = ao_scene(pkg, pkg.scenes.instanced_garden, ns, True, xres=32, yres=24, spp=1, flatten=False)
     sc, film = render_ao(pkg, gpu, sd, rp)
     sdf, rpf = ao_scene(pkg, pkg.scenes.instanced_garden, ns, True, xres=32, yres=24, spp=1, flatten=True)
-    want = AOReference(oracle, pkg._abi, sdf, rpf, ns, True).render()
+    want = oracle.scene(sdf).render(rpf, nthreads=4)
     a = sc.resolve(film); b = sc.resolve(want)
     diff = np.abs(a - b)
     assert (diff.max(axis=2) > 0.05).mean() <= 0.01 and diff.mean() < 2e-3
