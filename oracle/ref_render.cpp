@@ -1,8 +1,9 @@
 // ORACLE -- TEST INFRASTRUCTURE ONLY (see ref_math.h header).
-// ref_render.cpp: materials -> BSDF, one-light MIS, PathIntegrator::li, AOIntegrator::li, perspective camera, film,
-// the tile render loop, and the oracle's C ABI (driven from tests/ and bench.py's cpu_baseline leg).
-//   materials/{matte,mirror,glass,plastic,metal,uber,substrate}.rs; core/integrator.rs:81-237,263-403;
-//   integrators/path.rs:79-222; integrators/ao.rs:63-110; cameras/perspective.rs:120-179; core/film.rs:104-161,217-258,292-331.
+// ref_render.cpp: materials -> BSDF, media, one-light MIS, the BSSRDF exit step, PathIntegrator::li, VolPathIntegrator::li, AOIntegrator::li,
+// perspective camera, film, the tile render loop, and the oracle's C ABI (driven from tests/ and bench.py's cpu_baseline leg).
+//   materials/{matte,mirror,glass,plastic,metal,uber,substrate}.rs; media/{homogeneous,grid}.rs; core/integrator.rs:81-237,263-403;
+//   core/light.rs:120-150 (VisibilityTester::tr); core/scene.rs:68-87 (intersect_tr); core/bssrdf.rs:334-410,559-574 (sample_s); integrators/path.rs:79-222;
+//   integrators/volpath.rs:76-226; integrators/ao.rs:63-110; cameras/perspective.rs:120-179; core/film.rs:104-161,217-258,292-331.
 #include "ref_bssrdf.h"
 #include "ref_texture.h"
 #include "ref_hlbvh.h"
@@ -324,207 +325,8 @@ static bool material_scattering_functions(const Scene &scene, uint32_t mi, Surfa
     return false;
 }
 
-// ---- direct lighting (core/integrator.rs:81-237) ---------------------------------------------------
-struct RenderCtx {
-    const Scene *scene;
-    const LightSampler *lights;
-    Counters *c;
-};
-
-static RGB isect_le(const RenderCtx &ctx, const SurfaceInteraction &si, V3 w) {  // interaction.rs:344-349
-    uint32_t li = ctx.scene->prim_light[si.prim];
-    if (li == PT_NONE) return RGB(0.0f);
-    return ctx.lights->area_l(li, si.n, w);
-}
-
-static RGB estimate_direct(const RenderCtx &ctx, const SurfaceInteraction &si, const BSDF &bsdf, P2 uscatt, uint32_t li, P2 ulight) {
-    const int flags = BSDF_ALL & ~BSDF_SPECULAR;
-    RGB Ld(0.0f);
-    IData it; it.p = si.p; it.p_error = si.p_error; it.n = si.n; it.wo = si.wo;
-    V3 wi; Float lightpdf = 0.0f, scattpdf = 0.0f; IData p1;
-    RGB Li = ctx.lights->sample_li(li, it, ulight, wi, lightpdf, p1);
-    bool delta = ctx.lights->is_delta(li);
-    if (lightpdf > 0.0f && !Li.is_black()) {
-        RGB f = bsdf.f(si.wo, wi, flags) * abs_dot(wi, si.sh_n);
-        scattpdf = bsdf.pdf(si.wo, wi, flags);
-        if (!f.is_black()) {
-            Ray sr = spawn_ray_to(it, p1);  // VisibilityTester::unoccluded (light.rs:120-123)
-            if (ctx.scene->intersect_p(sr, *ctx.c)) Li = RGB(0.0f);
-            if (!Li.is_black()) {
-                if (delta) Ld += f * Li / lightpdf;
-                else {
-                    Float weight = power_heuristic(1, lightpdf, 1, scattpdf);
-                    Ld += f * Li * weight / lightpdf;
-                }
-            }
-        }
-    }
-    if (!delta) {
-        int sampled_type = 0;
-        RGB f = bsdf.sample_f(si.wo, wi, uscatt, scattpdf, flags, sampled_type);
-        f = f * abs_dot(wi, si.sh_n);
-        bool sampled_specular = (sampled_type & BSDF_SPECULAR) != 0;
-        if (!f.is_black() && scattpdf > 0.0f) {
-            Float weight = 1.0f;
-            if (!sampled_specular) {
-                lightpdf = ctx.lights->pdf_li(li, it, wi);
-                if (lightpdf == 0.0f) return Ld;
-                weight = power_heuristic(1, scattpdf, 1, lightpdf);
-            }
-            SurfaceInteraction lisect;
-            Ray ray = spawn_ray(it, wi);
-            bool found = ctx.scene->intersect(ray, lisect, *ctx.c);
-            RGB li_(0.0f);
-            if (found) {
-                if (ctx.scene->prim_light[lisect.prim] == li) li_ = isect_le(ctx, lisect, -wi);
-            } else li_ = ctx.lights->light_le(li, ray);
-            if (!li_.is_black()) Ld += f * li_ * RGB(1.0f) * weight / scattpdf;
-        }
-    }
-    return Ld;
-}
-
-static RGB uniform_sample_onelight(const RenderCtx &ctx, const SurfaceInteraction &si, const BSDF &bsdf, SobolSampler &sampler,
-                                   const Distribution1D *distrib) {
-    size_t nlights = ctx.scene->lights.size();
-    if (nlights == 0) return RGB(0.0f);
-    Float lightpdf = 0.0f;
-    size_t lightnum = distrib->sample_discrete(sampler.get_1d(), &lightpdf);
-    if (lightpdf == 0.0f) return RGB(0.0f);
-    P2 ulight = sampler.get_2d();
-    P2 uscatt = sampler.get_2d();
-    return estimate_direct(ctx, si, bsdf, uscatt, (uint32_t)lightnum, ulight) / lightpdf;
-}
-
-// ---- PathIntegrator::li (integrators/path.rs:79-222) ------------------------------------------------
-struct PathParams { uint32_t max_depth; Float rr_threshold; };
-
-static RGB path_li(const RenderCtx &ctx, const PathParams &pp, Ray ray, SobolSampler &sampler, RayDiff rdiff = RayDiff()) {
-    RGB L(0.0f), beta(1.0f);
-    bool specular_bounce = false;
-    uint32_t bounces = 0;
-    Float etascale = 1.0f;
-    for (;;) {
-        SurfaceInteraction isect;
-        bool found = ctx.scene->intersect(ray, isect, *ctx.c);
-        if (bounces == 0 || specular_bounce) {
-            if (found) L += isect_le(ctx, isect, -ray.d) * beta;
-            else for (uint32_t li : ctx.scene->infinite_lights) L += ctx.lights->light_le(li, ray) * beta;
-        }
-        if (!found || bounces >= pp.max_depth) break;
-        BSDF bsdf;
-        TabulatedBSSRDF bssrdf; bool has_bssrdf = false;
-        // SurfaceInteraction::compute_scattering_functions (interaction.rs:262-267): differentials of THIS ray first;
-        // only the camera ray carries them (every spawn_ray below creates a ray without differentials)
-        TexCtx tctx;
-        const bool textured = (bool)ctx.scene->textures;
-        if (textured) tctx = compute_differentials(isect, rdiff);
-        rdiff.has = false;
-        if (!compute_scattering_functions(*ctx.scene, isect, bsdf, &bssrdf, &has_bssrdf, textured ? &tctx : nullptr)) {
-            IData it; it.p = isect.p; it.p_error = isect.p_error; it.n = isect.n;
-            ray = spawn_ray(it, ray.d);
-            continue;
-        }
-        const Distribution1D *distrib = ctx.lights->lookup(isect.p);
-        if (bsdf.num_components(BSDF_ALL & ~BSDF_SPECULAR) > 0) {
-            ctx.c->zero_den++;
-            RGB Ld = beta * uniform_sample_onelight(ctx, isect, bsdf, sampler, distrib);
-            if (Ld.is_black()) ctx.c->zero_num++;
-            if (!(Ld.y() >= 0.0f)) ctx.c->ref_asserts++;   // path.rs:143 assert!(Ld.y() >= 0.0)
-            L += Ld;
-        }
-        V3 wo = -ray.d, wi;
-        Float pdf = 0.0f; int flags = 0;
-        RGB f = bsdf.sample_f(wo, wi, sampler.get_2d(), pdf, BSDF_ALL, flags);
-        if (f.is_black() || pdf == 0.0f) break;
-        beta *= f * abs_dot(wi, isect.sh_n) / pdf;
-        if (!(beta.y() >= 0.0f)) ctx.c->ref_asserts++;       // path.rs:162
-        if (std::isinf(beta.y())) ctx.c->ref_asserts++;      // path.rs:163
-        specular_bounce = (flags & BSDF_SPECULAR) != 0;
-        if ((flags & BSDF_SPECULAR) && (flags & BSDF_TRANSMISSION)) {
-            Float eta = bsdf.eta;
-            etascale *= (dot(wo, isect.n) > 0.0f) ? eta * eta : 1.0f / (eta * eta);
-        }
-        IData it; it.p = isect.p; it.p_error = isect.p_error; it.n = isect.n;
-        ray = spawn_ray(it, wi);
-        if (has_bssrdf && (flags & BSDF_TRANSMISSION)) {  // path.rs:177-204
-            P2 s2 = sampler.get_2d();
-            Float s1 = sampler.get_1d();
-            if (std::isinf(beta.y())) ctx.c->ref_asserts++;  // path.rs:184 (evaluated after sample_s whatever it returned)
-            // TabulatedBSSRDF::sample_s -> sample_sp (bssrdf.rs:334-410)
-            V3 start, target; Float u1n = 0.0f;
-            if (!bssrdf.probe_segment(s1, s2, start, target, u1n)) break;   // S black
-            IData base; base.p = start; base.p_error = V3(0, 0, 0); base.n = V3(0, 0, 0);
-            std::vector<SurfaceInteraction> chain;
-            for (;;) {
-                // spawn_rayto_point (interaction.rs:38-43): d = p2 - p measured from the un-offset point
-                V3 d = target - base.p;
-                Ray r(offset_ray_origin(base.p, base.p_error, base.n, d), d, 1.0f - SHADOW_EPSILON, 0.0f);
-                SurfaceInteraction si2;
-                if ((d.x == 0.0f && d.y == 0.0f && d.z == 0.0f) || !ctx.scene->intersect(r, si2, *ctx.c)) break;
-                base.p = si2.p; base.p_error = si2.p_error; base.n = si2.n;
-                if (ctx.scene->prim_material[si2.prim] == bssrdf.material) chain.push_back(si2);
-            }
-            size_t nfound = chain.size();
-            if (nfound == 0) break;
-            size_t selected = (size_t)clampv((int64_t)(u1n * (Float)nfound), (int64_t)0, (int64_t)nfound - 1);
-            SurfaceInteraction pi = chain[selected];
-            pdf = bssrdf.pdf_sp(pi.p, pi.n) / (Float)nfound;
-            RGB S = bssrdf.sr(length(bssrdf.po_p - pi.p));
-            if (S.is_black() || pdf == 0.0f) break;
-            // sample_s (bssrdf.rs:559-574): BSDF::new(pi, 1.0) + SeparableBSSRDFAdapter, pi.wo = shading.n
-            BSDF pibsdf; pibsdf.init(pi, 1.0f);
-            { Bxdf b; b.kind = BX_BSSRDF; b.type = BSDF_REFLECTION | BSDF_DIFFUSE; b.etab = bssrdf.eta; pibsdf.add(b); }
-            pi.wo = pi.sh_n;
-            beta *= S / pdf;
-            const Distribution1D *d2 = ctx.lights->lookup(pi.p);
-            L += beta * uniform_sample_onelight(ctx, pi, pibsdf, sampler, d2);
-            RGB ff = pibsdf.sample_f(pi.wo, wi, sampler.get_2d(), pdf, BSDF_ALL, flags);
-            if (ff.is_black() || pdf == 0.0f) break;
-            beta *= ff * abs_dot(wi, pi.sh_n) / pdf;
-            if (std::isinf(beta.y())) ctx.c->ref_asserts++;  // path.rs:201
-            specular_bounce = (flags & BSDF_SPECULAR) != 0;
-            IData pit; pit.p = pi.p; pit.p_error = pi.p_error; pit.n = pi.n;
-            ray = spawn_ray(pit, wi);
-        }
-        RGB rrbeta = beta * etascale;
-        if (rrbeta.max_component_value() < pp.rr_threshold && bounces > 3) {
-            Float q = fmax_(1.0f - rrbeta.max_component_value(), 0.05f);
-            if (sampler.get_1d() < q) break;
-            beta = beta / (1.0f - q);
-            if (std::isinf(beta.y())) ctx.c->ref_asserts++;  // path.rs:213 / volpath.rs:223
-        }
-        bounces += 1;
-    }
-    ctx.c->path_len[std::min<uint32_t>(bounces, 15)]++;
-    return L;
-}
-
-// ---- AOIntegrator::li (integrators/ao.rs:63-110) ----------------------------------------------------
-// compute_scattering_functions (ao.rs:79) changes only the BSDF and the shading geometry, which AO does not read.
-static RGB ao_li(const RenderCtx &ctx, const PtAOParams &ao, Ray ray, SobolSampler &sampler) {
-    RGB L(0.0f);
-    SurfaceInteraction isect;
-    if (!ctx.scene->intersect(ray, isect, *ctx.c)) return L;
-    // the frame of the true geometry, not the shading geometry
-    V3 n = face_forward(isect.n, -ray.d), s = normalize(isect.dpdu), t = cross(isect.n, s);
-    IData it; it.p = isect.p; it.p_error = isect.p_error; it.n = isect.n;
-    for (uint32_t k = 0; k < ao.nsamples; ++k) {
-        V3 wi; Float pdf;
-        if (ao.cos_sample) { wi = cosine_sample_hemisphere(sampler.get_2d_array(k)); pdf = std::fabs(wi.z) * INV_PI; }   // cosine_hemisphere_pdf
-        else { wi = uniform_sample_sphere(sampler.get_2d_array(k)); pdf = INV4_PI; }                                  // uniform_sphere_pdf
-        wi = V3(s.x * wi.x + t.x * wi.y + n.x * wi.z, s.y * wi.x + t.y * wi.y + n.y * wi.z, s.z * wi.x + t.z * wi.y + n.z * wi.z);
-        if (!ctx.scene->intersect_p(spawn_ray(it, wi), *ctx.c)) L += RGB(dot(wi, n) / (pdf * (Float)ao.nsamples));
-    }
-    return L;
-}
-
-
-// ---- VolPathIntegrator (integrators/volpath.rs:76-186) with HomogeneousMedium (media/homogeneous.rs) and the Henyey-Greenstein
-//      phase function (core/medium.rs:149-194). A primitive without a material is a medium-interface shell (api.rs:597): the path
-//      steps over it with `bounces -= 1; continue` (volpath.rs:152-156: the increment at the loop's end is skipped, so the count drops
-//      and, at 0, wraps -- the release build has no overflow checks), and the transmittance loops of VisibilityTester::tr
-//      (light.rs:125-150) and Scene::intersect_tr (scene.rs:68-87) walk on behind it.
+// ---- participating media: HomogeneousMedium (media/homogeneous.rs), GridDensityMedium (media/grid.rs) and the Henyey-Greenstein
+//      phase function (core/medium.rs:149-194)
 static inline Float dm_expf_(Float x) { return (Float)dm_expd((double)x); }   // f32::exp through the shared f64 exp
 static RGB medium_tr(const PtMedium &m, Float t_max, V3 d) {   // homogeneous.rs:32-35
     Float l = fmin_(t_max * length(d), std::numeric_limits<Float>::max());
@@ -662,36 +464,82 @@ static MedIface surface_iface(const Scene &s, uint32_t prim, uint32_t ray_medium
 }
 static inline uint32_t medium_toward(const MedIface &m, V3 n, V3 w) { return dot(w, n) > 0.0f ? m.outside : m.inside; }
 
-// estimate_direct with handle_media = true (integrator.rs:109-237) for a surface (bsdf != nullptr) or a medium vertex
-static RGB vol_estimate_direct(const RenderCtx &ctx, const IData &it, const MedIface &mif, const SurfaceInteraction *si, const BSDF *bsdf, Float g,
-                               P2 uscatt, uint32_t li, P2 ulight, SobolSampler &sampler) {   // the sampler: grid media draw their tracking steps from it (grid.rs)
+// ---- direct lighting (core/integrator.rs:81-237) ---------------------------------------------------
+struct RenderCtx {
+    const Scene *scene;
+    const LightSampler *lights;
+    Counters *c;
+};
+
+static RGB isect_le(const RenderCtx &ctx, const SurfaceInteraction &si, V3 w) {  // interaction.rs:344-349
+    uint32_t li = ctx.scene->prim_light[si.prim];
+    if (li == PT_NONE) return RGB(0.0f);
+    return ctx.lights->area_l(li, si.n, w);
+}
+static IData get_data(const SurfaceInteraction &si) { IData it; it.p = si.p; it.p_error = si.p_error; it.n = si.n; it.wo = si.wo; return it; }   // interaction.rs:79
+
+// The vertex that estimate_direct lights (Interactions, core/interaction.rs): a surface (si and its BSDF) or, with bsdf == nullptr, a
+// medium vertex whose phase function is Henyey-Greenstein with `g`. `mif` is its MediumInterface, read only when media are handled.
+struct Interaction {
+    IData it; MedIface mif;
+    const SurfaceInteraction *si = nullptr; const BSDF *bsdf = nullptr; Float g = 0.0f;
+};
+static Interaction surface_at(const SurfaceInteraction &si, const BSDF &bsdf, MedIface mif = MedIface()) {
+    return Interaction{get_data(si), mif, &si, &bsdf, 0.0f};
+}
+
+// VisibilityTester::tr (light.rs:125-150): the shadow ray from p0 to p1 walks on through the surfaces without a material (medium-interface
+// shells), one closest-hit intersect per segment; an opaque surface blocks it.
+static RGB visibility_tr(const RenderCtx &ctx, const IData &p0, const MedIface &mif, const IData &p1, SobolSampler &sampler) {
     const Scene &S = *ctx.scene;
+    Ray ray = spawn_ray_to(p0, p1);
+    ray.medium = medium_toward(mif, p0.n, ray.d);
+    RGB Tr(1.0f);
+    for (;;) {
+        SurfaceInteraction isect;
+        const bool hitt = S.intersect(ray, isect, *ctx.c);
+        if (hitt && S.prim_material[isect.prim] != PT_NONE) return RGB(0.0f);   // an opaque surface along the ray's path
+        if (ray.medium != PT_NONE) Tr = Tr * medium_tr_any(S, ray.medium, ray, sampler);   // the current segment (ray.t_max = the hit)
+        if (!hitt) break;
+        const uint32_t seg_medium = ray.medium;
+        ray = spawn_ray_to(get_data(isect), p1);                                       // isect.spawn_rayto_interaction(&self.p1)
+        ray.medium = medium_toward(surface_iface(S, isect.prim, seg_medium), isect.n, ray.d);   // get_medium(d) of the shell's interface (interaction.rs:54-66)
+    }
+    return Tr;
+}
+
+// Scene::intersect_tr (scene.rs:68-87): on through every surface that has no material; true when the ray ends on one that has (`isect`)
+static bool intersect_tr(const RenderCtx &ctx, Ray ray, SobolSampler &sampler, SurfaceInteraction &isect, RGB &Tr) {
+    const Scene &S = *ctx.scene;
+    Tr = RGB(1.0f);
+    for (;;) {
+        const bool hits = S.intersect(ray, isect, *ctx.c);
+        if (ray.medium != PT_NONE) Tr = Tr * medium_tr_any(S, ray.medium, ray, sampler);
+        if (!hits) return false;
+        if (S.prim_material[isect.prim] != PT_NONE) return true;
+        const uint32_t seg_medium = ray.medium;
+        ray = spawn_ray(get_data(isect), ray.d);                                       // isect.spawn_ray(&ray.d)
+        ray.medium = medium_toward(surface_iface(S, isect.prim, seg_medium), isect.n, ray.d);
+    }
+}
+
+// estimate_direct (integrator.rs:109-237) with specular = false. With handle_media the light sample's visibility is visibility_tr and the
+// BSDF-sampled ray follows intersect_tr; grid media draw their tracking samples from the sampler, for the light ray first. Without it the
+// light sample is one Scene::intersect_p (the any-hit counters), the BSDF-sampled ray one Scene::intersect, and nothing is drawn.
+static RGB estimate_direct(const RenderCtx &ctx, const Interaction &v, P2 uscatt, uint32_t li, P2 ulight, SobolSampler &sampler, bool handle_media) {
     const int flags = BSDF_ALL & ~BSDF_SPECULAR;
+    const IData &it = v.it;
     RGB Ld(0.0f);
     V3 wi; Float lightpdf = 0.0f, scattpdf = 0.0f; IData p1;
     RGB Li = ctx.lights->sample_li(li, it, ulight, wi, lightpdf, p1);
     bool delta = ctx.lights->is_delta(li);
     if (lightpdf > 0.0f && !Li.is_black()) {
         RGB f;
-        if (bsdf) { f = bsdf->f(si->wo, wi, flags) * abs_dot(wi, si->sh_n); scattpdf = bsdf->pdf(si->wo, wi, flags); }
-        else { Float p = phase_hg(dot(it.wo, wi), g); f = RGB(p); scattpdf = p; }
+        if (v.bsdf) { f = v.bsdf->f(v.si->wo, wi, flags) * abs_dot(wi, v.si->sh_n); scattpdf = v.bsdf->pdf(v.si->wo, wi, flags); }
+        else { Float p = phase_hg(dot(it.wo, wi), v.g); f = RGB(p); scattpdf = p; }
         if (!f.is_black()) {
-            // VisibilityTester::tr (light.rs:125-150): a loop over the segments between material-less surfaces (medium-interface shells)
-            Ray sr = spawn_ray_to(it, p1);
-            sr.medium = medium_toward(mif, it.n, sr.d);
-            RGB Tr(1.0f);
-            for (;;) {
-                SurfaceInteraction tmp;
-                const bool hitt = S.intersect(sr, tmp, *ctx.c);
-                if (hitt && S.prim_material[tmp.prim] != PT_NONE) { Tr = RGB(0.0f); break; }   // an opaque surface along the ray's path
-                if (sr.medium != PT_NONE) Tr = Tr * medium_tr_any(S, sr.medium, sr, sampler);   // the current segment (ray.t_max = the hit)
-                if (!hitt) break;
-                IData a; a.p = tmp.p; a.p_error = tmp.p_error; a.n = tmp.n;
-                const uint32_t seg_medium = sr.medium;
-                sr = spawn_ray_to(a, p1);                                                     // isect.spawn_rayto_interaction(&self.p1)
-                sr.medium = medium_toward(surface_iface(S, tmp.prim, seg_medium), tmp.n, sr.d);   // get_medium(d) of the shell's interface (interaction.rs:54-66)
-            }
-            Li = Li * Tr;
+            if (handle_media) Li = Li * visibility_tr(ctx, it, v.mif, p1, sampler);
+            else if (ctx.scene->intersect_p(spawn_ray_to(it, p1), *ctx.c)) Li = RGB(0.0f);   // VisibilityTester::unoccluded (light.rs:120-123)
             if (!Li.is_black()) {
                 if (delta) Ld += f * Li / lightpdf;
                 else { Float weight = power_heuristic(1, lightpdf, 1, scattpdf); Ld += f * Li * weight / lightpdf; }
@@ -700,12 +548,12 @@ static RGB vol_estimate_direct(const RenderCtx &ctx, const IData &it, const MedI
     }
     if (!delta) {
         RGB f; bool sampled_specular = false;
-        if (bsdf) {
+        if (v.bsdf) {
             int sampled_type = 0;
-            f = bsdf->sample_f(si->wo, wi, uscatt, scattpdf, flags, sampled_type);
-            f = f * abs_dot(wi, si->sh_n);
+            f = v.bsdf->sample_f(v.si->wo, wi, uscatt, scattpdf, flags, sampled_type);
+            f = f * abs_dot(wi, v.si->sh_n);
             sampled_specular = (sampled_type & BSDF_SPECULAR) != 0;
-        } else { Float p = hg_sample_p(g, it.wo, wi, uscatt); f = RGB(p); scattpdf = p; }
+        } else { Float p = hg_sample_p(v.g, it.wo, wi, uscatt); f = RGB(p); scattpdf = p; }
         if (!f.is_black() && scattpdf > 0.0f) {
             Float weight = 1.0f;
             if (!sampled_specular) {
@@ -715,38 +563,176 @@ static RGB vol_estimate_direct(const RenderCtx &ctx, const IData &it, const MedI
             }
             SurfaceInteraction lisect;
             Ray ray = spawn_ray(it, wi);
-            ray.medium = medium_toward(mif, it.n, wi);
-            // Scene::intersect_tr (scene.rs:68-87): on through every surface that has no material
-            bool found = false;
             RGB Tr(1.0f);
-            for (;;) {
-                const bool hits = S.intersect(ray, lisect, *ctx.c);
-                if (ray.medium != PT_NONE) Tr = Tr * medium_tr_any(S, ray.medium, ray, sampler);
-                if (!hits) { found = false; break; }
-                if (S.prim_material[lisect.prim] != PT_NONE) { found = true; break; }
-                IData a; a.p = lisect.p; a.p_error = lisect.p_error; a.n = lisect.n;
-                const uint32_t seg_medium = ray.medium;
-                ray = spawn_ray(a, ray.d);                                                     // isect.spawn_ray(&ray.d)
-                ray.medium = medium_toward(surface_iface(S, lisect.prim, seg_medium), lisect.n, ray.d);
-            }
+            bool found;
+            if (handle_media) { ray.medium = medium_toward(v.mif, it.n, wi); found = intersect_tr(ctx, ray, sampler, lisect, Tr); }
+            else found = ctx.scene->intersect(ray, lisect, *ctx.c);
             RGB li_(0.0f);
-            if (found) { if (S.prim_light[lisect.prim] == li) li_ = isect_le(ctx, lisect, -wi); }
+            if (found) { if (ctx.scene->prim_light[lisect.prim] == li) li_ = isect_le(ctx, lisect, -wi); }
             else li_ = ctx.lights->light_le(li, ray);
             if (!li_.is_black()) Ld += f * li_ * Tr * weight / scattpdf;
         }
     }
     return Ld;
 }
-static RGB vol_uniform_sample_onelight(const RenderCtx &ctx, const IData &it, const MedIface &mif, const SurfaceInteraction *si, const BSDF *bsdf, Float g,
-                                       SobolSampler &sampler, const Distribution1D *distrib) {
+
+static RGB uniform_sample_onelight(const RenderCtx &ctx, const Interaction &v, SobolSampler &sampler, bool handle_media, const Distribution1D *distrib) {
     if (ctx.scene->lights.empty()) return RGB(0.0f);
     Float lightpdf = 0.0f;
     size_t lightnum = distrib->sample_discrete(sampler.get_1d(), &lightpdf);
     if (lightpdf == 0.0f) return RGB(0.0f);
     P2 ulight = sampler.get_2d();
     P2 uscatt = sampler.get_2d();
-    return vol_estimate_direct(ctx, it, mif, si, bsdf, g, uscatt, (uint32_t)lightnum, ulight, sampler) / lightpdf;
+    return estimate_direct(ctx, v, uscatt, (uint32_t)lightnum, ulight, sampler, handle_media) / lightpdf;
 }
+
+// ---- the steps path.rs and volpath.rs share ---------------------------------------------------------
+struct PathParams { uint32_t max_depth; Float rr_threshold; };
+
+// The BSSRDF exit of path.rs:177-204 / volpath.rs:186-214 from the probe samples the caller drew: sample_s -> sample_sp's probe chain
+// (bssrdf.rs:334-410), the exit point's adapter BSDF (:559-574), its one-light estimate and the BSDF sample that leaves it; false ends the
+// path. With handle_media a probe hit's MediumInterface is the primitive's own at a transition, else the probe ray's medium on both sides
+// (primitive.rs:139-145), and the next probe ray and the exit ray take their medium from it; the first probe ray has none.
+static bool subsurface_step(const RenderCtx &ctx, const TabulatedBSSRDF &bssrdf, Float s1, P2 s2, SobolSampler &sampler, bool handle_media,
+                            RGB &L, RGB &beta, bool &specular_bounce, Ray &ray) {
+    const Scene &S = *ctx.scene;
+    if (std::isinf(beta.y())) ctx.c->ref_asserts++;   // path.rs:184 / volpath.rs:194 (evaluated after sample_s whatever it returned)
+    V3 start, target; Float u1n = 0.0f;
+    if (!bssrdf.probe_segment(s1, s2, start, target, u1n)) return false;   // S black
+    IData base; base.p = start; base.p_error = V3(0, 0, 0); base.n = V3(0, 0, 0);
+    MedIface base_if;
+    std::vector<SurfaceInteraction> chain; std::vector<MedIface> chain_if;
+    for (;;) {
+        // spawn_rayto_point (interaction.rs:38-43): d = p2 - p measured from the un-offset point
+        V3 d = target - base.p;
+        Ray r(offset_ray_origin(base.p, base.p_error, base.n, d), d, 1.0f - SHADOW_EPSILON, 0.0f);
+        if (handle_media) r.medium = medium_toward(base_if, base.n, d);
+        SurfaceInteraction si2;
+        if ((d.x == 0.0f && d.y == 0.0f && d.z == 0.0f) || !S.intersect(r, si2, *ctx.c)) break;
+        base = get_data(si2);
+        if (handle_media) base_if = surface_iface(S, si2.prim, r.medium);
+        if (S.prim_material[si2.prim] == bssrdf.material) { chain.push_back(si2); chain_if.push_back(base_if); }
+    }
+    const size_t nfound = chain.size();
+    if (nfound == 0) return false;
+    const size_t selected = (size_t)clampv((int64_t)(u1n * (Float)nfound), (int64_t)0, (int64_t)nfound - 1);
+    SurfaceInteraction pi = chain[selected];
+    const MedIface pif = chain_if[selected];
+    Float pdf = bssrdf.pdf_sp(pi.p, pi.n) / (Float)nfound;
+    const RGB Sp = bssrdf.sr(length(bssrdf.po_p - pi.p));
+    if (Sp.is_black() || pdf == 0.0f) return false;
+    // sample_s (bssrdf.rs:559-574): BSDF::new(pi, 1.0) + SeparableBSSRDFAdapter, pi.wo = shading.n
+    BSDF pibsdf; pibsdf.init(pi, 1.0f);
+    { Bxdf b; b.kind = BX_BSSRDF; b.type = BSDF_REFLECTION | BSDF_DIFFUSE; b.etab = bssrdf.eta; pibsdf.add(b); }
+    pi.wo = pi.sh_n;
+    beta *= Sp / pdf;
+    const Distribution1D *distrib = ctx.lights->lookup(pi.p);
+    const Interaction pv = surface_at(pi, pibsdf, pif);
+    L += beta * uniform_sample_onelight(ctx, pv, sampler, handle_media, distrib);
+    V3 wi; int flags = 0;
+    const RGB f = pibsdf.sample_f(pi.wo, wi, sampler.get_2d(), pdf, BSDF_ALL, flags);
+    if (f.is_black() || pdf == 0.0f) return false;
+    beta *= f * abs_dot(wi, pi.sh_n) / pdf;
+    if (std::isinf(beta.y())) ctx.c->ref_asserts++;   // path.rs:201 / volpath.rs:210
+    specular_bounce = (flags & BSDF_SPECULAR) != 0;
+    ray = spawn_ray(pv.it, wi);
+    if (handle_media) ray.medium = medium_toward(pif, pi.n, wi);
+    return true;
+}
+
+// Russian roulette (path.rs:205-213, volpath.rs:216-223); false ends the path
+static bool russian_roulette(const RenderCtx &ctx, const PathParams &pp, uint32_t bounces, Float etascale, SobolSampler &sampler, RGB &beta) {
+    RGB rrbeta = beta * etascale;
+    if (rrbeta.max_component_value() < pp.rr_threshold && bounces > 3) {
+        Float q = fmax_(1.0f - rrbeta.max_component_value(), 0.05f);
+        if (sampler.get_1d() < q) return false;
+        beta = beta / (1.0f - q);
+        if (std::isinf(beta.y())) ctx.c->ref_asserts++;  // path.rs:213 / volpath.rs:223
+    }
+    return true;
+}
+
+// ---- PathIntegrator::li (integrators/path.rs:79-222) ------------------------------------------------
+static RGB path_li(const RenderCtx &ctx, const PathParams &pp, Ray ray, SobolSampler &sampler, RayDiff rdiff = RayDiff()) {
+    RGB L(0.0f), beta(1.0f);
+    bool specular_bounce = false;
+    uint32_t bounces = 0;
+    Float etascale = 1.0f;
+    for (;;) {
+        SurfaceInteraction isect;
+        bool found = ctx.scene->intersect(ray, isect, *ctx.c);
+        if (bounces == 0 || specular_bounce) {
+            if (found) L += isect_le(ctx, isect, -ray.d) * beta;
+            else for (uint32_t li : ctx.scene->infinite_lights) L += ctx.lights->light_le(li, ray) * beta;
+        }
+        if (!found || bounces >= pp.max_depth) break;
+        BSDF bsdf;
+        TabulatedBSSRDF bssrdf; bool has_bssrdf = false;
+        // SurfaceInteraction::compute_scattering_functions (interaction.rs:262-267): differentials of THIS ray first;
+        // only the camera ray carries them (every spawn_ray below creates a ray without differentials)
+        TexCtx tctx;
+        const bool textured = (bool)ctx.scene->textures;
+        if (textured) tctx = compute_differentials(isect, rdiff);
+        rdiff.has = false;
+        if (!compute_scattering_functions(*ctx.scene, isect, bsdf, &bssrdf, &has_bssrdf, textured ? &tctx : nullptr)) {
+            ray = spawn_ray(get_data(isect), ray.d);
+            continue;
+        }
+        const Distribution1D *distrib = ctx.lights->lookup(isect.p);
+        if (bsdf.num_components(BSDF_ALL & ~BSDF_SPECULAR) > 0) {
+            ctx.c->zero_den++;
+            RGB Ld = beta * uniform_sample_onelight(ctx, surface_at(isect, bsdf), sampler, false, distrib);
+            if (Ld.is_black()) ctx.c->zero_num++;
+            if (!(Ld.y() >= 0.0f)) ctx.c->ref_asserts++;   // path.rs:143 assert!(Ld.y() >= 0.0)
+            L += Ld;
+        }
+        V3 wo = -ray.d, wi;
+        Float pdf = 0.0f; int flags = 0;
+        RGB f = bsdf.sample_f(wo, wi, sampler.get_2d(), pdf, BSDF_ALL, flags);
+        if (f.is_black() || pdf == 0.0f) break;
+        beta *= f * abs_dot(wi, isect.sh_n) / pdf;
+        if (!(beta.y() >= 0.0f)) ctx.c->ref_asserts++;       // path.rs:162
+        if (std::isinf(beta.y())) ctx.c->ref_asserts++;      // path.rs:163
+        specular_bounce = (flags & BSDF_SPECULAR) != 0;
+        if ((flags & BSDF_SPECULAR) && (flags & BSDF_TRANSMISSION)) {
+            Float eta = bsdf.eta;
+            etascale *= (dot(wo, isect.n) > 0.0f) ? eta * eta : 1.0f / (eta * eta);
+        }
+        ray = spawn_ray(get_data(isect), wi);
+        if (has_bssrdf && (flags & BSDF_TRANSMISSION)) {  // path.rs:177-204
+            P2 s2 = sampler.get_2d();
+            Float s1 = sampler.get_1d();
+            if (!subsurface_step(ctx, bssrdf, s1, s2, sampler, false, L, beta, specular_bounce, ray)) break;
+        }
+        if (!russian_roulette(ctx, pp, bounces, etascale, sampler, beta)) break;
+        bounces += 1;
+    }
+    ctx.c->path_len[std::min<uint32_t>(bounces, 15)]++;
+    return L;
+}
+
+// ---- AOIntegrator::li (integrators/ao.rs:63-110) ----------------------------------------------------
+// compute_scattering_functions (ao.rs:79) changes only the BSDF and the shading geometry, which AO does not read.
+static RGB ao_li(const RenderCtx &ctx, const PtAOParams &ao, Ray ray, SobolSampler &sampler) {
+    RGB L(0.0f);
+    SurfaceInteraction isect;
+    if (!ctx.scene->intersect(ray, isect, *ctx.c)) return L;
+    // the frame of the true geometry, not the shading geometry
+    V3 n = face_forward(isect.n, -ray.d), s = normalize(isect.dpdu), t = cross(isect.n, s);
+    IData it; it.p = isect.p; it.p_error = isect.p_error; it.n = isect.n;
+    for (uint32_t k = 0; k < ao.nsamples; ++k) {
+        V3 wi; Float pdf;
+        if (ao.cos_sample) { wi = cosine_sample_hemisphere(sampler.get_2d_array(k)); pdf = std::fabs(wi.z) * INV_PI; }   // cosine_hemisphere_pdf
+        else { wi = uniform_sample_sphere(sampler.get_2d_array(k)); pdf = INV4_PI; }                                  // uniform_sphere_pdf
+        wi = V3(s.x * wi.x + t.x * wi.y + n.x * wi.z, s.y * wi.x + t.y * wi.y + n.y * wi.z, s.z * wi.x + t.z * wi.y + n.z * wi.z);
+        if (!ctx.scene->intersect_p(spawn_ray(it, wi), *ctx.c)) L += RGB(dot(wi, n) / (pdf * (Float)ao.nsamples));
+    }
+    return L;
+}
+
+// ---- VolPathIntegrator::li (integrators/volpath.rs:76-226). A primitive without a material is a medium-interface shell (api.rs:597): the path
+//      steps over it with `bounces -= 1; continue` (volpath.rs:152-156: the increment at the loop's end is skipped, so the count drops and, at 0,
+//      wraps -- the release build has no overflow checks), and visibility_tr and intersect_tr walk on behind it.
 static RGB volpath_li(const RenderCtx &ctx, const PathParams &pp, Ray ray, SobolSampler &sampler, RayDiff rdiff = RayDiff()) {
     const Scene &S = *ctx.scene;
     RGB L(0.0f), beta(1.0f);
@@ -766,7 +752,7 @@ static RGB volpath_li(const RenderCtx &ctx, const PathParams &pp, Ray ray, Sobol
             const Distribution1D *distrib = ctx.lights->lookup(mi.p);
             IData it; it.p = mi.p; it.p_error = V3(0, 0, 0); it.n = V3(0, 0, 0); it.wo = mi.wo;
             MedIface mif; mif.inside = mif.outside = mi.medium;
-            L += beta * vol_uniform_sample_onelight(ctx, it, mif, nullptr, nullptr, mi.g, sampler, distrib);
+            L += beta * uniform_sample_onelight(ctx, Interaction{it, mif, nullptr, nullptr, mi.g}, sampler, true, distrib);
             V3 wi;
             hg_sample_p(mi.g, mi.wo, wi, sampler.get_2d());
             ray = spawn_ray(it, wi); ray.medium = mi.medium;
@@ -788,15 +774,14 @@ static RGB volpath_li(const RenderCtx &ctx, const PathParams &pp, Ray ray, Sobol
             if (!compute_scattering_functions(S, isect, bsdf, &bssrdf, &has_bssrdf, textured ? &tctx : nullptr)) {
                 // a material that leaves no BSDF (App. A #14): volpath.rs:127-131 then does `bounces -= 1; continue`, which skips the
                 // increment at the end of the loop -- the count drops by one (and wraps below zero, ending the path at its next vertex)
-                IData it; it.p = isect.p; it.p_error = isect.p_error; it.n = isect.n;
                 uint32_t med = medium_toward(mif, isect.n, ray.d);
-                ray = spawn_ray(it, ray.d); ray.medium = med;
+                ray = spawn_ray(get_data(isect), ray.d); ray.medium = med;
                 bounces -= 1;
                 continue;
             }
             const Distribution1D *distrib = ctx.lights->lookup(isect.p);
-            IData it; it.p = isect.p; it.p_error = isect.p_error; it.n = isect.n; it.wo = isect.wo;
-            L += beta * vol_uniform_sample_onelight(ctx, it, mif, &isect, &bsdf, 0.0f, sampler, distrib);
+            const Interaction v = surface_at(isect, bsdf, mif);
+            L += beta * uniform_sample_onelight(ctx, v, sampler, true, distrib);
             V3 wo = -ray.d, wi;
             Float pdf = 0.0f; int flags = 0;
             RGB f = bsdf.sample_f(wo, wi, sampler.get_2d(), pdf, BSDF_ALL, flags);
@@ -808,59 +793,14 @@ static RGB volpath_li(const RenderCtx &ctx, const PathParams &pp, Ray ray, Sobol
                 Float eta = bsdf.eta;
                 etascale *= (dot(wo, isect.n) > 0.0f) ? eta * eta : 1.0f / (eta * eta);
             }
-            ray = spawn_ray(it, wi); ray.medium = medium_toward(mif, isect.n, wi);
+            ray = spawn_ray(v.it, wi); ray.medium = medium_toward(mif, isect.n, wi);
             if (has_bssrdf && (flags & BSDF_TRANSMISSION)) {   // volpath.rs:186-214: as path.rs:177-204, with the probe's samples drawn in the OTHER order
                 const Float s1 = sampler.get_1d();                 // (`sample_s(scene, sampler.get_1d(), &sampler.get_2d(), ..)`: arguments left to right)
                 const P2 s2 = sampler.get_2d();
-                if (std::isinf(beta.y())) ctx.c->ref_asserts++;    // volpath.rs:194
-                V3 start, target; Float u1n = 0.0f;
-                if (!bssrdf.probe_segment(s1, s2, start, target, u1n)) break;
-                // TabulatedBSSRDF::sample_sp's chain (bssrdf.rs:367-395). Every hit's MediumInterface is the primitive's own when it is a transition and
-                // the probe RAY's medium on both sides otherwise (primitive.rs:139-145); the next probe ray takes its medium from that interface
-                // (`base = si.get_data()`, interaction.rs:38-43,54-66); the first one starts from an interaction without any (InteractionData::default)
-                IData base; base.p = start; base.p_error = V3(0, 0, 0); base.n = V3(0, 0, 0);
-                MedIface base_if; bool base_has_if = false;
-                std::vector<SurfaceInteraction> chain; std::vector<MedIface> chain_if;
-                for (;;) {
-                    V3 d = target - base.p;
-                    Ray r(offset_ray_origin(base.p, base.p_error, base.n, d), d, 1.0f - SHADOW_EPSILON, 0.0f);
-                    r.medium = base_has_if ? medium_toward(base_if, base.n, d) : PT_NONE;
-                    SurfaceInteraction si2;
-                    if ((d.x == 0.0f && d.y == 0.0f && d.z == 0.0f) || !S.intersect(r, si2, *ctx.c)) break;
-                    base.p = si2.p; base.p_error = si2.p_error; base.n = si2.n;
-                    base_if = surface_iface(S, si2.prim, r.medium); base_has_if = true;
-                    if (S.prim_material[si2.prim] == bssrdf.material) { chain.push_back(si2); chain_if.push_back(base_if); }
-                }
-                const size_t nfound = chain.size();
-                if (nfound == 0) break;
-                const size_t selected = (size_t)clampv((int64_t)(u1n * (Float)nfound), (int64_t)0, (int64_t)nfound - 1);
-                SurfaceInteraction pi = chain[selected];
-                const MedIface pif = chain_if[selected];
-                pdf = bssrdf.pdf_sp(pi.p, pi.n) / (Float)nfound;
-                const RGB Sp = bssrdf.sr(length(bssrdf.po_p - pi.p));
-                if (Sp.is_black() || pdf == 0.0f) break;
-                BSDF pibsdf; pibsdf.init(pi, 1.0f);
-                { Bxdf b; b.kind = BX_BSSRDF; b.type = BSDF_REFLECTION | BSDF_DIFFUSE; b.etab = bssrdf.eta; pibsdf.add(b); }
-                pi.wo = pi.sh_n;
-                beta *= Sp / pdf;
-                const Distribution1D *d2 = ctx.lights->lookup(pi.p);
-                IData pit; pit.p = pi.p; pit.p_error = pi.p_error; pit.n = pi.n; pit.wo = pi.wo;
-                L += beta * vol_uniform_sample_onelight(ctx, pit, pif, &pi, &pibsdf, 0.0f, sampler, d2);
-                const RGB ff = pibsdf.sample_f(pi.wo, wi, sampler.get_2d(), pdf, BSDF_ALL, flags);
-                if (ff.is_black() || pdf == 0.0f) break;
-                beta *= ff * abs_dot(wi, pi.sh_n) / pdf;
-                if (std::isinf(beta.y())) ctx.c->ref_asserts++;    // volpath.rs:210
-                specular_bounce = (flags & BSDF_SPECULAR) != 0;
-                ray = spawn_ray(pit, wi); ray.medium = medium_toward(pif, pi.n, wi);
+                if (!subsurface_step(ctx, bssrdf, s1, s2, sampler, true, L, beta, specular_bounce, ray)) break;
             }
         }
-        RGB rrbeta = beta * etascale;
-        if (rrbeta.max_component_value() < pp.rr_threshold && bounces > 3) {
-            Float q = fmax_(1.0f - rrbeta.max_component_value(), 0.05f);
-            if (sampler.get_1d() < q) break;
-            beta = beta / (1.0f - q);
-            if (std::isinf(beta.y())) ctx.c->ref_asserts++;  // path.rs:213 / volpath.rs:223
-        }
+        if (!russian_roulette(ctx, pp, bounces, etascale, sampler, beta)) break;
         bounces += 1;
     }
     ctx.c->path_len[std::min<uint32_t>(bounces, 15)]++;
