@@ -6,6 +6,7 @@ import sys
 
 import numpy as np
 import pytest
+from parity import assert_same_film
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -43,5 +44,4 @@ def test_dumped_film_is_the_render_of_the_timed_steps(pkg, gpu, tmp_path, trace_
     sd, rp = pkg.scenes.ganesha_scale(n=48, xres=160, yres=96, spp=8).world_end()
     ref = pkg.Scene(gpu, sd).render(rp)
     assert film.dtype == np.float32 and film.shape == ref.shape == (96, 160, 4)
-    assert np.array_equal(film[..., 3], ref[..., 3])
-    np.testing.assert_allclose(film[..., :3], ref[..., :3], rtol=2e-6, atol=1e-7)
+    assert_same_film(film, ref)

@@ -8,6 +8,7 @@ import re
 import subprocess
 import numpy as np
 import pytest
+from parity import assert_same_film, assert_same_render
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INC = os.path.join(ROOT, "include")
@@ -100,13 +101,12 @@ def test_plain_c_client_renders_what_the_ctypes_path_renders(pkg, gpu, oracle, t
     g = pkg.Scene(gpu, sd)
     film = g.render(rp); gc = g.counters()
     cfilm = np.fromfile(tmp_path / "film.bin", np.float32).reshape(film.shape)
-    assert np.array_equal(cfilm[..., 3], film[..., 3])
-    np.testing.assert_allclose(cfilm, film, rtol=2e-6, atol=1e-7)
+    assert_same_film(cfilm, film)
     words = r.stdout.split()
     cc = {words[i]: int(words[i + 1]) for i in range(0, len(words), 2)}
-    for k, v in cc.items():
+    for k, v in cc.items():   # (the counters the client prints)
         assert gc[k] == v, k
     orc = oracle.scene(sd)
     ofilm = orc.render(rp, nthreads=4)
-    np.testing.assert_allclose(cfilm, ofilm, rtol=2e-6, atol=1e-7)
+    assert_same_render(cfilm, ofilm, gc, orc.counters(), weights=2e-6)
     np.testing.assert_allclose(np.fromfile(tmp_path / "rgb.bin", np.float32).reshape(48, 64, 3), orc.resolve(ofilm, rp.scale), rtol=2e-5, atol=1e-6)

@@ -4,6 +4,7 @@ oracle is additionally checked through exact integer properties of the construct
 import ctypes as C
 import numpy as np
 import pytest
+from parity import assert_render_matches_oracle
 
 
 def _samples(fn, A, sb, n_dims, xy, sn, at_center=0):
@@ -137,29 +138,22 @@ def _halton(b):
 
 @pytest.mark.gpu
 def test_gpu_halton_render_matches_oracle(pkg, gpu, oracle):
-    from test_gpu_parity import _compare_render
     S = pkg.scenes
-    _compare_render(pkg, gpu, oracle, *_halton(S.ganesha_scale(n=24, xres=64, yres=48, spp=8)))
-    _compare_render(pkg, gpu, oracle, *_halton(S.material_zoo(xres=64, yres=48, spp=8)))
-    _compare_render(pkg, gpu, oracle, *_halton(S.spheres_c1(xres=48, yres=48, spp=8)))
+    assert_render_matches_oracle(pkg, gpu, oracle, *_halton(S.ganesha_scale(n=24, xres=64, yres=48, spp=8)))
+    assert_render_matches_oracle(pkg, gpu, oracle, *_halton(S.material_zoo(xres=64, yres=48, spp=8)))
+    assert_render_matches_oracle(pkg, gpu, oracle, *_halton(S.spheres_c1(xres=48, yres=48, spp=8)))
 
 
 @pytest.mark.gpu
 def test_gpu_halton_with_textures_thin_lens_and_subsurface(pkg, gpu, oracle):
-    from test_gpu_parity import _compare_render
     S = pkg.scenes
     b = S.textured(xres=64, yres=48, spp=4, trilinear=False)
     b.cam.update(lensradius=0.05, focaldistance=4.0)   # lens sample re-derived for the camera-ray differentials
-    _compare_render(pkg, gpu, oracle, *_halton(b), rtol=2e-5, atol=1e-6)
-    sd, rp = _halton(S.subsurface_c5(xres=48, yres=32, spp=4))   # probe chains are walked twice on the device: radiometry + the
-    g = pkg.Scene(gpu, sd); orc = oracle.scene(sd)               # counters that do not count the re-walk (see test_gpu_parity)
-    film, ref = g.render(rp), orc.render(rp, nthreads=4)
-    gc, oc = g.counters(), orc.counters()
-    for k in ("camera_rays", "shadow_tests", "path_length_hist", "film_splats"): assert gc[k] == oc[k], k
-    assert np.array_equal(film[..., 3], ref[..., 3])
-    np.testing.assert_allclose(film[..., :3], ref[..., :3], rtol=2e-6, atol=1e-7)
+    assert_render_matches_oracle(pkg, gpu, oracle, *_halton(b), rtol=2e-5, atol=1e-6)
+    # probe chains: the device's re-walk of a long chain is left out of its counters (see test_gpu_parity)
+    assert_render_matches_oracle(pkg, gpu, oracle, *_halton(S.subsurface_c5(xres=48, yres=32, spp=4)), resolved=None)
     b = S.ganesha_scale(n=16, xres=48, yres=32, spp=4); b.sample_at_pixel_center = True
-    film, ref = _compare_render(pkg, gpu, oracle, *_halton(b))
+    assert_render_matches_oracle(pkg, gpu, oracle, *_halton(b))
 
 
 @pytest.mark.gpu
@@ -178,7 +172,4 @@ WorldEnd
     fs = pkg.frontend.FrontScene(text=text)
     rp = fs.render_params()
     assert rp.sampler_type == pkg._abi.PT_SAMPLER_HALTON and rp.spp == 16
-    g = pkg.Scene(gpu, fs); orc = oracle.scene(fs)
-    film = g.render(rp); ref = orc.render(rp, nthreads=4)
-    assert np.array_equal(film[..., 3], ref[..., 3])
-    np.testing.assert_allclose(film[..., :3], ref[..., :3], rtol=2e-6, atol=1e-7)
+    assert_render_matches_oracle(pkg, gpu, oracle, fs, rp, resolved=None)

@@ -5,6 +5,7 @@ The reference's own HLBVH path is broken / timing dependent (bvh.rs:424-455,488-
   * rendering through it matches the oracle (bit-exact counters) and the SAH render (same hits)."""
 import numpy as np
 import pytest
+from parity import assert_render_matches_oracle, assert_same_film
 
 
 def _hlbvh(sd, pkg):
@@ -187,12 +188,10 @@ def test_gpu_hlbvh_large_mesh_and_leaf_sizes(pkg, gpu, oracle, maxp):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["ganesha", "instances", "spheres"])
 def test_gpu_hlbvh_render_matches_oracle_and_sah(pkg, gpu, oracle, name):
-    from test_gpu_parity import _compare_render
     sd, rp = _scenes(pkg)[name]
     sah_film = pkg.Scene(gpu, sd).render(rp)
-    film, ref = _compare_render(pkg, gpu, oracle, _hlbvh(sd, pkg), rp)
-    assert np.array_equal(film[..., 3], sah_film[..., 3])
-    np.testing.assert_allclose(film[..., :3], sah_film[..., :3], rtol=2e-5, atol=1e-6)   # same hits; only the film's atomic order differs
+    film = assert_render_matches_oracle(pkg, gpu, oracle, _hlbvh(sd, pkg), rp)[0]
+    assert_same_film(film, sah_film, rtol=2e-5, atol=1e-6)   # same hits; only the film's atomic order differs
 
 
 @pytest.mark.gpu
@@ -207,4 +206,4 @@ def test_gpu_hlbvh_through_the_front_end(pkg, gpu, tmp_path):
     assert fs_h.desc().split_method == pkg._abi.PT_SPLIT_HLBVH and fs_s.desc().split_method == pkg._abi.PT_SPLIT_SAH
     rp = fs_s.render_params()
     a = pkg.Scene(gpu, fs_s).render(rp); b = pkg.Scene(gpu, fs_h).render(fs_h.render_params())
-    np.testing.assert_allclose(a[..., :3], b[..., :3], rtol=2e-5, atol=1e-6)
+    assert_same_film(a, b, rtol=2e-5, atol=1e-6, weights=2e-5)

@@ -5,14 +5,9 @@ PT_LS_SPATIAL does that too when voxels x lights is large (include/mi355pt.h: Pt
 about to be shaded name their voxels (k_light_touch), the new ones are computed by one k_light_grid_contrib launch. The content of a
 voxel is a pure function of the voxel, so the two forms must give the same counters and films, and the first-touch form == the oracle
 on a scene whose emissive mesh makes 50 000 lights (every emissive triangle is one, api.rs:1531-1546)."""
-import os
-
 import numpy as np
 import pytest
-from conftest import ckeys
-
-COUNTERS = ("camera_rays", "intersect_tests", "shadow_tests", "bvh_nodes_visited", "triangle_tests", "sphere_tests", "path_length_hist", "film_splats",
-            "zero_radiance_paths_num", "zero_radiance_paths_den", "sanitized_nan", "sanitized_negative", "sanitized_infinite", "reference_asserts")
+from parity import ORACLE_THREADS, assert_render_matches_oracle, assert_same_film, assert_same_render
 
 
 def test_oracle_treats_the_forced_forms_as_spatial(pkg, oracle):
@@ -35,7 +30,6 @@ def test_first_touch_voxels_equal_the_precomputed_grid(pkg, gpu, oracle, scene):
     atomics; the lazy form also equals the oracle. zoo: every material class; garden: instances + spheres; fog: volpath (medium
     vertices name their voxel from ray.o + t d); skin: BSSRDF exit points (named after the probe launch)."""
     A = pkg._abi
-    from test_gpu_parity import _compare_render
     make = {"zoo": lambda: pkg.scenes.material_zoo(n=12, xres=64, yres=48, spp=4), "garden": lambda: pkg.scenes.instanced_garden(xres=64, yres=48, spp=4),
             "fog": lambda: pkg.scenes.foggy_room(xres=48, yres=36, spp=4), "skin": lambda: pkg.scenes.subsurface_c5(n=16, xres=48, yres=36, spp=4)}[scene]
     sd, rp = make().world_end()
@@ -45,12 +39,10 @@ def test_first_touch_voxels_equal_the_precomputed_grid(pkg, gpu, oracle, scene):
     rp.light_strategy = A.PT_LS_SPATIAL_LAZY
     fl = g.render(rp); cl = g.counters()
     assert "light_touch" in [k["name"] for k in g.kernel_stats()]
-    for k in ckeys(COUNTERS): assert ce[k] == cl[k], (k, ce[k], cl[k])
-    assert np.array_equal(fe[..., 3], fl[..., 3])
-    np.testing.assert_allclose(fl[..., :3], fe[..., :3], rtol=2e-6, atol=1e-7)
+    assert_same_render(fl, fe, cl, ce)
     fl2 = g.render(rp)          # second render: the voxels are there already, nothing is requested
-    np.testing.assert_allclose(fl2[..., :3], fl[..., :3], rtol=2e-6, atol=1e-7)
-    _compare_render(pkg, gpu, oracle, sd, rp)
+    assert_same_film(fl2, fl)
+    assert_render_matches_oracle(pkg, gpu, oracle, sd, rp)
 
 
 @pytest.mark.gpu
@@ -65,8 +57,6 @@ def test_fifty_thousand_emissive_triangles_under_the_spatial_strategy(pkg, gpu, 
     film = g.render(rp); gc = g.counters()
     stats = {k["name"]: k for k in g.kernel_stats()}
     assert stats["light_touch"]["launches"] > 0 and stats["light_grid"]["launches"] > 0      # the first-touch form was chosen by itself
-    ref = orc.render(rp, nthreads=min(16, os.cpu_count() or 1)); oc = orc.counters()
-    for k in ckeys(COUNTERS): assert gc[k] == oc[k], (k, gc[k], oc[k])
-    assert np.array_equal(film[..., 3], ref[..., 3])
-    np.testing.assert_allclose(film[..., :3], ref[..., :3], rtol=2e-6, atol=1e-7)
+    ref = orc.render(rp, nthreads=ORACLE_THREADS)
+    assert_same_render(film, ref, gc, orc.counters())
     assert film[..., :3].sum() > 0

@@ -9,7 +9,7 @@ import ctypes as C
 import json
 import numpy as np
 import pytest
-from conftest import ckeys
+from parity import assert_same_film, assert_same_render
 
 
 def test_replica_tile_shards_partition_the_callers_shard(pkg):
@@ -52,10 +52,7 @@ def test_three_replicas_on_one_device_equal_the_plain_render(pkg, gpu, scene):
     multi = pkg.MultiScene(gpu, sd, [0, 0, 0])
     film = multi.render(rp)
     mc = multi.counters()
-    for k in ckeys(("camera_rays", "intersect_tests", "shadow_tests", "bvh_nodes_visited", "triangle_tests", "path_length_hist", "film_splats")):
-        assert mc[k] == rc[k], (k, mc[k], rc[k])
-    assert np.array_equal(film[..., 3], ref[..., 3])
-    np.testing.assert_allclose(film[..., :3], ref[..., :3], rtol=2e-6, atol=1e-7)
+    assert_same_render(film, ref, mc, rc)
     # the device-pointer form adds into a film on the first device
     import torch
     dfilm = torch.zeros(film.shape, dtype=torch.float32, device="cuda:0")
@@ -63,13 +60,11 @@ def test_three_replicas_on_one_device_equal_the_plain_render(pkg, gpu, scene):
     torch.cuda.synchronize()
     # (weights bit for bit; radiance within the reordering of float atomics: a Sobol' sample that sits exactly on a pixel corner -- every
     #  pixel's sample 0 -- splats onto four pixels, three of them through atomics whose order against the owner's additions is not defined)
-    assert np.array_equal(dfilm.cpu().numpy()[..., 3], film[..., 3])
-    np.testing.assert_allclose(dfilm.cpu().numpy()[..., :3], film[..., :3], rtol=2e-6, atol=1e-7)
+    assert_same_film(dfilm.cpu().numpy(), film)
     # nested inside a 2-process launch: rank 1 of 2, split over the three replicas
     rp.tile_rank, rp.tile_world = 1, 2
     a = multi.render(rp); b = single.render(rp)
-    assert np.array_equal(a[..., 3], b[..., 3])
-    np.testing.assert_allclose(a[..., :3], b[..., :3], rtol=2e-6, atol=1e-7)
+    assert_same_film(a, b)
     assert len(multi.kernel_stats(2)) > 0
     tm = multi.timing()
     assert len(tm["render_ms"]) == 3 and all(x > 0 for x in tm["render_ms"]) and tm["merge_ms"] > 0 and tm["copy_ms"] == [0.0, 0.0, 0.0]   # replicas on the first device are summed in place
@@ -90,10 +85,8 @@ def test_eight_replicas_and_two_film_sizes_on_one_multiscene(pkg, gpu):
     for rp in (rp_small, rp_big, rp_small):
         ref = single.render(rp); rc = single.counters()
         film = multi.render(rp); mc = multi.counters()
-        for k in ckeys(("camera_rays", "intersect_tests", "shadow_tests", "bvh_nodes_visited", "triangle_tests", "path_length_hist", "film_splats")):
-            assert mc[k] == rc[k], (k, mc[k], rc[k])
-        assert film.shape == ref.shape and np.array_equal(film[..., 3], ref[..., 3])
-        np.testing.assert_allclose(film[..., :3], ref[..., :3], rtol=2e-6, atol=1e-7)
+        assert film.shape == ref.shape
+        assert_same_render(film, ref, mc, rc)
 
 
 @pytest.mark.gpu
@@ -105,7 +98,7 @@ def test_a_replica_that_cannot_be_created_fails_the_call_and_leaks_nothing(pkg, 
         pkg.MultiScene(gpu, sd, [0, 0, 99, 0])
     ref = pkg.Scene(gpu, sd).render(rp)
     film = pkg.MultiScene(gpu, sd, [0, 0]).render(rp)
-    assert np.array_equal(film[..., 3], ref[..., 3])
+    assert_same_film(film, ref)
 
 
 @pytest.mark.gpu
@@ -122,10 +115,7 @@ def test_distinct_devices_equal_the_plain_render(pkg, gpu):
     ref = single.render(rp); rc = single.counters()
     multi = pkg.MultiScene(gpu, sd, devs)
     film = multi.render(rp); mc = multi.counters()
-    for k in ckeys(("camera_rays", "intersect_tests", "shadow_tests", "bvh_nodes_visited", "triangle_tests", "path_length_hist", "film_splats")):
-        assert mc[k] == rc[k], (k, mc[k], rc[k])
-    assert np.array_equal(film[..., 3], ref[..., 3])
-    np.testing.assert_allclose(film[..., :3], ref[..., :3], rtol=2e-6, atol=1e-7)
+    assert_same_render(film, ref, mc, rc)
     tm = multi.timing()
     assert all(c > 0 for c in tm["copy_ms"][1:])
     assert multi.peer_access()[0] == "same device" and all(p in ("peer access", "staged through the host") for p in multi.peer_access()[1:])
@@ -176,5 +166,4 @@ def test_launcher_form_of_bench_runs_with_several_ranks_on_one_gpu(pkg, gpu, tmp
     sd, rp = pkg.scenes.ganesha_scale(n=64, xres=xres, yres=yres, spp=spp).world_end()
     ref = pkg.Scene(gpu, sd).render(rp)
     assert merged.shape == ref.shape
-    assert np.array_equal(merged[..., 3], ref[..., 3])
-    np.testing.assert_allclose(merged[..., :3], ref[..., :3], rtol=2e-6, atol=1e-7)
+    assert_same_film(merged, ref)

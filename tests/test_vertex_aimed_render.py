@@ -26,7 +26,7 @@ import time
 import numpy as np
 import pytest
 
-from conftest import ckeys
+from parity import assert_same_hits, assert_same_render
 
 W, H = 128, 96              # film; the aimed pixels are those with x < AIM_X (the sphere of variant 1 sits to their right)
 AIM_X = 96
@@ -310,8 +310,6 @@ def test_grid_and_edge_scenes_hold_on_the_oracle(pkg, oracle, kind):
 # kernel does not change with the tree): 30 instances, about 230 000 aimed primary rays per walk.
 
 INSTANCES = ([(k, 0, t) for k in KINDS for t in TREES] + [(k, 1, "sah1") for k in KINDS] + [(k, 2, "sah4") for k in KINDS] + [(k, 3, "hlbvh") for k in KINDS])
-RENDER_KEYS = ("camera_rays", "intersect_tests", "shadow_tests", "bvh_nodes_visited", "triangle_tests", "zero_radiance_paths_num", "zero_radiance_paths_den",
-               "path_length_hist", "film_splats", "sanitized_nan", "sanitized_negative", "sanitized_infinite", "reference_asserts")   # test_gpu_parity._compare_render
 _ORACLE_RUNS = {}   # the oracle's side of an instance does not depend on the walk: made once, used by both
 
 
@@ -322,15 +320,17 @@ def _oracle_run(pkg, oracle, kind, geometry, tree):
         orc = oracle.scene(sd)
         inf = np.full(len(info["o"]), np.inf, np.float32)
         oracle.lib.orc_reset_tmax_raises()
-        tr = orc.trace_closest(info["o"], info["d"], inf)
+        tr = orc.trace_closest(info["o"], info["d"], inf); tr_counters = orc.counters()
         raises = oracle.lib.orc_tmax_raises()
         check_aimed_hits(info, tr[0], tr[1])
         ta = ((info["point"] - info["o"].astype(np.float64)) * info["d"]).sum(1) / (info["d"].astype(np.float64) ** 2).sum(1)
         lo, hi = any_hit_tmax(ta)
         film = orc.render(rp, nthreads=8)
-        counters = orc.counters()   # (before the trace_any calls, which set the scene's counters anew)
-        _ORACLE_RUNS[key] = dict(sd=sd, rp=rp, info=info, trace=tr, lo=lo, hi=hi, any_lo=orc.trace_any(info["o"], info["d"], lo),
-                                 any_hi=orc.trace_any(info["o"], info["d"], hi), film=film, counters=counters, raises=raises)
+        counters = orc.counters()   # (every call sets the scene's counters anew)
+        any_lo = orc.trace_any(info["o"], info["d"], lo); lo_counters = orc.counters()
+        any_hi = orc.trace_any(info["o"], info["d"], hi); hi_counters = orc.counters()
+        _ORACLE_RUNS[key] = dict(sd=sd, rp=rp, info=info, trace=tr, trace_counters=tr_counters, lo=lo, hi=hi, any_lo=any_lo, any_hi=any_hi,
+                                 lo_counters=lo_counters, hi_counters=hi_counters, film=film, counters=counters, raises=raises)
         orc.close()
     return _ORACLE_RUNS[key]
 
@@ -342,13 +342,8 @@ def test_vertex_aimed_render_matches_oracle(pkg, gpu, oracle, kind, geometry, tr
     R = _oracle_run(pkg, oracle, kind, geometry, tree)
     info = R["info"]
     g = pkg.Scene(gpu, R["sd"])
-    # parity of the render at the standard of test_gpu_parity._compare_render
     film = g.render(R["rp"])
-    gc, oc, ref = g.counters(), R["counters"], R["film"]
-    for k in ckeys(RENDER_KEYS):
-        assert gc[k] == oc[k], (k, gc[k], oc[k])
-    assert np.array_equal(film[..., 3], ref[..., 3])
-    np.testing.assert_allclose(film[..., :3], ref[..., :3], rtol=2e-6, atol=1e-7)
+    assert_same_render(film, R["film"], g.counters(), R["counters"])
     # the trace launch of the render is the mixed kernel of the MODE this variant was built for
     traces = {k["kernel"] for k in g.kernel_stats() if k["kernel"].startswith("k_trace<")}
     assert any(k.startswith(f"k_trace<2, {info['mode']}, false, ") for k in traces), traces
@@ -359,14 +354,12 @@ def test_vertex_aimed_render_matches_oracle(pkg, gpu, oracle, kind, geometry, tr
     check_film(info, g.resolve(film), int(((ap >= info["occluder"][0]) & (ap < info["occluder"][1])).sum()))
     # pt_trace_closest on the aimed rays: the float64 checks, and the oracle's (prim, t, b) bit for bit
     inf = np.full(len(info["o"]), np.inf, np.float32)
-    gp, gt, gb = g.trace_closest(info["o"], info["d"], inf)
-    worst, _ = check_aimed_hits(info, gp, gt)
-    op, ot, ob = R["trace"]
-    bad = np.nonzero((gp != op) | (gt.view(np.uint32) != ot.view(np.uint32)) | (gb.view(np.uint32) != ob.view(np.uint32)).any(1))[0]
-    assert len(bad) == 0, (len(bad), [tuple(info["pix"][i]) for i in bad[:5]])
+    gh = g.trace_closest(info["o"], info["d"], inf)
+    worst, _ = check_aimed_hits(info, gh[0], gh[1])
+    assert_same_hits(gh, R["trace"], g.counters(), R["trace_counters"])
     # pt_trace_any just short of / just past the aimed point
-    lo, hi = g.trace_any(info["o"], info["d"], R["lo"]), g.trace_any(info["o"], info["d"], R["hi"])
+    lo = g.trace_any(info["o"], info["d"], R["lo"]); assert_same_hits(lo, R["any_lo"], g.counters(), R["lo_counters"])
+    hi = g.trace_any(info["o"], info["d"], R["hi"]); assert_same_hits(hi, R["any_hi"], g.counters(), R["hi_counters"])
     assert not lo.any() and hi.all()
-    assert np.array_equal(lo, R["any_lo"]) and np.array_equal(hi, R["any_hi"])
     g.close()
-    print(f"\n{kind} m{geometry} {tree}: {len(gp)} aimed rays, oracle t_max raises {R['raises']} (trace), worst |dt|/t {worst:.2f} 2^-23, {time.perf_counter() - t0:.2f} s")
+    print(f"\n{kind} m{geometry} {tree}: {len(gh[0])} aimed rays, oracle t_max raises {R['raises']} (trace), worst |dt|/t {worst:.2f} 2^-23, {time.perf_counter() - t0:.2f} s")

@@ -5,6 +5,7 @@ forms and against the path integrator, the GPU against the oracle (bit-exact cou
 Material-less interface shells are refused: the reference's own volpath mishandles them (volpath.rs:127-131)."""
 import numpy as np
 import pytest
+from parity import assert_render_matches_oracle
 
 
 def _absorbing_wall(pkg, sigma_a, dist, kind="volpath"):
@@ -198,21 +199,19 @@ WorldEnd
 @pytest.mark.gpu
 @pytest.mark.parametrize("kw", [dict(), dict(g=0.0), dict(g=-0.6, strategy="uniform"), dict(camera_in_fog=False), dict(maxdepth=1)])
 def test_gpu_volpath_matches_oracle(pkg, gpu, oracle, kw):
-    from test_gpu_parity import _compare_render
     sd, rp = pkg.scenes.foggy_room(**kw).world_end()
-    film, ref = _compare_render(pkg, gpu, oracle, sd, rp)
+    film = assert_render_matches_oracle(pkg, gpu, oracle, sd, rp)[0]
     assert film[..., :3].sum() > 0
 
 
 @pytest.mark.gpu
 def test_gpu_volpath_halton_thin_lens_and_no_media(pkg, gpu, oracle):
-    from test_gpu_parity import _compare_render
     b = pkg.scenes.foggy_room(xres=64, yres=48, spp=8); b.sampler = "halton"; b.cam.update(lensradius=0.05, focaldistance=5.0)
-    _compare_render(pkg, gpu, oracle, *b.world_end())
+    assert_render_matches_oracle(pkg, gpu, oracle, *b.world_end())
     b = pkg.scenes.material_zoo(xres=64, yres=48, spp=8); b.integ["kind"] = "volpath"     # volpath over a scene without media
-    _compare_render(pkg, gpu, oracle, *b.world_end())
+    assert_render_matches_oracle(pkg, gpu, oracle, *b.world_end())
     b = pkg.scenes.textured(xres=64, yres=48, spp=4); b.integ["kind"] = "volpath"
-    _compare_render(pkg, gpu, oracle, *b.world_end(), rtol=2e-5, atol=1e-6)
+    assert_render_matches_oracle(pkg, gpu, oracle, *b.world_end(), rtol=2e-5, atol=1e-6)
     sd, rp = _absorbing_wall(pkg, (0.1, 0.5, 1.5), 2.5)
     g = pkg.Scene(gpu, sd)
     rgb = g.resolve(g.render(rp)).reshape(-1, 3).mean(axis=0)
@@ -244,11 +243,10 @@ def test_oracle_subsurface_next_to_shells_and_grid_media(pkg, oracle, grid):
 @pytest.mark.gpu
 @pytest.mark.parametrize("grid", [False, True])
 def test_gpu_subsurface_next_to_shells_and_grid_media_matches_oracle(pkg, gpu, oracle, grid):
-    from test_gpu_parity import _compare_render
     b = _sss_with_shell(pkg, grid=grid, xres=48, yres=36, spp=8)
-    _compare_render(pkg, gpu, oracle, *b.world_end())
+    assert_render_matches_oracle(pkg, gpu, oracle, *b.world_end())
     b = _sss_with_shell(pkg, grid=grid, xres=32, yres=24, spp=4, sampler="halton")
-    _compare_render(pkg, gpu, oracle, *b.world_end())
+    assert_render_matches_oracle(pkg, gpu, oracle, *b.world_end())
 
 
 # ---- GridDensityMedium (media/grid.rs) ----------------------------------------------------------------
@@ -349,9 +347,8 @@ def test_smoke_room_renders_on_the_oracle(pkg, oracle):
 def test_gpu_grid_medium_matches_oracle(pkg, gpu, oracle, kw):
     """GridDensityMedium on the device: delta tracking in k_medium_route, ratio tracking on shadow / MIS rays in the second stage of
     the vertex (PF_STAGE_B) -- same sampler dimensions in the same order as the oracle, so counters are exact and the film agrees."""
-    from test_gpu_parity import _compare_render
     sd, rp = pkg.scenes.smoke_room(xres=48, yres=36, **kw).world_end()
-    film, ref = _compare_render(pkg, gpu, oracle, sd, rp)
+    film = assert_render_matches_oracle(pkg, gpu, oracle, sd, rp)[0]
     assert film[..., :3].sum() > 0
 
 
@@ -359,7 +356,6 @@ def test_gpu_grid_medium_matches_oracle(pkg, gpu, oracle, kw):
 def test_gpu_grid_medium_with_a_homogeneous_medium_and_closed_form(pkg, gpu, oracle):
     """A grid medium next to a homogeneous one (the juice in foggy_room's glass sphere stays homogeneous, the room's fog becomes a grid),
     and the absorbing-grid closed form evaluated on the device."""
-    from test_gpu_parity import _compare_render
     b = pkg.scenes.foggy_room(xres=48, yres=36, spp=8)
     b.sampler = "halton"
     dens = np.random.default_rng(2).uniform(0.2, 1.0, (4, 4, 4)).astype(np.float32)
@@ -371,7 +367,7 @@ def test_gpu_grid_medium_with_a_homogeneous_medium_and_closed_form(pkg, gpu, ora
     b.make_named_medium("gridfog", sigma_a=(0.05, 0.05, 0.05), sigma_s=(0.2, 0.2, 0.2), g=0.3, density=dens, p0=(-6.0, -0.5, -6.0), p1=(6.0, 5.0, 6.0))
     b.ctm = b.ctm_saved
     b.media[0] = b.media[-1]; b.media.pop(); b.named_media.pop("gridfog")
-    _compare_render(pkg, gpu, oracle, *b.world_end())
+    assert_render_matches_oracle(pkg, gpu, oracle, *b.world_end())
     dens = np.random.default_rng(3).uniform(0.1, 1.0, (5, 3, 4)).astype(np.float32)
     p0, p1 = (-1.0, -1.0, -2.0), (1.0, 1.0, -0.5)
     sd, rp = _grid_wall(pkg, 1.1, 0.0, 3.0, dens, p0, p1, spp=4096)
@@ -384,11 +380,10 @@ def test_gpu_grid_medium_with_a_homogeneous_medium_and_closed_form(pkg, gpu, ora
 def test_gpu_grid_medium_with_spectrally_varying_coefficients_renders_with_channel_zero(pkg, gpu, oracle, capfd):
     """grid.rs:46-52: `sigma_t = (sigma_a + sigma_s)[0]`, a spectrally varying coefficient is only reported (error!) -- the library used to
     refuse such a scene; now it renders, and exactly what the oracle's restatement of grid.rs renders."""
-    from test_gpu_parity import _compare_render
     b = pkg.scenes.smoke_room(xres=40, yres=30, spp=8)
     for k in range(3):
         b.media[0].sigma_a[k] = 0.3 + 0.2 * k; b.media[0].sigma_s[k] = 1.0 + 0.5 * k
-    film, ref = _compare_render(pkg, gpu, oracle, *b.world_end())
+    film = assert_render_matches_oracle(pkg, gpu, oracle, *b.world_end())[0]
     assert film[..., :3].sum() > 0
     assert "spectrally uniform" in capfd.readouterr().err
 
@@ -455,9 +450,8 @@ def test_gpu_media_in_material_less_shells_match_oracle(pkg, gpu, oracle, kw):
     (vol_chain_step: one traced segment per wavefront iteration, the shadow chain before the MIS chain so that grid media draw their
     ratio-tracking dimensions in the reference's order); films, every work counter and the path-length histogram (with the paths that
     volpath.rs:152-156's wrapping `bounces -= 1` ends) equal the oracle's."""
-    from test_gpu_parity import _compare_render
     sd, rp = pkg.scenes.shell_media(xres=56, yres=40, spp=8, **kw).world_end()
-    film, ref = _compare_render(pkg, gpu, oracle, sd, rp)
+    film = assert_render_matches_oracle(pkg, gpu, oracle, sd, rp)[0]
     assert film[..., :3].sum() > 0
 
 
@@ -493,7 +487,6 @@ def test_gpu_subsurface_under_volpath_matches_oracle(pkg, gpu, oracle, kw):
     """VERDICT r2 missing #5. The probe kernel hands every hit's MediumInterface down the chain (k_trace<.., PROBE>: cur_med), k_bssrdf<.., VOL>
     estimates direct light at the exit point with the media of the selected hit's interface and gives the new ray its medium; the probe's
     samples are drawn as volpath.rs:191 draws them. Films and every counter equal the oracle's."""
-    from test_gpu_parity import _compare_render
     sd, rp = pkg.scenes.subsurface_in_fog(xres=56, yres=40, spp=8, **kw).world_end()
-    film, ref = _compare_render(pkg, gpu, oracle, sd, rp)
+    film = assert_render_matches_oracle(pkg, gpu, oracle, sd, rp)[0]
     assert film[..., :3].sum() > 0

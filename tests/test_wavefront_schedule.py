@@ -9,13 +9,11 @@ import sys
 
 import numpy as np
 import pytest
-from conftest import ckeys, trace_env
+from conftest import trace_env
+from parity import assert_same_film, assert_same_render
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-COUNTERS = ("camera_rays", "intersect_tests", "shadow_tests", "bvh_nodes_visited", "triangle_tests", "sphere_tests", "path_length_hist", "film_splats",
-            "zero_radiance_paths_num", "zero_radiance_paths_den")
 
 _CHILD = r"""
 import json, sys
@@ -35,7 +33,7 @@ for name in ("zoo", "spheres", "instances"):
     film = g.render(rp)
     c = g.counters()
     np.save({out!r} + "/" + name + ".npy", film)
-    out[name] = dict(counters={{k: c[k] for k in {counters!r}}}, stats=sorted(s["name"] for s in g.kernel_stats() if s["launches"]))
+    out[name] = dict(counters=c, stats=sorted(s["name"] for s in g.kernel_stats() if s["launches"]))
 json.dump(out, open({out!r} + "/out.json", "w"))
 """
 
@@ -49,7 +47,7 @@ def test_mixed_traversal_launch_equals_one_launch_per_ray_kind(pkg, gpu, tmp_pat
     """PT_TRACE_SPLIT=1 (read by pt_init, so in a process of its own) traces the three ray kinds of an iteration in three launches, as
     round 1 did; the default traces them in one. Same counters, same weights bit for bit, same radiance up to the order of the film's float atomics; the launch kinds differ."""
     env = trace_env(dict(os.environ, PT_TRACE_SPLIT="1"))
-    code = _CHILD.format(root=ROOT, out=str(tmp_path), counters=COUNTERS)
+    code = _CHILD.format(root=ROOT, out=str(tmp_path))
     r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     split = json.load(open(tmp_path / "out.json"))
@@ -59,11 +57,8 @@ def test_mixed_traversal_launch_equals_one_launch_per_ray_kind(pkg, gpu, tmp_pat
         film = g.render(rp)
         c = g.counters()
         stats = sorted(s["name"] for s in g.kernel_stats() if s["launches"])
-        for k in ckeys(COUNTERS):
-            assert c[k] == split[name]["counters"][k], (name, k)
-        other = np.load(tmp_path / (name + ".npy"))
-        assert np.array_equal(film[..., 3], other[..., 3]), name
-        np.testing.assert_allclose(film[..., :3], other[..., :3], rtol=2e-6, atol=1e-7, err_msg=name)   # (corner samples reach their neighbours through float atomics: order not defined)
+        # (corner samples reach their neighbours through float atomics: order not defined)
+        assert_same_render(film, np.load(tmp_path / (name + ".npy")), c, split[name]["counters"])
         assert "trace" in stats and not {"extend", "extend_mis", "shadow"} & set(stats), stats
         assert {"extend", "shadow"} <= set(split[name]["stats"]) and "trace" not in split[name]["stats"], split[name]["stats"]
 
@@ -74,7 +69,7 @@ def test_film_kernel_that_ends_the_paths_equals_the_miss_pass(pkg, gpu, tmp_path
     path-length histogram, the zero-radiance count and the reference's asserts), same weights bit for bit, same radiance up to the order of the film's corner-sample atomics;
     only the launch kinds differ."""
     env = trace_env(dict(os.environ, PT_FILM_FINAL="0"))
-    code = _CHILD.format(root=ROOT, out=str(tmp_path), counters=COUNTERS)
+    code = _CHILD.format(root=ROOT, out=str(tmp_path))
     r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     old = json.load(open(tmp_path / "out.json"))
@@ -84,11 +79,7 @@ def test_film_kernel_that_ends_the_paths_equals_the_miss_pass(pkg, gpu, tmp_path
         film = g.render(rp)
         c = g.counters()
         st = {s["name"]: s["kernel"] for s in g.kernel_stats() if s["launches"]}
-        for k in ckeys(COUNTERS):
-            assert c[k] == old[name]["counters"][k], (name, k)
-        other = np.load(tmp_path / (name + ".npy"))
-        assert np.array_equal(film[..., 3], other[..., 3]), name
-        np.testing.assert_allclose(film[..., :3], other[..., :3], rtol=2e-6, atol=1e-7, err_msg=name)
+        assert_same_render(film, np.load(tmp_path / (name + ".npy")), c, old[name]["counters"])
         assert "shade_miss" not in st and st["film"].startswith("k_film_final<"), st
         assert "shade_miss" in old[name]["stats"], old[name]["stats"]
 
@@ -106,10 +97,7 @@ def test_pass_size_does_not_change_the_image(pkg, gpu, per_pass):
     b = g.render(rp); cb = g.counters()
     n_pass = [s["launches"] for s in g.kernel_stats() if s["name"] == "generate"][0]
     assert n_pass_auto == 1 and n_pass == -(-8 // per_pass)
-    for k in ckeys(COUNTERS):
-        assert ca[k] == cb[k], k
-    assert np.array_equal(a[..., 3], b[..., 3])
-    np.testing.assert_allclose(a[..., :3], b[..., :3], rtol=1e-6, atol=1e-7)
+    assert_same_render(a, b, ca, cb, rtol=1e-6)
 
 
 def test_specular_materials_have_a_shade_class_of_their_own(pkg, gpu, oracle):
@@ -120,10 +108,7 @@ def test_specular_materials_have_a_shade_class_of_their_own(pkg, gpu, oracle):
     film, ref = g.render(rp), orc.render(rp, nthreads=4)
     st = {s["name"]: s for s in g.kernel_stats() if s["launches"]}
     assert "shade_specular" in st and st["shade_specular"]["kernel"] == "k_shade<1, 1, 2>" and "shade_1lobe" not in st
-    gc, oc = g.counters(), orc.counters()
-    for k in ckeys(COUNTERS):
-        assert gc[k] == oc[k], k
-    np.testing.assert_allclose(film, ref, rtol=3e-6, atol=1e-6)
+    assert_same_render(film, ref, g.counters(), orc.counters(), rtol=3e-6, atol=1e-6, weights=3e-6)
     # the zoo has metal + substrate (one lobe, with NEE), mirror + glass (specular), plastic + rough glass (two lobes) and an uber with a specular term (class 3)
     sd, rp = pkg.scenes.material_zoo(n=16, xres=96, yres=64, spp=4).world_end()
     g = pkg.Scene(gpu, sd); g.render(rp)
@@ -145,11 +130,7 @@ def test_lobe_set_specialised_kernels_are_chosen_per_material_and_change_nothing
     st = {s["name"]: s["kernel"] for s in g.kernel_stats() if s["launches"]}
     assert st["shade_metal"] == "k_shade<1, 0, 3>" and st["shade_plastic"] == "k_shade<2, 0, 4>" and st["shade_uber"] == "k_shade<5, 0, 5>", st
     assert not ({"shade_1lobe", "shade_2lobe", "shade_manylobe"} & set(st)) and st["route"] == "k_route<6, 2048>", st
-    gc, oc = g.counters(), orc.counters()
-    for k in ckeys(COUNTERS):
-        assert gc[k] == oc[k], k
-    assert np.array_equal(film[..., 3], ref[..., 3])
-    np.testing.assert_allclose(film[..., :3], ref[..., :3], rtol=3e-6, atol=1e-6)
+    assert_same_render(film, ref, g.counters(), orc.counters(), rtol=3e-6, atol=1e-6)
     sd2, rp2 = pkg.scenes.country_kitchen_s3(xres=96, yres=64, spp=4, wall_n=6, box_n=3, obj_n=6, mixed=True).world_end()
     g2 = pkg.Scene(gpu, sd2); orc2 = oracle.scene(sd2)
     film2, ref2 = g2.render(rp2), orc2.render(rp2, nthreads=4)
@@ -159,11 +140,7 @@ def test_lobe_set_specialised_kernels_are_chosen_per_material_and_change_nothing
     assert st2["route"] == "k_route<12, 1024>", st2   # nine shade classes + the miss class
     items = {s["name"]: s["items"] for s in g2.kernel_stats() if s["launches"]}
     assert all(items[k] > 0 for k in ("shade_metal", "shade_plastic", "shade_uber", "shade_1lobe", "shade_2lobe", "shade_manylobe", "shade_matte", "shade_specular")), items
-    gc, oc = g2.counters(), orc2.counters()
-    for k in ckeys(COUNTERS):
-        assert gc[k] == oc[k], k
-    assert np.array_equal(film2[..., 3], ref2[..., 3])
-    np.testing.assert_allclose(film2[..., :3], ref2[..., :3], rtol=3e-6, atol=1e-6)
+    assert_same_render(film2, ref2, g2.counters(), orc2.counters(), rtol=3e-6, atol=1e-6)
     code = r"""
 import sys, numpy as np
 sys.path.insert(0, {root!r})
@@ -180,9 +157,7 @@ np.save({out!r}, film)
 """.format(root=ROOT, out=str(tmp_path / "general.npy"))
     r = subprocess.run([sys.executable, "-c", code], env=trace_env(dict(os.environ, PT_SHADE_SPECIALISE="0")), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
-    other = np.load(tmp_path / "general.npy")
-    assert np.array_equal(film[..., 3], other[..., 3])
-    np.testing.assert_allclose(film[..., :3], other[..., :3], rtol=2e-6, atol=1e-7)
+    assert_same_film(film, np.load(tmp_path / "general.npy"))
 
 
 def _uber_ball(pkg, uber):
@@ -213,10 +188,7 @@ def test_uber_without_specular_terms_is_a_two_lobe_material(pkg, gpu, oracle, ub
     film, ref = g.render(rp), orc.render(rp, nthreads=4)
     names = {s["name"] for s in g.kernel_stats() if s["launches"]}
     assert expect_class in names and ({"shade_plastic", "shade_uber", "shade_2lobe", "shade_manylobe"} - {expect_class}).isdisjoint(names), names
-    gc, oc = g.counters(), orc.counters()
-    for k in ckeys(COUNTERS):
-        assert gc[k] == oc[k], k
-    np.testing.assert_allclose(film, ref, rtol=3e-6, atol=1e-6)
+    assert_same_render(film, ref, g.counters(), orc.counters(), rtol=3e-6, atol=1e-6, weights=3e-6)
 
 
 @pytest.mark.parametrize("knobs", [
