@@ -6,8 +6,11 @@ synthetic scene (4,298,312-triangle displaced sphere, matte, quad area light + c
 1920x1080 x 256 spp, PathIntegrator maxdepth 5, Sobol sampler, box filter, spatial light sampling.
 `--config C3|C4|C5` selects the other BASELINE configs built to SURVEY 8(d)'s S3 / S4 / S5 specification
 (pbrt-rust_amd/scenes.py: country_kitchen_s3, ecosystem_s4, dragon_s5) at their named spp (override: --spp).
-The default C2 run on one GPU also renders C3 / C4 / C5 once each (one pass of the pass size) AFTER the headline's timed region and reports
-them under "other_configs" of the same JSON line, so every BASELINE config has a number on the driver's record.
+A plain run does what `value` needs and nothing more: it builds the scene, runs the warm-up and the timed steps, writes --dump-outputs and
+prints the JSON line (roofline and per-kernel figures in it come from the timed steps' own HIP events and the committed PMC record, not from runs
+of their own). `--full` adds the side measurements after the timed region: the CPU baseline (cpu_baseline), the film read-back
+(film_readback_ms, value_with_readback) and, for the default C2 run on one GPU, the 8-rank scaling projection (scaling_projection) and
+one render each of C3 / C4 / C5 (one pass of the pass size) under "other_configs", so every BASELINE config has a number on the record.
 Scene generation, BVH build and upload are outside the timed region. The film stays on the device
 (pt_render's film_is_device path): the 33 MB read-back of SURVEY 8(d)'s definition (0.6 ms over PCIe) is not in `value`;
 for N > 1 the film merge is inside the timed region.
@@ -300,16 +303,18 @@ def measure(pkg, lib, torch, dev, dist, args, config, spp, steps, warmup, device
     if args.dump_outputs and config == args.config:
         dump_outputs(args.dump_outputs, film.cpu().numpy())
 
-    # SURVEY 8(d)'s definition of the metric includes the film read-back: timed apart (pinned host buffer, the 4 x f32 x W x H film of the last step)
+    # --full: SURVEY 8(d)'s definition of the metric includes the film read-back: timed apart (pinned host buffer, the 4 x f32 x W x H film of the last step)
     # and reported beside `value`, which stays the device-resident figure the contract asks for
-    hostbuf = torch.empty((H, W, 4), dtype=torch.float32, pin_memory=True)
-    torch.cuda.synchronize()
-    t_rb = time.perf_counter()
-    for _ in range(3):
-        hostbuf.copy_(film, non_blocking=True)
+    film_readback_ms = None
+    if args.full:
+        hostbuf = torch.empty((H, W, 4), dtype=torch.float32, pin_memory=True)
         torch.cuda.synchronize()
-    film_readback_ms = (time.perf_counter() - t_rb) / 3 * 1e3
-    del hostbuf
+        t_rb = time.perf_counter()
+        for _ in range(3):
+            hostbuf.copy_(film, non_blocking=True)
+            torch.cuda.synchronize()
+        film_readback_ms = (time.perf_counter() - t_rb) / 3 * 1e3
+        del hostbuf
 
     # strong-scaling projection as far as ONE device can tell: rank 0's shard of a `proj_world`-rank job (every proj_world-th 16x16 tile, all of the
     # config's NAMED spp) against full-frame time / proj_world. Fixed per-launch costs and the tail of each traversal launch do not shrink with the shard.
@@ -380,11 +385,11 @@ def measure(pkg, lib, torch, dev, dist, args, config, spp, steps, warmup, device
         "config": {"workload": f"{config}: {workload_desc}; {n_tris} triangles" + (f", {n_inst} instances" if n_inst else "") +
                                f", {args.xres}x{args.yres}x{spp}spp, path maxdepth 5, sobol, box filter, spatial light sampling",
                    "name": config, "triangles": n_tris, "instances": n_inst, "spp": spp, "spp_per_pass": eff_spp_per_pass, "resolution": [args.xres, args.yres],
-                   "film": "stays on the device (no read-back in the timed region; film_readback_ms / value_with_readback give SURVEY 8(d)'s read-back-inclusive figure)",
+                   "film": "stays on the device (no read-back in the timed region; with --full, film_readback_ms / value_with_readback give SURVEY 8(d)'s read-back-inclusive figure)",
                    "parallelism": par},
         "code_hash": code_hash(ROOT),   # tools/code_hash.py: the device sources this line was measured on (tools/check_profiles.py holds committed records against it)
-        "film_readback_ms": round(film_readback_ms, 3),
-        "value_with_readback": round(n_samples / (elapsed / steps + film_readback_ms * 1e-3) / 1e6, 3),
+        **({"film_readback_ms": round(film_readback_ms, 3),
+            "value_with_readback": round(n_samples / (elapsed / steps + film_readback_ms * 1e-3) / 1e6, 3)} if film_readback_ms is not None else {}),
         "roofline": roofline, "cpu_baseline": cpu_baseline,
         **({"scaling_projection": projection} if projection else {}),
         **({"multi_gpu": multi_gpu} if multi_gpu else {}),
@@ -404,7 +409,16 @@ def measure(pkg, lib, torch, dev, dist, args, config, spp, steps, warmup, device
     return out
 
 
-def main():
+def side_measurements(args, world, in_process):
+    """Which side measurements a run makes after its headline's timed region: (projection world or 0, other configs on / off). With --projection /
+    --other-configs "auto" they belong to a --full run of the default C2 workload on one GPU; "on" / "off" decide either way."""
+    default_run = (args.config == "C2" and world == 1 and not in_process and args.sim_world <= 1 and args.spp == 0 and (args.xres, args.yres, args.mesh_n) == (1920, 1080, 1466))
+    proj = 8 if (args.projection == "on" or (args.projection == "auto" and args.full and default_run)) else 0
+    others = world == 1 and (args.other_configs == "on" or (args.other_configs == "auto" and args.full and default_run))
+    return proj, others
+
+
+def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2)
@@ -415,7 +429,9 @@ def main():
     ap.add_argument("--xres", type=int, default=1920)
     ap.add_argument("--yres", type=int, default=1080)
     ap.add_argument("--spp-per-pass", type=int, default=0)
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the cpu_baseline sample (0 disables)")
+    ap.add_argument("--full", action="store_true", help="also the side measurements a plain run leaves out: cpu_baseline, the film read-back and, for the default C2 run "
+                    "on one GPU, scaling_projection and other_configs")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: target CPU time of the cpu_baseline sample (0 disables)")
     ap.add_argument("--dump-image", default="")
     ap.add_argument("--sim-rank", type=int, default=0, help="with --sim-world: which rank's shard")
     ap.add_argument("--sim-world", type=int, default=0, help="single-GPU study: render rank 0's shard of an N-rank job (value is then this rank's share only)")
@@ -424,8 +440,13 @@ def main():
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"], help="launcher form: nccl (= RCCL, one GPU per rank) or gloo (film staged through the host; ranks may share a GPU: rehearsal on a one-GPU box)")
     ap.add_argument("--dump-film", default="", help="rank 0 writes the (merged) film of the last step as .npy")
     ap.add_argument("--dump-outputs", default="", metavar="DIR", help="rank 0 writes the (merged) film of the last timed step as DIR/film.npy (float32, at most 64 MB: a fixed sample of a larger film)")
-    ap.add_argument("--projection", default="auto", choices=["auto", "on", "off"], help="scaling_projection: rank 0's shard of an 8-rank job at the named spp, for the headline and for C4 / C5 (auto: default C2 run on one GPU)")
-    ap.add_argument("--other-configs", default="auto", choices=["auto", "on", "off"], help="after the headline, one step (one wavefront pass) each of C3 / C4 / C5 under 'other_configs' (auto: default C2 run on one GPU)")
+    ap.add_argument("--projection", default="auto", choices=["auto", "on", "off"], help="scaling_projection: rank 0's shard of an 8-rank job at the named spp, for the headline and for C4 / C5 (auto: --full default C2 run on one GPU)")
+    ap.add_argument("--other-configs", default="auto", choices=["auto", "on", "off"], help="after the headline, one step (one wavefront pass) each of C3 / C4 / C5 under 'other_configs' (auto: --full default C2 run on one GPU)")
+    return ap
+
+
+def main():
+    ap = parser()
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -462,12 +483,9 @@ def main():
         else:
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
 
-    default_run = (args.config == "C2" and world == 1 and not in_process and args.sim_world <= 1 and args.spp == 0 and (args.xres, args.yres, args.mesh_n) == (1920, 1080, 1466))
-    proj = 8 if (args.projection == "on" or (args.projection == "auto" and default_run)) else 0
-    out = measure(pkg, lib, torch, dev, dist, args, args.config, args.spp, args.steps, args.warmup, devices, in_process, rank, world, want_cpu_baseline=True, proj_world=proj)
-    others = args.other_configs == "on" or (args.other_configs == "auto" and args.config == "C2" and world == 1 and not in_process and args.sim_world <= 1
-                                             and args.spp == 0 and (args.xres, args.yres, args.mesh_n) == (1920, 1080, 1466))
-    if out is not None and others and world == 1:
+    proj, others = side_measurements(args, world, in_process)
+    out = measure(pkg, lib, torch, dev, dist, args, args.config, args.spp, args.steps, args.warmup, devices, in_process, rank, world, want_cpu_baseline=args.full, proj_world=proj)
+    if out is not None and others:
         oc = {}
         for cfg, cspp in OTHER_CONFIG_SPP.items():
             if cfg == args.config:

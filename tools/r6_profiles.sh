@@ -27,7 +27,7 @@ for l in open('$O/full_frame_parity.jsonl'):
 final)
   O=gpurun_out/r6/final; mkdir -p $O
   echo "== GPU tests"; timeout -k 10 1100 python -m pytest tests -m gpu -q --durations=12 > $O/gpu_tests.log 2>&1; tail -n 16 $O/gpu_tests.log
-  echo "== bench (driver form)"; timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+  echo "== bench (driver form)"; timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err
   python3 - $O/bench.json <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().split("\n")[-1])
@@ -39,7 +39,7 @@ print('projection', d.get('scaling_projection'))
 print({c:(v.get('value'),v.get('ms_per_step'),v.get('hbm_frac'),v.get('scaling_projection',{}).get('efficiency')) for c,v in d.get('other_configs',{}).items()})
 PY
   for C in C3 C4 C5; do
-    timeout -k 10 500 python3 bench.py --config $C --steps 1 --warmup 1 --cpu-seconds 8 --projection off > $O/bench_$C.json 2>> $O/bench.err
+    timeout -k 10 500 python3 bench.py --config $C --steps 1 --warmup 1 --full --cpu-seconds 8 --projection off > $O/bench_$C.json 2>> $O/bench.err
     python3 -c "
 import json;d=json.loads(open('$O/bench_$C.json').read().strip().split('\n')[-1]);r=d['roofline'];print('$C', d['value'], d['ms_per_step'], d['config']['spp_per_pass'], r['kernel'], 'frac', r['frac'], 'algo/peak', r['algorithmic_over_hbm_peak'], 'cpu', d['cpu_baseline']['value'] if d['cpu_baseline'] else None)"
   done
