@@ -20,51 +20,85 @@ def build(verbose=False):
     return LIB_PATH
 
 
+# orc_* functions that mirror a pt_* entry point of include/mi355pt.h: their signature is the one _abi.ENTRY_POINTS declares
+_MIRRORED = ("pt_scene_create", "pt_scene_destroy", "pt_scene_bvh_info", "pt_scene_bvh_read", "pt_get_counters", "pt_film_resolve",
+             "pt_trace_closest", "pt_trace_any", "pt_sobol_samples", "pt_halton_samples", "pt_camera_rays")
+
+
+def signatures(A, AO):
+    """{name: (restype, argtypes)} of every orc_* function liboracle.so exports (tests/test_oracle_binding.py holds the two sets equal).
+    A / AO: the ctypes mirrors of include/mi355pt.h / mi355ao.h."""
+    f, d, i, u32, u64, vp = C.c_float, C.c_double, C.c_int, C.c_uint32, C.c_uint64, C.c_void_p
+    fp, u32p, i32p = A.fp, A.u32p, A.i32p
+    ip, dp, rpp = C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(A.PtRenderParams)
+    tp, sp = C.POINTER(A.PtBSSRDFTable), C.POINTER(A.PtSphere)
+    sig = {k.replace("pt_", "orc_", 1): A.ENTRY_POINTS[k] for k in _MIRRORED}
+    sig.update({
+        # the render path and its parity API (ref_render.cpp)
+        "orc_load_tables": (i, [C.c_char_p]),
+        "orc_render": (i, [vp, rpp, fp, i]),
+        "orc_ao_render": (i, [vp, rpp, C.POINTER(AO.PtAOParams), fp, i]),
+        "orc_last_render_seconds": (d, [vp]),
+        "orc_tmax_raises": (u64, []),      # triangle hits that raised t_max (ref_scene.h g_tmax_raises)
+        "orc_reset_tmax_raises": (None, []),
+        # reference-test loops (ref_kats.cpp)
+        "orc_test_efloat": (i, [i, i, ip]),
+        "orc_test_float_bits": (i, [i, ip]),
+        "orc_test_scrambled_radical_inverse": (i, [i, dp]),
+        "orc_test_bitops": (i, []),
+        "orc_test_generator_matrix": (i, []),
+        "orc_test_hg_sampling_match": (d, []),
+        "orc_test_hg_orientation": (None, [f, ip, ip]),
+        "orc_test_hg_normalized": (None, [dp]),
+        # function probes (ref_kats.cpp)
+        "orc_sobol_sample_float": (f, [u64, i, u32]),
+        "orc_radical_inverse": (f, [i, u64]),
+        "orc_radical_inverse_any": (f, [u32, u64]),
+        "orc_halton_permutation": (u32, [u32, C.POINTER(C.c_uint16)]),
+        "orc_next_float_up": (f, [f]),
+        "orc_next_float_down": (f, [f]),
+        "orc_find_interval": (i, [i, fp, f]),
+        "orc_rng_u32_stream": (u32, [u64, i, u32, u32p, fp]),
+        "orc_dist1d_sample_discrete": (i, [fp, i, f, fp, fp]),
+        "orc_dist1d_discrete_pdf": (f, [fp, i, i]),
+        "orc_dist1d_sample_continuous": (f, [fp, i, f, fp, ip]),
+        "orc_dm_sin": (f, [f]),
+        "orc_dm_cos": (f, [f]),
+        "orc_dm_acos": (f, [f]),
+        "orc_dm_atan2": (f, [f, f]),
+        "orc_dm_log": (f, [f]),
+        "orc_offset_ray_origin": (None, [fp] * 5),
+        "orc_bssrdf_sr": (i, [tp, fp, fp, f, u32, fp, fp, fp]),
+        "orc_bssrdf_sample_sr": (i, [tp, fp, fp, f, i, u32, fp, fp]),
+        "orc_catmull_rom_weights": (i, [i, fp, f, ip, fp]),
+        "orc_bssrdf_sw": (f, [f, f]),
+        "orc_light_sample_li": (i, [vp, u32, fp, fp, fp, u32, fp, fp, fp, fp]),
+        "orc_light_pdf_li": (i, [vp, u32, fp, fp, fp, u32, fp, fp]),
+        "orc_bsdf_eval": (i, [vp, u32, u32, fp, fp, fp, fp, fp, fp, fp, fp, i32p, i32p]),
+        # shape loops and probes (ref_kats_shapes.cpp)
+        "orc_test_triangle_sampling": (i, [i, i, dp]),
+        "orc_test_triangle_solid_angle": (i, [i, i, dp]),
+        "orc_test_sphere_solid_angle": (i, [sp, i, dp]),
+        "orc_test_disk_solid_angle": (i, [sp, i, dp]),
+        "orc_test_triangle_watertight": (i, [i, i, fp, u32p, fp, fp, ip]),
+        "orc_test_partial_sphere_normal": (i, [i, ip, dp]),
+        "orc_test_triangle_reintersect": (i, [i, i, ip]),
+        "orc_test_sphere_reintersect": (i, [i, i, i, ip]),
+        "orc_tri_intersect": (i, [vp, u32, fp, fp, f, fp, fp, fp, fp, fp]),
+        "orc_tri_intersect_p": (i, [vp, u32, fp, fp, f]),
+    })
+    return sig
+
+
 class Oracle:
     def __init__(self, abi, tables_path):
         if not os.path.exists(LIB_PATH):
             build()
         self.A = abi
         self.AO = importlib.import_module("._abi_ao", abi.__package__)   # the ctypes mirror of include/mi355ao.h beside `abi`
-        A = abi
         lib = C.CDLL(LIB_PATH)
-        table = {k.replace("pt_", "orc_", 1): v for k, v in A.ENTRY_POINTS.items()
-                 if k in ("pt_scene_create", "pt_scene_destroy", "pt_scene_bvh_info", "pt_scene_bvh_read", "pt_get_counters",
-                          "pt_trace_closest", "pt_trace_any", "pt_sobol_samples", "pt_halton_samples", "pt_camera_rays")}
-        for name, (res, args) in table.items():
+        for name, (res, args) in signatures(abi, self.AO).items():
             fn = getattr(lib, name); fn.restype = res; fn.argtypes = args
-        lib.orc_render.restype = C.c_int
-        lib.orc_render.argtypes = [C.c_void_p, C.POINTER(A.PtRenderParams), A.fp, C.c_int]
-        lib.orc_ao_render.restype = C.c_int
-        lib.orc_ao_render.argtypes = [C.c_void_p, C.POINTER(A.PtRenderParams), C.POINTER(self.AO.PtAOParams), A.fp, C.c_int]
-        lib.orc_film_resolve.argtypes = [A.fp, C.c_uint32, C.c_float, A.fp]
-        lib.orc_last_render_seconds.restype = C.c_double; lib.orc_last_render_seconds.argtypes = [C.c_void_p]
-        lib.orc_tmax_raises.restype = C.c_uint64; lib.orc_tmax_raises.argtypes = []      # triangle hits that raised t_max (ref_scene.h g_tmax_raises)
-        lib.orc_reset_tmax_raises.restype = None; lib.orc_reset_tmax_raises.argtypes = []
-        lib.orc_load_tables.argtypes = [C.c_char_p]
-        f = C.c_float
-        lib.orc_sobol_sample_float.restype = f; lib.orc_sobol_sample_float.argtypes = [C.c_uint64, C.c_int, C.c_uint32]
-        lib.orc_radical_inverse.restype = f; lib.orc_radical_inverse.argtypes = [C.c_int, C.c_uint64]
-        lib.orc_radical_inverse_any.restype = f; lib.orc_radical_inverse_any.argtypes = [C.c_uint32, C.c_uint64]
-        lib.orc_halton_permutation.restype = C.c_uint32; lib.orc_halton_permutation.argtypes = [C.c_uint32, C.POINTER(C.c_uint16)]
-        for n in ("orc_next_float_up", "orc_next_float_down", "orc_dm_sin", "orc_dm_cos", "orc_dm_acos", "orc_dm_log"):
-            getattr(lib, n).restype = f; getattr(lib, n).argtypes = [f]
-        lib.orc_dm_atan2.restype = f; lib.orc_dm_atan2.argtypes = [f, f]
-        lib.orc_find_interval.argtypes = [C.c_int, A.fp, f]
-        lib.orc_rng_u32_stream.argtypes = [C.c_uint64, C.c_int, C.c_uint32, A.u32p, A.fp]
-        lib.orc_dist1d_sample_discrete.argtypes = [A.fp, C.c_int, f, A.fp, A.fp]
-        lib.orc_dist1d_discrete_pdf.restype = f; lib.orc_dist1d_discrete_pdf.argtypes = [A.fp, C.c_int, C.c_int]
-        lib.orc_dist1d_sample_continuous.restype = f; lib.orc_dist1d_sample_continuous.argtypes = [A.fp, C.c_int, f, A.fp, C.POINTER(C.c_int)]
-        lib.orc_tri_intersect.argtypes = [C.c_void_p, C.c_uint32, A.fp, A.fp, f, A.fp, A.fp, A.fp, A.fp, A.fp]
-        lib.orc_tri_intersect_p.argtypes = [C.c_void_p, C.c_uint32, A.fp, A.fp, f]
-        lib.orc_offset_ray_origin.argtypes = [A.fp] * 5
-        tp = C.POINTER(A.PtBSSRDFTable)
-        lib.orc_bssrdf_sr.argtypes = [tp, A.fp, A.fp, f, C.c_uint32, A.fp, A.fp, A.fp]
-        lib.orc_bssrdf_sample_sr.argtypes = [tp, A.fp, A.fp, f, C.c_int, C.c_uint32, A.fp, A.fp]
-        lib.orc_catmull_rom_weights.argtypes = [C.c_int, A.fp, f, C.POINTER(C.c_int), A.fp]
-        lib.orc_bssrdf_sw.restype = f; lib.orc_bssrdf_sw.argtypes = [f, f]
-        lib.orc_light_sample_li.argtypes = [C.c_void_p, C.c_uint32, A.fp, A.fp, A.fp, C.c_uint32, A.fp, A.fp, A.fp, A.fp]
-        lib.orc_light_pdf_li.argtypes = [C.c_void_p, C.c_uint32, A.fp, A.fp, A.fp, C.c_uint32, A.fp, A.fp]
         if lib.orc_load_tables(tables_path.encode()) != 0:
             raise RuntimeError("oracle: cannot load " + tables_path)
         self.lib = lib

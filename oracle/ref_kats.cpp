@@ -1,43 +1,36 @@
 // ORACLE -- TEST INFRASTRUCTURE ONLY (see ref_math.h header).
 // ref_kats.cpp: the reference's own test loops for code this oracle restates, run in C++ for speed and reported to
 // tests/test_oracle_kats.py:  tests/fp.rs:125-226 (EFloat abs / sqrt / add / sub / mul / div containment, 10^6 seeds each),
-// tests/fp.rs:46-57 (float_bits), tests/bitops.rs:7-64 (log2_int, round_up_pow2), tests/sampling.rs:55-97 (generator matrices, Gray-code samples).
+// tests/fp.rs:46-57 (float_bits), tests/bitops.rs:7-64 (log2_int, round_up_pow2), tests/sampling.rs:24-97 (scrambled radical inverse,
+// generator matrices, Gray-code samples), tests/hg.rs (HenyeyGreenstein::p / sample_p); then the function probes that
+// tests/test_oracle_kats.py and tests/test_oracle_bsdf.py call per query: Sobol / Halton / radical inverse, next_float, find_interval,
+// PCG32, Distribution1D, the deterministic math, offset_ray_origin, the BSSRDF tables, light sample_li / pdf_li and a material's BSDF.
 #include "ref_efloat.h"
-#include "ref_sampler.h"
+#include "ref_bssrdf.h"
 #include <cmath>
 
 namespace {
 using namespace ref;
-struct Rng {   // core/rng.rs:10-75, RNG::new(sequence_index)
-    uint64_t state = 0x853c49e6748fea9bull, inc = 0xda3e39cb94b95bdbull;
-    Rng() {}
-    explicit Rng(uint64_t seq) { state = 0; inc = (seq << 1) | 1; u32(); state += 0x853c49e6748fea9bull; u32(); }
-    uint32_t u32() { uint64_t old = state; state = old * 0x5851f42d4c957f2dull + inc; uint32_t xs = (uint32_t)(((old >> 18) ^ old) >> 27), rot = (uint32_t)(old >> 59); return (xs >> rot) | (xs << ((~rot + 1u) & 31)); }
-    uint32_t below(uint32_t b) { uint32_t threshold = (~b + 1u) % b; for (;;) { uint32_t r = u32(); if (r >= threshold) return r % b; } }
-    Float f() { return fmin_(ONE_MINUS_EPSILON, (Float)u32() * 0x1.0p-32f); }
-};
-Float bits_to_float(uint32_t b) { Float f; std::memcpy(&f, &b, 4); return f; }
-uint32_t float_to_bits(Float f) { uint32_t b; std::memcpy(&b, &f, 4); return b; }
-EFloat get_efloat(Rng &rng, Float min_exp = -6.0f, Float max_exp = 6.0f) {   // tests/fp.rs:73-98
-    const Float t = rng.f();
+EFloat get_efloat(RNG &rng, Float min_exp = -6.0f, Float max_exp = 6.0f) {   // tests/fp.rs:73-98
+    const Float t = rng.uniform_float();
     const Float logu = min_exp * (1.0f - t) + max_exp * t;   // lerp (pbrt.rs:136-144)
     const Float val = std::pow(10.0f, logu);
     Float err = 0.0f;
-    switch (rng.below(4)) {
-    case 1: { const uint32_t ulp = rng.below(1024); err = std::fabs(bits_to_float(float_to_bits(val) + ulp) - val); break; }
-    case 2: { const uint32_t ulp = rng.below(1024 * 1024); err = std::fabs(bits_to_float(float_to_bits(val) + ulp) - val); break; }
-    case 3: err = (4.0f * rng.f()) * std::fabs(val); break;
+    switch (rng.uniform_u32_bounded(4)) {
+    case 1: { const uint32_t ulp = rng.uniform_u32_bounded(1024); err = std::fabs(bits_to_float(float_to_bits(val) + ulp) - val); break; }
+    case 2: { const uint32_t ulp = rng.uniform_u32_bounded(1024 * 1024); err = std::fabs(bits_to_float(float_to_bits(val) + ulp) - val); break; }
+    case 3: err = (4.0f * rng.uniform_float()) * std::fabs(val); break;
     default: break;
     }
-    const Float sign = rng.f() < 0.5f ? -1.0f : 1.0f;
+    const Float sign = rng.uniform_float() < 0.5f ? -1.0f : 1.0f;
     return EFloat(sign * val, err);
 }
-double get_precise(const EFloat &ef, Rng &rng) {   // tests/fp.rs:100-114
-    switch (rng.below(3)) {
+double get_precise(const EFloat &ef, RNG &rng) {   // tests/fp.rs:100-114
+    switch (rng.uniform_u32_bounded(3)) {
     case 0: return (double)ef.low;
     case 1: return (double)ef.high;
     default: {
-        const Float t = rng.f();
+        const Float t = rng.uniform_float();
         double p = (1.0 - (double)t) * (double)ef.low + (double)t * (double)ef.high;
         if (p > (double)ef.high) p = (double)ef.high;
         if (p < (double)ef.low) p = (double)ef.low;
@@ -46,6 +39,14 @@ double get_precise(const EFloat &ef, Rng &rng) {   // tests/fp.rs:100-114
     }
 }
 inline Float abs_err(const EFloat &e) { return next_float_up(fmax_(std::fabs(e.high - e.v), std::fabs(e.v - e.low))); }   // efloat.rs get_absolute_error
+void kat_bssrdf(const PtBSSRDFTable *t, const float *sigma_a, const float *sigma_s, float eta, BssrdfTable &tb, TabulatedBSSRDF &b) {
+    tb.n_rho = (int)t->n_rho; tb.n_radius = (int)t->n_radius;
+    tb.rho_samples.assign(t->rho_samples, t->rho_samples + t->n_rho); tb.radius_samples.assign(t->radius_samples, t->radius_samples + t->n_radius);
+    tb.profile.assign(t->profile, t->profile + (size_t)t->n_rho * t->n_radius); tb.rhoeff.assign(t->rhoeff, t->rhoeff + t->n_rho);
+    tb.profile_cdf.assign(t->profile_cdf, t->profile_cdf + (size_t)t->n_rho * t->n_radius);
+    SurfaceInteraction si; si.p = V3(0, 0, 0); si.n = V3(0, 0, 1); si.sh_n = V3(0, 0, 1); si.sh_dpdu = V3(1, 0, 0);
+    b.init(si, 0, eta, RGB(sigma_a[0], sigma_a[1], sigma_a[2]), RGB(sigma_s[0], sigma_s[1], sigma_s[2]), &tb);
+}
 }  // namespace
 
 extern "C" {
@@ -54,7 +55,7 @@ extern "C" {
 int orc_test_efloat(int op, int iters, int *n_tested) {
     int failures = 0, tested = 0;
     for (int trial = 0; trial < iters; ++trial) {
-        Rng rng((uint64_t)trial);
+        RNG rng((uint64_t)trial);
         if (op <= 1) {
             const EFloat ef = get_efloat(rng);
             const double precise = get_precise(ef, rng);
@@ -81,10 +82,10 @@ int orc_test_efloat(int op, int iters, int *n_tested) {
 // ref_math.h's float_to_bits / bits_to_float (pbrt.rs:57-78), the pair under next_float_up / next_float_down and offset_ray_origin.
 // Returns the number of mismatches; *n_tested = the draws that were not NaN.
 int orc_test_float_bits(int iters, int *n_tested) {
-    Rng rng(1);
+    RNG rng(1);
     int failures = 0, tested = 0;
     for (int i = 0; i < iters; ++i) {
-        const uint32_t ui = rng.u32();
+        const uint32_t ui = rng.uniform_u32();
         const Float f = ref::bits_to_float(ui);
         if (f != f) continue;
         ++tested;
@@ -105,11 +106,11 @@ int orc_test_scrambled_radical_inverse(int n_dims, double *worst) {
     static const uint32_t indices[7] = {0u, 1u, 2u, 1151u, 32351u, 4363211u, 681122u};
     int failures = 0; double w = 0.0;
     for (int dim = 0; dim < n_dims; ++dim) {
-        Rng rng((uint64_t)dim);
+        RNG rng((uint64_t)dim);
         const uint32_t base = T.primes[dim];
         std::vector<uint16_t> perm(base);
         for (uint32_t i = 0; i < base; ++i) perm[i] = (uint16_t)(base - 1 - i);
-        for (uint32_t i = 0; i < base; ++i) { const uint32_t other = i + rng.below(base - i); std::swap(perm[i], perm[other]); }
+        for (uint32_t i = 0; i < base; ++i) { const uint32_t other = i + rng.uniform_u32_bounded(base - i); std::swap(perm[i], perm[other]); }
         for (uint32_t index : indices) {
             long double val = 0.0L, scale = 1.0L / (long double)base; uint32_t n = index;
             while (n > 0) { val += (long double)perm[n % base] * scale; scale /= (long double)base; n /= base; }
@@ -170,8 +171,8 @@ int orc_test_generator_matrix(void) {
         failures += radical_inverse_base(2, a) != (Float)reverse_bits32(multiply_generator(c, a)) * 2.3283064365386963e-10f;
         failures += radical_inverse_base(2, a) != sample_generator_matrix(crev, a, 0);
     }
-    Rng rng;   // RNG::default()
-    for (int i = 0; i < 32; ++i) { c[i] = rng.u32(); crev[i] = reverse_bits32(c[i]); }
+    RNG rng;   // RNG::default()
+    for (int i = 0; i < 32; ++i) { c[i] = rng.uniform_u32(); crev[i] = reverse_bits32(c[i]); }
     for (uint32_t a = 0; a < 1024; ++a) failures += reverse_bits32(multiply_generator(c, a)) != multiply_generator(crev, a);
     // gray_code_sample_test: the 64 Gray-code samples of the identity matrix are the 64 values multiply_generator produces
     for (int i = 0; i < 32; ++i) c[i] = 1u << i;
@@ -183,5 +184,161 @@ int orc_test_generator_matrix(void) {
         failures += !found;
     }
     return failures;
+}
+
+// ---- tests/hg.rs restated (the reference's assertions on HenyeyGreenstein::p / sample_p, medium.rs:149-193), run inside the oracle ----
+// tests/hg.rs:12-32 sampling_match: RNG::default(), g = -0.75 .. 0.75 step 0.25, 100 samples each; returns max |p0 - p(wo, wi)| / p
+double orc_test_hg_sampling_match(void) {
+    RNG rng;   // RNG::default()
+    double worst = 0.0;
+    for (Float g = -0.75f; g <= 0.75f; g += 0.25f)
+        for (int i = 0; i < 100; ++i) {
+            const Float a = rng.uniform_float(), b = rng.uniform_float();
+            const V3 wo = uniform_sample_sphere(P2(a, b));
+            V3 wi;
+            const Float u0 = rng.uniform_float(), u1 = rng.uniform_float();
+            const Float p0 = hg_sample_p(g, wo, wi, P2(u0, u1));
+            const Float p1 = phase_hg(dot(wo, wi), g);
+            worst = std::max(worst, (double)std::fabs(p0 - p1) / (double)std::fabs(p1));
+        }
+    return worst;
+}
+// tests/hg.rs:34-79 sampling_orientation_forward / sample_orientation_backward: wo = (-1, 0, 0), 100 samples, counts wi.x > 0
+void orc_test_hg_orientation(float g, int *nforward, int *nbackward) {
+    RNG rng;   // RNG::default()
+    *nforward = *nbackward = 0;
+    for (int i = 0; i < 100; ++i) {
+        const Float u0 = rng.uniform_float(), u1 = rng.uniform_float();
+        V3 wi;
+        hg_sample_p(g, V3(-1.0f, 0.0f, 0.0f), wi, P2(u0, u1));
+        if (wi.x > 0.0f) ++*nforward; else ++*nbackward;
+    }
+}
+// tests/hg.rs:81-103 normalized: per g, the mean of p(wo, wi) over 100 000 uniform directions (expected 1 / 4 pi)
+void orc_test_hg_normalized(double *means7) {
+    RNG rng;   // RNG::default()
+    int k = 0;
+    for (Float g = -0.75f; g <= 0.75f; g += 0.25f, ++k) {
+        const Float a = rng.uniform_float(), b = rng.uniform_float();
+        const V3 wo = uniform_sample_sphere(P2(a, b));
+        Float sum = 0.0f;
+        const int n = 100000;
+        for (int i = 0; i < n; ++i) { const Float c = rng.uniform_float(), d = rng.uniform_float(); sum += phase_hg(dot(wo, uniform_sample_sphere(P2(c, d))), g); }
+        means7[k] = (double)(sum / (Float)n);
+    }
+}
+
+// ---- function probes: oracle functions called once per query by the known-answer tests of tests/test_oracle_kats.py and tests/test_oracle_bsdf.py ----
+float orc_sobol_sample_float(uint64_t index, int dim, uint32_t scramble) { return sobol_sample_float(index, dim, scramble); }
+float orc_radical_inverse(int base_index, uint64_t n) { return radical_inverse(base_index, n); }
+// radical_inverse(base_index, n) (pbrt_macros:92-111) and the Halton digit permutation of a dimension
+float orc_radical_inverse_any(uint32_t base_index, uint64_t n) {
+    if (base_index == 0) return (float)reverse_bits64_h(n) * 0x1.0p-64f;
+    return radical_inverse_base(halton_tables().primes[base_index], n);
+}
+uint32_t orc_halton_permutation(uint32_t dim, uint16_t *out) {
+    const HaltonTables &T = halton_tables();
+    if (dim >= 1000) return 0;
+    for (uint32_t j = 0; j < T.primes[dim]; ++j) out[j] = T.perm[T.sums[dim] + j];
+    return T.primes[dim];
+}
+float orc_next_float_up(float v) { return next_float_up(v); }
+float orc_next_float_down(float v) { return next_float_down(v); }
+int orc_find_interval(int size, const float *a, float x) { return find_interval(size, [&](int i) { return a[i] <= x; }); }
+uint32_t orc_rng_u32_stream(uint64_t seq, int use_default, uint32_t n, uint32_t *out, float *outf) {
+    RNG r = use_default ? RNG() : RNG(seq);
+    for (uint32_t i = 0; i < n; ++i) { if (out) out[i] = r.uniform_u32(); else outf[i] = r.uniform_float(); }
+    return n;
+}
+// Distribution1D (tests/sampling.rs:202-257)
+int orc_dist1d_sample_discrete(const float *func, int n, float u, float *pdf, float *uremapped) {
+    Distribution1D d(std::vector<Float>(func, func + n));
+    return (int)d.sample_discrete(u, pdf, uremapped);
+}
+float orc_dist1d_discrete_pdf(const float *func, int n, int index) { return Distribution1D(std::vector<Float>(func, func + n)).discrete_pdf((size_t)index); }
+float orc_dist1d_sample_continuous(const float *func, int n, float u, float *pdf, int *offset) {   // Distribution1D::sample_continous (sampling.rs:38-64); pdf / offset may be null like the reference's Options
+    size_t off = 0;
+    const float x = Distribution1D(std::vector<Float>(func, func + n)).sample_continuous(u, pdf, &off);
+    if (offset) *offset = (int)off;
+    return x;
+}
+// deterministic math
+float orc_dm_sin(float x) { return dm_sinf(x); }
+float orc_dm_cos(float x) { return dm_cosf(x); }
+float orc_dm_acos(float x) { return dm_acosf(x); }
+float orc_dm_atan2(float y, float x) { return dm_atan2f(y, x); }
+float orc_dm_log(float x) { return dm_logf(x); }
+void orc_offset_ray_origin(const float *p, const float *perr, const float *n, const float *w, float *out) {
+    V3 r = offset_ray_origin(V3(p[0], p[1], p[2]), V3(perr[0], perr[1], perr[2]), V3(n[0], n[1], n[2]), V3(w[0], w[1], w[2]));
+    out[0] = r.x; out[1] = r.y; out[2] = r.z;
+}
+// BSSRDF restatement: Sr(r) and pdf_sr(ch, r) for n radii
+int orc_bssrdf_sr(const PtBSSRDFTable *t, const float *sigma_a, const float *sigma_s, float eta, uint32_t n, const float *r, float *sr3, float *pdf3) {
+    BssrdfTable tb; TabulatedBSSRDF b; kat_bssrdf(t, sigma_a, sigma_s, eta, tb, b);
+    for (uint32_t i = 0; i < n; ++i) {
+        RGB s = b.sr(r[i]);
+        for (int c = 0; c < 3; ++c) { sr3[3 * i + c] = s.c[c]; pdf3[3 * i + c] = b.pdf_sr(c, r[i]); }
+    }
+    return 0;
+}
+int orc_bssrdf_sample_sr(const PtBSSRDFTable *t, const float *sigma_a, const float *sigma_s, float eta, int ch, uint32_t n, const float *u, float *r) {
+    BssrdfTable tb; TabulatedBSSRDF b; kat_bssrdf(t, sigma_a, sigma_s, eta, tb, b);
+    for (uint32_t i = 0; i < n; ++i) r[i] = b.sample_sr(ch, u[i]);
+    return 0;
+}
+int orc_catmull_rom_weights(int size, const float *nodes, float x, int *offset, float *w4) {
+    return catmull_rom_weights(size, nodes, x, *offset, w4) ? 1 : 0;
+}
+float orc_bssrdf_sw(float eta, float cos_theta_) { return bssrdf_sw(eta, V3(std::sqrt(fmax_(0.0f, 1.0f - cos_theta_ * cos_theta_)), 0.0f, cos_theta_)); }
+// light sampling: sample_li for n sample points u (2n floats) from the reference point (p, p_error, n); outputs wi (3n), pdf (n), L (3n)
+int orc_light_sample_li(orc_scene *h, uint32_t li, const float *p, const float *perr, const float *nrm, uint32_t n, const float *u,
+                        float *wi_out, float *pdf_out, float *L_out) {
+    LightSampler ls; ls.init(h->scene, PT_LS_UNIFORM);
+    IData ref; ref.p = V3(p[0], p[1], p[2]); ref.p_error = V3(perr[0], perr[1], perr[2]); ref.n = V3(nrm[0], nrm[1], nrm[2]);
+    for (uint32_t i = 0; i < n; ++i) {
+        V3 wi(0, 0, 0); Float pdf = 0.0f; IData p1;
+        RGB L = ls.sample_li(li, ref, P2(u[2 * i], u[2 * i + 1]), wi, pdf, p1);
+        wi_out[3 * i] = wi.x; wi_out[3 * i + 1] = wi.y; wi_out[3 * i + 2] = wi.z; pdf_out[i] = pdf;
+        for (int c = 0; c < 3; ++c) L_out[3 * i + c] = L.c[c];
+    }
+    return 0;
+}
+int orc_light_pdf_li(orc_scene *h, uint32_t li, const float *p, const float *perr, const float *nrm, uint32_t n, const float *wi, float *pdf_out) {
+    LightSampler ls; ls.init(h->scene, PT_LS_UNIFORM);
+    IData ref; ref.p = V3(p[0], p[1], p[2]); ref.p_error = V3(perr[0], perr[1], perr[2]); ref.n = V3(nrm[0], nrm[1], nrm[2]);
+    for (uint32_t i = 0; i < n; ++i) pdf_out[i] = ls.pdf_li(li, ref, V3(wi[3 * i], wi[3 * i + 1], wi[3 * i + 2]));
+    return 0;
+}
+// BSDF of a material at a canonical interaction, for the analytic lobe checks of tests/test_oracle_bsdf.py.
+// The material `mi` is evaluated as Material::compute_scattering_functions would at a point with geometric and shading normal +z, dpdu = +x,
+// dpdv = +y, no textures; then for each of n queries: f(wo, wi) and pdf(wo, wi) over all lobes (reflection.rs:1541-1600), and sample_f(wo, u)
+// (reflection.rs:1602-1689) -> sampled wi, its f, pdf and lobe type. Directions are world = local here.
+int orc_bsdf_eval(orc_scene *h, uint32_t mi, uint32_t n, const float *wo, const float *wi, const float *u,
+                  float *f_out, float *pdf_out, float *s_wi_out, float *s_f_out, float *s_pdf_out, int32_t *s_type_out, int32_t *n_lobes_out) {
+    if (mi >= h->scene.materials.size()) return 1;
+    SurfaceInteraction si{};
+    si.p = V3(0, 0, 0); si.p_error = V3(0, 0, 0); si.n = V3(0, 0, 1); si.sh_n = V3(0, 0, 1); si.wo = V3(0, 0, 1);
+    si.dpdu = V3(1, 0, 0); si.dpdv = V3(0, 1, 0); si.sh_dpdu = V3(1, 0, 0); si.sh_dpdv = V3(0, 1, 0);
+    si.uv = P2(0.5f, 0.5f); si.has_shape = false; si.shape_flip = false; si.prim = 0;
+    BSDF bsdf;
+    if (!material_scattering_functions(h->scene, mi, si, bsdf, nullptr, nullptr, nullptr)) return 2;
+    if (n_lobes_out) *n_lobes_out = bsdf.n;
+    for (uint32_t i = 0; i < n; ++i) {
+        const V3 o(wo[3 * i], wo[3 * i + 1], wo[3 * i + 2]);
+        if (wi && f_out && pdf_out) {
+            const V3 w(wi[3 * i], wi[3 * i + 1], wi[3 * i + 2]);
+            const RGB f = bsdf.f(o, w, BSDF_ALL);
+            for (int c = 0; c < 3; ++c) f_out[3 * i + c] = f.c[c];
+            pdf_out[i] = bsdf.pdf(o, w, BSDF_ALL);
+        }
+        if (u && s_wi_out && s_f_out && s_pdf_out) {
+            V3 w(0, 0, 0); Float pdf = 0.0f; int sampled = 0;
+            const RGB f = bsdf.sample_f(o, w, P2(u[2 * i], u[2 * i + 1]), pdf, BSDF_ALL, sampled);
+            s_wi_out[3 * i] = w.x; s_wi_out[3 * i + 1] = w.y; s_wi_out[3 * i + 2] = w.z; s_pdf_out[i] = pdf;
+            for (int c = 0; c < 3; ++c) s_f_out[3 * i + c] = f.c[c];
+            if (s_type_out) s_type_out[i] = sampled;
+        }
+    }
+    return 0;
 }
 }  // extern "C"

@@ -12,6 +12,10 @@
 //                            Disk::sample through sample_interaction + a self-occlusion intersect_p)
 //   tests/shapes.rs:36-146   triangle_watertight   (Triangle::intersect over a closed triangulated sphere: every ray from inside hits;
 //                            the reference keeps this test DISABLED -- `//#[test]` at :35 -- see orc_test_triangle_watertight)
+//   tests/shapes.rs:490-535  partial_sphere_normal (Sphere::intersect's normal points along the hit point)
+//   tests/shapes.rs:173-224  triangle_reintersect  (rays spawned from a hit never re-hit the triangle; tests/shapes.rs:421-487,538-565:
+//                            the same for full and partial spheres)
+// and the single-triangle probes orc_tri_intersect / orc_tri_intersect_p.
 // Same seeds (RNG::new(i) / RNG::new(100 + i)), same sample counts, same radical-inverse points, same tolerances.
 #include "ref_shading.h"
 #include <cmath>
@@ -20,6 +24,18 @@ namespace {
 using namespace ref;
 
 Float punif(RNG &rng, Float range) { return lerp(rng.uniform_float(), -range, range); }   // tests/shapes.rs:30-32
+Float pexp(RNG &rng, Float e) { const Float logu = lerp(rng.uniform_float(), -e, e); return std::pow(10.0f, logu); }   // tests/shapes.rs:24-28
+// Sphere::new (sphere.rs:31-50) at the origin
+PtSphere sphere_new(Float radius, Float zmin, Float zmax, Float phimax) {
+    PtSphere S; std::memset(&S, 0, sizeof S);
+    for (int k = 0; k < 4; ++k) S.object_to_world[5 * k] = S.world_to_object[5 * k] = 1.0f;
+    S.radius = radius;
+    S.z_min = clampv(std::fmin(zmin, zmax), -radius, radius); S.z_max = clampv(std::fmax(zmin, zmax), -radius, radius);
+    S.theta_min = std::acos(clampv(std::fmin(zmin, zmax) / radius, -1.0f, 1.0f));
+    S.theta_max = std::acos(clampv(std::fmax(zmin, zmax) / radius, -1.0f, 1.0f));
+    S.phi_max = (PI / 180.0f) * clampv(phimax, 0.0f, 360.0f);
+    return S;
+}
 
 // get_random_trianlge (tests/shapes.rs:147-170) as a one-triangle scene with that triangle as light 0 (an area light is how the
 // oracle reaches Shape::sample_interaction). Returns false for the degenerate triangles the reference skips.
@@ -270,7 +286,6 @@ int orc_test_triangle_watertight(int n_seeds, int as_written, float *verts, uint
 // interaction's normal must point along the hit point: dot(normalize(n), normalize(p)) = 1. The Rust file evaluates `relative_eq!(1.0, dot, epsilon = 1e-5)` and drops the
 // result; here it is an assertion. Returns the number of hits with |dot - 1| > 1e-5 (relative_eq's max(|a|, |b|) * epsilon form); *n_tested = hits found; *worst = max |dot - 1|.
 int orc_test_partial_sphere_normal(int n_seeds, int *n_tested, double *worst) {
-    auto pexp = [](RNG &rng, float e) { const float logu = lerp(rng.uniform_float(), -e, e); return std::pow(10.0f, logu); };
     int failures = 0, tested = 0; double w = 0.0;
     for (int i = 0; i < n_seeds; ++i) {
         RNG rng((uint64_t)i);
@@ -278,14 +293,7 @@ int orc_test_partial_sphere_normal(int n_seeds, int *n_tested, double *worst) {
         const float zmin = (rng.uniform_float() < 0.5f) ? -radius : lerp(rng.uniform_float(), -radius, radius);
         const float zmax = (rng.uniform_float() < 0.5f) ? radius : lerp(rng.uniform_float(), -radius, radius);
         const float phimax = (rng.uniform_float() < 0.5f) ? 360.0f : rng.uniform_float() * 360.0f;
-        PtSphere S; std::memset(&S, 0, sizeof S);   // Sphere::new (sphere.rs:31-50)
-        for (int k = 0; k < 4; ++k) S.object_to_world[5 * k] = S.world_to_object[5 * k] = 1.0f;
-        S.radius = radius;
-        S.z_min = clampv(std::fmin(zmin, zmax), -radius, radius); S.z_max = clampv(std::fmax(zmin, zmax), -radius, radius);
-        S.theta_min = std::acos(clampv(std::fmin(zmin, zmax) / radius, -1.0f, 1.0f));
-        S.theta_max = std::acos(clampv(std::fmax(zmin, zmax) / radius, -1.0f, 1.0f));
-        S.phi_max = (PI / 180.0f) * clampv(phimax, 0.0f, 360.0f);
-        Scene s; s.spheres.push_back(S);
+        Scene s; s.spheres.push_back(sphere_new(radius, zmin, zmax, phimax));
         V3 o; o.x = pexp(rng, 8.0f); o.y = pexp(rng, 8.0f); o.z = pexp(rng, 8.0f);
         const Bounds3 bbox = s.sphere_world_bound(0);
         V3 t; t.x = rng.uniform_float(); t.y = rng.uniform_float(); t.z = rng.uniform_float();
@@ -302,6 +310,109 @@ int orc_test_partial_sphere_normal(int n_seeds, int *n_tested, double *worst) {
     }
     if (n_tested) *n_tested = tested;
     if (worst) *worst = w;
+    return failures;
+}
+
+// single-triangle tests (tests/shapes.rs): a 1-triangle scene is created by the caller.
+int orc_tri_intersect(orc_scene *h, uint32_t tri, const float *o, const float *d, float tmax, float *t, float *b, float *p, float *perr, float *n) {
+    Ray r(V3(o[0], o[1], o[2]), V3(d[0], d[1], d[2]), tmax);
+    Float tt, bb[3];
+    if (!h->scene.tri_intersect(tri, r, tt, bb)) return 0;
+    SurfaceInteraction si; h->scene.tri_fill_interaction(tri, r, tt, bb, true, si);
+    *t = tt; b[0] = bb[0]; b[1] = bb[1]; b[2] = bb[2];
+    p[0] = si.p.x; p[1] = si.p.y; p[2] = si.p.z; perr[0] = si.p_error.x; perr[1] = si.p_error.y; perr[2] = si.p_error.z;
+    n[0] = si.n.x; n[1] = si.n.y; n[2] = si.n.z;
+    return 1;
+}
+int orc_tri_intersect_p(orc_scene *h, uint32_t tri, const float *o, const float *d, float tmax) {
+    Ray r(V3(o[0], o[1], o[2]), V3(d[0], d[1], d[2]), tmax);
+    Float tt, bb[3];
+    return h->scene.tri_hit_params(tri, r, tt, bb) ? 1 : 0;
+}
+
+// tests/shapes.rs:173-224 triangle_reintersect: same PCG32 seeds (RNG::new(i)), pexp(rng, 8), 10 000 spawned rays
+// per triangle must not re-hit it (intersect_p and intersect). Returns the number of violations; *n_tested counts
+// the triangles that were actually hit by the first ray.
+int orc_test_triangle_reintersect(int n_seeds, int rays_per_tri, int *n_tested) {
+    int failures = 0, tested = 0;
+    for (int i = 0; i < n_seeds; ++i) {
+        RNG rng((uint64_t)i);
+        V3 v[3];
+        for (int j = 0; j < 3; ++j) { v[j].x = pexp(rng, 8.0f); v[j].y = pexp(rng, 8.0f); v[j].z = pexp(rng, 8.0f); }
+        if (length_squared(cross(v[1] - v[0], v[2] - v[0])) < 1.0e-20f) continue;
+        Scene s;
+        s.P = {v[0], v[1], v[2]}; s.idx = {0, 1, 2}; s.tri_flags = {0};
+        P2 u; u.x = rng.uniform_float(); u.y = rng.uniform_float();
+        P2 b = uniform_sample_triangle(u);
+        V3 ptri = v[0] * b.x + v[1] * b.y + v[2] * (1.0f - b.x - b.y);
+        V3 o; o.x = pexp(rng, 8.0f); o.y = pexp(rng, 8.0f); o.z = pexp(rng, 8.0f);
+        Ray r(o, ptri - o, INF, 0.0f);
+        Float t, bb[3];
+        if (!s.tri_intersect(0, r, t, bb)) continue;
+        SurfaceInteraction isect; s.tri_fill_interaction(0, r, t, bb, true, isect);
+        tested++;
+        for (int j = 0; j < rays_per_tri; ++j) {
+            P2 uu; uu.x = rng.uniform_float(); uu.y = rng.uniform_float();
+            V3 w = uniform_sample_sphere(uu);
+            IData it; it.p = isect.p; it.p_error = isect.p_error; it.n = isect.n;
+            Ray rout = spawn_ray(it, w);
+            Float t2, b2[3];
+            if (s.tri_hit_params(0, rout, t2, b2)) failures++;
+            if (s.tri_intersect(0, rout, t2, b2)) failures++;
+            V3 p2; p2.x = pexp(rng, 8.0f); p2.y = pexp(rng, 8.0f); p2.z = pexp(rng, 8.0f);
+            // spawn_rayto_point, interaction.rs:38-43
+            V3 d = p2 - it.p;
+            Ray r2(offset_ray_origin(it.p, it.p_error, it.n, d), d, 1.0f - SHADOW_EPSILON, 0.0f);
+            if (s.tri_hit_params(0, r2, t2, b2)) failures++;
+            if (s.tri_intersect(0, r2, t2, b2)) failures++;
+        }
+    }
+    if (n_tested) *n_tested = tested;
+    return failures;
+}
+
+// tests/shapes.rs:421-487,538-565: full / partial sphere re-intersection with the reference's seeds RNG::new(0..n).
+int orc_test_sphere_reintersect(int n_seeds, int rays_per_shape, int partial, int *n_tested) {
+    int failures = 0, tested = 0;
+    for (int i = 0; i < n_seeds; ++i) {
+        RNG rng((uint64_t)i);
+        float radius = pexp(rng, 4.0f);
+        float zmin = -radius, zmax = radius, phimax = 360.0f;
+        if (partial) {
+            zmin = (rng.uniform_float() < 0.5f) ? -radius : lerp(rng.uniform_float(), -radius, radius);
+            zmax = (rng.uniform_float() < 0.5f) ? radius : lerp(rng.uniform_float(), -radius, radius);
+            phimax = (rng.uniform_float() < 0.5f) ? 360.0f : rng.uniform_float() * 360.0f;
+        }
+        Scene s; s.spheres.push_back(sphere_new(radius, zmin, zmax, phimax));
+        // test_reintersect_convex
+        V3 o; o.x = pexp(rng, 8.0f); o.y = pexp(rng, 8.0f); o.z = pexp(rng, 8.0f);
+        Bounds3 bbox = s.sphere_world_bound(0);
+        V3 t; t.x = rng.uniform_float(); t.y = rng.uniform_float(); t.z = rng.uniform_float();
+        V3 p2 = bbox.lerp3(t);
+        Ray r(o, p2 - o, INF, 0.0f);
+        if (rng.uniform_float() < 0.5f) r.d = normalize(r.d);
+        SurfaceInteraction isect; Float thit;
+        if (!s.sphere_intersect(0, r, thit, isect, true)) continue;
+        tested++;
+        for (int j = 0; j < rays_per_shape; ++j) {
+            P2 u; u.x = rng.uniform_float(); u.y = rng.uniform_float();
+            V3 w = face_forward(uniform_sample_sphere(u), isect.n);
+            IData it; it.p = isect.p; it.p_error = isect.p_error; it.n = isect.n;
+            Ray rout = spawn_ray(it, w);
+            SurfaceInteraction tmp; Float th2;
+            if (s.sphere_intersect_p(0, rout)) failures++;
+            if (s.sphere_intersect(0, rout, th2, tmp, true)) failures++;
+            V3 p3; p3.x = pexp(rng, 8.0f); p3.y = pexp(rng, 8.0f); p3.z = pexp(rng, 8.0f);
+            w = face_forward(p3 - isect.p, isect.n);
+            p3 = isect.p + w;
+            V3 d = p3 - it.p;
+            Ray r2(offset_ray_origin(it.p, it.p_error, it.n, d), d, 1.0f - SHADOW_EPSILON, 0.0f);
+            if (s.sphere_intersect_p(0, r2)) failures++;
+            // the reference overwrites `isect` here when the (unexpected) hit happens; it must not happen
+            if (s.sphere_intersect(0, r2, th2, tmp, true)) failures++;
+        }
+    }
+    if (n_tested) *n_tested = tested;
     return failures;
 }
 }  // extern "C"

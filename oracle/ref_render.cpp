@@ -1,6 +1,7 @@
 // ORACLE -- TEST INFRASTRUCTURE ONLY (see ref_math.h header).
 // ref_render.cpp: materials -> BSDF, media, one-light MIS, the BSSRDF exit step, PathIntegrator::li, VolPathIntegrator::li, AOIntegrator::li,
-// perspective camera, film, the tile render loop, and the oracle's C ABI (driven from tests/ and bench.py's cpu_baseline leg).
+// perspective camera, film, the tile render loop, and the oracle's parity C ABI (driven from tests/ and bench.py's cpu_baseline leg): the orc_*
+// functions that mirror include/mi355pt.h / mi355ao.h, and the tmax-raise counter. Probes and reference-test loops: ref_kats.cpp, ref_kats_shapes.cpp.
 //   materials/{matte,mirror,glass,plastic,metal,uber,substrate}.rs; media/{homogeneous,grid}.rs; core/integrator.rs:81-237,263-403;
 //   core/light.rs:120-150 (VisibilityTester::tr); core/scene.rs:68-87 (intersect_tr); core/bssrdf.rs:334-410,559-574 (sample_s); integrators/path.rs:79-222;
 //   integrators/volpath.rs:76-226; integrators/ao.rs:63-110; cameras/perspective.rs:120-179; core/film.rs:104-161,217-258,292-331.
@@ -66,9 +67,6 @@ static void bump_shading(const Scene &scene, int d, const TexCtx &ctx, SurfaceIn
     si.sh_dpdu = dpdu; si.sh_dpdv = dpdv;
 }
 
-// Returns false when the material leaves `si.bsdf == None` (null surface, path.rs:124-129).
-static bool material_scattering_functions(const Scene &scene, uint32_t mi, SurfaceInteraction &si, BSDF &bsdf,
-                                          TabulatedBSSRDF *bssrdf, bool *has_bssrdf, const TexCtx *tctx);
 static bool compute_scattering_functions(const Scene &scene, SurfaceInteraction &si, BSDF &bsdf,
                                          TabulatedBSSRDF *bssrdf = nullptr, bool *has_bssrdf = nullptr, const TexCtx *tctx = nullptr) {
     uint32_t mi = scene.prim_material[si.prim];
@@ -90,8 +88,8 @@ static bool compute_scattering_functions(const Scene &scene, SurfaceInteraction 
     }
     return material_scattering_functions(scene, mi, si, bsdf, bssrdf, has_bssrdf, tctx);
 }
-static bool material_scattering_functions(const Scene &scene, uint32_t mi, SurfaceInteraction &si, BSDF &bsdf,
-                                          TabulatedBSSRDF *bssrdf, bool *has_bssrdf, const TexCtx *tctx) {
+bool material_scattering_functions(const Scene &scene, uint32_t mi, SurfaceInteraction &si, BSDF &bsdf,
+                                   TabulatedBSSRDF *bssrdf, bool *has_bssrdf, const TexCtx *tctx) {
     const PtMaterial &m = scene.materials[mi];
     const MatEval E{scene, m, tctx};
     // bump() modifies the caller's interaction in place (shading.n is what path.rs / estimate_direct read afterwards)
@@ -428,11 +426,7 @@ static RGB medium_sample(const PtMedium &m, uint32_t mid, const Ray &ray, SobolS
     RGB ss(m.sigma_s[0], m.sigma_s[1], m.sigma_s[2]);
     return sampled ? Tr * ss / pdf : Tr / pdf;
 }
-static inline Float phase_hg(Float cos_theta, Float g) {   // medium.rs:149-154
-    Float denom = 1.0f + g * g + 2.0f * g * cos_theta;
-    return INV4_PI * (1.0f - g * g) / (denom * std::sqrt(denom));
-}
-static Float hg_sample_p(Float g, V3 wo, V3 &wi, P2 u) {   // medium.rs:173-193
+Float hg_sample_p(Float g, V3 wo, V3 &wi, P2 u) {   // medium.rs:173-193
     Float cos_theta;
     if (std::fabs(g) < 1.0e-3f) cos_theta = 1.0f - 2.0f * u.x;
     else {
@@ -970,8 +964,6 @@ static void render_tiles(const RenderJob &job, float *film_xyzw, int nthreads, C
 // ---- oracle C ABI (ctypes) -----------------------------------------------------------------------
 using namespace ref;
 
-struct orc_scene { Scene scene; Counters counters; double last_render_seconds = 0; };
-
 extern "C" {
 
 int orc_load_tables(const char *path) { return sobol_tables().load(path) ? 0 : 1; }
@@ -1174,17 +1166,6 @@ int orc_halton_samples(const int32_t sb[4], uint32_t at_center, uint32_t n, cons
     }
     return PT_OK;
 }
-// KAT hooks: radical_inverse(base_index, n) (pbrt_macros:92-111) and the Halton digit permutation of a dimension
-float orc_radical_inverse_any(uint32_t base_index, uint64_t n) {
-    if (base_index == 0) return (float)reverse_bits64_h(n) * 0x1.0p-64f;
-    return radical_inverse_base(halton_tables().primes[base_index], n);
-}
-uint32_t orc_halton_permutation(uint32_t dim, uint16_t *out) {
-    const HaltonTables &T = halton_tables();
-    if (dim >= 1000) return 0;
-    for (uint32_t j = 0; j < T.primes[dim]; ++j) out[j] = T.perm[T.sums[dim] + j];
-    return T.primes[dim];
-}
 int orc_camera_rays(const PtRenderParams *rp, uint32_t n, const float *cs, float *out_o, float *out_d) {
     Camera cam;
     cam.raster_to_camera = m4_from(rp->raster_to_camera); cam.camera_to_world = m4_from(rp->camera_to_world);
@@ -1198,292 +1179,4 @@ int orc_camera_rays(const PtRenderParams *rp, uint32_t n, const float *cs, float
     return PT_OK;
 }
 
-// ---- known-answer-test hooks (reference tests/*.rs) ------------------------------------------------
-float orc_sobol_sample_float(uint64_t index, int dim, uint32_t scramble) { return sobol_sample_float(index, dim, scramble); }
-float orc_radical_inverse(int base_index, uint64_t n) { return radical_inverse(base_index, n); }
-float orc_next_float_up(float v) { return next_float_up(v); }
-float orc_next_float_down(float v) { return next_float_down(v); }
-int orc_find_interval(int size, const float *a, float x) { return find_interval(size, [&](int i) { return a[i] <= x; }); }
-uint32_t orc_rng_u32_stream(uint64_t seq, int use_default, uint32_t n, uint32_t *out, float *outf) {
-    RNG r = use_default ? RNG() : RNG(seq);
-    for (uint32_t i = 0; i < n; ++i) { if (out) out[i] = r.uniform_u32(); else outf[i] = r.uniform_float(); }
-    return n;
-}
-// Distribution1D (tests/sampling.rs:202-257)
-int orc_dist1d_sample_discrete(const float *func, int n, float u, float *pdf, float *uremapped) {
-    Distribution1D d(std::vector<Float>(func, func + n));
-    return (int)d.sample_discrete(u, pdf, uremapped);
-}
-float orc_dist1d_discrete_pdf(const float *func, int n, int index) { return Distribution1D(std::vector<Float>(func, func + n)).discrete_pdf((size_t)index); }
-float orc_dist1d_sample_continuous(const float *func, int n, float u, float *pdf, int *offset) {   // Distribution1D::sample_continous (sampling.rs:38-64); pdf / offset may be null like the reference's Options
-    size_t off = 0;
-    const float x = Distribution1D(std::vector<Float>(func, func + n)).sample_continuous(u, pdf, &off);
-    if (offset) *offset = (int)off;
-    return x;
-}
-// deterministic math
-float orc_dm_sin(float x) { return dm_sinf(x); }
-float orc_dm_cos(float x) { return dm_cosf(x); }
-float orc_dm_acos(float x) { return dm_acosf(x); }
-float orc_dm_atan2(float y, float x) { return dm_atan2f(y, x); }
-float orc_dm_log(float x) { return dm_logf(x); }
-// single-triangle tests (tests/shapes.rs): a 1-triangle scene is created by the caller.
-int orc_tri_intersect(orc_scene *h, uint32_t tri, const float *o, const float *d, float tmax, float *t, float *b, float *p, float *perr, float *n) {
-    Ray r(V3(o[0], o[1], o[2]), V3(d[0], d[1], d[2]), tmax);
-    Float tt, bb[3];
-    if (!h->scene.tri_intersect(tri, r, tt, bb)) return 0;
-    SurfaceInteraction si; h->scene.tri_fill_interaction(tri, r, tt, bb, true, si);
-    *t = tt; b[0] = bb[0]; b[1] = bb[1]; b[2] = bb[2];
-    p[0] = si.p.x; p[1] = si.p.y; p[2] = si.p.z; perr[0] = si.p_error.x; perr[1] = si.p_error.y; perr[2] = si.p_error.z;
-    n[0] = si.n.x; n[1] = si.n.y; n[2] = si.n.z;
-    return 1;
-}
-int orc_tri_intersect_p(orc_scene *h, uint32_t tri, const float *o, const float *d, float tmax) {
-    Ray r(V3(o[0], o[1], o[2]), V3(d[0], d[1], d[2]), tmax);
-    Float tt, bb[3];
-    return h->scene.tri_hit_params(tri, r, tt, bb) ? 1 : 0;
-}
-void orc_offset_ray_origin(const float *p, const float *perr, const float *n, const float *w, float *out) {
-    V3 r = offset_ray_origin(V3(p[0], p[1], p[2]), V3(perr[0], perr[1], perr[2]), V3(n[0], n[1], n[2]), V3(w[0], w[1], w[2]));
-    out[0] = r.x; out[1] = r.y; out[2] = r.z;
-}
-
-}  // extern "C"
-
-// ---- property tests restated from the reference's tests/shapes.rs (run inside the oracle for speed) ----
-extern "C" {
-// tests/shapes.rs:173-224 triangle_reintersect: same PCG32 seeds (RNG::new(i)), pexp(rng, 8), 10 000 spawned rays
-// per triangle must not re-hit it (intersect_p and intersect). Returns the number of violations; *n_tested counts
-// the triangles that were actually hit by the first ray.
-static float pexp_(RNG &rng, float e) { float logu = lerp(rng.uniform_float(), -e, e); return std::pow(10.0f, logu); }
-int orc_test_triangle_reintersect(int n_seeds, int rays_per_tri, int *n_tested) {
-    int failures = 0, tested = 0;
-    for (int i = 0; i < n_seeds; ++i) {
-        RNG rng((uint64_t)i);
-        V3 v[3];
-        for (int j = 0; j < 3; ++j) { v[j].x = pexp_(rng, 8.0f); v[j].y = pexp_(rng, 8.0f); v[j].z = pexp_(rng, 8.0f); }
-        if (length_squared(cross(v[1] - v[0], v[2] - v[0])) < 1.0e-20f) continue;
-        Scene s;
-        s.P = {v[0], v[1], v[2]}; s.idx = {0, 1, 2}; s.tri_flags = {0};
-        P2 u; u.x = rng.uniform_float(); u.y = rng.uniform_float();
-        P2 b = uniform_sample_triangle(u);
-        V3 ptri = v[0] * b.x + v[1] * b.y + v[2] * (1.0f - b.x - b.y);
-        V3 o; o.x = pexp_(rng, 8.0f); o.y = pexp_(rng, 8.0f); o.z = pexp_(rng, 8.0f);
-        Ray r(o, ptri - o, INF, 0.0f);
-        Float t, bb[3];
-        if (!s.tri_intersect(0, r, t, bb)) continue;
-        SurfaceInteraction isect; s.tri_fill_interaction(0, r, t, bb, true, isect);
-        tested++;
-        for (int j = 0; j < rays_per_tri; ++j) {
-            P2 uu; uu.x = rng.uniform_float(); uu.y = rng.uniform_float();
-            V3 w = uniform_sample_sphere(uu);
-            IData it; it.p = isect.p; it.p_error = isect.p_error; it.n = isect.n;
-            Ray rout = spawn_ray(it, w);
-            Float t2, b2[3];
-            if (s.tri_hit_params(0, rout, t2, b2)) failures++;
-            if (s.tri_intersect(0, rout, t2, b2)) failures++;
-            V3 p2; p2.x = pexp_(rng, 8.0f); p2.y = pexp_(rng, 8.0f); p2.z = pexp_(rng, 8.0f);
-            // spawn_rayto_point, interaction.rs:38-43
-            V3 d = p2 - it.p;
-            Ray r2(offset_ray_origin(it.p, it.p_error, it.n, d), d, 1.0f - SHADOW_EPSILON, 0.0f);
-            if (s.tri_hit_params(0, r2, t2, b2)) failures++;
-            if (s.tri_intersect(0, r2, t2, b2)) failures++;
-        }
-    }
-    if (n_tested) *n_tested = tested;
-    return failures;
-}
-}
-
-extern "C" {
-// tests/shapes.rs:421-487,538-565: full / partial sphere re-intersection with the reference's seeds RNG::new(0..n).
-int orc_test_sphere_reintersect(int n_seeds, int rays_per_shape, int partial, int *n_tested) {
-    int failures = 0, tested = 0;
-    for (int i = 0; i < n_seeds; ++i) {
-        RNG rng((uint64_t)i);
-        float radius = pexp_(rng, 4.0f);
-        float zmin = -radius, zmax = radius, phimax = 360.0f;
-        if (partial) {
-            zmin = (rng.uniform_float() < 0.5f) ? -radius : lerp(rng.uniform_float(), -radius, radius);
-            zmax = (rng.uniform_float() < 0.5f) ? radius : lerp(rng.uniform_float(), -radius, radius);
-            phimax = (rng.uniform_float() < 0.5f) ? 360.0f : rng.uniform_float() * 360.0f;
-        }
-        PtSphere S; std::memset(&S, 0, sizeof S);   // Sphere::new (sphere.rs:31-50)
-        for (int k = 0; k < 4; ++k) S.object_to_world[5 * k] = S.world_to_object[5 * k] = 1.0f;
-        S.radius = radius;
-        S.z_min = clampv(std::fmin(zmin, zmax), -radius, radius); S.z_max = clampv(std::fmax(zmin, zmax), -radius, radius);
-        S.theta_min = std::acos(clampv(std::fmin(zmin, zmax) / radius, -1.0f, 1.0f));
-        S.theta_max = std::acos(clampv(std::fmax(zmin, zmax) / radius, -1.0f, 1.0f));
-        S.phi_max = (PI / 180.0f) * clampv(phimax, 0.0f, 360.0f);
-        Scene s; s.spheres.push_back(S);
-        // test_reintersect_convex
-        V3 o; o.x = pexp_(rng, 8.0f); o.y = pexp_(rng, 8.0f); o.z = pexp_(rng, 8.0f);
-        Bounds3 bbox = s.sphere_world_bound(0);
-        V3 t; t.x = rng.uniform_float(); t.y = rng.uniform_float(); t.z = rng.uniform_float();
-        V3 p2 = bbox.lerp3(t);
-        Ray r(o, p2 - o, INF, 0.0f);
-        if (rng.uniform_float() < 0.5f) r.d = normalize(r.d);
-        SurfaceInteraction isect; Float thit;
-        if (!s.sphere_intersect(0, r, thit, isect, true)) continue;
-        tested++;
-        for (int j = 0; j < rays_per_shape; ++j) {
-            P2 u; u.x = rng.uniform_float(); u.y = rng.uniform_float();
-            V3 w = face_forward(uniform_sample_sphere(u), isect.n);
-            IData it; it.p = isect.p; it.p_error = isect.p_error; it.n = isect.n;
-            Ray rout = spawn_ray(it, w);
-            SurfaceInteraction tmp; Float th2;
-            if (s.sphere_intersect_p(0, rout)) failures++;
-            if (s.sphere_intersect(0, rout, th2, tmp, true)) failures++;
-            V3 p3; p3.x = pexp_(rng, 8.0f); p3.y = pexp_(rng, 8.0f); p3.z = pexp_(rng, 8.0f);
-            w = face_forward(p3 - isect.p, isect.n);
-            p3 = isect.p + w;
-            V3 d = p3 - it.p;
-            Ray r2(offset_ray_origin(it.p, it.p_error, it.n, d), d, 1.0f - SHADOW_EPSILON, 0.0f);
-            if (s.sphere_intersect_p(0, r2)) failures++;
-            // the reference overwrites `isect` here when the (unexpected) hit happens; it must not happen
-            if (s.sphere_intersect(0, r2, th2, tmp, true)) failures++;
-        }
-    }
-    if (n_tested) *n_tested = tested;
-    return failures;
-}
-}
-
-// ---- KAT hooks for the BSSRDF restatement (tests/test_oracle_kats.py) -------------------------------------------
-extern "C" {
-using namespace ref;
-static void kat_bssrdf(const PtBSSRDFTable *t, const float *sigma_a, const float *sigma_s, float eta, BssrdfTable &tb, TabulatedBSSRDF &b) {
-    tb.n_rho = (int)t->n_rho; tb.n_radius = (int)t->n_radius;
-    tb.rho_samples.assign(t->rho_samples, t->rho_samples + t->n_rho); tb.radius_samples.assign(t->radius_samples, t->radius_samples + t->n_radius);
-    tb.profile.assign(t->profile, t->profile + (size_t)t->n_rho * t->n_radius); tb.rhoeff.assign(t->rhoeff, t->rhoeff + t->n_rho);
-    tb.profile_cdf.assign(t->profile_cdf, t->profile_cdf + (size_t)t->n_rho * t->n_radius);
-    SurfaceInteraction si; si.p = V3(0, 0, 0); si.n = V3(0, 0, 1); si.sh_n = V3(0, 0, 1); si.sh_dpdu = V3(1, 0, 0);
-    b.init(si, 0, eta, RGB(sigma_a[0], sigma_a[1], sigma_a[2]), RGB(sigma_s[0], sigma_s[1], sigma_s[2]), &tb);
-}
-// Sr(r) and pdf_sr(ch, r) for n radii
-int orc_bssrdf_sr(const PtBSSRDFTable *t, const float *sigma_a, const float *sigma_s, float eta, uint32_t n, const float *r, float *sr3, float *pdf3) {
-    BssrdfTable tb; TabulatedBSSRDF b; kat_bssrdf(t, sigma_a, sigma_s, eta, tb, b);
-    for (uint32_t i = 0; i < n; ++i) {
-        RGB s = b.sr(r[i]);
-        for (int c = 0; c < 3; ++c) { sr3[3 * i + c] = s.c[c]; pdf3[3 * i + c] = b.pdf_sr(c, r[i]); }
-    }
-    return 0;
-}
-int orc_bssrdf_sample_sr(const PtBSSRDFTable *t, const float *sigma_a, const float *sigma_s, float eta, int ch, uint32_t n, const float *u, float *r) {
-    BssrdfTable tb; TabulatedBSSRDF b; kat_bssrdf(t, sigma_a, sigma_s, eta, tb, b);
-    for (uint32_t i = 0; i < n; ++i) r[i] = b.sample_sr(ch, u[i]);
-    return 0;
-}
-int orc_catmull_rom_weights(int size, const float *nodes, float x, int *offset, float *w4) {
-    return catmull_rom_weights(size, nodes, x, *offset, w4) ? 1 : 0;
-}
-float orc_bssrdf_sw(float eta, float cos_theta_) { return bssrdf_sw(eta, V3(std::sqrt(fmax_(0.0f, 1.0f - cos_theta_ * cos_theta_)), 0.0f, cos_theta_)); }
-}
-
-// ---- KAT hooks for light sampling (tests/test_oracle_kats.py) ----------------------------------------------------
-extern "C" {
-using namespace ref;
-// sample_li for n sample points u (2n floats) from the reference point (p, p_error, n); outputs wi (3n), pdf (n), L (3n)
-int orc_light_sample_li(orc_scene *h, uint32_t li, const float *p, const float *perr, const float *nrm, uint32_t n, const float *u,
-                        float *wi_out, float *pdf_out, float *L_out) {
-    LightSampler ls; ls.init(h->scene, PT_LS_UNIFORM);
-    IData ref; ref.p = V3(p[0], p[1], p[2]); ref.p_error = V3(perr[0], perr[1], perr[2]); ref.n = V3(nrm[0], nrm[1], nrm[2]);
-    for (uint32_t i = 0; i < n; ++i) {
-        V3 wi(0, 0, 0); Float pdf = 0.0f; IData p1;
-        RGB L = ls.sample_li(li, ref, P2(u[2 * i], u[2 * i + 1]), wi, pdf, p1);
-        wi_out[3 * i] = wi.x; wi_out[3 * i + 1] = wi.y; wi_out[3 * i + 2] = wi.z; pdf_out[i] = pdf;
-        for (int c = 0; c < 3; ++c) L_out[3 * i + c] = L.c[c];
-    }
-    return 0;
-}
-int orc_light_pdf_li(orc_scene *h, uint32_t li, const float *p, const float *perr, const float *nrm, uint32_t n, const float *wi, float *pdf_out) {
-    LightSampler ls; ls.init(h->scene, PT_LS_UNIFORM);
-    IData ref; ref.p = V3(p[0], p[1], p[2]); ref.p_error = V3(perr[0], perr[1], perr[2]); ref.n = V3(nrm[0], nrm[1], nrm[2]);
-    for (uint32_t i = 0; i < n; ++i) pdf_out[i] = ls.pdf_li(li, ref, V3(wi[3 * i], wi[3 * i + 1], wi[3 * i + 2]));
-    return 0;
-}
-}
-
-// ---- BSDF of a material at a canonical interaction, for the analytic lobe checks of tests/test_oracle_bsdf.py ---------------------------------
-// The material `mi` is evaluated as Material::compute_scattering_functions would at a point with geometric and shading normal +z, dpdu = +x,
-// dpdv = +y, no textures; then for each of n queries: f(wo, wi) and pdf(wo, wi) over all lobes (reflection.rs:1541-1600), and sample_f(wo, u)
-// (reflection.rs:1602-1689) -> sampled wi, its f, pdf and lobe type. Directions are world = local here.
-extern "C" {
-using namespace ref;
-int orc_bsdf_eval(orc_scene *h, uint32_t mi, uint32_t n, const float *wo, const float *wi, const float *u,
-                  float *f_out, float *pdf_out, float *s_wi_out, float *s_f_out, float *s_pdf_out, int32_t *s_type_out, int32_t *n_lobes_out) {
-    if (mi >= h->scene.materials.size()) return 1;
-    SurfaceInteraction si{};
-    si.p = V3(0, 0, 0); si.p_error = V3(0, 0, 0); si.n = V3(0, 0, 1); si.sh_n = V3(0, 0, 1); si.wo = V3(0, 0, 1);
-    si.dpdu = V3(1, 0, 0); si.dpdv = V3(0, 1, 0); si.sh_dpdu = V3(1, 0, 0); si.sh_dpdv = V3(0, 1, 0);
-    si.uv = P2(0.5f, 0.5f); si.has_shape = false; si.shape_flip = false; si.prim = 0;
-    BSDF bsdf;
-    if (!material_scattering_functions(h->scene, mi, si, bsdf, nullptr, nullptr, nullptr)) return 2;
-    if (n_lobes_out) *n_lobes_out = bsdf.n;
-    for (uint32_t i = 0; i < n; ++i) {
-        const V3 o(wo[3 * i], wo[3 * i + 1], wo[3 * i + 2]);
-        if (wi && f_out && pdf_out) {
-            const V3 w(wi[3 * i], wi[3 * i + 1], wi[3 * i + 2]);
-            const RGB f = bsdf.f(o, w, BSDF_ALL);
-            for (int c = 0; c < 3; ++c) f_out[3 * i + c] = f.c[c];
-            pdf_out[i] = bsdf.pdf(o, w, BSDF_ALL);
-        }
-        if (u && s_wi_out && s_f_out && s_pdf_out) {
-            V3 w(0, 0, 0); Float pdf = 0.0f; int sampled = 0;
-            const RGB f = bsdf.sample_f(o, w, P2(u[2 * i], u[2 * i + 1]), pdf, BSDF_ALL, sampled);
-            s_wi_out[3 * i] = w.x; s_wi_out[3 * i + 1] = w.y; s_wi_out[3 * i + 2] = w.z; s_pdf_out[i] = pdf;
-            for (int c = 0; c < 3; ++c) s_f_out[3 * i + c] = f.c[c];
-            if (s_type_out) s_type_out[i] = sampled;
-        }
-    }
-    return 0;
-}
-}
-
-// ---- tests/hg.rs restated (the reference's assertions on HenyeyGreenstein::p / sample_p, medium.rs:149-193), run inside the oracle ----
-extern "C" {
-using namespace ref;
-// tests/hg.rs:12-32 sampling_match: RNG::default(), g = -0.75 .. 0.75 step 0.25, 100 samples each; returns max |p0 - p(wo, wi)| / p
-double orc_test_hg_sampling_match(void) {
-    HaltonTables::Pcg32 rng;   // RNG::default()
-    auto uf = [&]() { return fmin_(ONE_MINUS_EPSILON, (Float)rng.uniform_int32() * 0x1.0p-32f); };
-    double worst = 0.0;
-    for (Float g = -0.75f; g <= 0.75f; g += 0.25f)
-        for (int i = 0; i < 100; ++i) {
-            const Float a = uf(), b = uf();
-            const V3 wo = uniform_sample_sphere(P2(a, b));
-            V3 wi;
-            const Float u0 = uf(), u1 = uf();
-            const Float p0 = hg_sample_p(g, wo, wi, P2(u0, u1));
-            const Float p1 = phase_hg(dot(wo, wi), g);
-            worst = std::max(worst, (double)std::fabs(p0 - p1) / (double)std::fabs(p1));
-        }
-    return worst;
-}
-// tests/hg.rs:34-79 sampling_orientation_forward / sample_orientation_backward: wo = (-1, 0, 0), 100 samples, counts wi.x > 0
-void orc_test_hg_orientation(float g, int *nforward, int *nbackward) {
-    HaltonTables::Pcg32 rng;
-    auto uf = [&]() { return fmin_(ONE_MINUS_EPSILON, (Float)rng.uniform_int32() * 0x1.0p-32f); };
-    *nforward = *nbackward = 0;
-    for (int i = 0; i < 100; ++i) {
-        const Float u0 = uf(), u1 = uf();
-        V3 wi;
-        hg_sample_p(g, V3(-1.0f, 0.0f, 0.0f), wi, P2(u0, u1));
-        if (wi.x > 0.0f) ++*nforward; else ++*nbackward;
-    }
-}
-// tests/hg.rs:81-103 normalized: per g, the mean of p(wo, wi) over 100 000 uniform directions (expected 1 / 4 pi)
-void orc_test_hg_normalized(double *means7) {
-    HaltonTables::Pcg32 rng;
-    auto uf = [&]() { return fmin_(ONE_MINUS_EPSILON, (Float)rng.uniform_int32() * 0x1.0p-32f); };
-    int k = 0;
-    for (Float g = -0.75f; g <= 0.75f; g += 0.25f, ++k) {
-        const Float a = uf(), b = uf();
-        const V3 wo = uniform_sample_sphere(P2(a, b));
-        Float sum = 0.0f;
-        const int n = 100000;
-        for (int i = 0; i < n; ++i) { const Float c = uf(), d = uf(); sum += phase_hg(dot(wo, uniform_sample_sphere(P2(c, d))), g); }
-        means7[k] = (double)(sum / (Float)n);
-    }
-}
 }  // extern "C"

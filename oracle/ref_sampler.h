@@ -85,20 +85,6 @@ inline Float sobol_sample_float(uint64_t a, int dimension, uint32_t scramble) {
 struct HaltonTables {   // PRIMES / PRIME_SUMS (lowdiscrepancy.rs:9-192) and compute_radical_inverse_permutations (:359-378)
     std::vector<uint32_t> primes, sums;
     std::vector<uint16_t> perm;
-    struct Pcg32 {      // rng.rs:17-58
-        uint64_t state = 0x853c49e6748fea9bull, inc = 0xda3e39cb94b95bdbull;
-        uint32_t uniform_int32() {
-            uint64_t old = state;
-            state = old * 0x5851f42d4c957f2dull + inc;
-            uint32_t xorshifted = (uint32_t)(((old >> 18) ^ old) >> 27);
-            uint32_t rot = (uint32_t)(old >> 59);
-            return (xorshifted >> rot) | (xorshifted << ((~rot + 1u) & 31));
-        }
-        uint32_t uniform_int32_2(uint32_t b) {
-            uint32_t threshold = (~b + 1u) % b;
-            for (;;) { uint32_t r = uniform_int32(); if (r >= threshold) return r % b; }
-        }
-    };
     HaltonTables() {
         for (uint32_t c = 2; primes.size() < 1000; ++c) {
             bool is_prime = true;
@@ -108,12 +94,12 @@ struct HaltonTables {   // PRIMES / PRIME_SUMS (lowdiscrepancy.rs:9-192) and com
         uint32_t total = 0;
         for (uint32_t q : primes) { sums.push_back(total); total += q; }
         perm.resize(total);
-        Pcg32 rng;   // RNG::default()
+        RNG rng;   // RNG::default()
         uint32_t p = 0;
         for (size_t i = 0; i < primes.size(); ++i) {
             for (uint32_t j = 0; j < primes[i]; ++j) perm[p + j] = (uint16_t)j;
             for (uint32_t j = 0; j < primes[i]; ++j) {   // shuffle(.., count = PRIMES[i], 1, rng) (sampling.rs:178-186)
-                uint32_t other = j + rng.uniform_int32_2(primes[i] - j);
+                uint32_t other = j + rng.uniform_u32_bounded(primes[i] - j);
                 std::swap(perm[p + j], perm[p + other]);
             }
             p += primes[i];

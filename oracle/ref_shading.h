@@ -321,4 +321,15 @@ struct LightSampler {
     bool is_delta(uint32_t li) const { uint32_t t = scene->lights[li].type; return t == PT_LIGHT_DISTANT || t == PT_LIGHT_POINT || t == PT_LIGHT_SPOT; }
 };
 
+// ---- shared by the transport of ref_render.cpp and the probes / reference-test loops of ref_kats.cpp --------------------
+struct TabulatedBSSRDF; struct TexCtx;   // ref_bssrdf.h, ref_texture.h
+// ref_render.cpp. Returns false when the material leaves `si.bsdf == None` (null surface, path.rs:124-129).
+bool material_scattering_functions(const Scene &scene, uint32_t mi, SurfaceInteraction &si, BSDF &bsdf,
+                                   TabulatedBSSRDF *bssrdf, bool *has_bssrdf, const TexCtx *tctx);
+inline Float phase_hg(Float cos_theta, Float g) {   // medium.rs:149-154
+    Float denom = 1.0f + g * g + 2.0f * g * cos_theta;
+    return INV4_PI * (1.0f - g * g) / (denom * std::sqrt(denom));
+}
+Float hg_sample_p(Float g, V3 wo, V3 &wi, P2 u);   // medium.rs:173-193, ref_render.cpp
+
 }  // namespace ref

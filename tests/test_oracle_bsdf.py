@@ -38,9 +38,6 @@ class Bsdf:
         self.sd, self.mi = _material_scene(pkg, kind, kw)
         self.s = oracle.scene(self.sd)
         self.fn = oracle.lib.orc_bsdf_eval
-        fp, ip = self.A.fp, C.POINTER(C.c_int32)
-        self.fn.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, fp, fp, fp, fp, fp, fp, fp, fp, ip, ip]
-        self.fn.restype = C.c_int
 
     def _p(self, a):
         return a.ctypes.data_as(self.A.fp)

@@ -136,8 +136,6 @@ def test_triangle_badcase(oracle, pkg):
 
 def test_triangle_reintersect_property(oracle):
     # tests/shapes.rs:173-224 with the same seeds RNG::new(0..999) and the reference's 10 000 spawned ray pairs per triangle
-
-    oracle.lib.orc_test_triangle_reintersect.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int)]
     n = C.c_int()
     failures = oracle.lib.orc_test_triangle_reintersect(1000, 10000, C.byref(n))
     assert n.value > 100
@@ -207,7 +205,6 @@ def test_furnace_closed_form(oracle, pkg):
 def test_sphere_reintersect_property(oracle):
     # tests/shapes.rs:472-487 (full) and :538-565 (partial), seeds RNG::new(0..99); 2 000 ray pairs per sphere here
     f = oracle.lib.orc_test_sphere_reintersect
-    f.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
     for partial in (0, 1):
         n = C.c_int()
         failures = f(100, 2000, partial, C.byref(n))
@@ -575,7 +572,6 @@ def test_sobol_pixel_samples_are_a_02_net(oracle, pkg, pixel):
 
 def test_hg_sampling_match_twin(oracle):
     """tests/hg.rs:12-32 sampling_match: sample_p's return value is p(wo, wi) (relative 1e-4), RNG::default(), g = -0.75 .. 0.75."""
-    oracle.lib.orc_test_hg_sampling_match.restype = C.c_double
     assert oracle.lib.orc_test_hg_sampling_match() < 1.0e-4
 
 
@@ -583,7 +579,6 @@ def test_hg_sampling_orientation_twin(oracle):
     """tests/hg.rs:34-79 sampling_orientation_forward / sample_orientation_backward: with wo = (-1, 0, 0), g = 0.95 scatters to
     wi.x > 0 more than ten times as often as not, g = -0.95 the other way round (pins the sign convention of sample_p)."""
     f, b = C.c_int(), C.c_int()
-    oracle.lib.orc_test_hg_orientation.argtypes = [C.c_float, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     oracle.lib.orc_test_hg_orientation(0.95, C.byref(f), C.byref(b))
     assert f.value + b.value == 100 and f.value > 10 * b.value
     oracle.lib.orc_test_hg_orientation(-0.95, C.byref(f), C.byref(b))
@@ -605,7 +600,6 @@ def test_efloat_containment_twin(oracle, op, name):
     """tests/fp.rs:125-226: for RNG::new(trial), trial = 0 .. 999 999, the exact f64 result of the operation on values drawn from inside
     the operands' intervals lies inside the result's interval (EFloat is what bounds Sphere::intersect's hit error, row a14)."""
     n = C.c_int()
-    oracle.lib.orc_test_efloat.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int)]
     failures = oracle.lib.orc_test_efloat(op, 1000000, C.byref(n))
     assert n.value > 400000 and failures == 0, (name, failures, n.value)
 
@@ -657,7 +651,6 @@ def test_triangle_sampling_twin(oracle):
     > 0 -- on the oracle's restatements (oracle/ref_kats_shapes.cpp runs the loops)."""
     n = 30
     out = (C.c_double * (4 * n))()
-    oracle.lib.orc_test_triangle_sampling.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_double)]
     assert oracle.lib.orc_test_triangle_sampling(n, 512 * 1024, out) == 0
     compared = sum(1 for i in range(n) if out[4 * i + 3] == 1.0)
     assert compared >= 25                                                     # the reference skips only tiny solid angles
@@ -669,7 +662,6 @@ def test_triangle_solid_angle_twin(oracle):
     Triangle::solid_angle -- Girard's theorem, triangle.rs:586-624 -- within 1.5 %."""
     n = 50
     out = (C.c_double * (3 * n))()
-    oracle.lib.orc_test_triangle_solid_angle.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_double)]
     assert oracle.lib.orc_test_triangle_solid_angle(n, 64 * 1024, out) == 0
     assert sum(1 for i in range(n) if out[3 * i] > 0.0) >= 45 and max(out[3 * i + 2] for i in range(n)) < 0.015
 
@@ -692,7 +684,6 @@ def test_sphere_solid_angle_twin(pkg, oracle):
     b.ctm = _test_transform(pkg)
     b.sphere(radius=1.0, zmin=-1.0, zmax=1.0, phimax=360.0)
     out = (C.c_double * 4)()
-    oracle.lib.orc_test_sphere_solid_angle.argtypes = [C.POINTER(pkg._abi.PtSphere), C.c_int, C.POINTER(C.c_double)]
     assert oracle.lib.orc_test_sphere_solid_angle(C.byref(b.spheres[0]), 128 * 1024, out) == 0
     assert abs(out[0] - 4 * np.pi) < 0.01 and out[1] == np.float32(4.0) * np.float32(np.pi) and abs(out[2] - out[3]) < 0.001 and 0.2 < out[3] < 2.0
 
@@ -704,7 +695,6 @@ def test_disk_solid_angle_twin(pkg, oracle):
     b.ctm = _test_transform(pkg)
     b.disk(height=0.0, radius=1.25, innerradius=0.0, phimax=360.0)
     out = (C.c_double * 2)()
-    oracle.lib.orc_test_disk_solid_angle.argtypes = [C.POINTER(pkg._abi.PtSphere), C.c_int, C.POINTER(C.c_double)]
     assert oracle.lib.orc_test_disk_solid_angle(C.byref(b.spheres[0]), 128 * 1024, out) == 0
     assert abs(out[0] - out[1]) < 0.001 and out[0] > 0.1
 
@@ -723,7 +713,6 @@ def test_oracle_counts_the_asserts_the_reference_would_panic_on(pkg, oracle):
 def _watertight(oracle, n_seeds, as_written):
     fn = oracle.lib.orc_test_triangle_watertight
     fp = C.POINTER(C.c_float)
-    fn.argtypes = [C.c_int, C.c_int, fp, C.POINTER(C.c_uint32), fp, fp, C.POINTER(C.c_int)]
     v = np.zeros((256, 3), np.float32); idx = np.zeros((420, 3), np.uint32)
     ro = np.zeros((2 * n_seeds, 3), np.float32); rd = np.zeros((2 * n_seeds, 3), np.float32); nh = np.zeros(2 * n_seeds, np.int32)
     failures = fn(n_seeds, as_written, v.ctypes.data_as(fp), idx.ctypes.data_as(C.POINTER(C.c_uint32)), ro.ctypes.data_as(fp), rd.ctypes.data_as(fp),
@@ -752,7 +741,6 @@ def test_triangle_watertight_twin(oracle):
 def test_float_bits_twin(oracle):
     # tests/fp.rs:46-57: RNG::new(1), 100 000 draws, float_to_bits(bits_to_float(ui)) == ui for every non-NaN pattern
     n = C.c_int()
-    oracle.lib.orc_test_float_bits.argtypes = [C.c_int, C.POINTER(C.c_int)]
     assert oracle.lib.orc_test_float_bits(100000, C.byref(n)) == 0
     assert 99000 < n.value <= 100000      # 2^24 - 2 of 2^32 patterns are NaNs: ~390 of the 100 000
 
@@ -792,7 +780,6 @@ def test_scrambled_radical_inverse_twin(oracle):
     """tests/sampling.rs:24-53 scrambled_radical_inverse_test (the Halton sampler's dimensions >= 2): 128 bases, RNG::new(dim)-shuffled permutations, the test's seven indices.
     The Rust test drops its `relative_eq!` and its hand-rolled expectation is broken (oracle/ref_kats.cpp); the twin asserts the function against the exact digit sum."""
     worst = C.c_double()
-    oracle.lib.orc_test_scrambled_radical_inverse.argtypes = [C.c_int, C.POINTER(C.c_double)]
     assert oracle.lib.orc_test_scrambled_radical_inverse(128, C.byref(worst)) == 0
     assert worst.value < 1.0e-6
 
@@ -801,6 +788,5 @@ def test_partial_sphere_normal_twin(oracle):
     """tests/shapes.rs:490-535 partial_sphere_normal: 10 000 seeds of random partial spheres; at every hit Sphere::intersect finds, the normal points along the hit point
     (the Rust file's dropped `relative_eq!(1.0, dot, epsilon = 1e-5)` as an assertion)."""
     n = C.c_int(); worst = C.c_double()
-    oracle.lib.orc_test_partial_sphere_normal.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]
     assert oracle.lib.orc_test_partial_sphere_normal(10000, C.byref(n), C.byref(worst)) == 0
     assert n.value > 3000 and worst.value <= 1.0e-5

@@ -7,7 +7,6 @@ from _pkg import import_pkg
 from oracle.oracle_binding import Oracle
 pkg = import_pkg()
 orc = Oracle(pkg._abi, pkg.runtime.TABLES_PATH)
-orc.lib.orc_test_triangle_reintersect.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int)]
 n = C.c_int(); t0 = time.time()
 failures = orc.lib.orc_test_triangle_reintersect(1000, 10000, C.byref(n))
 print(json.dumps(dict(test="tests/shapes.rs:173-224 triangle_reintersect", seeds=1000, rays_per_triangle=10000, triangles_hit=n.value, failures=failures, seconds=round(time.time() - t0, 1))))
