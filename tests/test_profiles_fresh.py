@@ -1,6 +1,6 @@
 """tools/check_profiles.py as a test: the round's committed profile record must belong to the code in the tree -- every file under
 profiles/r6/final/, every record of profiles/pmc_traffic.json and the numbers DESIGN.md section 7 quotes from them. A change to the device sources after the
-record was taken turns this test red until the record is re-taken (tools/r6_profiles.sh): stale evidence fails loudly instead of being quoted."""
+record was taken turns this test red until the record is re-taken (tools/profile_record.py final and pmc): stale evidence fails loudly instead of being quoted."""
 import json
 import os
 import subprocess

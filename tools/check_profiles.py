@@ -52,12 +52,12 @@ def check(strict=False, rnd=ROUND):
     d = final_dir(rnd)
     mpath = os.path.join(d, "MANIFEST.json")
     if not os.path.exists(mpath):
-        return [f"{os.path.relpath(mpath, ROOT)} does not exist: round {rnd} has no final record yet (tools/r{rnd}_profiles.sh final)"]
+        return [f"{os.path.relpath(mpath, ROOT)} does not exist: round {rnd} has no final record yet (tools/profile_record.py final)"]
     man = json.load(open(mpath))
     h = man["code_hash"]
     live = code_hash(ROOT)
     if strict and h != live:
-        bad.append(f"profiles/r{rnd}/final was taken on code {h}, the tree is {live}: re-take it (tools/r{rnd}_profiles.sh final + pmc) or the numbers quoted from it describe other code")
+        bad.append(f"profiles/r{rnd}/final was taken on code {h}, the tree is {live}: re-take it (tools/profile_record.py final, and pmc <config> for each config) or the numbers quoted from it describe other code")
     on_disk = {os.path.relpath(f, d) for f in glob.glob(os.path.join(d, "**", "*"), recursive=True) if os.path.isfile(f)} - {"MANIFEST.json"}
     for f in sorted(on_disk - set(man["files"])):
         bad.append(f"final/{f} is not in the manifest (copied in from another run?)")
