@@ -4,7 +4,6 @@ import ctypes as C
 import importlib
 import os
 import subprocess
-import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SAN = bool(os.environ.get("PT_SAN"))   # ASan/UBSan build of the oracle (tools/san_cpu_tests.sh preloads the sanitizer runtimes)
@@ -96,84 +95,38 @@ class Oracle:
             build()
         self.A = abi
         self.AO = importlib.import_module("._abi_ao", abi.__package__)   # the ctypes mirror of include/mi355ao.h beside `abi`
-        lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in signatures(abi, self.AO).items():
-            fn = getattr(lib, name); fn.restype = res; fn.argtypes = args
+        lib = abi.bind(C.CDLL(LIB_PATH), table=signatures(abi, self.AO))
         if lib.orc_load_tables(tables_path.encode()) != 0:
             raise RuntimeError("oracle: cannot load " + tables_path)
         self.lib = lib
+        self.Scene = _scene_class(importlib.import_module(".runtime", abi.__package__).Handle)   # (the package beside `abi`: its directory's name is no identifier)
 
     def scene(self, scene_data):
-        return OracleScene(self, scene_data)
+        return self.Scene(self, scene_data)
 
 
-def _fp(A, a):
-    return a.ctypes.data_as(A.fp)
+def _assert_ok(st, what=""):
+    assert st == 0, st
 
 
-class OracleScene:
-    def __init__(self, orc, scene_data):
-        self.O = orc; self.A = orc.A; self.data = scene_data
-        self.h = C.c_void_p()
-        d = scene_data.desc()
-        st = orc.lib.orc_scene_create(C.byref(d), C.byref(self.h))
-        assert st == 0, st
+def _scene_class(handle):
+    class OracleScene(handle):
+        """orc_scene handle: runtime.Handle's entry points on the oracle, every status asserted."""
+        PREFIX = LIB_PREFIX = "orc_"
 
-    def close(self):
-        if self.h:
-            self.O.lib.orc_scene_destroy(self.h); self.h = C.c_void_p()
+        def __init__(self, orc, scene_data):
+            self.O = orc
+            super().__init__(orc.lib, _assert_ok, scene_data)
 
-    def __del__(self):
-        try: self.close()
-        except Exception: pass
+        @property
+        def _ao(self):
+            return self.O.lib
 
-    def bvh(self):
-        A = self.A
-        nn, npr = C.c_uint32(), C.c_uint32()
-        self.O.lib.orc_scene_bvh_info(self.h, C.byref(nn), C.byref(npr))
-        nodes = (A.PtBVHNode * nn.value)(); ordered = np.zeros(npr.value, dtype=np.uint32)
-        self.O.lib.orc_scene_bvh_read(self.h, nodes, ordered.ctypes.data_as(A.u32p))
-        return nodes, ordered
+        def render(self, rp, nthreads=1, ao=None):
+            """The un-normalised film (H, W, 4), as runtime.Scene.render, on `nthreads` threads."""
+            return super().render(rp, ao=ao, last=nthreads)
 
-    def render(self, rp, nthreads=1, ao=None):
-        """The un-normalised film (H, W, 4), as runtime.Scene.render: rp.integrator == PT_INTEGRATOR_AO renders with orc_ao_render
-        and `ao` (a PtAOParams), else the scene's own (scene_data.ao_params())."""
-        cb = rp.cropped_pixel_bounds
-        w, h = cb[2] - cb[0], cb[3] - cb[1]
-        film = np.zeros((h, w, 4), dtype=np.float32)
-        if rp.integrator == self.O.AO.PT_INTEGRATOR_AO:
-            ao = self.data.ao_params() if ao is None else ao
-            st = self.O.lib.orc_ao_render(self.h, C.byref(rp), C.byref(ao), _fp(self.A, film), nthreads)
-        else:
-            st = self.O.lib.orc_render(self.h, C.byref(rp), _fp(self.A, film), nthreads)
-        assert st == 0, st
-        return film
+        def seconds(self):
+            return self.O.lib.orc_last_render_seconds(self.h)
 
-    def seconds(self):
-        return self.O.lib.orc_last_render_seconds(self.h)
-
-    def resolve(self, film, scale=1.0):
-        out = np.zeros(film.shape[:-1] + (3,), dtype=np.float32)
-        self.O.lib.orc_film_resolve(_fp(self.A, film), film.size // 4, scale, _fp(self.A, out))
-        return out
-
-    def counters(self):
-        c = self.A.PtCounters()
-        self.O.lib.orc_get_counters(self.h, C.byref(c))
-        return c.as_dict()
-
-    def trace_closest(self, o, d, tmax):
-        A = self.A
-        o, d, tmax = (np.ascontiguousarray(x, dtype=np.float32) for x in (o, d, tmax))
-        n = len(tmax)
-        prim = np.zeros(n, np.uint32); t = np.zeros(n, np.float32); b = np.zeros((n, 3), np.float32)
-        self.O.lib.orc_trace_closest(self.h, n, _fp(A, o), _fp(A, d), _fp(A, tmax), prim.ctypes.data_as(A.u32p), _fp(A, t), _fp(A, b))
-        return prim, t, b
-
-    def trace_any(self, o, d, tmax):
-        A = self.A
-        o, d, tmax = (np.ascontiguousarray(x, dtype=np.float32) for x in (o, d, tmax))
-        n = len(tmax)
-        hit = np.zeros(n, np.uint8)
-        self.O.lib.orc_trace_any(self.h, n, _fp(A, o), _fp(A, d), _fp(A, tmax), hit.ctypes.data_as(A.u8p))
-        return hit
+    return OracleScene

@@ -182,10 +182,10 @@ ENTRY_POINTS = {
 }
 
 
-def bind(lib, table=ENTRY_POINTS, prefix_from="pt_", prefix_to="pt_", strict=True):
+def bind(lib, table=ENTRY_POINTS, strict=True):
     """Attach restype/argtypes; raises AttributeError if a declared symbol is missing (strict=False: an older library variant of an A/B run may lack the newest entry points)."""
     for name, (res, args) in table.items():
-        fn = getattr(lib, name.replace(prefix_from, prefix_to, 1), None)
+        fn = getattr(lib, name, None)
         if fn is None:
             if strict:
                 raise AttributeError(f"{name}: symbol declared in " + ("include/mi355pt.h" if table is ENTRY_POINTS else "its C header") + " is missing from the library")

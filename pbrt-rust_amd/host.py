@@ -110,31 +110,32 @@ def _matmul(a, b):
     return (a.astype(F) @ b.astype(F)).astype(F)
 
 
-def box_filter_table(radius=(0.5, 0.5)):
-    return np.ones(256, dtype=F)  # filters/boxfilter.rs:19-21
+def _f3(v):
+    """A scalar or a 3-vector as c_float[3]."""
+    return (C.c_float * 3)(v, v, v) if np.isscalar(v) else (C.c_float * 3)(*v)
 
 
-def gaussian_filter_table(radius=(2.0, 2.0), alpha=2.0):  # filters/gaussian.rs:15-36 + film.rs:76-89
-    t = np.zeros(256, dtype=F)
-    a = F(alpha)
-    ex, ey = F(math.exp(-a * F(radius[0]) * F(radius[0]))), F(math.exp(-a * F(radius[1]) * F(radius[1])))
-    for y in range(16):
-        for x in range(16):
-            px = (F(x) + F(0.5)) * F(radius[0]) / F(16)
-            py = (F(y) + F(0.5)) * F(radius[1]) / F(16)
-            gx = max(F(0), F(math.exp(-a * px * px)) - ex)
-            gy = max(F(0), F(math.exp(-a * py * py)) - ey)
-            t[y * 16 + x] = F(gx) * F(gy)
-    return t
+def _v3(v):
+    """A scalar or a 3-vector as a float32 array."""
+    return np.asarray([v] * 3 if np.isscalar(v) else v, dtype=F)
+
+
+def _f16(m):
+    """A 4x4 matrix as c_float[16], row major."""
+    return (C.c_float * 16).from_buffer_copy(np.ascontiguousarray(m, dtype=F))
 
 
 def filter_table(kind, radius, alpha=2.0, B=1.0 / 3.0, Cc=1.0 / 3.0, tau=3.0):
     """Film::new's 16x16 table (film.rs:76-89) of filters/{boxfilter,gaussian,triangle,mitchell,sinc}.rs, each `evaluate` as written
     there (the Mitchell polynomial's `6B*30C` term and the sinc window that is zero INSIDE the radius included)."""
-    if kind == "box": return box_filter_table()
-    if kind == "gaussian": return gaussian_filter_table(radius, alpha)
     rx, ry = F(radius[0]), F(radius[1])
-    if kind == "triangle":
+    if kind == "box":
+        ev = lambda x, y: F(1)
+    elif kind == "gaussian":   # gaussian.rs:15-36
+        a = F(alpha)
+        ex, ey = F(math.exp(-a * rx * rx)), F(math.exp(-a * ry * ry))
+        ev = lambda x, y: F(max(F(0), F(math.exp(-a * x * x)) - ex)) * F(max(F(0), F(math.exp(-a * y * y)) - ey))
+    elif kind == "triangle":
         ev = lambda x, y: max(F(0), rx - abs(x)) * max(F(0), ry - abs(y))
     elif kind == "mitchell":
         B, Cc = F(B), F(Cc)
@@ -161,6 +162,34 @@ def filter_table(kind, radius, alpha=2.0, B=1.0 / 3.0, Cc=1.0 / 3.0, tau=3.0):
         for x in range(16):
             t[y * 16 + x] = F(ev((F(x) + F(0.5)) * rx / F(16), (F(y) + F(0.5)) * ry / F(16)))
     return t
+
+
+_MATERIAL_KINDS = dict(matte=A.PT_MAT_MATTE, mirror=A.PT_MAT_MIRROR, glass=A.PT_MAT_GLASS, plastic=A.PT_MAT_PLASTIC,
+                       metal=A.PT_MAT_METAL, uber=A.PT_MAT_UBER, substrate=A.PT_MAT_SUBSTRATE,
+                       subsurface=A.PT_MAT_SUBSURFACE, kdsubsurface=A.PT_MAT_SUBSURFACE, translucent=A.PT_MAT_TRANSLUCENT, mix=A.PT_MAT_MIX, disney=A.PT_MAT_DISNEY)
+
+_MATERIAL_DEFAULTS = dict(  # create_*_material defaults
+    matte=dict(Kd=0.5, sigma=0.0), mirror=dict(Kr=0.9), glass=dict(Kr=1.0, Kt=1.0, eta=1.5, uroughness=0.0, vroughness=0.0),
+    plastic=dict(Kd=0.25, Ks=0.25, roughness=0.1), metal=dict(roughness=0.01, uroughness=-1.0, vroughness=-1.0),
+    uber=dict(Kd=0.25, Ks=0.25, Kr=0.0, Kt=0.0, roughness=0.1, uroughness=-1.0, vroughness=-1.0, opacity=1.0, eta=1.5),
+    substrate=dict(Kd=0.5, Ks=0.5, uroughness=0.1, vroughness=0.1),
+    # translucent.rs:82-92 (reflect -> kr, transmit -> kt)
+    translucent=dict(Kd=0.25, Ks=0.25, reflect=0.5, transmit=0.5, roughness=0.1),
+    # mix.rs:52-56; the two materials are given as material ids
+    mix=dict(amount=0.5, namedmaterial1=None, namedmaterial2=None),
+    # disney.rs:842-887
+    disney=dict(color=0.5, metallic=0.0, eta=1.5, roughness=0.5, speculartint=0.0, anisotropic=0.0, sheen=0.0, sheentint=0.5, clearcoat=0.0,
+                clearcoatgloss=1.0, spectrans=0.0, scatterdistance=0.0, thin=False, flatness=0.0, difftrans=0.0),
+    # subsurface.rs:108-139 / kdsubsurface.rs:106-126
+    subsurface=dict(Kr=1.0, Kt=1.0, eta=1.33, uroughness=0.0, vroughness=0.0, scale=1.0, g=0.0, name="",
+                    sigma_a=(0.0011, 0.0024, 0.014), sigma_s=(2.55, 3.21, 3.77)),
+    kdsubsurface=dict(Kr=1.0, Kt=1.0, eta=1.33, uroughness=0.0, vroughness=0.0, scale=1.0, g=0.0, Kd=0.5, mfp=1.0))
+
+# material parameter -> (PT_MP_* texture slot, is a float texture)
+_TEXTURE_SLOTS = dict(Kd=(A.PT_MP_KD, 0), Ks=(A.PT_MP_KS, 0), Kr=(A.PT_MP_KR, 0), Kt=(A.PT_MP_KT, 0), reflect=(A.PT_MP_KR, 0), transmit=(A.PT_MP_KT, 0), amount=(A.PT_MP_KD, 0), color=(A.PT_MP_KD, 0), opacity=(A.PT_MP_OPACITY, 0),
+                      eta_rgb=(A.PT_MP_ETA_RGB, 0), k=(A.PT_MP_K_RGB, 0), sigma_a=(A.PT_MP_SIGMA_A, 0), sigma_s=(A.PT_MP_SIGMA_S, 0), mfp=(A.PT_MP_MFP, 0),
+                      sigma=(A.PT_MP_SIGMA, 1), roughness=(A.PT_MP_ROUGHNESS, 1), uroughness=(A.PT_MP_U_ROUGHNESS, 1),
+                      vroughness=(A.PT_MP_V_ROUGHNESS, 1), eta=(A.PT_MP_ETA, 1), bumpmap=(A.PT_MP_BUMP, 1))
 
 
 class SceneBuilder:
@@ -230,14 +259,14 @@ class SceneBuilder:
             from . import bssrdf as B
             if preset in B.NAMED_MEDIA and sigma_a == (0.0011, 0.0024, 0.014) and sigma_s == (2.55, 3.21, 3.77): sigma_s, sigma_a = B.NAMED_MEDIA[preset]
         m = A.PtMedium()
-        m.sigma_a = (C.c_float * 3)(*[float(F(x) * F(scale)) for x in sigma_a]); m.sigma_s = (C.c_float * 3)(*[float(F(x) * F(scale)) for x in sigma_s]); m.g = float(g)
+        m.sigma_a = _f3([F(x) * F(scale) for x in sigma_a]); m.sigma_s = _f3([F(x) * F(scale) for x in sigma_s]); m.g = float(g)
         m.type = A.PT_MEDIUM_HOMOGENEOUS
         if density is not None:   # "heterogeneous" (api.rs:723-752): GridDensityMedium over [p0, p1] of the CTM's space
             d = np.ascontiguousarray(density, dtype=F)
             nz, ny, nx = d.shape          # density[z][y][x]
             med2w = self.ctm * Transform.translate(tuple(float(x) for x in p0)) * Transform.scale(float(p1[0]) - float(p0[0]), float(p1[1]) - float(p0[1]), float(p1[2]) - float(p0[2]))
             m.type = A.PT_MEDIUM_GRID; m.nx, m.ny, m.nz = nx, ny, nz
-            m.world_to_medium = (C.c_float * 16)(*med2w.m_inv.flatten())
+            m.world_to_medium = _f16(med2w.m_inv)
             m.density = d.ctypes.data_as(A.fp)
             self._keep.append(d)         # the struct points into the array
         self.media.append(m); self.named_media[name] = len(self.media) - 1
@@ -274,99 +303,74 @@ class SceneBuilder:
             self.material_id = None
             return
         m = A.PtMaterial()
-        kinds = dict(matte=A.PT_MAT_MATTE, mirror=A.PT_MAT_MIRROR, glass=A.PT_MAT_GLASS, plastic=A.PT_MAT_PLASTIC,
-                     metal=A.PT_MAT_METAL, uber=A.PT_MAT_UBER, substrate=A.PT_MAT_SUBSTRATE,
-                     subsurface=A.PT_MAT_SUBSURFACE, kdsubsurface=A.PT_MAT_SUBSURFACE, translucent=A.PT_MAT_TRANSLUCENT, mix=A.PT_MAT_MIX, disney=A.PT_MAT_DISNEY)
-        m.type = kinds[kind]
-        d = dict(  # create_*_material defaults
-            matte=dict(Kd=0.5, sigma=0.0), mirror=dict(Kr=0.9), glass=dict(Kr=1.0, Kt=1.0, eta=1.5, uroughness=0.0, vroughness=0.0),
-            plastic=dict(Kd=0.25, Ks=0.25, roughness=0.1), metal=dict(roughness=0.01, uroughness=-1.0, vroughness=-1.0),
-            uber=dict(Kd=0.25, Ks=0.25, Kr=0.0, Kt=0.0, roughness=0.1, uroughness=-1.0, vroughness=-1.0, opacity=1.0, eta=1.5),
-            substrate=dict(Kd=0.5, Ks=0.5, uroughness=0.1, vroughness=0.1),
-            translucent=dict(Kd=0.25, Ks=0.25, reflect=0.5, transmit=0.5, roughness=0.1),
-            mix=dict(amount=0.5, namedmaterial1=None, namedmaterial2=None),
-            # disney.rs:842-887
-            disney=dict(color=0.5, metallic=0.0, eta=1.5, roughness=0.5, speculartint=0.0, anisotropic=0.0, sheen=0.0, sheentint=0.5, clearcoat=0.0,
-                        clearcoatgloss=1.0, spectrans=0.0, scatterdistance=0.0, thin=False, flatness=0.0, difftrans=0.0),   # mix.rs:52-56; the two materials are given as material ids
-   # translucent.rs:82-92 (reflect -> kr, transmit -> kt)
-            # subsurface.rs:108-139 / kdsubsurface.rs:106-126
-            subsurface=dict(Kr=1.0, Kt=1.0, eta=1.33, uroughness=0.0, vroughness=0.0, scale=1.0, g=0.0, name="",
-                            sigma_a=(0.0011, 0.0024, 0.014), sigma_s=(2.55, 3.21, 3.77)),
-            kdsubsurface=dict(Kr=1.0, Kt=1.0, eta=1.33, uroughness=0.0, vroughness=0.0, scale=1.0, g=0.0, Kd=0.5, mfp=1.0))[kind]
+        m.type = _MATERIAL_KINDS[kind]
+        d = dict(_MATERIAL_DEFAULTS[kind])
         d.update(kw)
         # a parameter given as a string names a texture ("texture Kd" "name"); the constant field then keeps the default
         m.tex = (C.c_int32 * 16)(*([-1] * 16))
-        slots = dict(Kd=(A.PT_MP_KD, 0), Ks=(A.PT_MP_KS, 0), Kr=(A.PT_MP_KR, 0), Kt=(A.PT_MP_KT, 0), reflect=(A.PT_MP_KR, 0), transmit=(A.PT_MP_KT, 0), amount=(A.PT_MP_KD, 0), color=(A.PT_MP_KD, 0), opacity=(A.PT_MP_OPACITY, 0),
-                     eta_rgb=(A.PT_MP_ETA_RGB, 0), k=(A.PT_MP_K_RGB, 0), sigma_a=(A.PT_MP_SIGMA_A, 0), sigma_s=(A.PT_MP_SIGMA_S, 0), mfp=(A.PT_MP_MFP, 0),
-                     sigma=(A.PT_MP_SIGMA, 1), roughness=(A.PT_MP_ROUGHNESS, 1), uroughness=(A.PT_MP_U_ROUGHNESS, 1),
-                     vroughness=(A.PT_MP_V_ROUGHNESS, 1), eta=(A.PT_MP_ETA, 1), bumpmap=(A.PT_MP_BUMP, 1))
         for key in list(kw):
-            if isinstance(kw[key], str) and key in slots:
-                slot, is_float = slots[key]
+            if isinstance(kw[key], str) and key in _TEXTURE_SLOTS:
+                slot, is_float = _TEXTURE_SLOTS[key]
                 table = self.float_textures if is_float else self.spectrum_textures
                 if kw[key] not in table: raise KeyError(f"texture {kw[key]!r} not declared ({'float' if is_float else 'spectrum'})")
-                if kind == "subsurface" and d.get("name") and key in ("sigma_a", "sigma_s"): pass   # (an explicit parameter overrides the named medium's value, subsurface.rs:127-128)
                 m.tex[slot] = table[kw[key]]
                 d.pop(key)   # keep the create_*_material default in the constant field
-        if kind == "metal" and m.tex[A.PT_MP_ROUGHNESS] >= 0:   # metal.rs: uroughness/vroughness fall back to "roughness"
-            for sl in (A.PT_MP_U_ROUGHNESS, A.PT_MP_V_ROUGHNESS):
-                if m.tex[sl] < 0 and "uroughness" not in kw and "vroughness" not in kw: pass
-        three = lambda v: (C.c_float * 3)(*([float(v)] * 3 if np.isscalar(v) else [float(x) for x in v]))
-        m.kd = three(d.get("Kd", d.get("amount", d.get("color", 0)))); m.ks = three(d.get("Ks", 0)); m.kr = three(d.get("Kr", d.get("reflect", 0))); m.kt = three(d.get("Kt", d.get("transmit", 0)))
-        m.opacity = three(d.get("opacity", 1)); m.eta_rgb = three(d.get("eta_rgb", (0.2, 0.92, 1.1))); m.k_rgb = three(d.get("k", (3.9, 2.45, 2.14)))
+        m.kd = _f3(d.get("Kd", d.get("amount", d.get("color", 0)))); m.ks = _f3(d.get("Ks", 0)); m.kr = _f3(d.get("Kr", d.get("reflect", 0))); m.kt = _f3(d.get("Kt", d.get("transmit", 0)))
+        m.opacity = _f3(d.get("opacity", 1)); m.eta_rgb = _f3(d.get("eta_rgb", (0.2, 0.92, 1.1))); m.k_rgb = _f3(d.get("k", (3.9, 2.45, 2.14)))
         m.sigma = d.get("sigma", 0.0); m.eta = d.get("eta", 1.5); m.roughness = d.get("roughness", 0.1)
         m.u_roughness = d.get("uroughness", -1.0); m.v_roughness = d.get("vroughness", -1.0)
         m.remap_roughness = 1 if d.get("remaproughness", True) else 0
-        if m.type == A.PT_MAT_SUBSURFACE:
-            from . import bssrdf as B
-            g = float(d["g"])
-            if kind == "subsurface":
-                siga, sigs = d.get("sigma_a", (0.0011, 0.0024, 0.014)), d.get("sigma_s", (2.55, 3.21, 3.77))   # (a textured parameter keeps the default in the constant field)
-                if d["name"]:  # subsurface.rs:111-122: a named medium overrides the defaults and forces g = 0
-                    if d["name"] in B.NAMED_MEDIA:
-                        sigs, siga = B.NAMED_MEDIA[d["name"]]
-                        if "sigma_a" in kw: siga = kw["sigma_a"]
-                        if "sigma_s" in kw: sigs = kw["sigma_s"]
-                        g = 0.0
-                table = B.compute_beam_diffusion_bssrdf(g, float(d["eta"]))
-                m.scale = float(d["scale"])
-            elif m.tex[A.PT_MP_KD] >= 0 or m.tex[A.PT_MP_MFP] >= 0:   # kdsubsurface.rs:96-99 with a textured Kd / mfp: the conversion runs at every hit
-                table = B.compute_beam_diffusion_bssrdf(g, float(d["eta"]))
-                m.kd_subsurface = 1; m.scale = float(d["scale"])
-                m.kd = three(d.get("Kd", 0.5)); m.mfp = three(d.get("mfp", 1.0))
-                siga, sigs = (0.0, 0.0, 0.0), (0.0, 0.0, 0.0)
-            else:  # kdsubsurface.rs:96-99: mfp * scale, then subsurface_from_diffuse (constant textures -> host side)
-                table = B.compute_beam_diffusion_bssrdf(g, float(d["eta"]))
-                three_np = lambda v: np.asarray([v] * 3 if np.isscalar(v) else v, dtype=F)
-                mfree = np.maximum(three_np(d["mfp"]), F(0)) * F(d["scale"])
-                siga, sigs = B.subsurface_from_diffuse(table, np.maximum(three_np(d["Kd"]), F(0)), mfree)
-                m.scale = 1.0
-            m.sigma_a = three(siga); m.sigma_s = three(sigs)
-            for i, t in enumerate(self.bssrdf_tables):
-                if t is table: m.bssrdf_table = i; break
-            else:
-                self.bssrdf_tables.append(table); m.bssrdf_table = len(self.bssrdf_tables) - 1
-        if kind == "disney":
-            sdv = np.asarray([d["scatterdistance"]] * 3 if np.isscalar(d["scatterdistance"]) else d["scatterdistance"], dtype=F)
-            m.disney_scatter = (C.c_float * 3)(*[float(x) for x in sdv])
-            if np.any(sdv != 0) and isinstance(kw.get("color"), str): raise NotImplementedError("disney: textured color together with scatterdistance")
-            names = ("metallic", "speculartint", "anisotropic", "sheen", "sheentint", "clearcoat", "clearcoatgloss", "spectrans", "flatness", "difftrans")
-            if any(isinstance(d[n], str) for n in names): raise NotImplementedError("textured disney parameters other than color / eta / roughness")
-            m.disney = (C.c_float * 10)(*[float(d[n]) for n in names]); m.disney_thin = 1 if d["thin"] else 0
-        if kind == "mix":
-            ids = (d["namedmaterial1"], d["namedmaterial2"])
-            for i in ids:
-                if not isinstance(i, int) or not (0 <= i < len(self.materials)) or self.materials[i].type in (A.PT_MAT_MIX, A.PT_MAT_SUBSURFACE): raise ValueError("mix needs the ids of two plain materials")
-            m.mix = (C.c_uint32 * 2)(*ids)
-            m.tex[A.PT_MP_BUMP] = self.materials[ids[0]].tex[A.PT_MP_BUMP]   # mix.rs:31-45: only material 1's bump map survives
+        if m.type == A.PT_MAT_SUBSURFACE: self._subsurface_tail(m, kind, d, kw)
+        elif kind == "disney": self._disney_tail(m, d, kw)
+        elif kind == "mix": self._mix_tail(m, d)
         self.materials.append(m)
         self.material_id = len(self.materials) - 1
+
+    def _subsurface_tail(self, m, kind, d, kw):
+        """sigma_a / sigma_s / scale and the BSSRDF table of "subsurface" and "kdsubsurface"."""
+        from . import bssrdf as B
+        named = kind == "subsurface" and d["name"] and d["name"] in B.NAMED_MEDIA   # subsurface.rs:111-122: a named medium overrides the defaults and forces g = 0
+        table = B.compute_beam_diffusion_bssrdf(0.0 if named else float(d["g"]), float(d["eta"]))
+        m.scale = float(d["scale"])
+        if kind == "subsurface":
+            siga, sigs = d.get("sigma_a", (0.0011, 0.0024, 0.014)), d.get("sigma_s", (2.55, 3.21, 3.77))   # (a textured parameter keeps the default in the constant field)
+            if named:
+                sigs, siga = B.NAMED_MEDIA[d["name"]]
+                if "sigma_a" in kw: siga = kw["sigma_a"]   # (an explicit parameter overrides the named medium's value, subsurface.rs:127-128)
+                if "sigma_s" in kw: sigs = kw["sigma_s"]
+        elif m.tex[A.PT_MP_KD] >= 0 or m.tex[A.PT_MP_MFP] >= 0:   # kdsubsurface.rs:96-99 with a textured Kd / mfp: the conversion runs at every hit
+            m.kd_subsurface = 1
+            m.kd = _f3(d.get("Kd", 0.5)); m.mfp = _f3(d.get("mfp", 1.0))
+            siga, sigs = (0.0, 0.0, 0.0), (0.0, 0.0, 0.0)
+        else:  # kdsubsurface.rs:96-99: mfp * scale, then subsurface_from_diffuse (constant textures -> host side)
+            mfree = np.maximum(_v3(d["mfp"]), F(0)) * F(d["scale"])
+            siga, sigs = B.subsurface_from_diffuse(table, np.maximum(_v3(d["Kd"]), F(0)), mfree)
+            m.scale = 1.0
+        m.sigma_a = _f3(siga); m.sigma_s = _f3(sigs)
+        for i, t in enumerate(self.bssrdf_tables):
+            if t is table: m.bssrdf_table = i; break
+        else:
+            self.bssrdf_tables.append(table); m.bssrdf_table = len(self.bssrdf_tables) - 1
+
+    def _disney_tail(self, m, d, kw):
+        sdv = _v3(d["scatterdistance"])
+        m.disney_scatter = _f3(sdv)
+        if np.any(sdv != 0) and isinstance(kw.get("color"), str): raise NotImplementedError("disney: textured color together with scatterdistance")
+        names = ("metallic", "speculartint", "anisotropic", "sheen", "sheentint", "clearcoat", "clearcoatgloss", "spectrans", "flatness", "difftrans")
+        if any(isinstance(d[n], str) for n in names): raise NotImplementedError("textured disney parameters other than color / eta / roughness")
+        m.disney = (C.c_float * 10)(*[float(d[n]) for n in names]); m.disney_thin = 1 if d["thin"] else 0
+
+    def _mix_tail(self, m, d):
+        ids = (d["namedmaterial1"], d["namedmaterial2"])
+        for i in ids:
+            if not isinstance(i, int) or not (0 <= i < len(self.materials)) or self.materials[i].type in (A.PT_MAT_MIX, A.PT_MAT_SUBSURFACE): raise ValueError("mix needs the ids of two plain materials")
+        m.mix = (C.c_uint32 * 2)(*ids)
+        m.tex[A.PT_MP_BUMP] = self.materials[ids[0]].tex[A.PT_MP_BUMP]   # mix.rs:31-45: only material 1's bump map survives
 
     # -- textures (api.rs pbrt_texture; textures/*.rs create_* functions)
     def _const_tex(self, value):
         t = A.PtTexture(); t.type = A.PT_TEX_CONSTANT; t.child = (C.c_int32 * 3)(-1, -1, -1)
-        v = [float(value)] * 3 if np.isscalar(value) else [float(x) for x in value]
-        t.value = (C.c_float * 3)(*v)
+        t.value = _f3(value)
         self.textures.append(t); return len(self.textures) - 1
 
     def _child(self, v, is_float):
@@ -380,21 +384,20 @@ class SceneBuilder:
         t.mapping = dict(uv=A.PT_MAP_UV, planar=A.PT_MAP_PLANAR, spherical=A.PT_MAP_SPHERICAL, cylindrical=A.PT_MAP_CYLINDRICAL)[kind]
         t.su, t.sv = float(kw.get("uscale", 1.0)), float(kw.get("vscale", 1.0))
         t.du, t.dv = float(kw.get("udelta", 0.0)), float(kw.get("vdelta", 0.0))
-        t.vs = (C.c_float * 3)(*[float(x) for x in kw.get("v1", (1, 0, 0))]); t.vt = (C.c_float * 3)(*[float(x) for x in kw.get("v2", (0, 1, 0))])
-        t.world_to_texture = (C.c_float * 16)(*self.ctm.m_inv.flatten())
+        t.vs = _f3(kw.get("v1", (1, 0, 0))); t.vt = _f3(kw.get("v2", (0, 1, 0)))
+        t.world_to_texture = _f16(self.ctm.m_inv)
 
     def texture(self, name, kind, cls, **kw):
         """Texture "name" "color|spectrum|float" "class" params.  Image maps take `pixels` (h, w, 3; top row first, as
         read_image returns) instead of a filename."""
         is_float = kind == "float"
         t = A.PtTexture(); t.child = (C.c_int32 * 3)(-1, -1, -1)
-        one = 1.0
         if cls == "constant":
             t.type = A.PT_TEX_CONSTANT
-            v = kw.get("value", 1.0); t.value = (C.c_float * 3)(*([float(v)] * 3 if np.isscalar(v) else [float(x) for x in v]))
+            t.value = _f3(kw.get("value", 1.0))
         elif cls == "scale":
             t.type = A.PT_TEX_SCALE
-            t.child = (C.c_int32 * 3)(self._child(kw.get("tex1", one), is_float), self._child(kw.get("tex2", one), is_float), -1)
+            t.child = (C.c_int32 * 3)(self._child(kw.get("tex1", 1.0), is_float), self._child(kw.get("tex2", 1.0), is_float), -1)
         elif cls == "mix":
             t.type = A.PT_TEX_MIX
             t.child = (C.c_int32 * 3)(self._child(kw.get("tex1", 0.0), is_float), self._child(kw.get("tex2", 1.0), is_float), self._child(kw.get("amount", 0.5), True))
@@ -405,7 +408,7 @@ class SceneBuilder:
                 t.type = A.PT_TEX_CHECKERBOARD2D; self._mapping(t, kw)
                 t.aa_closedform = 0 if kw.get("aamode", "none") == "none" else 1
             else:
-                t.type = A.PT_TEX_CHECKERBOARD3D; t.world_to_texture = (C.c_float * 16)(*self.ctm.m_inv.flatten())
+                t.type = A.PT_TEX_CHECKERBOARD3D; t.world_to_texture = _f16(self.ctm.m_inv)
         elif cls == "imagemap":
             from . import textures as T
             t.type = A.PT_TEX_IMAGEMAP; self._mapping(t, kw)
@@ -422,11 +425,11 @@ class SceneBuilder:
         elif cls == "bilerp":
             t.type = A.PT_TEX_BILERP; self._mapping(t, kw)
             for nm, dv in (("v00", 0.0), ("v01", 1.0), ("v10", 0.0), ("v11", 1.0)):
-                v = kw.get(nm, dv); setattr(t, nm, (C.c_float * 3)(*([float(v)] * 3 if np.isscalar(v) else [float(x) for x in v])))
+                setattr(t, nm, _f3(kw.get(nm, dv)))
         elif cls in ("fbm", "wrinkled", "windy", "marble"):   # IdentityMapping3D(texture-to-world CTM)
             if cls == "marble" and is_float: raise ValueError("marble textures are spectrum-only (textures/marble.rs:68-70)")
             t.type = dict(fbm=A.PT_TEX_FBM, wrinkled=A.PT_TEX_WRINKLED, windy=A.PT_TEX_WINDY, marble=A.PT_TEX_MARBLE)[cls]
-            t.world_to_texture = (C.c_float * 16)(*self.ctm.m_inv.flatten())
+            t.world_to_texture = _f16(self.ctm.m_inv)
             t.octaves = int(kw.get("octaves", 8)); t.omega = float(kw.get("roughness", 0.5))
             t.marble_scale = float(kw.get("scale", 1.0)); t.variation = float(kw.get("variation", 0.2))
         elif cls == "dots":
@@ -443,19 +446,19 @@ class SceneBuilder:
     def light_source(self, kind, **kw):
         l = A.PtLight()
         l2w = self.ctm
-        l.light_to_world = (C.c_float * 16)(*l2w.m.flatten()); l.world_to_light = (C.c_float * 16)(*l2w.m_inv.flatten())
+        l.light_to_world = _f16(l2w.m); l.world_to_light = _f16(l2w.m_inv)
         l.prim = A.PT_NONE
         sc = kw.get("scale", 1.0)
         if kind == "distant":  # distant.rs:124-132
             L = np.asarray(kw.get("L", (1, 1, 1)), dtype=F) * F(sc)
             frm, to = np.asarray(kw.get("from_", (0, 0, 0)), dtype=F), np.asarray(kw.get("to", (0, 0, 1)), dtype=F)
             w = l2w.vector(frm - to); w = w / np.sqrt((w * w).sum(dtype=F))
-            l.type = A.PT_LIGHT_DISTANT; l.L = (C.c_float * 3)(*L); l.dir = (C.c_float * 3)(*w)
+            l.type = A.PT_LIGHT_DISTANT; l.L = _f3(L); l.dir = _f3(w)
         elif kind == "point":  # point.rs:99-106 (translation quirk P.x,P.y,P.x -- App. A #15)
             I = np.asarray(kw.get("I", (1, 1, 1)), dtype=F) * F(sc)
             p = np.asarray(kw.get("from_", (0, 0, 0)), dtype=F)
             t = l2w * Transform.translate((p[0], p[1], p[0]))
-            l.type = A.PT_LIGHT_POINT; l.L = (C.c_float * 3)(*I); l.pos = (C.c_float * 3)(*t.point((0, 0, 0)))
+            l.type = A.PT_LIGHT_POINT; l.L = _f3(I); l.pos = _f3(t.point((0, 0, 0)))
         elif kind == "spot":  # spot.rs:118-147
             I = np.asarray(kw.get("I", (1, 1, 1)), dtype=F) * F(sc)
             frm, to = np.asarray(kw.get("from_", (0, 0, 0)), dtype=F), np.asarray(kw.get("to", (0, 0, 1)), dtype=F)
@@ -466,9 +469,9 @@ class SceneBuilder:
             dv = np.cross(d.astype(np.float64), du.astype(np.float64)).astype(F)
             mat = np.eye(4, dtype=F); mat[0, :3] = du; mat[1, :3] = dv; mat[2, :3] = d
             t = l2w * Transform.translate(frm) * Transform(mat).inverse()
-            l.type = A.PT_LIGHT_SPOT; l.L = (C.c_float * 3)(*I); l.pos = (C.c_float * 3)(*t.point((0, 0, 0)))
+            l.type = A.PT_LIGHT_SPOT; l.L = _f3(I); l.pos = _f3(t.point((0, 0, 0)))
             l.cos_total_width = math.cos(F(math.pi / 180.0) * coneangle); l.cos_falloff_start = math.cos(F(math.pi / 180.0) * (coneangle - conedelta))
-            l.light_to_world = (C.c_float * 16)(*t.m.flatten()); l.world_to_light = (C.c_float * 16)(*t.m_inv.flatten())
+            l.light_to_world = _f16(t.m); l.world_to_light = _f16(t.m_inv)
         elif kind == "infinite":  # infinite.rs:243-259, constant-L map = 1x1 texel
             L = np.asarray(kw.get("L", (1, 1, 1)), dtype=F) * F(sc)
             l.type = A.PT_LIGHT_INFINITE
@@ -489,9 +492,9 @@ class SceneBuilder:
 
     def _new_area_light(self, prim_index):  # api.rs:1531-1546: one DiffuseAreaLight per shape
         l = A.PtLight(); l.type = A.PT_LIGHT_DIFFUSE_AREA
-        l.L = (C.c_float * 3)(*self.area_light["L"]); l.two_sided = 1 if self.area_light["twosided"] else 0
+        l.L = _f3(self.area_light["L"]); l.two_sided = 1 if self.area_light["twosided"] else 0
         l.prim = prim_index
-        l.light_to_world = (C.c_float * 16)(*self.ctm.m.flatten()); l.world_to_light = (C.c_float * 16)(*self.ctm.m_inv.flatten())
+        l.light_to_world = _f16(self.ctm.m); l.world_to_light = _f16(self.ctm.m_inv)
         self.lights.append(l)
         return len(self.lights) - 1
 
@@ -513,64 +516,55 @@ class SceneBuilder:
             if isinstance(v, str): return self.float_textures[v]
             return self._const_tex(0.0) if float(v) == 0.0 else -1
         self.tri_alpha.append(np.full(nt, mask(alpha), dtype=np.int32)); self.tri_shadow_alpha.append(np.full(nt, mask(shadowalpha), dtype=np.int32))
-        first_prim = self.nprims
-        self.prim_shape.append((np.uint32(A.PT_SHAPE_TRIANGLE << 30) | (np.arange(nt, dtype=np.uint32) + np.uint32(self.ntris))).astype(np.uint32))
-        mid = A.PT_NONE if self.material_id is None else self.material_id
-        self.prim_material.append(np.full(nt, mid, dtype=np.uint32))
-        self._prim_media(nt)
-        if self.area_light is None or self.current_object is not None:  # api.rs:1605-1608: area lights inside instances are dropped
-            self.prim_light.append(np.full(nt, A.PT_NONE, dtype=np.uint32))
-        else:
-            self.prim_light.append(np.array([self._new_area_light(first_prim + t) for t in range(nt)], dtype=np.uint32))
-        if self.current_object is None: self.top_refs.append(np.arange(first_prim, first_prim + nt, dtype=np.uint32))
-        else: self.objects[self.current_object][1] += nt
-        self.nverts += nv; self.ntris += nt; self.nprims += nt
+        first_prim = self._add_prims((np.uint32(A.PT_SHAPE_TRIANGLE << 30) | (np.arange(nt, dtype=np.uint32) + np.uint32(self.ntris))).astype(np.uint32), nt)
+        self.nverts += nv; self.ntris += nt
         return first_prim
+
+    def _add_prims(self, shape_refs, n):
+        """The primitives of one shape (api.rs:1493-1619): their material, media and area lights (one DiffuseAreaLight per primitive), and their
+        place among the top-level primitives or in the object being defined. Returns the first one's index."""
+        first_prim = self.nprims
+        self.prim_shape.append(shape_refs)
+        self.prim_material.append(np.full(n, A.PT_NONE if self.material_id is None else self.material_id, dtype=np.uint32))
+        self._prim_media(n)
+        if self.area_light is None or self.current_object is not None:  # api.rs:1605-1608: area lights inside instances are dropped
+            self.prim_light.append(np.full(n, A.PT_NONE, dtype=np.uint32))
+        else:
+            self.prim_light.append(np.array([self._new_area_light(first_prim + t) for t in range(n)], dtype=np.uint32))
+        if self.current_object is None: self.top_refs.append(np.arange(first_prim, first_prim + n, dtype=np.uint32))
+        else: self.objects[self.current_object][1] += n
+        self.nprims += n
+        return first_prim
+
+    def _quadric(self, phimax):
+        """A new entry of the sphere table with what sphere and disk share filled in, as one primitive: (the PtSphere, its primitive index).
+        `phimax`: float32 degrees, clamped by the caller as its shape's constructor does."""
+        s = A.PtSphere()
+        s.object_to_world = _f16(self.ctm.m); s.world_to_object = _f16(self.ctm.m_inv)
+        s.phi_max = F(math.pi / 180.0) * F(phimax)
+        s.reverse_orientation = 1 if self.reverse_orientation else 0
+        s.transform_swaps_handedness = 1 if self.ctm.swaps_handedness() else 0
+        self.spheres.append(s)
+        return s, self._add_prims(np.array([(A.PT_SHAPE_SPHERE << 30) | (len(self.spheres) - 1)], dtype=np.uint32), 1)
 
     def sphere(self, radius=1.0, zmin=None, zmax=None, phimax=360.0):
         """shapes/sphere.rs:31-50,424-431."""
         r = F(radius)
         zmin = -r if zmin is None else F(zmin); zmax = r if zmax is None else F(zmax)
         clampf = lambda v, lo, hi: lo if v < lo else (hi if v > hi else v)
-        s = A.PtSphere()
-        s.object_to_world = (C.c_float * 16)(*self.ctm.m.flatten()); s.world_to_object = (C.c_float * 16)(*self.ctm.m_inv.flatten())
+        s, first_prim = self._quadric(clampf(F(phimax), F(0), F(360)))
         s.radius = r
         s.z_min = clampf(min(zmin, zmax), -r, r); s.z_max = clampf(max(zmin, zmax), -r, r)
         s.theta_min = math.acos(clampf(min(zmin, zmax) / r, F(-1), F(1))); s.theta_max = math.acos(clampf(max(zmin, zmax) / r, F(-1), F(1)))
-        s.phi_max = F(math.pi / 180.0) * F(clampf(F(phimax), F(0), F(360)))
-        s.reverse_orientation = 1 if self.reverse_orientation else 0
-        s.transform_swaps_handedness = 1 if self.ctm.swaps_handedness() else 0
-        self.spheres.append(s)
-        first_prim = self.nprims
-        self.prim_shape.append(np.array([(A.PT_SHAPE_SPHERE << 30) | (len(self.spheres) - 1)], dtype=np.uint32))
-        self.prim_material.append(np.array([A.PT_NONE if self.material_id is None else self.material_id], dtype=np.uint32))
-        self._prim_media(1)
-        self.prim_light.append(np.array([A.PT_NONE if (self.area_light is None or self.current_object is not None) else self._new_area_light(first_prim)], dtype=np.uint32))
-        if self.current_object is None: self.top_refs.append(np.array([first_prim], dtype=np.uint32))
-        else: self.objects[self.current_object][1] += 1
-        self.nprims += 1
+        return first_prim
+
+    def disk(self, height=0.0, radius=1.0, innerradius=0.0, phimax=360.0):
+        """shapes/disk.rs:17-43,175-189: stored in the sphere table with kind = PT_QUADRIC_DISK (z_min = z_max = height)."""
+        s, first_prim = self._quadric(min(max(F(phimax), F(0)), F(360)))
+        s.kind = A.PT_QUADRIC_DISK; s.radius = F(radius); s.inner_radius = F(innerradius); s.z_min = s.z_max = F(height)
         return first_prim
 
     # -- instancing (api.rs:1630-1713)
-    def disk(self, height=0.0, radius=1.0, innerradius=0.0, phimax=360.0):
-        """shapes/disk.rs:17-43,175-189: stored in the sphere table with kind = PT_QUADRIC_DISK (z_min = z_max = height)."""
-        s = A.PtSphere()
-        s.object_to_world = (C.c_float * 16)(*self.ctm.m.flatten()); s.world_to_object = (C.c_float * 16)(*self.ctm.m_inv.flatten())
-        s.kind = A.PT_QUADRIC_DISK; s.radius = F(radius); s.inner_radius = F(innerradius); s.z_min = s.z_max = F(height)
-        s.phi_max = F(math.pi / 180.0) * F(min(max(F(phimax), F(0)), F(360)))
-        s.reverse_orientation = 1 if self.reverse_orientation else 0
-        s.transform_swaps_handedness = 1 if self.ctm.swaps_handedness() else 0
-        self.spheres.append(s)
-        first_prim = self.nprims
-        self.prim_shape.append(np.array([(A.PT_SHAPE_SPHERE << 30) | (len(self.spheres) - 1)], dtype=np.uint32))
-        self.prim_material.append(np.array([A.PT_NONE if self.material_id is None else self.material_id], dtype=np.uint32))
-        self._prim_media(1)
-        self.prim_light.append(np.array([A.PT_NONE if (self.area_light is None or self.current_object is not None) else self._new_area_light(first_prim)], dtype=np.uint32))
-        if self.current_object is None: self.top_refs.append(np.array([first_prim], dtype=np.uint32))
-        else: self.objects[self.current_object][1] += 1
-        self.nprims += 1
-        return first_prim
-
     def object_begin(self, name):
         self.attribute_begin()
         self.objects[name] = [self.nprims, 0]
@@ -588,7 +582,7 @@ class SceneBuilder:
             self.object_list.append((name, first, n))
         oid = [o[0] for o in self.object_list].index(name)
         inst = A.PtInstance(); inst.object = oid
-        inst.instance_to_world = (C.c_float * 16)(*self.ctm.m.flatten()); inst.world_to_instance = (C.c_float * 16)(*self.ctm.m_inv.flatten())
+        inst.instance_to_world = _f16(self.ctm.m); inst.world_to_instance = _f16(self.ctm.m_inv)
         self.instances.append(inst)
         self.top_refs.append(np.array([A.PT_TOP_INSTANCE | (len(self.instances) - 1)], dtype=np.uint32))
 
@@ -623,8 +617,8 @@ class SceneBuilder:
         s2r = (Transform.scale(xres, yres, 1) * Transform.scale(F(1) / (sw[1] - sw[0]), F(1) / (sw[2] - sw[3]), 1) *
                Transform.translate((-sw[0], -sw[3], 0)))
         r2c = c2s.inverse() * s2r.inverse()
-        rp.raster_to_camera = (C.c_float * 16)(*r2c.m.flatten())
-        rp.camera_to_world = (C.c_float * 16)(*self.cam["c2w"].m.flatten())
+        rp.raster_to_camera = _f16(r2c.m)
+        rp.camera_to_world = _f16(self.cam["c2w"].m)
         rp.lens_radius = self.cam["lensradius"]; rp.focal_distance = self.cam["focaldistance"]
         rp.shutter_open = self.cam["shutteropen"]; rp.shutter_close = self.cam["shutterclose"]
         rp.max_depth = self.integ["maxdepth"]; rp.rr_threshold = self.integ["rrthreshold"]
@@ -639,6 +633,20 @@ class SceneBuilder:
         return rp
 
 
+def _triangle(L, up, vp):
+    """MIPMap::triangle (mipmap.rs:295-327) on the pyramid level `L` at every (u, v) of the grid `vp` x `up` (float32 arrays): the bilinear
+    lookup with Repeat wrap, in RGBSpectrum arithmetic summed as written there (tmp4 + tmp3 + tmp2 + tmp1)."""
+    lh, lw, _ = L.shape
+    one = F(1.0)
+    sx = (up * F(lw) - F(0.5)).astype(F); ty = (vp * F(lh) - F(0.5)).astype(F)
+    s0 = np.floor(sx).astype(np.int64); t0 = np.floor(ty).astype(np.int64)
+    ds = (sx - s0.astype(F)).astype(F)[None, :]; dt = (ty - t0.astype(F)).astype(F)[:, None]
+    tx = lambda si, ti: L[np.mod(ti, lh)[:, None], np.mod(si, lw)[None, :]].astype(F)   # texel(level, s, t), Repeat
+    rgb = ((tx(s0, t0) * ((one - ds) * (one - dt))[..., None] + tx(s0, t0 + 1) * ((one - ds) * dt)[..., None]).astype(F)
+           + tx(s0 + 1, t0) * (ds * (one - dt))[..., None]).astype(F)
+    return (rgb + tx(s0 + 1, t0 + 1) * (ds * dt)[..., None]).astype(F)
+
+
 def _env_power_lookup(tex):
     """`map.lookup((.5, .5), .5)` of InfiniteAreaLight::power (infinite.rs:103-109): MIPMap::lookup with width 0.5 is
     level = levels - 2 (exactly, delta = 0) -> `triangle(levels - 2, st)`; the texel for a 1x1 map (mipmap.rs:202-223)."""
@@ -646,20 +654,15 @@ def _env_power_lookup(tex):
     levels, w, h = T.build_mipmap(tex, "repeat")
     n = len(levels)
     if n == 1: return levels[0][0, 0].astype(F)
-    lv = levels[n - 2]; lh, lw, _ = lv.shape
-    s = F(F(0.5) * F(lw) - F(0.5)); t = F(F(0.5) * F(lh) - F(0.5))
-    s0, t0 = int(math.floor(s)), int(math.floor(t)); ds, dt = F(s - F(s0)), F(t - F(t0))
-    tx = lambda a, b: lv[b % lh, a % lw].astype(F)
-    r = (tx(s0, t0) * F(F(1 - ds) * F(1 - dt)) + tx(s0, t0 + 1) * F(F(1 - ds) * dt)).astype(F)
-    r = (r + tx(s0 + 1, t0) * F(ds * F(1 - dt))).astype(F)
-    return (r + tx(s0 + 1, t0 + 1) * F(ds * dt)).astype(F)
+    half = np.array([0.5], dtype=F)
+    return _triangle(levels[n - 2], half, half)[0, 0]
 
 
 def _env_importance(tex):
     """lights/infinite.rs:62-81 importance image (2w x 2h): `map.lookup(st, fwidth).y() * sin(theta)` with
     fwidth = 0.5 / min(2w, 2h).  MIPMap::lookup (mipmap.rs:202-223) picks level = levels - 1 + log2(fwidth)
     = log2(max(w,h)/min(w,h)) - 2: negative for power-of-two maps with aspect <= 2:1 -> `triangle(0, st)`, the level-0 bilinear
-    lookup with Repeat wrap (mipmap.rs:295-327); for wider maps `lerp(delta, triangle(ilevel), triangle(ilevel + 1))` on the pyramid
+    lookup with Repeat wrap; for wider maps `lerp(delta, triangle(ilevel), triangle(ilevel + 1))` on the pyramid
     (delta is exactly 0 for power-of-two sizes; the arithmetic is kept as written).  Non-power-of-two maps arrive here already
     resampled (`light_source`), so `tex` is level 0 of the reference's pyramid."""
     from . import textures as T
@@ -672,28 +675,15 @@ def _env_importance(tex):
     y_w = np.array([0.212671, 0.715160, 0.072169], dtype=F)
     up = ((np.arange(W, dtype=F) + F(0.5)) / F(W)).astype(F)
     vp = ((np.arange(H, dtype=F) + F(0.5)) / F(H)).astype(F)
-    one = F(1.0)
-
-    def triangle(lv):
-        lv = min(max(lv, 0), len(levels) - 1)
-        L = levels[lv]; lh, lw, _ = L.shape
-        sx = (up * F(lw) - F(0.5)).astype(F); ty = (vp * F(lh) - F(0.5)).astype(F)
-        s0 = np.floor(sx).astype(np.int64); t0 = np.floor(ty).astype(np.int64)
-        ds = (sx - s0.astype(F)).astype(F)[None, :]; dt = (ty - t0.astype(F)).astype(F)[:, None]
-        tx = lambda si, ti: L[np.mod(ti, lh)[:, None], np.mod(si, lw)[None, :]].astype(F)   # texel(level, s, t), Repeat
-        # RGBSpectrum arithmetic first (tmp4 + tmp3 + tmp2 + tmp1), then y(), exactly as `triangle(..).y()`
-        rgb = ((tx(s0, t0) * ((one - ds) * (one - dt))[..., None] + tx(s0, t0 + 1) * ((one - ds) * dt)[..., None]).astype(F)
-               + tx(s0 + 1, t0) * (ds * (one - dt))[..., None]).astype(F)
-        return (rgb + tx(s0 + 1, t0 + 1) * (ds * dt)[..., None]).astype(F)
-
+    triangle = lambda lv: _triangle(levels[min(max(lv, 0), len(levels) - 1)], up, vp)
     fwidth = F(F(0.5) / F(min(W, H)))
     level = F(F(len(levels) - 1) + F(np.log2(max(fwidth, F(1.0e-8)))))
     if level < 0: rgb = triangle(0)
     elif level >= len(levels) - 1: rgb = np.broadcast_to(levels[-1][0, 0].astype(F), (H, W, 3)).copy()
     else:
         il = int(np.floor(level)); delta = F(level - F(il))
-        rgb = (triangle(il) * F(one - delta) + triangle(il + 1) * delta).astype(F)
-    img = ((y_w[0] * rgb[..., 0] + y_w[1] * rgb[..., 1]).astype(F) + y_w[2] * rgb[..., 2]).astype(F)
+        rgb = (triangle(il) * F(F(1.0) - delta) + triangle(il + 1) * delta).astype(F)
+    img = ((y_w[0] * rgb[..., 0] + y_w[1] * rgb[..., 1]).astype(F) + y_w[2] * rgb[..., 2]).astype(F)   # `.y()` after the RGB arithmetic
     sin_theta = np.sin(F(math.pi) * (np.arange(H, dtype=F) + F(0.5)) / F(H)).astype(F)
     return np.ascontiguousarray(img * sin_theta[:, None], dtype=F)
 
@@ -702,10 +692,10 @@ class SceneData:
     """Owns the numpy arrays behind a PtSceneDesc (keeps them alive for the C call)."""
 
     def __init__(self, b):
-        cat = lambda parts, width, dt: (np.ascontiguousarray(np.concatenate(parts), dtype=dt) if parts else np.zeros((0, width), dtype=dt))
-        self.P = cat(b.P, 3, F)
-        self.idx = cat(b.idx, 3, np.uint32)
-        self.tri_flags = np.ascontiguousarray(np.concatenate(b.tri_flags), dtype=np.uint8) if b.tri_flags else np.zeros(0, np.uint8)
+        cat = lambda parts, dt, *width: (np.ascontiguousarray(np.concatenate(parts), dtype=dt) if parts else np.zeros((0, *width), dtype=dt))
+        self.P = cat(b.P, F, 3)
+        self.idx = cat(b.idx, np.uint32, 3)
+        self.tri_flags = cat(b.tri_flags, np.uint8)
 
         def opt(parts, width):
             if all(p is None for p in parts): return None
@@ -715,15 +705,14 @@ class SceneData:
                 o += len(pp)
             return np.ascontiguousarray(out)
         self.N, self.S, self.UV = opt(b.N, 3), opt(b.S, 3), opt(b.UV, 2)
-        c1 = lambda parts: np.ascontiguousarray(np.concatenate(parts), dtype=np.uint32) if parts else np.zeros(0, np.uint32)
-        self.prim_shape, self.prim_material, self.prim_light = c1(b.prim_shape), c1(b.prim_material), c1(b.prim_light)
+        self.prim_shape, self.prim_material, self.prim_light = cat(b.prim_shape, np.uint32), cat(b.prim_material, np.uint32), cat(b.prim_light, np.uint32)
         self.materials = (A.PtMaterial * max(1, len(b.materials)))(*b.materials)
         self.lights = (A.PtLight * max(1, len(b.lights)))(*b.lights)
         self.spheres = (A.PtSphere * max(1, len(b.spheres)))(*b.spheres)
         self.n_materials, self.n_lights, self.n_spheres = len(b.materials), len(b.lights), len(b.spheres)
         self.env = b.env
         self.media = (A.PtMedium * max(1, len(b.media)))(*b.media); self.n_media = len(b.media); self._keep = b._keep   # (grid media point into numpy arrays)
-        self.prim_med_in = c1(b.prim_med_in) if b.media else None; self.prim_med_out = c1(b.prim_med_out) if b.media else None
+        self.prim_med_in = cat(b.prim_med_in, np.uint32) if b.media else None; self.prim_med_out = cat(b.prim_med_out, np.uint32) if b.media else None
         self.integ = dict(b.integ)
         self.max_node_prims = b.max_node_prims
         self.split_method = {"sah": A.PT_SPLIT_SAH, "hlbvh": A.PT_SPLIT_HLBVH}[b.split_method]
@@ -731,9 +720,8 @@ class SceneData:
         self.n_objects, self.n_instances = len(b.object_list), len(b.instances)
         self.objects = (A.PtObject * max(1, self.n_objects))(*[A.PtObject(f, n) for _, f, n in b.object_list])
         self.instances = (A.PtInstance * max(1, self.n_instances))(*b.instances)
-        self.top_refs = np.ascontiguousarray(np.concatenate(b.top_refs), dtype=np.uint32) if (b.instances and b.top_refs) else None
-        ca = lambda parts: np.ascontiguousarray(np.concatenate(parts), dtype=np.int32) if parts else np.zeros(0, np.int32)
-        self.tri_alpha, self.tri_shadow_alpha = ca(b.tri_alpha), ca(b.tri_shadow_alpha)
+        self.top_refs = cat(b.top_refs, np.uint32) if (b.instances and b.top_refs) else None
+        self.tri_alpha, self.tri_shadow_alpha = cat(b.tri_alpha, np.int32), cat(b.tri_shadow_alpha, np.int32)
         if not (self.tri_alpha >= 0).any(): self.tri_alpha = None
         if not (self.tri_shadow_alpha >= 0).any(): self.tri_shadow_alpha = None
         self.n_textures = len(b.textures)
@@ -780,7 +768,7 @@ class SceneData:
             t = self.env["texels"]
             d.env_height, d.env_width = t.shape[0], t.shape[1]
             d.env_texels = ptr(t, A.fp); d.env_importance = ptr(self.env["importance"], A.fp)
-            d.env_power_lookup = (C.c_float * 3)(*[float(x) for x in self.env["power_lookup"]])
+            d.env_power_lookup = _f3(self.env["power_lookup"])
         d.max_node_prims = self.max_node_prims
         d.split_method = self.split_method
         if self.n_media:

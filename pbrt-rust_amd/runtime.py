@@ -71,19 +71,28 @@ def _fptr(a):
     return a.ctypes.data_as(A.fp)
 
 
-class Scene:
-    """pt_scene handle + the render / parity entry points."""
+class Handle:
+    """A scene handle of a library whose C functions carry a prefix: `pt_` (Scene), `pt_multi_` (MultiScene), `orc_` (the CPU oracle's scene).
+    `cdll` holds the functions, `check(status, what)` raises on a status other than PT_OK, `extra` goes between the description and the handle in
+    <PREFIX>scene_create. The AO integrator's functions live in `self._ao` (None: the handle has no AO integrator)."""
+    PREFIX = "pt_"
+    LIB_PREFIX = "pt_"   # of the functions that take no handle (film_resolve)
+    _ao = None
 
-    def __init__(self, lib, scene_data):
-        self.L = lib
+    def __init__(self, cdll, check, scene_data, *extra):
+        self._lib, self._check = cdll, check
         self.data = scene_data
         self.h = C.c_void_p()
         d = scene_data.desc()
-        lib.check(lib.lib.pt_scene_create(C.byref(d), C.byref(self.h)), "pt_scene_create")
+        self._call("scene_create", C.byref(d), *extra, C.byref(self.h))
+
+    def _call(self, name, *args, lib=None):
+        name = self.PREFIX + name
+        self._check(getattr(lib or self._lib, name)(*args), name)
 
     def close(self):
         if self.h:
-            self.L.lib.pt_scene_destroy(self.h); self.h = C.c_void_p()
+            getattr(self._lib, self.PREFIX + "scene_destroy")(self.h); self.h = C.c_void_p()
 
     def __del__(self):
         try: self.close()
@@ -91,33 +100,77 @@ class Scene:
 
     def bvh(self):
         nn, npr = C.c_uint32(), C.c_uint32()
-        self.L.check(self.L.lib.pt_scene_bvh_info(self.h, C.byref(nn), C.byref(npr)))
+        self._call("scene_bvh_info", self.h, C.byref(nn), C.byref(npr))
         nodes = (A.PtBVHNode * nn.value)(); ordered = np.zeros(npr.value, dtype=np.uint32)
-        self.L.check(self.L.lib.pt_scene_bvh_read(self.h, nodes, ordered.ctypes.data_as(A.u32p)))
+        self._call("scene_bvh_read", self.h, nodes, ordered.ctypes.data_as(A.u32p))
         return nodes, ordered
+
+    def render(self, rp, film=None, device_ptr=None, ao=None, last=None):
+        """Returns the un-normalised film (H, W, 4) = XYZ sums + weight sum, or None when it went to `device_ptr`. rp.integrator ==
+        PT_INTEGRATOR_AO renders with <PREFIX>ao_render: `ao` (a PtAOParams), else the scene's own (scene_data.ao_params()).
+        `last`: the call's final argument, by default the product library's `film_on_device`."""
+        args, lib, name = [self.h, C.byref(rp)], self._lib, "render"
+        if rp.integrator == AO.PT_INTEGRATOR_AO and self._ao is not None:
+            ao = self.data.ao_params() if ao is None else ao
+            args.append(C.byref(ao)); lib, name = self._ao, "ao_render"
+        if device_ptr is not None:
+            self._call(name, *args, C.c_void_p(device_ptr), 1, lib=lib); return None
+        if film is None:
+            cb = rp.cropped_pixel_bounds
+            film = np.zeros((cb[3] - cb[1], cb[2] - cb[0], 4), dtype=np.float32)
+        film_type = getattr(lib, self.PREFIX + name).argtypes[-2]   # void* in the product library, float* in the oracle
+        self._call(name, *args, film.ctypes.data_as(film_type), 0 if last is None else last, lib=lib)
+        return film
+
+    def resolve(self, film, scale=1.0):
+        film = np.ascontiguousarray(film, dtype=np.float32)
+        out = np.zeros(film.shape[:-1] + (3,), dtype=np.float32)
+        name = self.LIB_PREFIX + "film_resolve"
+        self._check(getattr(self._lib, name)(_fptr(film), film.size // 4, scale, _fptr(out)), name)
+        return out
+
+    def counters(self):
+        c = A.PtCounters()
+        self._call("get_counters", self.h, C.byref(c))
+        return c.as_dict()
+
+    def kernel_stats(self, *replica):
+        arr = (A.PtKernelStat * 32)(); n = C.c_uint32()
+        self._call("get_kernel_stats", self.h, *replica, arr, 32, C.byref(n))
+        text = lambda v: v.decode() if isinstance(v, bytes) else v
+        return [{k: text(getattr(arr[i], k)) for k, _ in A.PtKernelStat._fields_} for i in range(n.value)]
+
+    def trace_closest(self, o, d, tmax):
+        o, d, tmax = (np.ascontiguousarray(x, dtype=np.float32) for x in (o, d, tmax))
+        n = len(tmax)
+        prim = np.zeros(n, np.uint32); t = np.zeros(n, np.float32); b = np.zeros((n, 3), np.float32)
+        self._call("trace_closest", self.h, n, _fptr(o), _fptr(d), _fptr(tmax), prim.ctypes.data_as(A.u32p), _fptr(t), _fptr(b))
+        return prim, t, b
+
+    def trace_any(self, o, d, tmax):
+        o, d, tmax = (np.ascontiguousarray(x, dtype=np.float32) for x in (o, d, tmax))
+        n = len(tmax)
+        hit = np.zeros(n, np.uint8)
+        self._call("trace_any", self.h, n, _fptr(o), _fptr(d), _fptr(tmax), hit.ctypes.data_as(A.u8p))
+        return hit
+
+
+class Scene(Handle):
+    """pt_scene handle + the render / parity entry points."""
+
+    def __init__(self, lib, scene_data):
+        self.L = lib
+        super().__init__(lib.lib, lib.check, scene_data)
+
+    @property
+    def _ao(self):
+        return self.L.ao   # libmi355ao.so, loaded on first use
 
     def pass_size(self, rp):
         """Samples per pixel per wavefront pass pt_render would use for `rp` now (the library's choice from the free memory when rp.spp_per_pass == 0)."""
         s = C.c_uint32()
-        self.L.check(self.L.lib.pt_pass_size(self.h, C.byref(rp), C.byref(s)), "pt_pass_size")
+        self._call("pass_size", self.h, C.byref(rp), C.byref(s))
         return int(s.value)
-
-    def render(self, rp, film=None, device_ptr=None, ao=None):
-        """Returns the un-normalised film (H, W, 4) = XYZ sums + weight sum. rp.integrator == PT_INTEGRATOR_AO renders with
-        pt_ao_render: `ao` (a PtAOParams), else the scene's own (scene_data.ao_params())."""
-        cb = rp.cropped_pixel_bounds
-        w, h = cb[2] - cb[0], cb[3] - cb[1]
-        if rp.integrator == AO.PT_INTEGRATOR_AO:
-            ao = self.ao_params() if ao is None else ao
-            call, what = (lambda ptr, dev: self.L.ao.pt_ao_render(self.h, C.byref(rp), C.byref(ao), ptr, dev)), "pt_ao_render"
-        else:
-            call, what = (lambda ptr, dev: self.L.lib.pt_render(self.h, C.byref(rp), ptr, dev)), "pt_render"
-        if device_ptr is not None:
-            self.L.check(call(C.c_void_p(device_ptr), 1), what); return None
-        if film is None:
-            film = np.zeros((h, w, 4), dtype=np.float32)
-        self.L.check(call(film.ctypes.data_as(C.c_void_p), 0), what)
-        return film
 
     def ao_params(self):
         """The scene's PtAOParams (SceneBuilder.integ / the front end's "ambientocclusion" parameters)."""
@@ -127,102 +180,43 @@ class Scene:
         """Samples per pixel per pass pt_ao_render would use for `rp` now."""
         s = C.c_uint32()
         ao = self.ao_params() if ao is None else ao
-        self.L.check(self.L.ao.pt_ao_pass_size(self.h, C.byref(rp), C.byref(ao), C.byref(s)), "pt_ao_pass_size")
+        self._call("ao_pass_size", self.h, C.byref(rp), C.byref(ao), C.byref(s), lib=self.L.ao)
         return int(s.value)
 
-    def resolve(self, film, scale=1.0):
-        film = np.ascontiguousarray(film, dtype=np.float32)
-        out = np.zeros(film.shape[:-1] + (3,), dtype=np.float32)
-        self.L.check(self.L.lib.pt_film_resolve(_fptr(film), film.size // 4, scale, _fptr(out)))
-        return out
 
-    def counters(self):
-        c = A.PtCounters()
-        self.L.check(self.L.lib.pt_get_counters(self.h, C.byref(c)))
-        return c.as_dict()
-
-    def kernel_stats(self):
-        arr = (A.PtKernelStat * 32)(); n = C.c_uint32()
-        self.L.check(self.L.lib.pt_get_kernel_stats(self.h, arr, 32, C.byref(n)))
-        return [dict(name=arr[i].name.decode(), launches=arr[i].launches, total_ms=arr[i].total_ms, items=arr[i].items, bvh_nodes=arr[i].bvh_nodes, triangle_tests=arr[i].triangle_tests, kernel=arr[i].kernel.decode()) for i in range(n.value)]
-
-    def trace_closest(self, o, d, tmax):
-        o, d, tmax = (np.ascontiguousarray(x, dtype=np.float32) for x in (o, d, tmax))
-        n = len(tmax)
-        prim = np.zeros(n, np.uint32); t = np.zeros(n, np.float32); b = np.zeros((n, 3), np.float32)
-        self.L.check(self.L.lib.pt_trace_closest(self.h, n, _fptr(o), _fptr(d), _fptr(tmax), prim.ctypes.data_as(A.u32p), _fptr(t), _fptr(b)))
-        return prim, t, b
-
-    def trace_any(self, o, d, tmax):
-        o, d, tmax = (np.ascontiguousarray(x, dtype=np.float32) for x in (o, d, tmax))
-        n = len(tmax)
-        hit = np.zeros(n, np.uint8)
-        self.L.check(self.L.lib.pt_trace_any(self.h, n, _fptr(o), _fptr(d), _fptr(tmax), hit.ctypes.data_as(A.u8p)))
-        return hit
-
-
-class MultiScene:
+class MultiScene(Handle):
     """pt_multi_scene: the scene replicated on several devices of THIS process (one host thread + stream per replica inside
     pt_multi_render); a device ordinal may repeat. The film comes back summed, on the first device or in a host array."""
+    PREFIX = "pt_multi_"
 
     def __init__(self, lib, scene_data, devices):
-        self.L = lib; self.data = scene_data; self.devices = list(devices)
-        self.h = C.c_void_p()
-        d = scene_data.desc()
+        self.L = lib; self.devices = list(devices)
         devs = (C.c_int * len(self.devices))(*self.devices)
-        lib.check(lib.lib.pt_multi_scene_create(C.byref(d), devs, len(self.devices), C.byref(self.h)), "pt_multi_scene_create")
-
-    def close(self):
-        if self.h:
-            self.L.lib.pt_multi_scene_destroy(self.h); self.h = C.c_void_p()
-
-    def __del__(self):
-        try: self.close()
-        except Exception: pass
-
-    def render(self, rp, film=None, device_ptr=None):
-        cb = rp.cropped_pixel_bounds
-        w, h = cb[2] - cb[0], cb[3] - cb[1]
-        if device_ptr is not None:
-            self.L.check(self.L.lib.pt_multi_render(self.h, C.byref(rp), C.c_void_p(device_ptr), 1), "pt_multi_render"); return None
-        if film is None:
-            film = np.zeros((h, w, 4), dtype=np.float32)
-        self.L.check(self.L.lib.pt_multi_render(self.h, C.byref(rp), film.ctypes.data_as(C.c_void_p), 0), "pt_multi_render")
-        return film
-
-    def counters(self):
-        c = A.PtCounters()
-        self.L.check(self.L.lib.pt_multi_get_counters(self.h, C.byref(c)))
-        return c.as_dict()
-
-    def resolve(self, film, scale=1.0):
-        return Scene.resolve(self, film, scale)
+        super().__init__(lib.lib, lib.check, scene_data, devs, len(self.devices))
 
     def timing(self):
         """Last render: merge_ms and, per replica, the wall time of its pt_render and of its peer copy."""
         n = len(self.devices)
         merge = C.c_double(); r = (C.c_double * n)(); c = (C.c_double * n)()
-        self.L.check(self.L.lib.pt_multi_get_timing(self.h, C.byref(merge), r, c, n))
+        self._call("get_timing", self.h, C.byref(merge), r, c, n)
         return dict(merge_ms=merge.value, render_ms=list(r), copy_ms=list(c))
 
     def create_timing(self):
         """pt_multi_scene_create: wall time of the call and, per replica, of its own scene creation (replicas 1.. are created concurrently), in ms."""
         n = len(self.devices)
         wall = C.c_double(); r = (C.c_double * n)()
-        self.L.check(self.L.lib.pt_multi_get_create_timing(self.h, C.byref(wall), r, n))
+        self._call("get_create_timing", self.h, C.byref(wall), r, n)
         return dict(wall_ms=wall.value, replica_ms=list(r))
 
     def peer_access(self):
         """Per replica: "same device", "peer access" (device-to-device copies) or "staged through the host" -- how its film reaches the first device."""
         n = len(self.devices)
         p = (C.c_int * n)()
-        self.L.check(self.L.lib.pt_multi_get_peer_access(self.h, p, n))
+        self._call("get_peer_access", self.h, p, n)
         return [("same device", "peer access", "staged through the host")[v] for v in p]
 
     def kernel_stats(self, replica=0):
-        arr = (A.PtKernelStat * 32)(); n = C.c_uint32()
-        self.L.check(self.L.lib.pt_multi_get_kernel_stats(self.h, replica, arr, 32, C.byref(n)))
-        return [dict(name=arr[i].name.decode(), launches=arr[i].launches, total_ms=arr[i].total_ms, items=arr[i].items, bvh_nodes=arr[i].bvh_nodes, triangle_tests=arr[i].triangle_tests, kernel=arr[i].kernel.decode()) for i in range(n.value)]
+        return super().kernel_stats(replica)
 
 
 def tile_shard(lib, rank, world, replica, n_replicas):

@@ -224,7 +224,6 @@ def subsurface_c5(n=24, xres=96, yres=64, spp=16, maxdepth=5, rough=False, textu
     """Config C5: a displaced sphere with a `subsurface` material (skin-like medium, mm units
     scaled so the mean free path is a visible fraction of the object), a `kdsubsurface` sphere shape and a matte floor,
     lit by an area light and a dim environment.  Exercises path.rs:177-204 / bssrdf.rs sample_s."""
-    from .host import SceneBuilder
     b = SceneBuilder()
     b.film.update(xres=xres, yres=yres); b.spp = spp
     b.integ.update(maxdepth=maxdepth)
@@ -264,7 +263,6 @@ def subsurface_in_fog(n=16, xres=64, yres=48, spp=8, maxdepth=5, fog=True, sampl
     fog, one subsurface object is an ordinary primitive (its hits hand the probe ray's medium on: none for the first probe ray, so the path
     leaves the object in VACUUM -- bssrdf.rs:362-366 starts the chain from an interaction without a MediumInterface) and the other carries a
     MediumInterface of its own (its hits name "juice" inside / "fog" outside, whichever the chain reaches first)."""
-    from .host import SceneBuilder
     b = SceneBuilder()
     b.film.update(xres=xres, yres=yres); b.spp = spp; b.sampler = sampler
     b.integ.update(maxdepth=maxdepth, kind="volpath")
@@ -328,7 +326,6 @@ def sphere_lights(xres=96, yres=64, spp=16, maxdepth=4):
     sphere light (cone sampling), a one-sided sphere light (App. A #7: NEE light samples return L = 0; only BSDF-sampled rays
     see it), and a large two-sided partial sphere around a diffuse object (reference point INSIDE the light: uniform-area
     branch + shape_pdfwi)."""
-    from .host import SceneBuilder
     b = SceneBuilder()
     b.film.update(xres=xres, yres=yres); b.spp = spp
     b.integ.update(maxdepth=maxdepth)
@@ -359,7 +356,6 @@ def textured(xres=96, yres=64, spp=8, maxdepth=4, trilinear=False, bump=False, n
     """image map (EWA or trilinear MIPMap, uv and planar mappings), checkerboard (closed-form and point
     sampled, 2-D and 3-D), scale, mix, bilerp, uv, a float image texture driving a roughness, spherical + cylindrical
     mappings; camera-ray differentials drive the filtering at the first hit, later bounces use zero-width lookups."""
-    from .host import SceneBuilder
     b = SceneBuilder()
     b.film.update(xres=xres, yres=yres); b.spp = spp
     b.integ.update(maxdepth=maxdepth)
@@ -418,7 +414,6 @@ def alpha_foliage(xres=96, yres=64, spp=8, maxdepth=4, n_cards=40, seed=3, insta
     """Alpha-masked geometry (SURVEY 8f-1, config C4's foliage): leaf cards whose `alpha` is a checkerboard / image float
     texture (cut-outs seen by camera, bounce and shadow rays), one card with `shadowalpha` only (visible but casts
     partially no shadow), a constant-zero alpha mesh (fully invisible), inside object instances and at top level."""
-    from .host import SceneBuilder
     rng = np.random.default_rng(seed)
     b = SceneBuilder()
     b.film.update(xres=xres, yres=yres); b.spp = spp
