@@ -35,7 +35,8 @@ typedef enum PtStatus {
     PT_ERR_INVALID_ARG = 1,       /* null pointer / inconsistent sizes                      */
     PT_ERR_NO_DEVICE = 2,         /* HIP runtime reports no usable gfx950 device            */
     PT_ERR_HIP = 3,               /* a HIP call failed; see pt_last_error()                  */
-    PT_ERR_UNSUPPORTED = 4,       /* scene uses a feature outside the implemented rows      */
+    PT_ERR_UNSUPPORTED = 4,       /* scene uses a feature outside the implemented rows; also raised on the device when a hit's
+                                     material class has no shade queue in the render (an internal invariant of the router) */
     PT_ERR_SOBOL_DIMENSIONS = 5,  /* a path consumed >= 1024 Sobol' dimensions
                                      (the reference panics: samplers/sobol.rs:69-73)         */
     PT_ERR_STACK_OVERFLOW = 6,    /* a ray's BVH traversal stack grew beyond what the walk holds: 96 pending entries in the
@@ -43,8 +44,8 @@ typedef enum PtStatus {
                                      the reference indexes its 64-entry Vec without a check of its own: accelerators/bvh.rs:722) */
     PT_ERR_OUT_OF_MEMORY = 7,     /* a device allocation failed (e.g. spp_per_pass asks for more path state than the device has free);
                                      the scene stays usable: the next pt_render allocates its workspace afresh */
-    PT_ERR_PROBE_CHAIN = 8        /* a BSSRDF probe chain (core/bssrdf.rs:376-394) found more than 32767 intersections or a
-                                     pass needed more than 65536 wavefront iterations: the reference would still be walking its
+    PT_ERR_PROBE_CHAIN = 8        /* a BSSRDF probe chain (core/bssrdf.rs:376-394) found more than 2^32 - 1 intersections or a
+                                     pass needed more than 2^20 wavefront iterations: the reference would still be walking its
                                      linked list; the render is abandoned instead of returning a truncated chain          */
 } PtStatus;
 

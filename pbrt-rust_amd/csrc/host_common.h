@@ -2,7 +2,7 @@
 // handles, and the helpers that cross files. The driver used to be one file (capi.hip, 1 700 lines); it is split by what a reader looks for:
 //   host_device.hip   device binding per host thread, Sobol' / Halton tables, pt_init and the process-wide knobs
 //   scene_create.hip  pt_scene_create: validation, accelerators (host SAH / GPU HLBVH), two- and four-wide records, uploads, light records
-//   render_loop.hip   the wavefront scheduler: workspace, light grids, launch_trace / launch_shade, run_pass, pt_render, counters and kernel stats
+//   render_loop.hip   the wavefront scheduler: kernel variants and the shade-class table, workspace, light grids, launch_trace, run_pass and its steps, pt_render, counters and kernel stats
 //   parity_api.hip    the entry points tests use to compare single stages with the oracle (rays, Sobol' / Halton samples, camera rays)
 //   multi_device.hip  pt_multi_*: one process driving several devices (one host thread + stream per replica, peer-copy film merge)
 #pragma once
@@ -39,7 +39,6 @@ extern bool g_trace_exact;
 extern uint32_t g_inst_quorum;
 extern bool g_shade_specialise;
 extern bool g_film_final;
-extern int g_test_max_iterations;
 extern uint32_t g_trace_waves_per_cu;
 extern uint32_t g_test_pool_pad_records;
 extern thread_local SobolTables g_tabs;
@@ -187,6 +186,6 @@ int ensure_workspace(pt_scene *sc, size_t capacity, size_t film_px);
 int ensure_light_grid(pt_scene *sc, int requested, int &effective);
 void fill_render_const(const PtRenderParams *rp, RenderConst &rc);
 uint32_t choose_pass_size(const pt_scene *sc, uint32_t n_pix_slots, uint32_t spp, uint32_t share, bool volpath);
-int run_pass(pt_scene *sc, RenderConst &rc, const LightGrid &grid, bool rp_profile_exact);
+int run_pass(pt_scene *sc, RenderConst &rc, const LightGrid &grid, bool rp_profile_exact, int max_iterations);
 void read_counters(pt_scene *sc);
 }  // namespace pth

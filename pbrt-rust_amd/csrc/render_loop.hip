@@ -1,5 +1,20 @@
 // render_loop.hip -- the wavefront scheduler behind pt_render: workspace, light grids, launches, one pass, counters (host_common.h has the map).
 #include "host_common.h"
+#include <utility>
+
+// Blocks per CU of the persistent grids. Experiment hooks: tools/build_variant.sh overrides them with -D.
+#ifndef PT_SHADE_BLOCKS_PER_CU
+#define PT_SHADE_BLOCKS_PER_CU 24u   // each block walks a fixed stride of the queue: 24 a CU (2, 3 or 4 resident at a time) even out the per-vertex cost differences; 8 left the matte kernel's third round two-thirds full (80.1 -> 76.3 ms on C2)
+#endif
+#ifndef PT_GEN_BLOCKS_PER_CU
+#define PT_GEN_BLOCKS_PER_CU 40u     // 16 -> 40: k_generate 12.2 -> 11.7 ms on C2; the miss kernel does not care
+#endif
+#ifndef PT_ROUTE_BLOCKS_PER_CU
+#define PT_ROUTE_BLOCKS_PER_CU 3u    // what a CU's LDS holds of k_route (six 8 KB staging queues per block)
+#endif
+#ifndef PT_MISS_BLOCKS_PER_CU
+#define PT_MISS_BLOCKS_PER_CU 16u
+#endif
 
 namespace pth {
 #ifdef PT_TRACE_UTIL
@@ -9,16 +24,78 @@ __global__ void k_trace_util_fold(DevCounters *dc, uint32_t kind, uint32_t waves
 }
 #endif
 
-// Shade queues exist for the seven lobe-count / service classes always (the volumetric integrator uses all of them) and for the lobe-set classes the scene's materials map to.
-static bool class_has_queue(const pt_scene *sc, int c) {
-    // matte and the three service classes always (4 dead / escaped paths, 5 medium vertices, 6 also the waiting exit points of subsurface chains under volpath); a material
-    // class when the scene has such materials, a lobe-count class also when a lobe-set class of the scene folds into it under volpath (class_general)
-    if (c == 0 || c == kMissClass || c == kMediumClass || c == kSpecClass || sc->class_used[c]) return true;
-    if (c == 1 && sc->class_used[kSpecClass]) return true;   // (the volumetric router folds the specular class into class 1)
-    for (int k = kSpecClass + 1; k < kNumClasses; ++k) if (sc->class_used[k] && class_general((uint32_t)k) == (uint32_t)c) return true;
-    return false;
+// ---- kernel variants. A Variant is one instantiation of a kernel template and the symbol rocprofv3 prints for it, both made from the SAME template arguments (the
+// symbol is a key: bench.py looks the kernel's PMC record up by it, tests assert it). The run-time conditions pick a variant once; launch() takes function and name from it.
+template <class... P> struct Variant { void (*fn)(P...); std::string name; };
+static std::string targ(bool b) { return b ? "true" : "false"; }
+static std::string targ(int v) { return std::to_string(v); }
+template <class... T> std::string symbol(const char *kernel, T... args) { std::string s = std::string(kernel) + "<", sep; ((s += sep + targ(args), sep = ", "), ...); return s + ">"; }
+
+// every launch of the render stream: the symbol goes to the launch kind opened by the last begin()
+template <class... P, class... A> void launch(pt_scene *sc, const std::string &name, void (*fn)(P...), dim3 blocks, dim3 threads, const A &...args) { sc->set_kernel(name); hipLaunchKernelGGL(fn, blocks, threads, 0, sc->stream, static_cast<P>(args)...); }
+template <class... P, class... A> void launch(pt_scene *sc, const Variant<P...> &v, dim3 blocks, dim3 threads, const A &...args) { launch(sc, v.name, v.fn, blocks, threads, args...); }
+static dim3 blocks_for(uint32_t n_upper, uint32_t per_cu) { return dim3(std::min<uint32_t>((n_upper + 255) / 256, (uint32_t)g_num_cus * per_cu)); }   // persistent blocks of 256 threads
+static bool general_geometry(const pt_scene *sc) { return sc->ds.n_spheres > 0 || sc->ds.n_instances > 0; }   // the SPH forms: spheres or instances besides world-space triangles
+
+// k_trace (tu_trace.hip): ANY 0..2 x MODE 0..3 x QUADK 0..2, and the probe walk (closest hit, PROBE) in the same MODE x QUADK -- row 3 of the table
+using TraceVariant = Variant<DeviceScene, TraceJob>;
+template <int ANY, int MODE, bool PROBE, int QUADK> TraceVariant trace_inst() { return {k_trace<ANY, MODE, PROBE, QUADK>, symbol("k_trace", ANY, MODE, PROBE, QUADK)}; }
+template <int... I> const TraceVariant &trace_table(int i, std::integer_sequence<int, I...>) { static const TraceVariant t[] = {trace_inst<I / 12 % 3, I / 3 % 4, I / 12 == 3, I % 3>()...}; return t[i]; }
+static const TraceVariant &trace_variant(int any, int mode, bool probe, int quadk) { return trace_table((probe ? 3 : any) * 12 + mode * 3 + quadk, std::make_integer_sequence<int, 48>()); }
+
+// k_shade (tu_shade.hip). The forms that are not compiled fall back to the general kernel of the same lobe budget (DIFF 0), here and nowhere else: volpath (MODE 3) has
+// no DIFF >= 2 form -- its router folds the specular and the lobe-set classes back (shaded_in below) --, and the smooth-subsurface form (DIFF 6) is untextured only (MODE < 2)
+using ShadeVariant = Variant<DeviceScene, RenderConst, SobolTables, LightGrid, PathSoA, ShadeJob>;
+template <int MAXL, int MODE, int DIFF> const ShadeVariant &shade_inst() {
+    constexpr int D = ((MODE == 3 && DIFF >= 2) || (MODE == 2 && DIFF == 6)) ? 0 : DIFF;
+    static const ShadeVariant v{k_shade<MAXL, MODE, D>, symbol("k_shade", MAXL, MODE, D)};
+    return v;
 }
-static size_t n_class_queues(const pt_scene *sc) { size_t n = 0; for (int c = 0; c < kNumClasses; ++c) n += class_has_queue(sc, c) ? 1 : 0; return n; }
+template <int MAXL, int DIFF> const ShadeVariant &shade_variant(int mode) { return mode == 3 ? shade_inst<MAXL, 3, DIFF>() : mode == 2 ? shade_inst<MAXL, 2, DIFF>() : mode == 1 ? shade_inst<MAXL, 1, DIFF>() : shade_inst<MAXL, 0, DIFF>(); }
+
+// k_shade_miss (tu_aux.hip) and k_bssrdf (tu_bssrdf.hip): <SPH, VOL> = <false, false>, <true, false>, <true, true> (volpath runs the general-geometry form, like all its kernels)
+using MissVariant = Variant<DeviceScene, RenderConst, PathSoA, ShadeJob>;
+using BssrdfVariant = Variant<DeviceScene, RenderConst, SobolTables, LightGrid, PathSoA, BssrdfJob>;
+template <bool SPH, bool VOL> MissVariant miss_inst() { return {k_shade_miss<SPH, VOL>, symbol("k_shade_miss", SPH, VOL)}; }
+template <bool SPH, bool VOL> BssrdfVariant bssrdf_inst() { return {k_bssrdf<SPH, VOL>, symbol("k_bssrdf", SPH, VOL)}; }
+static const MissVariant &miss_variant(bool sph, bool vol) { static const MissVariant t[3] = {miss_inst<false, false>(), miss_inst<true, false>(), miss_inst<true, true>()}; return t[vol ? 2 : sph ? 1 : 0]; }
+static const BssrdfVariant &bssrdf_variant(bool sph, bool vol) { static const BssrdfVariant t[3] = {bssrdf_inst<false, false>(), bssrdf_inst<true, false>(), bssrdf_inst<true, true>()}; return t[vol ? 2 : sph ? 1 : 0]; }
+
+// k_film_final<SPH> (tu_aux.hip), k_light_touch<SPH> and k_route<NQ, CAP> (tu_misc.hip: six staging queues of 2048 entries or twelve of 1024)
+using FilmFinalVariant = Variant<DeviceScene, RenderConst, PathSoA, const float *, float *, DevCounters *>;
+using TouchVariant = Variant<DeviceScene, LightGrid, PathSoA, const uint32_t *, const uint32_t *, uint32_t, uint32_t, uint32_t *, uint32_t *, uint32_t *>;
+using RouteVariant = Variant<DeviceScene, const uint32_t *, const uint32_t *, PathSoA, uint32_t *, RouteJob>;
+template <bool SPH> FilmFinalVariant film_final_inst() { return {k_film_final<SPH>, symbol("k_film_final", SPH)}; }
+template <bool SPH> TouchVariant touch_inst() { return {k_light_touch<SPH>, symbol("k_light_touch", SPH)}; }
+template <int NQ, int CAP> RouteVariant route_inst() { return {k_route<NQ, CAP>, symbol("k_route", NQ, CAP)}; }
+static const FilmFinalVariant &film_final_variant(bool sph) { static const FilmFinalVariant t[2] = {film_final_inst<false>(), film_final_inst<true>()}; return t[sph]; }
+static const TouchVariant &touch_variant(bool sph) { static const TouchVariant t[2] = {touch_inst<false>(), touch_inst<true>()}; return t[sph]; }
+static const RouteVariant &route_variant(uint32_t n_slots) { static const RouteVariant t[2] = {route_inst<6, 2048>(), route_inst<12, 1024>()}; return t[n_slots > 6]; }
+
+template <int MAXL, int DIFF> void launch_shade(pt_scene *sc, const RenderConst &rc, const LightGrid &grid, const ShadeJob &job, uint32_t upper) {
+    const int mode = rc.volpath ? 3 : sc->ds.n_textures > 0 ? 2 : (general_geometry(sc) || rc.halton.enabled) ? 1 : 0;   // kern_shade.h: k_shade MODE
+    launch(sc, shade_variant<MAXL, DIFF>(mode), blocks_for(upper, PT_SHADE_BLOCKS_PER_CU), dim3(256), sc->ds, rc, g_tabs, grid, sc->ps, job);   // persistent blocks: the LDS Sobol' table is staged once per block
+}
+
+// ---- shade classes (kernels.h: kNumClasses). One row per class: the launch kind its statistics go by, what runs on its queue, and for the surface classes the k_shade
+// family <MAXL, DIFF> that does. The specular class is a surface class of the path integrator; volpath has none, and its queue serves the exit points of subsurface chains that
+// wait for their traced shadow / MIS rays (k_bssrdf, stage B).
+enum ClassKind { kSurface, kMiss, kMedium, kSpecularOrStageB };
+struct ClassInfo { const char *stat; ClassKind kind; void (*launch)(pt_scene *, const RenderConst &, const LightGrid &, const ShadeJob &, uint32_t); };
+constexpr ClassInfo kClasses[kNumClasses] = {
+    {"shade_matte", kSurface, launch_shade<1, 1>}, {"shade_1lobe", kSurface, launch_shade<1, 0>}, {"shade_2lobe", kSurface, launch_shade<2, 0>}, {"shade_manylobe", kSurface, launch_shade<5, 0>},
+    {"shade_miss", kMiss, nullptr}, {"shade_medium", kMedium, nullptr}, {"shade_specular", kSpecularOrStageB, launch_shade<1, 2>},
+    {"shade_metal", kSurface, launch_shade<1, 3>}, {"shade_plastic", kSurface, launch_shade<2, 4>}, {"shade_uber", kSurface, launch_shade<5, 5>}, {"shade_sss", kSurface, launch_shade<1, 6>}};
+
+// THE statement of class folding: the class in whose queue, and by whose kernel, a render shades the vertices of class c; -1 when the scene has none. The path integrator
+// shades every class in its own queue; the volumetric router (k_medium_route) folds the specular class into class 1 and the lobe-set classes into their lobe-count class.
+static int shaded_in(const pt_scene *sc, int c, bool volpath) { return !sc->class_used[c] ? -1 : !volpath ? c : c == kSpecClass ? 1 : (int)class_general((uint32_t)c); }
+static bool class_launched(const pt_scene *sc, int q, bool volpath) { for (int c = 0; c < kNumClasses; ++c) if (shaded_in(sc, c, volpath) == q) return true; return false; }
+// The workspace serves both integrators: a class has a queue when either launches it, and matte and the three service classes always (4 dead / escaped paths, 5 medium
+// vertices, 6 also the waiting exit points of volpath)
+static bool class_has_queue(const pt_scene *sc, int c) { return c == 0 || kClasses[c].kind != kSurface || class_launched(sc, c, false) || class_launched(sc, c, true); }
+// queues of one path index each: ext[2] + shade[2][classes with a queue] + shadow + mis (+ probe[2])
+static size_t n_queues(const pt_scene *sc) { size_t n = 2 + 2 + (sc->has_bssrdf ? 2 : 0); for (int c = 0; c < kNumClasses; ++c) n += class_has_queue(sc, c) ? 2 : 0; return n; }
 
 // any: 0 closest hit, 1 any hit (rays of job.sub[0]); 2 mixed: the queues of job.sub[0..2] in one launch (n_upper covers all three)
 int launch_trace(pt_scene *sc, int any, TraceJob job, uint32_t n_upper, bool probe) {
@@ -26,30 +103,19 @@ int launch_trace(pt_scene *sc, int any, TraceJob job, uint32_t n_upper, bool pro
     const uint32_t knob = job.sub[0].kind == 4 ? 0 : (job.sub[0].kind & 3);
     job.refill_min = (probe && !g_refill_from_env) ? 24u : g_refill_min[knob]; job.leaf_quorum = g_leaf_quorum[knob];   // (probe chains: 24 measured best on C5, 16: +1.6 %)
     if (sc->ds.n_instances > 0 && !g_refill_from_env) job.refill_min = 8;   // rays through instanced scenes are long (S4: 200 node visits): idle lanes are refilled early (measured 24 -> 8: +9 %)
-    uint32_t waves = (n_upper + 63) / 64;
-    uint32_t blocks = std::min<uint32_t>((waves + 3) / 4, sc->spill_waves / 4);
+    const uint32_t waves = (n_upper + 63) / 64, blocks = std::min<uint32_t>((waves + 3) / 4, sc->spill_waves / 4);
     const int mode = (sc->ds.tri_alpha || sc->ds.tri_shadow_alpha) ? 2 : sc->ds.n_spheres > 0 ? 1 : sc->ds.n_instances > 0 ? 3 : 0;  // kern_trace.h: k_trace MODE
     job.inst_quorum = g_inst_quorum;
     if (sc->quad_walk_only && (g_trace_exact || sc->exact_walk_only)) return fail(PT_ERR_UNSUPPORTED, "the two-wide (exact) walk addresses 2^25 records / packets: this scene has the production walk only");
+    // production: the four-wide records, through 64-bit addresses when records + packets lie beyond 4 GB; pt_set_trace_exact(1): the two-wide walk with the reference's node-visit counter
+    const int quadk = (g_trace_exact || sc->exact_walk_only) ? 0 : sc->pool_big ? 2 : 1;
 #ifdef PT_TRACE_UTIL
     hipLaunchKernelGGL(k_trace_util_fold, dim3(1), dim3(1), 0, sc->stream, sc->dc, job.sub[0].kind & 3u, 0u, 1);
 #endif
-    const bool quad = !g_trace_exact && !sc->exact_walk_only;   // production: the four-wide records; pt_set_trace_exact(1): the two-wide walk with the reference's node-visit counter
-    const bool big = sc->pool_big;   // records + packets beyond 4 GB: the production walk through 64-bit addresses
-    #define PT_LAUNCH_TRACE(A, M, P) do { if (quad && big) hipLaunchKernelGGL((k_trace<A, M, P, 2>), dim3(blocks), dim3(kTraceBlock), 0, sc->stream, sc->ds, job); \
-                                          else if (quad) hipLaunchKernelGGL((k_trace<A, M, P, 1>), dim3(blocks), dim3(kTraceBlock), 0, sc->stream, sc->ds, job); \
-                                          else hipLaunchKernelGGL((k_trace<A, M, P, 0>), dim3(blocks), dim3(kTraceBlock), 0, sc->stream, sc->ds, job); } while (0)
-    #define PT_LAUNCH_TRACE_MODE(A, P) do { if (mode == 3) PT_LAUNCH_TRACE(A, 3, P); else if (mode == 2) PT_LAUNCH_TRACE(A, 2, P); else if (mode == 1) PT_LAUNCH_TRACE(A, 1, P); else PT_LAUNCH_TRACE(A, 0, P); } while (0)
-    if (probe) PT_LAUNCH_TRACE_MODE(0, true);
-    else if (any == 2) PT_LAUNCH_TRACE_MODE(2, false);
-    else if (any == 1) PT_LAUNCH_TRACE_MODE(1, false);
-    else PT_LAUNCH_TRACE_MODE(0, false);
-    #undef PT_LAUNCH_TRACE_MODE
-    #undef PT_LAUNCH_TRACE
+    launch(sc, trace_variant(any, mode, probe, quadk), dim3(blocks), dim3(kTraceBlock), sc->ds, job);
 #ifdef PT_TRACE_UTIL
     hipLaunchKernelGGL(k_trace_util_fold, dim3(1), dim3(1), 0, sc->stream, sc->dc, job.sub[0].kind & 3u, blocks * (kTraceBlock / 64), 0);
 #endif
-    sc->set_kernel(std::string("k_trace<") + std::to_string(any) + ", " + std::to_string(mode) + ", " + (probe ? "true" : "false") + ", " + (quad ? (big ? "2" : "1") : "0") + ">");
     HIP_TRY(hipGetLastError());
     return PT_OK;
 }
@@ -91,9 +157,7 @@ int ensure_workspace(pt_scene *sc, size_t capacity, size_t film_px) {
             float4 *bp = (float4 *)sc->bss_slab;
             bs.probe = bp; bp += capacity * (size_t)BssSoA::kProbeQuads; bs.frame = bp; bp += capacity * (size_t)BssSoA::kFrameQuads; bs.coef = bp;
         }
-        // queues: ext[2] + shade[2][classes] + shadow + mis (+ probe[2])
-        size_t nq = 2 + 2 * n_class_queues(sc) + 2 + (sc->has_bssrdf ? 2 : 0);
-        e = hipMalloc((void **)&sc->qbuf, nq * capacity * 4);
+        e = hipMalloc((void **)&sc->qbuf, n_queues(sc) * capacity * 4);
         if (e != hipSuccess) { sc->qbuf = nullptr; return oom("queues", e); }
         uint32_t *qp = sc->qbuf;
         for (int i = 0; i < 2; ++i) { sc->q.ext[i] = qp; qp += capacity; }
@@ -124,6 +188,16 @@ void spatial_voxels(const pt_scene *sc, uint32_t nvox[3]) {
     }
 }
 constexpr size_t kEagerGridEntries = (size_t)1 << 25;   // voxels x lights up to which PT_LS_SPATIAL precomputes every voxel
+
+// The light distributions of n voxels (k_light_grid_contrib: 128 Halton points x every light each, lightdistrib.rs:151-228; k_light_grid_finish: their CDFs): of all
+// of them in order, or of those listed in `cells`, whose blocks (`stride` floats each, at func) are then published in cell_ptr
+static void light_grid_cells(pt_scene *sc, const LightGrid &g, size_t n, float *func, float *cdf, float *fint, const uint32_t *cells, size_t stride, unsigned long long *cell_ptr) {
+    const size_t total = n * g.n_lights;
+    sc->begin("light_grid", total);
+    launch(sc, "k_light_grid_contrib", k_light_grid_contrib, dim3((unsigned)((total + 255) / 256)), dim3(256), sc->ds, g.nvox[0], g.nvox[1], g.nvox[2], func, cells, cells ? n : 0, stride);
+    hipLaunchKernelGGL(k_light_grid_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, sc->stream, g.n_lights, n, func, cdf, fint, cells, stride, cell_ptr);
+    sc->end();
+}
 
 int ensure_light_grid(pt_scene *sc, int requested, int &effective) {
     effective = requested;
@@ -193,12 +267,7 @@ int ensure_light_grid(pt_scene *sc, int requested, int &effective) {
         if ((st = sc->dalloc(&func, ncell * nl))) return st;
         if ((st = sc->dalloc(&cdf, ncell * (nl + 1)))) return st;
         if ((st = sc->dalloc(&fint, ncell))) return st;
-        size_t total = ncell * nl;
-        sc->begin("light_grid", total);
-        sc->set_kernel("k_light_grid_contrib");
-        hipLaunchKernelGGL(k_light_grid_contrib, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, sc->stream, sc->ds, g.nvox[0], g.nvox[1], g.nvox[2], func, (const uint32_t *)nullptr, (size_t)0, (size_t)0);
-        hipLaunchKernelGGL(k_light_grid_finish, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, sc->stream, nl, ncell, func, cdf, fint, (const uint32_t *)nullptr, (size_t)0, (unsigned long long *)nullptr);
-        sc->end();
+        light_grid_cells(sc, g, ncell, func, cdf, fint, nullptr, 0, nullptr);
         HIP_TRY(hipGetLastError());
         g.func = func; g.cdf = cdf; g.func_int = fint;
     }
@@ -266,20 +335,6 @@ __global__ void k_reset(QCounters *qc, uint32_t mask, int cur) {
     if (mask & 8u) { qc->ext[cur] = 0; qc->probe[cur] = 0; for (int c = 0; c < kNumClasses; ++c) qc->shade[cur][c] = 0; }
 }
 
-template <int MAXL, int DIFF = 0> void launch_shade(pt_scene *sc, const RenderConst &rc, const LightGrid &grid, const ShadeJob &job, uint32_t upper) {
-#ifndef PT_SHADE_BLOCKS_PER_CU
-#define PT_SHADE_BLOCKS_PER_CU 24u   // experiment hook. Each block walks a fixed stride of the queue: 24 a CU (2, 3 or 4 resident at a time) even out the per-vertex cost differences; 8 left the matte kernel's third round two-thirds full (80.1 -> 76.3 ms on C2)
-#endif
-    const uint32_t blocks = std::min<uint32_t>((upper + 255) / 256, (uint32_t)g_num_cus * PT_SHADE_BLOCKS_PER_CU);  // persistent blocks: the LDS Sobol' table is staged once per block
-    const int mode = rc.volpath ? 3 : sc->ds.n_textures > 0 ? 2 : (sc->ds.n_spheres > 0 || sc->ds.n_instances > 0 || rc.halton.enabled) ? 1 : 0;
-    if (DIFF >= 3 && (mode == 3 || (DIFF == 6 && mode == 2))) { launch_shade<MAXL, 0>(sc, rc, grid, job, upper); return; }   // (volpath folds the lobe-set classes back; the smooth-subsurface form is untextured only)
-    sc->set_kernel("k_shade<" + std::to_string(MAXL) + ", " + std::to_string(mode) + ", " + std::to_string(DIFF) + ">");
-    if (rc.volpath) hipLaunchKernelGGL((k_shade<MAXL, 3, (DIFF >= 2) ? 0 : DIFF>), dim3(blocks), dim3(256), 0, sc->stream, sc->ds, rc, g_tabs, grid, sc->ps, job);
-    else if (sc->ds.n_textures > 0) hipLaunchKernelGGL((k_shade<MAXL, 2, DIFF == 6 ? 0 : DIFF>), dim3(blocks), dim3(256), 0, sc->stream, sc->ds, rc, g_tabs, grid, sc->ps, job);
-    else if (sc->ds.n_spheres > 0 || sc->ds.n_instances > 0 || rc.halton.enabled) hipLaunchKernelGGL((k_shade<MAXL, 1, DIFF>), dim3(blocks), dim3(256), 0, sc->stream, sc->ds, rc, g_tabs, grid, sc->ps, job);
-    else hipLaunchKernelGGL((k_shade<MAXL, 0, DIFF>), dim3(blocks), dim3(256), 0, sc->stream, sc->ds, rc, g_tabs, grid, sc->ps, job);
-}
-
 // Samples per pass when the caller leaves the choice to the library (PtRenderParams.spp_per_pass = 0): as many paths in flight as the
 // memory allows, up to 2^28 (69 GB of path state + 17-36 GB of queues / probe state out of 288 GB). Every wavefront iteration ends
 // in a tail of straggling rays (~0.8 ms on S2, whatever the launch size), so fewer, larger iterations spend less of the render in tails:
@@ -293,7 +348,7 @@ constexpr double kPassMemFraction = 0.65;   // of the device's free memory
 uint32_t choose_pass_size(const pt_scene *sc, uint32_t n_pix_slots, uint32_t spp, uint32_t share, bool volpath) {
     // per path: the five state records, the queues, the probe state of scenes with subsurface materials and -- volpath through material-less shells -- the
     // 128-byte chain record (PathSoA::ext, allocated after the main slab: left out of this sum, a shell scene asked for ~1.4x its budget)
-    const size_t per_path = (size_t)kPathBytes + 4u * (2 + 2 * n_class_queues(sc) + 2 + (sc->has_bssrdf ? 2 : 0)) + (sc->has_bssrdf ? (size_t)kBssBytes : 0u)
+    const size_t per_path = (size_t)kPathBytes + 4u * n_queues(sc) + (sc->has_bssrdf ? (size_t)kBssBytes : 0u)
                             + ((volpath && sc->has_null_material) ? 4u * (size_t)PathSoA::kExtWords : 0u);
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
@@ -305,16 +360,12 @@ uint32_t choose_pass_size(const pt_scene *sc, uint32_t n_pix_slots, uint32_t spp
     return (spp + n_pass - 1) / n_pass;   // passes of equal size
 }
 
-// First-touch voxels of PT_LS_SPATIAL_LAZY. touch: the vertices of one queue name their voxels; fill: the voxels named since the last fill are
-// computed (k_light_grid_contrib over the list: 128 Halton points x every light each, lightdistrib.rs:151-228) and published in cell_ptr.
+// First-touch voxels of PT_LS_SPATIAL_LAZY. touch: the vertices of one queue name their voxels; fill: the voxels named since the last fill are computed and published.
 int lazy_light_touch(pt_scene *sc, const RenderConst &rc, const LightGrid &grid, const uint32_t *queue, const uint32_t *count, uint32_t n_upper, uint32_t kind) {
+    const pt_scene::LazyGrid &z = sc->lazy;
     if (!grid.cell_ptr || n_upper == 0) return PT_OK;
-    pt_scene::LazyGrid &z = sc->lazy;
-    const unsigned blocks = std::min<uint32_t>((n_upper + 255) / 256, (uint32_t)g_num_cus * 16u);
-    const bool sph = sc->ds.n_spheres > 0 || sc->ds.n_instances > 0;
-    sc->begin("light_touch", n_upper); sc->set_kernel(sph ? "k_light_touch<true>" : "k_light_touch<false>");
-    if (sph) hipLaunchKernelGGL((k_light_touch<true>), dim3(blocks), dim3(256), 0, sc->stream, sc->ds, grid, sc->ps, queue, count, kind, rc.max_depth, z.req_flag, z.req_list, z.req_count);
-    else hipLaunchKernelGGL((k_light_touch<false>), dim3(blocks), dim3(256), 0, sc->stream, sc->ds, grid, sc->ps, queue, count, kind, rc.max_depth, z.req_flag, z.req_list, z.req_count);
+    sc->begin("light_touch", n_upper);
+    launch(sc, touch_variant(general_geometry(sc)), blocks_for(n_upper, 16u), dim3(256), sc->ds, grid, sc->ps, queue, count, kind, rc.max_depth, z.req_flag, z.req_list, z.req_count);
     sc->end();
     return PT_OK;
 }
@@ -336,16 +387,11 @@ int lazy_light_fill(pt_scene *sc, const LightGrid &grid) {
         const size_t need = n * z.stride;
         if (need > z.arena_left) {
             const size_t slab = std::max<size_t>(need, (size_t)16 << 20);   // floats
-            int st;
-            if ((st = sc->dalloc(&z.arena, slab))) return st;
+            if (int st = sc->dalloc(&z.arena, slab)) return st;
             z.arena_left = slab;
         }
         float *blocks = z.arena; z.arena += need; z.arena_left -= need;
-        const size_t total = n * nl;
-        sc->begin("light_grid", total); sc->set_kernel("k_light_grid_contrib");
-        hipLaunchKernelGGL(k_light_grid_contrib, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, sc->stream, sc->ds, grid.nvox[0], grid.nvox[1], grid.nvox[2], blocks, (const uint32_t *)(z.req_list + first), n, z.stride);
-        hipLaunchKernelGGL(k_light_grid_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, sc->stream, nl, n, blocks, (float *)nullptr, (float *)nullptr, (const uint32_t *)(z.req_list + first), z.stride, z.cell_ptr);
-        sc->end();
+        light_grid_cells(sc, grid, n, blocks, nullptr, nullptr, z.req_list + first, z.stride, z.cell_ptr);
     }
     HIP_TRY(hipMemsetAsync(z.req_count, 0, 4, sc->stream));
     HIP_TRY(hipGetLastError());
@@ -364,230 +410,187 @@ const char *device_error_text(uint32_t code) {
     }
 }
 
-int run_pass(pt_scene *sc, RenderConst &rc, const LightGrid &grid, bool rp_profile_exact) {
+// ---- one pass. An iteration consumes the queue set `cur` and fills the other one: trace, route, touch, probe, shade per class, reset (run_pass below). Its steps see it as
+// an Iter: the queue sizes the host read at its start, and what the pass fixed (fin: the film kernel ends the paths, there is no miss class).
+struct Iter { pt_scene *sc; const RenderConst &rc; const LightGrid &grid; bool fin, profile_exact; int index, cur; uint32_t n_ext, n_resolve, n_shadow, n_mis, n_probe, n_stage_b; };
+
+// A shading job (ShadeJob / BssrdfJob) with the outputs all of them share: its queue, the next iteration's continuation-ray queue, miss queue (none when the film kernel
+// ends the paths) and the queue of class `self` (stage B of a volpath vertex), the shadow and MIS ray queues, the error word and the counters.
+template <class Job> Job shading_job(const Iter &it, const uint32_t *queue, const uint32_t *count, int self) {
+    pt_scene *sc = it.sc; QCounters *qc = sc->qc; const int nxt = 1 - it.cur;
+    Job j{}; j.queue = queue; j.count = count;
+    j.ext_next = sc->q.ext[nxt]; j.ext_next_count = &qc->ext[nxt];
+    if (!it.fin) { j.shade_next0 = sc->q.shade[nxt][kMissClass]; j.shade_next0_count = &qc->shade[nxt][kMissClass]; }
+    j.self_next = sc->q.shade[nxt][self]; j.self_next_count = &qc->shade[nxt][self];
+    j.shadow = sc->q.shadow; j.shadow_count = &qc->shadow; j.mis = sc->q.mis; j.mis_count = &qc->mis;
+    j.error = &qc->error; j.counters = sc->dc;
+    return j;
+}
+
+// The rays of one kind: their queue, where a ray lies (`ray`, ray_words apart) and the counter slot (TraceSub::kind). The caller adds where the hit goes.
+static TraceSub trace_sub(uint32_t *queue, uint32_t *count, const float *ray, int ray_words, float tmax, uint32_t kind) {
+    TraceSub s{}; s.queue = queue; s.count = count; s.ray = (const float4 *)ray; s.ray_stride = ray_words / 4; s.scalar_tmax = tmax; s.kind = kind; return s;
+}
+static TraceJob trace_job(pt_scene *sc, int head) { TraceJob tj{}; tj.spill = sc->spill; tj.error = &sc->qc->error; tj.counters = sc->dc; tj.head = &sc->qc->head[head]; return tj; }
+static int traced(pt_scene *sc, const char *stat, int any, const TraceJob &tj, uint32_t n_upper, bool probe = false) {
+    if (n_upper == 0) return PT_OK;   // (a launch kind with no work is not a launch: the per-launch averages of bench.py / rocprofv3 count real dispatches)
+    sc->begin(stat, n_upper); const int st = launch_trace(sc, any, tj, n_upper, probe); sc->end();
+    return st;
+}
+
+// trace: this iteration's continuation rays and the shadow / MIS rays of the vertices shaded in the previous one
+static int trace_rays(const Iter &it) {
+    pt_scene *sc = it.sc; QCounters *qc = sc->qc; PathSoA &ps = sc->ps; const RenderConst &rc = it.rc;
+    // continuation rays -> hit record (routed to the material classes next)
+    TraceSub ext = trace_sub(sc->q.ext[it.cur], &qc->ext[it.cur], ps.ray, PathSoA::kRayWords, INFINITY, it.index == 0 ? 3 : 0);
+    ext.out_hit = (float4 *)ps.hit; ext.out_hit_stride = PathSoA::kHitWords / 4; ext.out_hit2 = (float4 *)ps.hit + 1;   // {inst, t, packet, packet flags}
+    // MIS rays of the previous vertex (closest hit, integrator.rs:215)
+    TraceSub mis = trace_sub(sc->q.mis, &qc->mis, ps.mis, PathSoA::kMisWords, INFINITY, 1);
+    mis.out_hit = (float4 *)&ps.mis_prim(0); mis.out_hit_stride = PathSoA::kMisWords / 4;
+    mis.out_t = rc.volpath ? &ps.mis_t(0) : nullptr; mis.out_t_stride = PathSoA::kMisWords;
+    const bool shells = rc.volpath && ps.ext != nullptr;   // the chains of VisibilityTester::tr / Scene::intersect_tr need every segment's full hit record
+    if (shells) { mis.out_hit = (float4 *)ps.ext + 6; mis.out_hit_stride = PathSoA::kExtWords / 4; mis.out_hit2 = (float4 *)ps.ext + 7; mis.out_t = nullptr; }
+    // shadow rays (any hit, light.rs:120-123). volpath: VisibilityTester::tr (light.rs:125-150) calls Scene::intersect, a closest-hit
+    // query counted as one; without out_hit the primitive goes to out_word = nee.sh_prim, the slot `occluded` uses otherwise
+    TraceSub sh = trace_sub(sc->q.shadow, &qc->shadow, ps.nee, PathSoA::kNeeWords, 1.0f - 0.0001f, 2);
+    sh.out_word = &ps.occluded(0); sh.out_word_stride = PathSoA::kNeeWords; sh.any = rc.volpath ? 0u : 1u;
+    if (shells) { sh.out_hit = (float4 *)ps.ext + 4; sh.out_hit_stride = PathSoA::kExtWords / 4; sh.out_hit2 = (float4 *)ps.ext + 5; }
+    if (it.n_mis + it.n_shadow == 0 || g_trace_split) {   // camera rays (nothing else to trace in the first iteration) / PT_TRACE_SPLIT=1: one launch per kind, each with its own work head
+        auto one = [&](const char *stat, const TraceSub &sub, int head, int any, uint32_t n) { TraceJob tj = trace_job(sc, head); tj.sub[0] = sub; return traced(sc, stat, any, tj, n); };
+        int st;
+        if ((st = one(it.index == 0 ? "extend_camera" : "extend", ext, 0, 0, it.n_ext)) || (st = one("extend_mis", mis, 1, 0, it.n_mis))) return st;
+        return one("shadow", sh, 2, (int)sh.any, it.n_shadow);
+    }
+    TraceJob tj = trace_job(sc, 0);   // the three ray kinds of this iteration in one launch: one tail of straggling rays instead of three
+    tj.sub[0] = ext; tj.sub[1] = mis; tj.sub[2] = sh;
+    return traced(sc, "trace", 2, tj, it.n_ext + it.n_mis + it.n_shadow);
+}
+
+// route: every hit goes to the shade queue of its material class. volpath: after medium sampling (volpath.rs:98-105), which may make the vertex a medium vertex
+static void route_hits(const Iter &it) {
+    pt_scene *sc = it.sc; QCounters *qc = sc->qc; const int cur = it.cur;
+    if (it.n_ext == 0) return;
+    sc->begin("route", it.n_ext);
+    if (it.rc.volpath) {
+        launch(sc, "k_medium_route", k_medium_route, blocks_for(it.n_ext, 8u), dim3(256), sc->ds, it.rc, g_tabs, sc->ps, sc->q.ext[cur], &qc->ext[cur], &qc->shade[cur][0],
+               sc->q.shade[cur][0], sc->q.shade[cur][1], sc->q.shade[cur][2], sc->q.shade[cur][3], sc->q.shade[cur][4], sc->q.shade[cur][5], &qc->error);
+    } else {
+        RouteJob rj{}; rj.slot_map = ~0ull; rj.error = &qc->error; rj.drop_cls = it.fin ? (uint32_t)kMissClass : ~0u;   // (fin: escaped rays are dropped here, the film kernel ends them)
+        int slot_of[kNumClasses]; std::fill(slot_of, slot_of + kNumClasses, -1);
+        for (int c = 0; c < kNumClasses; ++c) {   // class c's nibble of slot_map names the staging queue ("slot") of the class it is shaded in; no hit is a medium vertex
+            const int q = kClasses[c].kind == kMedium ? -1 : kClasses[c].kind == kMiss ? (it.fin ? -1 : c) : shaded_in(sc, c, false);
+            if (q < 0) continue;
+            if (slot_of[q] < 0) { slot_of[q] = (int)rj.n_slots; rj.cls_of_slot[rj.n_slots] = (uint32_t)q; rj.buf[rj.n_slots++] = sc->q.shade[cur][q]; }
+            rj.slot_map = (rj.slot_map & ~(15ull << (4 * c))) | ((unsigned long long)slot_of[q] << (4 * c));
+        }
+        launch(sc, route_variant(rj.n_slots), blocks_for(it.n_ext, PT_ROUTE_BLOCKS_PER_CU), dim3(256), sc->ds, sc->q.ext[cur], &qc->ext[cur], sc->ps, &qc->shade[cur][0], rj);
+    }
+    sc->end();
+}
+
+// touch (first-touch light grids only): the vertices of every shade queue name their voxels, then the new ones are computed
+static int touch_voxels(const Iter &it) {
+    pt_scene *sc = it.sc;
+    for (int c = 0; c < kNumClasses; ++c) {
+        if (kClasses[c].kind == kMiss || !class_has_queue(sc, c)) continue;
+        if (int st = lazy_light_touch(sc, it.rc, it.grid, sc->q.shade[it.cur][c], &sc->qc->shade[it.cur][c], it.n_ext + it.n_resolve + it.n_stage_b, kClasses[c].kind == kMedium ? 1u : 0u)) return st;
+    }
+    return lazy_light_fill(sc, it.grid);
+}
+
+// probe: subsurface probe chains (bssrdf.rs:367-402). Each lane of k_trace<.., PROBE> walks a whole chain, then k_bssrdf shades the vertex at the chain's exit point
+static int probe_chains(const Iter &it) {
+    pt_scene *sc = it.sc; QCounters *qc = sc->qc; PathSoA &ps = sc->ps; const int cur = it.cur;
+    if (it.n_probe == 0) return PT_OK;
+    TraceSub pr = trace_sub(sc->q.probe[cur], &qc->probe[cur], ps.ray, PathSoA::kRayWords, 1.0f - 0.0001f, 4);
+    pr.out_hit = (float4 *)ps.hit; pr.out_hit_stride = PathSoA::kHitWords / 4; pr.out_hit2 = (float4 *)ps.hit + 1;
+    TraceJob tj = trace_job(sc, 3); tj.sub[0] = pr; tj.bs = sc->bs; tj.ring = sc->probe_ring;
+    int st;
+    if ((st = traced(sc, "extend_probe", 0, tj, it.n_probe, true))) return st;
+    // (first-touch light grids: the chains' exit points look their voxels up in k_bssrdf)
+    if ((st = lazy_light_touch(sc, it.rc, it.grid, sc->q.probe[cur], &qc->probe[cur], it.n_probe, 2u)) || (st = lazy_light_fill(sc, it.grid))) return st;
+    BssrdfJob bj = shading_job<BssrdfJob>(it, sc->q.probe[cur], &qc->probe[cur], kSpecClass);   // (self: under volpath the exit points wait for stage B in the specular class's queue)
+    bj.bs = sc->bs;
+    sc->begin("bssrdf", it.n_probe);
+    launch(sc, bssrdf_variant(general_geometry(sc), it.rc.volpath), blocks_for(it.n_probe, PT_SHADE_BLOCKS_PER_CU), dim3(256), sc->ds, it.rc, g_tabs, it.grid, ps, bj);
+    sc->end();
+    return PT_OK;
+}
+
+// shade: the n (an upper bound unless the pass counts exactly) vertices in the queue of class c, by the kernel of the class's kind
+static void shade_class(const Iter &it, int c, uint32_t n) {
+    pt_scene *sc = it.sc; QCounters *qc = sc->qc; const RenderConst &rc = it.rc; const ClassInfo &ci = kClasses[c];
+    if (n == 0) return;
+    if (ci.kind == kSpecularOrStageB && rc.volpath) {   // exit-point vertices of subsurface chains in stage B (k_bssrdf put them here an iteration ago)
+        if (!sc->has_bssrdf || !(sc->ds.has_grid || sc->ds.has_shells)) return;
+        BssrdfJob bj = shading_job<BssrdfJob>(it, sc->q.shade[it.cur][c], &qc->shade[it.cur][c], c);
+        bj.bs = sc->bs; bj.stage_b = 1u;
+        sc->begin("bssrdf_stage_b", it.profile_exact ? n : 0);
+        launch(sc, bssrdf_variant(general_geometry(sc), true), blocks_for(n, PT_SHADE_BLOCKS_PER_CU), dim3(256), sc->ds, rc, g_tabs, it.grid, sc->ps, bj);
+        sc->end();
+        return;
+    }
+    if (!class_launched(sc, c, rc.volpath != 0) || (ci.kind == kMiss && it.fin)) return;
+    ShadeJob sj = shading_job<ShadeJob>(it, sc->q.shade[it.cur][c], &qc->shade[it.cur][c], c);
+    sj.cls = (uint32_t)c;
+    if ((c == 3 || c == kSssClass) && sc->has_bssrdf) { sj.probe_next = sc->q.probe[1 - it.cur]; sj.probe_next_count = &qc->probe[1 - it.cur]; sj.bs = sc->bs; }
+    sc->begin(ci.stat, it.profile_exact ? n : 0);
+    if (ci.kind == kMedium) launch(sc, "k_shade_medium", k_shade_medium, blocks_for(n, 8u), dim3(256), sc->ds, rc, g_tabs, it.grid, sc->ps, sj);
+    else if (ci.kind == kMiss) launch(sc, miss_variant(general_geometry(sc), rc.volpath != 0), blocks_for(n, PT_MISS_BLOCKS_PER_CU), dim3(256), sc->ds, rc, sc->ps, sj);
+    else ci.launch(sc, rc, it.grid, sj, n);
+    sc->end();
+}
+
+int run_pass(pt_scene *sc, RenderConst &rc, const LightGrid &grid, bool rp_profile_exact, int max_iterations) {
     const uint32_t total = rc.n_pix_slots * rc.s_count;
     QCounters *qc = sc->qc;
     HIP_TRY(hipMemsetAsync(qc, 0, offsetof(QCounters, error), sc->stream));
     sc->begin("generate", total);
-        sc->set_kernel("k_generate");
-    #ifndef PT_GEN_BLOCKS_PER_CU
-#define PT_GEN_BLOCKS_PER_CU 40u   // experiment hook (16 -> 40: k_generate 12.2 -> 11.7 ms on C2; the miss kernel does not care)
-#endif
-    hipLaunchKernelGGL(k_generate, dim3(std::min<uint32_t>((total + 255) / 256, (uint32_t)g_num_cus * PT_GEN_BLOCKS_PER_CU)), dim3(256), 0, sc->stream, rc, g_tabs, sc->ps, sc->q.ext[0], &qc->ext[0], sc->dc);
+    launch(sc, "k_generate", k_generate, blocks_for(total, PT_GEN_BLOCKS_PER_CU), dim3(256), rc, g_tabs, sc->ps, sc->q.ext[0], &qc->ext[0], sc->dc);
     sc->end();
     // The plain path integrator's paths are ended by the film kernel (k_film_final, kern_aux.h): no miss class, no k_shade_miss pass. Volpath keeps the pass (its
     // transmittance estimates draw sampler dimensions in iteration order).
-    const bool fin = g_film_final && !rc.volpath;
-    int cur = 0;
-    static const char *shade_names[kNumClasses] = {"shade_matte", "shade_1lobe", "shade_2lobe", "shade_manylobe", "shade_miss", "shade_medium", "shade_specular", "shade_metal", "shade_plastic", "shade_uber", "shade_sss"};
-    const int kMaxIterations = g_test_max_iterations > 0 ? g_test_max_iterations : 1 << 20;   // a path needs <= max_depth + null-surface skips + probe segments iterations (PT_TEST_MAX_ITERATIONS: the error path's test)
-    for (int iter = 0; iter <= kMaxIterations; ++iter) {
+    Iter it{sc, rc, grid, g_film_final && !rc.volpath, rp_profile_exact};
+    const bool debug_iter = getenv("PT_DEBUG_ITER") != nullptr;
+    auto reset = [&](uint32_t mask) { hipLaunchKernelGGL(k_reset, dim3(1), dim3(64), 0, sc->stream, qc, mask, it.cur); };
+    int st;
+    for (it.index = 0, it.cur = 0; it.index <= max_iterations; ++it.index, it.cur = 1 - it.cur) {   // a path needs <= max_depth + null-surface skips + probe segments iterations
         QCounters h;
         HIP_TRY(hipMemcpyAsync(&h, qc, sizeof h, hipMemcpyDeviceToHost, sc->stream));
         HIP_TRY(hipStreamSynchronize(sc->stream));
         if (h.error) return fail((int)h.error, device_error_text(h.error));
-        if (iter == kMaxIterations) return fail(PT_ERR_PROBE_CHAIN, "pass did not finish within " + std::to_string(kMaxIterations) + " wavefront iterations");
-        if (iter > 0 && iter % 2048 == 0 && getenv("PT_DEBUG_ITER")) {
-            fprintf(stderr, "[iter %d] ext %u shadow %u mis %u probe %u shade:", iter, h.ext[cur], h.shadow, h.mis, h.probe[cur]);
+        if (it.index == max_iterations) return fail(PT_ERR_PROBE_CHAIN, "pass did not finish within " + std::to_string(max_iterations) + " wavefront iterations");
+        const int cur = it.cur;
+        if (debug_iter && it.index > 0 && it.index % 2048 == 0) {
+            fprintf(stderr, "[iter %d] ext %u shadow %u mis %u probe %u shade:", it.index, h.ext[cur], h.shadow, h.mis, h.probe[cur]);
             for (int c = 0; c < kNumClasses; ++c) fprintf(stderr, " %u", h.shade[cur][c]);
             fprintf(stderr, "\n");
         }
-        const uint32_t n_ext = h.ext[cur], n_resolve = h.shade[cur][kMissClass], n_shadow = h.shadow, n_mis = h.mis, n_probe = h.probe[cur];
+        it.n_ext = h.ext[cur]; it.n_resolve = h.shade[cur][kMissClass]; it.n_shadow = h.shadow; it.n_mis = h.mis; it.n_probe = h.probe[cur];
         // volpath with grid media: vertices that did their NEE set-up last iteration wait in their own shade class for stage B
-        uint32_t n_stage_b = 0;
-        if (rc.volpath && (sc->ds.has_grid || sc->ds.has_shells)) for (int c = 0; c < kNumClasses; ++c) if (c != kMissClass) n_stage_b += h.shade[cur][c];
-        if (n_ext == 0 && n_resolve == 0 && n_probe == 0 && n_stage_b == 0 && (!fin || (n_shadow == 0 && n_mis == 0))) break;   // (fin: the last vertices' shadow / MIS rays are still to be traced)
-        hipLaunchKernelGGL(k_reset, dim3(1), dim3(64), 0, sc->stream, qc, 4u | 1u, cur);
-        TraceJob tj{};
-        tj.spill = sc->spill; tj.error = &qc->error; tj.counters = sc->dc; tj.head = &qc->head[0];
-        PathSoA &ps = sc->ps;
-        // continuation rays -> hit record (routed to the material classes below)
-        TraceSub ext{};
-        ext.queue = sc->q.ext[cur]; ext.count = &qc->ext[cur]; ext.scalar_tmax = INFINITY;
-        ext.ray = (const float4 *)ps.ray; ext.ray_stride = PathSoA::kRayWords / 4;
-        ext.out_hit = (float4 *)ps.hit; ext.out_hit_stride = PathSoA::kHitWords / 4; ext.out_hit2 = (float4 *)ps.hit + 1;   // {inst, t, packet, packet flags}
-        ext.kind = (iter == 0) ? 3 : 0;
-        // MIS rays of the previous vertex (closest hit, integrator.rs:215)
-        TraceSub mis{};
-        mis.queue = sc->q.mis; mis.count = &qc->mis; mis.scalar_tmax = INFINITY;
-        mis.ray = (const float4 *)ps.mis; mis.ray_stride = PathSoA::kMisWords / 4;
-        mis.out_hit = (float4 *)&ps.mis_prim(0); mis.out_hit_stride = PathSoA::kMisWords / 4;
-        mis.out_t = rc.volpath ? &ps.mis_t(0) : nullptr; mis.out_t_stride = PathSoA::kMisWords;
-        mis.kind = 1;
-        const bool shells = rc.volpath && ps.ext != nullptr;   // the chains of VisibilityTester::tr / Scene::intersect_tr need every segment's full hit record
-        if (shells) { mis.out_hit = (float4 *)ps.ext + 6; mis.out_hit_stride = PathSoA::kExtWords / 4; mis.out_hit2 = (float4 *)ps.ext + 7; mis.out_t = nullptr; }
-        // shadow rays (any hit, light.rs:120-123). volpath: VisibilityTester::tr (light.rs:125-150) calls Scene::intersect, a closest-hit
-        // query counted as one; without out_hit the primitive goes to out_word = nee.sh_prim, the slot `occluded` uses otherwise
-        TraceSub sh{};
-        sh.queue = sc->q.shadow; sh.count = &qc->shadow; sh.scalar_tmax = 1.0f - 0.0001f;
-        sh.ray = (const float4 *)ps.nee; sh.ray_stride = PathSoA::kNeeWords / 4;
-        sh.out_word = &ps.occluded(0); sh.out_word_stride = PathSoA::kNeeWords;
-        sh.kind = 2; sh.any = rc.volpath ? 0u : 1u;
-        if (shells) { sh.out_hit = (float4 *)ps.ext + 4; sh.out_hit_stride = PathSoA::kExtWords / 4; sh.out_hit2 = (float4 *)ps.ext + 5; }
-        int st = PT_OK;
-        if (n_mis + n_shadow == 0 || g_trace_split) {   // camera rays (nothing else to trace in the first iteration) / PT_TRACE_SPLIT=1: one launch per kind
-            if (n_ext) {   // (a launch kind with no work is not a launch: the per-launch averages of bench.py / rocprofv3 count real dispatches)
-                tj.sub[0] = ext;
-                sc->begin(iter == 0 ? "extend_camera" : "extend", n_ext);
-                st = launch_trace(sc, 0, tj, n_ext);
-                sc->end();
-                if (st) return st;
-            }
-            if (n_mis) {
-                tj.sub[0] = mis; tj.head = &qc->head[1];
-                sc->begin("extend_mis", n_mis);
-                st = launch_trace(sc, 0, tj, n_mis);
-                sc->end();
-                if (st) return st;
-            }
-            if (n_shadow) {
-                tj.sub[0] = sh; tj.head = &qc->head[2];
-                sc->begin("shadow", n_shadow);
-                st = launch_trace(sc, (int)sh.any, tj, n_shadow);
-                sc->end();
-                if (st) return st;
-            }
-        } else {   // the three ray kinds of this iteration in one launch: one tail of straggling rays instead of three
-            tj.sub[0] = ext; tj.sub[1] = mis; tj.sub[2] = sh;
-            sc->begin("trace", (uint64_t)n_ext + n_mis + n_shadow);
-            st = launch_trace(sc, 2, tj, n_ext + n_mis + n_shadow);
-            sc->end();
-            if (st) return st;
-        }
-        if (n_ext && rc.volpath) {  // medium sampling (volpath.rs:98-105) + material-sorted shade queues + the medium-vertex queue
-            sc->begin("route", n_ext); sc->set_kernel("k_medium_route");
-            hipLaunchKernelGGL(k_medium_route, dim3(std::min<uint32_t>((n_ext + 255) / 256, (uint32_t)g_num_cus * 8u)), dim3(256), 0, sc->stream, sc->ds, rc, g_tabs, sc->ps,
-                               (const uint32_t *)sc->q.ext[cur], (const uint32_t *)&qc->ext[cur], &qc->shade[cur][0],
-                               sc->q.shade[cur][0], sc->q.shade[cur][1], sc->q.shade[cur][2], sc->q.shade[cur][3], sc->q.shade[cur][4], sc->q.shade[cur][5], &qc->error);
-            sc->end();
-        } else if (n_ext) {  // material-sorted shade queues
-            sc->begin("route", n_ext); sc->set_kernel("k_route<6, 2048>");
-            #ifndef PT_ROUTE_BLOCKS_PER_CU
-#define PT_ROUTE_BLOCKS_PER_CU 3u   // what a CU's LDS holds of this kernel (six 8 KB staging queues per block)
-#endif
-            RouteJob rj{}; rj.slot_map = ~0ull; rj.error = &qc->error; rj.drop_cls = fin ? (uint32_t)kMissClass : ~0u;
-            for (int c = 0; c < kNumClasses; ++c) if (c != kMediumClass && ((c == kMissClass && !fin) || (c != kMissClass && sc->class_used[c]))) {   // (fin: escaped rays are dropped here, the film kernel ends them)
-                rj.slot_map = (rj.slot_map & ~(15ull << (4 * c))) | ((unsigned long long)rj.n_slots << (4 * c));
-                rj.cls_of_slot[rj.n_slots] = (uint32_t)c; rj.buf[rj.n_slots] = sc->q.shade[cur][c]; rj.n_slots++;
-            }
-            const dim3 rgrid(std::min<uint32_t>((n_ext + 255) / 256, (uint32_t)g_num_cus * PT_ROUTE_BLOCKS_PER_CU));
-            if (rj.n_slots <= 6) hipLaunchKernelGGL((k_route<6, 2048>), rgrid, dim3(256), 0, sc->stream, sc->ds, (const uint32_t *)sc->q.ext[cur], (const uint32_t *)&qc->ext[cur], sc->ps, &qc->shade[cur][0], rj);
-            else { sc->set_kernel("k_route<12, 1024>"); hipLaunchKernelGGL((k_route<12, 1024>), rgrid, dim3(256), 0, sc->stream, sc->ds, (const uint32_t *)sc->q.ext[cur], (const uint32_t *)&qc->ext[cur], sc->ps, &qc->shade[cur][0], rj); }
-            sc->end();
-        }
-        hipLaunchKernelGGL(k_reset, dim3(1), dim3(64), 0, sc->stream, qc, 2u, cur);
-        if (grid.cell_ptr) {   // first-touch voxels: the vertices of every shade class name theirs, then the new ones are computed
-            const uint32_t upper0 = n_ext + n_resolve;
-            for (int c = 0; c < kNumClasses; ++c) {
-                if (c == kMissClass || !class_has_queue(sc, c)) continue;
-                if ((st = lazy_light_touch(sc, rc, grid, sc->q.shade[cur][c], &qc->shade[cur][c], upper0 + n_stage_b, c == kMediumClass ? 1u : 0u))) return st;
-            }
-            if ((st = lazy_light_fill(sc, grid))) return st;
-        }
-        if (n_probe) {  // subsurface probe chains (bssrdf.rs:367-402): each lane of k_trace<.., PROBE> walks a whole chain, then k_bssrdf
-            TraceSub pr{};
-            pr.queue = sc->q.probe[cur]; pr.count = &qc->probe[cur]; pr.scalar_tmax = 1.0f - 0.0001f;
-            pr.ray = (const float4 *)ps.ray; pr.ray_stride = PathSoA::kRayWords / 4;
-            pr.out_hit = (float4 *)ps.hit; pr.out_hit_stride = PathSoA::kHitWords / 4; pr.out_hit2 = (float4 *)ps.hit + 1;
-            pr.kind = 4;
-            tj.sub[0] = pr; tj.head = &qc->head[3]; tj.bs = sc->bs; tj.ring = sc->probe_ring;
-            sc->begin("extend_probe", n_probe);
-            st = launch_trace(sc, 0, tj, n_probe, true);
-            sc->end();
-            if (st) return st;
-            if (grid.cell_ptr) {   // the chains' exit points look their voxels up in k_bssrdf
-                if ((st = lazy_light_touch(sc, rc, grid, sc->q.probe[cur], &qc->probe[cur], n_probe, 2u))) return st;
-                if ((st = lazy_light_fill(sc, grid))) return st;
-            }
-            BssrdfJob bj{};
-            bj.queue = sc->q.probe[cur]; bj.count = &qc->probe[cur];
-            bj.self_next = sc->q.shade[1 - cur][kSpecClass]; bj.self_next_count = &qc->shade[1 - cur][kSpecClass];   // (volpath has no specular-only class: its queue serves the waiting exit-point vertices)
-            bj.ext_next = sc->q.ext[1 - cur]; bj.ext_next_count = &qc->ext[1 - cur];
-            if (!fin) { bj.shade_next0 = sc->q.shade[1 - cur][kMissClass]; bj.shade_next0_count = &qc->shade[1 - cur][kMissClass]; }
-            bj.shadow = sc->q.shadow; bj.shadow_count = &qc->shadow; bj.mis = sc->q.mis; bj.mis_count = &qc->mis;
-            bj.error = &qc->error; bj.counters = sc->dc; bj.bs = sc->bs;
-            const uint32_t blocks = std::min<uint32_t>((n_probe + 255) / 256, (uint32_t)g_num_cus * PT_SHADE_BLOCKS_PER_CU);
-            sc->begin("bssrdf", n_probe);
-            const bool bsph = sc->ds.n_spheres > 0 || sc->ds.n_instances > 0;
-            sc->set_kernel(rc.volpath ? "k_bssrdf<true, true>" : bsph ? "k_bssrdf<true, false>" : "k_bssrdf<false, false>");
-            if (rc.volpath) hipLaunchKernelGGL((k_bssrdf<true, true>), dim3(blocks), dim3(256), 0, sc->stream, sc->ds, rc, g_tabs, grid, sc->ps, bj);
-            else if (bsph) hipLaunchKernelGGL((k_bssrdf<true, false>), dim3(blocks), dim3(256), 0, sc->stream, sc->ds, rc, g_tabs, grid, sc->ps, bj);
-            else hipLaunchKernelGGL((k_bssrdf<false, false>), dim3(blocks), dim3(256), 0, sc->stream, sc->ds, rc, g_tabs, grid, sc->ps, bj);
-            sc->end();
-        }
+        it.n_stage_b = 0;
+        if (rc.volpath && (sc->ds.has_grid || sc->ds.has_shells)) for (int c = 0; c < kNumClasses; ++c) if (c != kMissClass) it.n_stage_b += h.shade[cur][c];
+        if (it.n_ext == 0 && it.n_resolve == 0 && it.n_probe == 0 && it.n_stage_b == 0 && (!it.fin || (it.n_shadow == 0 && it.n_mis == 0))) break;   // (fin: the last vertices' shadow / MIS rays are still to be traced)
+        reset(4u | 1u);
+        if ((st = trace_rays(it))) return st;
+        route_hits(it);
+        reset(2u);
+        if ((st = touch_voxels(it)) || (st = probe_chains(it))) return st;
         uint32_t class_n[kNumClasses];
-        const uint32_t upper = n_ext + n_resolve + n_stage_b;
         if (rp_profile_exact) {  // exact per-class item counts for the statistics (costs one extra sync per iteration)
             QCounters h2;
             HIP_TRY(hipMemcpyAsync(&h2, qc, sizeof h2, hipMemcpyDeviceToHost, sc->stream));
             HIP_TRY(hipStreamSynchronize(sc->stream));
             for (int c = 0; c < kNumClasses; ++c) class_n[c] = h2.shade[cur][c];
-        } else for (int c = 0; c < kNumClasses; ++c) class_n[c] = upper;
-        for (int c = 0; c < kNumClasses; ++c) {
-            bool used = sc->class_used[c] || (c == 1 && rc.volpath && sc->class_used[kSpecClass]);   // (the volumetric router folds class 6 into class 1)
-            if (rc.volpath) { if (c > kSpecClass) used = false; else for (int k = kSpecClass + 1; k < kNumClasses; ++k) if (sc->class_used[k] && class_general((uint32_t)k) == (uint32_t)c) used = true; }   // (... and the lobe-set classes into their lobe-count class)
-            if (c == kSpecClass && rc.volpath) {   // exit-point vertices of subsurface chains in stage B (k_bssrdf put them here an iteration ago)
-                if (!sc->has_bssrdf || !(sc->ds.has_grid || sc->ds.has_shells) || class_n[c] == 0) continue;
-                BssrdfJob bj{};
-                bj.queue = sc->q.shade[cur][c]; bj.count = &qc->shade[cur][c];
-                bj.ext_next = sc->q.ext[1 - cur]; bj.ext_next_count = &qc->ext[1 - cur];
-                bj.shade_next0 = sc->q.shade[1 - cur][kMissClass]; bj.shade_next0_count = &qc->shade[1 - cur][kMissClass];
-                bj.shadow = sc->q.shadow; bj.shadow_count = &qc->shadow; bj.mis = sc->q.mis; bj.mis_count = &qc->mis;
-                bj.error = &qc->error; bj.counters = sc->dc; bj.bs = sc->bs;
-                bj.self_next = sc->q.shade[1 - cur][c]; bj.self_next_count = &qc->shade[1 - cur][c]; bj.stage_b = 1u;
-                sc->begin("bssrdf_stage_b", rp_profile_exact ? class_n[c] : 0);
-                sc->set_kernel("k_bssrdf<true, true>");
-                hipLaunchKernelGGL((k_bssrdf<true, true>), dim3(std::min<uint32_t>((class_n[c] + 255) / 256, (uint32_t)g_num_cus * PT_SHADE_BLOCKS_PER_CU)), dim3(256), 0, sc->stream, sc->ds, rc, g_tabs, grid, sc->ps, bj);
-                sc->end();
-                continue;
-            }
-            if (!used || class_n[c] == 0 || (c == kMissClass && fin)) continue;
-            ShadeJob sj{};
-            sj.queue = sc->q.shade[cur][c]; sj.count = &qc->shade[cur][c];
-            sj.ext_next = sc->q.ext[1 - cur]; sj.ext_next_count = &qc->ext[1 - cur];
-            if (!fin) { sj.shade_next0 = sc->q.shade[1 - cur][kMissClass]; sj.shade_next0_count = &qc->shade[1 - cur][kMissClass]; }
-            sj.shadow = sc->q.shadow; sj.shadow_count = &qc->shadow; sj.mis = sc->q.mis; sj.mis_count = &qc->mis;
-            sj.error = &qc->error; sj.counters = sc->dc; sj.cls = (uint32_t)c;
-            sj.self_next = sc->q.shade[1 - cur][c]; sj.self_next_count = &qc->shade[1 - cur][c];
-            if ((c == 3 || c == kSssClass) && sc->has_bssrdf) { sj.probe_next = sc->q.probe[1 - cur]; sj.probe_next_count = &qc->probe[1 - cur]; sj.bs = sc->bs; }
-            sc->begin(shade_names[c], rp_profile_exact ? class_n[c] : 0);
-            if (c == kMediumClass) {
-                const uint32_t blocks = std::min<uint32_t>((class_n[c] + 255) / 256, (uint32_t)g_num_cus * 8u);
-                sc->set_kernel("k_shade_medium");
-                hipLaunchKernelGGL(k_shade_medium, dim3(blocks), dim3(256), 0, sc->stream, sc->ds, rc, g_tabs, grid, sc->ps, sj);
-            }
-            else if (c == kMissClass) {
-                #ifndef PT_MISS_BLOCKS_PER_CU
-#define PT_MISS_BLOCKS_PER_CU 16u   // experiment hook
-#endif
-                const uint32_t blocks = std::min<uint32_t>((class_n[c] + 255) / 256, (uint32_t)g_num_cus * PT_MISS_BLOCKS_PER_CU);
-                sc->set_kernel(rc.volpath ? "k_shade_miss<true, true>" : (sc->ds.n_spheres > 0 || sc->ds.n_instances > 0) ? "k_shade_miss<true, false>" : "k_shade_miss<false, false>");
-                if (rc.volpath) hipLaunchKernelGGL((k_shade_miss<true, true>), dim3(blocks), dim3(256), 0, sc->stream, sc->ds, rc, sc->ps, sj);
-                else if (sc->ds.n_spheres > 0 || sc->ds.n_instances > 0) hipLaunchKernelGGL((k_shade_miss<true, false>), dim3(blocks), dim3(256), 0, sc->stream, sc->ds, rc, sc->ps, sj);
-                else hipLaunchKernelGGL((k_shade_miss<false, false>), dim3(blocks), dim3(256), 0, sc->stream, sc->ds, rc, sc->ps, sj);
-            }
-            else if (c == 0) launch_shade<1, 1>(sc, rc, grid, sj, class_n[c]);
-            else if (c == kSpecClass) launch_shade<1, 2>(sc, rc, grid, sj, class_n[c]);
-            else if (c == 1) launch_shade<1>(sc, rc, grid, sj, class_n[c]);
-            else if (c == 2) launch_shade<2>(sc, rc, grid, sj, class_n[c]);
-            else if (c == kMetalClass) launch_shade<1, 3>(sc, rc, grid, sj, class_n[c]);     // (the lobe-set classes exist in untextured scenes only and never reach this loop under volpath)
-            else if (c == kPlasticClass) launch_shade<2, 4>(sc, rc, grid, sj, class_n[c]);
-            else if (c == kUberClass) launch_shade<5, 5>(sc, rc, grid, sj, class_n[c]);
-            else if (c == kSssClass) launch_shade<1, 6>(sc, rc, grid, sj, class_n[c]);
-            else launch_shade<5>(sc, rc, grid, sj, class_n[c]);
-            sc->end();
-        }
+        } else for (int c = 0; c < kNumClasses; ++c) class_n[c] = it.n_ext + it.n_resolve + it.n_stage_b;
+        for (int c = 0; c < kNumClasses; ++c) shade_class(it, c, class_n[c]);
         HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_reset, dim3(1), dim3(64), 0, sc->stream, qc, 8u, cur);
-        cur = 1 - cur;
+        reset(8u);
     }
     sc->begin("film", total);
-    const bool fsph = sc->ds.n_spheres > 0 || sc->ds.n_instances > 0;
-    sc->set_kernel(fin ? (fsph ? "k_film_final<true>" : "k_film_final<false>") : "k_film");
     const dim3 fgrid((unsigned)(((size_t)rc.n_pix_slots * kFilmLanes + 255) / 256));   // kFilmLanes threads per pixel slot (kern_film.h)
-    if (fin && fsph) hipLaunchKernelGGL((k_film_final<true>), fgrid, dim3(256), 0, sc->stream, sc->ds, rc, sc->ps, sc->d_filter, sc->film_rgbw, sc->dc);
-    else if (fin) hipLaunchKernelGGL((k_film_final<false>), fgrid, dim3(256), 0, sc->stream, sc->ds, rc, sc->ps, sc->d_filter, sc->film_rgbw, sc->dc);
-    else hipLaunchKernelGGL(k_film, fgrid, dim3(256), 0, sc->stream, rc, sc->ps, sc->d_filter, sc->film_rgbw, sc->dc);
+    if (it.fin) launch(sc, film_final_variant(general_geometry(sc)), fgrid, dim3(256), sc->ds, rc, sc->ps, sc->d_filter, sc->film_rgbw, sc->dc);
+    else launch(sc, "k_film", k_film, fgrid, dim3(256), rc, sc->ps, sc->d_filter, sc->film_rgbw, sc->dc);
     sc->end();
     HIP_TRY(hipGetLastError());
     return PT_OK;
@@ -604,8 +607,7 @@ void read_counters(pt_scene *sc) {
     for (int i = 0; i < 16; ++i) c.path_length_hist[i] = d.path_len[i];
     c.sanitized_nan = d.san_nan; c.sanitized_negative = d.san_neg; c.sanitized_infinite = d.san_inf;
     c.film_splats = d.splats; c.wavefront_stages = d.stages; c.reference_asserts = d.ref_asserts;
-    static const char *sn[kNumClasses] = {"shade_matte", "shade_1lobe", "shade_2lobe", "shade_manylobe", "shade_miss", "shade_medium", "shade_specular", "shade_metal", "shade_plastic", "shade_uber", "shade_sss"};
-    for (int k = 0; k < kNumClasses; ++k) for (auto &s : sc->stats) if (s.name == sn[k]) { s.items = d.shade_items[k]; s.nodes = d.shade_bytes[k]; }
+    for (int k = 0; k < kNumClasses; ++k) for (auto &s : sc->stats) if (s.name == kClasses[k].stat) { s.items = d.shade_items[k]; s.nodes = d.shade_bytes[k]; }
     static const char *kn[5] = {"extend", "extend_mis", "shadow", "extend_camera", "extend_probe"};
     for (int k = 0; k < 5; ++k) for (auto &s : sc->stats) if (s.name == kn[k]) { s.nodes = d.k_nodes[k]; s.tris = d.k_tris[k]; if (k == 4) s.items = d.k_rays[k]; }   // probe chains: items = segments traced
     for (auto &s : sc->stats) if (s.name == "trace") { s.nodes = d.k_nodes[0] + d.k_nodes[1] + d.k_nodes[2]; s.tris = d.k_tris[0] + d.k_tris[1] + d.k_tris[2]; }   // the mixed launches: all three kinds
@@ -685,8 +687,8 @@ int pt_render(pt_scene *sc, const PtRenderParams *rp, float *film_xyzw, int film
     if (!sc || !rp || !film_xyzw) return fail(PT_ERR_INVALID_ARG, "null argument");
     RenderConst rc; uint32_t S = 0;
     if (int gst = render_geometry(sc, rp, rc, &S)) return gst;
-    g_test_max_iterations = 0;
-    if (const char *e = getenv("PT_TEST_MAX_ITERATIONS")) { const int v = atoi(e); if (v > 0) g_test_max_iterations = v; }
+    int max_iterations = 1 << 20;   // wavefront iterations per pass. TEST HOOK (env PT_TEST_MAX_ITERATIONS, read at every call): a smaller cap, so that the PT_ERR_PROBE_CHAIN return of a pass that does not end can be tested
+    if (const char *e = getenv("PT_TEST_MAX_ITERATIONS")) { const int v = atoi(e); if (v > 0) max_iterations = v; }
     const size_t film_px = (size_t)rc.film_w * rc.film_h;
     sc->profile = rp->profile != 0;
     sc->drop_timings();
@@ -712,7 +714,7 @@ int pt_render(pt_scene *sc, const PtRenderParams *rp, float *film_xyzw, int film
         HIP_TRY(hipMemsetAsync(sc->qc, 0, sizeof(QCounters), sc->stream));
         for (uint32_t s0 = 0; s0 < rp->spp; s0 += S) {
             rc.s_begin = s0; rc.s_count = std::min(S, rp->spp - s0);
-            if ((st = run_pass(sc, rc, sc->grid[eff], rp->profile >= 2))) return st;
+            if ((st = run_pass(sc, rc, sc->grid[eff], rp->profile >= 2, max_iterations))) return st;
         }
         if (sc->grid[eff].cell_ptr) {   // a vertex that looked up a voxel nobody had computed: cannot happen (k_light_touch names every voxel first)
             uint32_t missing = 0;
@@ -728,8 +730,7 @@ int pt_render(pt_scene *sc, const PtRenderParams *rp, float *film_xyzw, int film
             dst = tmp;
         }
         sc->begin("film_finish", film_px);
-        sc->set_kernel("k_film_finish");
-        hipLaunchKernelGGL(k_film_finish, dim3((unsigned)((film_px + 255) / 256)), dim3(256), 0, sc->stream, sc->film_rgbw, dst, (uint32_t)film_px);
+        launch(sc, "k_film_finish", k_film_finish, dim3((unsigned)((film_px + 255) / 256)), dim3(256), sc->film_rgbw, dst, film_px);
         sc->end();
         HIP_TRY(hipStreamSynchronize(sc->stream));
         if (!film_is_device) {

@@ -8,7 +8,7 @@
 //   cameras/perspective.rs:40-86,298-356, core/film.rs:55-112,364-398, filters/*.rs, lights/*.rs create_* functions,
 //   materials/*.rs create_* functions, shapes/{triangle.rs:700-760, sphere.rs:424-431, plymesh.rs}.
 // Out of scope here (an error names the directive): other cameras / samplers / integrators than perspective / sobol, halton / path, volpath, ambientocclusion,
-// participating media, spectral (non-RGB) parameters, image formats other than PFM, per-shape material parameter
+// spectral (non-RGB) parameters, image formats other than those of fe_imageio.h (PFM, Radiance HDR, PNG, TGA, EXR), per-shape material parameter
 // overrides, animated transforms (ActiveTransform / TransformTimes are accepted and ignored for static scenes).
 #include "../../include/mi355pt.h"
 #include "../../include/mi355ao.h"
@@ -190,7 +190,6 @@ private:
             std::stringstream ss; ss << f.rdbuf(); std::string text = ss.str();
             Lexer sub(text); run(sub);
         }
-        else if (w == "MakeNamedMedium" || w == "MediumInterface") fail(d, w + ": participating media are out of scope (SURVEY 8f-4)");
         else fail(d, "unknown directive " + w);
         (void)in_world;
     }
