@@ -37,6 +37,10 @@ typedef struct PtAOParams {
  * Errors: PT_ERR_INVALID_ARG for a NULL argument, nsamples == 0, or more sample numbers per pixel (spp * nsamples) than the
  * sampler's tables serve; otherwise pt_render's statuses. Text: pt_last_error(). */
 int pt_ao_render(pt_scene *scene, const PtRenderParams *params, const PtAOParams *ao, float *film_xyzw, int film_is_device);
+/* pt_render_samples for the AO integrator: samples [first_sample, first_sample + n_samples) of every pixel, ADDED to film_xyzw. params->spp stays the job's sample
+ * count: element k of sample s is sample number s * nsamples + k of the job, and the table-size check is the job's. n_samples == 0 or first_sample + n_samples > spp
+ * (in 64 bits): PT_ERR_INVALID_ARG before the device is touched. pt_ao_render is the call (0, spp). */
+int pt_ao_render_samples(pt_scene *scene, const PtRenderParams *params, const PtAOParams *ao, uint32_t first_sample, uint32_t n_samples, float *film_xyzw, int film_is_device);
 /* Samples per pixel per pass pt_ao_render would use. The workspace grows with paths x nsamples: the AO rays of a pass are
  * traced in chunks of at most 64 per path, accumulated in order. */
 int pt_ao_pass_size(pt_scene *scene, const PtRenderParams *params, const PtAOParams *ao, uint32_t *spp_per_pass);

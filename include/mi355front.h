@@ -34,6 +34,26 @@ int ptf_write_image(const char *path, int width, int height, const float *rgb);
 /* read_image (core/imageio.rs:18-40): pfm, hdr, png, tga, exr (scan-line / tiled / multi-part, NO/RLE/ZIPS/ZIP). Call with rgb == NULL to get the
  * size, then with a buffer of width*height*3 floats (top row first). */
 int ptf_read_image(const char *path, int *width, int *height, float *rgb, size_t capacity_floats);
+/* Checkpoints of a render made in sample ranges (pt_render_samples; `mi355pbrt --checkpoint FILE`): the header below, then width * height * 4 floats, the raw XYZW
+ * film sums of sample numbers [first_sample, first_sample + samples_done) of a job of `spp` samples per pixel. Little endian, as the host writes it. */
+#define PTF_CHECKPOINT_MAGIC 0x4b433550u   /* "P5CK" */
+typedef struct PtfCheckpointHeader {
+    uint32_t magic, version;          /* PTF_CHECKPOINT_MAGIC, 1 */
+    uint32_t width, height;           /* the cropped film */
+    uint32_t spp;                     /* the job's samples per pixel */
+    uint32_t first_sample;            /* where the render began */
+    uint32_t samples_done;            /* samples per pixel in the film sums */
+    uint32_t reserved;
+    uint64_t params_hash;             /* ptf_params_hash of the job */
+} PtfCheckpointHeader;
+/* FNV-1a over the render parameters that decide the film: every byte of *params but spp_per_pass and profile (they change the schedule, not the result), and *ao when
+ * given. */
+uint64_t ptf_params_hash(const PtRenderParams *params, const PtAOParams *ao_or_null);
+/* Writes header + film to `path` (through path + ".tmp" and a rename, so that a crash leaves the previous checkpoint). */
+int ptf_checkpoint_write(const char *path, const PtfCheckpointHeader *header, const float *film_xyzw);
+/* Reads the checkpoint at `path` for the job `expect` describes (samples_done is not compared). No such file: PT_OK, *samples_done = 0, film untouched. A file whose
+ * magic, version, film size, spp, first_sample or params_hash differ, or that is truncated: PT_ERR_INVALID_ARG, ptf_last_error() names the field, film untouched. */
+int ptf_checkpoint_read(const char *path, const PtfCheckpointHeader *expect, uint32_t *samples_done, float *film_xyzw);
 #ifdef __cplusplus
 }
 #endif

@@ -469,6 +469,15 @@ int pt_scene_bvh_read(const pt_scene *scene, PtBVHNode *nodes, uint32_t *ordered
  * caller zeroes it), so shards from several ranks can be summed. If film_is_device != 0 the
  * pointer is a HIP device pointer on the selected device. */
 int pt_render(pt_scene *scene, const PtRenderParams *params, float *film_xyzw, int film_is_device);
+/* A range of the job's sample numbers: renders samples [first_sample, first_sample + n_samples) of every pixel of this rank's tiles and ADDS them to film_xyzw.
+ * params->spp stays the JOB's sample count (it scales the ray differentials, integrator.rs:340, so a range of a textured scene filters its textures as the whole
+ * job does). Sample k of a pixel is a function of the pixel and k alone for both samplers, so disjoint ranges whose union is [0, spp) add up to pt_render's film --
+ * the same contributions, added in another order -- and their counters add up to pt_render's. pt_render IS the call (0, spp). This is what resume / checkpoint
+ * (keep the film sums and the number of samples done), progressive preview and two-half-buffer error estimates (pt_film_halves_error) are built from.
+ * n_samples == 0 or first_sample + n_samples > spp (the sum taken in 64 bits): PT_ERR_INVALID_ARG before the device is touched, the film unmodified.
+ * Passes: params->spp_per_pass samples each (the last one the remainder), or the library's choice of equal passes over the range; never more than n_samples.
+ * pt_get_counters / pt_get_kernel_stats describe the last call, i.e. the range. First-touch light voxels (PT_LS_SPATIAL_LAZY) persist from call to call. */
+int pt_render_samples(pt_scene *scene, const PtRenderParams *params, uint32_t first_sample, uint32_t n_samples, float *film_xyzw, int film_is_device);
 /* The samples per pixel per wavefront pass pt_render would use for these parameters on the device as it is now (params->spp_per_pass, or the library's choice from
  * the free memory when that is 0; passes are of equal size). No reference counterpart: the reference renders a tile at a time. */
 int pt_pass_size(pt_scene *scene, const PtRenderParams *params, uint32_t *spp_per_pass);
@@ -476,6 +485,19 @@ int pt_pass_size(pt_scene *scene, const PtRenderParams *params, uint32_t *spp_pe
 /* Film::write_image normalisation (film.rs:217-258): rgb = max(0, xyz_to_rgb(xyz)/w) * scale.
  * Pure host arithmetic on a host buffer. */
 int pt_film_resolve(const float *film_xyzw, uint32_t n_pixels, float scale, float *rgb_out);
+
+/* pt_film_resolve on the device: film_xyzw_dev (n_pixels x XYZW on the scene's device) -> rgb_dev (3 floats per pixel, bit-identical to pt_film_resolve's) and / or
+ * srgb8_dev (3 bytes per pixel: the reference's 8-bit write path, core/imageio.rs:365-366 with gamma_correct, core/pbrt.rs:210-216:
+ * clamp(255 * gamma_correct(v) + 0.5, 0, 255) as u8, applied to that rgb). Either output may be NULL, not both (PT_ERR_INVALID_ARG). Blocking. The launch is added
+ * to the kernel statistics of the scene's last render as "film_resolve". */
+int pt_film_resolve_device(pt_scene *scene, const float *film_xyzw_dev, uint32_t n_pixels, float scale, float *rgb_dev, uint8_t *srgb8_dev);
+/* The two-half-buffer convergence estimate. The host renders alternating sample ranges into two device films A and B (A + B is the film). Per pixel, with rA / rB the
+ * resolved rgb of A / B at scale 1: e = (|rA.r - rB.r| + |rA.g - rB.g| + |rA.b - rB.b|) / sqrt(1e-4 + m), m = r + g + b of (rA + rB) / 2; e = 0 where either
+ * film's weight is 0. tile_error_dev (device, ceil(width / 16) * ceil(height / 16) floats, row-major over the film's 16x16 tile grid, or NULL) receives the mean of e
+ * over each tile's pixels (edge tiles ragged); *mean_error_host the mean of e over all pixels, *max_tile_error_host the largest tile error (either may be NULL).
+ * Deterministic: fixed summation order, no float atomics. Blocking; launch kinds "film_halves_error" and "film_error_reduce". */
+int pt_film_halves_error(pt_scene *scene, const float *film_a_dev, const float *film_b_dev, uint32_t width, uint32_t height,
+                         float *tile_error_dev, float *mean_error_host, float *max_tile_error_host);
 
 /* One process, several GPUs -- the shape of the reference itself: ONE process fans the 16x16 tiles out over its workers
  * (core/integrator.rs:294-296, rayon) and merges them into one Film (integrator.rs:392-396). pt_multi_scene_create replicates the
@@ -491,6 +513,8 @@ int pt_film_resolve(const float *film_xyzw, uint32_t n_pixels, float scale, floa
 int pt_multi_scene_create(const PtSceneDesc *desc, const int *device_ordinals, uint32_t n_devices, pt_multi_scene **out_scene);
 void pt_multi_scene_destroy(pt_multi_scene *scene);
 int pt_multi_render(pt_multi_scene *scene, const PtRenderParams *params, float *film_xyzw, int film_is_device);
+/* pt_render_samples over the replicas: every replica renders sample numbers [first_sample, first_sample + n_samples) of its tiles. pt_multi_render is (0, spp). */
+int pt_multi_render_samples(pt_multi_scene *scene, const PtRenderParams *params, uint32_t first_sample, uint32_t n_samples, float *film_xyzw, int film_is_device);
 int pt_multi_get_counters(const pt_multi_scene *scene, PtCounters *out);
 int pt_multi_get_kernel_stats(const pt_multi_scene *scene, uint32_t replica, PtKernelStat *out, uint32_t max_entries, uint32_t *n_out);
 /* Wall-clock times of the last pt_multi_render: per replica the duration of its pt_render (its device's busy time) and of its peer

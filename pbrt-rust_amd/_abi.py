@@ -158,13 +158,17 @@ ENTRY_POINTS = {
     "pt_scene_bvh_info": (C.c_int, [VP, u32p, u32p]),
     "pt_scene_bvh_read": (C.c_int, [VP, C.POINTER(PtBVHNode), u32p]),
     "pt_render": (C.c_int, [VP, C.POINTER(PtRenderParams), VP, C.c_int]),
+    "pt_render_samples": (C.c_int, [VP, C.POINTER(PtRenderParams), u32, u32, VP, C.c_int]),
     "pt_pass_size": (C.c_int, [VP, C.POINTER(PtRenderParams), u32p]),
     "pt_film_resolve": (C.c_int, [fp, u32, f32, fp]),
+    "pt_film_resolve_device": (C.c_int, [VP, VP, u32, f32, VP, VP]),
+    "pt_film_halves_error": (C.c_int, [VP, VP, VP, u32, u32, VP, fp, fp]),
     "pt_device_count": (C.c_int, [C.POINTER(C.c_int)]),
     "pt_set_trace_exact": (C.c_int, [C.c_int]),
     "pt_multi_scene_create": (C.c_int, [C.POINTER(PtSceneDesc), C.POINTER(C.c_int), u32, C.POINTER(VP)]),
     "pt_multi_scene_destroy": (None, [VP]),
     "pt_multi_render": (C.c_int, [VP, C.POINTER(PtRenderParams), VP, C.c_int]),
+    "pt_multi_render_samples": (C.c_int, [VP, C.POINTER(PtRenderParams), u32, u32, VP, C.c_int]),
     "pt_multi_get_counters": (C.c_int, [VP, C.POINTER(PtCounters)]),
     "pt_multi_get_kernel_stats": (C.c_int, [VP, u32, C.POINTER(PtKernelStat), u32, u32p]),
     "pt_multi_get_timing": (C.c_int, [VP, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), u32]),

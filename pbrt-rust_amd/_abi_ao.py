@@ -13,5 +13,6 @@ class PtAOParams(C.Structure):
 # Every symbol include/mi355ao.h declares, with its signature (restype, argtypes).
 ENTRY_POINTS = {
     "pt_ao_render": (C.c_int, [VP, C.POINTER(PtRenderParams), C.POINTER(PtAOParams), VP, C.c_int]),
+    "pt_ao_render_samples": (C.c_int, [VP, C.POINTER(PtRenderParams), C.POINTER(PtAOParams), u32, u32, VP, C.c_int]),
     "pt_ao_pass_size": (C.c_int, [VP, C.POINTER(PtRenderParams), C.POINTER(PtAOParams), u32p]),
 }

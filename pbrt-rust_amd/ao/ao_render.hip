@@ -1,4 +1,4 @@
-// ao_render.hip -- pt_ao_render / pt_ao_pass_size (include/mi355ao.h): the ambient-occlusion integrator (integrators/ao.rs) in the
+// ao_render.hip -- pt_ao_render / pt_ao_render_samples / pt_ao_pass_size (include/mi355ao.h): the ambient-occlusion integrator (integrators/ao.rs) in the
 // render loop of SamplerIntegrator::render (integrator.rs:263-403). Per pass of s_count samples of every pixel slot:
 //   k_generate                     camera rays (libmi355pt; dimensions 0-4 of the sample)
 //   k_trace<closest>               their hits ("extend_camera")
@@ -26,7 +26,9 @@ constexpr size_t kAOPathBytes = (size_t)kPathBytes + 4 * (2 + 2 * kNumClasses + 
 struct Geometry { RenderConst rc; uint32_t S; uint32_t K; };
 
 // The checks of pt_render's render_geometry (render_loop.hip) and the AO parameters; the pass size.
-int ao_geometry(pt_scene *sc, const PtRenderParams *rp, const PtAOParams *ao, Geometry &g) {
+// `n_samples`: how many of the job's rp->spp samples per pixel the call renders (pt_ao_render_samples): it caps and divides the pass size only -- the array numbering
+// s * nsamples + k and its table-size check are the job's.
+int ao_geometry(pt_scene *sc, const PtRenderParams *rp, const PtAOParams *ao, uint32_t n_samples, Geometry &g) {
     if (!sc || !rp || !ao) return fail(PT_ERR_INVALID_ARG, "null argument");
     if (ao->nsamples == 0) return fail(PT_ERR_INVALID_ARG, "ambientocclusion: nsamples must be > 0");
     if (rp->spp == 0) return fail(PT_ERR_INVALID_ARG, "spp must be > 0");
@@ -63,11 +65,11 @@ int ao_geometry(pt_scene *sc, const PtRenderParams *rp, const PtAOParams *ao, Ge
             // (the scene's present workspace is freed before a larger one is allocated)
             const size_t afford = (size_t)((double)(free_b + sc->capacity * (size_t)kPathBytes) * kAOMemFraction) / per_path;
             const size_t paths = std::min(afford, kAOMaxRays / g.K);
-            S = (uint32_t)std::min<size_t>(rp->spp, std::max<size_t>(1, paths / rc.n_pix_slots));
-            const uint32_t n_pass = (rp->spp + S - 1) / S;
-            S = (rp->spp + n_pass - 1) / n_pass;   // passes of equal size
+            S = (uint32_t)std::min<size_t>(n_samples, std::max<size_t>(1, paths / rc.n_pix_slots));
+            const uint32_t n_pass = (n_samples + S - 1) / S;
+            S = (n_samples + n_pass - 1) / n_pass;   // passes of equal size
         }
-        S = std::min(S, rp->spp);
+        S = std::min(S, n_samples);
         if ((size_t)rc.n_pix_slots * S > ((size_t)1 << 31)) return fail(PT_ERR_INVALID_ARG, "pass too large: pixel slots x samples per pass > 2^31 paths (lower spp_per_pass)");
         if ((size_t)rc.n_pix_slots * S * g.K > kAOMaxRays) return fail(PT_ERR_INVALID_ARG, "pass too large: paths x min(nsamples, 64) AO rays per launch > 2^31 (lower spp_per_pass)");
     }
@@ -163,15 +165,24 @@ extern "C" {
 __attribute__((visibility("default"))) int pt_ao_pass_size(pt_scene *sc, const PtRenderParams *rp, const PtAOParams *ao, uint32_t *spp_per_pass) {
     if (!spp_per_pass) return fail(PT_ERR_INVALID_ARG, "null argument");
     Geometry g;
-    if (int st = ao_geometry(sc, rp, ao, g)) return st;
+    if (int st = ao_geometry(sc, rp, ao, rp ? rp->spp : 0, g)) return st;
     *spp_per_pass = g.S ? g.S : rp->spp;   // (a rank that owns no tile renders nothing: any size)
     return PT_OK;
 }
 
-__attribute__((visibility("default"))) int pt_ao_render(pt_scene *sc, const PtRenderParams *rp, const PtAOParams *ao, float *film_xyzw, int film_is_device) {
-    if (!film_xyzw) return fail(PT_ERR_INVALID_ARG, "null argument");
+__attribute__((visibility("default"))) int pt_ao_render(pt_scene *sc, const PtRenderParams *rp, const PtAOParams *ao, float *film_xyzw, int film_is_device) {   // the whole job: [0, spp)
+    if (!sc || !rp || !ao || !film_xyzw) return fail(PT_ERR_INVALID_ARG, "null argument");
+    if (ao->nsamples == 0) return fail(PT_ERR_INVALID_ARG, "ambientocclusion: nsamples must be > 0");
+    if (rp->spp == 0) return fail(PT_ERR_INVALID_ARG, "spp must be > 0");
+    return pt_ao_render_samples(sc, rp, ao, 0, rp->spp, film_xyzw, film_is_device);
+}
+
+// Sample numbers [first, first + n) of every pixel: element k of sample s stays sample number s * nsamples + k of the JOB (k_ao_rays: rc.s_begin + sl)
+__attribute__((visibility("default"))) int pt_ao_render_samples(pt_scene *sc, const PtRenderParams *rp, const PtAOParams *ao, uint32_t first, uint32_t n_samples, float *film_xyzw, int film_is_device) {
+    if (!sc || !rp || !ao || !film_xyzw) return fail(PT_ERR_INVALID_ARG, "null argument");
+    if (int rst = check_sample_range(rp, first, n_samples)) return rst;   // (before the device is touched)
     Geometry g;
-    if (int gst = ao_geometry(sc, rp, ao, g)) return gst;
+    if (int gst = ao_geometry(sc, rp, ao, n_samples, g)) return gst;
     RenderConst &rc = g.rc;
     const size_t film_px = (size_t)rc.film_w * rc.film_h;
     sc->profile = rp->profile != 0;
@@ -188,8 +199,8 @@ __attribute__((visibility("default"))) int pt_ao_render(pt_scene *sc, const PtRe
     HIP_TRY(hipMemsetAsync(sc->film_rgbw, 0, film_px * 16, sc->stream));
     HIP_TRY(hipMemsetAsync(sc->dc, 0, sizeof(DevCounters), sc->stream));
     HIP_TRY(hipMemsetAsync(sc->qc, 0, sizeof(QCounters), sc->stream));
-    for (uint32_t s0 = 0; s0 < rp->spp; s0 += g.S) {
-        rc.s_begin = s0; rc.s_count = std::min(g.S, rp->spp - s0);
+    for (uint32_t s0 = first, end = first + n_samples; s0 < end; s0 += g.S) {
+        rc.s_begin = s0; rc.s_count = std::min(g.S, end - s0);
         if ((st = ao_pass(sc, rc, ao, g.K, b))) return st;
     }
     float *dst = film_xyzw, *tmp = nullptr; DevTmp film_tmp;

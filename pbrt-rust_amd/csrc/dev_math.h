@@ -292,6 +292,14 @@ PT_HD void xyz_to_rgb(const float xyz[3], float rgb[3]) {  // spectrum.rs:484-49
     rgb[1] = -0.969256f * xyz[0] + 1.875991f * xyz[1] + 0.041556f * xyz[2];
     rgb[2] = 0.055648f * xyz[0] - 0.204043f * xyz[1] + 1.057311f * xyz[2];
 }
+// Film::write_image's normalisation of one pixel (film.rs:217-258): rgb = max(0, xyz_to_rgb(xyz) / w) * scale. ONE body for the host's pt_film_resolve and the device's
+// k_film_resolve / k_film_halves_error, whose floats are equal bit for bit (both sides compile with -ffp-contract=off and IEEE division).
+PT_HD void film_resolve_pixel(const float xyzw[4], float scale, float rgb[3]) {
+    float c[3]; xyz_to_rgb(xyzw, c);
+    const float w = xyzw[3];
+    if (w != 0.0f) { const float inv = 1.0f / w; for (int k = 0; k < 3; ++k) c[k] = fmaxf(c[k] * inv, 0.0f); }
+    for (int k = 0; k < 3; ++k) rgb[k] = c[k] * scale;
+}
 PT_HD void rgb_to_xyz(const float rgb[3], float xyz[3]) {  // spectrum.rs:494-502
     xyz[0] = 0.412453f * rgb[0] + 0.357580f * rgb[1] + 0.180423f * rgb[2];
     xyz[1] = 0.212671f * rgb[0] + 0.715160f * rgb[1] + 0.072169f * rgb[2];

@@ -5,6 +5,7 @@
 //   render_loop.hip   the wavefront scheduler: kernel variants and the shade-class table, workspace, light grids, launch_trace, run_pass and its steps, pt_render, counters and kernel stats
 //   parity_api.hip    the entry points tests use to compare single stages with the oracle (rays, Sobol' / Halton samples, camera rays)
 //   multi_device.hip  pt_multi_*: one process driving several devices (one host thread + stream per replica, peer-copy film merge)
+//   film_tools.hip    pt_film_resolve_device / pt_film_halves_error: a film on the device resolved to rgb / 8-bit sRGB, and the convergence estimate of two half films
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -176,6 +177,8 @@ struct pt_multi_scene {
 };
 
 namespace pth {
+// every launch of the render stream: the symbol goes to the launch kind opened by the last begin()
+template <class... P, class... A> void launch(pt_scene *sc, const std::string &name, void (*fn)(P...), dim3 blocks, dim3 threads, const A &...args) { sc->set_kernel(name); hipLaunchKernelGGL(fn, blocks, threads, 0, sc->stream, static_cast<P>(args)...); }
 // scene_create.hip
 uint8_t material_class(const PtMaterial &m, bool specialise, bool untextured);
 void dist1d(const std::vector<float> &func, std::vector<float> &cdf, float &func_int);
@@ -188,4 +191,5 @@ void fill_render_const(const PtRenderParams *rp, RenderConst &rc);
 uint32_t choose_pass_size(const pt_scene *sc, uint32_t n_pix_slots, uint32_t spp, uint32_t share, bool volpath);
 int run_pass(pt_scene *sc, RenderConst &rc, const LightGrid &grid, bool rp_profile_exact, int max_iterations);
 void read_counters(pt_scene *sc);
+int check_sample_range(const PtRenderParams *rp, uint32_t first, uint32_t n);
 }  // namespace pth

@@ -80,8 +80,16 @@ void pt_multi_scene_destroy(pt_multi_scene *ms) {
     delete ms;
 }
 
-int pt_multi_render(pt_multi_scene *ms, const PtRenderParams *rp, float *film_xyzw, int film_is_device) {
+int pt_multi_render(pt_multi_scene *ms, const PtRenderParams *rp, float *film_xyzw, int film_is_device) {   // the whole job: sample numbers [0, spp)
     if (!ms || !rp || !film_xyzw || ms->sc.empty()) return fail(PT_ERR_INVALID_ARG, "null argument");
+    if (rp->spp == 0) return fail(PT_ERR_INVALID_ARG, "spp must be > 0");
+    return pt_multi_render_samples(ms, rp, 0, rp->spp, film_xyzw, film_is_device);
+}
+
+// Every replica renders sample numbers [first, first + n) of its tiles (pt_render_samples)
+int pt_multi_render_samples(pt_multi_scene *ms, const PtRenderParams *rp, uint32_t first, uint32_t n_samples, float *film_xyzw, int film_is_device) {
+    if (!ms || !rp || !film_xyzw || ms->sc.empty()) return fail(PT_ERR_INVALID_ARG, "null argument");
+    if (int rst = check_sample_range(rp, first, n_samples)) return rst;   // (before a device is touched)
     const int home = g_device;
     const uint32_t n = (uint32_t)ms->sc.size();
     const int64_t fw = (int64_t)rp->cropped_pixel_bounds[2] - rp->cropped_pixel_bounds[0], fh = (int64_t)rp->cropped_pixel_bounds[3] - rp->cropped_pixel_bounds[1];
@@ -109,7 +117,7 @@ int pt_multi_render(pt_multi_scene *ms, const PtRenderParams *rp, float *film_xy
             pt_multi_tile_shard(rp->tile_rank, rp->tile_world, i, n, &p.tile_rank, &p.tile_world);
             fill_render_const(&p, rc);
             const uint32_t ntiles = rc.ntx * rc.nty, slots = rc.tile_rank < ntiles ? (ntiles - rc.tile_rank + rc.tile_world - 1) / rc.tile_world * 256u : 0u;
-            if (slots) pass_size[i] = choose_pass_size(ms->sc[i], slots, rp->spp, share, rc.volpath != 0);
+            if (slots) pass_size[i] = choose_pass_size(ms->sc[i], slots, n_samples, share, rc.volpath != 0);
         }
     }
     std::vector<clk::time_point> t_rendered(n);
@@ -127,7 +135,7 @@ int pt_multi_render(pt_multi_scene *ms, const PtRenderParams *rp, float *film_xy
             PtRenderParams p = *rp;
             pt_multi_tile_shard(rp->tile_rank, rp->tile_world, i, n, &p.tile_rank, &p.tile_world);
             p.spp_per_pass = pass_size[i];
-            st = pt_render(ms->sc[i], &p, ms->film[i], 1);
+            st = pt_render_samples(ms->sc[i], &p, first, n_samples, ms->film[i], 1);
         }
         t_rendered[i] = clk::now();
         ms->render_ms[i] = ms_between(t0, t_rendered[i]); ms->copy_ms[i] = 0;

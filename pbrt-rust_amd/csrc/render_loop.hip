@@ -31,8 +31,7 @@ static std::string targ(bool b) { return b ? "true" : "false"; }
 static std::string targ(int v) { return std::to_string(v); }
 template <class... T> std::string symbol(const char *kernel, T... args) { std::string s = std::string(kernel) + "<", sep; ((s += sep + targ(args), sep = ", "), ...); return s + ">"; }
 
-// every launch of the render stream: the symbol goes to the launch kind opened by the last begin()
-template <class... P, class... A> void launch(pt_scene *sc, const std::string &name, void (*fn)(P...), dim3 blocks, dim3 threads, const A &...args) { sc->set_kernel(name); hipLaunchKernelGGL(fn, blocks, threads, 0, sc->stream, static_cast<P>(args)...); }
+// (launch(sc, name, fn, ...): host_common.h)
 template <class... P, class... A> void launch(pt_scene *sc, const Variant<P...> &v, dim3 blocks, dim3 threads, const A &...args) { launch(sc, v.name, v.fn, blocks, threads, args...); }
 static dim3 blocks_for(uint32_t n_upper, uint32_t per_cu) { return dim3(std::min<uint32_t>((n_upper + 255) / 256, (uint32_t)g_num_cus * per_cu)); }   // persistent blocks of 256 threads
 static bool general_geometry(const pt_scene *sc) { return sc->ds.n_spheres > 0 || sc->ds.n_instances > 0; }   // the SPH forms: spheres or instances besides world-space triangles
@@ -641,14 +640,22 @@ void read_counters(pt_scene *sc) {
 #endif
 }
 
+// The range [first, first + n) of a job of rp->spp samples per pixel (pt_render_samples, pt_ao_render_samples, pt_multi_render_samples): host arithmetic, the sum in 64 bits
+int check_sample_range(const PtRenderParams *rp, uint32_t first, uint32_t n) {
+    if (n == 0) return fail(PT_ERR_INVALID_ARG, "n_samples must be > 0");
+    if ((uint64_t)first + n > rp->spp) return fail(PT_ERR_INVALID_ARG, "sample range [" + std::to_string(first) + ", " + std::to_string((uint64_t)first + n) + ") exceeds the job's spp = " + std::to_string(rp->spp));
+    return PT_OK;
+}
+
 }  // namespace pth
 
 extern "C" {
 
 // What pt_render checks before it touches the device and the pass size it then uses -- ONE function for pt_render and pt_pass_size, so that the size pt_pass_size
 // reports is the size of a render that would be accepted (the two had drifted apart). Fills rc (incl. n_tile_slots / n_pix_slots); *S = samples per pixel
-// per wavefront pass (0 when this rank owns no tile).
-static int render_geometry(pt_scene *sc, const PtRenderParams *rp, RenderConst &rc, uint32_t *S_out) {
+// per wavefront pass (0 when this rank owns no tile). `n_samples`: how many of the job's rp->spp sample numbers the call renders (pt_render_samples; rp->spp for pt_render and
+// pt_pass_size) -- the pass size is capped at it and the library's choice makes equal passes over it, while rc keeps the JOB's spp (rc.inv_sqrt_spp, the differential scale).
+static int render_geometry(pt_scene *sc, const PtRenderParams *rp, uint32_t n_samples, RenderConst &rc, uint32_t *S_out) {
     if (rp->spp == 0) return fail(PT_ERR_INVALID_ARG, "spp must be > 0");
     if (!(rp->filter_radius[0] > 0.0f) || !(rp->filter_radius[1] > 0.0f)) return fail(PT_ERR_INVALID_ARG, "filter radius must be > 0");
     if (rp->tile_world > 1 && rp->tile_rank >= rp->tile_world) return fail(PT_ERR_INVALID_ARG, "tile_rank >= tile_world");
@@ -667,8 +674,8 @@ static int render_geometry(pt_scene *sc, const PtRenderParams *rp, RenderConst &
     uint32_t S = 0;
     if (rc.n_pix_slots > 0) {
         S = rp->spp_per_pass;
-        if (S == 0) S = choose_pass_size(sc, rc.n_pix_slots, rp->spp, 1, rc.volpath != 0);
-        S = std::min(S, rp->spp);
+        if (S == 0) S = choose_pass_size(sc, rc.n_pix_slots, n_samples, 1, rc.volpath != 0);
+        S = std::min(S, n_samples);
         if ((size_t)rc.n_pix_slots * S > ((size_t)1 << 31)) return fail(PT_ERR_INVALID_ARG, "pass too large: pixel slots x samples per pass > 2^31 paths (lower spp_per_pass)");
     }
     *S_out = S;
@@ -678,15 +685,24 @@ static int render_geometry(pt_scene *sc, const PtRenderParams *rp, RenderConst &
 int pt_pass_size(pt_scene *sc, const PtRenderParams *rp, uint32_t *spp_per_pass) {
     if (!sc || !rp || !spp_per_pass) return fail(PT_ERR_INVALID_ARG, "null argument");
     RenderConst rc; uint32_t S = 0;
-    if (int st = render_geometry(sc, rp, rc, &S)) return st;
+    if (int st = render_geometry(sc, rp, rp->spp, rc, &S)) return st;
     *spp_per_pass = S ? S : rp->spp;   // (a rank that owns no tile renders nothing: any size)
     return PT_OK;
 }
 
-int pt_render(pt_scene *sc, const PtRenderParams *rp, float *film_xyzw, int film_is_device) {
+int pt_render(pt_scene *sc, const PtRenderParams *rp, float *film_xyzw, int film_is_device) {   // the whole job: sample numbers [0, spp)
     if (!sc || !rp || !film_xyzw) return fail(PT_ERR_INVALID_ARG, "null argument");
+    if (rp->spp == 0) return fail(PT_ERR_INVALID_ARG, "spp must be > 0");
+    return pt_render_samples(sc, rp, 0, rp->spp, film_xyzw, film_is_device);
+}
+
+// Sample numbers [first, first + n) of the job `rp` describes. Sample k of a pixel is a function of the pixel and k alone (k_generate: rc.s_begin + sl), the film is added
+// to, and everything that depends on the job's sample count -- the differential scale -- reads rp->spp: the range only sets the pass loop's bounds.
+int pt_render_samples(pt_scene *sc, const PtRenderParams *rp, uint32_t first, uint32_t n_samples, float *film_xyzw, int film_is_device) {
+    if (!sc || !rp || !film_xyzw) return fail(PT_ERR_INVALID_ARG, "null argument");
+    if (int rst = check_sample_range(rp, first, n_samples)) return rst;   // (before the device is touched)
     RenderConst rc; uint32_t S = 0;
-    if (int gst = render_geometry(sc, rp, rc, &S)) return gst;
+    if (int gst = render_geometry(sc, rp, n_samples, rc, &S)) return gst;
     int max_iterations = 1 << 20;   // wavefront iterations per pass. TEST HOOK (env PT_TEST_MAX_ITERATIONS, read at every call): a smaller cap, so that the PT_ERR_PROBE_CHAIN return of a pass that does not end can be tested
     if (const char *e = getenv("PT_TEST_MAX_ITERATIONS")) { const int v = atoi(e); if (v > 0) max_iterations = v; }
     const size_t film_px = (size_t)rc.film_w * rc.film_h;
@@ -712,8 +728,8 @@ int pt_render(pt_scene *sc, const PtRenderParams *rp, float *film_xyzw, int film
         HIP_TRY(hipMemsetAsync(sc->film_rgbw, 0, film_px * 16, sc->stream));
         HIP_TRY(hipMemsetAsync(sc->dc, 0, sizeof(DevCounters), sc->stream));
         HIP_TRY(hipMemsetAsync(sc->qc, 0, sizeof(QCounters), sc->stream));
-        for (uint32_t s0 = 0; s0 < rp->spp; s0 += S) {
-            rc.s_begin = s0; rc.s_count = std::min(S, rp->spp - s0);
+        for (uint32_t s0 = first, end = first + n_samples; s0 < end; s0 += S) {
+            rc.s_begin = s0; rc.s_count = std::min(S, end - s0);
             if ((st = run_pass(sc, rc, sc->grid[eff], rp->profile >= 2, max_iterations))) return st;
         }
         if (sc->grid[eff].cell_ptr) {   // a vertex that looked up a voxel nobody had computed: cannot happen (k_light_touch names every voxel first)
@@ -746,12 +762,7 @@ int pt_render(pt_scene *sc, const PtRenderParams *rp, float *film_xyzw, int film
 
 int pt_film_resolve(const float *xyzw, uint32_t n, float scale, float *rgb) {  // film.rs:217-258 (host arithmetic)
     if (!xyzw || !rgb) return fail(PT_ERR_INVALID_ARG, "null argument");
-    for (uint32_t i = 0; i < n; ++i) {
-        float c[3]; xyz_to_rgb(xyzw + 4 * (size_t)i, c);
-        float w = xyzw[4 * (size_t)i + 3];
-        if (w != 0.0f) { float inv = 1.0f / w; for (int k = 0; k < 3; ++k) c[k] = std::fmax(c[k] * inv, 0.0f); }
-        for (int k = 0; k < 3; ++k) rgb[3 * (size_t)i + k] = c[k] * scale;
-    }
+    for (uint32_t i = 0; i < n; ++i) film_resolve_pixel(xyzw + 4 * (size_t)i, scale, rgb + 3 * (size_t)i);
     return PT_OK;
 }
 

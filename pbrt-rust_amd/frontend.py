@@ -11,6 +11,15 @@ LIB_PATH = os.path.join(_HERE, "frontend", "libmi355front_san.so" if SAN else "l
 CLI_PATH = os.path.join(_HERE, "frontend", "mi355pbrt")
 
 
+PTF_CHECKPOINT_MAGIC = 0x4b433550
+
+
+class PtfCheckpointHeader(C.Structure):
+    """include/mi355front.h: the header of a range render's checkpoint file (then width * height * 4 floats of XYZW sums)."""
+    _fields_ = [("magic", A.u32), ("version", A.u32), ("width", A.u32), ("height", A.u32), ("spp", A.u32), ("first_sample", A.u32), ("samples_done", A.u32),
+                ("reserved", A.u32), ("params_hash", A.u64)]
+
+
 def build(verbose=False):
     r = subprocess.run(["make", "-C", os.path.join(_HERE, "frontend")] + (["SAN=1"] if SAN else []), capture_output=True, text=True)
     if verbose or r.returncode != 0:
@@ -40,6 +49,9 @@ def lib():
         L.ptf_write_pfm.argtypes = [C.c_char_p, C.c_int, C.c_int, A.fp]
         L.ptf_write_image.argtypes = [C.c_char_p, C.c_int, C.c_int, A.fp]
         L.ptf_read_image.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), A.fp, C.c_size_t]
+        L.ptf_params_hash.restype = C.c_uint64; L.ptf_params_hash.argtypes = [C.POINTER(A.PtRenderParams), C.POINTER(AO.PtAOParams)]
+        L.ptf_checkpoint_write.argtypes = [C.c_char_p, C.POINTER(PtfCheckpointHeader), A.fp]
+        L.ptf_checkpoint_read.argtypes = [C.c_char_p, C.POINTER(PtfCheckpointHeader), A.u32p, A.fp]
         _lib = L
     return _lib
 
@@ -101,3 +113,25 @@ def write_image(path, rgb):
     rgb = np.ascontiguousarray(rgb, dtype=np.float32)
     L = lib()
     if L.ptf_write_image(os.fsencode(path), rgb.shape[1], rgb.shape[0], rgb.ctypes.data_as(A.fp)) != 0: raise ValueError(L.ptf_last_error().decode(errors="replace"))
+
+
+def checkpoint_header(rp, ao=None, first_sample=0, samples_done=0):
+    """The header of the job (rp, ao) rendered from `first_sample` on."""
+    cb = rp.cropped_pixel_bounds
+    return PtfCheckpointHeader(PTF_CHECKPOINT_MAGIC, 1, cb[2] - cb[0], cb[3] - cb[1], rp.spp, first_sample, samples_done, 0,
+                               lib().ptf_params_hash(C.byref(rp), C.byref(ao) if ao is not None else None))
+
+
+def write_checkpoint(path, header, film):
+    import numpy as np
+    film = np.ascontiguousarray(film, dtype=np.float32)
+    assert film.size == header.width * header.height * 4
+    if lib().ptf_checkpoint_write(os.fsencode(path), C.byref(header), film.ctypes.data_as(A.fp)) != A.PT_OK: raise ValueError(lib().ptf_last_error().decode(errors="replace"))
+
+
+def read_checkpoint(path, expect):
+    """(samples done, film (h, w, 4)) of the checkpoint at `path` for the job `expect` describes; (0, zeros) when there is none; ValueError when it is of another job."""
+    import numpy as np
+    film = np.zeros((expect.height, expect.width, 4), np.float32); done = C.c_uint32()
+    if lib().ptf_checkpoint_read(os.fsencode(path), C.byref(expect), C.byref(done), film.ctypes.data_as(A.fp)) != A.PT_OK: raise ValueError(lib().ptf_last_error().decode(errors="replace"))
+    return done.value, film

@@ -12,6 +12,7 @@
 // overrides, animated transforms (ActiveTransform / TransformTimes are accepted and ignored for static scenes).
 #include "../../include/mi355pt.h"
 #include "../../include/mi355ao.h"
+#include "../../include/mi355front.h"
 #include "fe_bssrdf.h"
 #include "fe_image.h"
 #include "fe_imageio.h"
@@ -685,6 +686,47 @@ int ptf_read_image(const char *path, int *width, int *height, float *rgb, size_t
         if (height) *height = im.h;
         if (rgb) { if (capacity_floats < im.rgb.size()) { fe::g_error = "buffer too small"; return PT_ERR_INVALID_ARG; } std::memcpy(rgb, im.rgb.data(), im.rgb.size() * 4); }
     } catch (const std::exception &e) { fe::g_error = e.what(); return PT_ERR_INVALID_ARG; }
+    return PT_OK;
+}
+// ---- checkpoints of range renders (mi355front.h: PtfCheckpointHeader) ----
+uint64_t ptf_params_hash(const PtRenderParams *params, const PtAOParams *ao) {
+    uint64_t h = 1469598103934665603ull;
+    auto eat = [&](const void *p, size_t n) { for (size_t i = 0; i < n; ++i) { h ^= ((const unsigned char *)p)[i]; h *= 1099511628211ull; } };
+    if (params) { PtRenderParams p = *params; p.spp_per_pass = 0; p.profile = 0; eat(&p, sizeof p); }
+    if (ao) eat(ao, sizeof *ao);
+    return h;
+}
+int ptf_checkpoint_write(const char *path, const PtfCheckpointHeader *header, const float *film) {
+    if (!path || !header || !film) { fe::g_error = "null argument"; return PT_ERR_INVALID_ARG; }
+    const std::string tmp = std::string(path) + ".tmp";
+    FILE *f = std::fopen(tmp.c_str(), "wb");
+    if (!f) { fe::g_error = "cannot write \"" + tmp + "\""; return PT_ERR_INVALID_ARG; }
+    const size_t n = (size_t)header->width * header->height * 4;
+    const bool ok = std::fwrite(header, sizeof *header, 1, f) == 1 && std::fwrite(film, 4, n, f) == n;
+    if (std::fclose(f) != 0 || !ok || std::rename(tmp.c_str(), path) != 0) { std::remove(tmp.c_str()); fe::g_error = std::string("cannot write checkpoint \"") + path + "\""; return PT_ERR_INVALID_ARG; }
+    return PT_OK;
+}
+int ptf_checkpoint_read(const char *path, const PtfCheckpointHeader *expect, uint32_t *samples_done, float *film) {
+    if (!path || !expect || !samples_done || !film) { fe::g_error = "null argument"; return PT_ERR_INVALID_ARG; }
+    *samples_done = 0;
+    FILE *f = std::fopen(path, "rb");
+    if (!f) return PT_OK;   // nothing to resume
+    auto refuse = [&](const std::string &what) { std::fclose(f); fe::g_error = std::string("checkpoint \"") + path + "\" is not of this job: " + what; return (int)PT_ERR_INVALID_ARG; };
+    PtfCheckpointHeader h;
+    if (std::fread(&h, sizeof h, 1, f) != 1) return refuse("no header");
+    if (h.magic != PTF_CHECKPOINT_MAGIC) return refuse("not a checkpoint file");
+    if (h.version != expect->version) return refuse("version " + std::to_string(h.version));
+    if (h.width != expect->width || h.height != expect->height) return refuse("film size " + std::to_string(h.width) + "x" + std::to_string(h.height) + ", the job's is " + std::to_string(expect->width) + "x" + std::to_string(expect->height));
+    if (h.spp != expect->spp) return refuse("spp " + std::to_string(h.spp) + ", the job's is " + std::to_string(expect->spp));
+    if (h.first_sample != expect->first_sample) return refuse("first sample " + std::to_string(h.first_sample) + ", the job's is " + std::to_string(expect->first_sample));
+    if (h.params_hash != expect->params_hash) return refuse("the render parameters differ (hash)");
+    if ((uint64_t)h.first_sample + h.samples_done > h.spp) return refuse("samples done beyond spp");
+    const size_t n = (size_t)h.width * h.height * 4;
+    std::vector<float> buf(n);
+    if (std::fread(buf.data(), 4, n, f) != n) return refuse("film truncated");
+    std::fclose(f);
+    std::memcpy(film, buf.data(), n * 4);
+    *samples_done = h.samples_done;
     return PT_OK;
 }
 }

@@ -1,53 +1,115 @@
 // mi355pbrt -- command-line renderer: the drop-in for `pbrt-rust scene.pbrt` on this back end (main.rs + api.rs:1715-1748).
-//   mi355pbrt scene.pbrt [--outfile out.pfm] [--device N] [--spp N] [--quiet]
+//   mi355pbrt scene.pbrt [--outfile out.pfm] [--device N] [--spp N] [--quiet] [--samples A:B] [--checkpoint FILE] [--preview-every N]
 // Parses with libmi355front.so, renders with libmi355pt.so (HIP; Integrator "ambientocclusion": libmi355ao.so), writes the film in the format the Film's "filename"
 // extension names (exr -- the reference's default "pbrt.exr" -- png, tga, pfm: core/imageio.rs:42-60).
+// The film lives on the device and is rendered in groups of samples (pt_render_samples); one group -- the whole job -- unless asked otherwise:
+//   --samples A:B        sample numbers [A, B) of the job's spp only (0 <= A < B <= spp)
+//   --checkpoint FILE    after every group (--preview-every N samples, else one wavefront pass) the raw XYZW sums + a header go to FILE; a FILE of this job found at the
+//                        start is resumed from its `samples done`, one of another job is refused
+//   --preview-every N    every N samples the outfile is written from the film so far (pt_film_resolve_device)
 #include "../../include/mi355front.h"
+#include <hip/hip_runtime_api.h>
 #include <chrono>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
 
+static const char *kUsage = "usage: mi355pbrt scene.pbrt [--outfile out.pfm] [--device N] [--spp N] [--quiet] [--samples A:B] [--checkpoint FILE] [--preview-every N]\n";
+static int usage(const std::string &why = "") { if (!why.empty()) std::fprintf(stderr, "mi355pbrt: %s\n", why.c_str()); std::fputs(kUsage, stderr); return 2; }
+
+// "A:B" with decimal A < B, both fitting 32 bits
+static bool parse_range(const std::string &a, long long &lo, long long &hi) {
+    const size_t c = a.find(':');
+    if (c == std::string::npos || c == 0 || c + 1 >= a.size() || a.size() > 21) return false;
+    for (size_t i = 0; i < a.size(); ++i) if (i != c && (a[i] < '0' || a[i] > '9')) return false;
+    lo = std::atoll(a.substr(0, c).c_str()); hi = std::atoll(a.substr(c + 1).c_str());
+    return lo < hi && hi <= 0xffffffffll;
+}
+
 int main(int argc, char **argv) {
-    std::string scene, outfile; int device = 0, spp = 0; bool quiet = false;
+    std::string scene, outfile, samples, checkpoint; int device = 0, spp = 0; long long preview = 0; bool quiet = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         if (a == "--outfile" && i + 1 < argc) outfile = argv[++i];
         else if (a == "--device" && i + 1 < argc) device = std::atoi(argv[++i]);
         else if (a == "--spp" && i + 1 < argc) spp = std::atoi(argv[++i]);
+        else if (a == "--samples" && i + 1 < argc) samples = argv[++i];
+        else if (a == "--checkpoint" && i + 1 < argc) checkpoint = argv[++i];
+        else if (a == "--preview-every" && i + 1 < argc) { preview = std::atoll(argv[++i]); if (preview <= 0 || preview > 0xffffffffll) return usage("--preview-every takes a number of samples > 0"); }
         else if (a == "--quiet") quiet = true;
         else if (a[0] != '-') scene = a;
-        else { std::fprintf(stderr, "usage: mi355pbrt scene.pbrt [--outfile out.pfm] [--device N] [--spp N] [--quiet]\n"); return 2; }
+        else return usage();
     }
-    if (scene.empty()) { std::fprintf(stderr, "usage: mi355pbrt scene.pbrt [--outfile out.pfm] [--device N] [--spp N] [--quiet]\n"); return 2; }
+    if (scene.empty()) return usage();
+    long long lo = 0, hi = 0;
+    if (!samples.empty() && !parse_range(samples, lo, hi)) return usage("--samples takes A:B with 0 <= A < B, got \"" + samples + "\"");
     ptf_scene *fs = nullptr;
     if (ptf_parse_file(scene.c_str(), &fs) != PT_OK) { std::fprintf(stderr, "mi355pbrt: %s\n", ptf_last_error()); return 1; }
     PtRenderParams rp = *ptf_render_params(fs);
     if (spp > 0) rp.spp = (uint32_t)spp;
+    if (samples.empty()) hi = rp.spp;
+    else if (hi > (long long)rp.spp) return usage("--samples " + samples + " goes beyond the job's " + std::to_string(rp.spp) + " samples per pixel");
+    const uint32_t first = (uint32_t)lo, last = (uint32_t)hi;
     if (outfile.empty()) {
         outfile = ptf_output_filename(fs);
+    }
+    const bool is_ao = rp.integrator == PT_INTEGRATOR_AO;   // Integrator "ambientocclusion" (libmi355ao.so)
+    PtAOParams ao{}; if (is_ao) ptf_ao_params(fs, &ao);
+    const int w = rp.cropped_pixel_bounds[2] - rp.cropped_pixel_bounds[0], h = rp.cropped_pixel_bounds[3] - rp.cropped_pixel_bounds[1];
+    if (w <= 0 || h <= 0) { std::fprintf(stderr, "mi355pbrt: empty film\n"); return 1; }
+    const size_t npix = (size_t)w * h;
+    std::vector<float> film(npix * 4, 0.0f), rgb(npix * 3);
+    // a checkpoint of this job: continue after its samples (host work: a file of another job is refused before the device is touched)
+    PtfCheckpointHeader ck{PTF_CHECKPOINT_MAGIC, 1u, (uint32_t)w, (uint32_t)h, rp.spp, first, 0u, 0u, ptf_params_hash(&rp, is_ao ? &ao : nullptr)};
+    if (!checkpoint.empty()) {
+        if (ptf_checkpoint_read(checkpoint.c_str(), &ck, &ck.samples_done, film.data()) != PT_OK) { std::fprintf(stderr, "mi355pbrt: %s\n", ptf_last_error()); return 1; }
+        if (ck.samples_done > last - first) { std::fprintf(stderr, "mi355pbrt: checkpoint \"%s\" holds more samples than --samples asks for\n", checkpoint.c_str()); return 1; }
+        if (ck.samples_done && !quiet) std::printf("resuming %s at sample %u of [%u, %u)\n", checkpoint.c_str(), first + ck.samples_done, first, last);
     }
     if (pt_init(device) != PT_OK) { std::fprintf(stderr, "mi355pbrt: %s\n", pt_last_error()); return 1; }
     const auto t0 = std::chrono::steady_clock::now();
     pt_scene *sc = nullptr;
     if (pt_scene_create(ptf_scene_desc(fs), &sc) != PT_OK) { std::fprintf(stderr, "mi355pbrt: %s\n", pt_last_error()); return 1; }
     const auto t1 = std::chrono::steady_clock::now();
-    const int w = rp.cropped_pixel_bounds[2] - rp.cropped_pixel_bounds[0], h = rp.cropped_pixel_bounds[3] - rp.cropped_pixel_bounds[1];
-    std::vector<float> film((size_t)w * h * 4, 0.0f), rgb((size_t)w * h * 3);
-    int rst;
-    if (rp.integrator == PT_INTEGRATOR_AO) { PtAOParams ao; ptf_ao_params(fs, &ao); rst = pt_ao_render(sc, &rp, &ao, film.data(), 0); }   // Integrator "ambientocclusion" (libmi355ao.so)
-    else rst = pt_render(sc, &rp, film.data(), 0);
-    if (rst != PT_OK) { std::fprintf(stderr, "mi355pbrt: %s\n", pt_last_error()); return 1; }
+    float *d_film = nullptr, *d_rgb = nullptr;
+    if (hipMalloc((void **)&d_film, npix * 16) != hipSuccess || hipMalloc((void **)&d_rgb, npix * 12) != hipSuccess ||
+        hipMemcpy(d_film, film.data(), npix * 16, hipMemcpyHostToDevice) != hipSuccess) { std::fprintf(stderr, "mi355pbrt: device film: %s\n", hipGetErrorString(hipGetLastError())); return 1; }
+    // the film so far -> outfile, resolved on the device
+    auto write_out = [&]() {
+        if (pt_film_resolve_device(sc, d_film, (uint32_t)npix, rp.scale, d_rgb, nullptr) != PT_OK) { std::fprintf(stderr, "mi355pbrt: %s\n", pt_last_error()); return false; }
+        if (hipMemcpy(rgb.data(), d_rgb, npix * 12, hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "mi355pbrt: reading the image back failed\n"); return false; }
+        if (ptf_write_image(outfile.c_str(), w, h, rgb.data()) != PT_OK) { std::fprintf(stderr, "mi355pbrt: %s\n", ptf_last_error()); return false; }
+        return true;
+    };
+    uint32_t group = last - first;   // samples per pt_render_samples call
+    if (preview > 0) group = (uint32_t)std::min<long long>(preview, group);
+    else if (!checkpoint.empty()) {
+        const int pst = is_ao ? pt_ao_pass_size(sc, &rp, &ao, &group) : pt_pass_size(sc, &rp, &group);
+        if (pst != PT_OK) { std::fprintf(stderr, "mi355pbrt: %s\n", pt_last_error()); return 1; }
+    }
+    unsigned long long camera_rays = 0;
+    for (uint32_t s = first + ck.samples_done; s < last; ) {
+        const uint32_t n = std::min(group, last - s);
+        const int rst = is_ao ? pt_ao_render_samples(sc, &rp, &ao, s, n, d_film, 1) : pt_render_samples(sc, &rp, s, n, d_film, 1);
+        if (rst != PT_OK) { std::fprintf(stderr, "mi355pbrt: %s\n", pt_last_error()); return 1; }
+        PtCounters c; pt_get_counters(sc, &c); camera_rays += c.camera_rays;
+        s += n; ck.samples_done = s - first;
+        if (!checkpoint.empty()) {
+            if (hipMemcpy(film.data(), d_film, npix * 16, hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "mi355pbrt: reading the film back failed\n"); return 1; }
+            if (ptf_checkpoint_write(checkpoint.c_str(), &ck, film.data()) != PT_OK) { std::fprintf(stderr, "mi355pbrt: %s\n", ptf_last_error()); return 1; }
+        }
+        if (preview > 0 && s < last && !write_out()) return 1;
+    }
     const auto t2 = std::chrono::steady_clock::now();
-    pt_film_resolve(film.data(), (uint32_t)(w * h), rp.scale, rgb.data());
-    if (ptf_write_image(outfile.c_str(), w, h, rgb.data()) != PT_OK) { std::fprintf(stderr, "mi355pbrt: %s\n", ptf_last_error()); return 1; }
+    if (!write_out()) return 1;
     if (!quiet) {
-        PtCounters c; pt_get_counters(sc, &c);
         const double ts = std::chrono::duration<double>(t1 - t0).count(), tr = std::chrono::duration<double>(t2 - t1).count();
         std::printf("%s: %dx%d, %u spp, %llu camera rays, scene %.2f s, render %.3f s (%.1f Msamples/s) -> %s\n", scene.c_str(), w, h, rp.spp,
-                    (unsigned long long)c.camera_rays, ts, tr, (double)c.camera_rays / tr / 1e6, outfile.c_str());
+                    camera_rays, ts, tr, (double)camera_rays / tr / 1e6, outfile.c_str());
     }
+    (void)hipFree(d_film); (void)hipFree(d_rgb);
     pt_scene_destroy(sc); ptf_scene_destroy(fs);
     return 0;
 }

@@ -105,14 +105,18 @@ class Handle:
         self._call("scene_bvh_read", self.h, nodes, ordered.ctypes.data_as(A.u32p))
         return nodes, ordered
 
-    def render(self, rp, film=None, device_ptr=None, ao=None, last=None):
+    def render(self, rp, film=None, device_ptr=None, ao=None, last=None, samples=None):
         """Returns the un-normalised film (H, W, 4) = XYZ sums + weight sum, or None when it went to `device_ptr`. rp.integrator ==
         PT_INTEGRATOR_AO renders with <PREFIX>ao_render: `ao` (a PtAOParams), else the scene's own (scene_data.ao_params()).
-        `last`: the call's final argument, by default the product library's `film_on_device`."""
+        `last`: the call's final argument, by default the product library's `film_on_device`.
+        `samples` = (first, n): sample numbers [first, first + n) of the job of rp.spp samples per pixel (<PREFIX>render_samples), ADDED to `film`; unset: the whole job."""
         args, lib, name = [self.h, C.byref(rp)], self._lib, "render"
         if rp.integrator == AO.PT_INTEGRATOR_AO and self._ao is not None:
             ao = self.data.ao_params() if ao is None else ao
             args.append(C.byref(ao)); lib, name = self._ao, "ao_render"
+        if samples is not None:
+            first, n = samples
+            args += [first, n]; name += "_samples"
         if device_ptr is not None:
             self._call(name, *args, C.c_void_p(device_ptr), 1, lib=lib); return None
         if film is None:
@@ -171,6 +175,39 @@ class Scene(Handle):
         s = C.c_uint32()
         self._call("pass_size", self.h, C.byref(rp), C.byref(s))
         return int(s.value)
+
+    def resolve_device(self, film_ptr, n_pixels, scale=1.0, rgb_ptr=None, srgb8_ptr=None):
+        """pt_film_resolve_device: a film on the device -> rgb floats and / or 8-bit sRGB codes on the device (device pointers as integers)."""
+        self._call("film_resolve_device", self.h, C.c_void_p(film_ptr), n_pixels, scale, C.c_void_p(rgb_ptr), C.c_void_p(srgb8_ptr))
+
+    def halves_error(self, film_a_ptr, film_b_ptr, width, height, tile_error_ptr=None):
+        """pt_film_halves_error of two half films on the device: (mean error, largest tile error); the per-tile errors go to `tile_error_ptr` when given."""
+        mean, worst = C.c_float(), C.c_float()
+        self._call("film_halves_error", self.h, C.c_void_p(film_a_ptr), C.c_void_p(film_b_ptr), width, height, C.c_void_p(tile_error_ptr), C.byref(mean), C.byref(worst))
+        return mean.value, worst.value
+
+    def render_progressive(self, rp, step, on_step=None, target_error=None):
+        """The job `rp` in ranges of `step` samples, alternately into two torch films A and B on the device (A + B is the film). After each range:
+        pt_film_halves_error of A and B, then on_step(done, mean_error, max_tile_error); nothing but those two numbers is read back. Stops when the job is done or,
+        once both halves hold samples, when mean_error <= target_error. Returns (A + B as a numpy film (H, W, 4), samples rendered per pixel)."""
+        import torch
+        if step <= 0:
+            raise ValueError("step must be > 0")
+        cb = rp.cropped_pixel_bounds
+        w, h = cb[2] - cb[0], cb[3] - cb[1]
+        halves = [torch.zeros((h, w, 4), dtype=torch.float32, device="cuda") for _ in range(2)]
+        torch.cuda.synchronize()   # (the library renders on its own stream: the zeroed films must be there before it adds to them)
+        done = k = 0
+        while done < rp.spp:
+            n = min(step, rp.spp - done)
+            self.render(rp, device_ptr=halves[k % 2].data_ptr(), samples=(done, n))
+            done += n; k += 1
+            mean, worst = self.halves_error(halves[0].data_ptr(), halves[1].data_ptr(), w, h)
+            if on_step is not None:
+                on_step(done, mean, worst)
+            if target_error is not None and k >= 2 and k % 2 == 0 and mean <= target_error:
+                break
+        return (halves[0] + halves[1]).cpu().numpy(), done
 
     def ao_params(self):
         """The scene's PtAOParams (SceneBuilder.integ / the front end's "ambientocclusion" parameters)."""

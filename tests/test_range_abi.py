@@ -1,0 +1,98 @@
+"""No GPU: the range / film-tool entry points as a C compiler and ctypes see them, mi355pbrt's usage errors for --samples, and the checkpoint file's round trip."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+INC = os.path.join(ROOT, "include")
+
+# the prototypes as the feature defines them: C type of the function, and the ctypes signature the mirrors must carry
+PROTOTYPES = {
+    "pt_render_samples": ("int(pt_scene *, const PtRenderParams *, uint32_t, uint32_t, float *, int)", "pt"),
+    "pt_multi_render_samples": ("int(pt_multi_scene *, const PtRenderParams *, uint32_t, uint32_t, float *, int)", "pt"),
+    "pt_ao_render_samples": ("int(pt_scene *, const PtRenderParams *, const PtAOParams *, uint32_t, uint32_t, float *, int)", "ao"),
+    "pt_film_resolve_device": ("int(pt_scene *, const float *, uint32_t, float, float *, uint8_t *)", "pt"),
+    "pt_film_halves_error": ("int(pt_scene *, const float *, const float *, uint32_t, uint32_t, float *, float *, float *)", "pt"),
+}
+
+
+def _ctype_of(c_param, A, AO):
+    c_param = c_param.strip()
+    if c_param == "const PtRenderParams *": return C.POINTER(A.PtRenderParams)
+    if c_param == "const PtAOParams *": return C.POINTER(AO.PtAOParams)
+    if c_param.endswith("*"): return (C.c_void_p, A.fp)   # handles and buffers: an address (device pointers are integers on the Python side)
+    return {"uint32_t": C.c_uint32, "int": C.c_int, "float": C.c_float}[c_param]
+
+
+def test_range_entry_points_match_the_headers(pkg, tmp_path):
+    A, AO = pkg._abi, pkg._abi_ao
+    src = ['#include "mi355ao.h"']
+    for name, (ctype, _) in PROTOTYPES.items():
+        src.append(f'_Static_assert(__builtin_types_compatible_p(__typeof__({name}), {ctype}), "{name}");')
+    src.append("int main(void) { return 0; }")
+    cfile = tmp_path / "probe.c"; cfile.write_text("\n".join(src))
+    r = subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I", INC, "-c", str(cfile), "-o", str(tmp_path / "probe.o")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    libs = {"pt": C.CDLL(pkg.runtime.LIB_PATH), "ao": C.CDLL(pkg.runtime.AO_LIB_PATH)}
+    for name, (ctype, where) in PROTOTYPES.items():
+        res, args = (A.ENTRY_POINTS if where == "pt" else AO.ENTRY_POINTS)[name]
+        params = ctype[ctype.index("(") + 1:-1].split(",")
+        assert res is C.c_int and len(args) == len(params), name
+        for got, c_param in zip(args, params):
+            want = _ctype_of(c_param, A, AO)
+            assert got in want if isinstance(want, tuple) else got is want, (name, c_param, got)
+        getattr(libs[where], name)   # exported
+
+
+SCENE = ('LookAt 0 0 -1  0 0 0  0 1 0\nCamera "perspective" "float fov" 30\nFilm "image" "integer xresolution" 16 "integer yresolution" 16\n'
+         'Sampler "sobol" "integer pixelsamples" 4\nWorldBegin\n'
+         'Shape "trianglemesh" "integer indices" [0 1 2 0 2 3] "point P" [-100 -100 0 100 -100 0 100 100 0 -100 100 0]\nWorldEnd\n')
+
+
+@pytest.mark.parametrize("arg", ["3:2", "2:2", "1", ":3", "2:", "a:b", "-1:2", "0:5", "4:9", "0:99999999999"])
+def test_mi355pbrt_refuses_malformed_sample_ranges_before_any_gpu_call(pkg, tmp_path, arg):
+    scene = tmp_path / "s.pbrt"; scene.write_text(SCENE)
+    out = tmp_path / "o.pfm"
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="", ROCR_VISIBLE_DEVICES="")   # no device to touch: a usage error must come first
+    r = subprocess.run([pkg.frontend.CLI_PATH, str(scene), "--outfile", str(out), "--samples", arg], capture_output=True, text=True, timeout=60, env=env)
+    assert r.returncode == 2, (r.returncode, r.stderr)
+    assert "usage:" in r.stderr and "--samples" in r.stderr and not out.exists()
+
+
+def test_checkpoint_round_trip_and_refusal(pkg, tmp_path):
+    F = pkg.frontend
+    rp = F.FrontScene(text=SCENE).render_params()
+    hdr = F.checkpoint_header(rp, first_sample=1, samples_done=2)
+    assert (hdr.width, hdr.height, hdr.spp, hdr.magic, hdr.version) == (16, 16, 4, F.PTF_CHECKPOINT_MAGIC, 1)
+    film = np.random.default_rng(3).normal(size=(16, 16, 4)).astype(np.float32)
+    path = tmp_path / "job.ckpt"
+    assert F.read_checkpoint(path, hdr)[0] == 0   # no file: nothing done
+    F.write_checkpoint(path, hdr, film)
+    assert os.path.getsize(path) == C.sizeof(F.PtfCheckpointHeader) + film.nbytes and not os.path.exists(str(path) + ".tmp")
+    done, back = F.read_checkpoint(path, F.checkpoint_header(rp, first_sample=1))
+    assert done == 2 and np.array_equal(back.view(np.uint32), film.view(np.uint32))
+    # schedule knobs do not change the job; anything that changes the film does
+    rp.spp_per_pass = 3; rp.profile = 1
+    assert F.read_checkpoint(path, F.checkpoint_header(rp, first_sample=1))[0] == 2
+    for change in (dict(spp=8), dict(max_depth=rp.max_depth + 1), dict(sampler_type=1), dict(first_sample=0)):
+        rp2 = F.FrontScene(text=SCENE).render_params(); first = change.pop("first_sample", 1)
+        for k, v in change.items():
+            setattr(rp2, k, v)
+        with pytest.raises(ValueError, match="not of this job"):
+            F.read_checkpoint(path, F.checkpoint_header(rp2, first_sample=first))
+    ao = pkg._abi_ao.PtAOParams(8, 1)
+    with pytest.raises(ValueError, match="not of this job"):
+        F.read_checkpoint(path, F.checkpoint_header(rp, ao=ao, first_sample=1))
+    small = F.checkpoint_header(rp, first_sample=1); small.width = 8
+    with pytest.raises(ValueError, match="film size"):
+        F.read_checkpoint(path, small)
+    with open(path, "r+b") as f:   # a truncated film
+        f.truncate(C.sizeof(F.PtfCheckpointHeader) + 100)
+    with pytest.raises(ValueError, match="truncated"):
+        F.read_checkpoint(path, hdr)
+    path.write_bytes(b"not a checkpoint" * 4)
+    with pytest.raises(ValueError, match="not a checkpoint"):
+        F.read_checkpoint(path, hdr)
