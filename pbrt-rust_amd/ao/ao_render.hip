@@ -152,7 +152,7 @@ int ao_pass(pt_scene *sc, const RenderConst &rc, const PtAOParams *ao, uint32_t 
         HIP_TRY(hipGetLastError());
     }
     sc->begin("film", total); sc->set_kernel("k_film");
-    hipLaunchKernelGGL(k_film, dim3((unsigned)(((size_t)rc.n_pix_slots * kFilmLanes + 255) / 256)), dim3(256), 0, sc->stream, rc, sc->ps, sc->d_filter, sc->film_rgbw, sc->dc);
+    hipLaunchKernelGGL(k_film, dim3((unsigned)(((size_t)rc.n_pix_slots + 255) / 256)), dim3(256), 0, sc->stream, rc, sc->ps, sc->d_filter, sc->film_rgbw, sc->dc);
     sc->end();
     HIP_TRY(hipGetLastError());
     return check_device_error(sc);

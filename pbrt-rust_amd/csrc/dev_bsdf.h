@@ -12,11 +12,7 @@ enum LobeKind : uint8_t { LB_LAMBERT_R, LB_LAMBERT_T, LB_OREN_NAYAR, LB_SPEC_R, 
                           LB_DISNEY_DIFFUSE, LB_DISNEY_FAKESS, LB_DISNEY_RETRO, LB_DISNEY_SHEEN, LB_DISNEY_CLEARCOAT };   // materials/disney.rs
 enum FresnelKind : uint8_t { FR_NOOP, FR_DIELECTRIC, FR_CONDUCTOR, FR_DISNEY };
 
-#ifdef PT_OUTLINE_BSDF   // experiment: the scalar microfacet / Fresnel helpers as real functions (like the f64 transcendentals, dev_math.h)
-#define PT_DEVO __device__ __noinline__ inline
-#else
-#define PT_DEVO PT_DEV
-#endif
+// (the scalar microfacet / Fresnel helpers as real functions, like the f64 transcendentals of dev_math.h: five-lobe kernel -3 %, one-lobe +7 % -- profiles/r3/NOTES.md)
 PT_DEV V3 cosine_sample_hemisphere(P2 u) {  // sampling.rs:188-193
     P2 d = concentric_sample_disk(u);
     float z = sqrtf(maxf(0.0f, 1.0f - d.x * d.x - d.y * d.y));
@@ -49,7 +45,7 @@ PT_DEV bool refract(V3 wi, V3 n, float eta, V3 &wt) {  // reflection.rs:160-174
     wt = n * (eta * cos_i - cos_t) + (-wi) * eta;
     return true;
 }
-PT_DEVO float fr_dielectric(float cos_i, float etai, float etat) {  // reflection.rs:29-52
+PT_DEV float fr_dielectric(float cos_i, float etai, float etat) {  // reflection.rs:29-52
     cos_i = clampf(cos_i, -1.0f, 1.0f);
     if (!(cos_i > 0.0f)) { float t = etai; etai = etat; etat = t; cos_i = fabsf(cos_i); }
     float sin_i = sqrtf(maxf(0.0f, 1.0f - cos_i * cos_i));
@@ -60,7 +56,7 @@ PT_DEVO float fr_dielectric(float cos_i, float etai, float etat) {  // reflectio
     float rperp = ((etai * cos_i) - (etat * cos_t)) / ((etai * cos_i) + (etat * cos_t));
     return (rparl * rparl + rperp * rperp) / 2.0f;
 }
-PT_DEVO RGB fr_conductor(float cos_i, RGB etai, RGB etat, RGB k) {  // reflection.rs:54-76
+PT_DEV RGB fr_conductor(float cos_i, RGB etai, RGB etat, RGB k) {  // reflection.rs:54-76
     cos_i = clampf(cos_i, -1.0f, 1.0f);
     RGB eta = etat / etai, etak = k / etai;
     float cos2 = cos_i * cos_i, sin2 = 1.0f - cos2;
@@ -116,14 +112,14 @@ PT_DEV float roughness_to_alpha(float roughness) {  // microfacet.rs:334-340
     float x = dm_logf(roughness);
     return 1.62142f + 0.819955f * x + 0.1734f * x * x + 0.0171201f * x * x * x + 0.000640711f * x * x * x * x;
 }
-PT_DEVO float tr_d(float ax, float ay, V3 wh) {
+PT_DEV float tr_d(float ax, float ay, V3 wh) {
     float t2 = tan2_theta(wh);
     if (__builtin_isinf(t2)) return 0.0f;
     float c4 = cos2_theta(wh) * cos2_theta(wh);
     float e = (cos2_phi(wh) / (ax * ax) + sin2_phi(wh) / (ay * ay)) * t2;
     return 1.0f / (kPi * ax * ay * c4 * (1.0f + e) * (1.0f + e));
 }
-PT_DEVO float tr_lambda(float ax, float ay, V3 w) {
+PT_DEV float tr_lambda(float ax, float ay, V3 w) {
     float abs_tan = fabsf(tan_theta(w));
     if (__builtin_isinf(abs_tan)) return 0.0f;
     float alpha = sqrtf(cos2_phi(w) * ax * ax + sin2_phi(w) * ay * ay);
@@ -158,7 +154,7 @@ PT_DEV void tr_sample11(float cos_t, float u1, float u2, float &sx, float &sy) {
     float z = (u2 * (u2 * (u2 * 0.27385f - 0.73369f) + 0.46341f)) / (u2 * (u2 * (u2 * 0.093073f + 0.309420f) - 1.000000f) + 0.597999f);
     sy = S * z * sqrtf(1.0f + sx * sx);
 }
-PT_DEVO V3 tr_sample_wh(float ax, float ay, V3 wo, P2 u) {  // microfacet.rs:293-316,394-401
+PT_DEV V3 tr_sample_wh(float ax, float ay, V3 wo, P2 u) {  // microfacet.rs:293-316,394-401
     bool flip = wo.z < 0.0f;
     V3 wi = flip ? -wo : wo;
     V3 wis = normalize(V3(ax * wi.x, ay * wi.y, wi.z));
@@ -510,16 +506,11 @@ template <int MAXL, int DIFF = 0> struct Bsdf {
     // f(wow, wiw, flags) and pdf(wow, wiw, flags) of the same pair of directions (estimate_direct's light sample, integrator.rs:142-147) in ONE
     // pass over the lobes: each lobe is fetched from the LDS store and decoded once, and what its value and its density share (the half
     // vector, the microfacet distribution's D) is computed once -- the two functions are inlined side by side on the same operands.
-#ifndef PT_FUSE_FPDF
-#define PT_FUSE_FPDF 1   // experiment hooks: 0 = the two passes as they were
-#endif
-#ifndef PT_FUSE_TAIL
-#define PT_FUSE_TAIL 1
-#endif
+    // (The switches that turned this fusion and sample_f's off again: profiles/r6/experiments/settled_ab_hooks.patch.)
     PT_DEV RGB f_pdf(V3 wow, V3 wiw, int flags, float &pdf_out) const {
         // (one lobe in registers: nothing to share; the five-lobe class, already spilling, loses more to the longer live ranges than it gains:
         //  C3 two-lobe kernel 130.6 -> 124.7 ms with both fusions, five-lobe kernel 157.8 -> 150.4 ms with only sample_f's)
-        if (MAXL != 2 || !PT_FUSE_FPDF) { const RGB r = f(wow, wiw, flags); pdf_out = pdf(wow, wiw, flags); return r; }
+        if (MAXL != 2) { const RGB r = f(wow, wiw, flags); pdf_out = pdf(wow, wiw, flags); return r; }
         pdf_out = 0.0f;
         V3 wi = to_local(wiw), wo = to_local(wow);
         if (wo.z == 0.0f) return RGB(0.0f);
@@ -559,7 +550,7 @@ template <int MAXL, int DIFF = 0> struct Bsdf {
         fv = scaled(idx, lobe_sample_f<DIFF, FULL>(get(idx), wo, wi, ur, pdf, sampled));
         if (pdf == 0.0f) { sampled = 0; return RGB(0.0f); }
         wiw = to_world(wi);
-        if (!LDS || !PT_FUSE_TAIL) {
+        if (!LDS) {
             if (!(btype & BSDF_SPECULAR) && matching > 1) {
 #pragma unroll 1
                 for (int i = 0; i < n; ++i) if (i != idx && matches(i, ty)) pdf += lobe_pdf<DIFF, FULL>(get(i), wo, wi);

@@ -9,23 +9,12 @@
 
 #define PT_DEV __device__ __forceinline__
 #define PT_HD __host__ __device__ __forceinline__
-#ifdef PT_NOINLINE_HEAVY   // code-size experiment: heavy helpers as real functions
-#define PT_HDX __host__ __device__ __noinline__
-#define PT_DEVX __device__ __noinline__
-#else
-#define PT_HDX PT_HD
-#define PT_DEVX PT_DEV
-#endif
 // The scalar f64 transcendentals (sin/cos, atan2, ln, exp: numbers in, numbers out, no memory arguments) are REAL functions since round 3:
 // inlined at each of their ~10 call sites they made up 20 % of the matte shade kernel's code and, more to the point, 16 of its 202 VGPRs
 // (k_shade<1, 0, 1>: 84 -> 67 KB, 202 -> 186 VGPRs; the specular-only kernel 145 -> 127 = four waves per SIMD). By itself that changes
 // nothing (the kernel's instruction cache hit rate was 99.98 % already: SQC_ICACHE counters, profiles/r3); it is what lets the matte kernel
-// run THREE waves per SIMD with 32 bytes of scratch instead of 76 (kern_shade.h): 93.4 -> 83.7 ms per C2 step. -DPT_INLINE_MATH restores the old form.
-#ifdef PT_INLINE_MATH
-#define PT_HDM PT_HDX
-#else
+// run THREE waves per SIMD with 32 bytes of scratch instead of 76 (kern_shade.h): 93.4 -> 83.7 ms per C2 step.
 #define PT_HDM __host__ __device__ __noinline__ inline
-#endif
 
 namespace ptd {
 
@@ -336,7 +325,7 @@ PT_HD V3 xf_vector(const M4 &t, V3 v) {  // transform.rs:496-508
 }
 
 // geometry.rs:6-24
-PT_HDX V3 offset_ray_origin(V3 p, V3 perr, V3 n, V3 w) {
+PT_HD V3 offset_ray_origin(V3 p, V3 perr, V3 n, V3 w) {
     float d = dot(vabs(n), perr);
     V3 offset = n * d;
     if (dot(w, n) < 0.0f) offset = -offset;

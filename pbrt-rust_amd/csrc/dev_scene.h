@@ -234,7 +234,7 @@ struct SurfaceInteraction {
 // `with_shape` = the `s: Option<Arc<Shapes>>` argument (None inside Shape::pdf_wi, shape.rs:72).
 // tri_fill_from: the triangle's vertices and flag byte are already at hand (the 48-byte TriPacket the traversal hit); the index
 // triple is fetched only for meshes with per-vertex N / S / UV.
-PT_DEVX void tri_fill_from(const DeviceScene &s, uint32_t tri, uint32_t fl, V3 p0, V3 p1, V3 p2, V3 ray_d, float b0, float b1, float b2, bool with_shape, SurfaceInteraction &si) {
+PT_DEV void tri_fill_from(const DeviceScene &s, uint32_t tri, uint32_t fl, V3 p0, V3 p1, V3 p2, V3 ray_d, float b0, float b1, float b2, bool with_shape, SurfaceInteraction &si) {
     uint32_t i0 = 0, i1 = 0, i2 = 0;
     if (fl & (PT_TRI_HAS_N | PT_TRI_HAS_S | PT_TRI_HAS_UV)) { i0 = s.indices[3 * tri]; i1 = s.indices[3 * tri + 1]; i2 = s.indices[3 * tri + 2]; }
     P2 uv[3];   // triangle.rs:109-115
@@ -293,7 +293,7 @@ PT_DEVX void tri_fill_from(const DeviceScene &s, uint32_t tri, uint32_t fl, V3 p
         si.sh_dpdu = ss; si.sh_dpdv = ts;
     }
 }
-PT_DEVX void tri_fill_interaction(const DeviceScene &s, uint32_t tri, V3 ray_d, float b0, float b1, float b2, bool with_shape, SurfaceInteraction &si) {
+PT_DEV void tri_fill_interaction(const DeviceScene &s, uint32_t tri, V3 ray_d, float b0, float b1, float b2, bool with_shape, SurfaceInteraction &si) {
     const uint32_t i0 = s.indices[3 * tri], i1 = s.indices[3 * tri + 1], i2 = s.indices[3 * tri + 2];
     tri_fill_from(s, tri, s.tri_flags[tri], ld3(s.P, i0), ld3(s.P, i1), ld3(s.P, i2), ray_d, b0, b1, b2, with_shape, si);
 }

@@ -74,11 +74,7 @@ __global__ __launch_bounds__(256) void k_shade_medium(DeviceScene s, RenderConst
     __shared__ uint32_t s_hist[16];
     lq_init(s_qext); lq_init(s_qres); lq_init(s_qsh); lq_init(s_qmis); lq_init(s_qself);
     if (threadIdx.x < 16) s_hist[threadIdx.x] = 0;
-#ifdef PT_REGION_PROFILE
-    __shared__ long long s_pt[4]; __shared__ int s_pr[4]; __shared__ unsigned long long s_pacc[64];
-    if (threadIdx.x < 4) { s_pt[threadIdx.x] = clock64(); s_pr[threadIdx.x] = 15; }
-    Prof prof{s_pt, s_pr, s_pacc};
-#endif
+    PT_PROF_BEGIN
     sobol_stage_lds(s_sobol, tabs.nib, LDS_DIMS, threadIdx.x, blockDim.x);
     __syncthreads();
     const uint32_t count = *job.count;
@@ -179,17 +175,10 @@ __global__ __launch_bounds__(256) void k_shade_medium(DeviceScene s, RenderConst
 // NEE resolved, the environment's Le where path.rs:106-117 adds it, and the path-length histogram entry -- none of the
 // BSDF / light-sampling code. Keeping them out of k_shade leaves its waves full of real surface hits.
 template <bool SPH, bool VOL>
-#ifndef PT_MISS_WAVES
-#define PT_MISS_WAVES 1   // experiment hook
-#endif
 __global__ __launch_bounds__(256, PT_MISS_WAVES) void k_shade_miss(DeviceScene s, RenderConst rc, PathSoA ps, ShadeJob job) {
     __shared__ uint32_t s_hist[16];
     if (threadIdx.x < 16) s_hist[threadIdx.x] = 0;
-#ifdef PT_REGION_PROFILE
-    __shared__ long long s_pt[4]; __shared__ int s_pr[4]; __shared__ unsigned long long s_pacc[64];
-    if (threadIdx.x < 4) { s_pt[threadIdx.x] = clock64(); s_pr[threadIdx.x] = 15; }
-    Prof prof{s_pt, s_pr, s_pacc};   // not reported: the region table is k_shade's
-#endif
+    PT_PROF_BEGIN   // not reported: the region table is k_shade's
     __syncthreads();
     const uint32_t count = *job.count;
     unsigned long long zero_num = 0, n_valid = 0, n_bytes = 0;
@@ -232,19 +221,13 @@ __global__ __launch_bounds__(256, PT_MISS_WAVES) void k_shade_miss(DeviceScene s
 // scattered 64-byte gathers at 1.8x their useful bytes. The film kernel reads every path's core record anyway, in path-id order: it now does that last step itself,
 // on fully coalesced streams, and the per-iteration miss pass (a queue append in the shade kernels and the router, a launch, a gather and a write-back) is gone.
 // The arithmetic on L is k_shade_miss's, in its order (resolve_pending, then Le): the same bits reach the film.
-#ifndef PT_FILM_WAVES
-#define PT_FILM_WAVES 4   // waves per SIMD the kernel is compiled for: 128 registers + 32 B of scratch; C2 film 21.9 (three waves, no scratch) -> 19.2 ms, five / six / eight: 24.3 / 28.9 / 33.7
-#endif
+// PT_FILM_WAVES (knobs.h) = 4 waves per SIMD the kernel is compiled for: 128 registers + 32 B of scratch; C2 film 21.9 (three waves, no scratch) -> 19.2 ms, five / six / eight: 24.3 / 28.9 / 33.7
 template <bool SPH>
 __global__ __launch_bounds__(256, PT_FILM_WAVES) void k_film_final(DeviceScene s, RenderConst rc, PathSoA ps, const float *filter_table, float *film_rgbw, DevCounters *counters) {
     __shared__ uint32_t s_hist[16];
     if (threadIdx.x < 16) s_hist[threadIdx.x] = 0;
     __syncthreads();
-#ifdef PT_REGION_PROFILE
-    __shared__ long long s_pt[4]; __shared__ int s_pr[4]; __shared__ unsigned long long s_pacc[64];
-    if (threadIdx.x < 4) { s_pt[threadIdx.x] = clock64(); s_pr[threadIdx.x] = 15; }
-    Prof prof{s_pt, s_pr, s_pacc};   // not reported: the region table is k_shade's
-#endif
+    PT_PROF_BEGIN   // not reported: the region table is k_shade's
     unsigned long long zero_num = 0, n_final = 0, n_bytes = 0;
     uint32_t n_assert = 0;
     film_slot(rc, ps, filter_table, film_rgbw, counters, [&](uint32_t pid, RGB &L) {

@@ -8,11 +8,9 @@
 // NEE at pi through the adapter BSDF, sample the adapter BSDF, Russian roulette, bounces += 1.
 // VOL: under the volumetric integrator (volpath.rs:186-214) -- the estimate at pi handles media (shadow / MIS rays start in the medium pi's
 // MediumInterface names for their side; the interface is the one the probe chain handed on: BssSoA::iface), and the new ray carries its medium.
+// PT_BSSRDF_WAVES (knobs.h): waves per SIMD the kernel is compiled for. Triangle-only scenes: three (168 VGPRs + 64 bytes of scratch instead of 197: C5 41.1 -> 35.7 ms
+// per 216-sample pass; like the matte shade kernel it is VALU-bound at two waves); with spheres / instances three waves spill 192 bytes: left alone
 template <bool SPH, bool VOL>
-#ifndef PT_BSSRDF_WAVES
-#define PT_BSSRDF_WAVES ((SPH || VOL) ? 1 : 3)   // waves per SIMD the kernel is compiled for. Triangle-only scenes: three (168 VGPRs + 64 bytes of scratch instead of 197: C5 41.1 -> 35.7 ms
-                                        // per 216-sample pass; like the matte shade kernel it is VALU-bound at two waves); with spheres / instances three waves spill 192 bytes: left alone
-#endif
 __global__ __launch_bounds__(256, PT_BSSRDF_WAVES) void k_bssrdf(DeviceScene s, RenderConst rc, SobolTables tabs, LightGrid grid, PathSoA ps, BssrdfJob job) {
     constexpr uint32_t LDS_DIMS = 56u;
     __shared__ uint32_t s_sobol[LDS_DIMS * kSobolNibWords];
@@ -23,11 +21,7 @@ __global__ __launch_bounds__(256, PT_BSSRDF_WAVES) void k_bssrdf(DeviceScene s, 
     if (threadIdx.x < 16) s_hist[threadIdx.x] = 0;
     sobol_stage_lds(s_sobol, tabs.nib, LDS_DIMS, threadIdx.x, blockDim.x);
     __syncthreads();
-#ifdef PT_REGION_PROFILE
-    __shared__ long long s_pt[4]; __shared__ int s_pr[4]; __shared__ unsigned long long s_pacc[64];
-    if (threadIdx.x < 4) { s_pt[threadIdx.x] = clock64(); s_pr[threadIdx.x] = 15; }
-    Prof prof{s_pt, s_pr, s_pacc};
-#endif
+    PT_PROF_BEGIN
     const BssSoA &bs = job.bs;
     const uint32_t count = *job.count;
     const uint32_t rounded = (count + 255u) & ~255u;

@@ -1,28 +1,29 @@
 // kern_shade.h -- split out of the former single-file kernels.hip so that the translation units compile in parallel.
 #pragma once
 #include "kern_shade_common.h"
-#ifndef PT_SHADE_ATTR
-#define PT_SHADE_ATTR   // experiment hook: e.g. __attribute__((amdgpu_waves_per_eu(4,4)))
-#endif
 // MODE: 0 = triangle-only scenes, 1 = general geometry (spheres and/or instances), 2 = general geometry + textures
 // DIFF: 1 = the launch serves class 0 (matte materials: Lambertian / Oren-Nayar lobes only); 2 = class 6 (mirror / smooth glass: perfectly
 //       specular lobes only, no next-event estimation); 0 = any material of the lobe budget MAXL
+// Waves per SIMD the kernel is compiled for (knobs.h holds the PT_* defaults). The others lose more to spills than they gain (one-lobe general kernel at
+// three waves: 160 bytes of scratch, 112.8 -> 114.8 ms on C3).
+template <int MAXL, int MODE, int DIFF> constexpr int shade_waves() {
+    // the plastic-like two-lobe kernel (DIFF 4) of triangle-only scenes: three waves per SIMD (168 VGPRs + 80 B of scratch) with 28 Sobol' dimensions staged in LDS and
+    // 512-entry queues (51 KB per workgroup: three fit a CU) -- C3 shade_2lobe 101.0 -> 86.9 ms against two waves with 56 dimensions / 1024 entries
+    if constexpr (MAXL == 2 && MODE == 0 && DIFF == 4) return PT_P2_WAVES;
+    // the metal-only one-lobe kernel (DIFF 3) of triangle-only scenes
+    else if constexpr (MAXL == 1 && MODE == 0 && DIFF == 3) return PT_METAL_WAVES;
+    // the matte kernel of triangle-only scenes (the headline's) takes three: 168 VGPRs + 32 bytes of scratch, VALU-bound at two waves (57 % busy, 9 % of the
+    // wave cycles waiting on memory: SQ counters in profiles/r3)
+    else if constexpr (MAXL == 1 && MODE == 0 && DIFF == 1) return PT_SHADE_WAVES > 3 ? PT_SHADE_WAVES : 3;
+    // the specular-only kernel: 127 VGPRs (dev_math.h)
+    else if constexpr (MAXL == 1 && MODE == 0 && DIFF == 2) return 4;
+    else if constexpr (MAXL == 1 && MODE == 1) return PT_SHADE_WAVES > 2 ? PT_SHADE_WAVES : 2;
+    else if constexpr (MAXL == 1) return PT_SHADE_WAVES;   // PT_SHADE_WAVES: the minimum the one-lobe kernels are compiled for (tools/build_variant.sh -DPT_SHADE_WAVES=N)
+    else if constexpr (MAXL >= 2 && MODE < 2) return 2;
+    else return 1;
+}
 template <int MAXL, int MODE, int DIFF>
-#ifndef PT_SHADE_WAVES
-#define PT_SHADE_WAVES 1   // experiment hook (tools/build_variant.sh -DPT_SHADE_WAVES=N): minimum waves per SIMD the one-lobe kernels are compiled for
-#endif
-// Waves per SIMD the kernel is compiled for. The matte kernel of triangle-only scenes (MAXL 1, MODE 0, DIFF 1: the headline's) takes three:
-// 168 VGPRs + 32 bytes of scratch, VALU-bound at two waves (57 % busy, 9 % of the wave cycles waiting on memory: SQ counters in profiles/r3).
-// The others lose more to spills than they gain (one-lobe general kernel at three waves: 160 bytes of scratch, 112.8 -> 114.8 ms on C3).
-#ifndef PT_P2_WAVES
-#define PT_P2_WAVES 3     // the plastic-like two-lobe kernel (DIFF 4) of triangle-only scenes: three waves per SIMD (168 VGPRs + 80 B of scratch) with 28 Sobol' dimensions staged
-#define PT_P2_DIMS 28u    // in LDS and 512-entry queues (51 KB per workgroup: three fit a CU) -- C3 shade_2lobe 101.0 -> 86.9 ms against two waves with 56 dimensions / 1024 entries
-#define PT_P2_QCAP 512
-#endif
-#ifndef PT_METAL_WAVES
-#define PT_METAL_WAVES 3   // experiment hook: waves per SIMD of the metal-only one-lobe kernel (DIFF 3) of triangle-only scenes
-#endif
-__global__ __launch_bounds__(256, (MAXL == 2 && MODE == 0 && DIFF == 4) ? PT_P2_WAVES : (MAXL == 1 && MODE == 0 && DIFF == 3) ? PT_METAL_WAVES : (MAXL == 1 && MODE == 0 && DIFF == 1) ? (PT_SHADE_WAVES > 3 ? PT_SHADE_WAVES : 3) : (MAXL == 1 && MODE == 0 && DIFF == 2) ? 4 : (MAXL == 1 && MODE == 1) ? (PT_SHADE_WAVES > 2 ? PT_SHADE_WAVES : 2) : (MAXL == 1 ? PT_SHADE_WAVES : (MAXL >= 2 && MODE < 2) ? 2 : 1)) PT_SHADE_ATTR void k_shade(DeviceScene s, RenderConst rc, SobolTables tabs, LightGrid grid, PathSoA ps, ShadeJob job) {
+__global__ __launch_bounds__(256, (shade_waves<MAXL, MODE, DIFF>())) void k_shade(DeviceScene s, RenderConst rc, SobolTables tabs, LightGrid grid, PathSoA ps, ShadeJob job) {
     constexpr bool SPH = MODE >= 1, TEX = MODE >= 2, VOL = MODE == 3;   // MODE 3: general + textures + participating media (volpath.rs)
     // Sobol' nibble tables of the first dimensions (dev_sampler.h): 56 cover the vertices of bounces 0..5; the five-lobe class, whose lobe store
     // fills the LDS, keeps 20 and reads the rest from HBM (one 64-byte line per look-up, the same for every lane of a bounce)
@@ -38,16 +39,10 @@ __global__ __launch_bounds__(256, (MAXL == 2 && MODE == 0 && DIFF == 4) ? PT_P2_
     __shared__ LdsQueue<SSS ? QCAP : 1> s_qprobe;
     __shared__ LdsQueue<(MODE == 3) ? QCAP : 1> s_qself;   // volpath with grid media: vertices waiting for stage B, back into this class's next queue
     __shared__ uint32_t s_hist[16];
-    __shared__ uint32_t s_bins[16];
     __shared__ float s_lobes[lobe_store_words<MAXL>()];   // the two- and five-lobe classes keep their BxDFs here (dev_bsdf.h)
     lq_init(s_qext); lq_init(s_qres); lq_init(s_qsh); lq_init(s_qmis); lq_init(s_qprobe); lq_init(s_qself);
     if (threadIdx.x < 16) s_hist[threadIdx.x] = 0;
-#ifdef PT_REGION_PROFILE
-    __shared__ long long s_pt[4]; __shared__ int s_pr[4]; __shared__ unsigned long long s_pacc[64];
-    if (threadIdx.x < 64) s_pacc[threadIdx.x] = 0;
-    if (threadIdx.x < 4) { s_pt[threadIdx.x] = clock64(); s_pr[threadIdx.x] = 15; }
-    Prof prof{s_pt, s_pr, s_pacc};
-#endif
+    PT_PROF_BEGIN
     sobol_stage_lds(s_sobol, tabs.nib, LDS_DIMS, threadIdx.x, blockDim.x);
     __syncthreads();
     const uint32_t count = *job.count;
@@ -58,7 +53,7 @@ __global__ __launch_bounds__(256, (MAXL == 2 && MODE == 0 && DIFF == 4) ? PT_P2_
     const bool valid = qi < count;
     bool push_ext = false, push_resolve = false, push_shadow = false, push_mis = false, push_probe = false, push_self = false;
     int finished_bounces = -1;
-    uint32_t pid = 0, ext_oct = 0;   // direction octant of the continuation ray
+    uint32_t pid = 0;
     PT_T(0);
     if (valid) {
         n_valid++;
@@ -177,7 +172,7 @@ __global__ __launch_bounds__(256, (MAXL == 2 && MODE == 0 && DIFF == 4) ? PT_P2_
                         ps.medium(pid) = medium_toward(mif, si.n, rd);
                         bounces = (bounces - 1u) & 0xffu;
                     }
-                    push_ext = true; ext_oct = (rd.x < 0.0f ? 1u : 0u) | (rd.y < 0.0f ? 2u : 0u) | (rd.z < 0.0f ? 4u : 0u);
+                    push_ext = true;
                 } else {
                     const V3 wo = -rd;  // path.rs:148; estimate_direct uses isect.wo (== -rd for triangles, triangle.rs:296)
                     // uniform_sample_onelight (integrator.rs:81-106)
@@ -264,7 +259,6 @@ __global__ __launch_bounds__(256, (MAXL == 2 && MODE == 0 && DIFF == 4) ? PT_P2_
                             rq[0] = make_float4(o.x, o.y, o.z, wi.x); rq[1] = make_float4(wi.y, wi.z, 0.0f, 0.0f);
                             if (VOL) ps.medium(pid) = medium_toward(mif, si.n, wi);   // isect.spawn_ray(wi) (interaction.rs:32-36,54-66)
                             push_ext = true; n_bytes += 32 + 4;  // new ray record, ext queue entry
-                            ext_oct = (wi.x < 0.0f ? 1u : 0u) | (wi.y < 0.0f ? 2u : 0u) | (wi.z < 0.0f ? 4u : 0u);
                         }
                     }
                 }
@@ -281,11 +275,7 @@ __global__ __launch_bounds__(256, (MAXL == 2 && MODE == 0 && DIFF == 4) ? PT_P2_
         cw[1] = make_float4(beta.r, beta.g, beta.b, __uint_as_float((smp.dim & 0xffffu) | ((bounces & 0xffu) << 16) | (flags << 24)));
     }
     PT_T(13);
-#ifdef PT_BIN_EXT
-    lq_push_binned(s_qext, s_bins, pid, push_ext, ext_oct);
-#else
-    lq_push(s_qext, pid, push_ext);
-#endif
+    lq_push(s_qext, pid, push_ext);   // (grouped by the new ray's direction octant: trace no faster -- profiles/HISTORY.md; profiles/r6/experiments/settled_ab_hooks.patch)
     lq_push(s_qres, pid, push_resolve && job.shade_next0 != nullptr);   // (no miss pass: the film kernel ends the dead paths, k_film_final)
     lq_push(s_qsh, pid, push_shadow);
     lq_push(s_qmis, pid, push_mis);
@@ -309,11 +299,7 @@ __global__ __launch_bounds__(256, (MAXL == 2 && MODE == 0 && DIFF == 4) ? PT_P2_
     if constexpr (MODE == 3) lq_flush_nosync(s_qself, job.self_next_count, job.self_next, 0u, true);
     __syncthreads();
     __syncthreads();   // s_hist complete
-#ifdef PT_REGION_PROFILE
-    PT_T(14);
-    __syncthreads();
-    if (threadIdx.x < 16) atomicAdd(&job.counters->regions[threadIdx.x], s_pacc[threadIdx.x] + s_pacc[16 + threadIdx.x] + s_pacc[32 + threadIdx.x] + s_pacc[48 + threadIdx.x]);
-#endif
+    PT_PROF_END(job.counters);
     if (threadIdx.x < 16 && s_hist[threadIdx.x]) atomicAdd(&job.counters->path_len[threadIdx.x], (unsigned long long)s_hist[threadIdx.x]);
     counter_add(&job.counters->zero_num, zero_num);
     counter_add(&job.counters->zero_den, zero_den);

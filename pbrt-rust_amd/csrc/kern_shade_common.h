@@ -5,14 +5,24 @@
 
 // ---- optional region timers (build with -DPT_REGION_PROFILE): wave time between markers is charged to the region of the
 // previous marker; one lane per wave updates three LDS words. Printed by the host when the scene is destroyed.
+// PT_PROF_BEGIN: a kernel's timer state (`prof`, handed on to the helpers with PT_PROF_PASS); PT_PROF_END(counters): the block's sums go to counters->regions
+// (k_shade only: the region table is k_shade's, the other kernels keep their timers to themselves).
 #ifdef PT_REGION_PROFILE
 struct Prof { long long *t; int *r; unsigned long long *acc; };
+#define PT_PROF_BEGIN __shared__ long long s_pt[4]; __shared__ int s_pr[4]; __shared__ unsigned long long s_pacc[64]; \
+    if (threadIdx.x < 64) s_pacc[threadIdx.x] = 0; \
+    if (threadIdx.x < 4) { s_pt[threadIdx.x] = clock64(); s_pr[threadIdx.x] = 15; } \
+    Prof prof{s_pt, s_pr, s_pacc};
+#define PT_PROF_END(counters) do { PT_T(14); __syncthreads(); \
+    if (threadIdx.x < 16) atomicAdd(&(counters)->regions[threadIdx.x], prof.acc[threadIdx.x] + prof.acc[16 + threadIdx.x] + prof.acc[32 + threadIdx.x] + prof.acc[48 + threadIdx.x]); } while (0)
 #define PT_T(k) do { if ((int)__lane_id() == __ffsll((unsigned long long)__ballot(1)) - 1) { const long long _n = clock64(); const int _w = threadIdx.x >> 6; \
     prof.acc[_w * 16 + prof.r[_w]] += (unsigned long long)(_n - prof.t[_w]); prof.t[_w] = _n; prof.r[_w] = (k); } } while (0)
 #define PT_PROF_ARG , Prof prof
 #define PT_PROF_PASS , prof
 #else
 #define PT_T(k) do {} while (0)
+#define PT_PROF_BEGIN
+#define PT_PROF_END(counters) do {} while (0)
 #define PT_PROF_ARG
 #define PT_PROF_PASS
 #endif

@@ -18,15 +18,49 @@
 // Node steps and leaf (triangle) work share one loop: every iteration a lane fetches ONE record, an interior node's or a leaf packet's
 // ("if-if"); lanes at a leaf join once a quorum of them waits. Instance entry / exit is a step of its own (ST_INST / ST_RET).
 
-#ifndef PT_TRACE_WAVES
-#define PT_TRACE_WAVES 6        // waves per SIMD of the triangle-only kernels of the exact (two-wide) walk: 80 VGPRs, no scratch (knob history: profiles/HISTORY.md)
+// ---- optional SIMD utilisation study (build with -DPT_TRACE_UTIL, tools/profile_record.py): wave iterations and active lanes of the node phase / the leaf phase / the
+// transform step, wave cycles of the steps' parts, how long the launch's wave slots were occupied. All of it lives in these macros, which expand to nothing in the default build.
+#ifdef PT_TRACE_UTIL
+#define PT_UTIL_DECL \
+    uint32_t u_it1 = 0, u_act1 = 0, u_it2 = 0, u_act2 = 0, u_it3 = 0, u_act3 = 0; \
+    uint32_t u_ent = 0, u_rej = 0, u_ihit = 0, u_spill = 0;   /* instance entries tried / turned away by the object's root test / left with a hit; stack entries written beyond the LDS ones */ \
+    unsigned long long u_cxf = 0, u_cmain = 0;   /* wave cycles inside the transform step / the record step */ \
+    unsigned long long u_cfetch = 0, u_cnode = 0, u_cleaf = 0, u_cpop = 0;   /* of the record step: issue + wait of the loads, the node branch, the leaf branch, the pops */ \
+    long long u_cm = 0; \
+    const unsigned long long u_t0 = wall_clock64(); const long long u_t0c = clock64();
+#define PT_UTIL(it, act, pred) do { const unsigned long long m_ = __ballot(pred); if (pred) { act++; it += (lane == (uint32_t)(__ffsll((long long)m_) - 1)); } } while (0)
+#define PT_UTIL_COUNT(n, pred) do { if (pred) n++; } while (0)
+#define PT_UTIL_CLOCK(var) const long long var = clock64(); u_cm = var   /* a step starts: its own start time, and PT_UTIL_MARK's stopwatch restarts */
+#define PT_UTIL_MARK(acc) do { const long long n_ = clock64(); acc += (unsigned long long)(n_ - u_cm); u_cm = n_; } while (0)
+#define PT_UTIL_SINCE(acc, var) acc += (unsigned long long)(clock64() - var)
+#define PT_UTIL_EPILOGUE \
+    if (blockIdx.x == 0 && threadIdx.x == 0) { job.counters->dbg[0] = job.leaf_quorum; job.counters->dbg[1] = job.refill_min; } \
+    if (lane == 0) {   /* how long the launch's wave slots were occupied: a wave leaves when the queue is drained and its own rays are done */ \
+        const unsigned long long u_t1 = wall_clock64(); \
+        atomicMin(&job.counters->tail[0], u_t0); atomicMax(&job.counters->tail[1], u_t1); atomicAdd(&job.counters->tail[4 + 2 * (job.sub[0].kind & 3)], u_t1 - u_t0); \
+    } \
+    for (int o = 32; o > 0; o >>= 1) { u_it3 += __shfl_xor(u_it3, o); u_act3 += __shfl_xor(u_act3, o); u_ent += __shfl_xor(u_ent, o); u_rej += __shfl_xor(u_rej, o); u_ihit += __shfl_xor(u_ihit, o); u_spill += __shfl_xor(u_spill, o); } \
+    if (lane == 0) { atomicAdd(&job.counters->util2[4], (unsigned long long)u_ent); atomicAdd(&job.counters->util2[5], (unsigned long long)u_rej); atomicAdd(&job.counters->util2[6], (unsigned long long)u_ihit); atomicAdd(&job.counters->util2[7], (unsigned long long)u_spill); } \
+    if (lane == 0) { \
+        atomicAdd(&job.counters->tail[12], (unsigned long long)u_it3); atomicAdd(&job.counters->tail[13], (unsigned long long)u_act3); \
+        atomicAdd(&job.counters->tail[14], u_cxf); atomicAdd(&job.counters->tail[15], u_cmain); \
+        atomicAdd(&job.counters->util2[0], u_cfetch); atomicAdd(&job.counters->util2[1], u_cnode); atomicAdd(&job.counters->util2[2], u_cleaf); atomicAdd(&job.counters->util2[3], u_cpop); atomicAdd(&job.counters->tail[2], (unsigned long long)(clock64() - (long long)u_t0c)); \
+    } \
+    for (int o = 32; o > 0; o >>= 1) { u_it1 += __shfl_xor(u_it1, o); u_act1 += __shfl_xor(u_act1, o); u_it2 += __shfl_xor(u_it2, o); u_act2 += __shfl_xor(u_act2, o); } \
+    if (lane == 0) { \
+        atomicAdd(&job.counters->regions[4 * (job.sub[0].kind & 3) + 0], (unsigned long long)u_it1); atomicAdd(&job.counters->regions[4 * (job.sub[0].kind & 3) + 1], (unsigned long long)u_act1); \
+        atomicAdd(&job.counters->regions[4 * (job.sub[0].kind & 3) + 2], (unsigned long long)u_it2); atomicAdd(&job.counters->regions[4 * (job.sub[0].kind & 3) + 3], (unsigned long long)u_act2); \
+    }
+#else
+#define PT_UTIL_DECL
+#define PT_UTIL(it, act, pred) do { } while (0)
+#define PT_UTIL_COUNT(n, pred) do { } while (0)
+#define PT_UTIL_CLOCK(var) do { } while (0)
+#define PT_UTIL_MARK(acc) do { } while (0)
+#define PT_UTIL_SINCE(acc, var) do { } while (0)
+#define PT_UTIL_EPILOGUE
 #endif
-#ifndef PT_TRACE_WAVES_INST
-#define PT_TRACE_WAVES_INST 4   // exact walk, triangles + instances (MODE 3)
-#endif
-#ifndef PT_TRACE_ATTR
-#define PT_TRACE_ATTR   // experiment hook, e.g. __attribute__((amdgpu_waves_per_eu(6,6)))
-#endif
+
 // MODE: 0 = triangle-only scenes, 1 = general geometry (spheres, instances), 2 = general geometry + alpha-masked triangles
 // PROBE (closest hit only): every queue entry is a whole BSSRDF probe chain (TabulatedBSSRDF::sample_sp, bssrdf.rs:367-402). The lane
 // walks the chain of Scene::intersect calls itself -- hit, interaction, next segment towards the target -- keeps the last
@@ -41,17 +75,18 @@
 // visited in the reference's order, so every hit (primitive, t, barycentrics) and the triangle / sphere test counters are the reference's; the node
 // counter then counts RECORDS fetched (128 B each). QUAD = false walks the two-wide records and reproduces the reference's node-visit counter
 // (pt_set_trace_exact / PT_TRACE_EXACT=1: the counter tests and the oracle comparisons of bvh_nodes_visited).
+// Waves per SIMD the kernel is compiled for (knobs.h holds the defaults; knob history: profiles/HISTORY.md).
+template <int MODE, bool PROBE, int QUADK> constexpr int trace_waves() {
+    // the triangle-only kernels: the four-wide walk (eight quads of a record in flight per lane) / the exact (two-wide) walk: 80 VGPRs, no scratch
+    if constexpr (MODE == 0 && !PROBE) return QUADK != 0 ? PT_TRACE_WAVES_QUAD : PT_TRACE_WAVES;
+    // triangles + instances (MODE 3)
+    else if constexpr (MODE == 3 && !PROBE) return QUADK != 0 ? PT_TRACE_WAVES_QUAD_INST : PT_TRACE_WAVES_INST;
+    // the triangle-only probe-chain kernel (125 VGPRs = four by itself)
+    else if constexpr (MODE == 0 && PROBE) return PT_TRACE_WAVES_PROBE;
+    else return 1;
+}
 template <int ANY, int MODE, bool PROBE, int QUADK>
-#ifndef PT_TRACE_WAVES_PROBE
-#define PT_TRACE_WAVES_PROBE 1   // experiment hook: waves per SIMD of the triangle-only probe-chain kernel (125 VGPRs = four by itself)
-#endif
-#ifndef PT_TRACE_WAVES_QUAD
-#define PT_TRACE_WAVES_QUAD 5        // waves per SIMD of the four-wide triangle-only kernels (eight quads of a record in flight per lane)
-#endif
-#ifndef PT_TRACE_WAVES_QUAD_INST
-#define PT_TRACE_WAVES_QUAD_INST 4
-#endif
-__global__ __launch_bounds__(kTraceBlock, (MODE == 0 && !PROBE) ? ((QUADK != 0) ? PT_TRACE_WAVES_QUAD : PT_TRACE_WAVES) : (MODE == 3 && !PROBE) ? ((QUADK != 0) ? PT_TRACE_WAVES_QUAD_INST : PT_TRACE_WAVES_INST) : (MODE == 0 && PROBE) ? PT_TRACE_WAVES_PROBE : 1) PT_TRACE_ATTR void k_trace(DeviceScene s, TraceJob job) {
+__global__ __launch_bounds__(kTraceBlock, (trace_waves<MODE, PROBE, QUADK>())) void k_trace(DeviceScene s, TraceJob job) {
     static_assert(!(ANY != 0 && PROBE), "probe chains are closest-hit queries");
     // QUADK: 0 = the two-wide (exact) walk, 1 = the production walk, 2 = the production walk of a scene whose records + packets exceed the 4 GB that a buffer load's
     // 32-bit byte offset reaches: the same walk through global loads with 64-bit addresses (~15 more vector instructions per step for the address arithmetic)
@@ -64,12 +99,10 @@ __global__ __launch_bounds__(kTraceBlock, (MODE == 0 && !PROBE) ? ((QUADK != 0) 
     constexpr int kLds = QUAD ? (INST ? kLdsStackQuadInst : kLdsStackQuad) : (MODE == 0 ? kLdsStack : kLdsStackGeneral);   // LDS stack entries per lane
     constexpr int kMaxS = QUAD ? kMaxStackQuad : kMaxStack;   // deepest stack (the four-wide walk pushes up to three entries per record)
     __shared__ uint32_t lds_stack[(kTraceBlock / 64) * kLds * 2 * 64];
-#ifndef PT_WRAY_HBM
-#define PT_WRAY_HBM 1
-#endif
     // the world-space ray of a lane that is inside an instance: six words, written when the instance is entered and read when its marker is popped. The production walk keeps
     // them in the wave's HBM slab behind the spilled stack entries -- the 1.5 KB per wave buy three more LDS stack entries
-    constexpr bool kWrayHbm = INST && QUAD && PT_WRAY_HBM != 0;
+    // (the exact walk keeps its LDS copy)
+    constexpr bool kWrayHbm = INST && QUAD;
     __shared__ float lds_wray[(INST && !kWrayHbm) ? (kTraceBlock / 64) * 6 * 64 : 1];
     const uint32_t lane = lane_id();
     const uint32_t wave_in_block = threadIdx.x >> 6;
@@ -128,19 +161,7 @@ __global__ __launch_bounds__(kTraceBlock, (MODE == 0 && !PROBE) ? ((QUADK != 0) 
     gpool_u32 *const gpool = (gpool_u32 *)s.quad;
     const uint4 *leaf4 = reinterpret_cast<const uint4 *>(s.leaf);
     uint32_t n_nodes = 0, n_tris = 0, n_rays = 0, n_sph = 0;
-#ifdef PT_TRACE_UTIL   // SIMD utilisation study: wave iterations and active lanes of the node phase / the leaf phase
-    uint32_t u_it1 = 0, u_act1 = 0, u_it2 = 0, u_act2 = 0, u_it3 = 0, u_act3 = 0;
-    uint32_t u_ent = 0, u_rej = 0, u_ihit = 0, u_spill = 0;   // instance entries tried / turned away by the object's root test / left with a hit; stack entries written beyond the LDS ones
-    unsigned long long u_cxf = 0, u_cmain = 0;   // wave cycles inside the transform step / the record step
-    unsigned long long u_cfetch = 0, u_cnode = 0, u_cleaf = 0, u_cpop = 0;   // of the record step: issue + wait of the loads, the node branch, the leaf branch, the pops
-    long long u_cm = 0;
-#define PT_UTIL_MARK(acc) do { const long long n_ = clock64(); acc += (unsigned long long)(n_ - u_cm); u_cm = n_; } while (0)
-    const unsigned long long u_t0 = wall_clock64(); const long long u_t0c = clock64();
-#define PT_UTIL(it, act, pred) do { const unsigned long long m_ = __ballot(pred); if (pred) { act++; it += (lane == (uint32_t)(__ffsll((long long)m_) - 1)); } } while (0)
-#else
-#define PT_UTIL(it, act, pred) do { } while (0)
-#define PT_UTIL_MARK(acc) do { } while (0)
-#endif
+    PT_UTIL_DECL
 
     // lane state: ST_IDLE (no ray), ST_ENTER (fetch record `cur`), ST_LEAF (test packets from `cur`), ST_DONE
     // ST_INST (an instance packet at `cur` waits to be entered) and ST_RET (the instance's marker was popped, the world ray waits to
@@ -148,18 +169,12 @@ __global__ __launch_bounds__(kTraceBlock, (MODE == 0 && !PROBE) ? ((QUADK != 0) 
     // need in any one iteration, so they run in a step of their own once `inst_quorum` lanes wait for it (like leaves, below)
     enum : uint32_t { ST_IDLE = 0, ST_ENTER = 1, ST_LEAF = 2, ST_DONE = 3, ST_INST = 4, ST_RET = 5, ST_LEAFS = 6 };   // ST_LEAFS: at a leaf and being served (leaf_quorum below)
     uint32_t state = ST_IDLE;
-#ifndef PT_TRACE_CHUNK
-#define PT_TRACE_CHUNK 512   // queue entries a wave reserves per atomic (sweeps: profiles/HISTORY.md)
-#endif
-    constexpr int kChunk = PT_TRACE_CHUNK;
+    constexpr int kChunk = PT_TRACE_CHUNK;   // queue entries a wave reserves per atomic (knobs.h; sweeps: profiles/HISTORY.md)
     // Scenes with instances: the bites shrink near the end of the queue (guided self-scheduling). Their rays are long (S4: 50 records and 20 triangle tests on average, some
     // ten times that), so a wave that bites 512 entries when nothing is left behind them works them off while the chip idles. What is left is known for free: the atomic
     // returns the old head. Within the last `PT_TRACE_TAIL_ROUNDS` rounds of the grid the bite is a quarter, within the last quarter round a sixteenth (C4 trace 932 -> 915 ms).
     // Triangle-only scenes keep the full bite to the end: their launches end on single long rays, not on bites (C2: 131.4 -> 133.5 ms with the small ones, the eighth
     // of the job that rank 0 of 8 renders 22.1 -> 22.7 ms; a plain look at the head before every bite cost more than the tail it saved, round 2).
-#ifndef PT_TRACE_TAIL_ROUNDS
-#define PT_TRACE_TAIL_ROUNDS 2
-#endif
     constexpr bool kTailBites = MODE != 0 && PT_TRACE_TAIL_ROUNDS > 0;
     uint32_t bite = kChunk;   // wave-uniform (only the kernels with shrinking bites ever change it)
     bool exhausted = false;
@@ -224,9 +239,7 @@ __global__ __launch_bounds__(kTraceBlock, (MODE == 0 && !PROBE) ? ((QUADK != 0) 
         if (sp < (uint32_t)kLds) { stack[(2 * sp) * 64] = w0; stack[(2 * sp + 1) * 64] = w1; }
         else {
             spill[(2 * (sp - kLds)) * 64] = w0; spill[(2 * (sp - kLds) + 1) * 64] = w1;
-#ifdef PT_TRACE_UTIL
-            u_spill++;
-#endif
+            PT_UTIL_COUNT(u_spill, true);
         }
         sp++;
     };
@@ -471,10 +484,8 @@ __global__ __launch_bounds__(kTraceBlock, (MODE == 0 && !PROBE) ? ((QUADK != 0) 
             const unsigned long long xf_m = __ballot(state == ST_INST || state == ST_RET);
             if (xf_m != 0ull && ((uint32_t)__popcll(xf_m) >= job.inst_quorum || __ballot(at_node || at_leaf) == 0ull)) {
                 bool need_pop = false;
-#ifdef PT_TRACE_UTIL
                 PT_UTIL(u_it3, u_act3, state == ST_INST || state == ST_RET);
-                const long long u_c0 = clock64();
-#endif
+                PT_UTIL_CLOCK(u_c0);
                 if (state == ST_RET) {
                     const uint32_t w0 = xf_arg;
                     if (!QUAD) pending = (w0 >> 25) & 63u;            // the outer traversal's skipped entries
@@ -483,9 +494,7 @@ __global__ __launch_bounds__(kTraceBlock, (MODE == 0 && !PROBE) ? ((QUADK != 0) 
                     inv_dir = V3(1.0f / rd.x, 1.0f / rd.y, 1.0f / rd.z);
                     nx = inv_dir.x < 0.0f; ny = inv_dir.y < 0.0f; nz = inv_dir.z < 0.0f; PT_SGN3();
                     PT_TRI_RAY();
-#ifdef PT_TRACE_UTIL
-                    if (inst_hit) u_ihit++;
-#endif
+                    PT_UTIL_COUNT(u_ihit, inst_hit);
                     t_max = inst_hit ? t_max : t_max_world;  // r.t_max = ray.t_max only when the instance was hit
                     in_inst = PT_NONE; inst_hit = false;
                     if (w0 & kLeafBit) { cur = w0 & kMaskRef; state = ST_LEAF; }  // remaining packets of the outer leaf
@@ -505,9 +514,7 @@ __global__ __launch_bounds__(kTraceBlock, (MODE == 0 && !PROBE) ? ((QUADK != 0) 
                     const bool nx2 = inv2.x < 0.0f, ny2 = inv2.y < 0.0f, nz2 = inv2.z < 0.0f;
                     bool enter = true;
                     if (!I.single) { if (!QUAD) n_nodes++; enter = slab_test(I.root_min, I.root_max, o2, inv2, nx2, ny2, nz2, tm2); }  // object BVH root (bvh.rs:725-727)
-#ifdef PT_TRACE_UTIL
-                    u_ent++; if (!enter) u_rej++;
-#endif
+                    PT_UTIL_COUNT(u_ent, true); PT_UTIL_COUNT(u_rej, !enter);
                     if (enter && ((!QUAD && pending > 63u) || sp >= (uint32_t)kMaxS)) { atomicMax(job.error, (uint32_t)PT_ERR_STACK_OVERFLOW); enter = false; }
                     if (enter) {
                         // remember where to resume: the rest of this leaf (if any) and the outer skip count
@@ -525,17 +532,13 @@ __global__ __launch_bounds__(kTraceBlock, (MODE == 0 && !PROBE) ? ((QUADK != 0) 
                     else need_pop = true;
                 }
                 if (need_pop) pop_next();
-#ifdef PT_TRACE_UTIL
-                u_cxf += (unsigned long long)(clock64() - u_c0);
-#endif
+                PT_UTIL_SINCE(u_cxf, u_c0);
                 continue;   // states changed: re-evaluate which step runs next
             }
         }
         PT_UTIL(u_it1, u_act1, at_node || at_leaf);
         PT_UTIL(u_it2, u_act2, at_leaf);
-#ifdef PT_TRACE_UTIL
-        const long long u_c1 = clock64(); u_cm = u_c1;
-#endif
+        PT_UTIL_CLOCK(u_c1);
         if (at_node || at_leaf) {
             uint4 q0, q1, q2, q3;
             bool need_pop = false;
@@ -729,9 +732,7 @@ __global__ __launch_bounds__(kTraceBlock, (MODE == 0 && !PROBE) ? ((QUADK != 0) 
             if (need_pop) pop_next();
             PT_UTIL_MARK(u_cpop);
         }
-#ifdef PT_TRACE_UTIL
-        u_cmain += (unsigned long long)(clock64() - u_c1);
-#endif
+        PT_UTIL_SINCE(u_cmain, u_c1);
     }
     if (!MIX) { counter_add(&job.counters->nodes, n_nodes); counter_add(&job.counters->tri_tests, n_tris); }
     if (SPH) counter_add(&job.counters->sphere_tests, n_sph);
@@ -752,29 +753,9 @@ __global__ __launch_bounds__(kTraceBlock, (MODE == 0 && !PROBE) ? ((QUADK != 0) 
         counter_add(&job.counters->k_tris[job.sub[0].kind], n_tris);
         counter_add(&job.counters->k_rays[job.sub[0].kind], n_rays);
     }
-#ifdef PT_TRACE_UTIL
-    if (blockIdx.x == 0 && threadIdx.x == 0) { job.counters->dbg[0] = job.leaf_quorum; job.counters->dbg[1] = job.refill_min; }
-    if (lane == 0) {   // how long the launch's wave slots were occupied: a wave leaves when the queue is drained and its own rays are done
-        const unsigned long long u_t1 = wall_clock64();
-        atomicMin(&job.counters->tail[0], u_t0); atomicMax(&job.counters->tail[1], u_t1); atomicAdd(&job.counters->tail[4 + 2 * (job.sub[0].kind & 3)], u_t1 - u_t0);
-    }
-    for (int o = 32; o > 0; o >>= 1) { u_it3 += __shfl_xor(u_it3, o); u_act3 += __shfl_xor(u_act3, o); u_ent += __shfl_xor(u_ent, o); u_rej += __shfl_xor(u_rej, o); u_ihit += __shfl_xor(u_ihit, o); u_spill += __shfl_xor(u_spill, o); }
-    if (lane == 0) { atomicAdd(&job.counters->util2[4], (unsigned long long)u_ent); atomicAdd(&job.counters->util2[5], (unsigned long long)u_rej); atomicAdd(&job.counters->util2[6], (unsigned long long)u_ihit); atomicAdd(&job.counters->util2[7], (unsigned long long)u_spill); }
-    if (lane == 0) {
-        atomicAdd(&job.counters->tail[12], (unsigned long long)u_it3); atomicAdd(&job.counters->tail[13], (unsigned long long)u_act3);
-        atomicAdd(&job.counters->tail[14], u_cxf); atomicAdd(&job.counters->tail[15], u_cmain);
-        atomicAdd(&job.counters->util2[0], u_cfetch); atomicAdd(&job.counters->util2[1], u_cnode); atomicAdd(&job.counters->util2[2], u_cleaf); atomicAdd(&job.counters->util2[3], u_cpop); atomicAdd(&job.counters->tail[2], (unsigned long long)(clock64() - (long long)u_t0c));
-    }
-    for (int o = 32; o > 0; o >>= 1) { u_it1 += __shfl_xor(u_it1, o); u_act1 += __shfl_xor(u_act1, o); u_it2 += __shfl_xor(u_it2, o); u_act2 += __shfl_xor(u_act2, o); }
-    if (lane == 0) {
-        atomicAdd(&job.counters->regions[4 * (job.sub[0].kind & 3) + 0], (unsigned long long)u_it1); atomicAdd(&job.counters->regions[4 * (job.sub[0].kind & 3) + 1], (unsigned long long)u_act1);
-        atomicAdd(&job.counters->regions[4 * (job.sub[0].kind & 3) + 2], (unsigned long long)u_it2); atomicAdd(&job.counters->regions[4 * (job.sub[0].kind & 3) + 3], (unsigned long long)u_act2);
-    }
-#endif
+    PT_UTIL_EPILOGUE
 }
 #undef PT_SUB
 #undef PT_GPTR
-#undef PT_UTIL
-#undef PT_UTIL_MARK
 #undef PT_SGN3
 #undef PT_TRI_RAY

@@ -1,5 +1,6 @@
-// kernels.h -- shared declarations between the HIP kernels (kernels.hip) and the host driver (host_common.h: scene_create.hip, render_loop.hip, ...).
+// kernels.h -- shared declarations between the HIP kernels (kern_*.h, instantiated by the tu_*.hip translation units) and the host driver (host_common.h: scene_create.hip, render_loop.hip, ...).
 #pragma once
+#include "knobs.h"
 #include <cstddef>
 #include "dev_scene.h"
 #include "dev_sampler.h"
@@ -25,34 +26,18 @@ constexpr int kRouteSlots = 12;        // most staging queues a k_route block ho
 // slot_map: the slot of class c in nibble c (15 = the class does not occur in this scene).
 struct RouteJob { uint32_t n_slots; unsigned long long slot_map; uint32_t cls_of_slot[kRouteSlots]; uint32_t *buf[kRouteSlots]; uint32_t *error; uint32_t drop_cls; };   // slot_map: 4 bits per class, 15 = no queue; drop_cls: the one class whose entries are dropped on purpose (escaped rays when the film kernel ends the paths), any other class without a queue raises *error
 constexpr int kRouteQueueCap = 2048;   // k_route's LDS staging queues (entries)
-#ifndef PT_LDS_STACK
-#define PT_LDS_STACK 10
-#endif
 constexpr int kLdsStack = PT_LDS_STACK;       // traversal stack entries (2 words each) kept in LDS per lane; deeper entries spill to HBM. Triangle-only scenes: 10, so
                                               // that seven workgroups fit a CU's LDS; scenes with instances push a marker entry per instance entered and run five
                                               // waves per SIMD: 12 (C4 with 10: trace +2.3 %)
-#ifndef PT_LDS_STACK_GENERAL
-#define PT_LDS_STACK_GENERAL 12
-#endif
 constexpr int kLdsStackGeneral = PT_LDS_STACK_GENERAL;
 constexpr int kMaxStack = 64;       // the reference's stack size (accelerators/bvh.rs:722)
-#ifndef PT_LDS_STACK_QUAD
-#define PT_LDS_STACK_QUAD 15
-#endif
 constexpr int kLdsStackQuad = PT_LDS_STACK_QUAD;   // the four-wide walk (kern_trace.h, QUAD): up to three pushes per record; five waves per SIMD x 7 KB per wave of LDS
-#ifndef PT_LDS_STACK_QUAD_INST
-#define PT_LDS_STACK_QUAD_INST 19
-#endif
 constexpr int kLdsStackQuadInst = PT_LDS_STACK_QUAD_INST;   // the four-wide walk of scenes with instances (outer tree + marker + object tree on one stack): four waves per SIMD share a CU's LDS
 constexpr int kMaxStackQuad = 96;   // a reference tree of depth 64 collapses to 32 four-wide levels x 3 pushes
 constexpr int kLdsStackMinQuad = kLdsStackQuad < kLdsStackQuadInst ? kLdsStackQuad : kLdsStackQuadInst, kLdsStackMinTwo = kLdsStack < kLdsStackGeneral ? kLdsStack : kLdsStackGeneral;
 constexpr int kSpillEntries = (kMaxStackQuad - kLdsStackMinQuad) > (kMaxStack - kLdsStackMinTwo) ? (kMaxStackQuad - kLdsStackMinQuad) : (kMaxStack - kLdsStackMinTwo);   // per-lane HBM stack entries behind the LDS ones
 constexpr int kSpillWords = 2 * kSpillEntries + 8;   // per lane in the HBM slab of a wave: the stack entries behind the LDS ones, then the world-space ray of a lane inside an instance (six words; the four-wide walk of instanced scenes keeps it here, kern_trace.h)
 constexpr int kTraceBlock = 256;
-#ifndef PT_FILM_LANES
-#define PT_FILM_LANES 1
-#endif
-constexpr uint32_t kFilmLanes = PT_FILM_LANES;   // threads per pixel slot of the film kernels (kern_film.h: film_slot); a power of two <= 64. 1: measured best (profiles/r6/NOTES.md section 4)
 constexpr int kProbeRing = 8;       // k_trace<.., PROBE>: matching intersections of a BSSRDF probe chain kept per lane (3 x uint4 each)
 
 // path flags (meta >> 24)

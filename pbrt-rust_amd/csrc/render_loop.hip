@@ -2,19 +2,10 @@
 #include "host_common.h"
 #include <utility>
 
-// Blocks per CU of the persistent grids. Experiment hooks: tools/build_variant.sh overrides them with -D.
-#ifndef PT_SHADE_BLOCKS_PER_CU
-#define PT_SHADE_BLOCKS_PER_CU 24u   // each block walks a fixed stride of the queue: 24 a CU (2, 3 or 4 resident at a time) even out the per-vertex cost differences; 8 left the matte kernel's third round two-thirds full (80.1 -> 76.3 ms on C2)
-#endif
-#ifndef PT_GEN_BLOCKS_PER_CU
-#define PT_GEN_BLOCKS_PER_CU 40u     // 16 -> 40: k_generate 12.2 -> 11.7 ms on C2; the miss kernel does not care
-#endif
-#ifndef PT_ROUTE_BLOCKS_PER_CU
-#define PT_ROUTE_BLOCKS_PER_CU 3u    // what a CU's LDS holds of k_route (six 8 KB staging queues per block)
-#endif
-#ifndef PT_MISS_BLOCKS_PER_CU
-#define PT_MISS_BLOCKS_PER_CU 16u
-#endif
+// Blocks per CU of the persistent grids (knobs.h: PT_*_BLOCKS_PER_CU).
+//   k_shade 24: each block walks a fixed stride of the queue: 24 a CU (2, 3 or 4 resident at a time) even out the per-vertex cost differences; 8 left the matte kernel's third round two-thirds full (80.1 -> 76.3 ms on C2)
+//   k_generate 40: 16 -> 40: k_generate 12.2 -> 11.7 ms on C2; the miss kernel does not care
+//   k_route 3: what a CU's LDS holds of k_route (six 8 KB staging queues per block)
 
 namespace pth {
 #ifdef PT_TRACE_UTIL
@@ -339,10 +330,7 @@ __global__ void k_reset(QCounters *qc, uint32_t mask, int cur) {
 // in a tail of straggling rays (~0.8 ms on S2, whatever the launch size), so fewer, larger iterations spend less of the render in tails:
 // S2 at 1080p x 256 spp: 32 samples per pass 1267, 64: 1367, 128: 1439, 256: 1468 Msamples/s. `share` = renders that will hold a
 // workspace on this device at the same time (pt_multi_render with a device listed more than once).
-#ifndef PT_PASS_MAX_PATHS_LOG2
-#define PT_PASS_MAX_PATHS_LOG2 29   // round 3: 2^29 paths = 256 samples per pixel at 1080p in ONE pass (137 GB of path state + 39 GB of queues of the 288 GB): half the iterations of 2^28
-#endif
-constexpr size_t kPassMaxPaths = (size_t)1 << PT_PASS_MAX_PATHS_LOG2;
+constexpr size_t kPassMaxPaths = (size_t)1 << PT_PASS_MAX_PATHS_LOG2;   // (knobs.h) round 3: 2^29 paths = 256 samples per pixel at 1080p in ONE pass (137 GB of path state + 39 GB of queues of the 288 GB): half the iterations of 2^28
 constexpr double kPassMemFraction = 0.65;   // of the device's free memory
 uint32_t choose_pass_size(const pt_scene *sc, uint32_t n_pix_slots, uint32_t spp, uint32_t share, bool volpath) {
     // per path: the five state records, the queues, the probe state of scenes with subsurface materials and -- volpath through material-less shells -- the
@@ -587,7 +575,7 @@ int run_pass(pt_scene *sc, RenderConst &rc, const LightGrid &grid, bool rp_profi
         reset(8u);
     }
     sc->begin("film", total);
-    const dim3 fgrid((unsigned)(((size_t)rc.n_pix_slots * kFilmLanes + 255) / 256));   // kFilmLanes threads per pixel slot (kern_film.h)
+    const dim3 fgrid((unsigned)(((size_t)rc.n_pix_slots + 255) / 256));   // one thread per pixel slot (kern_film.h)
     if (it.fin) launch(sc, film_final_variant(general_geometry(sc)), fgrid, dim3(256), sc->ds, rc, sc->ps, sc->d_filter, sc->film_rgbw, sc->dc);
     else launch(sc, "k_film", k_film, fgrid, dim3(256), rc, sc->ps, sc->d_filter, sc->film_rgbw, sc->dc);
     sc->end();

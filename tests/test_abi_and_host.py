@@ -131,3 +131,37 @@ def test_scene_builder_mirrors_api_state_machine(pkg):
     b.filter.update(kind="gaussian", radius=(2.0, 2.0))
     rp = b.render_params()
     assert tuple(rp.sample_bounds) == (-2, -2, 1282, 722)  # film.rs:104-112
+
+
+def test_compile_time_switches_are_knobs_or_instrumentation():
+    """Every `#if` on a PT_* macro in the native sources is a tuning constant of knobs.h, one of the two instruments, a translation-unit selector
+    or a build setting: settled A/B experiments live as patches under profiles/rN/experiments/, not as switches in the product sources."""
+    import glob
+    root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "pbrt-rust_amd")
+    files = sorted(p for ext in ("h", "hip", "cpp") for p in glob.glob(os.path.join(root, "csrc", "*." + ext))) + sorted(glob.glob(os.path.join(root, "ao", "*")))
+    assert any(p.endswith("knobs.h") for p in files) and any(p.endswith("ao_render.hip") for p in files)
+    instruments = {"PT_TRACE_UTIL", "PT_REGION_PROFILE"}
+    tu_selectors = {"PT_TU_ANY", "PT_TU_QUAD", "PT_TU_MODE", "PT_TU_MAXL"}
+    build_settings = {"PT_TABLES_PATH", "PT_SAN"}
+    conditional = re.compile(r"^\s*#\s*(if|ifdef|ifndef|elif)\b(.*)$")
+    bad, n_util = [], 0
+    for path in files:
+        if not os.path.isfile(path):
+            continue
+        name = os.path.basename(path)
+        lines = open(path, errors="replace").read().split("\n")
+        for i, line in enumerate(lines):
+            m = conditional.match(line)
+            if not m:
+                continue
+            if name == "kern_trace.h" and re.match(r"^\s*#\s*ifdef\s+PT_TRACE_UTIL\b", line):
+                n_util += 1
+            macros = set(re.findall(r"\bPT_[A-Z0-9_]+\b", m.group(2).split("//")[0]))
+            if not macros or name == "knobs.h":
+                continue
+            guard = m.group(1) == "ifndef" and len(macros) == 1 and i + 1 < len(lines) and re.match(r"^\s*#\s*define\s+%s\s*$" % next(iter(macros)), lines[i + 1])
+            if guard or macros <= instruments or macros <= tu_selectors or macros <= build_settings:
+                continue
+            bad.append("%s:%d: %s" % (name, i + 1, line.strip()))
+    assert not bad, "compile-time switches outside knobs.h:\n" + "\n".join(bad)
+    assert n_util == 1, "kern_trace.h keeps its PT_TRACE_UTIL pieces in one block"
