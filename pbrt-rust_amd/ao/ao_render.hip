@@ -1,14 +1,15 @@
 // ao_render.hip -- pt_ao_render / pt_ao_render_samples / pt_ao_pass_size (include/mi355ao.h): the ambient-occlusion integrator (integrators/ao.rs) in the
 // render loop of SamplerIntegrator::render (integrator.rs:263-403). Per pass of s_count samples of every pixel slot:
-//   k_generate                     camera rays (libmi355pt; dimensions 0-4 of the sample)
+//   k_generate                     camera rays (libmi355pt's render_frame; dimensions 0-4 of the sample)
 //   k_trace<closest>               their hits ("extend_camera")
 //   per chunk of <= 64 AO rays per path:
 //     k_ao_rays                    the chunk's rays from each hit (dimensions 5 and 6 of sample numbers s * nsamples + k)
 //     k_trace<any>                 the rays' any-hit walk ("shadow": Scene::intersect_p, t_max = infinity)
 //     k_ao_accum                   L += the unoccluded rays' terms, in order
 //   k_film                         sanitise + splat (libmi355pt)
-// The scene, its workspace, the device counters and the traversal are libmi355pt's (host_common.h): this library adds the kernels
-// of ao_kernels.h and the buffers of the AO rays, which live for one call.
+// The scene, its workspace, the device counters, the traversal and the render frame -- the shared checks, the pass loop, the film's way out, the counters
+// (frame_geometry / render_frame, render_loop.hip) -- are libmi355pt's (host_common.h): this library adds AO's own checks and pass size (ao_geometry), one pass
+// (ao_pass), the kernels of ao_kernels.h and the buffers of the AO rays, which live for one call.
 #include "../csrc/host_common.h"
 #include "../../include/mi355ao.h"
 #include "ao_kernels.h"
@@ -25,22 +26,16 @@ constexpr size_t kAOPathBytes = (size_t)kPathBytes + 4 * (2 + 2 * kNumClasses + 
 
 struct Geometry { RenderConst rc; uint32_t S; uint32_t K; };
 
-// The checks of pt_render's render_geometry (render_loop.hip) and the AO parameters; the pass size.
+// The frame's checks (frame_geometry, libmi355pt) around AO's own: its parameters, the sample numbers its arrays use, its pass size and the rays of one launch.
 // `n_samples`: how many of the job's rp->spp samples per pixel the call renders (pt_ao_render_samples): it caps and divides the pass size only -- the array numbering
 // s * nsamples + k and its table-size check are the job's.
 int ao_geometry(pt_scene *sc, const PtRenderParams *rp, const PtAOParams *ao, uint32_t n_samples, Geometry &g) {
     if (!sc || !rp || !ao) return fail(PT_ERR_INVALID_ARG, "null argument");
     if (ao->nsamples == 0) return fail(PT_ERR_INVALID_ARG, "ambientocclusion: nsamples must be > 0");
-    if (rp->spp == 0) return fail(PT_ERR_INVALID_ARG, "spp must be > 0");
-    if (!(rp->filter_radius[0] > 0.0f) || !(rp->filter_radius[1] > 0.0f)) return fail(PT_ERR_INVALID_ARG, "filter radius must be > 0");
-    if (rp->tile_world > 1 && rp->tile_rank >= rp->tile_world) return fail(PT_ERR_INVALID_ARG, "tile_rank >= tile_world");
-    if (sc->device != g_device) { int bst = bind_device(sc->device); if (bst) return bst; }
     RenderConst &rc = g.rc;
     PtRenderParams p = *rp;
     p.integrator = PT_INTEGRATOR_PATH;   // (no medium, no volpath state)
-    fill_render_const(&p, rc);
-    if (rc.film_w == 0 || rc.film_h == 0 || rc.ntx == 0 || rc.nty == 0) return fail(PT_ERR_INVALID_ARG, "empty film or sample bounds");
-    if (rc.sobol.log2_resolution > 25) return fail(PT_ERR_INVALID_ARG, "sample bounds exceed the 2^25 Sobol' pixel grid");
+    if (int st = frame_geometry(sc, &p, rc)) return st;
     // The array values of a pixel are sample numbers 0 .. spp * nsamples - 1 (sampler.rs:288-302). Sobol': the global index of
     // sample number j is j << 2m plus the pixel's bits, and the generator matrices have 52 columns (lowdiscrepancy.rs:512-569).
     // Halton: index = offset + j * stride must fit in 64 bits (halton.rs:122-155).
@@ -51,29 +46,21 @@ int ao_geometry(pt_scene *sc, const PtRenderParams *rp, const PtAOParams *ao, ui
         return fail(PT_ERR_INVALID_ARG, "ambientocclusion: spp x nsamples = " + std::to_string(numbers) + " sample numbers per pixel exceed the 2^" +
                                          std::to_string(52 - 2 * rc.sobol.log2_resolution) + " the Sobol' tables serve at this resolution");
     }
-    const uint32_t ntiles = rc.ntx * rc.nty;
-    rc.n_tile_slots = rc.tile_rank < ntiles ? (ntiles - rc.tile_rank + rc.tile_world - 1) / rc.tile_world : 0;
-    rc.n_pix_slots = rc.n_tile_slots * 256u;
     g.K = std::min<uint32_t>(ao->nsamples, kAOChunk);
-    uint32_t S = 0;
-    if (rc.n_pix_slots > 0) {
-        S = rp->spp_per_pass;
+    uint32_t S = rp->spp_per_pass;
+    if (S == 0 && rc.n_pix_slots > 0) {
         const size_t per_path = kAOPathBytes + (size_t)g.K * kAORayBytes;
-        if (S == 0) {
-            size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
-            // (the scene's present workspace is freed before a larger one is allocated)
-            const size_t afford = (size_t)((double)(free_b + sc->capacity * (size_t)kPathBytes) * kAOMemFraction) / per_path;
-            const size_t paths = std::min(afford, kAOMaxRays / g.K);
-            S = (uint32_t)std::min<size_t>(n_samples, std::max<size_t>(1, paths / rc.n_pix_slots));
-            const uint32_t n_pass = (n_samples + S - 1) / S;
-            S = (n_samples + n_pass - 1) / n_pass;   // passes of equal size
-        }
-        S = std::min(S, n_samples);
-        if ((size_t)rc.n_pix_slots * S > ((size_t)1 << 31)) return fail(PT_ERR_INVALID_ARG, "pass too large: pixel slots x samples per pass > 2^31 paths (lower spp_per_pass)");
-        if ((size_t)rc.n_pix_slots * S * g.K > kAOMaxRays) return fail(PT_ERR_INVALID_ARG, "pass too large: paths x min(nsamples, 64) AO rays per launch > 2^31 (lower spp_per_pass)");
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
+        // (the scene's present workspace is freed before a larger one is allocated)
+        const size_t afford = (size_t)((double)(free_b + sc->capacity * (size_t)kPathBytes) * kAOMemFraction) / per_path;
+        const size_t paths = std::min(afford, kAOMaxRays / g.K);
+        S = (uint32_t)std::min<size_t>(n_samples, std::max<size_t>(1, paths / rc.n_pix_slots));
+        const uint32_t n_pass = (n_samples + S - 1) / S;
+        S = (n_samples + n_pass - 1) / n_pass;   // passes of equal size
     }
-    g.S = S;
+    if (int st = frame_pass_size(rc, S, n_samples, &g.S)) return st;
+    if ((size_t)rc.n_pix_slots * g.S * g.K > kAOMaxRays) return fail(PT_ERR_INVALID_ARG, "pass too large: paths x min(nsamples, 64) AO rays per launch > 2^31 (lower spp_per_pass)");
     return PT_OK;
 }
 
@@ -92,23 +79,10 @@ struct AOBuffers {
     }
 };
 
-int check_device_error(pt_scene *sc) {
-    uint32_t err = 0;
-    HIP_TRY(hipMemcpyAsync(&err, &sc->qc->error, 4, hipMemcpyDeviceToHost, sc->stream));
-    HIP_TRY(hipStreamSynchronize(sc->stream));
-    if (err) return fail((int)err, device_error_text(err));
-    return PT_OK;
-}
-
 int ao_pass(pt_scene *sc, const RenderConst &rc, const PtAOParams *ao, uint32_t K, AOBuffers &b) {
     const uint32_t total = rc.n_pix_slots * rc.s_count;
     QCounters *qc = sc->qc;
     const uint32_t blocks_cap = (uint32_t)g_num_cus * 16u;
-    HIP_TRY(hipMemsetAsync(qc, 0, offsetof(QCounters, error), sc->stream));
-    sc->begin("generate", total); sc->set_kernel("k_generate");
-    hipLaunchKernelGGL(k_generate, dim3(std::min<uint32_t>((total + 255) / 256, (uint32_t)g_num_cus * 40u)), dim3(256), 0, sc->stream, rc, g_tabs, sc->ps, sc->q.ext[0], &qc->ext[0], sc->dc);
-    sc->end();
-    HIP_TRY(hipGetLastError());
     TraceJob tj{};
     tj.spill = sc->spill; tj.error = &qc->error; tj.counters = sc->dc; tj.head = &qc->head[0];
     TraceSub cam{};   // camera rays -> hit records (Scene::intersect, ao.rs:72)
@@ -155,7 +129,8 @@ int ao_pass(pt_scene *sc, const RenderConst &rc, const PtAOParams *ao, uint32_t 
     hipLaunchKernelGGL(k_film, dim3((unsigned)(((size_t)rc.n_pix_slots + 255) / 256)), dim3(256), 0, sc->stream, rc, sc->ps, sc->d_filter, sc->film_rgbw, sc->dc);
     sc->end();
     HIP_TRY(hipGetLastError());
-    return check_device_error(sc);
+    QCounters h;
+    return sync_queue_counters(sc, h);   // (a status a kernel raised fails the call here)
 }
 
 }  // namespace
@@ -166,14 +141,14 @@ __attribute__((visibility("default"))) int pt_ao_pass_size(pt_scene *sc, const P
     if (!spp_per_pass) return fail(PT_ERR_INVALID_ARG, "null argument");
     Geometry g;
     if (int st = ao_geometry(sc, rp, ao, rp ? rp->spp : 0, g)) return st;
-    *spp_per_pass = g.S ? g.S : rp->spp;   // (a rank that owns no tile renders nothing: any size)
+    *spp_per_pass = reported_pass_size(g.S, rp);
     return PT_OK;
 }
 
 __attribute__((visibility("default"))) int pt_ao_render(pt_scene *sc, const PtRenderParams *rp, const PtAOParams *ao, float *film_xyzw, int film_is_device) {   // the whole job: [0, spp)
     if (!sc || !rp || !ao || !film_xyzw) return fail(PT_ERR_INVALID_ARG, "null argument");
     if (ao->nsamples == 0) return fail(PT_ERR_INVALID_ARG, "ambientocclusion: nsamples must be > 0");
-    if (rp->spp == 0) return fail(PT_ERR_INVALID_ARG, "spp must be > 0");
+    if (int st = check_spp(rp)) return st;
     return pt_ao_render_samples(sc, rp, ao, 0, rp->spp, film_xyzw, film_is_device);
 }
 
@@ -183,45 +158,14 @@ __attribute__((visibility("default"))) int pt_ao_render_samples(pt_scene *sc, co
     if (int rst = check_sample_range(rp, first, n_samples)) return rst;   // (before the device is touched)
     Geometry g;
     if (int gst = ao_geometry(sc, rp, ao, n_samples, g)) return gst;
-    RenderConst &rc = g.rc;
-    const size_t film_px = (size_t)rc.film_w * rc.film_h;
-    sc->profile = rp->profile != 0;
-    sc->drop_timings();
-    sc->stats.clear();
-    sc->counters = PtCounters{};
-    if (rc.n_pix_slots == 0) return PT_OK;
-    int st = PT_OK;
-    const size_t paths = (size_t)rc.n_pix_slots * g.S;
-    if ((st = ensure_workspace(sc, paths, film_px))) return st;
-    AOBuffers b;
-    if (hipError_t e = b.alloc(paths, paths * g.K); e != hipSuccess) { (void)hipGetLastError(); return fail(PT_ERR_OUT_OF_MEMORY, std::string("ambientocclusion rays: ") + hipGetErrorString(e)); }
-    HIP_TRY(hipMemcpyAsync(sc->d_filter, rp->filter_table, 256 * 4, hipMemcpyHostToDevice, sc->stream));
-    HIP_TRY(hipMemsetAsync(sc->film_rgbw, 0, film_px * 16, sc->stream));
-    HIP_TRY(hipMemsetAsync(sc->dc, 0, sizeof(DevCounters), sc->stream));
-    HIP_TRY(hipMemsetAsync(sc->qc, 0, sizeof(QCounters), sc->stream));
-    for (uint32_t s0 = first, end = first + n_samples; s0 < end; s0 += g.S) {
-        rc.s_begin = s0; rc.s_count = std::min(g.S, end - s0);
-        if ((st = ao_pass(sc, rc, ao, g.K, b))) return st;
-    }
-    float *dst = film_xyzw, *tmp = nullptr; DevTmp film_tmp;
-    if (!film_is_device) {
-        HIP_TRY(film_tmp.alloc(&tmp, film_px * 16));
-        HIP_TRY(hipMemsetAsync(tmp, 0, film_px * 16, sc->stream));
-        dst = tmp;
-    }
-    sc->begin("film_finish", film_px); sc->set_kernel("k_film_finish");
-    hipLaunchKernelGGL(k_film_finish, dim3((unsigned)((film_px + 255) / 256)), dim3(256), 0, sc->stream, sc->film_rgbw, dst, (uint32_t)film_px);
-    sc->end();
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(sc->stream));
-    if (!film_is_device) {
-        std::vector<float> host(film_px * 4);
-        HIP_TRY(hipMemcpy(host.data(), tmp, film_px * 16, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < film_px * 4; ++i) film_xyzw[i] += host[i];
-    }
-    sc->resolve_timings();
-    read_counters(sc);
-    return PT_OK;
+    AOBuffers b;   // (freed when the call returns, however it ends)
+    // (the steps cross as std::function, FrameStep: render_frame launches libmi355pt's k_generate / k_film_finish, so it is one function there, not a header template compiled here too)
+    auto prepare = [&]() {
+        const size_t paths = (size_t)g.rc.n_pix_slots * g.S;
+        if (hipError_t e = b.alloc(paths, paths * g.K); e != hipSuccess) { (void)hipGetLastError(); return fail(PT_ERR_OUT_OF_MEMORY, std::string("ambientocclusion rays: ") + hipGetErrorString(e)); }
+        return (int)PT_OK;
+    };
+    return render_frame(sc, rp, g.rc, g.S, first, n_samples, film_xyzw, film_is_device, prepare, [&]() { return ao_pass(sc, g.rc, ao, g.K, b); });
 }
 
 }  // extern "C"

@@ -2,7 +2,8 @@
 // handles, and the helpers that cross files. The driver used to be one file (capi.hip, 1 700 lines); it is split by what a reader looks for:
 //   host_device.hip   device binding per host thread, Sobol' / Halton tables, pt_init and the process-wide knobs
 //   scene_create.hip  pt_scene_create: validation, accelerators (host SAH / GPU HLBVH), two- and four-wide records, uploads, light records
-//   render_loop.hip   the wavefront scheduler: kernel variants and the shade-class table, workspace, light grids, launch_trace, run_pass and its steps, pt_render, counters and kernel stats
+//   render_loop.hip   the wavefront scheduler: kernel variants and the shade-class table, workspace, light grids, launch_trace, run_pass and its steps, counters and kernel stats;
+//                     the render frame every integrator's entry point goes through (frame_geometry, render_frame, deliver_film) and the path integrator's own: pt_render, pt_pass_size
 //   parity_api.hip    the entry points tests use to compare single stages with the oracle (rays, Sobol' / Halton samples, camera rays)
 //   multi_device.hip  pt_multi_*: one process driving several devices (one host thread + stream per replica, peer-copy film merge)
 //   film_tools.hip    pt_film_resolve_device / pt_film_halves_error: a film on the device resolved to rgb / 8-bit sRGB, and the convergence estimate of two half films
@@ -15,6 +16,7 @@
 #include <cstring>
 #include <atomic>
 #include <chrono>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -185,11 +187,23 @@ void dist1d(const std::vector<float> &func, std::vector<float> &cdf, float &func
 // render_loop.hip
 int launch_trace(pt_scene *sc, int any, TraceJob job, uint32_t n_upper, bool probe = false);
 const char *device_error_text(uint32_t code);
+int sync_queue_counters(pt_scene *sc, QCounters &h);
 int ensure_workspace(pt_scene *sc, size_t capacity, size_t film_px);
 int ensure_light_grid(pt_scene *sc, int requested, int &effective);
 void fill_render_const(const PtRenderParams *rp, RenderConst &rc);
 uint32_t choose_pass_size(const pt_scene *sc, uint32_t n_pix_slots, uint32_t spp, uint32_t share, bool volpath);
-int run_pass(pt_scene *sc, RenderConst &rc, const LightGrid &grid, bool rp_profile_exact, int max_iterations);
 void read_counters(pt_scene *sc);
+// The render frame: what pt_render_samples, pt_ao_render_samples (libmi355ao) and pt_multi_render_samples share. An integrator's geometry function is
+// frame_geometry, its own checks, its choice of a pass size, frame_pass_size -- and serves its render AND its pass-size query; its render is render_frame around its pass.
+using FrameStep = std::function<int()>;
+int check_spp(const PtRenderParams *rp);
 int check_sample_range(const PtRenderParams *rp, uint32_t first, uint32_t n);
+uint32_t tile_slots(const RenderConst &rc);
+int frame_geometry(pt_scene *sc, const PtRenderParams *rp, RenderConst &rc);
+int frame_pass_size(const RenderConst &rc, uint32_t S, uint32_t n_samples, uint32_t *S_out);
+inline uint32_t reported_pass_size(uint32_t S, const PtRenderParams *rp) { return S ? S : rp->spp; }   // (a rank that owns no tile renders nothing: any size)
+int render_frame(pt_scene *sc, const PtRenderParams *rp, RenderConst &rc, uint32_t S, uint32_t first, uint32_t n_samples, float *film_xyzw, int film_is_device,
+                 const FrameStep &prepare, const FrameStep &pass, const FrameStep &finish = nullptr);
+int deliver_film(pt_scene *sc, size_t film_px, float *film_xyzw, int film_is_device);
+int add_device_film(const float *d_film, size_t film_px, float *film_xyzw);
 }  // namespace pth

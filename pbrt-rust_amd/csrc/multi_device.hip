@@ -82,7 +82,7 @@ void pt_multi_scene_destroy(pt_multi_scene *ms) {
 
 int pt_multi_render(pt_multi_scene *ms, const PtRenderParams *rp, float *film_xyzw, int film_is_device) {   // the whole job: sample numbers [0, spp)
     if (!ms || !rp || !film_xyzw || ms->sc.empty()) return fail(PT_ERR_INVALID_ARG, "null argument");
-    if (rp->spp == 0) return fail(PT_ERR_INVALID_ARG, "spp must be > 0");
+    if (int st = check_spp(rp)) return st;
     return pt_multi_render_samples(ms, rp, 0, rp->spp, film_xyzw, film_is_device);
 }
 
@@ -116,7 +116,7 @@ int pt_multi_render_samples(pt_multi_scene *ms, const PtRenderParams *rp, uint32
             PtRenderParams p = *rp; RenderConst rc;
             pt_multi_tile_shard(rp->tile_rank, rp->tile_world, i, n, &p.tile_rank, &p.tile_world);
             fill_render_const(&p, rc);
-            const uint32_t ntiles = rc.ntx * rc.nty, slots = rc.tile_rank < ntiles ? (ntiles - rc.tile_rank + rc.tile_world - 1) / rc.tile_world * 256u : 0u;
+            const uint32_t slots = tile_slots(rc) * 256u;
             if (slots) pass_size[i] = choose_pass_size(ms->sc[i], slots, n_samples, share, rc.volpath != 0);
         }
     }
@@ -170,9 +170,7 @@ int pt_multi_render_samples(pt_multi_scene *ms, const PtRenderParams *rp, uint32
     } else {
         hipLaunchKernelGGL(k_film_sum, dim3(blocks), dim3(256), 0, s0->stream, fa, (float4 *)ms->film[0], 0, film_px);
         HIP_TRY(hipStreamSynchronize(s0->stream));
-        std::vector<float> host(film_px * 4);
-        HIP_TRY(hipMemcpy(host.data(), ms->film[0], film_px * 16, hipMemcpyDeviceToHost));
-        for (size_t k = 0; k < film_px * 4; ++k) film_xyzw[k] += host[k];
+        if ((st = add_device_film(ms->film[0], film_px, film_xyzw))) return st;
     }
     HIP_TRY(hipGetLastError());
     ms->merge_ms = ms_between(t_last, clk::now());

@@ -396,6 +396,13 @@ const char *device_error_text(uint32_t code) {
     default: return "error raised on the device";
     }
 }
+// The queue counters as the stream has left them; a status a kernel raised meanwhile fails the call (run_pass at the start of every iteration, libmi355ao after every pass)
+int sync_queue_counters(pt_scene *sc, QCounters &h) {
+    HIP_TRY(hipMemcpyAsync(&h, sc->qc, sizeof h, hipMemcpyDeviceToHost, sc->stream));
+    HIP_TRY(hipStreamSynchronize(sc->stream));
+    if (h.error) return fail((int)h.error, device_error_text(h.error));
+    return PT_OK;
+}
 
 // ---- one pass. An iteration consumes the queue set `cur` and fills the other one: trace, route, touch, probe, shade per class, reset (run_pass below). Its steps see it as
 // an Iter: the queue sizes the host read at its start, and what the pass fixed (fin: the film kernel ends the paths, there is no miss class).
@@ -528,13 +535,9 @@ static void shade_class(const Iter &it, int c, uint32_t n) {
     sc->end();
 }
 
-int run_pass(pt_scene *sc, RenderConst &rc, const LightGrid &grid, bool rp_profile_exact, int max_iterations) {
+static int run_pass(pt_scene *sc, RenderConst &rc, const LightGrid &grid, bool rp_profile_exact, int max_iterations) {
     const uint32_t total = rc.n_pix_slots * rc.s_count;
-    QCounters *qc = sc->qc;
-    HIP_TRY(hipMemsetAsync(qc, 0, offsetof(QCounters, error), sc->stream));
-    sc->begin("generate", total);
-    launch(sc, "k_generate", k_generate, blocks_for(total, PT_GEN_BLOCKS_PER_CU), dim3(256), rc, g_tabs, sc->ps, sc->q.ext[0], &qc->ext[0], sc->dc);
-    sc->end();
+    QCounters *qc = sc->qc;   // (render_frame has zeroed the queue counters and put the pass's camera rays into ext[0])
     // The plain path integrator's paths are ended by the film kernel (k_film_final, kern_aux.h): no miss class, no k_shade_miss pass. Volpath keeps the pass (its
     // transmittance estimates draw sampler dimensions in iteration order).
     Iter it{sc, rc, grid, g_film_final && !rc.volpath, rp_profile_exact};
@@ -543,9 +546,7 @@ int run_pass(pt_scene *sc, RenderConst &rc, const LightGrid &grid, bool rp_profi
     int st;
     for (it.index = 0, it.cur = 0; it.index <= max_iterations; ++it.index, it.cur = 1 - it.cur) {   // a path needs <= max_depth + null-surface skips + probe segments iterations
         QCounters h;
-        HIP_TRY(hipMemcpyAsync(&h, qc, sizeof h, hipMemcpyDeviceToHost, sc->stream));
-        HIP_TRY(hipStreamSynchronize(sc->stream));
-        if (h.error) return fail((int)h.error, device_error_text(h.error));
+        if ((st = sync_queue_counters(sc, h))) return st;
         if (it.index == max_iterations) return fail(PT_ERR_PROBE_CHAIN, "pass did not finish within " + std::to_string(max_iterations) + " wavefront iterations");
         const int cur = it.cur;
         if (debug_iter && it.index > 0 && it.index % 2048 == 0) {
@@ -628,10 +629,88 @@ void read_counters(pt_scene *sc) {
 #endif
 }
 
+// ---- the render frame (host_common.h): what every integrator's render does before, around and after its passes
+int check_spp(const PtRenderParams *rp) { return rp->spp == 0 ? fail(PT_ERR_INVALID_ARG, "spp must be > 0") : PT_OK; }
 // The range [first, first + n) of a job of rp->spp samples per pixel (pt_render_samples, pt_ao_render_samples, pt_multi_render_samples): host arithmetic, the sum in 64 bits
 int check_sample_range(const PtRenderParams *rp, uint32_t first, uint32_t n) {
     if (n == 0) return fail(PT_ERR_INVALID_ARG, "n_samples must be > 0");
     if ((uint64_t)first + n > rp->spp) return fail(PT_ERR_INVALID_ARG, "sample range [" + std::to_string(first) + ", " + std::to_string((uint64_t)first + n) + ") exceeds the job's spp = " + std::to_string(rp->spp));
+    return PT_OK;
+}
+// 16x16 tiles of rank rc.tile_rank among rc.tile_world (tile t belongs to rank t % world)
+uint32_t tile_slots(const RenderConst &rc) { const uint32_t ntiles = rc.ntx * rc.nty; return rc.tile_rank < ntiles ? (ntiles - rc.tile_rank + rc.tile_world - 1) / rc.tile_world : 0; }
+
+// What every render checks before it touches the device, the re-bind to the scene's device, and rc (incl. n_tile_slots / n_pix_slots; 0: this rank owns no tile)
+int frame_geometry(pt_scene *sc, const PtRenderParams *rp, RenderConst &rc) {
+    if (int st = check_spp(rp)) return st;
+    if (!(rp->filter_radius[0] > 0.0f) || !(rp->filter_radius[1] > 0.0f)) return fail(PT_ERR_INVALID_ARG, "filter radius must be > 0");
+    if (rp->tile_world > 1 && rp->tile_rank >= rp->tile_world) return fail(PT_ERR_INVALID_ARG, "tile_rank >= tile_world");
+    if (sc->device != g_device) { int bst = bind_device(sc->device); if (bst) return bst; }
+    fill_render_const(rp, rc);
+    if (rc.film_w == 0 || rc.film_h == 0 || rc.ntx == 0 || rc.nty == 0) return fail(PT_ERR_INVALID_ARG, "empty film or sample bounds");
+    if (rc.sobol.log2_resolution > 25) return fail(PT_ERR_INVALID_ARG, "sample bounds exceed the 2^25 Sobol' pixel grid");
+    rc.n_tile_slots = tile_slots(rc);
+    rc.n_pix_slots = rc.n_tile_slots * 256u;
+    return PT_OK;
+}
+// The pass size S an integrator asked for or chose, for a call that renders n_samples sample numbers: capped at them; 0 when this rank owns no tile
+int frame_pass_size(const RenderConst &rc, uint32_t S, uint32_t n_samples, uint32_t *S_out) {
+    S = rc.n_pix_slots ? std::min(S, n_samples) : 0;
+    if ((size_t)rc.n_pix_slots * S > ((size_t)1 << 31)) return fail(PT_ERR_INVALID_ARG, "pass too large: pixel slots x samples per pass > 2^31 paths (lower spp_per_pass)");
+    *S_out = S;
+    return PT_OK;
+}
+
+int add_device_film(const float *d_film, size_t film_px, float *film_xyzw) {   // host film += device film, element by element in index order
+    std::vector<float> host(film_px * 4);
+    HIP_TRY(hipMemcpy(host.data(), d_film, film_px * 16, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < film_px * 4; ++i) film_xyzw[i] += host[i];
+    return PT_OK;
+}
+// The film's way out: k_film_finish adds the render's sums (sc->film_rgbw) to the caller's device film, or to a zeroed temporary that is then added to the host film
+int deliver_film(pt_scene *sc, size_t film_px, float *film_xyzw, int film_is_device) {
+    float *dst = film_xyzw; DevTmp film_tmp;
+    if (!film_is_device) {
+        HIP_TRY(film_tmp.alloc(&dst, film_px * 16));
+        HIP_TRY(hipMemsetAsync(dst, 0, film_px * 16, sc->stream));
+    }
+    sc->begin("film_finish", film_px);
+    launch(sc, "k_film_finish", k_film_finish, dim3((unsigned)((film_px + 255) / 256)), dim3(256), sc->film_rgbw, dst, film_px);
+    sc->end();
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(sc->stream));
+    return film_is_device ? PT_OK : add_device_film(dst, film_px, film_xyzw);
+}
+
+// Sample numbers [first, first + n_samples) in passes of S, between the geometry function (rc, S) and the caller's film. `prepare`: what the integrator needs besides the
+// workspace; `pass`: the camera rays of rc.s_count samples from rc.s_begin, waiting in ext[0], to their splats in sc->film_rgbw; `finish`: what it checks after the
+// last one. A rank that owns no tile leaves zeroed counters and no stats.
+int render_frame(pt_scene *sc, const PtRenderParams *rp, RenderConst &rc, uint32_t S, uint32_t first, uint32_t n_samples, float *film_xyzw, int film_is_device,
+                 const FrameStep &prepare, const FrameStep &pass, const FrameStep &finish) {
+    const size_t film_px = (size_t)rc.film_w * rc.film_h;
+    sc->profile = rp->profile != 0;
+    sc->drop_timings();
+    sc->stats.clear();
+    sc->counters = PtCounters{};
+    if (rc.n_pix_slots == 0) return PT_OK;
+    int st;
+    if ((st = ensure_workspace(sc, (size_t)rc.n_pix_slots * S, film_px)) || (st = prepare())) return st;
+    HIP_TRY(hipMemcpyAsync(sc->d_filter, rp->filter_table, 256 * 4, hipMemcpyHostToDevice, sc->stream));
+    HIP_TRY(hipMemsetAsync(sc->film_rgbw, 0, film_px * 16, sc->stream));
+    HIP_TRY(hipMemsetAsync(sc->dc, 0, sizeof(DevCounters), sc->stream));
+    HIP_TRY(hipMemsetAsync(sc->qc, 0, sizeof(QCounters), sc->stream));
+    for (uint32_t s0 = first, end = first + n_samples; s0 < end; s0 += S) {
+        rc.s_begin = s0; rc.s_count = std::min(S, end - s0);
+        HIP_TRY(hipMemsetAsync(sc->qc, 0, offsetof(QCounters, error), sc->stream));
+        sc->begin("generate", (uint64_t)rc.n_pix_slots * rc.s_count);   // SamplerIntegrator::render's camera rays (integrator.rs:331-340): every integrator's pass starts from them
+        launch(sc, "k_generate", k_generate, blocks_for(rc.n_pix_slots * rc.s_count, PT_GEN_BLOCKS_PER_CU), dim3(256), rc, g_tabs, sc->ps, sc->q.ext[0], &sc->qc->ext[0], sc->dc);
+        sc->end();
+        if ((st = pass())) return st;
+    }
+    if (finish && (st = finish())) return st;
+    if ((st = deliver_film(sc, film_px, film_xyzw, film_is_device))) return st;
+    sc->resolve_timings();
+    read_counters(sc);
     return PT_OK;
 }
 
@@ -639,48 +718,33 @@ int check_sample_range(const PtRenderParams *rp, uint32_t first, uint32_t n) {
 
 extern "C" {
 
-// What pt_render checks before it touches the device and the pass size it then uses -- ONE function for pt_render and pt_pass_size, so that the size pt_pass_size
-// reports is the size of a render that would be accepted (the two had drifted apart). Fills rc (incl. n_tile_slots / n_pix_slots); *S = samples per pixel
-// per wavefront pass (0 when this rank owns no tile). `n_samples`: how many of the job's rp->spp sample numbers the call renders (pt_render_samples; rp->spp for pt_render and
-// pt_pass_size) -- the pass size is capped at it and the library's choice makes equal passes over it, while rc keeps the JOB's spp (rc.inv_sqrt_spp, the differential scale).
+// The path integrators' geometry -- ONE function for pt_render and pt_pass_size, so that the size pt_pass_size reports is the size of a render that would be accepted
+// (the two had drifted apart): the frame's checks, what path / volpath take, and *S_out = samples per pixel per wavefront pass (0 when this rank owns no tile).
+// `n_samples`: how many of the job's rp->spp sample numbers the call renders (pt_render_samples; rp->spp for pt_render and pt_pass_size) -- the pass size is capped at it and
+// the library's choice makes equal passes over it, while rc keeps the JOB's spp (rc.inv_sqrt_spp, the differential scale).
 static int render_geometry(pt_scene *sc, const PtRenderParams *rp, uint32_t n_samples, RenderConst &rc, uint32_t *S_out) {
-    if (rp->spp == 0) return fail(PT_ERR_INVALID_ARG, "spp must be > 0");
-    if (!(rp->filter_radius[0] > 0.0f) || !(rp->filter_radius[1] > 0.0f)) return fail(PT_ERR_INVALID_ARG, "filter radius must be > 0");
-    if (rp->tile_world > 1 && rp->tile_rank >= rp->tile_world) return fail(PT_ERR_INVALID_ARG, "tile_rank >= tile_world");
-    if (sc->device != g_device) { int bst = bind_device(sc->device); if (bst) return bst; }
-    fill_render_const(rp, rc);
-    if (rc.film_w == 0 || rc.film_h == 0 || rc.ntx == 0 || rc.nty == 0) return fail(PT_ERR_INVALID_ARG, "empty film or sample bounds");
-    if (rc.sobol.log2_resolution > 25) return fail(PT_ERR_INVALID_ARG, "sample bounds exceed the 2^25 Sobol' pixel grid");
+    if (int st = frame_geometry(sc, rp, rc)) return st;
     if (rp->max_depth > 254) return fail(PT_ERR_INVALID_ARG, "maxdepth must be <= 254 (the bounce count of a path is kept in 8 bits)");
     if (rc.volpath) {   // VolPathIntegrator (volpath.rs): what this back end takes
         if (sc->has_bssrdf && sc->ds.n_media >= 0xffffu) return fail(PT_ERR_UNSUPPORTED, "volpath: subsurface materials with more than 65534 media");
         if (rp->camera_medium != PT_NONE && rp->camera_medium >= sc->ds.n_media) return fail(PT_ERR_INVALID_ARG, "camera_medium out of range");
     }
-    const uint32_t ntiles = rc.ntx * rc.nty;
-    rc.n_tile_slots = rc.tile_rank < ntiles ? (ntiles - rc.tile_rank + rc.tile_world - 1) / rc.tile_world : 0;
-    rc.n_pix_slots = rc.n_tile_slots * 256u;
-    uint32_t S = 0;
-    if (rc.n_pix_slots > 0) {
-        S = rp->spp_per_pass;
-        if (S == 0) S = choose_pass_size(sc, rc.n_pix_slots, n_samples, 1, rc.volpath != 0);
-        S = std::min(S, n_samples);
-        if ((size_t)rc.n_pix_slots * S > ((size_t)1 << 31)) return fail(PT_ERR_INVALID_ARG, "pass too large: pixel slots x samples per pass > 2^31 paths (lower spp_per_pass)");
-    }
-    *S_out = S;
-    return PT_OK;
+    uint32_t S = rp->spp_per_pass;
+    if (S == 0 && rc.n_pix_slots > 0) S = choose_pass_size(sc, rc.n_pix_slots, n_samples, 1, rc.volpath != 0);
+    return frame_pass_size(rc, S, n_samples, S_out);
 }
 
 int pt_pass_size(pt_scene *sc, const PtRenderParams *rp, uint32_t *spp_per_pass) {
     if (!sc || !rp || !spp_per_pass) return fail(PT_ERR_INVALID_ARG, "null argument");
     RenderConst rc; uint32_t S = 0;
     if (int st = render_geometry(sc, rp, rp->spp, rc, &S)) return st;
-    *spp_per_pass = S ? S : rp->spp;   // (a rank that owns no tile renders nothing: any size)
+    *spp_per_pass = reported_pass_size(S, rp);
     return PT_OK;
 }
 
 int pt_render(pt_scene *sc, const PtRenderParams *rp, float *film_xyzw, int film_is_device) {   // the whole job: sample numbers [0, spp)
     if (!sc || !rp || !film_xyzw) return fail(PT_ERR_INVALID_ARG, "null argument");
-    if (rp->spp == 0) return fail(PT_ERR_INVALID_ARG, "spp must be > 0");
+    if (int st = check_spp(rp)) return st;
     return pt_render_samples(sc, rp, 0, rp->spp, film_xyzw, film_is_device);
 }
 
@@ -693,59 +757,32 @@ int pt_render_samples(pt_scene *sc, const PtRenderParams *rp, uint32_t first, ui
     if (int gst = render_geometry(sc, rp, n_samples, rc, &S)) return gst;
     int max_iterations = 1 << 20;   // wavefront iterations per pass. TEST HOOK (env PT_TEST_MAX_ITERATIONS, read at every call): a smaller cap, so that the PT_ERR_PROBE_CHAIN return of a pass that does not end can be tested
     if (const char *e = getenv("PT_TEST_MAX_ITERATIONS")) { const int v = atoi(e); if (v > 0) max_iterations = v; }
-    const size_t film_px = (size_t)rc.film_w * rc.film_h;
-    sc->profile = rp->profile != 0;
-    sc->drop_timings();
-    sc->stats.clear();
-    int st = PT_OK;
-    if (rc.n_pix_slots > 0) {
-        if ((st = ensure_workspace(sc, (size_t)rc.n_pix_slots * S, film_px))) return st;
+    int eff = 0;
+    auto lazy_grid = [&]() { return sc->grid[eff].cell_ptr != nullptr; };   // first-touch voxels (PT_LS_SPATIAL_LAZY)
+    auto prepare = [&]() {
         if (rc.volpath && sc->has_null_material && sc->ext_capacity < sc->capacity) {   // the shells' chain state (PathSoA::ext)
             if (sc->ext_slab) { hipFree(sc->ext_slab); sc->ext_slab = nullptr; sc->ext_capacity = 0; }
             if (hipMalloc(&sc->ext_slab, sc->capacity * (size_t)PathSoA::kExtWords * 4) != hipSuccess) { (void)hipGetLastError(); return fail(PT_ERR_OUT_OF_MEMORY, "volpath: chain state of material-less shells"); }
             sc->ext_capacity = sc->capacity;
         }
         sc->ps.ext = (rc.volpath && sc->has_null_material) ? (float *)sc->ext_slab : nullptr;
-        int eff;
-        if ((st = ensure_light_grid(sc, (int)rp->light_strategy, eff))) return st;
-        if (sc->grid[eff].cell_ptr) {   // first-touch voxels: a render that failed half way may have named voxels it never computed -- start from a clean request list
+        if (int st = ensure_light_grid(sc, (int)rp->light_strategy, eff)) return st;
+        if (lazy_grid()) {   // a render that failed half way may have named voxels it never computed -- start from a clean request list
             HIP_TRY(hipMemsetAsync(sc->lazy.req_flag, 0, sc->lazy.ncell * 4, sc->stream));
             HIP_TRY(hipMemsetAsync(sc->lazy.req_count, 0, 8, sc->stream));
         }
-        HIP_TRY(hipMemcpyAsync(sc->d_filter, rp->filter_table, 256 * 4, hipMemcpyHostToDevice, sc->stream));
-        HIP_TRY(hipMemsetAsync(sc->film_rgbw, 0, film_px * 16, sc->stream));
-        HIP_TRY(hipMemsetAsync(sc->dc, 0, sizeof(DevCounters), sc->stream));
-        HIP_TRY(hipMemsetAsync(sc->qc, 0, sizeof(QCounters), sc->stream));
-        for (uint32_t s0 = first, end = first + n_samples; s0 < end; s0 += S) {
-            rc.s_begin = s0; rc.s_count = std::min(S, end - s0);
-            if ((st = run_pass(sc, rc, sc->grid[eff], rp->profile >= 2, max_iterations))) return st;
-        }
-        if (sc->grid[eff].cell_ptr) {   // a vertex that looked up a voxel nobody had computed: cannot happen (k_light_touch names every voxel first)
-            uint32_t missing = 0;
-            HIP_TRY(hipMemcpyAsync(&missing, sc->lazy.missing, 4, hipMemcpyDeviceToHost, sc->stream));
-            HIP_TRY(hipStreamSynchronize(sc->stream));
-            if (missing) { HIP_TRY(hipMemset(sc->lazy.missing, 0, 4)); return fail(PT_ERR_HIP, "internal: " + std::to_string(missing) + " light-distribution lookups hit a voxel that had not been computed"); }
-        }
-        float *dst = film_xyzw, *tmp = nullptr; DevTmp film_tmp;
-        std::vector<float> host;
-        if (!film_is_device) {
-            HIP_TRY(film_tmp.alloc(&tmp, film_px * 16));
-            HIP_TRY(hipMemsetAsync(tmp, 0, film_px * 16, sc->stream));
-            dst = tmp;
-        }
-        sc->begin("film_finish", film_px);
-        launch(sc, "k_film_finish", k_film_finish, dim3((unsigned)((film_px + 255) / 256)), dim3(256), sc->film_rgbw, dst, film_px);
-        sc->end();
+        return (int)PT_OK;
+    };
+    auto pass = [&]() { return run_pass(sc, rc, sc->grid[eff], rp->profile >= 2, max_iterations); };
+    auto finish = [&]() {   // a vertex that looked up a voxel nobody had computed: cannot happen (k_light_touch names every voxel first)
+        uint32_t missing = 0;
+        if (!lazy_grid()) return (int)PT_OK;
+        HIP_TRY(hipMemcpyAsync(&missing, sc->lazy.missing, 4, hipMemcpyDeviceToHost, sc->stream));
         HIP_TRY(hipStreamSynchronize(sc->stream));
-        if (!film_is_device) {
-            host.resize(film_px * 4);
-            HIP_TRY(hipMemcpy(host.data(), tmp, film_px * 16, hipMemcpyDeviceToHost));
-            for (size_t i = 0; i < film_px * 4; ++i) film_xyzw[i] += host[i];
-        }
-        sc->resolve_timings();
-        read_counters(sc);
-    }
-    return PT_OK;
+        if (missing) { HIP_TRY(hipMemset(sc->lazy.missing, 0, 4)); return fail(PT_ERR_HIP, "internal: " + std::to_string(missing) + " light-distribution lookups hit a voxel that had not been computed"); }
+        return (int)PT_OK;
+    };
+    return render_frame(sc, rp, rc, S, first, n_samples, film_xyzw, film_is_device, prepare, pass, finish);
 }
 
 int pt_film_resolve(const float *xyzw, uint32_t n, float scale, float *rgb) {  // film.rs:217-258 (host arithmetic)

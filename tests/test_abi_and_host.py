@@ -165,3 +165,20 @@ def test_compile_time_switches_are_knobs_or_instrumentation():
             bad.append("%s:%d: %s" % (name, i + 1, line.strip()))
     assert not bad, "compile-time switches outside knobs.h:\n" + "\n".join(bad)
     assert n_util == 1, "kern_trace.h keeps its PT_TRACE_UTIL pieces in one block"
+
+
+def test_the_render_frame_is_written_once():
+    """pt_render_samples, pt_ao_render_samples and pt_multi_render_samples go through one frame (render_loop.hip: frame_geometry, render_frame, deliver_film): the tile-slot
+    formula stands once in the package's sources, and each shared refusal's text once in the two libraries' host code (the pt_render / pt_ao_render / pt_multi_render wrappers
+    refuse spp = 0 through check_spp, the function frame_geometry calls)."""
+    import glob
+    root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "pbrt-rust_amd")
+    sources = [p for ext in ("h", "hip", "cpp", "py") for p in glob.glob(os.path.join(root, "**", "*." + ext), recursive=True)]
+    host = sorted(glob.glob(os.path.join(root, "csrc", "*.hip")) + glob.glob(os.path.join(root, "ao", "*.hip")))
+    assert any(p.endswith("render_loop.hip") for p in host) and any(p.endswith("ao_render.hip") for p in host) and any(p.endswith("multi_device.hip") for p in host)
+    count = lambda files, text: sum(open(p, errors="replace").read().count(text) for p in files)
+    assert count(sources, "(ntiles - rc.tile_rank + rc.tile_world - 1) / rc.tile_world") == 1
+    for phrase in ('"spp must be > 0"', '"filter radius must be > 0"', '"tile_rank >= tile_world"'):
+        assert count(host, phrase) == 1, phrase
+    for wrapper in ("render_loop.hip", "ao_render.hip", "multi_device.hip"):
+        assert count([p for p in host if p.endswith(wrapper)], "check_spp(rp)") >= 1, wrapper

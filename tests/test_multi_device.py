@@ -72,6 +72,20 @@ def test_three_replicas_on_one_device_equal_the_plain_render(pkg, gpu, scene):
 
 
 @pytest.mark.gpu
+def test_two_replicas_add_to_a_host_film_that_holds_something(pkg, gpu):
+    """The host form ADDS: a film pre-filled with a constant comes back as the constant plus the plain render, element by element, and the counters are the replicas'
+    sum. spp_per_pass = 0: replicas that share a device have their pass sizes chosen from their tile shares before either allocates."""
+    sd, rp = pkg.scenes.ganesha_scale(n=24, xres=64, yres=48, spp=4).world_end()
+    assert rp.spp_per_pass == 0
+    single = pkg.Scene(gpu, sd)
+    ref = single.render(rp); rc = single.counters()
+    multi = pkg.MultiScene(gpu, sd, [0, 0])
+    film = multi.render(rp, film=np.full(ref.shape, 3.0, np.float32))
+    assert_same_render(film, np.float32(3.0) + ref, multi.counters(), rc)
+    assert all(len(multi.kernel_stats(i)) > 0 for i in (0, 1))
+
+
+@pytest.mark.gpu
 def test_eight_replicas_and_two_film_sizes_on_one_multiscene(pkg, gpu):
     """The 8-way merge (one sum kernel over eight films, integrator.rs:392-396) and a pt_multi_scene rendered at a small, then a larger,
     then the small film size again (the landing / replica buffers follow the film size instead of keeping the first one)."""

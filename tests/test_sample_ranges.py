@@ -102,3 +102,55 @@ def test_bad_ranges_are_refused_and_leave_the_film_alone(pkg, gpu, first, n):
     ao = pkg._abi_ao.PtAOParams(4, 1)
     assert gpu.ao.pt_ao_render_samples(g.h, C.byref(rp), C.byref(ao), first, n, ptr, 0) == A.PT_ERR_INVALID_ARG
     assert (film == 7.0).all()
+
+
+def _all_zero(counters):
+    return all(not np.any(v) for v in counters.values())
+
+
+def test_a_rank_that_owns_no_tile_renders_nothing_and_reports_nothing(pkg, gpu, oracle):
+    """32x16 pixels under the box filter are two 16x16 tiles: rank 3 of 4 owns none. Either integrator's call returns PT_OK (render() raises otherwise), adds nothing to the
+    film and leaves zeroed counters and no launches behind -- not those of the render before it --, and the handle renders on as before."""
+    AO = pkg._abi_ao
+    sd, rp = range_scene(pkg, xres=32, yres=16)
+    sb = rp.sample_bounds
+    assert -(-(sb[2] - sb[0]) // 16) * -(-(sb[3] - sb[1]) // 16) == 2
+    g = pkg.Scene(gpu, sd); orc = oracle.scene(sd)
+    ref = orc.render(rp, nthreads=ORACLE_THREADS); oc = orc.counters()
+    for integrator in (rp.integrator, AO.PT_INTEGRATOR_AO):
+        assert_same_render(g.render(rp), ref, g.counters(), oc)   # a normal render: counters and stats to go stale
+        assert sum(s["launches"] for s in g.kernel_stats()) > 0
+        path = rp.integrator
+        rp.tile_world, rp.tile_rank, rp.integrator = 4, 3, integrator
+        film = g.render(rp, film=np.full((16, 32, 4), 7.0, np.float32), ao=AO.PtAOParams(4, 1))
+        assert (film == 7.0).all()
+        assert _all_zero(g.counters()), g.counters()
+        assert sum(s["launches"] for s in g.kernel_stats()) == 0, g.kernel_stats()
+        rp.tile_world, rp.tile_rank, rp.integrator = 1, 0, path
+    assert_same_render(g.render(rp), ref, g.counters(), oc)
+
+
+@pytest.mark.parametrize("samples", [None, (2, 5)])
+@pytest.mark.parametrize("spp_per_pass", [0, 3])
+@pytest.mark.parametrize("integrator", ["path", "ao"])
+def test_pass_size_is_the_size_of_the_passes_of_the_render_that_follows(pkg, gpu, integrator, spp_per_pass, samples):
+    """pt_pass_size / pt_ao_pass_size answer from the function their render takes its geometry from: what they report for the job -- capped at the length of a range -- is
+    the samples per `generate` launch (one launch per pass; the last pass may be ragged, so: n over the launches, rounded up) of the render that follows."""
+    AO = pkg._abi_ao
+    sd, rp = range_scene(pkg, xres=32, yres=16, spp_per_pass=spp_per_pass)
+    assert rp.spp == 8
+    g = pkg.Scene(gpu, sd)
+    if integrator == "ao":
+        rp.integrator = AO.PT_INTEGRATOR_AO
+        size = g.ao_pass_size(rp, AO.PtAOParams(4, 1))
+    else:
+        size = g.pass_size(rp)
+    n = rp.spp if samples is None else samples[1]
+    want = min(size, n)
+    print("pass size", size, "samples of the call", n)
+    assert size == spp_per_pass or (spp_per_pass == 0 and 1 <= size <= rp.spp)
+    g.render(rp, ao=AO.PtAOParams(4, 1), samples=samples)
+    gen = [s for s in g.kernel_stats() if s["name"] == "generate"][0]
+    print("generate launches", gen["launches"], "items", gen["items"])
+    assert gen["launches"] == -(-n // want) and -(-n // gen["launches"]) == want
+    assert gen["items"] == 2 * 256 * n   # two tiles of 256 pixel slots, every sample of the call once
