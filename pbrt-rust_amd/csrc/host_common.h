@@ -1,7 +1,9 @@
 // host_common.h -- what the host driver's translation units share: the library's process / thread state, the scene objects behind the C ABI's opaque
 // handles, and the helpers that cross files. The driver used to be one file (capi.hip, 1 700 lines); it is split by what a reader looks for:
 //   host_device.hip   device binding per host thread, Sobol' / Halton tables, pt_init and the process-wide knobs
-//   scene_create.hip  pt_scene_create: validation, accelerators (host SAH / GPU HLBVH), two- and four-wide records, uploads, light records
+//   scene_plan.hip    the host-only half of pt_scene_create (scene_plan.h; no HIP call, none of the globals below): plan_validate, every refusal of a PtSceneDesc;
+//                     plan_build, accelerators and every derived table (two- and four-wide records, packet order, shade classes, texture programs, env distribution)
+//   scene_create.hip  pt_scene_create: plan_validate, ensure_device, plan_build (host SAH / GPU HLBVH), uploads, the record / packet pool, light records
 //   render_loop.hip   the wavefront scheduler: kernel variants and the shade-class table, workspace, light grids, launch_trace, run_pass and its steps, counters and kernel stats;
 //                     the render frame every integrator's entry point goes through (frame_geometry, render_frame, deliver_film) and the path integrator's own: pt_render, pt_pass_size
 //   parity_api.hip    the entry points tests use to compare single stages with the oracle (rays, Sobol' / Halton samples, camera rays)
@@ -23,6 +25,7 @@
 #include <vector>
 #include "kern_decl.h"   // kernel declarations; the definitions are instantiated by the tu_*.hip translation units
 #include "host_bvh.h"
+#include "scene_plan.h"   // material_class, dist1d, the scene plan
 
 namespace pth {
 
@@ -81,8 +84,8 @@ struct pt_scene {
     std::vector<uint32_t> ordered;
     bool pool_big = false;          // four-wide records + packets beyond 4 GB: k_trace<.., 2> (64-bit addresses)
     bool quad_walk_only = false;    // more than 2^25 two-wide records or packets: the scene has no exact (two-wide) walk, pt_set_trace_exact(1) renders are refused
-    bool exact_walk_only = false;   // an adopted top-level tree whose child boxes do not nest: the two-wide walk tests every box like the reference (scene_create.hip)
-    bool class_used[kNumClasses] = {true, false, false, false, true, false, false, false, false, false, false};   // shade classes the scene's materials map to (kernels.h: kNumClasses; scene_create.hip: material_class)
+    bool exact_walk_only = false;   // an adopted top-level tree whose child boxes do not nest: the two-wide walk tests every box like the reference (scene_plan.hip)
+    bool class_used[kNumClasses] = {true, false, false, false, true, false, false, false, false, false, false};   // shade classes the scene's materials map to (kernels.h: kNumClasses; scene_plan.hip: material_class)
     bool has_null_material = false;   // a primitive without a material: a medium-interface shell (api.rs:597). The path integrator steps over it (path.rs:124-129);
                                       // the volumetric one also walks its shadow / MIS rays through it, segment by segment (kern_shade_common.h: vol_chain_step)
     void *ext_slab = nullptr; size_t ext_capacity = 0;   // PathSoA::ext, allocated for volpath renders of scenes with shells
@@ -181,9 +184,6 @@ struct pt_multi_scene {
 namespace pth {
 // every launch of the render stream: the symbol goes to the launch kind opened by the last begin()
 template <class... P, class... A> void launch(pt_scene *sc, const std::string &name, void (*fn)(P...), dim3 blocks, dim3 threads, const A &...args) { sc->set_kernel(name); hipLaunchKernelGGL(fn, blocks, threads, 0, sc->stream, static_cast<P>(args)...); }
-// scene_create.hip
-uint8_t material_class(const PtMaterial &m, bool specialise, bool untextured);
-void dist1d(const std::vector<float> &func, std::vector<float> &cdf, float &func_int);
 // render_loop.hip
 int launch_trace(pt_scene *sc, int any, TraceJob job, uint32_t n_upper, bool probe = false);
 const char *device_error_text(uint32_t code);

@@ -371,7 +371,7 @@ __global__ void k_camera_rays(RenderConst rc, uint32_t n, const float *cs, float
     out_d[3 * i] = d.x; out_d[3 * i + 1] = d.y; out_d[3 * i + 2] = d.z;
 }
 // Parity entry (pt_dist1d_sample): the device's Distribution1D -- dist_sample_continuous (the environment map's rows and marginal, sampling.rs:38-64) or
-// dist_sample_discrete (the light choice, sampling.rs:66-85) -- on a distribution the host built with Distribution1D::new (scene_create.hip: dist1d).
+// dist_sample_discrete (the light choice, sampling.rs:66-85) -- on a distribution the host built with Distribution1D::new (scene_plan.hip: dist1d).
 __global__ void k_dist1d_sample(const float *func, const float *cdf, float func_int, int n, int discrete, uint32_t n_u, const float *u, float *out_x, float *out_pdf, int32_t *out_off) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_u) return;

@@ -1,4 +1,4 @@
-// kernels.h -- shared declarations between the HIP kernels (kern_*.h, instantiated by the tu_*.hip translation units) and the host driver (host_common.h: scene_create.hip, render_loop.hip, ...).
+// kernels.h -- shared declarations between the HIP kernels (kern_*.h, instantiated by the tu_*.hip translation units) and the host driver (host_common.h: scene_plan.hip, scene_create.hip, render_loop.hip, ...).
 #pragma once
 #include "knobs.h"
 #include <cstddef>
@@ -18,7 +18,7 @@ constexpr int kNumClasses = 11;     // material-sorted shade queues, one per sha
 //       // material in a scene no longer sends every metal / plastic / uber vertex back to the general kernel of its lobe count):
 //       // 7 metal (k_shade<1, ., 3>), 8 plastic-like: plastic and the opaque uber without specular terms (k_shade<2, ., 4>), 9 uber (k_shade<5, ., 5>),
 //       // 10 smooth subsurface (k_shade<1, ., 6>). Classes 7-9 are handed out in textured scenes too (round 6: a texture changes a material's parameters, not its lobe set),
-//       // class 10 in untextured scenes only (material_class(), scene_create.hip); the volumetric router folds all four back (class_general).
+//       // class 10 in untextured scenes only (material_class(), scene_plan.hip); the volumetric router folds all four back (class_general).
 constexpr int kMissClass = 4, kMediumClass = 5, kSpecClass = 6, kMetalClass = 7, kPlasticClass = 8, kUberClass = 9, kSssClass = 10;
 PT_HD uint32_t class_general(uint32_t c) { return c == (uint32_t)kMetalClass ? 1u : c == (uint32_t)kPlasticClass ? 2u : (c == (uint32_t)kUberClass || c == (uint32_t)kSssClass) ? 3u : c; }
 constexpr int kRouteSlots = 12;        // most staging queues a k_route block holds

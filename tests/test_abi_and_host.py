@@ -113,6 +113,21 @@ def test_host_sah_builder_equals_oracle_builder(pkg, oracle):
             assert all(x.n_prims <= 4 or True for x in leaves)
 
 
+def test_scene_plan_on_the_cpu(pkg, tmp_path):
+    """The host-only half of pt_scene_create (csrc/scene_plan.h) checked without a device: tests/scene_plan/check_plan.cpp, a program of its own built from the
+    plan unit and the SAH builder, provokes every refusal a toy scene can reach (and counts the refusal texts of scene_plan.hip against its table), holds the
+    two- and four-wide records of small trees against their binary nodes for all eight sign octants, and recomputes the derived tables. It passes when it exits 0."""
+    import subprocess
+    here = os.path.dirname(pkg.runtime.LIB_PATH)
+    root = os.path.dirname(os.path.abspath(__file__))
+    exe = str(tmp_path / "check_plan")
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    subprocess.check_call([hipcc, "-x", "hip", "--offload-host-only", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-pthread", "-I", here, "-o", exe,
+                           os.path.join(root, "scene_plan", "check_plan.cpp"), os.path.join(here, "scene_plan.hip"), os.path.join(here, "host_bvh.cpp")])
+    r = subprocess.run([exe, os.path.join(here, "scene_plan.hip")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-2000:]
+
+
 def test_scene_builder_mirrors_api_state_machine(pkg):
     b = pkg.host.SceneBuilder()
     assert b.materials[0].type == pkg._abi.PT_MAT_MATTE and tuple(b.materials[0].kd) == (0.5, 0.5, 0.5)  # api.rs:345-361
