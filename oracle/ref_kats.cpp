@@ -321,7 +321,7 @@ int orc_bsdf_eval(orc_scene *h, uint32_t mi, uint32_t n, const float *wo, const 
     si.dpdu = V3(1, 0, 0); si.dpdv = V3(0, 1, 0); si.sh_dpdu = V3(1, 0, 0); si.sh_dpdv = V3(0, 1, 0);
     si.uv = P2(0.5f, 0.5f); si.has_shape = false; si.shape_flip = false; si.prim = 0;
     BSDF bsdf;
-    if (!material_scattering_functions(h->scene, mi, si, bsdf, nullptr, nullptr, nullptr)) return 2;
+    if (!scattering_functions_of(h->scene, mi, si, bsdf, nullptr, nullptr, nullptr)) return 2;   // (mix materials included)
     if (n_lobes_out) *n_lobes_out = bsdf.n;
     for (uint32_t i = 0; i < n; ++i) {
         const V3 o(wo[3 * i], wo[3 * i + 1], wo[3 * i + 2]);

@@ -67,10 +67,8 @@ static void bump_shading(const Scene &scene, int d, const TexCtx &ctx, SurfaceIn
     si.sh_dpdu = dpdu; si.sh_dpdv = dpdv;
 }
 
-static bool compute_scattering_functions(const Scene &scene, SurfaceInteraction &si, BSDF &bsdf,
-                                         TabulatedBSSRDF *bssrdf = nullptr, bool *has_bssrdf = nullptr, const TexCtx *tctx = nullptr) {
-    uint32_t mi = scene.prim_material[si.prim];
-    if (mi == PT_NONE) return false;  // primitive.rs:168-170: no material => no bsdf
+// Material::compute_scattering_functions of material `mi`, MixMaterial included (material_scattering_functions: the plain materials).
+bool scattering_functions_of(const Scene &scene, uint32_t mi, SurfaceInteraction &si, BSDF &bsdf, TabulatedBSSRDF *bssrdf, bool *has_bssrdf, const TexCtx *tctx) {
     const PtMaterial &m = scene.materials[mi];
     if (m.type == PT_MAT_MIX) {   // MixMaterial::compute_scattering_functions (mix.rs:25-50)
         const MatEval E{scene, m, tctx};
@@ -87,6 +85,12 @@ static bool compute_scattering_functions(const Scene &scene, SurfaceInteraction 
         return true;
     }
     return material_scattering_functions(scene, mi, si, bsdf, bssrdf, has_bssrdf, tctx);
+}
+static bool compute_scattering_functions(const Scene &scene, SurfaceInteraction &si, BSDF &bsdf,
+                                         TabulatedBSSRDF *bssrdf = nullptr, bool *has_bssrdf = nullptr, const TexCtx *tctx = nullptr) {
+    uint32_t mi = scene.prim_material[si.prim];
+    if (mi == PT_NONE) return false;  // primitive.rs:168-170: no material => no bsdf
+    return scattering_functions_of(scene, mi, si, bsdf, bssrdf, has_bssrdf, tctx);
 }
 bool material_scattering_functions(const Scene &scene, uint32_t mi, SurfaceInteraction &si, BSDF &bsdf,
                                    TabulatedBSSRDF *bssrdf, bool *has_bssrdf, const TexCtx *tctx) {

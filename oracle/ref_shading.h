@@ -326,6 +326,8 @@ struct TabulatedBSSRDF; struct TexCtx;   // ref_bssrdf.h, ref_texture.h
 // ref_render.cpp. Returns false when the material leaves `si.bsdf == None` (null surface, path.rs:124-129).
 bool material_scattering_functions(const Scene &scene, uint32_t mi, SurfaceInteraction &si, BSDF &bsdf,
                                    TabulatedBSSRDF *bssrdf, bool *has_bssrdf, const TexCtx *tctx);
+// the same for any material: a MixMaterial's two BSDFs in one, scaled (mix.rs:25-50), else material_scattering_functions
+bool scattering_functions_of(const Scene &scene, uint32_t mi, SurfaceInteraction &si, BSDF &bsdf, TabulatedBSSRDF *bssrdf, bool *has_bssrdf, const TexCtx *tctx);
 inline Float phase_hg(Float cos_theta, Float g) {   // medium.rs:149-154
     Float denom = 1.0f + g * g + 2.0f * g * cos_theta;
     return INV4_PI * (1.0f - g * g) / (denom * std::sqrt(denom));
