@@ -499,6 +499,30 @@ int pt_film_resolve_device(pt_scene *scene, const float *film_xyzw_dev, uint32_t
 int pt_film_halves_error(pt_scene *scene, const float *film_a_dev, const float *film_b_dev, uint32_t width, uint32_t height,
                          float *tile_error_dev, float *mean_error_host, float *max_tile_error_host);
 
+/* ---- adaptive sampling: renders of listed tiles and the selection of the tiles that go on. No reference counterpart (the reference renders every tile to the job's spp).
+ * TWO tile grids are involved. A render's tiles are the 16x16 blocks of params->sample_bounds, row major -- the grid tile_rank / tile_world index, integrator.rs:277-279; the
+ * tile lists below hold indices into it. The tile errors of pt_film_halves_error are over the 16x16 blocks of the cropped FILM. The grids coincide for filter radii <= 0.5
+ * only (sample_bounds is the crop grown by the radius); pt_tiles_select maps one onto the other through a tile's film footprint (after Film::get_film_tile, film.rs:125-140). */
+/* ntx, nty of the render's 16x16 sample-tile grid (the grid tile_rank / tile_world index). Host arithmetic, no device. */
+int pt_tile_grid(const PtRenderParams *params, uint32_t *ntx, uint32_t *nty);
+/* pt_render_samples on the listed tiles only. tiles: host array, strictly ascending, every entry < ntx*nty.
+ * params->tile_world must be 0 or 1 (the list replaces the shard rule). A list that is not ascending, repeats a tile (the film kernel keeps a thread's own pixel in
+ * registers: a tile rendered twice in one call would lose samples), names a tile outside the grid or is NULL with n_tiles > 0: PT_ERR_INVALID_ARG before the device is
+ * touched, the film unmodified. n_tiles == 0 is PT_OK: nothing is launched, the film is untouched and the counters are zero, as for a rank that owns no tile -- the natural
+ * end of an adaptive loop. Renders of disjoint lists whose union is the grid add up to the range's film, and their counters to its counters. Pass sizing, pt_get_counters
+ * and pt_get_kernel_stats describe the call, as for a range. */
+int pt_render_tiles(pt_scene *scene, const PtRenderParams *params, uint32_t first_sample, uint32_t n_samples,
+                    const uint32_t *tiles, uint32_t n_tiles, float *film_xyzw, int film_is_device);
+/* Of `candidates` (host, strictly ascending; NULL = every tile of the grid, n_candidates ignored) those whose footprint meets a film tile with
+ * error > threshold. tile_error_dev is what pt_film_halves_error wrote for a film of params' cropped size.
+ * tiles_out: host, room for the candidates; *n_out the number selected. A tile's footprint is every film pixel whose filter support overlaps the tile's area, clipped to the
+ * crop: Film::get_film_tile without the pixels whose support only touches the tile's edge, which none but a sample exactly on that edge reaches -- under the box filter of
+ * radius 0.5 the footprint is the tile itself. The tile is selected iff !(e <= threshold) for the error e of any film tile the footprint intersects (a NaN error keeps the
+ * tile; an empty footprint never does): an unconverged film tile keeps receiving ALL the samples that reach it. The selection keeps the candidates' order and is
+ * deterministic (no atomics). Blocking; launch kind "tiles_select". */
+int pt_tiles_select(pt_scene *scene, const PtRenderParams *params, const float *tile_error_dev, float threshold,
+                    const uint32_t *candidates, uint32_t n_candidates, uint32_t *tiles_out, uint32_t *n_out);
+
 /* One process, several GPUs -- the shape of the reference itself: ONE process fans the 16x16 tiles out over its workers
  * (core/integrator.rs:294-296, rayon) and merges them into one Film (integrator.rs:392-396). pt_multi_scene_create replicates the
  * scene on every listed device (an ordinal may repeat: the replicas then share that device); pt_multi_render renders, on one

@@ -160,6 +160,9 @@ ENTRY_POINTS = {
     "pt_render": (C.c_int, [VP, C.POINTER(PtRenderParams), VP, C.c_int]),
     "pt_render_samples": (C.c_int, [VP, C.POINTER(PtRenderParams), u32, u32, VP, C.c_int]),
     "pt_pass_size": (C.c_int, [VP, C.POINTER(PtRenderParams), u32p]),
+    "pt_tile_grid": (C.c_int, [C.POINTER(PtRenderParams), u32p, u32p]),
+    "pt_render_tiles": (C.c_int, [VP, C.POINTER(PtRenderParams), u32, u32, u32p, u32, VP, C.c_int]),
+    "pt_tiles_select": (C.c_int, [VP, C.POINTER(PtRenderParams), VP, f32, u32p, u32, u32p, u32p]),
     "pt_film_resolve": (C.c_int, [fp, u32, f32, fp]),
     "pt_film_resolve_device": (C.c_int, [VP, VP, u32, f32, VP, VP]),
     "pt_film_halves_error": (C.c_int, [VP, VP, VP, u32, u32, VP, fp, fp]),

@@ -1,6 +1,6 @@
-// film_tools.hip -- pt_film_resolve_device / pt_film_halves_error: the device film tools (kern_preview.h) behind the C ABI (host_common.h has the map).
+// film_tools.hip -- pt_film_resolve_device / pt_film_halves_error / pt_tiles_select: the device film tools (kern_preview.h) behind the C ABI (host_common.h has the map).
 // They run on the scene's stream through the render's begin() / launch() / end() bookkeeping and ADD their launch kinds ("film_resolve", "film_halves_error",
-// "film_error_reduce") to the kernel statistics of the last render; the counters are not touched.
+// "film_error_reduce", "tiles_select") to the kernel statistics of the last render; the counters are not touched.
 #include "host_common.h"
 
 namespace {
@@ -53,6 +53,34 @@ int pt_film_halves_error(pt_scene *sc, const float *film_a_dev, const float *fil
     if (int st = film_tool_end(sc)) return st;
     if (mean_error_host) *mean_error_host = h[0];
     if (max_tile_error_host) *max_tile_error_host = h[1];
+    return PT_OK;
+}
+
+// The candidates whose film footprint meets a film tile with error > threshold (k_tiles_select), in the candidates' order. The count and the list come back in one copy.
+int pt_tiles_select(pt_scene *sc, const PtRenderParams *rp, const float *tile_error_dev, float threshold, const uint32_t *candidates, uint32_t n_candidates, uint32_t *tiles_out, uint32_t *n_out) {
+    if (!sc || !rp || !tile_error_dev || !tiles_out || !n_out) return fail(PT_ERR_INVALID_ARG, "null argument");
+    uint32_t ntx = 0, nty = 0; tile_grid(rp, &ntx, &nty);
+    const uint64_t n_grid = (uint64_t)ntx * nty;
+    if (n_grid > (1ull << 31)) return fail(PT_ERR_INVALID_ARG, "pt_tiles_select: more than 2^31 tiles");
+    if (candidates) { if (int lst = check_tile_list(candidates, n_candidates, n_grid, "pt_tiles_select")) return lst; }   // (before the device is touched)
+    const uint32_t n = candidates ? n_candidates : (uint32_t)n_grid;
+    RenderConst rc;
+    if (int st = frame_geometry(sc, rp, rc)) return st;
+    *n_out = 0;
+    if (n == 0) return PT_OK;
+    if (int st = film_tool_begin(sc)) return st;
+    DevTmp tmp; uint32_t *cand = nullptr, *out = nullptr;
+    if ((candidates && tmp.alloc(&cand, (size_t)n * 4) != hipSuccess) || tmp.alloc(&out, ((size_t)n + 1) * 4) != hipSuccess) { (void)hipGetLastError(); return fail(PT_ERR_OUT_OF_MEMORY, "pt_tiles_select: tile lists"); }
+    if (candidates) HIP_TRY(hipMemcpyAsync(cand, candidates, (size_t)n * 4, hipMemcpyHostToDevice, sc->stream));
+    sc->begin("tiles_select", n);
+    launch(sc, "k_tiles_select", k_tiles_select, dim3(1), dim3(256), rc, tile_error_dev, threshold, (const uint32_t *)cand, n, out);
+    sc->end();
+    std::vector<uint32_t> h((size_t)n + 1, 0u);
+    HIP_TRY(hipMemcpyAsync(h.data(), out, h.size() * 4, hipMemcpyDeviceToHost, sc->stream));
+    if (int st = film_tool_end(sc)) return st;
+    if (h[0] > n) return fail(PT_ERR_HIP, "internal: pt_tiles_select selected more tiles than it was given");
+    std::copy(h.begin() + 1, h.begin() + 1 + h[0], tiles_out);
+    *n_out = h[0];
     return PT_OK;
 }
 

@@ -8,7 +8,8 @@
 //                     the render frame every integrator's entry point goes through (frame_geometry, render_frame, deliver_film) and the path integrator's own: pt_render, pt_pass_size
 //   parity_api.hip    the entry points tests use to compare single stages with the oracle (rays, Sobol' / Halton samples, camera rays)
 //   multi_device.hip  pt_multi_*: one process driving several devices (one host thread + stream per replica, peer-copy film merge)
-//   film_tools.hip    pt_film_resolve_device / pt_film_halves_error: a film on the device resolved to rgb / 8-bit sRGB, and the convergence estimate of two half films
+//   film_tools.hip    pt_film_resolve_device / pt_film_halves_error / pt_tiles_select: a film on the device resolved to rgb / 8-bit sRGB, the convergence estimate of two
+//                     half films, and the tiles that estimate leaves to render
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -108,6 +109,7 @@ struct pt_scene {
     uint32_t *spill = nullptr; uint32_t spill_waves = 0;
     float *film_rgbw = nullptr; size_t film_px = 0;
     float *d_filter = nullptr;
+    uint32_t *tile_list = nullptr; size_t tile_list_cap = 0;   // pt_render_tiles: the call's tile list on the device (grows on demand, freed at destroy)
     PtCounters counters{};
     std::vector<Stat> stats;
     std::vector<TimedLaunch> timed;
@@ -199,6 +201,8 @@ using FrameStep = std::function<int()>;
 int check_spp(const PtRenderParams *rp);
 int check_sample_range(const PtRenderParams *rp, uint32_t first, uint32_t n);
 uint32_t tile_slots(const RenderConst &rc);
+void tile_grid(const PtRenderParams *rp, uint32_t *ntx, uint32_t *nty);
+int check_tile_list(const uint32_t *tiles, uint32_t n, uint64_t n_grid, const char *what);
 int frame_geometry(pt_scene *sc, const PtRenderParams *rp, RenderConst &rc);
 int frame_pass_size(const RenderConst &rc, uint32_t S, uint32_t n_samples, uint32_t *S_out);
 inline uint32_t reported_pass_size(uint32_t S, const PtRenderParams *rp) { return S ? S : rp->spp; }   // (a rank that owns no tile renders nothing: any size)

@@ -21,6 +21,7 @@ __global__ void k_film_finish(const float *film_rgbw, float *film_xyzw, uint32_t
 __global__ void k_film_resolve(const float4 *film_xyzw, uint32_t n_pixels, float scale, float *rgb, uint8_t *srgb8, int packed);   // kern_preview.h (tu_preview.hip)
 __global__ void k_film_halves_error(const float4 *film_a, const float4 *film_b, uint32_t width, uint32_t height, uint32_t ntx, float *tile_sum, float *tile_err);
 __global__ void k_film_error_reduce(const float *tile_sum, const float *tile_err, uint32_t n_tiles, float n_pixels, float *out);
+__global__ void k_tiles_select(RenderConst rc, const float *tile_err, float threshold, const uint32_t *candidates, uint32_t n_candidates, uint32_t *out);
 __global__ void k_film_sum(FilmSumArgs a, float4 *dst, int accumulate, size_t n_quads);
 __global__ void k_light_grid_contrib(DeviceScene s, uint32_t nvx, uint32_t nvy, uint32_t nvz, float *func, const uint32_t *cells, size_t n_cells, size_t stride);
 __global__ void k_light_grid_finish(uint32_t n_lights, size_t ncell, float *func, float *cdf, float *func_int, const uint32_t *cells, size_t stride, unsigned long long *cell_ptr);

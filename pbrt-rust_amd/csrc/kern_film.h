@@ -1,10 +1,31 @@
 // kern_film.h -- the film kernel's body, shared by k_film (kern_misc.h) and k_film_final (kern_aux.h).
 #pragma once
 #include "kern_common.h"
-// pixel slot -> pixel: slot = tile_slot*256 + ty*16 + tx, tile index = tile_rank + tile_slot*tile_world
+// The tile of a tile slot: the rank's share of the grid, tile_rank + tile_slot * tile_world, or -- a render of listed tiles (pt_render_tiles) -- the list's entry.
+// tile_slot < rc.n_tile_slots, which is then the list's length.
+PT_DEV uint32_t slot_tile(const RenderConst &rc, uint32_t tile_slot) { return rc.tile_list ? rc.tile_list[tile_slot] : rc.tile_rank + tile_slot * rc.tile_world; }
+// A tile's film footprint: the pixels [x0, x1) x [y0, y1) its samples splat onto, clipped to the crop window; empty (x0 >= x1 or y0 >= y1) for a tile of the sample bounds
+// that lies wholly outside the crop's reach. EDGE = true is Film::get_film_tile (film.rs:125-140), the bounds film_slot clips its splats to: it counts the pixels whose filter
+// support merely TOUCHES the tile, which only a sample exactly on the tile's edge reaches (the box filter of radius 0.5: a rim of one pixel around the tile). EDGE = false
+// leaves those out -- the pixels whose support overlaps the tile's area, where all but a vanishing share of its samples land: what pt_tiles_select asks about, so that under
+// the box filter a tile's footprint is the tile. The two differ only where tile edge -/+ radius falls on a pixel centre (radii 0.5, 1.5, ...).
+struct FilmRect { int64_t x0, y0, x1, y1; };
+template <bool EDGE> PT_DEV FilmRect tile_footprint(const RenderConst &rc, uint32_t tile) {
+    int32_t tx0 = rc.sample_bounds[0] + (int32_t)((tile % rc.ntx) * 16u), ty0 = rc.sample_bounds[1] + (int32_t)((tile / rc.ntx) * 16u);
+    int32_t tx1 = min(tx0 + 16, rc.sample_bounds[2]), ty1 = min(ty0 + 16, rc.sample_bounds[3]);
+    const float lx = (float)tx0 - 0.5f - rc.filter_radius[0], ly = (float)ty0 - 0.5f - rc.filter_radius[1];
+    const float hx = (float)tx1 - 0.5f + rc.filter_radius[0], hy = (float)ty1 - 0.5f + rc.filter_radius[1];
+    FilmRect r;
+    r.x0 = max(EDGE ? f2i_sat(ceilf(lx)) : f2i_sat(floorf(lx)) + 1, (int64_t)rc.crop[0]);
+    r.y0 = max(EDGE ? f2i_sat(ceilf(ly)) : f2i_sat(floorf(ly)) + 1, (int64_t)rc.crop[1]);
+    r.x1 = min(EDGE ? f2i_sat(floorf(hx)) + 1 : f2i_sat(ceilf(hx)), (int64_t)rc.crop[2]);
+    r.y1 = min(EDGE ? f2i_sat(floorf(hy)) + 1 : f2i_sat(ceilf(hy)), (int64_t)rc.crop[3]);
+    return r;
+}
+// pixel slot -> pixel: slot = tile_slot*256 + ty*16 + tx, tile index = slot_tile(tile_slot)
 PT_DEV bool slot_to_pixel(const RenderConst &rc, uint32_t slot, int32_t &px, int32_t &py) {
     uint32_t tile_slot = slot >> 8, in_tile = slot & 255u;
-    uint32_t tile = rc.tile_rank + tile_slot * rc.tile_world;
+    uint32_t tile = slot_tile(rc, tile_slot);
     uint32_t tx = tile % rc.ntx, ty = tile / rc.ntx;
     px = rc.sample_bounds[0] + (int32_t)(tx * 16u + (in_tile & 15u));
     py = rc.sample_bounds[1] + (int32_t)(ty * 16u + (in_tile >> 4));
@@ -29,14 +50,8 @@ template <class Fin> PT_DEV void film_slot(const RenderConst &rc, const PathSoA 
     int32_t px, py;
     if (slot < rc.n_pix_slots && slot_to_pixel(rc, slot, px, py)) {
         // tile pixel bounds (Film::get_film_tile, film.rs:125-140)
-        uint32_t tile_slot = slot >> 8;
-        uint32_t tile = rc.tile_rank + tile_slot * rc.tile_world;
-        int32_t tx0 = rc.sample_bounds[0] + (int32_t)((tile % rc.ntx) * 16u), ty0 = rc.sample_bounds[1] + (int32_t)((tile / rc.ntx) * 16u);
-        int32_t tx1 = min(tx0 + 16, rc.sample_bounds[2]), ty1 = min(ty0 + 16, rc.sample_bounds[3]);
-        int64_t tb0 = max(f2i_sat(ceilf((float)tx0 - 0.5f - rc.filter_radius[0])), (int64_t)rc.crop[0]);
-        int64_t tb1 = max(f2i_sat(ceilf((float)ty0 - 0.5f - rc.filter_radius[1])), (int64_t)rc.crop[1]);
-        int64_t tb2 = min(f2i_sat(floorf((float)tx1 - 0.5f + rc.filter_radius[0])) + 1, (int64_t)rc.crop[2]);
-        int64_t tb3 = min(f2i_sat(floorf((float)ty1 - 0.5f + rc.filter_radius[1])) + 1, (int64_t)rc.crop[3]);
+        const FilmRect tb = tile_footprint<true>(rc, slot_tile(rc, slot >> 8));
+        const int64_t tb0 = tb.x0, tb1 = tb.y0, tb2 = tb.x1, tb3 = tb.y1;
         const float invrx = 1.0f / rc.filter_radius[0], invry = 1.0f / rc.filter_radius[1];
         // Splats onto this thread's own pixel are accumulated in registers, seeded with the pixel's current value, and written
         // back once: the additions happen in sample order exactly as before (and as FilmTile::add_sample does), without one

@@ -1,7 +1,8 @@
 // kern_preview.h -- the device film tools (pt_film_resolve_device, pt_film_halves_error): a host that renders in ranges (pt_render_samples) looks at its film, and at how far
-// it has converged, without reading the film back.
+// it has converged, without reading the film back -- and picks the tiles that have not (pt_tiles_select), for a render of listed tiles (pt_render_tiles).
 #pragma once
 #include "kern_common.h"
+#include "kern_film.h"   // tile_footprint
 
 // write_image_png_tga (imageio.rs:365-366): clamp(255 * gamma_correct(v) + 0.5, 0, 255) as u8, gamma_correct (pbrt.rs:210-216); `as u8` truncates and takes NaN to 0
 PT_DEV uint32_t srgb8_code(float v) {
@@ -85,4 +86,38 @@ __global__ __launch_bounds__(256) void k_film_error_reduce(const float *tile_sum
     for (uint32_t t = threadIdx.x; t < n_tiles; t += 256u) { s += tile_sum[t]; m = fmaxf(m, tile_err[t]); }
     s = block_sum_256(s, red_s); m = block_max_256(m, red_m);
     if (threadIdx.x == 0u) { out[0] = s / n_pixels; out[1] = m; }
+}
+
+// The tiles of a candidate list that go on rendering: those whose film footprint (tile_footprint<false>, kern_film.h: without the rim only edge samples reach) meets a film-grid tile with tile_err > threshold. The two
+// grids differ: a candidate is a 16x16 tile of the SAMPLE bounds, tile_err is indexed by the 16x16 tiles of the cropped FILM (k_film_halves_error), and a tile's samples
+// splat onto its whole footprint -- up to 3x3 film tiles for filter radii <= 16. Selected iff !(e <= threshold) for any film tile e of the footprint, i.e. for their largest
+// with a NaN among them kept (the job's spp ends the host's loop); an empty footprint is never selected. candidates == NULL: every tile 0 .. n_candidates - 1.
+// ONE block of 256 lanes walks the list in chunks of 256. Compaction keeps the list's order and uses no atomics: per wave a ballot and the popcount of the lanes below, the
+// four wave totals through LDS, and a base carried from chunk to chunk -- two calls write the same list. out[0] = the count, out[1 ..] = the tiles.
+__global__ __launch_bounds__(256) void k_tiles_select(RenderConst rc, const float *tile_err, float threshold, const uint32_t *candidates, uint32_t n_candidates, uint32_t *out) {
+    __shared__ uint32_t wave_n[4];
+    const uint32_t fntx = (rc.film_w + 15u) / 16u, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t base = 0;   // (uniform: every lane adds the same four totals)
+    for (uint32_t c0 = 0; c0 < n_candidates; c0 += 256u) {
+        const uint32_t i = c0 + threadIdx.x;
+        uint32_t tile = 0; bool keep = false;
+        if (i < n_candidates) {
+            tile = candidates ? candidates[i] : i;
+            const FilmRect r = tile_footprint<false>(rc, tile);
+            if (r.x0 < r.x1 && r.y0 < r.y1) {   // inside the crop, so inside the film's tile grid
+                const uint32_t fx0 = (uint32_t)(r.x0 - rc.crop[0]) >> 4, fx1 = (uint32_t)(r.x1 - 1 - rc.crop[0]) >> 4;
+                const uint32_t fy0 = (uint32_t)(r.y0 - rc.crop[1]) >> 4, fy1 = (uint32_t)(r.y1 - 1 - rc.crop[1]) >> 4;
+                for (uint32_t fy = fy0; fy <= fy1; ++fy) for (uint32_t fx = fx0; fx <= fx1; ++fx) keep = keep || !(tile_err[(size_t)fy * fntx + fx] <= threshold);
+            }
+        }
+        const unsigned long long kept = __ballot(keep);
+        if (lane == 0u) wave_n[wave] = (uint32_t)__popcll(kept);
+        __syncthreads();
+        uint32_t before = 0, total = 0;
+        for (uint32_t w = 0; w < 4u; ++w) { const uint32_t n = wave_n[w]; before += w < wave ? n : 0u; total += n; }
+        if (keep) out[1u + base + before + (uint32_t)__popcll(kept & ((1ull << lane) - 1ull))] = tile;
+        base += total;
+        __syncthreads();   // (wave_n is rewritten by the next chunk)
+    }
+    if (threadIdx.x == 0u) out[0] = base;
 }

@@ -150,7 +150,7 @@ struct DevCounters {  // PtCounters mirror, atomically updated once per wave
 
 struct RenderConst {
     // pass geometry
-    uint32_t n_tile_slots;            // tiles owned by this rank
+    uint32_t n_tile_slots;            // tiles owned by this rank, or listed (tile_list)
     uint32_t tile_rank, tile_world;
     uint32_t ntx, nty;                // tile grid of integrator.rs:277-279
     uint32_t spp, s_begin, s_count;   // samples of this pass: [s_begin, s_begin + s_count)
@@ -166,6 +166,7 @@ struct RenderConst {
     uint32_t volpath, camera_medium;   // VolPathIntegrator (volpath.rs) instead of PathIntegrator; the camera's medium
     float filter_radius[2]; float max_sample_luminance;
     uint32_t film_w, film_h;
+    const uint32_t *tile_list;        // pt_render_tiles: tile slot i renders tile tile_list[i] (device, n_tile_slots entries, ascending); NULL: tile_rank + i * tile_world
 };
 
 // One kind of ray of a traversal launch: where its rays come from and where its results go.

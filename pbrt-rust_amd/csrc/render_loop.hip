@@ -265,13 +265,19 @@ int ensure_light_grid(pt_scene *sc, int requested, int &effective) {
     return PT_OK;
 }
 
+// The 16x16 tiles of the sample bounds (integrator.rs:277-279): the grid tile_rank / tile_world and the tile lists index, row major
+void tile_grid(const PtRenderParams *rp, uint32_t *ntx, uint32_t *nty) {
+    const int32_t dx = rp->sample_bounds[2] - rp->sample_bounds[0], dy = rp->sample_bounds[3] - rp->sample_bounds[1];
+    *ntx = (uint32_t)((dx + 15) / 16); *nty = (uint32_t)((dy + 15) / 16);
+}
+
 void fill_render_const(const PtRenderParams *rp, RenderConst &rc) {
     std::memset(&rc, 0, sizeof rc);
     std::memcpy(rc.sample_bounds, rp->sample_bounds, 16);
     std::memcpy(rc.pixel_bounds, rp->pixel_bounds, 16);
     std::memcpy(rc.crop, rp->cropped_pixel_bounds, 16);
     int32_t dx = rp->sample_bounds[2] - rp->sample_bounds[0], dy = rp->sample_bounds[3] - rp->sample_bounds[1];
-    rc.ntx = (uint32_t)((dx + 15) / 16); rc.nty = (uint32_t)((dy + 15) / 16);
+    tile_grid(rp, &rc.ntx, &rc.nty);
     // SobolSampler::new (sobol.rs:42-44)
     int32_t v = std::max(dx, dy); v--; v |= v >> 1; v |= v >> 2; v |= v >> 4; v |= v >> 8; v |= v >> 16; v++;
     rc.sobol.resolution = v; rc.sobol.log2_resolution = 31 - __builtin_clz((uint32_t)v);
@@ -640,6 +646,17 @@ int check_sample_range(const PtRenderParams *rp, uint32_t first, uint32_t n) {
 // 16x16 tiles of rank rc.tile_rank among rc.tile_world (tile t belongs to rank t % world)
 uint32_t tile_slots(const RenderConst &rc) { const uint32_t ntiles = rc.ntx * rc.nty; return rc.tile_rank < ntiles ? (ntiles - rc.tile_rank + rc.tile_world - 1) / rc.tile_world : 0; }
 
+// A tile list of the C ABI (pt_render_tiles, pt_tiles_select): strictly ascending -- so no tile twice: film_slot accumulates a thread's own pixel in registers, which is only
+// right when no two slots name one pixel --, every entry inside the grid of n_grid tiles, and an array when n > 0. Host arithmetic.
+int check_tile_list(const uint32_t *tiles, uint32_t n, uint64_t n_grid, const char *what) {
+    if (n > 0 && !tiles) return fail(PT_ERR_INVALID_ARG, std::string(what) + ": null tile list");
+    for (uint32_t i = 0; i < n; ++i) {
+        if (tiles[i] >= n_grid) return fail(PT_ERR_INVALID_ARG, std::string(what) + ": tile " + std::to_string(tiles[i]) + " is outside the grid of " + std::to_string(n_grid) + " tiles");
+        if (i > 0 && tiles[i] <= tiles[i - 1]) return fail(PT_ERR_INVALID_ARG, std::string(what) + ": the tile list must be strictly ascending (entry " + std::to_string(i) + ")");
+    }
+    return PT_OK;
+}
+
 // What every render checks before it touches the device, the re-bind to the scene's device, and rc (incl. n_tile_slots / n_pix_slots; 0: this rank owns no tile)
 int frame_geometry(pt_scene *sc, const PtRenderParams *rp, RenderConst &rc) {
     if (int st = check_spp(rp)) return st;
@@ -721,9 +738,11 @@ extern "C" {
 // The path integrators' geometry -- ONE function for pt_render and pt_pass_size, so that the size pt_pass_size reports is the size of a render that would be accepted
 // (the two had drifted apart): the frame's checks, what path / volpath take, and *S_out = samples per pixel per wavefront pass (0 when this rank owns no tile).
 // `n_samples`: how many of the job's rp->spp sample numbers the call renders (pt_render_samples; rp->spp for pt_render and pt_pass_size) -- the pass size is capped at it and
-// the library's choice makes equal passes over it, while rc keeps the JOB's spp (rc.inv_sqrt_spp, the differential scale).
-static int render_geometry(pt_scene *sc, const PtRenderParams *rp, uint32_t n_samples, RenderConst &rc, uint32_t *S_out) {
+// the library's choice makes equal passes over it, while rc keeps the JOB's spp (rc.inv_sqrt_spp, the differential scale). `n_listed` (pt_render_tiles): the call renders
+// that many listed tiles instead of the rank's share -- the tile slots are the list's entries (rc.tile_list, set once the list is on the device).
+static int render_geometry(pt_scene *sc, const PtRenderParams *rp, uint32_t n_samples, RenderConst &rc, uint32_t *S_out, const uint32_t *n_listed = nullptr) {
     if (int st = frame_geometry(sc, rp, rc)) return st;
+    if (n_listed) { rc.n_tile_slots = *n_listed; rc.n_pix_slots = rc.n_tile_slots * 256u; }
     if (rp->max_depth > 254) return fail(PT_ERR_INVALID_ARG, "maxdepth must be <= 254 (the bounce count of a path is kept in 8 bits)");
     if (rc.volpath) {   // VolPathIntegrator (volpath.rs): what this back end takes
         if (sc->has_bssrdf && sc->ds.n_media >= 0xffffu) return fail(PT_ERR_UNSUPPORTED, "volpath: subsurface materials with more than 65534 media");
@@ -750,11 +769,22 @@ int pt_render(pt_scene *sc, const PtRenderParams *rp, float *film_xyzw, int film
 
 // Sample numbers [first, first + n) of the job `rp` describes. Sample k of a pixel is a function of the pixel and k alone (k_generate: rc.s_begin + sl), the film is added
 // to, and everything that depends on the job's sample count -- the differential scale -- reads rp->spp: the range only sets the pass loop's bounds.
-int pt_render_samples(pt_scene *sc, const PtRenderParams *rp, uint32_t first, uint32_t n_samples, float *film_xyzw, int film_is_device) {
-    if (!sc || !rp || !film_xyzw) return fail(PT_ERR_INVALID_ARG, "null argument");
-    if (int rst = check_sample_range(rp, first, n_samples)) return rst;   // (before the device is touched)
+// `tiles` != NULL (pt_render_tiles): on *n_listed checked tiles (check_tile_list) instead of the rank's share.
+static int render_range(pt_scene *sc, const PtRenderParams *rp, uint32_t first, uint32_t n_samples, const uint32_t *tiles, const uint32_t *n_listed, float *film_xyzw, int film_is_device) {
     RenderConst rc; uint32_t S = 0;
-    if (int gst = render_geometry(sc, rp, n_samples, rc, &S)) return gst;
+    if (int gst = render_geometry(sc, rp, n_samples, rc, &S, n_listed)) return gst;
+    if (n_listed && *n_listed > 0) {   // the list goes to the scene's device buffer (the device is bound by now); the render's stream carries it before the first launch
+        const size_t n = *n_listed;
+        if (!sc->stream) HIP_TRY(hipStreamCreate(&sc->stream));
+        if (n > sc->tile_list_cap) {
+            if (sc->tile_list) hipFree(sc->tile_list);
+            sc->tile_list = nullptr; sc->tile_list_cap = 0;
+            if (hipError_t e = hipMalloc((void **)&sc->tile_list, n * 4); e != hipSuccess) { (void)hipGetLastError(); sc->tile_list = nullptr; return fail(PT_ERR_OUT_OF_MEMORY, std::string("tile list: ") + hipGetErrorString(e)); }
+            sc->tile_list_cap = n;
+        }
+        HIP_TRY(hipMemcpyAsync(sc->tile_list, tiles, n * 4, hipMemcpyHostToDevice, sc->stream));
+        rc.tile_list = sc->tile_list;
+    }
     int max_iterations = 1 << 20;   // wavefront iterations per pass. TEST HOOK (env PT_TEST_MAX_ITERATIONS, read at every call): a smaller cap, so that the PT_ERR_PROBE_CHAIN return of a pass that does not end can be tested
     if (const char *e = getenv("PT_TEST_MAX_ITERATIONS")) { const int v = atoi(e); if (v > 0) max_iterations = v; }
     int eff = 0;
@@ -783,6 +813,29 @@ int pt_render_samples(pt_scene *sc, const PtRenderParams *rp, uint32_t first, ui
         return (int)PT_OK;
     };
     return render_frame(sc, rp, rc, S, first, n_samples, film_xyzw, film_is_device, prepare, pass, finish);
+}
+
+int pt_render_samples(pt_scene *sc, const PtRenderParams *rp, uint32_t first, uint32_t n_samples, float *film_xyzw, int film_is_device) {
+    if (!sc || !rp || !film_xyzw) return fail(PT_ERR_INVALID_ARG, "null argument");
+    if (int rst = check_sample_range(rp, first, n_samples)) return rst;   // (before the device is touched)
+    return render_range(sc, rp, first, n_samples, nullptr, nullptr, film_xyzw, film_is_device);
+}
+
+int pt_tile_grid(const PtRenderParams *rp, uint32_t *ntx, uint32_t *nty) {
+    if (!rp || !ntx || !nty) return fail(PT_ERR_INVALID_ARG, "null argument");
+    tile_grid(rp, ntx, nty);
+    return PT_OK;
+}
+
+// pt_render_samples on listed tiles. The list replaces the shard rule in the one place the kernels derive a slot's tile (slot_tile, kern_film.h); an empty list is a
+// rank that owns no tile: PT_OK, nothing launched, zeroed counters.
+int pt_render_tiles(pt_scene *sc, const PtRenderParams *rp, uint32_t first, uint32_t n_samples, const uint32_t *tiles, uint32_t n_tiles, float *film_xyzw, int film_is_device) {
+    if (!sc || !rp || !film_xyzw) return fail(PT_ERR_INVALID_ARG, "null argument");
+    if (int rst = check_sample_range(rp, first, n_samples)) return rst;   // (all of this before the device is touched)
+    if (rp->tile_world > 1) return fail(PT_ERR_INVALID_ARG, "pt_render_tiles: the tile list replaces the shard rule, params->tile_world must be 0 or 1");
+    uint32_t ntx = 0, nty = 0; tile_grid(rp, &ntx, &nty);
+    if (int lst = check_tile_list(tiles, n_tiles, (uint64_t)ntx * nty, "pt_render_tiles")) return lst;
+    return render_range(sc, rp, first, n_samples, tiles, &n_tiles, film_xyzw, film_is_device);
 }
 
 int pt_film_resolve(const float *xyzw, uint32_t n, float scale, float *rgb) {  // film.rs:217-258 (host arithmetic)

@@ -151,6 +151,7 @@ void pt_scene_destroy(pt_scene *sc) {
     if (sc->bss_slab) hipFree(sc->bss_slab);
     if (sc->ext_slab) hipFree(sc->ext_slab);
     if (sc->film_rgbw) hipFree(sc->film_rgbw);
+    if (sc->tile_list) hipFree(sc->tile_list);
     sc->drop_timings();
     for (auto e : sc->event_pool) hipEventDestroy(e);
     if (sc->stream) hipStreamDestroy(sc->stream);

@@ -1,5 +1,6 @@
 // mi355pbrt -- command-line renderer: the drop-in for `pbrt-rust scene.pbrt` on this back end (main.rs + api.rs:1715-1748).
 //   mi355pbrt scene.pbrt [--outfile out.pfm] [--device N] [--spp N] [--quiet] [--samples A:B] [--checkpoint FILE] [--preview-every N]
+//                        [--adaptive T [--adaptive-step N] [--adaptive-min N]]
 // Parses with libmi355front.so, renders with libmi355pt.so (HIP; Integrator "ambientocclusion": libmi355ao.so), writes the film in the format the Film's "filename"
 // extension names (exr -- the reference's default "pbrt.exr" -- png, tga, pfm: core/imageio.rs:42-60).
 // The film lives on the device and is rendered in groups of samples (pt_render_samples); one group -- the whole job -- unless asked otherwise:
@@ -7,6 +8,10 @@
 //   --checkpoint FILE    after every group (--preview-every N samples, else one wavefront pass) the raw XYZW sums + a header go to FILE; a FILE of this job found at the
 //                        start is resumed from its `samples done`, one of another job is refused
 //   --preview-every N    every N samples the outfile is written from the film so far (pt_film_resolve_device)
+//   --adaptive T         adaptive sampling: two half films, rounds of --adaptive-step N samples (default 4) into each; after a round (once --adaptive-min N samples are
+//                        done, default 0) the 16x16 tiles whose film footprint no longer meets a film tile with halves error > T stop for good (pt_film_halves_error,
+//                        pt_tiles_select, pt_render_tiles), the others go on up to the job's spp. Not with --samples / --checkpoint (the state of an adaptive render is
+//                        a sample count per tile, which neither holds) nor Integrator "ambientocclusion" (libmi355ao has no tile-list render).
 #include "../../include/mi355front.h"
 #include <hip/hip_runtime_api.h>
 #include <chrono>
@@ -16,7 +21,8 @@
 #include <string>
 #include <vector>
 
-static const char *kUsage = "usage: mi355pbrt scene.pbrt [--outfile out.pfm] [--device N] [--spp N] [--quiet] [--samples A:B] [--checkpoint FILE] [--preview-every N]\n";
+static const char *kUsage = "usage: mi355pbrt scene.pbrt [--outfile out.pfm] [--device N] [--spp N] [--quiet] [--samples A:B] [--checkpoint FILE] [--preview-every N]\n"
+                            "                 [--adaptive T [--adaptive-step N] [--adaptive-min N]]\n";
 static int usage(const std::string &why = "") { if (!why.empty()) std::fprintf(stderr, "mi355pbrt: %s\n", why.c_str()); std::fputs(kUsage, stderr); return 2; }
 
 // "A:B" with decimal A < B, both fitting 32 bits
@@ -30,6 +36,7 @@ static bool parse_range(const std::string &a, long long &lo, long long &hi) {
 
 int main(int argc, char **argv) {
     std::string scene, outfile, samples, checkpoint; int device = 0, spp = 0; long long preview = 0; bool quiet = false;
+    bool adaptive = false; float threshold = 0.0f; long long astep = 4, amin = 0;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         if (a == "--outfile" && i + 1 < argc) outfile = argv[++i];
@@ -38,11 +45,20 @@ int main(int argc, char **argv) {
         else if (a == "--samples" && i + 1 < argc) samples = argv[++i];
         else if (a == "--checkpoint" && i + 1 < argc) checkpoint = argv[++i];
         else if (a == "--preview-every" && i + 1 < argc) { preview = std::atoll(argv[++i]); if (preview <= 0 || preview > 0xffffffffll) return usage("--preview-every takes a number of samples > 0"); }
+        else if (a == "--adaptive" && i + 1 < argc) {
+            char *end = nullptr; threshold = std::strtof(argv[++i], &end);
+            if (end == argv[i] || *end || !(threshold >= 0.0f)) return usage("--adaptive takes an error threshold >= 0");
+            adaptive = true;
+        }
+        else if (a == "--adaptive-step" && i + 1 < argc) { astep = std::atoll(argv[++i]); if (astep <= 0 || astep > 0xffffffffll) return usage("--adaptive-step takes a number of samples > 0"); }
+        else if (a == "--adaptive-min" && i + 1 < argc) { amin = std::atoll(argv[++i]); if (amin < 0 || amin > 0xffffffffll) return usage("--adaptive-min takes a number of samples >= 0"); }
         else if (a == "--quiet") quiet = true;
         else if (a[0] != '-') scene = a;
         else return usage();
     }
     if (scene.empty()) return usage();
+    if (adaptive && !samples.empty()) return usage("--adaptive with --samples: an adaptive render chooses its own sample ranges, tile by tile");
+    if (adaptive && !checkpoint.empty()) return usage("--adaptive with --checkpoint: a checkpoint holds one sample count for the frame, an adaptive render one per tile");
     long long lo = 0, hi = 0;
     if (!samples.empty() && !parse_range(samples, lo, hi)) return usage("--samples takes A:B with 0 <= A < B, got \"" + samples + "\"");
     ptf_scene *fs = nullptr;
@@ -57,6 +73,7 @@ int main(int argc, char **argv) {
     }
     const bool is_ao = rp.integrator == PT_INTEGRATOR_AO;   // Integrator "ambientocclusion" (libmi355ao.so)
     PtAOParams ao{}; if (is_ao) ptf_ao_params(fs, &ao);
+    if (adaptive && is_ao) return usage("--adaptive with Integrator \"ambientocclusion\": the ambient-occlusion integrator has no tile-list render");
     const int w = rp.cropped_pixel_bounds[2] - rp.cropped_pixel_bounds[0], h = rp.cropped_pixel_bounds[3] - rp.cropped_pixel_bounds[1];
     if (w <= 0 || h <= 0) { std::fprintf(stderr, "mi355pbrt: empty film\n"); return 1; }
     const size_t npix = (size_t)w * h;
@@ -90,7 +107,43 @@ int main(int argc, char **argv) {
         if (pst != PT_OK) { std::fprintf(stderr, "mi355pbrt: %s\n", pt_last_error()); return 1; }
     }
     unsigned long long camera_rays = 0;
-    for (uint32_t s = first + ck.samples_done; s < last; ) {
+    if (adaptive) {   // runtime.Scene.render_adaptive's loop: d_film is half A, d_half half B, the active set only shrinks
+        const auto fail_pt = [&]() { std::fprintf(stderr, "mi355pbrt: %s\n", pt_last_error()); return 1; };
+        uint32_t ntx = 0, nty = 0;
+        if (pt_tile_grid(&rp, &ntx, &nty) != PT_OK) return fail_pt();
+        const size_t n_film_tiles = (size_t)((w + 15) / 16) * ((h + 15) / 16);
+        float *d_half = nullptr, *d_err = nullptr;
+        if (hipMalloc((void **)&d_half, npix * 16) != hipSuccess || hipMalloc((void **)&d_err, n_film_tiles * 4) != hipSuccess || hipMemset(d_half, 0, npix * 16) != hipSuccess ||
+            hipDeviceSynchronize() != hipSuccess) { std::fprintf(stderr, "mi355pbrt: device film: %s\n", hipGetErrorString(hipGetLastError())); return 1; }
+        std::vector<uint32_t> active((size_t)ntx * nty), kept(active.size());
+        for (size_t i = 0; i < active.size(); ++i) active[i] = (uint32_t)i;
+        unsigned long long tile_samples = 0; unsigned rounds = 0;
+        for (uint32_t done = 0; done < rp.spp && !active.empty(); ++rounds) {
+            uint32_t n_b = 0;
+            for (float *half : {d_film, d_half}) {
+                const uint32_t n = (uint32_t)std::min<long long>(astep, rp.spp - done);
+                if (half == d_half) n_b = n;
+                if (n == 0) continue;
+                if (pt_render_tiles(sc, &rp, done, n, active.data(), (uint32_t)active.size(), half, 1) != PT_OK) return fail_pt();
+                PtCounters c; pt_get_counters(sc, &c); camera_rays += c.camera_rays;
+                done += n; tile_samples += (unsigned long long)n * active.size();
+            }
+            if (n_b > 0 && done >= (uint32_t)amin) {
+                uint32_t n_kept = 0;
+                if (pt_film_halves_error(sc, d_film, d_half, (uint32_t)w, (uint32_t)h, d_err, nullptr, nullptr) != PT_OK ||
+                    pt_tiles_select(sc, &rp, d_err, threshold, active.data(), (uint32_t)active.size(), kept.data(), &n_kept) != PT_OK) return fail_pt();
+                active.assign(kept.begin(), kept.begin() + n_kept);
+            }
+        }
+        // A += B: the film is the sum of the halves (host arithmetic on the read-back halves, element by element)
+        std::vector<float> half_b(npix * 4);
+        if (hipMemcpy(film.data(), d_film, npix * 16, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(half_b.data(), d_half, npix * 16, hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "mi355pbrt: reading the film back failed\n"); return 1; }
+        for (size_t i = 0; i < film.size(); ++i) film[i] += half_b[i];
+        if (hipMemcpy(d_film, film.data(), npix * 16, hipMemcpyHostToDevice) != hipSuccess) { std::fprintf(stderr, "mi355pbrt: writing the film back failed\n"); return 1; }
+        (void)hipFree(d_half); (void)hipFree(d_err);
+        if (!quiet) std::printf("adaptive: %llu of %llu tile-samples, %u rounds\n", tile_samples, (unsigned long long)ntx * nty * rp.spp, rounds);
+    }
+    for (uint32_t s = first + ck.samples_done; s < last && !adaptive; ) {
         const uint32_t n = std::min(group, last - s);
         const int rst = is_ao ? pt_ao_render_samples(sc, &rp, &ao, s, n, d_film, 1) : pt_render_samples(sc, &rp, s, n, d_film, 1);
         if (rst != PT_OK) { std::fprintf(stderr, "mi355pbrt: %s\n", pt_last_error()); return 1; }

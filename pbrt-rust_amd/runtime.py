@@ -209,6 +209,80 @@ class Scene(Handle):
                 break
         return (halves[0] + halves[1]).cpu().numpy(), done
 
+    def tile_grid(self, rp):
+        """(ntx, nty) of the render's 16x16 sample-tile grid (pt_tile_grid): the grid rp.tile_rank / tile_world and the tile lists index, row major."""
+        ntx, nty = C.c_uint32(), C.c_uint32()
+        self._call("tile_grid", C.byref(rp), C.byref(ntx), C.byref(nty))
+        return int(ntx.value), int(nty.value)
+
+    def render_tiles(self, rp, samples, tiles, film=None, device_ptr=None):
+        """pt_render_tiles: sample numbers samples = (first, n) of the listed tiles (strictly ascending indices into tile_grid(rp)) only, ADDED to `film`
+        (a numpy film, made when None and returned) or to the device film at `device_ptr` (returns None)."""
+        first, n = samples
+        tiles = np.ascontiguousarray(tiles, dtype=np.uint32)
+        args = [self.h, C.byref(rp), first, n, tiles.ctypes.data_as(A.u32p), len(tiles)]
+        if device_ptr is not None:
+            self._call("render_tiles", *args, C.c_void_p(device_ptr), 1); return None
+        if film is None:
+            cb = rp.cropped_pixel_bounds
+            film = np.zeros((cb[3] - cb[1], cb[2] - cb[0], 4), dtype=np.float32)
+        self._call("render_tiles", *args, film.ctypes.data_as(C.c_void_p), 0)
+        return film
+
+    def select_tiles(self, rp, tile_error_ptr, threshold, candidates=None):
+        """pt_tiles_select: of `candidates` (ascending tile indices; None: every tile of the grid) those whose film footprint meets a film tile whose error -- the
+        device array pt_film_halves_error wrote, at `tile_error_ptr` -- is not <= threshold. A uint32 array, in the candidates' order."""
+        if candidates is None:
+            ntx, nty = self.tile_grid(rp)
+            cand, n = None, ntx * nty
+        else:
+            candidates = np.ascontiguousarray(candidates, dtype=np.uint32)
+            cand, n = candidates.ctypes.data_as(A.u32p), len(candidates)
+        out = np.zeros(max(n, 1), dtype=np.uint32); n_out = C.c_uint32()
+        self._call("tiles_select", self.h, C.byref(rp), C.c_void_p(tile_error_ptr), threshold, cand, n, out.ctypes.data_as(A.u32p), C.byref(n_out))
+        return out[:n_out.value].copy()
+
+    def render_adaptive(self, rp, threshold, step, min_samples=0, on_round=None):
+        """The job `rp` with a shrinking set of active tiles: render_progressive's two half films, stopped tile by tile instead of as a whole frame.
+        A round renders sample numbers [done, done + step) of the active tiles into film A and the next `step` into film B (both clipped to rp.spp). After a round in
+        which both halves got samples, and once done >= min_samples, pt_film_halves_error writes the per-tile errors and pt_tiles_select keeps the active tiles whose
+        footprint still meets a film tile with error > threshold. A tile that leaves the active set never returns, so all active tiles share one sample count and
+        every call is one (first, n). Ends when no tile is active or done == rp.spp. on_round(done, active tiles, max_tile_error or None) is called after every round.
+        Returns (A + B as a numpy film (H, W, 4), a (nty, ntx) uint32 array of the samples rendered per tile); self.adaptive_counters then holds the counters summed
+        over the loop's render calls (counters() describes the last call alone).
+        Caveat: the stopping rule reads the same samples it stops. A tile whose two halves happen to agree early stops early, so the estimate is biased (towards
+        the values at which halves agree); min_samples bounds how early that can happen, it does not remove the bias."""
+        import torch
+        if step <= 0:
+            raise ValueError("step must be > 0")
+        cb = rp.cropped_pixel_bounds
+        w, h = cb[2] - cb[0], cb[3] - cb[1]
+        ntx, nty = self.tile_grid(rp)
+        halves = [torch.zeros((h, w, 4), dtype=torch.float32, device="cuda") for _ in range(2)]
+        tile_err = torch.zeros((-(-w // 16)) * (-(-h // 16)), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()   # (the library renders on its own stream: the zeroed films must be there before it adds to them)
+        active = np.arange(ntx * nty, dtype=np.uint32)
+        per_tile = np.zeros(ntx * nty, dtype=np.uint32)
+        done, total = 0, None
+        while done < rp.spp and len(active):
+            got = []
+            for half in halves:
+                n = min(step, rp.spp - done)
+                if n > 0:
+                    self.render_tiles(rp, (done, n), active, device_ptr=half.data_ptr())
+                    done += n; per_tile[active] += n
+                    c = self.counters()
+                    total = c if total is None else {k: ([a + x for a, x in zip(total[k], v)] if isinstance(v, list) else total[k] + v) for k, v in c.items()}
+                got.append(n)
+            worst = None
+            if got[1] > 0 and done >= min_samples:
+                _, worst = self.halves_error(halves[0].data_ptr(), halves[1].data_ptr(), w, h, tile_err.data_ptr())
+                active = self.select_tiles(rp, tile_err.data_ptr(), threshold, candidates=active)
+            if on_round is not None:
+                on_round(done, active, worst)
+        self.adaptive_counters = total
+        return (halves[0] + halves[1]).cpu().numpy(), per_tile.reshape(nty, ntx)
+
     def ao_params(self):
         """The scene's PtAOParams (SceneBuilder.integ / the front end's "ambientocclusion" parameters)."""
         return self.data.ao_params()
