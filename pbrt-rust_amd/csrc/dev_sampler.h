@@ -218,6 +218,12 @@ struct Sampler {
         return P2(x, y);
     }
 };
+// The sampler of one path vertex: sample `index` at dimension `dim`, the first lds_dims dimensions' nibble tables staged at `lds` (none: nullptr, 0); no window loaded yet.
+PT_DEV Sampler make_sampler(const SobolTables &tabs, const uint32_t *lds, uint32_t lds_dims, uint64_t index, uint32_t dim, bool halton) {
+    Sampler smp; smp.index = index; smp.dim = dim; smp.m32 = tabs.m32; smp.nib = tabs.nib; smp.lds = lds; smp.lds_dims = lds_dims; smp.overflow = false; smp.halton = halton;
+    smp.prime = tabs.prime; smp.prime_sum = tabs.prime_sum; smp.perm = tabs.perm; smp.base = 0xffffffffu;
+    return smp;
+}
 
 // Film-plane dimensions 0/1 are remapped to the pixel (sobol.rs:77-81).
 PT_DEV float sobol_pixel_dim(const uint32_t *m32, const SobolParams &sp, uint64_t index, int d, int32_t pixel) {

@@ -24,8 +24,7 @@ __global__ __launch_bounds__(256) void k_medium_route(DeviceScene s, RenderConst
             const uint32_t med = ps.medium(pid);
             if (med != PT_NONE) {
                 uint32_t meta = ps.meta(pid);
-                Sampler smp; smp.index = ps.sobol_index(pid); smp.dim = meta & 0xffffu; smp.m32 = tabs.m32; smp.nib = tabs.nib; smp.lds = nullptr; smp.lds_dims = 0u; smp.overflow = false;
-                smp.halton = rc.halton.enabled != 0; smp.prime = tabs.prime; smp.prime_sum = tabs.prime_sum; smp.perm = tabs.perm; smp.base = 0xffffffffu;
+                Sampler smp = make_sampler(tabs, nullptr, 0u, ps.sobol_index(pid), meta & 0xffffu, rc.halton.enabled != 0);
                 const V3 rd(ps.dx(pid), ps.dy(pid), ps.dz(pid));
                 bool sampled; float t;
                 RGB w(1.0f);
@@ -70,10 +69,10 @@ __global__ __launch_bounds__(256) void k_medium_route(DeviceScene s, RenderConst
 __global__ __launch_bounds__(256) void k_shade_medium(DeviceScene s, RenderConst rc, SobolTables tabs, LightGrid grid, PathSoA ps, ShadeJob job) {
     constexpr uint32_t LDS_DIMS = 56u;
     __shared__ uint32_t s_sobol[LDS_DIMS * kSobolNibWords];
-    __shared__ LdsQueue<1024> s_qext, s_qres, s_qsh, s_qmis, s_qself;
+    __shared__ VertexQueues<1024, false, true> s_q;
     __shared__ uint32_t s_hist[16];
-    lq_init(s_qext); lq_init(s_qres); lq_init(s_qsh); lq_init(s_qmis); lq_init(s_qself);
-    if (threadIdx.x < 16) s_hist[threadIdx.x] = 0;
+    s_q.init();
+    hist_init(s_hist);
     PT_PROF_BEGIN
     sobol_stage_lds(s_sobol, tabs.nib, LDS_DIMS, threadIdx.x, blockDim.x);
     __syncthreads();
@@ -91,8 +90,7 @@ __global__ __launch_bounds__(256) void k_shade_medium(DeviceScene s, RenderConst
             pid = job.queue[qi];
             const uint32_t meta = ps.meta(pid);
             uint32_t flags = meta >> 24, bounces = (meta >> 16) & 0xffu;
-            Sampler smp; smp.index = ps.sobol_index(pid); smp.dim = meta & 0xffffu; smp.m32 = tabs.m32; smp.nib = tabs.nib; smp.lds = s_sobol; smp.lds_dims = LDS_DIMS; smp.overflow = false;
-            smp.halton = rc.halton.enabled != 0; smp.prime = tabs.prime; smp.prime_sum = tabs.prime_sum; smp.perm = tabs.perm; smp.base = 0xffffffffu;
+            Sampler smp = make_sampler(tabs, s_sobol, LDS_DIMS, ps.sobol_index(pid), meta & 0xffffu, rc.halton.enabled != 0);
             RGB L(ps.L_r(pid), ps.L_g(pid), ps.L_b(pid));
             RGB beta(ps.beta_r(pid), ps.beta_g(pid), ps.beta_b(pid));
             const bool stage_b = (flags & PF_STAGE_B) != 0u;   // grid media: this vertex's own NEE rays are back (see k_shade)
@@ -119,15 +117,7 @@ __global__ __launch_bounds__(256) void k_shade_medium(DeviceScene s, RenderConst
                 V3 wi;
                 hg_sample_p(phase.g, si.wo, wi, smp.get_2d());
                 flags &= ~PF_SPECULAR;   // specular_bounce = false
-                // Russian roulette (volpath.rs:171-176)
-                const RGB rrbeta = beta * ps.etascale(pid);
-                bool rr_kill = false;
-                if (rrbeta.max_component_value() < rc.rr_threshold && bounces > 3) {
-                    const float q = maxf(1.0f - rrbeta.max_component_value(), 0.05f);
-                    if (smp.get_1d() < q) rr_kill = true;
-                    else { beta = beta / (1.0f - q); if (__builtin_isinf(beta.y())) n_assert++; }   // volpath.rs:223
-                }
-                if (rr_kill) terminated = true;
+                if (russian_roulette(rc, smp, beta, ps.etascale(pid), bounces, n_assert)) terminated = true;   // volpath.rs:171-176
                 else {
                     bounces += 1;
                     ps.ox(pid) = si.p.x; ps.oy(pid) = si.p.y; ps.oz(pid) = si.p.z;   // mi.spawn_ray(wi): no offset (n = 0, p_error = 0)
@@ -138,36 +128,17 @@ __global__ __launch_bounds__(256) void k_shade_medium(DeviceScene s, RenderConst
             }
             if (terminated) {
                 if (flags & (PF_PEND_SHADOW | PF_PEND_MIS)) { flags |= PF_DEAD; push_resolve = true; }
-                else finished_bounces = (int)bounces;
+                else finished_bounces = (int)bounces;   // (no PF_FINISHED from this kernel)
             }
-            if (smp.overflow) atomicMax(job.error, (uint32_t)PT_ERR_SOBOL_DIMENSIONS);
-            ps.L_r(pid) = L.r; ps.L_g(pid) = L.g; ps.L_b(pid) = L.b;
-            ps.beta_r(pid) = beta.r; ps.beta_g(pid) = beta.g; ps.beta_b(pid) = beta.b;
-            ps.meta(pid) = (smp.dim & 0xffffu) | ((bounces & 0xffu) << 16) | (flags << 24);
+            store_vertex(ps, pid, L, beta, smp, bounces, flags, job.error);
         }
-        lq_push(s_qext, pid, push_ext); lq_push(s_qres, pid, push_resolve); lq_push(s_qsh, pid, push_shadow); lq_push(s_qmis, pid, push_mis); lq_push(s_qself, pid, push_self);
-        if (finished_bounces >= 0) atomicAdd(&s_hist[finished_bounces > 15 ? 15 : finished_bounces], 1u);
-        __syncthreads();
-        lq_flush_nosync(s_qext, job.ext_next_count, job.ext_next, 256u, false);
-        lq_flush_nosync(s_qres, job.shade_next0_count, job.shade_next0, 256u, false);
-        lq_flush_nosync(s_qsh, job.shadow_count, job.shadow, 256u, false);
-        lq_flush_nosync(s_qmis, job.mis_count, job.mis, 256u, false);
-        lq_flush_nosync(s_qself, job.self_next_count, job.self_next, 256u, false);
-        __syncthreads();
+        s_q.push(job, pid, push_ext, push_resolve, push_shadow, push_mis, push_self);
+        if (finished_bounces >= 0) hist_add(s_hist, (uint32_t)finished_bounces);
+        s_q.flush(job, 256u, false);
     }
-    lq_flush_nosync(s_qext, job.ext_next_count, job.ext_next, 0u, true);
-    lq_flush_nosync(s_qres, job.shade_next0_count, job.shade_next0, 0u, true);
-    lq_flush_nosync(s_qsh, job.shadow_count, job.shadow, 0u, true);
-    lq_flush_nosync(s_qmis, job.mis_count, job.mis, 0u, true);
-    lq_flush_nosync(s_qself, job.self_next_count, job.self_next, 0u, true);
-    __syncthreads();
-    __syncthreads();
-    if (threadIdx.x < 16 && s_hist[threadIdx.x]) atomicAdd(&job.counters->path_len[threadIdx.x], (unsigned long long)s_hist[threadIdx.x]);
-    counter_add(&job.counters->stages, n_valid);
-    counter_add(&job.counters->shade_items[kMediumClass], n_valid);
-    counter_add(&job.counters->shade_bytes[kMediumClass], n_bytes);
-    counter_add(&job.counters->ref_asserts, (unsigned long long)n_assert);
-    (void)zero_num;
+    s_q.flush(job, 0u, true);
+    vertex_epilogue(s_hist, job.counters, &job.counters->shade_items[kMediumClass], &job.counters->shade_bytes[kMediumClass], n_valid, n_bytes, n_assert);
+    (void)zero_num;   // (resolve_pending<.., VOL> counts none)
 }
 
 // ---- escaped rays and dead paths (class kMissClass) -------------------------------------------------------------------
@@ -177,7 +148,7 @@ __global__ __launch_bounds__(256) void k_shade_medium(DeviceScene s, RenderConst
 template <bool SPH, bool VOL>
 __global__ __launch_bounds__(256, PT_MISS_WAVES) void k_shade_miss(DeviceScene s, RenderConst rc, PathSoA ps, ShadeJob job) {
     __shared__ uint32_t s_hist[16];
-    if (threadIdx.x < 16) s_hist[threadIdx.x] = 0;
+    hist_init(s_hist);
     PT_PROF_BEGIN   // not reported: the region table is k_shade's
     __syncthreads();
     const uint32_t count = *job.count;
@@ -199,19 +170,15 @@ __global__ __launch_bounds__(256, PT_MISS_WAVES) void k_shade_miss(DeviceScene s
             const float4 *rq = reinterpret_cast<const float4 *>(ps.ray) + 2 * (size_t)pid;
             const float4 r0 = rq[0], r1 = rq[1];
             const V3 rd(r0.w, r1.x, r1.y);
-            for (uint32_t k = 0; k < s.n_infinite; ++k) L = L + light_le(s, s.lights[s.infinite_lights[k]], rd) * beta;
+            add_escaped_le(s, rd, beta, L);
         }
         cq[0] = make_float4(L.r, L.g, L.b, c0.w);
         ps.meta(pid) = (meta & 0x00ffffffu) | ((flags & ~PF_CAMERA_RAY) << 24);
-        atomicAdd(&s_hist[bounces > 15u ? 15u : bounces], 1u);   // path.rs:219
+        hist_add(s_hist, bounces);   // path.rs:219
     }
     __syncthreads();
-    if (threadIdx.x < 16 && s_hist[threadIdx.x]) atomicAdd(&job.counters->path_len[threadIdx.x], (unsigned long long)s_hist[threadIdx.x]);
     counter_add(&job.counters->zero_num, zero_num);
-    counter_add(&job.counters->ref_asserts, (unsigned long long)n_assert);
-    counter_add(&job.counters->stages, n_valid);
-    counter_add(&job.counters->shade_items[kMissClass], n_valid);
-    counter_add(&job.counters->shade_bytes[kMissClass], n_bytes);
+    vertex_epilogue(s_hist, job.counters, &job.counters->shade_items[kMissClass], &job.counters->shade_bytes[kMissClass], n_valid, n_bytes, n_assert);
     (void)rc;
 }
 
@@ -225,7 +192,7 @@ __global__ __launch_bounds__(256, PT_MISS_WAVES) void k_shade_miss(DeviceScene s
 template <bool SPH>
 __global__ __launch_bounds__(256, PT_FILM_WAVES) void k_film_final(DeviceScene s, RenderConst rc, PathSoA ps, const float *filter_table, float *film_rgbw, DevCounters *counters) {
     __shared__ uint32_t s_hist[16];
-    if (threadIdx.x < 16) s_hist[threadIdx.x] = 0;
+    hist_init(s_hist);
     __syncthreads();
     PT_PROF_BEGIN   // not reported: the region table is k_shade's
     unsigned long long zero_num = 0, n_final = 0, n_bytes = 0;
@@ -247,15 +214,11 @@ __global__ __launch_bounds__(256, PT_FILM_WAVES) void k_film_final(DeviceScene s
             const float4 *rq = reinterpret_cast<const float4 *>(ps.ray) + 2 * (size_t)pid;
             const float4 r0 = rq[0], r1 = rq[1];
             const V3 rd(r0.w, r1.x, r1.y);
-            for (uint32_t k = 0; k < s.n_infinite; ++k) L = L + light_le(s, s.lights[s.infinite_lights[k]], rd) * beta;
+            add_escaped_le(s, rd, beta, L);
         }
-        atomicAdd(&s_hist[bounces > 15u ? 15u : bounces], 1u);   // path.rs:219
+        hist_add(s_hist, bounces);   // path.rs:219
     });
     __syncthreads();
-    if (threadIdx.x < 16 && s_hist[threadIdx.x]) atomicAdd(&counters->path_len[threadIdx.x], (unsigned long long)s_hist[threadIdx.x]);
     counter_add(&counters->zero_num, zero_num);
-    counter_add(&counters->ref_asserts, (unsigned long long)n_assert);
-    counter_add(&counters->stages, n_final);
-    counter_add(&counters->shade_items[kMissClass], n_final);
-    counter_add(&counters->shade_bytes[kMissClass], n_bytes);
+    vertex_epilogue(s_hist, counters, &counters->shade_items[kMissClass], &counters->shade_bytes[kMissClass], n_final, n_bytes, n_assert);
 }

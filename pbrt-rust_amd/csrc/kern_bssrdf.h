@@ -14,11 +14,10 @@ template <bool SPH, bool VOL>
 __global__ __launch_bounds__(256, PT_BSSRDF_WAVES) void k_bssrdf(DeviceScene s, RenderConst rc, SobolTables tabs, LightGrid grid, PathSoA ps, BssrdfJob job) {
     constexpr uint32_t LDS_DIMS = 56u;
     __shared__ uint32_t s_sobol[LDS_DIMS * kSobolNibWords];
-    __shared__ LdsQueue<1024> s_qext, s_qres, s_qsh, s_qmis;
-    __shared__ LdsQueue<VOL ? 1024 : 1> s_qself;   // volpath, grid media / shells: exit-point vertices waiting for stage B
+    __shared__ VertexQueues<1024, false, VOL> s_q;   // volpath, grid media / shells: exit-point vertices waiting for stage B (self)
     __shared__ uint32_t s_hist[16];
-    lq_init(s_qext); lq_init(s_qres); lq_init(s_qsh); lq_init(s_qmis); lq_init(s_qself);
-    if (threadIdx.x < 16) s_hist[threadIdx.x] = 0;
+    s_q.init();
+    hist_init(s_hist);
     sobol_stage_lds(s_sobol, tabs.nib, LDS_DIMS, threadIdx.x, blockDim.x);
     __syncthreads();
     PT_PROF_BEGIN
@@ -53,8 +52,7 @@ __global__ __launch_bounds__(256, PT_BSSRDF_WAVES) void k_bssrdf(DeviceScene s, 
         if (at_exit || dead) {
             uint32_t meta = ps.meta(pid);
             uint32_t flags = meta >> 24, bounces = (meta >> 16) & 0xffu;
-            Sampler smp; smp.index = ps.sobol_index(pid); smp.dim = meta & 0xffffu; smp.m32 = tabs.m32; smp.nib = tabs.nib; smp.lds = s_sobol; smp.lds_dims = LDS_DIMS; smp.overflow = false; smp.halton = rc.halton.enabled != 0; smp.prime = tabs.prime; smp.prime_sum = tabs.prime_sum; smp.perm = tabs.perm;
-            smp.base = 0xffffffffu;
+            Sampler smp = make_sampler(tabs, s_sobol, LDS_DIMS, ps.sobol_index(pid), meta & 0xffffu, rc.halton.enabled != 0);
             RGB L(ps.L_r(pid), ps.L_g(pid), ps.L_b(pid));
             RGB beta(ps.beta_r(pid), ps.beta_g(pid), ps.beta_b(pid));
             n_bytes += 4 + 8 + 12 + 12 + 12 + 12 + 4;
@@ -114,15 +112,7 @@ __global__ __launch_bounds__(256, PT_BSSRDF_WAVES) void k_bssrdf(DeviceScene s, 
                         if (__builtin_isinf(beta.y())) n_assert++;   // path.rs:201 / volpath.rs:210
                         if (sflags & BSDF_SPECULAR) flags |= PF_SPECULAR; else flags &= ~PF_SPECULAR;
                         V3 o; spawn_ray(it, wi, o);
-                        // path.rs:206-214 Russian roulette
-                        const RGB rrbeta = beta * ps.etascale(pid);
-                        bool rr_kill = false;
-                        if (rrbeta.max_component_value() < rc.rr_threshold && bounces > 3) {
-                            const float q = maxf(1.0f - rrbeta.max_component_value(), 0.05f);
-                            if (smp.get_1d() < q) rr_kill = true;
-                            else { beta = beta / (1.0f - q); if (__builtin_isinf(beta.y())) n_assert++; }   // path.rs:213
-                        }
-                        if (rr_kill) terminated = true;
+                        if (russian_roulette(rc, smp, beta, ps.etascale(pid), bounces, n_assert)) terminated = true;
                         else {
                             bounces += 1;
                             ps.ox(pid) = o.x; ps.oy(pid) = o.y; ps.oz(pid) = o.z;
@@ -137,36 +127,14 @@ __global__ __launch_bounds__(256, PT_BSSRDF_WAVES) void k_bssrdf(DeviceScene s, 
                 if (flags & (PF_PEND_SHADOW | PF_PEND_MIS)) { flags |= PF_DEAD; push_resolve = true; }
                 else { finished_bounces = (int)bounces; flags |= PF_FINISHED; }
             }
-            if (smp.overflow) atomicMax(job.error, (uint32_t)PT_ERR_SOBOL_DIMENSIONS);
-            ps.L_r(pid) = L.r; ps.L_g(pid) = L.g; ps.L_b(pid) = L.b;
-            ps.beta_r(pid) = beta.r; ps.beta_g(pid) = beta.g; ps.beta_b(pid) = beta.b;
-            ps.meta(pid) = (smp.dim & 0xffffu) | ((bounces & 0xffu) << 16) | (flags << 24);
+            store_vertex(ps, pid, L, beta, smp, bounces, flags, job.error);
         }
     }
-    lq_push(s_qext, pid, push_ext);
-    lq_push(s_qres, pid, push_resolve && job.shade_next0 != nullptr);   // (no miss pass: k_film_final ends the dead paths)
-    lq_push(s_qsh, pid, push_shadow);
-    lq_push(s_qmis, pid, push_mis);
-    if (VOL) lq_push(s_qself, pid, push_self);
-    if (finished_bounces >= 0) atomicAdd(&s_hist[finished_bounces > 15 ? 15 : finished_bounces], 1u);
-    __syncthreads();
-    lq_flush_nosync(s_qext, job.ext_next_count, job.ext_next, 256u, false);
-    lq_flush_nosync(s_qres, job.shade_next0_count, job.shade_next0, 256u, false);
-    lq_flush_nosync(s_qsh, job.shadow_count, job.shadow, 256u, false);
-    lq_flush_nosync(s_qmis, job.mis_count, job.mis, 256u, false);
-    if (VOL) lq_flush_nosync(s_qself, job.self_next_count, job.self_next, 256u, false);
-    __syncthreads();
+    s_q.push(job, pid, push_ext, push_resolve, push_shadow, push_mis, push_self);   // (resolve-only paths: no miss pass -- k_film_final ends the dead paths)
+    if (finished_bounces >= 0) hist_add(s_hist, (uint32_t)finished_bounces);
+    s_q.flush(job, 256u, false);
     }
-    lq_flush_nosync(s_qext, job.ext_next_count, job.ext_next, 0u, true);
-    lq_flush_nosync(s_qres, job.shade_next0_count, job.shade_next0, 0u, true);
-    lq_flush_nosync(s_qsh, job.shadow_count, job.shadow, 0u, true);
-    lq_flush_nosync(s_qmis, job.mis_count, job.mis, 0u, true);
-    if (VOL) lq_flush_nosync(s_qself, job.self_next_count, job.self_next, 0u, true);
-    __syncthreads();
-    if (threadIdx.x < 16 && s_hist[threadIdx.x]) atomicAdd(&job.counters->path_len[threadIdx.x], (unsigned long long)s_hist[threadIdx.x]);
+    s_q.flush(job, 0u, true);
     counter_add(&job.counters->zero_num, zero_num);
-    counter_add(&job.counters->ref_asserts, (unsigned long long)n_assert);
-    counter_add(&job.counters->stages, n_valid);
-    counter_add(&job.counters->bss_items, n_valid);
-    counter_add(&job.counters->bss_bytes, n_bytes);
+    vertex_epilogue(s_hist, job.counters, &job.counters->bss_items, &job.counters->bss_bytes, n_valid, n_bytes, n_assert);
 }

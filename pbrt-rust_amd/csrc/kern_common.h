@@ -21,17 +21,6 @@ using namespace ptd;
 // ---- wave-level helpers ------------------------------------------------------------------------
 PT_DEV uint32_t lane_id() { return __lane_id(); }
 
-// Stream compaction: append `value` for every lane with pred set; one atomic per wave.
-PT_DEV void queue_push(uint32_t *count, uint32_t *buf, uint32_t value, bool pred) {
-    unsigned long long mask = __ballot(pred);
-    if (mask == 0ull) return;
-    uint32_t lane = lane_id();
-    uint32_t leader = (uint32_t)__ffsll((long long)mask) - 1u;
-    uint32_t base = 0;
-    if (lane == leader) base = atomicAdd(count, (uint32_t)__popcll(mask));
-    base = __shfl(base, (int)leader);
-    if (pred) buf[base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = value;
-}
 PT_DEV unsigned long long wave_sum(unsigned long long v) {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
     return v;

@@ -34,14 +34,12 @@ __global__ __launch_bounds__(256, (shade_waves<MAXL, MODE, DIFF>())) void k_shad
     // (the five-lobe class flushes its queues every round -- 256-entry buffers: with the 60 KB lobe store, two of its workgroups fit a CU's
     //  LDS; its vertices cost ~0.8 ns each, so the extra global atomics, one per queue and 256 vertices, do not show)
     constexpr int QCAP = MAXL == 5 ? 256 : (MAXL == 2 && MODE == 0 && DIFF == 4) ? PT_P2_QCAP : 1024;
-    __shared__ LdsQueue<QCAP> s_qext, s_qres, s_qsh, s_qmis;
     constexpr bool SSS = MAXL == 5 || DIFF == 6;   // the launch can hold subsurface materials: the five-lobe class, or its smooth-dielectric-only form (DIFF 6: one FresnelSpecular lobe + the BSSRDF)
-    __shared__ LdsQueue<SSS ? QCAP : 1> s_qprobe;
-    __shared__ LdsQueue<(MODE == 3) ? QCAP : 1> s_qself;   // volpath with grid media: vertices waiting for stage B, back into this class's next queue
+    __shared__ VertexQueues<QCAP, SSS, MODE == 3> s_q;   // probe chains where SSS; volpath with grid media: vertices waiting for stage B, back into this class's next queue
     __shared__ uint32_t s_hist[16];
     __shared__ float s_lobes[lobe_store_words<MAXL>()];   // the two- and five-lobe classes keep their BxDFs here (dev_bsdf.h)
-    lq_init(s_qext); lq_init(s_qres); lq_init(s_qsh); lq_init(s_qmis); lq_init(s_qprobe); lq_init(s_qself);
-    if (threadIdx.x < 16) s_hist[threadIdx.x] = 0;
+    s_q.init();
+    hist_init(s_hist);
     PT_PROF_BEGIN
     sobol_stage_lds(s_sobol, tabs.nib, LDS_DIMS, threadIdx.x, blockDim.x);
     __syncthreads();
@@ -65,8 +63,8 @@ __global__ __launch_bounds__(256, (shade_waves<MAXL, MODE, DIFF>())) void k_shad
         uint32_t meta = __float_as_uint(c1.w);
         uint32_t flags = meta >> 24, bounces = (meta >> 16) & 0xffu;
         float etascale = c0.w;
-        Sampler smp; smp.index = (uint64_t)__float_as_uint(c2.x) | ((uint64_t)__float_as_uint(c2.y) << 32); smp.dim = meta & 0xffffu; smp.m32 = tabs.m32; smp.nib = tabs.nib; smp.lds = s_sobol; smp.lds_dims = LDS_DIMS; smp.overflow = false; smp.halton = MODE >= 1 && rc.halton.enabled != 0;   /* Halton scenes run the general kernels: the triangle-only ones stay Sobol'-only */ smp.prime = tabs.prime; smp.prime_sum = tabs.prime_sum; smp.perm = tabs.perm;
-        smp.base = 0xffffffffu;
+        Sampler smp = make_sampler(tabs, s_sobol, LDS_DIMS, (uint64_t)__float_as_uint(c2.x) | ((uint64_t)__float_as_uint(c2.y) << 32), meta & 0xffffu,
+                                   MODE >= 1 && rc.halton.enabled != 0);   // Halton scenes run the general kernels: the triangle-only ones stay Sobol'-only
         RGB L(c0.x, c0.y, c0.z);
         RGB beta(c1.x, c1.y, c1.z);
 
@@ -102,7 +100,7 @@ __global__ __launch_bounds__(256, (shade_waves<MAXL, MODE, DIFF>())) void k_shad
                     const uint32_t al = s.prim_light[hp];
                     L = L + (al != PT_NONE ? area_l(s.lights[al], si.n, -rd) : RGB(0.0f)) * beta;   // isect.le() of a non-emissive primitive is 0, and `L += beta * 0` still happens (path.rs:110): NaN for a non-finite beta
                 } else {
-                    for (uint32_t k = 0; k < s.n_infinite; ++k) L = L + light_le(s, s.lights[s.infinite_lights[k]], rd) * beta;
+                    add_escaped_le(s, rd, beta, L);
                 }
             }
             bool terminated = !found || bounces >= rc.max_depth;  // path.rs:120
@@ -246,7 +244,7 @@ __global__ __launch_bounds__(256, (shade_waves<MAXL, MODE, DIFF>())) void k_shad
                                 }
                             }
                         }
-                        // path.rs:206-214 Russian roulette
+                        // path.rs:206-214 Russian roulette (written out: through russian_roulette, kern_shade_common.h, several forms of this kernel move by a register -- profiles/r6/NOTES.md section 12)
                         RGB rrbeta = beta * etascale;
                         if (!to_probe && !rr_kill && rrbeta.max_component_value() < rc.rr_threshold && bounces > 3) {
                             const float q = maxf(1.0f - rrbeta.max_component_value(), 0.05f);
@@ -269,42 +267,19 @@ __global__ __launch_bounds__(256, (shade_waves<MAXL, MODE, DIFF>())) void k_shad
             }
         }
         PT_T(12);
-        if (smp.overflow) atomicMax(job.error, (uint32_t)PT_ERR_SOBOL_DIMENSIONS);
+        const uint32_t meta_out = vertex_meta(smp, bounces, flags, job.error);
         float4 *cw = reinterpret_cast<float4 *>(ps.core) + 4 * (size_t)pid;
         cw[0] = make_float4(L.r, L.g, L.b, etascale);
-        cw[1] = make_float4(beta.r, beta.g, beta.b, __uint_as_float((smp.dim & 0xffffu) | ((bounces & 0xffu) << 16) | (flags << 24)));
+        cw[1] = make_float4(beta.r, beta.g, beta.b, __uint_as_float(meta_out));
     }
     PT_T(13);
-    lq_push(s_qext, pid, push_ext);   // (grouped by the new ray's direction octant: trace no faster -- profiles/HISTORY.md; profiles/r6/experiments/settled_ab_hooks.patch)
-    lq_push(s_qres, pid, push_resolve && job.shade_next0 != nullptr);   // (no miss pass: the film kernel ends the dead paths, k_film_final)
-    lq_push(s_qsh, pid, push_shadow);
-    lq_push(s_qmis, pid, push_mis);
-    if (finished_bounces >= 0) atomicAdd(&s_hist[finished_bounces > 15 ? 15 : finished_bounces], 1u);  // path.rs:219 (LDS)
-    if constexpr (SSS) if (job.probe_next) lq_push(s_qprobe, pid, push_probe);
-    if constexpr (MODE == 3) lq_push(s_qself, pid, push_self);
-    __syncthreads();
-    lq_flush_nosync(s_qext, job.ext_next_count, job.ext_next, 256u, false);
-    lq_flush_nosync(s_qres, job.shade_next0_count, job.shade_next0, 256u, false);
-    lq_flush_nosync(s_qsh, job.shadow_count, job.shadow, 256u, false);
-    lq_flush_nosync(s_qmis, job.mis_count, job.mis, 256u, false);
-    if constexpr (SSS) if (job.probe_next) lq_flush_nosync(s_qprobe, job.probe_next_count, job.probe_next, 256u, false);
-    if constexpr (MODE == 3) lq_flush_nosync(s_qself, job.self_next_count, job.self_next, 256u, false);
-    __syncthreads();
+    s_q.push(job, pid, push_ext, push_resolve, push_shadow, push_mis, push_self, push_probe);
+    if (finished_bounces >= 0) hist_add(s_hist, (uint32_t)finished_bounces);  // path.rs:219 (LDS)
+    s_q.flush(job, 256u, false);
     }  // persistent loop over the queue
-    lq_flush_nosync(s_qext, job.ext_next_count, job.ext_next, 0u, true);
-    lq_flush_nosync(s_qres, job.shade_next0_count, job.shade_next0, 0u, true);
-    lq_flush_nosync(s_qsh, job.shadow_count, job.shadow, 0u, true);
-    lq_flush_nosync(s_qmis, job.mis_count, job.mis, 0u, true);
-    if constexpr (SSS) if (job.probe_next) lq_flush_nosync(s_qprobe, job.probe_next_count, job.probe_next, 0u, true);
-    if constexpr (MODE == 3) lq_flush_nosync(s_qself, job.self_next_count, job.self_next, 0u, true);
-    __syncthreads();
-    __syncthreads();   // s_hist complete
+    s_q.flush(job, 0u, true);   // (its closing barrier: s_hist complete)
     PT_PROF_END(job.counters);
-    if (threadIdx.x < 16 && s_hist[threadIdx.x]) atomicAdd(&job.counters->path_len[threadIdx.x], (unsigned long long)s_hist[threadIdx.x]);
     counter_add(&job.counters->zero_num, zero_num);
     counter_add(&job.counters->zero_den, zero_den);
-    counter_add(&job.counters->ref_asserts, (unsigned long long)n_assert);
-    counter_add(&job.counters->stages, n_valid);
-    counter_add(&job.counters->shade_items[job.cls], n_valid);
-    counter_add(&job.counters->shade_bytes[job.cls], n_bytes);
+    vertex_epilogue(s_hist, job.counters, &job.counters->shade_items[job.cls], &job.counters->shade_bytes[job.cls], n_valid, n_bytes, n_assert);
 }

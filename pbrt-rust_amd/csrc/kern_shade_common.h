@@ -1,4 +1,5 @@
-// kern_shade_common.h -- split out of the former single-file kernels.hip so that the translation units compile in parallel.
+// kern_shade_common.h -- what the kernels that finish a path vertex share (kern_shade.h, kern_bssrdf.h, kern_aux.h): region timers, resolve_pending / vol_chain_step / nee_vertex,
+// the vertex frame (LDS queue set, roulette, meta word, escaped-ray Le, histogram + epilogue), textured material parameters, camera-ray differentials.
 #pragma once
 #include "kern_common.h"
 // ---- shading ---------------------------------------------------------------------------------------------
@@ -174,6 +175,83 @@ template <bool SPH> PT_DEV bool vol_chain_step(const DeviceScene &s, const PathS
         nq[1] = make_float4(n1.x, n1.y, __uint_as_float(PT_NONE), n1.w); nq[3] = make_float4(n3.x, n3.y, n3.z, __uint_as_float(PT_NONE));
     }
     return false;
+}
+
+// ---- the vertex frame: what k_shade, k_bssrdf (kern_bssrdf.h) and k_shade_medium (kern_aux.h) share around the vertex itself -- a surface hit, a subsurface exit point,
+// a medium event. Each keeps its persistent loop and its record loads / stores written out (k_shade moves the core record as whole quads, the other two by field), and
+// the steps that moved a kernel's register count when they were shared (profiles/r6/NOTES.md section 12): "resolve the pending estimate, or walk a shell segment in stage B" and
+// "the path ends: dead with an estimate pending, or finished" in all three, the roulette in k_shade.
+
+// The block's LDS queues (kern_common.h: LdsQueue) in front of the job's global ones: continuation rays, resolve-only paths (to the miss class), shadow rays, MIS rays, and
+// where the kernel has them (one-entry stubs where not) probe chains (PROBE) and vertices waiting for stage B (SELF). Written against the field names ShadeJob and BssrdfJob share.
+template <int QCAP, bool PROBE, bool SELF> struct VertexQueues {
+    LdsQueue<QCAP> ext, res, sh, mis;
+    LdsQueue<PROBE ? QCAP : 1> probe;
+    LdsQueue<SELF ? QCAP : 1> self;
+    PT_DEV void init() { lq_init(ext); lq_init(res); lq_init(sh); lq_init(mis); lq_init(probe); lq_init(self); }
+    // where a finished vertex goes next (the kernels keep these flags as plain bools: as members of one struct they cost several k_shade forms a register)
+    template <class Job> PT_DEV void push(const Job &job, uint32_t pid, bool to_ext, bool to_resolve, bool to_shadow, bool to_mis, bool to_self = false, bool to_probe = false) {
+        lq_push(ext, pid, to_ext);   // (grouped by the new ray's direction octant: trace no faster -- profiles/HISTORY.md; profiles/r6/experiments/settled_ab_hooks.patch)
+        lq_push(res, pid, to_resolve && job.shade_next0 != nullptr);   // (no miss pass: the film kernel ends the dead paths, k_film_final; k_shade_medium pushed without this test: volpath always has the miss pass)
+        lq_push(sh, pid, to_shadow);
+        lq_push(mis, pid, to_mis);
+        if constexpr (PROBE) if (job.probe_next) lq_push(probe, pid, to_probe);
+        if constexpr (SELF) lq_push(self, pid, to_self);
+    }
+    // One flush round, all threads of the block together: a barrier makes the pushes visible, every queue with fewer than `reserve` free slots (or any entry, `force`) goes to
+    // its global queue, a barrier closes the round. In the loop: (256, false) after each round's pushes; after it: (0, true).
+    template <class Job> PT_DEV void flush(const Job &job, uint32_t reserve, bool force) {
+        __syncthreads();
+        lq_flush_nosync(ext, job.ext_next_count, job.ext_next, reserve, force);
+        lq_flush_nosync(res, job.shade_next0_count, job.shade_next0, reserve, force);
+        lq_flush_nosync(sh, job.shadow_count, job.shadow, reserve, force);
+        lq_flush_nosync(mis, job.mis_count, job.mis, reserve, force);
+        if constexpr (PROBE) if (job.probe_next) lq_flush_nosync(probe, job.probe_next_count, job.probe_next, reserve, force);
+        if constexpr (SELF) lq_flush_nosync(self, job.self_next_count, job.self_next, reserve, force);
+        __syncthreads();
+    }
+};
+
+// Russian roulette (path.rs:206-214, volpath.rs:171-176, 223): true when the path is killed, else beta is rescaled.
+PT_DEV bool russian_roulette(const RenderConst &rc, Sampler &smp, RGB &beta, float etascale, uint32_t bounces, uint32_t &n_assert) {
+    const RGB rrbeta = beta * etascale;
+    if (rrbeta.max_component_value() < rc.rr_threshold && bounces > 3) {
+        const float q = maxf(1.0f - rrbeta.max_component_value(), 0.05f);
+        if (smp.get_1d() < q) return true;
+        beta = beta / (1.0f - q); if (__builtin_isinf(beta.y())) n_assert++;   // path.rs:213, volpath.rs:223
+    }
+    return false;
+}
+
+// The meta word a vertex leaves: the sampler's next dimension, the bounce count, the path flags; and the Sobol' table's end, reported once per job.
+PT_DEV uint32_t vertex_meta(const Sampler &smp, uint32_t bounces, uint32_t flags, uint32_t *error) {
+    if (smp.overflow) atomicMax(error, (uint32_t)PT_ERR_SOBOL_DIMENSIONS);
+    return (smp.dim & 0xffffu) | ((bounces & 0xffu) << 16) | (flags << 24);
+}
+// ... with L and beta, field by field (k_bssrdf, k_shade_medium)
+PT_DEV void store_vertex(const PathSoA &ps, uint32_t pid, RGB L, RGB beta, const Sampler &smp, uint32_t bounces, uint32_t flags, uint32_t *error) {
+    const uint32_t meta = vertex_meta(smp, bounces, flags, error);
+    ps.L_r(pid) = L.r; ps.L_g(pid) = L.g; ps.L_b(pid) = L.b;
+    ps.beta_r(pid) = beta.r; ps.beta_g(pid) = beta.g; ps.beta_b(pid) = beta.b;
+    ps.meta(pid) = meta;
+}
+
+// path.rs:106-117, the ray escaped: the infinite lights' Le along it.
+PT_DEV void add_escaped_le(const DeviceScene &s, V3 rd, RGB beta, RGB &L) {
+    for (uint32_t k = 0; k < s.n_infinite; ++k) L = L + light_le(s, s.lights[s.infinite_lights[k]], rd) * beta;
+}
+
+// The block's path-length histogram (path.rs:219) in LDS, and the end of a kernel that finishes vertices: histogram and the thread's tallies to the job's counters. `items` /
+// `bytes`: the launch kind's work counters (zero_num / zero_den: the kernels that count them add them beside the call). Call block-convergent, after the barrier that follows the last hist_add.
+PT_DEV void hist_init(uint32_t *s_hist) { if (threadIdx.x < 16) s_hist[threadIdx.x] = 0; }
+PT_DEV void hist_add(uint32_t *s_hist, uint32_t bounces) { atomicAdd(&s_hist[bounces > 15u ? 15u : bounces], 1u); }
+PT_DEV void vertex_epilogue(const uint32_t *s_hist, DevCounters *c, unsigned long long *items, unsigned long long *bytes, unsigned long long n_valid, unsigned long long n_bytes,
+                            uint32_t n_assert) {
+    if (threadIdx.x < 16 && s_hist[threadIdx.x]) atomicAdd(&c->path_len[threadIdx.x], (unsigned long long)s_hist[threadIdx.x]);
+    counter_add(&c->ref_asserts, (unsigned long long)n_assert);
+    counter_add(&c->stages, n_valid);
+    counter_add(items, n_valid);
+    counter_add(bytes, n_bytes);
 }
 
 // uniform_sample_onelight + estimate_direct (integrator.rs:81-237) at one vertex: samples the light and the BSDF,

@@ -24,7 +24,10 @@ template <class... T> std::string symbol(const char *kernel, T... args) { std::s
 
 // (launch(sc, name, fn, ...): host_common.h)
 template <class... P, class... A> void launch(pt_scene *sc, const Variant<P...> &v, dim3 blocks, dim3 threads, const A &...args) { launch(sc, v.name, v.fn, blocks, threads, args...); }
-static dim3 blocks_for(uint32_t n_upper, uint32_t per_cu) { return dim3(std::min<uint32_t>((n_upper + 255) / 256, (uint32_t)g_num_cus * per_cu)); }   // persistent blocks of 256 threads
+// TEST HOOK (env PT_TEST_MAX_BLOCKS, read at every render call like PT_TEST_MAX_ITERATIONS, by the thread that launches): a cap on the persistent grids. A persistent kernel's
+// result may not depend on its grid, and under a cap of 1 the one block makes many rounds on a tiny render -- the mid-loop queue flushes (kern_shade_common.h: VertexQueues::flush) at test size.
+static thread_local uint32_t t_max_blocks = ~0u;
+static dim3 blocks_for(uint32_t n_upper, uint32_t per_cu) { return dim3(std::min(std::min<uint32_t>((n_upper + 255) / 256, (uint32_t)g_num_cus * per_cu), t_max_blocks)); }   // persistent blocks of 256 threads
 static bool general_geometry(const pt_scene *sc) { return sc->ds.n_spheres > 0 || sc->ds.n_instances > 0; }   // the SPH forms: spheres or instances besides world-space triangles
 
 // k_trace (tu_trace.hip): ANY 0..2 x MODE 0..3 x QUADK 0..2, and the probe walk (closest hit, PROBE) in the same MODE x QUADK -- row 3 of the table
@@ -787,6 +790,8 @@ static int render_range(pt_scene *sc, const PtRenderParams *rp, uint32_t first, 
     }
     int max_iterations = 1 << 20;   // wavefront iterations per pass. TEST HOOK (env PT_TEST_MAX_ITERATIONS, read at every call): a smaller cap, so that the PT_ERR_PROBE_CHAIN return of a pass that does not end can be tested
     if (const char *e = getenv("PT_TEST_MAX_ITERATIONS")) { const int v = atoi(e); if (v > 0) max_iterations = v; }
+    struct CapReset { ~CapReset() { t_max_blocks = ~0u; } } cap_reset;   // TEST HOOK (env PT_TEST_MAX_BLOCKS): see blocks_for; the cap holds for this call alone
+    if (const char *e = getenv("PT_TEST_MAX_BLOCKS")) { const int v = atoi(e); if (v > 0) t_max_blocks = (uint32_t)v; }
     int eff = 0;
     auto lazy_grid = [&]() { return sc->grid[eff].cell_ptr != nullptr; };   // first-touch voxels (PT_LS_SPATIAL_LAZY)
     auto prepare = [&]() {
