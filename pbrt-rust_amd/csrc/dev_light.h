@@ -64,6 +64,12 @@ PT_DEV void spawn_ray_to(const IData &a, const IData &b, V3 &o, V3 &d) {  // int
     d = t - o;
 }
 
+// DeviceScene::env_u in the constant address space: the block is written before any render starts and every lane reads the same address, so its loads are scalar loads
+// into scalar registers (through a plain global pointer the compiler issues per-lane vector loads, since the kernels store to global memory)
+typedef const __attribute__((address_space(4))) EnvUniform *EnvBlock;
+typedef const __attribute__((address_space(4))) float *ConstFloats;
+PT_DEV EnvBlock env_block(const DeviceScene &s) { return (EnvBlock)s.env_u; }
+
 // MIPMap::lookup(st, 0.0) == triangle(level 0) with Repeat wrap (mipmap.rs:202-223,295-327)
 PT_DEV RGB env_lookup(const DeviceScene &s, P2 st) {
     int w = (int)s.env_w, h = (int)s.env_h;
@@ -77,6 +83,15 @@ PT_DEV RGB env_lookup(const DeviceScene &s, P2 st) {
         int64_t r = v % n; if (r < 0) r += n;
         return (int)r;
     };
+    if (w == 1 && h == 1) {   // a constant environment: all four texels are texel 0, read at a uniform address (EnvUniform); the weights and the sum stay per lane
+        const EnvBlock e = env_block(s);
+        const RGB c(e->texel0[0], e->texel0[1], e->texel0[2]);
+        RGB tmp1 = c * (ds * dt);
+        RGB tmp2 = c * (ds * (1.0f - dt));
+        RGB tmp3 = c * ((1.0f - ds) * dt);
+        RGB tmp4 = c * ((1.0f - ds) * (1.0f - dt));
+        return tmp4 + tmp3 + tmp2 + tmp1;
+    }
     const int sa = wrap(s0, w), sb = wrap(s0 + 1, w), ta = wrap(t0, h), tb = wrap(t0 + 1, h);
     auto texel = [&](int si, int ti) -> RGB {
         const float *p = s.env_texels + 3 * ((size_t)ti * w + si);
@@ -89,43 +104,88 @@ PT_DEV RGB env_lookup(const DeviceScene &s, P2 st) {
     return tmp4 + tmp3 + tmp2 + tmp1;
 }
 
-PT_DEV bool light_is_delta(const PtLight &L) { return L.type == PT_LIGHT_DISTANT || L.type == PT_LIGHT_POINT || L.type == PT_LIGHT_SPOT; }
+// A light's record header (dev_scene.h: light_rec_head + the triangle's bits): quad 0 word 3 of its record
+PT_DEV uint32_t light_head(const DeviceScene &s, uint32_t li) { return __float_as_uint(s.light_rec[6 * (size_t)li].w); }
+PT_DEV uint32_t head_type(uint32_t head) { return (head >> kLrecTypeShift) & kLrecTypeMask; }
+PT_DEV bool head_is_delta(uint32_t head) { return (head & kLrecDelta) != 0u; }
 
 PT_DEV RGB area_l(const PtLight &L, V3 n, V3 w) {  // diffuse.rs:71-79
     if (L.two_sided || dot(n, w) > 0.0f) return RGB(L.L[0], L.L[1], L.L[2]);
     return RGB(0.0f);
 }
 // A triangle area light from DeviceScene::light_rec
-struct LightTri { V3 p0, p1, p2, n_sample, n_pdf; uint32_t fl, tri; float area, inv_area; RGB Lemit; bool two_sided, degenerate; };
+struct LightTri { V3 p0, p1, p2, n_sample, n_pdf; uint32_t fl, tri, head; float area, inv_area; RGB Lemit; bool two_sided, degenerate; };   // head: written for every light, valid record or not
 PT_DEV bool load_light_tri(const DeviceScene &s, uint32_t li, LightTri &t, bool for_pdf) {
     const float4 *r = s.light_rec + 6 * (size_t)li;
     const float4 q0 = r[0], q1 = r[1], q2 = r[2];
     t.p0 = V3(q0.x, q0.y, q0.z); t.p1 = V3(q1.x, q1.y, q1.z); t.p2 = V3(q2.x, q2.y, q2.z);
     const uint32_t bits = __float_as_uint(q0.w);
-    t.fl = bits & 0xffu; t.degenerate = (bits & 0x200u) != 0u; t.tri = __float_as_uint(q1.w); t.area = q2.w;
+    t.head = bits; t.fl = bits & 0xffu; t.degenerate = (bits & kLrecDegenerate) != 0u; t.tri = __float_as_uint(q1.w); t.area = q2.w;
     if (for_pdf) { const float4 q5 = r[5]; t.n_pdf = V3(q5.x, q5.y, q5.z); }
     else {
         const float4 q3 = r[3], q4 = r[4];
         t.Lemit = RGB(q3.x, q3.y, q3.z); t.two_sided = __float_as_uint(q3.w) != 0u;
         t.n_sample = V3(q4.x, q4.y, q4.z); t.inv_area = q4.w;
     }
-    return (bits & 0x100u) != 0u;
+    return (bits & kLrecValid) != 0u;
+}
+// Lemit / two_sided of ANY area light from its record's fourth quad (k_light_area writes it for every light): diffuse.rs:71-79
+PT_DEV RGB area_l_rec(const DeviceScene &s, uint32_t li, V3 n, V3 w) {
+    const float4 q3 = s.light_rec[6 * (size_t)li + 3];
+    return (__float_as_uint(q3.w) != 0u || dot(n, w) > 0.0f) ? RGB(q3.x, q3.y, q3.z) : RGB(0.0f);
 }
 PT_DEV RGB area_l(const LightTri &t, V3 n, V3 w) { return (t.two_sided || dot(n, w) > 0.0f) ? t.Lemit : RGB(0.0f); }   // diffuse.rs:71-79
 PT_DEV M4 ldm4(const float *p) { M4 m; for (int i = 0; i < 16; ++i) m.m[i] = p[i]; return m; }
+PT_DEV M4 ldm4(ConstFloats p) { M4 m; for (int i = 0; i < 16; ++i) m.m[i] = p[i]; return m; }
 
-PT_DEV RGB light_le(const DeviceScene &s, const PtLight &L, V3 ray_d) {  // infinite.rs:118-126 (others: 0)
-    if (L.type != PT_LIGHT_INFINITE) return RGB(0.0f);
-    V3 w = normalize(xf_vector(ldm4(L.world_to_light), ray_d));
+// An infinite light's transforms: the scene's first one from the uniform block (EnvUniform: scalar registers, the same values for every lane of every launch),
+// any further one through its PtLight
+PT_DEV M4 env_world_to_light(const DeviceScene &s, uint32_t li) { const EnvBlock e = env_block(s); return li == e->light ? ldm4(e->world_to_light) : ldm4(s.lights[li].world_to_light); }
+PT_DEV M4 env_light_to_world(const DeviceScene &s, uint32_t li) { const EnvBlock e = env_block(s); return li == e->light ? ldm4(e->light_to_world) : ldm4(s.lights[li].light_to_world); }
+PT_DEV RGB light_le_infinite(const DeviceScene &s, uint32_t li, V3 ray_d) {  // infinite.rs:118-126
+    V3 w = normalize(xf_vector(env_world_to_light(s, li), ray_d));
     P2 st(spherical_phi(w) * kInv2Pi, spherical_theta(w) * kInvPi);
     return env_lookup(s, st);
+}
+PT_DEV RGB light_le(const DeviceScene &s, uint32_t li, V3 ray_d) {  // Light::le: infinite.rs:118-126, every other light 0 -- the kind from the record's header
+    if (head_type(light_head(s, li)) != PT_LIGHT_INFINITE) return RGB(0.0f);
+    return light_le_infinite(s, li, ray_d);
+}
+
+// Distribution1D::sample_continuous (sampling.rs:38-64) of a TWO-entry function whose cdf, function and integral are at hand (a row or the marginal of a 2 x 2
+// importance image, from the uniform block): find_interval_cdf's bisection with its comparisons and clamp, over registers, then the expressions of dist_sample_continuous
+PT_DEV float dist2_sample_continuous(float c0, float c1, float c2, float f0, float f1, float func_int, float u, float &pdf, int &off) {
+    int first = 0, len = 3;
+    while (len > 0) {
+        const int half = len >> 1, middle = first + half;
+        const float cm = middle == 0 ? c0 : middle == 1 ? c1 : c2;
+        if (cm <= u) { first = middle + 1; len -= half + 1; }
+        else len = half;
+    }
+    const int r = first - 1;
+    off = r < 0 ? 0 : (r > 1 ? 1 : r);
+    const float co = off == 0 ? c0 : c1, cn = off == 0 ? c1 : c2;
+    float du = u - co;
+    float diff = cn - co;
+    if (diff > 0.0f) du /= diff;
+    pdf = (func_int > 0.0f) ? (off == 0 ? f0 : f1) / func_int : 0.0f;
+    return ((float)off + du) / 2.0f;
 }
 
 // Distribution2D::sample_continuous / pdf over the env importance image (sampling.rs:119-145)
 PT_DEV P2 env_sample_continuous(const DeviceScene &s, P2 u, float &pdf) {
     int nu = 2 * (int)s.env_w, nv = 2 * (int)s.env_h;
-    Dist1D marg{s.env_marg_func, s.env_marg_cdf, s.env_marg_int, nv};
     float pdf1, pdf0; int v, dummy;
+    if (s.env_w == 1 && s.env_h == 1) {   // a 2 x 2 importance image: the whole distribution comes from the uniform block, 17 floats in scalar registers
+        const EnvUniform __attribute__((address_space(4))) &e = *env_block(s);
+        float d1 = dist2_sample_continuous(e.marg_cdf[0], e.marg_cdf[1], e.marg_cdf[2], e.row_int[0], e.row_int[1], e.marg_int, u.y, pdf1, v);
+        const bool v0 = v == 0;
+        float d0 = dist2_sample_continuous(v0 ? e.row_cdf[0][0] : e.row_cdf[1][0], v0 ? e.row_cdf[0][1] : e.row_cdf[1][1], v0 ? e.row_cdf[0][2] : e.row_cdf[1][2],
+                                           v0 ? e.row_func[0][0] : e.row_func[1][0], v0 ? e.row_func[0][1] : e.row_func[1][1], v0 ? e.row_int[0] : e.row_int[1], u.x, pdf0, dummy);
+        pdf = pdf0 * pdf1;
+        return P2(d0, d1);
+    }
+    Dist1D marg{s.env_marg_func, s.env_marg_cdf, s.env_marg_int, nv};
     float d1 = dist_sample_continuous(marg, u.y, pdf1, v);
     Dist1D cond{s.env_func + (size_t)v * nu, s.env_cdf + (size_t)v * (nu + 1), s.env_func_int[v], nu};
     float d0 = dist_sample_continuous(cond, u.x, pdf0, dummy);
@@ -136,6 +196,7 @@ PT_DEV float env_pdf(const DeviceScene &s, P2 p) {
     int nu = 2 * (int)s.env_w, nv = 2 * (int)s.env_h;
     uint32_t iu = f2u32_sat(p.x * (float)nu); if (iu > (uint32_t)(nu - 1)) iu = nu - 1;
     uint32_t iv = f2u32_sat(p.y * (float)nv); if (iv > (uint32_t)(nv - 1)) iv = nv - 1;
+    if (s.env_w == 1 && s.env_h == 1) { const EnvBlock e = env_block(s); return (iv == 0 ? (iu == 0 ? e->row_func[0][0] : e->row_func[0][1]) : (iu == 0 ? e->row_func[1][0] : e->row_func[1][1])) / e->marg_int; }
     return s.env_func[(size_t)iv * nu + iu] / s.env_marg_int;
 }
 
@@ -186,12 +247,14 @@ PT_DEV IData sphere_sample_interaction(const PtSphere &S, const IData &ref, P2 u
     return it;
 }
 
-// Light::sample_li. Returns Li; fills wi, pdf and the far end of the visibility segment.
-template <bool SPH> PT_DEV RGB light_sample_li(const DeviceScene &s, uint32_t li, const IData &ref, P2 u, V3 &wi, float &pdf, IData &p1) {
+// Light::sample_li. Returns Li; fills wi, pdf and the far end of the visibility segment; `head`: the light's record header (type, delta bit), read on the way.
+template <bool SPH> PT_DEV RGB light_sample_li_rec(const DeviceScene &s, uint32_t li, const IData &ref, P2 u, V3 &wi, float &pdf, IData &p1, uint32_t &head) {
     p1.p = V3(); p1.p_error = V3(); p1.n = V3();
     {   // a triangle area light (diffuse.rs:95-112 + shape.rs:40-58 + triangle.rs:556-584), everything from its record
         LightTri t;
-        if (load_light_tri(s, li, t, false)) {
+        const bool is_tri = load_light_tri(s, li, t, false);
+        head = t.head;
+        if (is_tri) {
             const float su0 = sqrtf(u.x);
             const float b0 = 1.0f - su0, b1 = u.y * su0;  // uniform_sample_triangle, sampling.rs:250-254
             IData it;
@@ -219,9 +282,11 @@ template <bool SPH> PT_DEV RGB light_sample_li(const DeviceScene &s, uint32_t li
             return area_l(t, it.n, -wi);
         }
     }
-    const PtLight &L = s.lights[li];
-    switch (L.type) {
+    // the kind from the record's header; PtLight is gathered only by the kinds that read its fields
+    switch (head_type(head)) {
     case PT_LIGHT_DIFFUSE_AREA: {  // diffuse.rs:95-112 + shape.rs:40-58 + triangle.rs:556-584
+        if (!SPH) { pdf = 0.0f; return RGB(0.0f); }   // the scene holds no sphere (triangle lights were served from their record above)
+        const PtLight &L = s.lights[li];
         if (SPH && (s.prim_shape[L.prim] >> 30) == PT_SHAPE_SPHERE && s.spheres[s.prim_shape[L.prim] & 0x3fffffffu].kind == PT_QUADRIC_DISK) {
             // Disk::sample (disk.rs:124-139: the whole disk of `radius`, normal from (0, 0, 0.1)) + Shape::sample_interaction (shape.rs:40-52)
             const PtSphere &S = s.spheres[s.prim_shape[L.prim] & 0x3fffffffu];
@@ -254,18 +319,21 @@ template <bool SPH> PT_DEV RGB light_sample_li(const DeviceScene &s, uint32_t li
         pdf = 0.0f; return RGB(0.0f);   // (triangle lights were served from their record above)
     }
     case PT_LIGHT_DISTANT: {  // distant.rs:64-84
+        const PtLight &L = s.lights[li];
         V3 wl(L.dir[0], L.dir[1], L.dir[2]);
         wi = wl; pdf = 1.0f;
         p1.p = ref.p + wl * (2.0f * s.world_radius);
         return RGB(L.L[0], L.L[1], L.L[2]);
     }
     case PT_LIGHT_POINT: {  // point.rs:52-69
+        const PtLight &L = s.lights[li];
         V3 pl(L.pos[0], L.pos[1], L.pos[2]);
         wi = normalize(pl - ref.p); pdf = 1.0f;
         p1.p = pl;
         return RGB(L.L[0], L.L[1], L.L[2]) / distance_squared(pl, ref.p);
     }
     case PT_LIGHT_SPOT: {  // spot.rs:48-56,71-87
+        const PtLight &L = s.lights[li];
         V3 pl(L.pos[0], L.pos[1], L.pos[2]);
         wi = normalize(pl - ref.p); pdf = 1.0f;
         p1.p = pl;
@@ -285,7 +353,7 @@ template <bool SPH> PT_DEV RGB light_sample_li(const DeviceScene &s, uint32_t li
         dm_sincosf(theta, sin_t, cos_t);
         dm_sincosf(phi, sin_p, cos_p);
         V3 v(sin_t * cos_p, sin_t * sin_p, cos_t);
-        wi = xf_vector(ldm4(L.light_to_world), v);
+        wi = xf_vector(env_light_to_world(s, li), v);
         pdf = map_pdf / (2.0f * kPi * kPi * sin_t);
         if (sin_t == 0.0f) pdf = 0.0f;
         p1.p = ref.p + wi * (2.0f * s.world_radius);
@@ -294,13 +362,20 @@ template <bool SPH> PT_DEV RGB light_sample_li(const DeviceScene &s, uint32_t li
     default: pdf = 0.0f; return RGB(0.0f);
     }
 }
+template <bool SPH> PT_DEV RGB light_sample_li(const DeviceScene &s, uint32_t li, const IData &ref, P2 u, V3 &wi, float &pdf, IData &p1) {
+    uint32_t head;
+    return light_sample_li_rec<SPH>(s, li, ref, u, wi, pdf, p1, head);
+}
 
 // Light::pdf_li (area: Shape::pdf_wi re-intersects the light's own triangle, shape.rs:63-82)
 template <bool SPH> PT_DEV float light_pdf_li(const DeviceScene &s, uint32_t li, const IData &ref, V3 wi) {
+    uint32_t type;   // from the record's header
     {   // Shape::pdf_wi of a triangle light (shape.rs:63-82): intersect the light's own triangle, without a shape (no orientation from
         // shading normals: interaction.n is the geometric normal, flipped by the triangle's flags -- triangle.rs:266-392 with `s` = None)
         LightTri t;
-        if (load_light_tri(s, li, t, true)) {
+        const bool is_tri = load_light_tri(s, li, t, true);
+        type = head_type(t.head);
+        if (is_tri) {
             V3 o; spawn_ray(ref, wi, o);
             float th, b0, b1, b2;
             if (!tri_hit_params(t.p0, t.p1, t.p2, o, wi, PT_INF, th, b0, b1, b2)) return 0.0f;
@@ -312,8 +387,16 @@ template <bool SPH> PT_DEV float light_pdf_li(const DeviceScene &s, uint32_t li,
             return pdf;
         }
     }
-    const PtLight &L = s.lights[li];
-    if (SPH && L.type == PT_LIGHT_DIFFUSE_AREA && (s.prim_shape[L.prim] >> 30) == PT_SHAPE_SPHERE && s.spheres[s.prim_shape[L.prim] & 0x3fffffffu].kind == PT_QUADRIC_DISK) {
+    if (type == PT_LIGHT_INFINITE) {  // infinite.rs:128-138
+        V3 w = xf_vector(env_world_to_light(s, li), wi);
+        float theta = spherical_theta(w), phi = spherical_phi(w);
+        float sin_t = dm_sinf(theta);
+        if (sin_t == 0.0f) return 0.0f;
+        return env_pdf(s, P2(phi * kInv2Pi, theta * kInvPi)) / (2.0f * kPi * kPi * sin_t);
+    }
+    if (!SPH || type != PT_LIGHT_DIFFUSE_AREA) return 0.0f;   // delta lights; area lights of a scene without spheres were served from their record above
+    const PtLight &L = s.lights[li];   // a sphere or a disk light
+    if (SPH && (s.prim_shape[L.prim] >> 30) == PT_SHAPE_SPHERE && s.spheres[s.prim_shape[L.prim] & 0x3fffffffu].kind == PT_QUADRIC_DISK) {
         // Shape::pdf_wi (shape.rs:59-73): intersect without a shape (no orientation flip), signed cosine
         const PtSphere &S = s.spheres[s.prim_shape[L.prim] & 0x3fffffffu];
         V3 o; spawn_ray(ref, wi, o);
@@ -323,7 +406,7 @@ template <bool SPH> PT_DEV float light_pdf_li(const DeviceScene &s, uint32_t li,
         if (__builtin_isinf(pdf)) pdf = 0.0f;
         return pdf;
     }
-    if (SPH && L.type == PT_LIGHT_DIFFUSE_AREA && (s.prim_shape[L.prim] >> 30) == PT_SHAPE_SPHERE) {  // Sphere::pdf_wi (sphere.rs:380-395)
+    if (SPH && (s.prim_shape[L.prim] >> 30) == PT_SHAPE_SPHERE) {  // Sphere::pdf_wi (sphere.rs:380-395)
         const PtSphere &S = s.spheres[s.prim_shape[L.prim] & 0x3fffffffu];
         const V3 pcenter = xf_point(ldm4g(S.object_to_world), V3(0.0f, 0.0f, 0.0f));
         const V3 porigin = offset_ray_origin(ref.p, ref.p_error, ref.n, pcenter - ref.p);
@@ -339,15 +422,7 @@ template <bool SPH> PT_DEV float light_pdf_li(const DeviceScene &s, uint32_t li,
         const float cos_thetamax = sqrtf(maxf(1.0f - sin_thetamax2, 0.0f));
         return 1.0f / (2.0f * kPi * (1.0f - cos_thetamax));
     }
-    if (L.type == PT_LIGHT_DIFFUSE_AREA) return 0.0f;   // (triangle lights were served from their record above)
-    if (L.type == PT_LIGHT_INFINITE) {  // infinite.rs:128-138
-        V3 w = xf_vector(ldm4(L.world_to_light), wi);
-        float theta = spherical_theta(w), phi = spherical_phi(w);
-        float sin_t = dm_sinf(theta);
-        if (sin_t == 0.0f) return 0.0f;
-        return env_pdf(s, P2(phi * kInv2Pi, theta * kInvPi)) / (2.0f * kPi * kPi * sin_t);
-    }
-    return 0.0f;
+    return 0.0f;   // (triangle lights were served from their record above)
 }
 
 // ---- light-selection distributions (lightdistrib.rs) -------------------------------------------------

@@ -74,6 +74,24 @@ struct DevBssTable { int n_rho, n_radius; const float *rho_samples, *radius_samp
 // MIPMap pyramid on the device (PtImage + per-level offsets in floats)
 struct DevImage { uint32_t width, height, n_levels, channels; const float *texels; uint32_t level_offset[16]; };
 
+// What the shade kernels read of the environment light through ONE wave-uniform pointer (DeviceScene::env_u, scalar loads) instead of through a per-lane PtLight address:
+// the transforms of the scene's FIRST infinite light (`light`; PT_NONE: the scene has none -- further infinite lights keep the PtLight path), and, for a 1 x 1 map
+// (a constant environment: a 2 x 2 importance image), the whole of what sampling it reads -- the texel, the marginal Distribution1D (its function = row_int) and the
+// two conditional rows, the values of DeviceScene::env_texels / env_marg_cdf / env_marg_int / env_func_int / env_cdf / env_func. Larger maps leave the tables zero.
+struct EnvUniform {
+    uint32_t light;
+    float world_to_light[16], light_to_world[16];
+    float texel0[3];
+    float marg_cdf[3], marg_int, row_int[2];
+    float row_cdf[2][3], row_func[2][2];
+};
+// Header bits of a light's record (DeviceScene::light_rec, quad 0 word 3) above the triangle's PT_TRI_* byte: every light carries its type and whether it is a delta light
+// (light.rs:24-31: DeltaPosition | DeltaDirection)
+constexpr uint32_t kLrecValid = 0x100u, kLrecDegenerate = 0x200u, kLrecDelta = 0x400u, kLrecTypeShift = 12, kLrecTypeMask = 15u;
+PT_HD uint32_t light_rec_head(uint32_t type) {
+    return ((type & kLrecTypeMask) << kLrecTypeShift) | ((type == PT_LIGHT_DISTANT || type == PT_LIGHT_POINT || type == PT_LIGHT_SPOT) ? kLrecDelta : 0u);
+}
+
 struct DeviceScene {
     const WideNode *wide; uint32_t n_nodes;   // n_nodes = nodes of the reference tree (0 => empty scene)
     float root_min[3], root_max[3]; uint32_t root_ref;  // the root's own bounds and reference
@@ -92,7 +110,9 @@ struct DeviceScene {
     // area light and evaluating its pdf read, in one place instead of behind the chain lights -> prim_shape -> indices -> P, with the
     // per-light constants of both computed once by k_light_area (the same instruction sequences the shade kernels ran per vertex).
     // flags: the triangle's PT_TRI_* byte | 0x100 = the record is valid | 0x200 = Triangle::intersect rejects every hit (degenerate
-    // partials, triangle.rs:236-264); n_sample = Triangle::sample's normal before the face-forward to interpolated normals
+    // partials, triangle.rs:236-264) | light_rec_head(type): 0x400 = a delta light, bits 12-15 = the light's type -- these and the {Lemit, two_sided} quad are
+    // written for EVERY light, so the shade kernels learn a light's kind from the record they read anyway and gather PtLight only for the kinds that need
+    // its fields (point, spot, distant, sphere and disk lights, infinite lights after the first); n_sample = Triangle::sample's normal before the face-forward to interpolated normals
     // (triangle.rs:566-577), n_pdf = the interaction normal Triangle::intersect leaves without a shape (triangle.rs:283-300)
     const float4 *light_rec;
     const uint32_t *infinite_lights; uint32_t n_infinite;
@@ -100,10 +120,12 @@ struct DeviceScene {
     const DevBssTable *bss_tables; uint32_t n_bss_tables;   // subsurface materials (row a23)
     const PtMedium *media; uint32_t n_media;                 // media + per-primitive MediumInterface (volpath, dev_medium.h)
     uint32_t has_shells;                                     // a primitive without a material: a medium-interface shell (api.rs:597; volpath's transmittance loops walk through it)
-    const DevGridAux *grid_aux; uint32_t has_grid;           // per medium: GridDensityMedium's device density array, sigma_t, 1 / max density (grid.rs:46-60); any grid medium in the scene
+    const DevGridAux *grid_aux; uint32_t has_grid; uint32_t n_textures;   // per medium: GridDensityMedium's device density array, sigma_t, 1 / max density (grid.rs:46-60); any grid medium in the scene
     const uint32_t *prim_med_in; const uint32_t *prim_med_out;
     // textures (8f-1): nodes, one postfix program per node (tex_prog[tex_prog_offset[i] .. tex_prog_offset[i+1])), images
-    const PtTexture *textures; uint32_t n_textures; const uint32_t *tex_prog_offset; const uint32_t *tex_prog;
+    const PtTexture *textures;           // (n_textures: beside has_grid, where padding was, so that env_u takes its place and no other field moves -- k_trace keeps the struct on its stack)
+    const EnvUniform *env_u;             // the environment light's uniform block, always set (dev_light.h reads it through the constant address space: scalar loads)
+    const uint32_t *tex_prog_offset; const uint32_t *tex_prog;
     const DevImage *images; const float *ewa_lut;
     const int32_t *tri_alpha; const int32_t *tri_shadow_alpha;   // per triangle float-texture index or -1 (NULL: no masks)
     // env map

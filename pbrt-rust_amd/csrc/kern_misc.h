@@ -44,12 +44,12 @@ __global__ void k_mark_leaf_ends(TriPacket *leaf, const uint32_t *last_index, ui
     if (i < n) leaf[last_index[i]].flags |= TP_LAST;
 }
 
-__global__ void k_light_area(DeviceScene s, float *area, float4 *rec) {  // DiffuseAreaLight::new -> shape.area(); DeviceScene::light_rec
+__global__ void k_light_area(DeviceScene s, const uint32_t *head, float *area, float4 *rec) {  // DiffuseAreaLight::new -> shape.area(); DeviceScene::light_rec (head: the plan's light_rec_head per light)
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= s.n_lights) return;
     float a = 0.0f;
     const PtLight &L = s.lights[i];
-    float4 r0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), r1 = r0, r2 = r0, r4 = r0, r5 = r0;
+    float4 r0 = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(head[i])), r1 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), r2 = r1, r4 = r1, r5 = r1;
     if (L.type == PT_LIGHT_DIFFUSE_AREA) {
         uint32_t shape = s.prim_shape[L.prim];
         if ((shape >> 30) == PT_SHAPE_TRIANGLE) {
@@ -66,7 +66,7 @@ __global__ void k_light_area(DeviceScene s, float *area, float4 *rec) {  // Diff
             V3 dpdu, dpdv;
             const bool degenerate = !tri_partials(p0, p1, p2, uv, dpdu, dpdv);
             r4 = make_float4(ns.x, ns.y, ns.z, 1.0f / a); r5 = make_float4(np.x, np.y, np.z, 0.0f);
-            r0 = make_float4(p0.x, p0.y, p0.z, __uint_as_float(fl | 0x100u | (degenerate ? 0x200u : 0u)));
+            r0 = make_float4(p0.x, p0.y, p0.z, __uint_as_float(fl | kLrecValid | (degenerate ? kLrecDegenerate : 0u) | head[i]));
             r1 = make_float4(p1.x, p1.y, p1.z, __uint_as_float(tri)); r2 = make_float4(p2.x, p2.y, p2.z, a);
         } else {  // Sphere::area (sphere.rs:291-293)
             const PtSphere &S = s.spheres[shape & 0x3fffffffu];

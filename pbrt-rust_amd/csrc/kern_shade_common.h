@@ -68,7 +68,6 @@ template <bool SPH, bool VOL = false, bool EARLY = false> PT_DEV void resolve_pe
     if (flags & PF_PEND_MIS) {
         const float4 *mq = reinterpret_cast<const float4 *>(ps.mis) + 4 * (size_t)pid;
         const float4 m0 = EARLY ? e0 : mq[0], m1 = EARLY ? e1 : mq[1], m2 = EARLY ? e2 : mq[2], m3 = EARLY ? e3 : mq[3];
-        const PtLight &Lt = s.lights[li];
         V3 wi(m0.w, m1.x, m1.y);
         RGB lrad(0.0f);
         const uint32_t mp = __float_as_uint(m2.x);
@@ -76,9 +75,9 @@ template <bool SPH, bool VOL = false, bool EARLY = false> PT_DEV void resolve_pe
             if (s.prim_light[mp] == li) {  // Arc::ptr_eq(light), integrator.rs:222-228
                 SurfaceInteraction lsi;
                 fill_hit<SPH>(s, mp, PT_NONE, V3(m0.x, m0.y, m0.z), wi, m2.y, m2.z, m2.w, lsi);  // lights are never inside instances (api.rs:1605-1608)
-                lrad = area_l(Lt, lsi.n, -wi);
+                lrad = area_l_rec(s, li, lsi.n, -wi);   // Lemit / two_sided from the light's record, not from a PtLight gather
             }
-        } else { PT_T(2); lrad = light_le(s, Lt, wi); PT_T(1); }
+        } else { PT_T(2); lrad = light_le(s, li, wi); PT_T(1); }
         RGB Tr(1.0f);
         bool tr_done = false;
         if (VOL) {   // Scene::intersect_tr (scene.rs:68-87) always evaluates the medium's tr -- a grid medium draws its dimensions whether or not the light is seen
@@ -238,7 +237,7 @@ PT_DEV void store_vertex(const PathSoA &ps, uint32_t pid, RGB L, RGB beta, const
 
 // path.rs:106-117, the ray escaped: the infinite lights' Le along it.
 PT_DEV void add_escaped_le(const DeviceScene &s, V3 rd, RGB beta, RGB &L) {
-    for (uint32_t k = 0; k < s.n_infinite; ++k) L = L + light_le(s, s.lights[s.infinite_lights[k]], rd) * beta;
+    for (uint32_t k = 0; k < s.n_infinite; ++k) L = L + light_le_infinite(s, s.infinite_lights[k], rd) * beta;
 }
 
 // The block's path-length histogram (path.rs:219) in LDS, and the end of a kernel that finishes vertices: histogram and the thread's tallies to the job's counters. `items` /
@@ -278,9 +277,10 @@ PT_DEV bool nee_vertex(const DeviceScene &s, const LightGrid &grid, const PathSo
             RGB A(0.0f); V3 sh_o(0.0f, 0.0f, 0.0f), sh_d(0.0f, 0.0f, 0.0f);   // the shadow ray and its term, stored with the rest of the nee record below
             uint32_t sh_medium = PT_NONE;                                       // VOL: a grid medium the shadow ray travels in
             PT_T(6);
-            RGB Li = light_sample_li<SPH>(s, li, it, ulight, wi, lightpdf, p1);
+            uint32_t lhead;   // the light's record header: its delta bit comes with the record light_sample_li reads anyway
+            RGB Li = light_sample_li_rec<SPH>(s, li, it, ulight, wi, lightpdf, p1, lhead);
             PT_T(7);
-            const bool delta = light_is_delta(s.lights[li]);
+            const bool delta = head_is_delta(lhead);
             if (lightpdf > 0.0f && !Li.is_black()) {
                 RGB f = bsdf.f_pdf(si.wo, wi, bf, scattpdf);
                 if (!MEDIUM) f = f * abs_dot(wi, si.sh_n);

@@ -104,6 +104,7 @@ int pt_scene_create(const PtSceneDesc *d, pt_scene **out) {
         if (any_mask(d->tri_shadow_alpha)) up(&ds.tri_shadow_alpha, d->tri_shadow_alpha, d->n_triangles);
     }
     up(&ds.infinite_lights, plan.infinite_lights); ds.n_infinite = (uint32_t)plan.infinite_lights.size();
+    up(&ds.env_u, &plan.env_u, 1);
     if (d->env_texels) {
         ds.env_w = d->env_width; ds.env_h = d->env_height;
         up(&ds.env_texels, d->env_texels, 3 * (size_t)ds.env_w * ds.env_h);
@@ -112,8 +113,8 @@ int pt_scene_create(const PtSceneDesc *d, pt_scene **out) {
     }
     for (int k = 0; k < 3; ++k) { ds.wb_min[k] = plan.wb_min[k]; ds.wb_max[k] = plan.wb_max[k]; ds.world_center[k] = plan.world_center[k]; }
     ds.world_radius = plan.world_radius;
-    const uint32_t *d_ordered = nullptr, *d_last = nullptr;
-    up(&d_ordered, plan.packet_refs);
+    const uint32_t *d_ordered = nullptr, *d_last = nullptr, *d_head = nullptr;
+    up(&d_ordered, plan.packet_refs); up(&d_head, plan.light_head);
     if (up.st) return up.st;
 
     // ---- the four-wide records and the packets share ONE allocation, so that the production traversal addresses both with 32-bit quad indices from one
@@ -135,7 +136,7 @@ int pt_scene_create(const PtSceneDesc *d, pt_scene **out) {
     hipLaunchKernelGGL(k_build_packets, dim3((n_packets + 255) / 256), dim3(256), 0, 0, ds, d_ordered, n_packets, leaf);
     ds.leaf = leaf;
     hipLaunchKernelGGL(k_mark_leaf_ends, dim3((n_leaves + 255) / 256), dim3(256), 0, 0, leaf, d_last, n_leaves);
-    if (d->n_lights) hipLaunchKernelGGL(k_light_area, dim3((d->n_lights + 255) / 256), dim3(256), 0, 0, ds, area, lrec);
+    if (d->n_lights) hipLaunchKernelGGL(k_light_area, dim3((d->n_lights + 255) / 256), dim3(256), 0, 0, ds, d_head, area, lrec);
     ds.light_area = area; ds.light_rec = lrec;
     if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return fail(PT_ERR_HIP, "scene preparation kernels failed");
     *out = owner.release();

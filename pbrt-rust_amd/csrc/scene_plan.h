@@ -50,6 +50,9 @@ struct ScenePlan {
     std::vector<DevImage> images;
     // Distribution2D::new (sampling.rs:100-117) over env_importance: conditional cdf rows, their integrals (= the marginal's function), the marginal's cdf and integral
     std::vector<float> env_cdf, env_func_int, env_marg_cdf; float env_marg_int = 0.0f;
+    // the environment light's wave-uniform block (dev_scene.h: EnvUniform) and every light's record header (light_rec_head: type and delta bit; k_light_area adds the triangle's bits)
+    EnvUniform env_u;
+    std::vector<uint32_t> light_head;       // at least one entry
     // GridDensityMedium::new (grid.rs:40-72) per medium: sigma_t, 1 / max density (density: NULL, the caller's)
     std::vector<DevGridAux> grid_aux; bool has_grid = false;
     // world bound = root node bounds (bvh.rs:697-703); Light::preprocess -> bounding sphere (bounds.rs:516-524)

@@ -396,6 +396,8 @@ PtStatus plan_build(const PtSceneDesc &d, const PlanOptions &opt, const AccelBui
     }
     for (uint32_t i = 0; i < d.n_prims; ++i) if (d.prim_material[i] == PT_NONE) plan.has_null_material = true;
     for (uint32_t i = 0; i < d.n_lights; ++i) if (d.lights[i].type == PT_LIGHT_INFINITE) plan.infinite_lights.push_back(i);
+    plan.light_head.assign(std::max<uint32_t>(1, d.n_lights), 0u);
+    for (uint32_t i = 0; i < d.n_lights; ++i) plan.light_head[i] = light_rec_head(d.lights[i].type);
     // ---- textures: the programs, and per image its level offsets
     if (d.n_textures) {
         if ((st = tex_programs(d, plan.tex_prog_offset, plan.tex_prog, msg))) return st;
@@ -435,6 +437,24 @@ PtStatus plan_build(const PtSceneDesc &d, const PlanOptions &opt, const AccelBui
             std::copy(c.begin(), c.end(), plan.env_cdf.begin() + v * (nu + 1));
         }
         dist1d(plan.env_func_int, plan.env_marg_cdf, plan.env_marg_int);
+    }
+    // ---- the environment light's uniform block: the first infinite light's transforms; the tables of a 1 x 1 map, copied from the arrays above
+    std::memset(&plan.env_u, 0, sizeof plan.env_u);
+    plan.env_u.light = PT_NONE;
+    if (!plan.infinite_lights.empty()) {
+        const PtLight &L = d.lights[plan.infinite_lights[0]];
+        plan.env_u.light = plan.infinite_lights[0];
+        std::copy(L.world_to_light, L.world_to_light + 16, plan.env_u.world_to_light); std::copy(L.light_to_world, L.light_to_world + 16, plan.env_u.light_to_world);
+    }
+    if (d.env_texels && d.env_width == 1 && d.env_height == 1) {
+        EnvUniform &e = plan.env_u;
+        std::copy(d.env_texels, d.env_texels + 3, e.texel0);
+        std::copy(plan.env_marg_cdf.begin(), plan.env_marg_cdf.begin() + 3, e.marg_cdf); e.marg_int = plan.env_marg_int;
+        for (int v = 0; v < 2; ++v) {
+            e.row_int[v] = plan.env_func_int[v];
+            std::copy(plan.env_cdf.begin() + 3 * v, plan.env_cdf.begin() + 3 * v + 3, e.row_cdf[v]);
+            std::copy(d.env_importance + 2 * v, d.env_importance + 2 * v + 2, e.row_func[v]);
+        }
     }
     // ---- world bound = root node bounds (bvh.rs:697-703); Light::preprocess -> bounding sphere (bounds.rs:516-524)
     bool inside = true;
