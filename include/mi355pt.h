@@ -586,6 +586,12 @@ int pt_camera_rays(const PtRenderParams *params, uint32_t n, const float *camera
  * (sampling.rs:66-85, the light choice) -> out_offset, out_pdf (out_x = 0). Twin of the reference's tests/sampling.rs:202-283. */
 int pt_dist1d_sample(const float *func, uint32_t n, int discrete, uint32_t n_u, const float *u,
                      float *out_x, float *out_pdf, int32_t *out_offset);
+/* The shade kernels' block-level queue stage on its own: n_blocks blocks of 256 threads make `rounds` rounds of pushes with the flushes the kernels make.
+ * Thread-round t = (block * rounds + round) * 256 + thread pushes path id t with the ray kinds masks[t] names (bit 0 continuation, bit 1 MIS, bit 2 shadow).
+ * qcap: the LDS queue size of a shade kernel form (256, 512, 1024). out_rays (3 * n_blocks * rounds * 256 entries: path id | kind << 30) and out_ext
+ * (n_blocks * rounds * 256 path ids) receive the two global queues, out_n_rays / out_n_ext their counts. */
+int pt_test_ray_queue_push(uint32_t qcap, uint32_t n_blocks, uint32_t rounds, const uint8_t *masks,
+                           uint32_t *out_rays, uint32_t *out_n_rays, uint32_t *out_ext, uint32_t *out_n_ext);
 
 #ifdef __cplusplus
 }

@@ -186,6 +186,7 @@ ENTRY_POINTS = {
     "pt_halton_samples": (C.c_int, [i32p, u32, u32, i32p, u32p, u32, fp, u64p]),
     "pt_camera_rays": (C.c_int, [C.POINTER(PtRenderParams), u32, fp, fp, fp]),
     "pt_dist1d_sample": (C.c_int, [fp, u32, C.c_int, u32, fp, fp, fp, i32p]),
+    "pt_test_ray_queue_push": (C.c_int, [u32, u32, u32, u8p, u32p, u32p, u32p, u32p]),
 }
 
 

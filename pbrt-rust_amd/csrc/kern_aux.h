@@ -141,6 +141,21 @@ __global__ __launch_bounds__(256) void k_shade_medium(DeviceScene s, RenderConst
     (void)zero_num;   // (resolve_pending<.., VOL> counts none)
 }
 
+// Parity entry (pt_test_ray_queue_push): VertexQueues driven as the kernels that finish a vertex drive it -- init, then `rounds` rounds of one push per thread and the
+// mid-loop flush, then the forced flush. masks[t]: bit k set = thread-round t emits a ray of kind k (0 continuation, 1 MIS, 2 shadow); t doubles as the path id.
+template <int QCAP> __global__ __launch_bounds__(256) void k_test_ray_queue(const uint8_t *masks, uint32_t rounds, ShadeJob job) {
+    __shared__ VertexQueues<QCAP, false, false> s_q;
+    s_q.init();
+    __syncthreads();
+    for (uint32_t r = 0; r < rounds; ++r) {
+        const uint32_t t = (blockIdx.x * rounds + r) * 256u + threadIdx.x;
+        const uint32_t m = masks[t];
+        s_q.push(job, t, (m & 1u) != 0u, false, (m & 4u) != 0u, (m & 2u) != 0u);
+        s_q.flush(job, 256u, false);
+    }
+    s_q.flush(job, 0u, true);
+}
+
 // ---- escaped rays and dead paths (class kMissClass) -------------------------------------------------------------------
 // More than half of the vertices of an open scene are rays that left it (S2: 54 %). They only need the previous vertex's
 // NEE resolved, the environment's Le where path.rs:106-117 adds it, and the path-length histogram entry -- none of the

@@ -4,11 +4,12 @@
 // Pipeline per pass (one pass = s_count samples of every pixel owned by this rank):
 //   k_generate   integrator.rs:331-346  sampler.rs:170-180  perspective.rs:120-179
 //   repeat until no path is alive:
-//     k_trace<closest>  bvh.rs:705-760 + triangle.rs:136-233   (continuation rays, then MIS rays)
-//     k_trace<any>      bvh.rs:762-814 + triangle.rs:400-495   (shadow rays)
+//     k_trace<mixed>    bvh.rs:705-760 + triangle.rs:136-233 (continuation and MIS rays: closest hit), bvh.rs:762-814 + triangle.rs:400-495 (shadow rays: any hit) --
+//                       one launch over the ray queue, in which the rays of a vertex are neighbours (PT_TRACE_SPLIT=1: a k_trace<closest | any> launch per kind)
+//     k_route           every hit to the shade queue of its material class
 //     k_shade<class>    path.rs:97-217 + integrator.rs:81-237  (one launch per material class queue)
 //   k_film       integrator.rs:350-374 + film.rs:292-331
-// Queues hold path ids; path state is SoA in HBM (kernels.h). Compaction is wave64 ballot + popcount.
+// Queues hold path ids -- the ray queue a path id and the ray's kind (kernels.h: kRayKindShift); path state is records in HBM (kernels.h). Compaction is wave64 ballot + popcount.
 #pragma once
 #include "kernels.h"
 #include "dev_bsdf.h"

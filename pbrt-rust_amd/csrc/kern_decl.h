@@ -10,10 +10,12 @@ template <bool SPH, bool VOL> __global__ void k_bssrdf(DeviceScene s, RenderCons
 __global__ void k_medium_route(DeviceScene s, RenderConst rc, SobolTables tabs, PathSoA ps, const uint32_t *queue, const uint32_t *count_ptr,
                                uint32_t *class_count, uint32_t *c0, uint32_t *c1, uint32_t *c2, uint32_t *c3, uint32_t *c4, uint32_t *c5, uint32_t *error);
 __global__ void k_shade_medium(DeviceScene s, RenderConst rc, SobolTables tabs, LightGrid grid, PathSoA ps, ShadeJob job);
+template <int QCAP> __global__ void k_test_ray_queue(const uint8_t *masks, uint32_t rounds, ShadeJob job);   // kern_aux.h: the parity entry of VertexQueues
 __global__ void k_build_packets(DeviceScene s, const uint32_t *ordered, uint32_t n_refs, TriPacket *out);
 __global__ void k_mark_leaf_ends(TriPacket *leaf, const uint32_t *last_index, uint32_t n);
 __global__ void k_light_area(DeviceScene s, const uint32_t *head, float *area, float4 *rec);
 template <int NQ, int CAP> __global__ void k_route(DeviceScene s, const uint32_t *queue, const uint32_t *count_ptr, PathSoA ps, uint32_t *class_count, RouteJob rj);
+__global__ void k_split_rays(const uint32_t *rays, const uint32_t *count_ptr, uint32_t *mis, uint32_t *mis_count, uint32_t *shadow, uint32_t *shadow_count);
 __global__ void k_generate(RenderConst rc, SobolTables tabs, PathSoA ps, uint32_t *q_ext, uint32_t *q_ext_count, DevCounters *counters);
 __global__ void k_film(RenderConst rc, PathSoA ps, const float *filter_table, float *film_rgbw, DevCounters *counters);
 template <bool SPH> __global__ void k_film_final(DeviceScene s, RenderConst rc, PathSoA ps, const float *filter_table, float *film_rgbw, DevCounters *counters);

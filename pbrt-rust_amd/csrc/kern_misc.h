@@ -112,6 +112,26 @@ __global__ __launch_bounds__(256) void k_route(DeviceScene s, const uint32_t *qu
 #pragma unroll
     for (int k = 0; k < NQ; ++k) if ((uint32_t)k < rj.n_slots) lq_flush_nosync(q[k], class_count + rj.cls_of_slot[k], rj.buf[k], 0u, true);
 }
+// PT_TRACE_SPLIT=1 only (one traversal launch per ray kind): the ray queue's MIS and shadow entries go to queues of plain path ids, as the single-kind launches read them.
+// The continuation rays have their own queue already (`ext`, what k_route reads), so entries of kind 0 are skipped.
+__global__ __launch_bounds__(256) void k_split_rays(const uint32_t *rays, const uint32_t *count_ptr, uint32_t *mis, uint32_t *mis_count, uint32_t *shadow, uint32_t *shadow_count) {
+    __shared__ LdsQueue<1024> q_mis, q_sh;
+    lq_init(q_mis); lq_init(q_sh);
+    __syncthreads();
+    const uint32_t count = *count_ptr;
+    const uint32_t rounded = (count + 255u) & ~255u;
+    for (uint32_t qi = blockIdx.x * blockDim.x + threadIdx.x; qi < rounded; qi += gridDim.x * blockDim.x) {
+        const uint32_t e = qi < count ? rays[qi] : 0u;   // (an entry of kind 0 goes nowhere)
+        lq_push(q_mis, e & kRayPidMask, (e >> kRayKindShift) == 1u);
+        lq_push(q_sh, e & kRayPidMask, (e >> kRayKindShift) == 2u);
+        __syncthreads();
+        lq_flush_nosync(q_mis, mis_count, mis, 256u, false);
+        lq_flush_nosync(q_sh, shadow_count, shadow, 256u, false);
+        __syncthreads();
+    }
+    lq_flush_nosync(q_mis, mis_count, mis, 0u, true);
+    lq_flush_nosync(q_sh, shadow_count, shadow, 0u, true);
+}
 // ---- camera rays -------------------------------------------------------------------------------------
 PT_DEV void camera_ray(const RenderConst &rc, float pfx, float pfy, float time_u, P2 plens_u, V3 &o, V3 &d) {  // perspective.rs:120-179
     V3 pcamera = xf_point(rc.raster_to_camera, V3(pfx, pfy, 0.0f));

@@ -181,30 +181,47 @@ template <bool SPH> PT_DEV bool vol_chain_step(const DeviceScene &s, const PathS
 // the steps that moved a kernel's register count when they were shared (profiles/r6/NOTES.md section 12): "resolve the pending estimate, or walk a shell segment in stage B" and
 // "the path ends: dead with an estimate pending, or finished" in all three, the roulette in k_shade.
 
-// The block's LDS queues (kern_common.h: LdsQueue) in front of the job's global ones: continuation rays, resolve-only paths (to the miss class), shadow rays, MIS rays, and
-// where the kernel has them (one-entry stubs where not) probe chains (PROBE) and vertices waiting for stage B (SELF). Written against the field names ShadeJob and BssrdfJob share.
+// The block's LDS queues (kern_common.h: LdsQueue) in front of the job's global ones: continuation rays (what k_route reads), resolve-only paths (to the miss class), the ray
+// queue (kernels.h: kRayKindShift -- every ray of the vertex, tagged with its kind, the continuation ray once more: what the mixed trace launch reads), and where the kernel
+// has them (one-entry stubs where not) probe chains (PROBE) and vertices waiting for stage B (SELF). Written against the field names ShadeJob and BssrdfJob share.
 template <int QCAP, bool PROBE, bool SELF> struct VertexQueues {
-    LdsQueue<QCAP> ext, res, sh, mis;
+    // `rays` lives in the LDS bytes the separate shadow and MIS queues took; it holds at least one round's worth, three entries per thread (the QCAP = 256 form: 768)
+    static constexpr int kRayCap = 2 * QCAP > 768 ? 2 * QCAP : 768;
+    LdsQueue<QCAP> ext, res;
+    LdsQueue<kRayCap> rays;
     LdsQueue<PROBE ? QCAP : 1> probe;
     LdsQueue<SELF ? QCAP : 1> self;
-    PT_DEV void init() { lq_init(ext); lq_init(res); lq_init(sh); lq_init(mis); lq_init(probe); lq_init(self); }
+    PT_DEV void init() { lq_init(ext); lq_init(res); lq_init(rays); lq_init(probe); lq_init(self); }
+    // A lane's 0-3 rays as CONSECUTIVE entries in kind order (continuation, MIS, shadow) at the lane's prefix: three ballots, one LDS atomic of the wave's leader.
+    PT_DEV void push_rays(uint32_t pid, bool to_ext, bool to_mis, bool to_shadow) {
+        const unsigned long long m_e = __ballot(to_ext), m_m = __ballot(to_mis), m_s = __ballot(to_shadow), any = m_e | m_m | m_s;
+        if (any == 0ull) return;
+        const uint32_t lane = lane_id(), leader = (uint32_t)__ffsll((long long)any) - 1u;
+        const unsigned long long below = (1ull << lane) - 1ull;
+        uint32_t base = 0;
+        if (lane == leader) base = atomicAdd(&rays.count, (uint32_t)(__popcll(m_e) + __popcll(m_m) + __popcll(m_s)));
+        base = __shfl(base, (int)leader);
+        uint32_t at = base + (uint32_t)(__popcll(m_e & below) + __popcll(m_m & below) + __popcll(m_s & below));
+        if (to_ext) rays.buf[at++] = pid;
+        if (to_mis) rays.buf[at++] = pid | (1u << kRayKindShift);
+        if (to_shadow) rays.buf[at] = pid | (2u << kRayKindShift);
+    }
     // where a finished vertex goes next (the kernels keep these flags as plain bools: as members of one struct they cost several k_shade forms a register)
     template <class Job> PT_DEV void push(const Job &job, uint32_t pid, bool to_ext, bool to_resolve, bool to_shadow, bool to_mis, bool to_self = false, bool to_probe = false) {
         lq_push(ext, pid, to_ext);   // (grouped by the new ray's direction octant: trace no faster -- profiles/HISTORY.md; profiles/r6/experiments/settled_ab_hooks.patch)
         lq_push(res, pid, to_resolve && job.shade_next0 != nullptr);   // (no miss pass: the film kernel ends the dead paths, k_film_final; k_shade_medium pushed without this test: volpath always has the miss pass)
-        lq_push(sh, pid, to_shadow);
-        lq_push(mis, pid, to_mis);
+        push_rays(pid, to_ext, to_mis, to_shadow);
         if constexpr (PROBE) if (job.probe_next) lq_push(probe, pid, to_probe);
         if constexpr (SELF) lq_push(self, pid, to_self);
     }
     // One flush round, all threads of the block together: a barrier makes the pushes visible, every queue with fewer than `reserve` free slots (or any entry, `force`) goes to
-    // its global queue, a barrier closes the round. In the loop: (256, false) after each round's pushes; after it: (0, true).
+    // its global queue, a barrier closes the round. In the loop: (256, false) after each round's pushes; after it: (0, true). `reserve` counts threads: the ray queue
+    // keeps three entries for each.
     template <class Job> PT_DEV void flush(const Job &job, uint32_t reserve, bool force) {
         __syncthreads();
         lq_flush_nosync(ext, job.ext_next_count, job.ext_next, reserve, force);
         lq_flush_nosync(res, job.shade_next0_count, job.shade_next0, reserve, force);
-        lq_flush_nosync(sh, job.shadow_count, job.shadow, reserve, force);
-        lq_flush_nosync(mis, job.mis_count, job.mis, reserve, force);
+        lq_flush_nosync(rays, job.rays_count, job.rays, 3u * reserve, force);
         if constexpr (PROBE) if (job.probe_next) lq_flush_nosync(probe, job.probe_next_count, job.probe_next, reserve, force);
         if constexpr (SELF) lq_flush_nosync(self, job.self_next_count, job.self_next, reserve, force);
         __syncthreads();

@@ -116,9 +116,8 @@ __global__ __launch_bounds__(kTraceBlock, (trace_waves<MODE, PROBE, QUADK>())) v
     glb_u32 *spill = (glb_u32 *)job.spill + (size_t)(blockIdx.x * (kTraceBlock / 64) + wave_in_block) * 64 * kSpillWords + lane;
     typedef __attribute__((address_space(1))) float glb_f32;
     glb_f32 *wray_g = (glb_f32 *)(spill + (2 * kSpillEntries) * 64);   // (the slab is sized for the deeper of the two walks: both index it the same way)
-    // MIX: queue entry qi belongs to sub 0 below c0, to sub 1 below c01, to sub 2 otherwise
-    const uint32_t c0 = *job.sub[0].count, c01 = c0 + (MIX ? *job.sub[1].count : 0u);
-    const uint32_t count = c01 + (MIX ? *job.sub[2].count : 0u);
+    // MIX: sub[0]'s queue is the ray queue (kernels.h: kRayKindShift); every entry names its path and its sub
+    const uint32_t count = *job.sub[0].count;
     uint32_t ksel = 0; bool lane_any = ANY == 1;   // the lane's ray: its sub and whether it is an any-hit query
     __shared__ uint32_t lds_kcnt[MIX ? (kTraceBlock / 64) * 16 : 1];   // MIX: per wave {nodes, tris, rays} x 3 subs
     uint32_t *kcnt = lds_kcnt + (MIX ? (threadIdx.x >> 6) * 16 : 0u);
@@ -127,7 +126,7 @@ __global__ __launch_bounds__(kTraceBlock, (trace_waves<MODE, PROBE, QUADK>())) v
     // rows (five quads each, row stride 20 words: the three rows' quads fall into different banks) and is fetched with the lane's `ksel` as the row:
     // two ds_read_b128 per refill, three per retire. Chosen per lane out of the kernel arguments it was 26 + 47 selects, and the 60 scalars of the
     // three TraceSubs overflowed the SGPR file (123 v_readlane / 45 v_writelane in the kernel, 69 of them in this block).
-    //   quad 0: queue, ray   quad 1: ray_stride, per_ray_tmax | any << 1, scalar_tmax, first queue index of the kind
+    //   quad 0: -, ray   quad 1: ray_stride, per_ray_tmax | any << 1, scalar_tmax, -
     //   quad 2: out_hit, out_hit2   quad 3: out_word, out_t   quad 4: out_hit_stride, out_word_stride, out_t_stride, -
     constexpr int kSubRow = 20;
     __shared__ __attribute__((aligned(16))) uint32_t lds_sub[MIX ? 3 * kSubRow : 4];
@@ -137,10 +136,10 @@ __global__ __launch_bounds__(kTraceBlock, (trace_waves<MODE, PROBE, QUADK>())) v
             for (int k = 0; k < 3; ++k) {
                 const TraceSub &S = job.sub[k];
                 uint32_t *r = lds_sub + k * kSubRow;
-                const unsigned long long pq = (unsigned long long)S.queue, pr = (unsigned long long)S.ray, ph = (unsigned long long)S.out_hit, ph2 = (unsigned long long)S.out_hit2,
+                const unsigned long long pr = (unsigned long long)S.ray, ph = (unsigned long long)S.out_hit, ph2 = (unsigned long long)S.out_hit2,
                                          pw = (unsigned long long)S.out_word, pt = (unsigned long long)S.out_t;
-                r[0] = (uint32_t)pq; r[1] = (uint32_t)(pq >> 32); r[2] = (uint32_t)pr; r[3] = (uint32_t)(pr >> 32);
-                r[4] = S.ray_stride; r[5] = (S.per_ray_tmax ? 1u : 0u) | (S.any ? 2u : 0u); r[6] = __float_as_uint(S.scalar_tmax); r[7] = k == 0 ? 0u : (k == 1 ? c0 : c01);
+                r[0] = 0u; r[1] = 0u; r[2] = (uint32_t)pr; r[3] = (uint32_t)(pr >> 32);
+                r[4] = S.ray_stride; r[5] = (S.per_ray_tmax ? 1u : 0u) | (S.any ? 2u : 0u); r[6] = __float_as_uint(S.scalar_tmax); r[7] = 0u;
                 r[8] = (uint32_t)ph; r[9] = (uint32_t)(ph >> 32); r[10] = (uint32_t)ph2; r[11] = (uint32_t)(ph2 >> 32);
                 r[12] = (uint32_t)pw; r[13] = (uint32_t)(pw >> 32); r[14] = (uint32_t)pt; r[15] = (uint32_t)(pt >> 32);
                 r[16] = S.out_hit_stride; r[17] = S.out_word_stride; r[18] = S.out_t_stride; r[19] = 0u;
@@ -350,17 +349,12 @@ __global__ __launch_bounds__(kTraceBlock, (trace_waves<MODE, PROBE, QUADK>())) v
             if (retire) state = ST_IDLE;
             // (B)
             bool get = false; v4f_ rr0 = {0.0f, 0.0f, 0.0f, 0.0f}, rr1 = rr0, pb0 = rr0, pb1 = rr0; bool per_ray_tmax = PT_SUB(per_ray_tmax) != 0u; float scalar_tmax = PT_SUB(scalar_tmax);
-            // the wave's queue window: lane l holds the path id of queue entry win_base + l
+            // the wave's queue window: lane l holds queue entry win_base + l (a path id; MIX: with the ray's kind)
             auto load_window = [&](uint32_t base, uint32_t left) {
                 const uint32_t qi = base + lane; uint32_t w = 0u;
                 if (lane < left) {
-                    uint32_t qk = qi; gcu32 *qp = (gcu32 *)PT_SUB(queue);
-                    if constexpr (MIX) {
-                        const uint32_t kk = (qi >= c0 ? 1u : 0u) + (qi >= c01 ? 1u : 0u);
-                        const uint4 r0 = sub_rows[5u * kk], r1 = sub_rows[5u * kk + 1u];
-                        qp = PT_GPTR(const uint32_t, r0.x, r0.y); qk = qi - r1.w;
-                    }
-                    w = qp ? qp[qk] : qk;   // (the loaded word as it is: anything computed from it here would make the wave wait for the prefetch)
+                    gcu32 *qp = (gcu32 *)job.sub[0].queue;
+                    w = qp ? qp[qi] : qi;   // (the loaded word as it is: anything computed from it here would make the wave wait for the prefetch)
                 }
                 return w;
             };
@@ -385,14 +379,13 @@ __global__ __launch_bounds__(kTraceBlock, (trace_waves<MODE, PROBE, QUADK>())) v
                 const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idlem >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idlem, 0u));   // set bits below this lane (v_mbcnt: no per-lane mask registers)
                 const uint32_t take = min(chunk_left, (uint32_t)__popcll(idlem));
                 const uint32_t wsel = (uint32_t)__shfl((int)qwin, (int)(rank & 63u));   // entry chunk_next + rank (the window starts at chunk_next)
-                const uint32_t qi = chunk_next + rank;
                 get = state == ST_IDLE && rank < take;
                 chunk_next += take; chunk_left -= take;
                 if (get) {
                     gcf4 *rays = (gcf4 *)PT_SUB(ray); uint32_t ray_stride = PT_SUB(ray_stride);
                     pid = wsel;
                     if constexpr (MIX) {
-                        ksel = (qi >= c0 ? 1u : 0u) + (qi >= c01 ? 1u : 0u);
+                        ksel = wsel >> kRayKindShift; pid = wsel & kRayPidMask;
                         const uint4 r0 = sub_rows[5u * ksel], r1 = sub_rows[5u * ksel + 1u];
                         rays = PT_GPTR(const v4f_, r0.z, r0.w);
                         ray_stride = r1.x; per_ray_tmax = (r1.y & 1u) != 0u; lane_any = (r1.y & 2u) != 0u; scalar_tmax = __uint_as_float(r1.z);

@@ -114,17 +114,24 @@ constexpr int kBssBytes = 16 * (BssSoA::kProbeQuads + BssSoA::kFrameQuads + BssS
 // kdsubsurface materials (their conversion, subsurface_from_diffuse, is a Catmull-Rom inversion nobody wants to run twice)
 PT_HD bool bss_coef_stored(uint32_t n_textures, const PtMaterial &m) { return n_textures > 0u || m.kd_subsurface != 0u; }
 
+// An entry of the ray queue: bits 0-29 the path id, bits 30-31 the ray's kind -- 0 continuation, 1 MIS, 2 shadow (TraceSub::kind of the mixed launch's three subs).
+// A vertex's rays are consecutive entries in kind order, so the mixed launch traces them side by side: they start at one point and fetch nearly the same records.
+constexpr uint32_t kRayKindShift = 30u, kRayPidMask = (1u << kRayKindShift) - 1u;
+constexpr size_t kMaxRayQueuePaths = (size_t)1 << 29;   // paths in flight the entry format is used for (the host refuses more)
+
 struct QueueSet {
     uint32_t *ext[2];                 // pids with a continuation ray to trace (ping-pong)
     uint32_t *shade[2][kNumClasses];  // pids to shade, per material class (ping-pong)
-    uint32_t *shadow, *mis;           // pids with pending shadow / MIS rays
+    uint32_t *rays;                   // the rays of the vertices shaded last, vertex by vertex: path id | kind << 30 (kRayKindShift), 3 x capacity entries
+    uint32_t *shadow, *mis;           // pids with pending shadow / MIS rays: PT_TRACE_SPLIT=1 only (k_split_rays fills them from `rays`), else NULL
     uint32_t *probe[2];               // pids walking a BSSRDF probe chain (ping-pong; NULL without subsurface materials)
     // counters (device): layout documented in QCounters
 };
 struct QCounters {
     uint32_t ext[2];
     uint32_t shade[2][kNumClasses];
-    uint32_t shadow, mis;
+    uint32_t shadow, mis;             // PT_TRACE_SPLIT=1 only
+    uint32_t rays;
     uint32_t probe[2];
     uint32_t head[4];                 // persistent-wave work heads for the trace launches
     uint32_t error;                   // PtStatus raised on device (stack / sobol overflow)
@@ -186,11 +193,11 @@ struct TraceSub {
     uint32_t any;            // k_trace<2, ..> (mixed launch): this kind's rays are any-hit queries (Scene::intersect_p)
 };
 
-// A traversal launch. k_trace<0 | 1, ..> walks the rays of sub[0] (closest hit | any hit); k_trace<2, ..> walks the queues of
-// sub[0..2] back to back -- the continuation, MIS and shadow rays of one wavefront iteration in ONE launch, so that the iteration
-// has one tail of straggling rays instead of three (run_pass in render_loop.hip).
+// A traversal launch. k_trace<0 | 1, ..> walks the rays of sub[0] (closest hit | any hit); k_trace<2, ..> walks the ray queue, whose
+// entries name one of sub[0..2] each -- the continuation, MIS and shadow rays of one wavefront iteration in ONE launch, so that the iteration
+// has one tail of straggling rays instead of three (run_pass in render_loop.hip), and a vertex's rays next to each other.
 struct TraceJob {
-    TraceSub sub[3];
+    TraceSub sub[3];         // k_trace<2, ..>: sub[0].queue / count are the ray queue (QueueSet::rays) and its count; no other queue of the subs is read
     uint32_t *head;          // persistent-wave work head (zeroed before launch)
     uint32_t *spill;         // [waves_in_grid][64 lanes][2 * (kMaxStack - the kernel's LDS stack entries)], allocated for the smaller LDS stack
     uint32_t *error;
@@ -207,7 +214,7 @@ struct ShadeJob {
     const uint32_t *queue; const uint32_t *count;
     uint32_t *ext_next, *ext_next_count;
     uint32_t *shade_next0, *shade_next0_count;   // resolve-only paths go to the miss class (kMissClass) of the next iteration
-    uint32_t *shadow, *shadow_count, *mis, *mis_count;
+    uint32_t *rays, *rays_count;                 // the ray queue (QueueSet::rays): every ray the vertex emits, the continuation ray too
     uint32_t *error;
     DevCounters *counters;
     uint32_t cls;            // material class of this launch (statistics)
@@ -220,7 +227,7 @@ struct BssrdfJob {           // k_bssrdf: the vertex at the exit point of every 
     const uint32_t *queue; const uint32_t *count;
     uint32_t *ext_next, *ext_next_count;
     uint32_t *shade_next0, *shade_next0_count;
-    uint32_t *shadow, *shadow_count, *mis, *mis_count;
+    uint32_t *rays, *rays_count;                 // the ray queue (QueueSet::rays): every ray the vertex emits, the continuation ray too
     uint32_t *error;
     DevCounters *counters;
     BssSoA bs;

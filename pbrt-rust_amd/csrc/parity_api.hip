@@ -145,4 +145,32 @@ int pt_dist1d_sample(const float *func, uint32_t n, int discrete, uint32_t n_u, 
     return PT_OK;
 }
 
+// VertexQueues (kern_shade_common.h) on its own: n_blocks blocks of 256 threads make `rounds` rounds; thread-round t = (block * rounds + round) * 256 + thread pushes path
+// id t with the ray kinds masks[t] names. Out: the ray queue and the continuation queue as the block flushes left them, and their counts.
+int pt_test_ray_queue_push(uint32_t qcap, uint32_t n_blocks, uint32_t rounds, const uint8_t *masks, uint32_t *out_rays, uint32_t *out_n_rays, uint32_t *out_ext, uint32_t *out_n_ext) {
+    DevTmp scratch;
+    if (!masks || !out_rays || !out_n_rays || !out_ext || !out_n_ext) return fail(PT_ERR_INVALID_ARG, "null argument");
+    if (qcap != 256u && qcap != (uint32_t)PT_P2_QCAP && qcap != 1024u) return fail(PT_ERR_INVALID_ARG, "qcap: 256, " + std::to_string(PT_P2_QCAP) + " or 1024 (the shade kernels' LDS queue sizes)");
+    const size_t n = (size_t)n_blocks * rounds * 256;
+    if (n == 0 || n > kRayPidMask) return fail(PT_ERR_INVALID_ARG, "n_blocks * rounds * 256 must be in [1, 2^30)");
+    int st = ensure_device();
+    if (st) return st;
+    uint8_t *dmasks; uint32_t *drays, *dext, *dcount;
+    HIP_TRY(scratch.alloc(&dmasks, n)); HIP_TRY(scratch.alloc(&drays, 3 * n * 4)); HIP_TRY(scratch.alloc(&dext, n * 4)); HIP_TRY(scratch.alloc(&dcount, 8));
+    HIP_TRY(hipMemcpy(dmasks, masks, n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(dcount, 0, 8));
+    ShadeJob job{}; job.rays = drays; job.rays_count = dcount; job.ext_next = dext; job.ext_next_count = dcount + 1;
+    if (qcap == 256u) hipLaunchKernelGGL(k_test_ray_queue<256>, dim3(n_blocks), dim3(256), 0, 0, dmasks, rounds, job);
+    else if (qcap == 1024u) hipLaunchKernelGGL(k_test_ray_queue<1024>, dim3(n_blocks), dim3(256), 0, 0, dmasks, rounds, job);
+    else hipLaunchKernelGGL(k_test_ray_queue<PT_P2_QCAP>, dim3(n_blocks), dim3(256), 0, 0, dmasks, rounds, job);
+    HIP_TRY(hipDeviceSynchronize());
+    uint32_t cnt[2];
+    HIP_TRY(hipMemcpy(cnt, dcount, 8, hipMemcpyDeviceToHost));
+    if (cnt[0] > 3 * n || cnt[1] > n) return fail(PT_ERR_HIP, "ray queue test: more entries than were pushed");
+    HIP_TRY(hipMemcpy(out_rays, drays, (size_t)cnt[0] * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_ext, dext, (size_t)cnt[1] * 4, hipMemcpyDeviceToHost));
+    *out_n_rays = cnt[0]; *out_n_ext = cnt[1];
+    return PT_OK;
+}
+
 }  // extern "C"

@@ -88,7 +88,8 @@ static bool class_launched(const pt_scene *sc, int q, bool volpath) { for (int c
 // vertices, 6 also the waiting exit points of volpath)
 static bool class_has_queue(const pt_scene *sc, int c) { return c == 0 || kClasses[c].kind != kSurface || class_launched(sc, c, false) || class_launched(sc, c, true); }
 // queues of one path index each: ext[2] + shade[2][classes with a queue] + shadow + mis (+ probe[2])
-static size_t n_queues(const pt_scene *sc) { size_t n = 2 + 2 + (sc->has_bssrdf ? 2 : 0); for (int c = 0; c < kNumClasses; ++c) n += class_has_queue(sc, c) ? 2 : 0; return n; }
+// (in units of `capacity` entries: ext x 2, the ray queue's three entries per path, under PT_TRACE_SPLIT=1 the single-kind launches' MIS and shadow queues, probe x 2, the classes')
+static size_t n_queues(const pt_scene *sc) { size_t n = 2 + 3 + (g_trace_split ? 2 : 0) + (sc->has_bssrdf ? 2 : 0); for (int c = 0; c < kNumClasses; ++c) n += class_has_queue(sc, c) ? 2 : 0; return n; }
 
 // any: 0 closest hit, 1 any hit (rays of job.sub[0]); 2 mixed: the queues of job.sub[0..2] in one launch (n_upper covers all three)
 int launch_trace(pt_scene *sc, int any, TraceJob job, uint32_t n_upper, bool probe) {
@@ -150,12 +151,16 @@ int ensure_workspace(pt_scene *sc, size_t capacity, size_t film_px) {
             float4 *bp = (float4 *)sc->bss_slab;
             bs.probe = bp; bp += capacity * (size_t)BssSoA::kProbeQuads; bs.frame = bp; bp += capacity * (size_t)BssSoA::kFrameQuads; bs.coef = bp;
         }
+        // (after the path state, so that a pass too large for the device's memory is reported as that)
+        if (capacity > kMaxRayQueuePaths) { drop(); return fail(PT_ERR_INVALID_ARG, "more than 2^29 paths in one pass: a ray-queue entry keeps the path id beside the ray's kind"); }
         e = hipMalloc((void **)&sc->qbuf, n_queues(sc) * capacity * 4);
         if (e != hipSuccess) { sc->qbuf = nullptr; return oom("queues", e); }
         uint32_t *qp = sc->qbuf;
         for (int i = 0; i < 2; ++i) { sc->q.ext[i] = qp; qp += capacity; }
         for (int i = 0; i < 2; ++i) for (int c = 0; c < kNumClasses; ++c) { sc->q.shade[i][c] = nullptr; if (class_has_queue(sc, c)) { sc->q.shade[i][c] = qp; qp += capacity; } }
-        sc->q.shadow = qp; qp += capacity; sc->q.mis = qp; qp += capacity;
+        sc->q.rays = qp; qp += 3 * capacity;
+        sc->q.shadow = sc->q.mis = nullptr;
+        if (g_trace_split) { sc->q.shadow = qp; qp += capacity; sc->q.mis = qp; qp += capacity; }
         sc->q.probe[0] = sc->q.probe[1] = nullptr;
         if (sc->has_bssrdf) { sc->q.probe[0] = qp; qp += capacity; sc->q.probe[1] = qp; }
         sc->capacity = capacity;
@@ -325,11 +330,11 @@ void fill_render_const(const PtRenderParams *rp, RenderConst &rc) {
 }
 
 __global__ void k_reset(QCounters *qc, uint32_t mask, int cur) {
-    // mask bit0: next ext + next shade queues; bit1: shadow + mis; bit2: trace heads; bit3: current ext + shade
+    // mask bit0: next ext + next shade queues; bit1: the ray queue (+ shadow + mis); bit2: trace heads; bit3: current ext + shade
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     int nxt = 1 - cur;
     if (mask & 1u) { qc->ext[nxt] = 0; qc->probe[nxt] = 0; for (int c = 0; c < kNumClasses; ++c) qc->shade[nxt][c] = 0; }
-    if (mask & 2u) { qc->shadow = 0; qc->mis = 0; }
+    if (mask & 2u) { qc->rays = 0; qc->shadow = 0; qc->mis = 0; }
     if (mask & 4u) { for (int i = 0; i < 4; ++i) qc->head[i] = 0; }
     if (mask & 8u) { qc->ext[cur] = 0; qc->probe[cur] = 0; for (int c = 0; c < kNumClasses; ++c) qc->shade[cur][c] = 0; }
 }
@@ -415,17 +420,19 @@ int sync_queue_counters(pt_scene *sc, QCounters &h) {
 
 // ---- one pass. An iteration consumes the queue set `cur` and fills the other one: trace, route, touch, probe, shade per class, reset (run_pass below). Its steps see it as
 // an Iter: the queue sizes the host read at its start, and what the pass fixed (fin: the film kernel ends the paths, there is no miss class).
-struct Iter { pt_scene *sc; const RenderConst &rc; const LightGrid &grid; bool fin, profile_exact; int index, cur; uint32_t n_ext, n_resolve, n_shadow, n_mis, n_probe, n_stage_b; };
+// n_rays: this iteration's rays of every kind -- the ray queue the vertices shaded last filled, which names their continuation rays (the n_ext entries of `ext`) once more;
+// the camera rays of the first iteration are in `ext` alone.
+struct Iter { pt_scene *sc; const RenderConst &rc; const LightGrid &grid; bool fin, profile_exact; int index, cur; uint32_t n_ext, n_resolve, n_rays, n_probe, n_stage_b; };
 
 // A shading job (ShadeJob / BssrdfJob) with the outputs all of them share: its queue, the next iteration's continuation-ray queue, miss queue (none when the film kernel
-// ends the paths) and the queue of class `self` (stage B of a volpath vertex), the shadow and MIS ray queues, the error word and the counters.
+// ends the paths) and the queue of class `self` (stage B of a volpath vertex), the ray queue, the error word and the counters.
 template <class Job> Job shading_job(const Iter &it, const uint32_t *queue, const uint32_t *count, int self) {
     pt_scene *sc = it.sc; QCounters *qc = sc->qc; const int nxt = 1 - it.cur;
     Job j{}; j.queue = queue; j.count = count;
     j.ext_next = sc->q.ext[nxt]; j.ext_next_count = &qc->ext[nxt];
     if (!it.fin) { j.shade_next0 = sc->q.shade[nxt][kMissClass]; j.shade_next0_count = &qc->shade[nxt][kMissClass]; }
     j.self_next = sc->q.shade[nxt][self]; j.self_next_count = &qc->shade[nxt][self];
-    j.shadow = sc->q.shadow; j.shadow_count = &qc->shadow; j.mis = sc->q.mis; j.mis_count = &qc->mis;
+    j.rays = sc->q.rays; j.rays_count = &qc->rays;
     j.error = &qc->error; j.counters = sc->dc;
     return j;
 }
@@ -458,15 +465,24 @@ static int trace_rays(const Iter &it) {
     TraceSub sh = trace_sub(sc->q.shadow, &qc->shadow, ps.nee, PathSoA::kNeeWords, 1.0f - 0.0001f, 2);
     sh.out_word = &ps.occluded(0); sh.out_word_stride = PathSoA::kNeeWords; sh.any = rc.volpath ? 0u : 1u;
     if (shells) { sh.out_hit = (float4 *)ps.ext + 4; sh.out_hit_stride = PathSoA::kExtWords / 4; sh.out_hit2 = (float4 *)ps.ext + 5; }
-    if (it.n_mis + it.n_shadow == 0 || g_trace_split) {   // camera rays (nothing else to trace in the first iteration) / PT_TRACE_SPLIT=1: one launch per kind, each with its own work head
+    if (it.n_rays == it.n_ext || g_trace_split) {   // continuation rays only (the camera rays of the first iteration) / PT_TRACE_SPLIT=1: one launch per kind, each with its own work head
         auto one = [&](const char *stat, const TraceSub &sub, int head, int any, uint32_t n) { TraceJob tj = trace_job(sc, head); tj.sub[0] = sub; return traced(sc, stat, any, tj, n); };
         int st;
-        if ((st = one(it.index == 0 ? "extend_camera" : "extend", ext, 0, 0, it.n_ext)) || (st = one("extend_mis", mis, 1, 0, it.n_mis))) return st;
-        return one("shadow", sh, 2, (int)sh.any, it.n_shadow);
+        uint32_t n_mis = 0, n_shadow = 0;
+        if (it.n_rays != it.n_ext) {   // the single-kind launches read queues of plain path ids: the ray queue's MIS and shadow entries, scattered (the sizes: one more read of the counters)
+            hipLaunchKernelGGL(k_split_rays, blocks_for(it.n_rays, 8u), dim3(256), 0, sc->stream, (const uint32_t *)sc->q.rays, (const uint32_t *)&qc->rays, sc->q.mis, &qc->mis, sc->q.shadow, &qc->shadow);
+            QCounters h;
+            if ((st = sync_queue_counters(sc, h))) return st;
+            n_mis = h.mis; n_shadow = h.shadow;
+        }
+        if ((st = one(it.index == 0 ? "extend_camera" : "extend", ext, 0, 0, it.n_ext)) || (st = one("extend_mis", mis, 1, 0, n_mis))) return st;
+        return one("shadow", sh, 2, (int)sh.any, n_shadow);
     }
-    TraceJob tj = trace_job(sc, 0);   // the three ray kinds of this iteration in one launch: one tail of straggling rays instead of three
+    // the three ray kinds of this iteration in one launch: one tail of straggling rays instead of three, and the rays of a vertex side by side (the ray queue's order)
+    TraceJob tj = trace_job(sc, 0);
     tj.sub[0] = ext; tj.sub[1] = mis; tj.sub[2] = sh;
-    return traced(sc, "trace", 2, tj, it.n_ext + it.n_mis + it.n_shadow);
+    tj.sub[0].queue = sc->q.rays; tj.sub[0].count = &qc->rays;   // (TraceJob: the mixed launch's one queue)
+    return traced(sc, "trace", 2, tj, it.n_rays);
 }
 
 // route: every hit goes to the shade queue of its material class. volpath: after medium sampling (volpath.rs:98-105), which may make the vertex a medium vertex
@@ -559,15 +575,15 @@ static int run_pass(pt_scene *sc, RenderConst &rc, const LightGrid &grid, bool r
         if (it.index == max_iterations) return fail(PT_ERR_PROBE_CHAIN, "pass did not finish within " + std::to_string(max_iterations) + " wavefront iterations");
         const int cur = it.cur;
         if (debug_iter && it.index > 0 && it.index % 2048 == 0) {
-            fprintf(stderr, "[iter %d] ext %u shadow %u mis %u probe %u shade:", it.index, h.ext[cur], h.shadow, h.mis, h.probe[cur]);
+            fprintf(stderr, "[iter %d] ext %u rays %u probe %u shade:", it.index, h.ext[cur], h.rays, h.probe[cur]);
             for (int c = 0; c < kNumClasses; ++c) fprintf(stderr, " %u", h.shade[cur][c]);
             fprintf(stderr, "\n");
         }
-        it.n_ext = h.ext[cur]; it.n_resolve = h.shade[cur][kMissClass]; it.n_shadow = h.shadow; it.n_mis = h.mis; it.n_probe = h.probe[cur];
+        it.n_ext = h.ext[cur]; it.n_resolve = h.shade[cur][kMissClass]; it.n_rays = it.index == 0 ? h.ext[cur] : h.rays; it.n_probe = h.probe[cur];
         // volpath with grid media: vertices that did their NEE set-up last iteration wait in their own shade class for stage B
         it.n_stage_b = 0;
         if (rc.volpath && (sc->ds.has_grid || sc->ds.has_shells)) for (int c = 0; c < kNumClasses; ++c) if (c != kMissClass) it.n_stage_b += h.shade[cur][c];
-        if (it.n_ext == 0 && it.n_resolve == 0 && it.n_probe == 0 && it.n_stage_b == 0 && (!it.fin || (it.n_shadow == 0 && it.n_mis == 0))) break;   // (fin: the last vertices' shadow / MIS rays are still to be traced)
+        if (it.n_ext == 0 && it.n_resolve == 0 && it.n_probe == 0 && it.n_stage_b == 0 && (!it.fin || it.n_rays == 0)) break;   // (fin: the last vertices' shadow / MIS rays are still to be traced)
         reset(4u | 1u);
         if ((st = trace_rays(it))) return st;
         route_hits(it);

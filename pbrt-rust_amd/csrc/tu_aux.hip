@@ -3,5 +3,8 @@
 template __global__ void k_shade_miss<false, false>(DeviceScene, RenderConst, PathSoA, ShadeJob);
 template __global__ void k_shade_miss<true, false>(DeviceScene, RenderConst, PathSoA, ShadeJob);
 template __global__ void k_shade_miss<true, true>(DeviceScene, RenderConst, PathSoA, ShadeJob);
+template __global__ void k_test_ray_queue<256>(const uint8_t *, uint32_t, ShadeJob);
+template __global__ void k_test_ray_queue<PT_P2_QCAP>(const uint8_t *, uint32_t, ShadeJob);
+template __global__ void k_test_ray_queue<1024>(const uint8_t *, uint32_t, ShadeJob);
 template __global__ void k_film_final<false>(DeviceScene, RenderConst, PathSoA, const float *, float *, DevCounters *);
 template __global__ void k_film_final<true>(DeviceScene, RenderConst, PathSoA, const float *, float *, DevCounters *);
