@@ -31,6 +31,9 @@ int ptf_write_pfm(const char *path, int width, int height, const float *rgb);
 /* write_image (core/imageio.rs:42-60): by extension -- exr (three FLOAT channels, uncompressed), png / tga (8-bit, gamma
  * encoded, imageio.rs:359-381), pfm. */
 int ptf_write_image(const char *path, int width, int height, const float *rgb);
+/* An EXR file of n_channels FLOAT channels (one part, scan lines, uncompressed): pixel (x, y) of channel i is data[i][(y * width + x) * strides[i]], top row
+ * first. `names` in the byte-wise sorted order the format stores them in (e.g. "N.X" < "Z" < "albedo.B"); anything else is PT_ERR_INVALID_ARG. */
+int ptf_write_exr_channels(const char *path, int width, int height, uint32_t n_channels, const char *const *names, const float *const *data, const uint32_t *strides);
 /* read_image (core/imageio.rs:18-40): pfm, hdr, png, tga, exr (scan-line / tiled / multi-part, NO/RLE/ZIPS/ZIP). Call with rgb == NULL to get the
  * size, then with a buffer of width*height*3 floats (top row first). */
 int ptf_read_image(const char *path, int *width, int *height, float *rgb, size_t capacity_floats);

@@ -48,6 +48,7 @@ def lib():
         L.ptf_scene_destroy.argtypes = [C.c_void_p]
         L.ptf_write_pfm.argtypes = [C.c_char_p, C.c_int, C.c_int, A.fp]
         L.ptf_write_image.argtypes = [C.c_char_p, C.c_int, C.c_int, A.fp]
+        L.ptf_write_exr_channels.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(A.fp), A.u32p]
         L.ptf_read_image.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), A.fp, C.c_size_t]
         L.ptf_params_hash.restype = C.c_uint64; L.ptf_params_hash.argtypes = [C.POINTER(A.PtRenderParams), C.POINTER(AO.PtAOParams)]
         L.ptf_checkpoint_write.argtypes = [C.c_char_p, C.POINTER(PtfCheckpointHeader), A.fp]

@@ -335,16 +335,22 @@ inline Image read_exr(const std::string &path) {
     }
     return im;
 }
-// write_image_exr (imageio.rs:99-114, `write_rgb_f32_file`): three FLOAT channels, scan lines, no compression
-inline void write_exr(const std::string &path, int w, int h, const float *rgb_top_first) {
+// A FLOAT channel of an EXR file to write: pixel (x, y) is data[(y * w + x) * stride], top row first.
+struct ExrChannel { const char *name; const float *data; size_t stride; };
+// One part of FLOAT channels, scan lines in increasing y, no compression. The channel list is stored -- and each scan line's planes follow -- in the order given, which
+// must be the byte-wise sorted order of the names the format requires.
+inline void write_exr(const std::string &path, int w, int h, const std::vector<ExrChannel> &channels) {
+    for (size_t i = 1; i < channels.size(); ++i) if (std::strcmp(channels[i - 1].name, channels[i].name) >= 0) throw std::runtime_error("EXR \"" + path + "\": channel names must be sorted and distinct");
     std::vector<unsigned char> o;
     auto put = [&](const void *q, size_t n) { o.insert(o.end(), (const unsigned char *)q, (const unsigned char *)q + n); };
     auto i32 = [&](int32_t v) { put(&v, 4); };
     auto str = [&](const char *t) { put(t, std::strlen(t) + 1); };
     auto attr = [&](const char *name, const char *type, int32_t size) { str(name); str(type); i32(size); };
     i32(20000630); i32(2);
-    attr("channels", "chlist", 3 * 18 + 1);
-    for (const char *c : {"B", "G", "R"}) { str(c); i32(2); i32(0); i32(1); i32(1); }
+    size_t chlist = 1;
+    for (const ExrChannel &c : channels) chlist += std::strlen(c.name) + 1 + 16;
+    attr("channels", "chlist", (int32_t)chlist);
+    for (const ExrChannel &c : channels) { str(c.name); i32(2); i32(0); i32(1); i32(1); }
     o.push_back(0);
     attr("compression", "compression", 1); o.push_back(0);
     attr("dataWindow", "box2i", 16); i32(0); i32(0); i32(w - 1); i32(h - 1);
@@ -355,16 +361,20 @@ inline void write_exr(const std::string &path, int w, int h, const float *rgb_to
     attr("screenWindowCenter", "v2f", 8); put(&zero, 4); put(&zero, 4);
     attr("screenWindowWidth", "float", 4); put(&one, 4);
     o.push_back(0);
-    const size_t line = 8 + (size_t)w * 12; uint64_t off = o.size() + 8 * (uint64_t)h;
+    const size_t row = (size_t)w * 4 * channels.size(), line = 8 + row; uint64_t off = o.size() + 8 * (uint64_t)h;
     for (int y = 0; y < h; ++y) { put(&off, 8); off += line; }
     std::vector<float> plane((size_t)w);
     for (int y = 0; y < h; ++y) {
-        i32(y); i32((int32_t)((size_t)w * 12));
-        for (int c = 2; c >= 0; --c) { for (int x = 0; x < w; ++x) plane[x] = rgb_top_first[((size_t)y * w + x) * 3 + c]; put(plane.data(), (size_t)w * 4); }   // B, G, R
+        i32(y); i32((int32_t)row);
+        for (const ExrChannel &c : channels) { for (int x = 0; x < w; ++x) plane[x] = c.data[((size_t)y * w + x) * c.stride]; put(plane.data(), (size_t)w * 4); }
     }
     FILE *fp = std::fopen(path.c_str(), "wb");
     if (!fp || std::fwrite(o.data(), 1, o.size(), fp) != o.size()) { if (fp) std::fclose(fp); throw std::runtime_error("cannot write \"" + path + "\""); }
     std::fclose(fp);
+}
+// write_image_exr (imageio.rs:99-114, `write_rgb_f32_file`): three FLOAT channels B, G, R
+inline void write_exr(const std::string &path, int w, int h, const float *rgb_top_first) {
+    write_exr(path, w, h, {{"B", rgb_top_first + 2, 3}, {"G", rgb_top_first + 1, 3}, {"R", rgb_top_first, 3}});
 }
 
 // write_image_png_tga (imageio.rs:359-381): clamp(255 * gamma_correct(v) + 0.5, 0, 255) as u8 (pbrt.rs:210-216)

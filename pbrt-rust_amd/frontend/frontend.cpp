@@ -679,6 +679,14 @@ int ptf_write_image(const char *path, int width, int height, const float *rgb) {
     try { fe::write_image(path, width, height, rgb); } catch (const std::exception &e) { fe::g_error = e.what(); return PT_ERR_INVALID_ARG; }
     return PT_OK;
 }
+int ptf_write_exr_channels(const char *path, int width, int height, uint32_t n_channels, const char *const *names, const float *const *data, const uint32_t *strides) {
+    if (!path || !names || !data || !strides || n_channels == 0 || width <= 0 || height <= 0) { fe::g_error = "ptf_write_exr_channels: bad argument"; return PT_ERR_INVALID_ARG; }
+    std::vector<fe::ExrChannel> ch;
+    for (uint32_t i = 0; i < n_channels; ++i) if (!names[i] || !data[i] || strides[i] == 0) { fe::g_error = "ptf_write_exr_channels: channel " + std::to_string(i) + " has no name, no data or a stride of 0"; return PT_ERR_INVALID_ARG; }
+    for (uint32_t i = 0; i < n_channels; ++i) ch.push_back(fe::ExrChannel{names[i], data[i], strides[i]});
+    try { fe::write_exr(path, width, height, ch); } catch (const std::exception &e) { fe::g_error = e.what(); return PT_ERR_INVALID_ARG; }
+    return PT_OK;
+}
 int ptf_read_image(const char *path, int *width, int *height, float *rgb, size_t capacity_floats) {
     try {
         const fe::Image im = fe::read_image(path);

@@ -1,6 +1,6 @@
 // mi355pbrt -- command-line renderer: the drop-in for `pbrt-rust scene.pbrt` on this back end (main.rs + api.rs:1715-1748).
 //   mi355pbrt scene.pbrt [--outfile out.pfm] [--device N] [--spp N] [--quiet] [--samples A:B] [--checkpoint FILE] [--preview-every N]
-//                        [--adaptive T [--adaptive-step N] [--adaptive-min N]]
+//                        [--adaptive T [--adaptive-step N] [--adaptive-min N]] [--aov FILE.exr]
 // Parses with libmi355front.so, renders with libmi355pt.so (HIP; Integrator "ambientocclusion": libmi355ao.so), writes the film in the format the Film's "filename"
 // extension names (exr -- the reference's default "pbrt.exr" -- png, tga, pfm: core/imageio.rs:42-60).
 // The film lives on the device and is rendered in groups of samples (pt_render_samples); one group -- the whole job -- unless asked otherwise:
@@ -12,7 +12,11 @@
 //                        done, default 0) the 16x16 tiles whose film footprint no longer meets a film tile with halves error > T stop for good (pt_film_halves_error,
 //                        pt_tiles_select, pt_render_tiles), the others go on up to the job's spp. Not with --samples / --checkpoint (the state of an adaptive render is
 //                        a sample count per tile, which neither holds) nor Integrator "ambientocclusion" (libmi355ao has no tile-list render).
+//   --aov FILE.exr       the feature buffers a denoiser takes beside the image (libmi355aov.so), for the sample numbers the image is made of: one uncompressed FLOAT
+//                        scan-line EXR with the channels N.X N.Y N.Z (normalised mean shading normal), Z (mean depth of the hits), albedo.B albedo.G albedo.R. Not with
+//                        --adaptive (libmi355aov has no tile-list render).
 #include "../../include/mi355front.h"
+#include "../../include/mi355aov.h"
 #include <hip/hip_runtime_api.h>
 #include <chrono>
 #include <cstdio>
@@ -22,7 +26,7 @@
 #include <vector>
 
 static const char *kUsage = "usage: mi355pbrt scene.pbrt [--outfile out.pfm] [--device N] [--spp N] [--quiet] [--samples A:B] [--checkpoint FILE] [--preview-every N]\n"
-                            "                 [--adaptive T [--adaptive-step N] [--adaptive-min N]]\n";
+                            "                 [--adaptive T [--adaptive-step N] [--adaptive-min N]] [--aov FILE.exr]\n";
 static int usage(const std::string &why = "") { if (!why.empty()) std::fprintf(stderr, "mi355pbrt: %s\n", why.c_str()); std::fputs(kUsage, stderr); return 2; }
 
 // "A:B" with decimal A < B, both fitting 32 bits
@@ -35,7 +39,7 @@ static bool parse_range(const std::string &a, long long &lo, long long &hi) {
 }
 
 int main(int argc, char **argv) {
-    std::string scene, outfile, samples, checkpoint; int device = 0, spp = 0; long long preview = 0; bool quiet = false;
+    std::string scene, outfile, samples, checkpoint, aov; int device = 0, spp = 0; long long preview = 0; bool quiet = false;
     bool adaptive = false; float threshold = 0.0f; long long astep = 4, amin = 0;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -44,6 +48,7 @@ int main(int argc, char **argv) {
         else if (a == "--spp" && i + 1 < argc) spp = std::atoi(argv[++i]);
         else if (a == "--samples" && i + 1 < argc) samples = argv[++i];
         else if (a == "--checkpoint" && i + 1 < argc) checkpoint = argv[++i];
+        else if (a == "--aov" && i + 1 < argc) aov = argv[++i];
         else if (a == "--preview-every" && i + 1 < argc) { preview = std::atoll(argv[++i]); if (preview <= 0 || preview > 0xffffffffll) return usage("--preview-every takes a number of samples > 0"); }
         else if (a == "--adaptive" && i + 1 < argc) {
             char *end = nullptr; threshold = std::strtof(argv[++i], &end);
@@ -59,6 +64,7 @@ int main(int argc, char **argv) {
     if (scene.empty()) return usage();
     if (adaptive && !samples.empty()) return usage("--adaptive with --samples: an adaptive render chooses its own sample ranges, tile by tile");
     if (adaptive && !checkpoint.empty()) return usage("--adaptive with --checkpoint: a checkpoint holds one sample count for the frame, an adaptive render one per tile");
+    if (adaptive && !aov.empty()) return usage("--adaptive with --aov: the feature buffers have no tile-list render");
     long long lo = 0, hi = 0;
     if (!samples.empty() && !parse_range(samples, lo, hi)) return usage("--samples takes A:B with 0 <= A < B, got \"" + samples + "\"");
     ptf_scene *fs = nullptr;
@@ -157,6 +163,22 @@ int main(int argc, char **argv) {
     }
     const auto t2 = std::chrono::steady_clock::now();
     if (!write_out()) return 1;
+    if (!aov.empty()) {   // the planes of sample numbers [first, last), whatever groups (or earlier runs, --checkpoint) rendered the image's
+        std::vector<float> sums(npix * 10, 0.0f), res(npix * 7);
+        float *d_sums = nullptr;
+        if (hipMalloc((void **)&d_sums, npix * 40) != hipSuccess || hipMemset(d_sums, 0, npix * 40) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { std::fprintf(stderr, "mi355pbrt: feature buffers: %s\n", hipGetErrorString(hipGetLastError())); return 1; }
+        const PtAOVBuffers d_planes{d_sums, d_sums + npix * 4, d_sums + npix * 8};
+        if (pt_aov_render_samples(sc, &rp, first, last - first, &d_planes, 1) != PT_OK) { std::fprintf(stderr, "mi355pbrt: %s\n", pt_last_error()); return 1; }
+        if (hipMemcpy(sums.data(), d_sums, npix * 40, hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "mi355pbrt: reading the feature buffers back failed\n"); return 1; }
+        (void)hipFree(d_sums);
+        const PtAOVBuffers planes{sums.data(), sums.data() + npix * 4, sums.data() + npix * 8};
+        float *albedo = res.data(), *normal = res.data() + npix * 3, *depth = res.data() + npix * 6;
+        if (pt_aov_resolve(&planes, (uint32_t)npix, albedo, normal, depth) != PT_OK) { std::fprintf(stderr, "mi355pbrt: %s\n", pt_last_error()); return 1; }
+        const char *names[7] = {"N.X", "N.Y", "N.Z", "Z", "albedo.B", "albedo.G", "albedo.R"};   // (byte-wise sorted, as the format stores them)
+        const float *data[7] = {normal, normal + 1, normal + 2, depth, albedo + 2, albedo + 1, albedo};
+        const uint32_t strides[7] = {3, 3, 3, 1, 3, 3, 3};
+        if (ptf_write_exr_channels(aov.c_str(), w, h, 7, names, data, strides) != PT_OK) { std::fprintf(stderr, "mi355pbrt: %s\n", ptf_last_error()); return 1; }
+    }
     if (!quiet) {
         const double ts = std::chrono::duration<double>(t1 - t0).count(), tr = std::chrono::duration<double>(t2 - t1).count();
         std::printf("%s: %dx%d, %u spp, %llu camera rays, scene %.2f s, render %.3f s (%.1f Msamples/s) -> %s\n", scene.c_str(), w, h, rp.spp,

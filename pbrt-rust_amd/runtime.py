@@ -6,16 +6,18 @@ import subprocess
 import numpy as np
 from . import _abi as A
 from . import _abi_ao as AO
+from . import _abi_aov as AOV
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PT_LIB_PATH") or os.path.join(_HERE, "csrc", "libmi355pt.so")   # PT_LIB_PATH: kernel-variant experiments
 AO_LIB_PATH = os.path.join(_HERE, "ao", "libmi355ao.so")   # the ambient-occlusion integrator (include/mi355ao.h), linked against libmi355pt.so
+AOV_LIB_PATH = os.path.join(_HERE, "aov", "libmi355aov.so")   # the feature buffers for denoising (include/mi355aov.h), linked against libmi355pt.so
 TABLES_PATH = os.path.join(_HERE, "data", "sobol_tables.bin")
 
 
 def build_library(verbose=False):
-    """Compile every HIP source for gfx950 (hipcc cross-compiles without a GPU): libmi355pt.so, then libmi355ao.so, which links against it."""
-    for sub, name in (("csrc", "libmi355pt.so"), ("ao", "libmi355ao.so")):
+    """Compile every HIP source for gfx950 (hipcc cross-compiles without a GPU): libmi355pt.so, then libmi355ao.so and libmi355aov.so, which link against it."""
+    for sub, name in (("csrc", "libmi355pt.so"), ("ao", "libmi355ao.so"), ("aov", "libmi355aov.so")):
         r = subprocess.run(["make", "-C", os.path.join(_HERE, sub), "-j8"], capture_output=True, text=True)
         if verbose or r.returncode != 0:
             print(r.stdout[-4000:]); print(r.stderr[-4000:])
@@ -34,6 +36,16 @@ class Library:
             raise PtError(f"{path} not found: build it with __graft_entry__.build() (no CPU fallback exists)")
         self.lib = A.bind(C.CDLL(path), strict=not os.environ.get("PT_LIB_PATH"))   # (PT_LIB_PATH: a kernel-variant library of an A/B run, possibly built from an older tree)
         self._ao = None
+        self._aov = None
+
+    @property
+    def aov(self):
+        """libmi355aov.so (include/mi355aov.h), loaded on first use."""
+        if self._aov is None:
+            if not os.path.exists(AOV_LIB_PATH):
+                raise PtError(f"{AOV_LIB_PATH} not found: build it with __graft_entry__.build() (no CPU fallback exists)")
+            self._aov = A.bind(C.CDLL(AOV_LIB_PATH), table=AOV.ENTRY_POINTS)
+        return self._aov
 
     @property
     def ao(self):
@@ -69,6 +81,18 @@ def load_library():
 
 def _fptr(a):
     return a.ctypes.data_as(A.fp)
+
+
+def resolve_aov(sums, lib=None):
+    """pt_aov_resolve of the sums Scene.render_aov returns: {"albedo": (H, W, 3) = sum / weight of all samples, "normal": (H, W, 3) = the normalised sum,
+    "depth": (H, W) = sum / weight of the hits}, 0 where the weight is 0; the planes `sums` holds."""
+    lib = lib or load_library()
+    sums = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in sums.items()}
+    shape = next(iter(sums.values())).shape[:2]
+    out = {k: np.zeros(shape + ((3,) if k != "depth" else ()), dtype=np.float32) for k in sums}
+    bufs = AOV.PtAOVBuffers(*[_fptr(sums[k]) if k in sums else None for k in AOV.PLANES])
+    lib.check(lib.aov.pt_aov_resolve(C.byref(bufs), shape[0] * shape[1], *[_fptr(out[k]) if k in out else None for k in AOV.PLANES]), "pt_aov_resolve")
+    return out
 
 
 class Handle:
@@ -282,6 +306,29 @@ class Scene(Handle):
                 on_round(done, active, worst)
         self.adaptive_counters = total
         return (halves[0] + halves[1]).cpu().numpy(), per_tile.reshape(nty, ntx)
+
+    def render_aov(self, rp, samples=None, planes=AOV.PLANES, device_ptrs=None, sums=None):
+        """The feature buffers of the job `rp` (pt_aov_render; `samples` = (first, n): pt_aov_render_samples): a dict of the un-normalised sums per wanted plane --
+        "albedo" (H, W, 4) = sum w * rgb and sum w over all samples, "normal" (H, W, 4) = sum w * n and sum w over the samples that reach a surface, "depth" (H, W, 2) =
+        sum w * t and the same weight. ADDED to the arrays of `sums` (a dict this method returned, for the same planes) when given, in place: a pixel's samples
+        continue the chain of additions where the earlier call left it. `device_ptrs` = {plane: device pointer as an integer}: added to those buffers, returns None."""
+        args = [self.h, C.byref(rp)] + ([] if samples is None else list(samples))
+        name = "aov_render" if samples is None else "aov_render_samples"
+        if device_ptrs is not None:
+            bufs = AOV.PtAOVBuffers(*[C.cast(C.c_void_p(device_ptrs[k]), A.fp) if k in device_ptrs else None for k in AOV.PLANES])
+            self._call(name, *args, C.byref(bufs), 1, lib=self.L.aov); return None
+        if sums is None:
+            cb = rp.cropped_pixel_bounds
+            sums = {k: np.zeros((cb[3] - cb[1], cb[2] - cb[0], AOV.CHANNELS[k]), dtype=np.float32) for k in planes}
+        bufs = AOV.PtAOVBuffers(*[_fptr(sums[k]) if k in sums else None for k in AOV.PLANES])
+        self._call(name, *args, C.byref(bufs), 0, lib=self.L.aov)
+        return sums
+
+    def aov_pass_size(self, rp):
+        """Samples per pixel per pass pt_aov_render would use for `rp` now."""
+        s = C.c_uint32()
+        self._call("aov_pass_size", self.h, C.byref(rp), C.byref(s), lib=self.L.aov)
+        return int(s.value)
 
     def ao_params(self):
         """The scene's PtAOParams (SceneBuilder.integ / the front end's "ambientocclusion" parameters)."""

@@ -616,12 +616,13 @@ def foggy_room(xres=96, yres=64, spp=16, maxdepth=5, g=0.3, camera_in_fog=True, 
     return b
 
 
-def shell_media(xres=64, yres=48, spp=8, maxdepth=5, grid=True, sampler="sobol", light_inside=True):
+def shell_media(xres=64, yres=48, spp=8, maxdepth=5, grid=True, sampler="sobol", light_inside=True, box_lift=0.0):
     """Media bounded the way a .pbrt file bounds them: by shapes WITHOUT a material (`Material "none"`, api.rs:597) that only carry a
     MediumInterface. The camera stands in vacuum; a sphere shell holds a homogeneous coloured fog, a box shell a GridDensityMedium
     (grid=True), the two overlap the light paths of an opaque floor, a wall, an area light, a point light (inside the fog when
     light_inside) and an environment. Every shadow ray and MIS ray that crosses a shell walks VisibilityTester::tr / Scene::intersect_tr
-    segment by segment (light.rs:125-150, scene.rs:68-87); camera paths cross with volpath.rs:152-156's `bounces -= 1`."""
+    segment by segment (light.rs:125-150, scene.rs:68-87); camera paths cross with volpath.rs:152-156's `bounces -= 1`.
+    The box shell's bottom face lies in the floor's plane (a ray inside the box meets both at one t); box_lift > 0 raises the box and its medium by that much."""
     b = SceneBuilder()
     b.film.update(xres=xres, yres=yres); b.spp = spp; b.sampler = sampler
     b.integ.update(maxdepth=maxdepth, kind="volpath")
@@ -629,7 +630,7 @@ def shell_media(xres=64, yres=48, spp=8, maxdepth=5, grid=True, sampler="sobol",
     if grid:
         rng = np.random.default_rng(9)
         dens = rng.uniform(0.1, 1.0, (5, 4, 6)).astype(np.float32)
-        b.make_named_medium("smoke", sigma_a=(0.4, 0.4, 0.4), sigma_s=(1.6, 1.6, 1.6), g=-0.2, density=dens, p0=(0.6, 0.0, -1.0), p1=(2.6, 1.6, 1.0))
+        b.make_named_medium("smoke", sigma_a=(0.4, 0.4, 0.4), sigma_s=(1.6, 1.6, 1.6), g=-0.2, density=dens, p0=(0.6, 0.0 + box_lift, -1.0), p1=(2.6, 1.6 + box_lift, 1.0))
     b.look_at((0.0, 1.8, 6.5), (0.0, 0.7, 0.0), (0.0, 1.0, 0.0)); b.camera(fov=40.0)
     b.world_begin()
     b.light_source("infinite", L=(0.08, 0.1, 0.14))
@@ -644,7 +645,7 @@ def shell_media(xres=64, yres=48, spp=8, maxdepth=5, grid=True, sampler="sobol",
     b.attribute_begin(); b.material("none"); b.medium_interface("fog", ""); b.translate(-1.4, 0.95, 0.0); b.sphere(radius=0.9); b.attribute_end()
     if grid:   # the grid medium in a box shell of twelve triangles
         b.attribute_begin(); b.material("none"); b.medium_interface("smoke", "")
-        x0, y0, z0, x1, y1, z1 = 0.6, 0.0, -1.0, 2.6, 1.6, 1.0
+        x0, y0, z0, x1, y1, z1 = 0.6, 0.0 + box_lift, -1.0, 2.6, 1.6 + box_lift, 1.0
         c = [(x0, y0, z0), (x1, y0, z0), (x1, y1, z0), (x0, y1, z0), (x0, y0, z1), (x1, y0, z1), (x1, y1, z1), (x0, y1, z1)]
         faces = [(0, 3, 2, 1), (4, 5, 6, 7), (0, 1, 5, 4), (3, 7, 6, 2), (0, 4, 7, 3), (1, 2, 6, 5)]   # outward normals
         for f in faces:
