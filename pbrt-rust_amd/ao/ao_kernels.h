@@ -48,17 +48,9 @@ __global__ __launch_bounds__(256) void k_ao_rays(DeviceScene s, RenderConst rc, 
             found = __float_as_uint(h0.x) != PT_NONE;
         }
         // one atomic per wave: the wave's hit paths take consecutive blocks of kn ray ids, in lane order
-        const unsigned long long mask = __ballot(found);
-        const uint32_t lane = lane_id();
-        uint32_t base = 0;
-        if (mask != 0ull) {
-            const uint32_t leader = (uint32_t)__ffsll((long long)mask) - 1u;
-            if (lane == leader) base = atomicAdd(job.ray_count, (uint32_t)__popcll(mask) * job.kn);
-            base = __shfl(base, (int)leader);
-        }
+        const uint32_t first = wave_reserve(job.ray_count, found, job.kn);
         if (qi >= count) continue;
         if (!found) { job.base[pid] = PT_NONE; continue; }
-        const uint32_t first = base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull)) * job.kn;
         job.base[pid] = first;
         const V3 ro(r0.x, r0.y, r0.z), rd(r0.w, r1.x, r1.y);
         SurfaceInteraction si;

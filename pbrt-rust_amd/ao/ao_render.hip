@@ -8,8 +8,10 @@
 //     k_ao_accum                   L += the unoccluded rays' terms, in order
 //   k_film                         sanitise + splat (libmi355pt)
 // The scene, its workspace, the device counters, the traversal and the render frame -- the shared checks, the pass loop, the film's way out, the counters
-// (frame_geometry / render_frame, render_loop.hip) -- are libmi355pt's (host_common.h): this library adds AO's own checks and pass size (ao_geometry), one pass
-// (ao_pass), the kernels of ao_kernels.h and the buffers of the AO rays, which live for one call.
+// (frame_geometry / render_frame, render_loop.hip) -- are libmi355pt's (host_common.h), and so are the steps a pass shares with the path integrator's: the pass size the
+// library chooses (choose_pass_size: one budget rule, given AO's bytes per path), the camera-ray traversal set-up (extend_sub / trace_job / traced), the launch geometry
+// (blocks_for, general_geometry) and the k_film step (film_pass). This library adds AO's own checks and budget (ao_geometry), one pass (ao_pass), the kernels of
+// ao_kernels.h and the buffers of the AO rays, which live for one call.
 #include "../csrc/host_common.h"
 #include "../../include/mi355ao.h"
 #include "ao_kernels.h"
@@ -21,8 +23,6 @@ namespace {
 constexpr double kAOMemFraction = 0.5;   // of the device's free memory, for a pass the caller leaves to the library
 constexpr size_t kAOMaxRays = (size_t)1 << 31;   // ray ids per chunk (32-bit ids, k_trace's queue index)
 constexpr size_t kAORayBytes = 32 + 4 + 4;       // ray record, weight, any-hit flag
-// per path: libmi355pt's workspace (path records + at most 2 + 2 x 11 + 2 + 2 queues) and the ray id base
-constexpr size_t kAOPathBytes = (size_t)kPathBytes + 4 * (2 + 2 * kNumClasses + 2 + 2) + 4;
 
 struct Geometry { RenderConst rc; uint32_t S; uint32_t K; };
 
@@ -48,17 +48,8 @@ int ao_geometry(pt_scene *sc, const PtRenderParams *rp, const PtAOParams *ao, ui
     }
     g.K = std::min<uint32_t>(ao->nsamples, kAOChunk);
     uint32_t S = rp->spp_per_pass;
-    if (S == 0 && rc.n_pix_slots > 0) {
-        const size_t per_path = kAOPathBytes + (size_t)g.K * kAORayBytes;
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
-        // (the scene's present workspace is freed before a larger one is allocated)
-        const size_t afford = (size_t)((double)(free_b + sc->capacity * (size_t)kPathBytes) * kAOMemFraction) / per_path;
-        const size_t paths = std::min(afford, kAOMaxRays / g.K);
-        S = (uint32_t)std::min<size_t>(n_samples, std::max<size_t>(1, paths / rc.n_pix_slots));
-        const uint32_t n_pass = (n_samples + S - 1) / S;
-        S = (n_samples + n_pass - 1) / n_pass;   // passes of equal size
-    }
+    // (per path besides libmi355pt's workspace: the ray id base and the chunk's rays)
+    if (S == 0 && rc.n_pix_slots > 0) S = choose_pass_size(sc, rc.n_pix_slots, n_samples, 1, false, PassBudget{4 + (size_t)g.K * kAORayBytes, kAOMemFraction, kAOMaxRays / g.K});
     if (int st = frame_pass_size(rc, S, n_samples, &g.S)) return st;
     if ((size_t)rc.n_pix_slots * g.S * g.K > kAOMaxRays) return fail(PT_ERR_INVALID_ARG, "pass too large: paths x min(nsamples, 64) AO rays per launch > 2^31 (lower spp_per_pass)");
     return PT_OK;
@@ -82,21 +73,12 @@ struct AOBuffers {
 int ao_pass(pt_scene *sc, const RenderConst &rc, const PtAOParams *ao, uint32_t K, AOBuffers &b) {
     const uint32_t total = rc.n_pix_slots * rc.s_count;
     QCounters *qc = sc->qc;
-    const uint32_t blocks_cap = (uint32_t)g_num_cus * 16u;
-    TraceJob tj{};
-    tj.spill = sc->spill; tj.error = &qc->error; tj.counters = sc->dc; tj.head = &qc->head[0];
-    TraceSub cam{};   // camera rays -> hit records (Scene::intersect, ao.rs:72)
-    cam.queue = sc->q.ext[0]; cam.count = &qc->ext[0]; cam.scalar_tmax = INFINITY;
-    cam.ray = (const float4 *)sc->ps.ray; cam.ray_stride = PathSoA::kRayWords / 4;
-    cam.out_hit = (float4 *)sc->ps.hit; cam.out_hit_stride = PathSoA::kHitWords / 4; cam.out_hit2 = (float4 *)sc->ps.hit + 1;
-    cam.kind = 3;
-    tj.sub[0] = cam;
-    sc->begin("extend_camera", total);
-    int st = launch_trace(sc, 0, tj, total);
-    sc->end();
-    if (st) return st;
-    const bool sph = sc->ds.n_spheres > 0 || sc->ds.n_instances > 0;
-    const uint32_t qblocks = std::min<uint32_t>((total + 255) / 256, blocks_cap);
+    TraceJob cam = trace_job(sc, 0);   // camera rays -> hit records (Scene::intersect, ao.rs:72)
+    cam.sub[0] = extend_sub(sc, 0, true);
+    int st;
+    if ((st = traced(sc, "extend_camera", 0, cam, total))) return st;
+    const bool sph = general_geometry(sc);
+    const dim3 qblocks = blocks_for(total, 16u);
     for (uint32_t k0 = 0; k0 < ao->nsamples; k0 += K) {
         AOJob job{};
         job.nsamples = ao->nsamples; job.cos_sample = ao->cos_sample ? 1u : 0u;
@@ -105,30 +87,20 @@ int ao_pass(pt_scene *sc, const RenderConst &rc, const PtAOParams *ao, uint32_t 
         HIP_TRY(hipMemsetAsync(b.count, 0, 4, sc->stream));
         HIP_TRY(hipMemsetAsync(qc->head, 0, sizeof qc->head, sc->stream));
         sc->begin("ao_rays", (uint64_t)total * job.kn);
-        sc->set_kernel(sph ? "ptao::k_ao_rays<true>" : "ptao::k_ao_rays<false>");
-        if (sph) hipLaunchKernelGGL((k_ao_rays<true>), dim3(qblocks), dim3(256), 0, sc->stream, sc->ds, rc, g_tabs, sc->ps, (const uint32_t *)sc->q.ext[0], (const uint32_t *)&qc->ext[0], job);
-        else hipLaunchKernelGGL((k_ao_rays<false>), dim3(qblocks), dim3(256), 0, sc->stream, sc->ds, rc, g_tabs, sc->ps, (const uint32_t *)sc->q.ext[0], (const uint32_t *)&qc->ext[0], job);
+        if (sph) launch(sc, "ptao::k_ao_rays<true>", k_ao_rays<true>, qblocks, dim3(256), sc->ds, rc, g_tabs, sc->ps, sc->q.ext[0], &qc->ext[0], job);
+        else launch(sc, "ptao::k_ao_rays<false>", k_ao_rays<false>, qblocks, dim3(256), sc->ds, rc, g_tabs, sc->ps, sc->q.ext[0], &qc->ext[0], job);
         sc->end();
         HIP_TRY(hipGetLastError());
-        TraceSub sh{};   // the AO rays: Scene::intersect_p of spawn_ray(wi) (ao.rs:94)
-        sh.queue = nullptr; sh.count = b.count; sh.scalar_tmax = INFINITY;
-        sh.ray = b.ray; sh.ray_stride = 2;
-        sh.out_word = b.occ; sh.out_word_stride = 1;
-        sh.kind = 2; sh.any = 1;
-        tj.sub[0] = sh; tj.head = &qc->head[2];
-        sc->begin("shadow", (uint64_t)total * job.kn);
-        st = launch_trace(sc, 1, tj, total * job.kn);   // (an upper bound: the launch reads the count of rays spawned)
-        sc->end();
-        if (st) return st;
-        sc->begin("ao_accum", total); sc->set_kernel("ptao::k_ao_accum");
-        hipLaunchKernelGGL(k_ao_accum, dim3(qblocks), dim3(256), 0, sc->stream, sc->ps, (const uint32_t *)sc->q.ext[0], (const uint32_t *)&qc->ext[0], job);
+        TraceJob tj = trace_job(sc, 2);   // the AO rays: Scene::intersect_p of spawn_ray(wi) (ao.rs:94); ray ids, no queue
+        tj.sub[0] = trace_sub(nullptr, b.count, (const float *)b.ray, 8, INFINITY, 2);
+        tj.sub[0].out_word = b.occ; tj.sub[0].out_word_stride = 1; tj.sub[0].any = 1;
+        if ((st = traced(sc, "shadow", 1, tj, total * job.kn))) return st;   // (an upper bound: the launch reads the count of rays spawned)
+        sc->begin("ao_accum", total);
+        launch(sc, "ptao::k_ao_accum", k_ao_accum, qblocks, dim3(256), sc->ps, sc->q.ext[0], &qc->ext[0], job);
         sc->end();
         HIP_TRY(hipGetLastError());
     }
-    sc->begin("film", total); sc->set_kernel("k_film");
-    hipLaunchKernelGGL(k_film, dim3((unsigned)(((size_t)rc.n_pix_slots + 255) / 256)), dim3(256), 0, sc->stream, rc, sc->ps, sc->d_filter, sc->film_rgbw, sc->dc);
-    sc->end();
-    HIP_TRY(hipGetLastError());
+    if ((st = film_pass(sc, rc))) return st;
     QCounters h;
     return sync_queue_counters(sc, h);   // (a status a kernel raised fails the call here)
 }

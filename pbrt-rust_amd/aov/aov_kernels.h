@@ -76,8 +76,9 @@ __global__ __launch_bounds__(256, 1) void k_aov(DeviceScene s, RenderConst rc, S
                     }
                     const TexCtx tctx = compute_differentials(si, rdiff);
                     V3 n = si.sh_n;
-                    // bump() (core/material.rs:46-87). NOTE: the body is k_shade's (kern_shade.h, `if (mi != PT_NONE && s.materials[mi].tex[PT_MP_BUMP] >= 0)`), restated here because
-                    // csrc/ could not change with this library: a fix to either belongs in both, until the next change to csrc/ makes it one device helper.
+                    // bump() (core/material.rs:46-87). NOTE: the body is k_shade's (kern_shade.h, `if (mi != PT_NONE && s.materials[mi].tex[PT_MP_BUMP] >= 0)`), restated here: as one
+                    // inlined device helper called from both, the textured k_shade forms came out of the compiler with other registers (k_shade<1, 2, 0> 63 -> 64 AGPRs, <1, 2, 1>
+                    // 52 -> 54; profiles/r6/NOTES.md section 15), and those kernels' code objects do not move for a tidier source. A fix to either belongs in both.
                     if ((job.mask & kAovNormal) && m.tex[PT_MP_BUMP] >= 0) {
                         const int dtex = m.tex[PT_MP_BUMP];
                         TexCtx e = tctx;
@@ -111,14 +112,8 @@ __global__ __launch_bounds__(256, 1) void k_aov(DeviceScene s, RenderConst rc, S
             }
         }
         // one atomic per wave: its continuing lanes take consecutive queue entries, in lane order
-        const unsigned long long mask = __ballot(go_on);
-        if (mask != 0ull) {
-            const uint32_t lane = lane_id(), leader = (uint32_t)__ffsll((long long)mask) - 1u;
-            uint32_t base = 0;
-            if (lane == leader) base = atomicAdd(job.next_count, (uint32_t)__popcll(mask));
-            base = __shfl(base, (int)leader);
-            if (go_on) job.next[base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = pid;
-        }
+        const uint32_t at = wave_reserve(job.next_count, go_on, 1u);
+        if (go_on) job.next[at] = pid;
     }
 }
 

@@ -7,8 +7,10 @@
 //     k_trace<closest>             the continuations' hits ("extend")
 //     k_aov                        their records
 //   k_aov_film                     the records' splats onto the planes, a pixel's own samples in sample order
-// The scene, its workspace, the device counters, the traversal and the render frame are libmi355pt's (host_common.h), as for libmi355ao: this library adds its checks and
-// pass size (aov_geometry), one pass (aov_pass), the kernels of aov_kernels.h, the records and the planes. The planes are the CALLER's while a call runs: device buffers
+// The scene, its workspace, the device counters, the traversal, the render frame and the steps a pass shares with the path integrator's -- the pass size the library chooses
+// (choose_pass_size: one budget rule, given the record's bytes per path), the traversal set-up (extend_sub / trace_job / traced) and the launch geometry (blocks_for, film_grid,
+// general_geometry) -- are libmi355pt's (host_common.h), as for libmi355ao: this library adds its checks and budget (aov_geometry), one pass (aov_pass), the kernels of
+// aov_kernels.h, the records and the planes. The planes are the CALLER's while a call runs: device buffers
 // are added to in place; host buffers are copied up, added to and copied back when every pass has succeeded -- so the additions onto a pixel are one chain in sample order
 // however the job is cut into calls and passes. The frame's own film stays empty and is delivered to a scratch buffer.
 #include "../csrc/host_common.h"
@@ -20,9 +22,7 @@ using namespace ptaov;
 namespace {
 
 constexpr double kAovMemFraction = 0.5;   // of the device's free memory, for a pass the caller leaves to the library
-constexpr size_t kAovRecBytes = 32;       // the sample's record (aov_kernels.h: AovJob)
-// per path: libmi355pt's workspace (path records + at most 2 + 2 x 11 + 2 + 2 queues) and the record
-constexpr size_t kAovPathBytes = (size_t)kPathBytes + 4 * (2 + 2 * kNumClasses + 2 + 2) + kAovRecBytes;
+constexpr size_t kAovRecBytes = 32;       // the sample's record (aov_kernels.h: AovJob): what a path costs besides libmi355pt's workspace
 constexpr int kAovMaxRounds = 1 << 16;    // continuations of one camera ray: a scene's shells are finitely many
 
 struct Geometry { RenderConst rc; uint32_t S; };
@@ -40,15 +40,8 @@ int aov_geometry(pt_scene *sc, const PtRenderParams *rp, uint32_t n_samples, Geo
     p.integrator = PT_INTEGRATOR_PATH;   // (not read: no medium, no volpath state)
     if (int st = frame_geometry(sc, &p, rc)) return st;
     uint32_t S = rp->spp_per_pass;
-    if (S == 0 && rc.n_pix_slots > 0) {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
-        // (the scene's present workspace is freed before a larger one is allocated)
-        const size_t paths = (size_t)((double)(free_b + sc->capacity * (size_t)kPathBytes) * kAovMemFraction) / kAovPathBytes;
-        S = (uint32_t)std::min<size_t>(n_samples, std::max<size_t>(1, paths / rc.n_pix_slots));
-        const uint32_t n_pass = (n_samples + S - 1) / S;
-        S = (n_samples + n_pass - 1) / n_pass;   // passes of equal size
-    }
+    // (the most paths of a pass: what the workspace's ray queue addresses, kernels.h)
+    if (S == 0 && rc.n_pix_slots > 0) S = choose_pass_size(sc, rc.n_pix_slots, n_samples, 1, false, PassBudget{kAovRecBytes, kAovMemFraction, kMaxRayQueuePaths});
     return frame_pass_size(rc, S, n_samples, &g.S);
 }
 
@@ -84,28 +77,19 @@ int aov_prepare(pt_scene *sc, const Geometry &g, const PtAOVBuffers *b, int on_d
 int aov_pass(pt_scene *sc, const RenderConst &rc, AovCall &c) {
     const uint32_t total = rc.n_pix_slots * rc.s_count;
     QCounters *qc = sc->qc;
-    const uint32_t blocks_cap = (uint32_t)g_num_cus * 16u;
-    const bool sph = sc->ds.n_spheres > 0 || sc->ds.n_instances > 0;
-    TraceJob tj{};
-    tj.spill = sc->spill; tj.error = &qc->error; tj.counters = sc->dc; tj.head = &qc->head[0];
+    const bool sph = general_geometry(sc);
     uint32_t n = total;   // rays of the round (round 0: an upper bound, the launches read the count of camera rays)
     for (int round = 0, cur = 0; n > 0; ++round, cur = 1 - cur) {
         if (round == kAovMaxRounds) return fail(PT_ERR_PROBE_CHAIN, "feature buffers: camera rays still going on behind material-less surfaces after " + std::to_string(round) + " continuations");
-        TraceSub sub{};   // Scene::intersect of the camera rays, then of the rays spawned behind shells
-        sub.queue = sc->q.ext[cur]; sub.count = &qc->ext[cur]; sub.scalar_tmax = INFINITY;
-        sub.ray = (const float4 *)sc->ps.ray; sub.ray_stride = PathSoA::kRayWords / 4;
-        sub.out_hit = (float4 *)sc->ps.hit; sub.out_hit_stride = PathSoA::kHitWords / 4; sub.out_hit2 = (float4 *)sc->ps.hit + 1;
-        sub.kind = round == 0 ? 3 : 0;
-        tj.sub[0] = sub;
+        TraceJob tj = trace_job(sc, 0);   // Scene::intersect of the camera rays, then of the rays spawned behind shells
+        tj.sub[0] = extend_sub(sc, cur, round == 0);
         if (round > 0) HIP_TRY(hipMemsetAsync(qc->head, 0, sizeof qc->head, sc->stream));
-        sc->begin(round == 0 ? "extend_camera" : "extend", n);
-        int st = launch_trace(sc, 0, tj, n);
-        sc->end();
-        if (st) return st;
+        int st;
+        if ((st = traced(sc, round == 0 ? "extend_camera" : "extend", 0, tj, n))) return st;
         AovJob job{};
         job.rec = c.rec; job.next = sc->q.ext[1 - cur]; job.next_count = &qc->ext[1 - cur]; job.mask = c.mask; job.first_round = round == 0 ? 1u : 0u;
         HIP_TRY(hipMemsetAsync(&qc->ext[1 - cur], 0, 4, sc->stream));
-        const dim3 grid(std::min<uint32_t>((n + 255) / 256, blocks_cap));
+        const dim3 grid = blocks_for(n, 16u);
         sc->begin("aov", n);
         if (sph) launch(sc, "ptaov::k_aov<true>", k_aov<true>, grid, dim3(256), sc->ds, rc, g_tabs, sc->ps, sc->q.ext[cur], &qc->ext[cur], job);
         else launch(sc, "ptaov::k_aov<false>", k_aov<false>, grid, dim3(256), sc->ds, rc, g_tabs, sc->ps, sc->q.ext[cur], &qc->ext[cur], job);
@@ -117,7 +101,7 @@ int aov_pass(pt_scene *sc, const RenderConst &rc, AovCall &c) {
         n = h.ext[1 - cur];
     }
     sc->begin("film", total);
-    launch(sc, "ptaov::k_aov_film", k_aov_film, dim3((unsigned)(((size_t)rc.n_pix_slots + 255) / 256)), dim3(256), rc, sc->ps, c.rec, sc->d_filter, c.planes, sc->dc);
+    launch(sc, "ptaov::k_aov_film", k_aov_film, film_grid(rc), dim3(256), rc, sc->ps, c.rec, sc->d_filter, c.planes, sc->dc);
     sc->end();
     HIP_TRY(hipGetLastError());
     QCounters h;

@@ -5,7 +5,11 @@
 //                     plan_build, accelerators and every derived table (two- and four-wide records, packet order, shade classes, texture programs, env distribution)
 //   scene_create.hip  pt_scene_create: plan_validate, ensure_device, plan_build (host SAH / GPU HLBVH), uploads, the record / packet pool, light records
 //   render_loop.hip   the wavefront scheduler: kernel variants and the shade-class table, workspace, light grids, launch_trace, run_pass and its steps, counters and kernel stats;
-//                     the render frame every integrator's entry point goes through (frame_geometry, render_frame, deliver_film) and the path integrator's own: pt_render, pt_pass_size
+//                     the render frame every integrator's entry point goes through (frame_geometry, render_frame, deliver_film) and the path integrator's own: pt_render, pt_pass_size.
+//                     What an integrator library's pass (libmi355ao, libmi355aov) shares with run_pass is declared below: the pass size the library chooses
+//                     (choose_pass_size: ONE budget rule, pass_budget.h), the launch geometry (blocks_for, film_grid, general_geometry), the traversal set-up
+//                     (trace_sub, extend_sub, trace_job, traced) and the k_film step (film_pass)
+//   pass_budget.h     that rule's arithmetic, host-only (no HIP call): checked on the CPU by tests/pass_budget
 //   parity_api.hip    the entry points tests use to compare single stages with the oracle (rays, Sobol' / Halton samples, camera rays)
 //   multi_device.hip  pt_multi_*: one process driving several devices (one host thread + stream per replica, peer-copy film merge)
 //   film_tools.hip    pt_film_resolve_device / pt_film_halves_error / pt_tiles_select: a film on the device resolved to rgb / 8-bit sRGB, the convergence estimate of two
@@ -27,6 +31,7 @@
 #include "kern_decl.h"   // kernel declarations; the definitions are instantiated by the tu_*.hip translation units
 #include "host_bvh.h"
 #include "scene_plan.h"   // material_class, dist1d, the scene plan
+#include "pass_budget.h"  // PassBudget, pass_size_for: the pass size the library chooses
 
 namespace pth {
 
@@ -187,13 +192,28 @@ namespace pth {
 // every launch of the render stream: the symbol goes to the launch kind opened by the last begin()
 template <class... P, class... A> void launch(pt_scene *sc, const std::string &name, void (*fn)(P...), dim3 blocks, dim3 threads, const A &...args) { sc->set_kernel(name); hipLaunchKernelGGL(fn, blocks, threads, 0, sc->stream, static_cast<P>(args)...); }
 // render_loop.hip
+// Launch geometry: persistent blocks of 256 threads for n_upper items, per_cu a CU at the most; one thread per pixel slot for the film kernels (kern_film.h)
+dim3 blocks_for(uint32_t n_upper, uint32_t per_cu);
+inline dim3 film_grid(const RenderConst &rc) { return dim3((unsigned)(((size_t)rc.n_pix_slots + 255) / 256)); }
+bool general_geometry(const pt_scene *sc);   // spheres or instances besides world-space triangles: the kernels' SPH forms
+// A traversal launch: the rays of one kind (trace_sub; extend_sub: the continuation rays of queue set `cur`, camera rays in a pass's first round) in a job with the scene's
+// spill area, error word, counters and work head (trace_job), launched under the launch kind `stat` unless there is no work (traced)
+TraceSub trace_sub(uint32_t *queue, uint32_t *count, const float *ray, int ray_words, float tmax, uint32_t kind);
+TraceSub extend_sub(pt_scene *sc, int cur, bool camera);
+TraceJob trace_job(pt_scene *sc, int head);
+int traced(pt_scene *sc, const char *stat, int any, const TraceJob &tj, uint32_t n_upper, bool probe = false);
+int film_pass(pt_scene *sc, const RenderConst &rc);
 int launch_trace(pt_scene *sc, int any, TraceJob job, uint32_t n_upper, bool probe = false);
 const char *device_error_text(uint32_t code);
 int sync_queue_counters(pt_scene *sc, QCounters &h);
 int ensure_workspace(pt_scene *sc, size_t capacity, size_t film_px);
 int ensure_light_grid(pt_scene *sc, int requested, int &effective);
 void fill_render_const(const PtRenderParams *rp, RenderConst &rc);
-uint32_t choose_pass_size(const pt_scene *sc, uint32_t n_pix_slots, uint32_t spp, uint32_t share, bool volpath);
+// The library's choice of a pass size (spp_per_pass = 0), for every integrator: pass_budget.h's rule on the device's free memory and the scene's workspace
+// (path records + the n_queues(sc) queues that exist + probe / chain state), with the integrator's budget. The path integrators': 0.65 of the memory, and 2^29 paths (knobs.h) =
+// 256 samples per pixel at 1080p in ONE pass (137 GB of path state + 39 GB of queues of the 288 GB): half the iterations of 2^28.
+constexpr PassBudget kPathPassBudget{0, 0.65, (size_t)1 << PT_PASS_MAX_PATHS_LOG2};
+uint32_t choose_pass_size(const pt_scene *sc, uint32_t n_pix_slots, uint32_t spp, uint32_t share, bool volpath, const PassBudget &budget = kPathPassBudget);
 void read_counters(pt_scene *sc);
 // The render frame: what pt_render_samples, pt_ao_render_samples (libmi355ao) and pt_multi_render_samples share. An integrator's geometry function is
 // frame_geometry, its own checks, its choice of a pass size, frame_pass_size -- and serves its render AND its pass-size query; its render is render_frame around its pass.

@@ -30,6 +30,17 @@ PT_DEV void counter_add(unsigned long long *dst, unsigned long long v) {  // cal
     v = wave_sum(v);
     if (lane_id() == 0 && v) atomicAdd(dst, v);
 }
+// Wave-aggregated reservation (call wave-convergent): the lanes with `pred` take `n` consecutive entries each (n wave-uniform) behind *counter, in lane order, with ONE
+// returning atomic per wave. Returns the lane's first entry; meaningless for a lane without `pred`.
+PT_DEV uint32_t wave_reserve(uint32_t *counter, bool pred, uint32_t n) {
+    const unsigned long long mask = __ballot(pred);
+    if (mask == 0ull) return 0u;
+    const uint32_t lane = lane_id(), leader = (uint32_t)__ffsll((long long)mask) - 1u;
+    uint32_t base = 0;
+    if (lane == leader) base = atomicAdd(counter, (uint32_t)__popcll(mask) * n);
+    base = __shfl(base, (int)leader);
+    return base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull)) * n;
+}
 
 // Staging of queue appends in LDS. A single global counter sustains only ~88 returning atomics per microsecond
 // (MI355X_MICROARCH.md, row "dequeue"); one atomic per wave per append made every queue-producing kernel atomic bound.
@@ -38,6 +49,7 @@ PT_DEV void counter_add(unsigned long long *dst, unsigned long long v) {  // cal
 // the whole block flushes ~1000 entries with ONE global atomic. All threads of the block call lq_sync_flush together.
 template <int CAP> struct LdsQueue { uint32_t count; uint32_t base; uint32_t buf[CAP]; };
 template <int CAP> PT_DEV void lq_init(LdsQueue<CAP> &q) { if (threadIdx.x == 0) { q.count = 0; q.base = 0; } }
+// (the reservation is wave_reserve's, written out: through the helper the compiler schedules every kernel that pushes differently, and k_shade's code objects stay as they are)
 template <int CAP> PT_DEV void lq_push(LdsQueue<CAP> &q, uint32_t value, bool pred) {
     unsigned long long mask = __ballot(pred);
     if (mask == 0ull) return;

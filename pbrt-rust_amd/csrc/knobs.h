@@ -76,5 +76,5 @@
 #define PT_MISS_BLOCKS_PER_CU 16u     // k_shade_miss: insensitive (render_loop.hip)
 #endif
 #ifndef PT_PASS_MAX_PATHS_LOG2
-#define PT_PASS_MAX_PATHS_LOG2 29     // log2 of the most paths in flight in one pass (render_loop.hip: choose_pass_size)
+#define PT_PASS_MAX_PATHS_LOG2 29     // log2 of the most paths in flight in one pass (host_common.h: kPathPassBudget, the path integrators' budget of choose_pass_size)
 #endif

@@ -27,8 +27,8 @@ template <class... P, class... A> void launch(pt_scene *sc, const Variant<P...> 
 // TEST HOOK (env PT_TEST_MAX_BLOCKS, read at every render call like PT_TEST_MAX_ITERATIONS, by the thread that launches): a cap on the persistent grids. A persistent kernel's
 // result may not depend on its grid, and under a cap of 1 the one block makes many rounds on a tiny render -- the mid-loop queue flushes (kern_shade_common.h: VertexQueues::flush) at test size.
 static thread_local uint32_t t_max_blocks = ~0u;
-static dim3 blocks_for(uint32_t n_upper, uint32_t per_cu) { return dim3(std::min(std::min<uint32_t>((n_upper + 255) / 256, (uint32_t)g_num_cus * per_cu), t_max_blocks)); }   // persistent blocks of 256 threads
-static bool general_geometry(const pt_scene *sc) { return sc->ds.n_spheres > 0 || sc->ds.n_instances > 0; }   // the SPH forms: spheres or instances besides world-space triangles
+dim3 blocks_for(uint32_t n_upper, uint32_t per_cu) { return dim3(std::min(std::min<uint32_t>((n_upper + 255) / 256, (uint32_t)g_num_cus * per_cu), t_max_blocks)); }   // persistent blocks of 256 threads
+bool general_geometry(const pt_scene *sc) { return sc->ds.n_spheres > 0 || sc->ds.n_instances > 0; }   // the SPH forms: spheres or instances besides world-space triangles
 
 // k_trace (tu_trace.hip): ANY 0..2 x MODE 0..3 x QUADK 0..2, and the probe walk (closest hit, PROBE) in the same MODE x QUADK -- row 3 of the table
 using TraceVariant = Variant<DeviceScene, TraceJob>;
@@ -339,26 +339,16 @@ __global__ void k_reset(QCounters *qc, uint32_t mask, int cur) {
     if (mask & 8u) { qc->ext[cur] = 0; qc->probe[cur] = 0; for (int c = 0; c < kNumClasses; ++c) qc->shade[cur][c] = 0; }
 }
 
-// Samples per pass when the caller leaves the choice to the library (PtRenderParams.spp_per_pass = 0): as many paths in flight as the
-// memory allows, up to 2^28 (69 GB of path state + 17-36 GB of queues / probe state out of 288 GB). Every wavefront iteration ends
-// in a tail of straggling rays (~0.8 ms on S2, whatever the launch size), so fewer, larger iterations spend less of the render in tails:
-// S2 at 1080p x 256 spp: 32 samples per pass 1267, 64: 1367, 128: 1439, 256: 1468 Msamples/s. `share` = renders that will hold a
-// workspace on this device at the same time (pt_multi_render with a device listed more than once).
-constexpr size_t kPassMaxPaths = (size_t)1 << PT_PASS_MAX_PATHS_LOG2;   // (knobs.h) round 3: 2^29 paths = 256 samples per pixel at 1080p in ONE pass (137 GB of path state + 39 GB of queues of the 288 GB): half the iterations of 2^28
-constexpr double kPassMemFraction = 0.65;   // of the device's free memory
-uint32_t choose_pass_size(const pt_scene *sc, uint32_t n_pix_slots, uint32_t spp, uint32_t share, bool volpath) {
-    // per path: the five state records, the queues, the probe state of scenes with subsurface materials and -- volpath through material-less shells -- the
+// Samples per pass when the caller leaves the choice to the library (PtRenderParams.spp_per_pass = 0): the device's free memory and what the scene's workspace holds and
+// costs per path, handed to the one rule (pass_budget.h: pass_size_for) with the integrator's budget (host_common.h: kPathPassBudget; libmi355ao and libmi355aov pass their own)
+uint32_t choose_pass_size(const pt_scene *sc, uint32_t n_pix_slots, uint32_t spp, uint32_t share, bool volpath, const PassBudget &budget) {
+    // per path: the five state records, the queues that exist, the probe state of scenes with subsurface materials and -- volpath through material-less shells -- the
     // 128-byte chain record (PathSoA::ext, allocated after the main slab: left out of this sum, a shell scene asked for ~1.4x its budget)
-    const size_t per_path = (size_t)kPathBytes + 4u * n_queues(sc) + (sc->has_bssrdf ? (size_t)kBssBytes : 0u)
-                            + ((volpath && sc->has_null_material) ? 4u * (size_t)PathSoA::kExtWords : 0u);
+    const size_t workspace = (size_t)kPathBytes + 4u * n_queues(sc) + (sc->has_bssrdf ? (size_t)kBssBytes : 0u)
+                             + ((volpath && sc->has_null_material) ? 4u * (size_t)PathSoA::kExtWords : 0u);
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
-    // (the present workspace is freed before a larger one is allocated)
-    const size_t afford = std::max(sc->capacity, (size_t)((double)(free_b / std::max(1u, share) + sc->capacity * per_path) * kPassMemFraction) / per_path);
-    const size_t paths = std::min(afford, kPassMaxPaths / std::max(1u, share));
-    uint32_t S = (uint32_t)std::min<size_t>(spp, std::max<size_t>(1, paths / std::max(1u, n_pix_slots)));
-    const uint32_t n_pass = (spp + S - 1) / S;
-    return (spp + n_pass - 1) / n_pass;   // passes of equal size
+    return pass_size_for(free_b, sc->capacity * workspace, workspace + budget.extra_bytes_per_path, budget, n_pix_slots, spp, share);
 }
 
 // First-touch voxels of PT_LS_SPATIAL_LAZY. touch: the vertices of one queue name their voxels; fill: the voxels named since the last fill are computed and published.
@@ -438,11 +428,18 @@ template <class Job> Job shading_job(const Iter &it, const uint32_t *queue, cons
 }
 
 // The rays of one kind: their queue, where a ray lies (`ray`, ray_words apart) and the counter slot (TraceSub::kind). The caller adds where the hit goes.
-static TraceSub trace_sub(uint32_t *queue, uint32_t *count, const float *ray, int ray_words, float tmax, uint32_t kind) {
+TraceSub trace_sub(uint32_t *queue, uint32_t *count, const float *ray, int ray_words, float tmax, uint32_t kind) {
     TraceSub s{}; s.queue = queue; s.count = count; s.ray = (const float4 *)ray; s.ray_stride = ray_words / 4; s.scalar_tmax = tmax; s.kind = kind; return s;
 }
-static TraceJob trace_job(pt_scene *sc, int head) { TraceJob tj{}; tj.spill = sc->spill; tj.error = &sc->qc->error; tj.counters = sc->dc; tj.head = &sc->qc->head[head]; return tj; }
-static int traced(pt_scene *sc, const char *stat, int any, const TraceJob &tj, uint32_t n_upper, bool probe = false) {
+// The continuation rays of queue set `cur` -> hit record (Scene::intersect); `camera`: a pass's first rays, counted as camera rays (kind 3)
+TraceSub extend_sub(pt_scene *sc, int cur, bool camera) {
+    PathSoA &ps = sc->ps;
+    TraceSub ext = trace_sub(sc->q.ext[cur], &sc->qc->ext[cur], ps.ray, PathSoA::kRayWords, INFINITY, camera ? 3 : 0);
+    ext.out_hit = (float4 *)ps.hit; ext.out_hit_stride = PathSoA::kHitWords / 4; ext.out_hit2 = (float4 *)ps.hit + 1;   // {inst, t, packet, packet flags}
+    return ext;
+}
+TraceJob trace_job(pt_scene *sc, int head) { TraceJob tj{}; tj.spill = sc->spill; tj.error = &sc->qc->error; tj.counters = sc->dc; tj.head = &sc->qc->head[head]; return tj; }
+int traced(pt_scene *sc, const char *stat, int any, const TraceJob &tj, uint32_t n_upper, bool probe) {
     if (n_upper == 0) return PT_OK;   // (a launch kind with no work is not a launch: the per-launch averages of bench.py / rocprofv3 count real dispatches)
     sc->begin(stat, n_upper); const int st = launch_trace(sc, any, tj, n_upper, probe); sc->end();
     return st;
@@ -451,9 +448,7 @@ static int traced(pt_scene *sc, const char *stat, int any, const TraceJob &tj, u
 // trace: this iteration's continuation rays and the shadow / MIS rays of the vertices shaded in the previous one
 static int trace_rays(const Iter &it) {
     pt_scene *sc = it.sc; QCounters *qc = sc->qc; PathSoA &ps = sc->ps; const RenderConst &rc = it.rc;
-    // continuation rays -> hit record (routed to the material classes next)
-    TraceSub ext = trace_sub(sc->q.ext[it.cur], &qc->ext[it.cur], ps.ray, PathSoA::kRayWords, INFINITY, it.index == 0 ? 3 : 0);
-    ext.out_hit = (float4 *)ps.hit; ext.out_hit_stride = PathSoA::kHitWords / 4; ext.out_hit2 = (float4 *)ps.hit + 1;   // {inst, t, packet, packet flags}
+    const TraceSub ext = extend_sub(sc, it.cur, it.index == 0);   // (routed to the material classes next)
     // MIS rays of the previous vertex (closest hit, integrator.rs:215)
     TraceSub mis = trace_sub(sc->q.mis, &qc->mis, ps.mis, PathSoA::kMisWords, INFINITY, 1);
     mis.out_hit = (float4 *)&ps.mis_prim(0); mis.out_hit_stride = PathSoA::kMisWords / 4;
@@ -560,6 +555,15 @@ static void shade_class(const Iter &it, int c, uint32_t n) {
     sc->end();
 }
 
+// film: the pass's paths sanitised and splatted by k_film (kern_film.h) -- the passes whose paths the film kernel does not also end (volpath, PT_FILM_FINAL=0, libmi355ao)
+int film_pass(pt_scene *sc, const RenderConst &rc) {
+    sc->begin("film", rc.n_pix_slots * rc.s_count);
+    launch(sc, "k_film", k_film, film_grid(rc), dim3(256), rc, sc->ps, sc->d_filter, sc->film_rgbw, sc->dc);
+    sc->end();
+    HIP_TRY(hipGetLastError());
+    return PT_OK;
+}
+
 static int run_pass(pt_scene *sc, RenderConst &rc, const LightGrid &grid, bool rp_profile_exact, int max_iterations) {
     const uint32_t total = rc.n_pix_slots * rc.s_count;
     QCounters *qc = sc->qc;   // (render_frame has zeroed the queue counters and put the pass's camera rays into ext[0])
@@ -600,10 +604,9 @@ static int run_pass(pt_scene *sc, RenderConst &rc, const LightGrid &grid, bool r
         HIP_TRY(hipGetLastError());
         reset(8u);
     }
+    if (!it.fin) return film_pass(sc, rc);
     sc->begin("film", total);
-    const dim3 fgrid((unsigned)(((size_t)rc.n_pix_slots + 255) / 256));   // one thread per pixel slot (kern_film.h)
-    if (it.fin) launch(sc, film_final_variant(general_geometry(sc)), fgrid, dim3(256), sc->ds, rc, sc->ps, sc->d_filter, sc->film_rgbw, sc->dc);
-    else launch(sc, "k_film", k_film, fgrid, dim3(256), rc, sc->ps, sc->d_filter, sc->film_rgbw, sc->dc);
+    launch(sc, film_final_variant(general_geometry(sc)), film_grid(rc), dim3(256), sc->ds, rc, sc->ps, sc->d_filter, sc->film_rgbw, sc->dc);
     sc->end();
     HIP_TRY(hipGetLastError());
     return PT_OK;

@@ -35,26 +35,18 @@ class Library:
         if not os.path.exists(path):
             raise PtError(f"{path} not found: build it with __graft_entry__.build() (no CPU fallback exists)")
         self.lib = A.bind(C.CDLL(path), strict=not os.environ.get("PT_LIB_PATH"))   # (PT_LIB_PATH: a kernel-variant library of an A/B run, possibly built from an older tree)
-        self._ao = None
-        self._aov = None
+        self._side = {}
 
-    @property
-    def aov(self):
-        """libmi355aov.so (include/mi355aov.h), loaded on first use."""
-        if self._aov is None:
-            if not os.path.exists(AOV_LIB_PATH):
-                raise PtError(f"{AOV_LIB_PATH} not found: build it with __graft_entry__.build() (no CPU fallback exists)")
-            self._aov = A.bind(C.CDLL(AOV_LIB_PATH), table=AOV.ENTRY_POINTS)
-        return self._aov
+    def _side_library(self, path, table):
+        """An integrator library linked against libmi355pt.so, loaded and bound on first use."""
+        if path not in self._side:
+            if not os.path.exists(path):
+                raise PtError(f"{path} not found: build it with __graft_entry__.build() (no CPU fallback exists)")
+            self._side[path] = A.bind(C.CDLL(path), table=table)
+        return self._side[path]
 
-    @property
-    def ao(self):
-        """libmi355ao.so (include/mi355ao.h), loaded on first use."""
-        if self._ao is None:
-            if not os.path.exists(AO_LIB_PATH):
-                raise PtError(f"{AO_LIB_PATH} not found: build it with __graft_entry__.build() (no CPU fallback exists)")
-            self._ao = A.bind(C.CDLL(AO_LIB_PATH), table=AO.ENTRY_POINTS)
-        return self._ao
+    aov = property(lambda self: self._side_library(AOV_LIB_PATH, AOV.ENTRY_POINTS), doc="libmi355aov.so (include/mi355aov.h), loaded on first use.")
+    ao = property(lambda self: self._side_library(AO_LIB_PATH, AO.ENTRY_POINTS), doc="libmi355ao.so (include/mi355ao.h), loaded on first use.")
 
     def check(self, st, what=""):
         if st != A.PT_OK:

@@ -197,3 +197,42 @@ def test_the_render_frame_is_written_once():
         assert count(host, phrase) == 1, phrase
     for wrapper in ("render_loop.hip", "ao_render.hip", "multi_device.hip"):
         assert count([p for p in host if p.endswith(wrapper)], "check_spp(rp)") >= 1, wrapper
+
+
+def test_pass_budget_on_the_cpu(pkg, tmp_path):
+    """The pass size the library chooses (csrc/pass_budget.h: pass_size_for, the arithmetic of choose_pass_size for every integrator) checked without a device:
+    tests/pass_budget/check_pass_budget.cpp, a program of its own over the header alone. Its header comment lists what it holds. It passes when it exits 0."""
+    import subprocess
+    here = os.path.dirname(pkg.runtime.LIB_PATH)
+    root = os.path.dirname(os.path.abspath(__file__))
+    exe = str(tmp_path / "check_pass_budget")
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    subprocess.check_call([hipcc, "-x", "hip", "--offload-host-only", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-I", here, "-o", exe,
+                           os.path.join(root, "pass_budget", "check_pass_budget.cpp")])
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-2000:]
+
+
+def test_the_pass_budget_and_bump_are_not_restated():
+    """The integrator libraries beside libmi355pt choose their pass size through choose_pass_size (render_loop.hip): neither the stale bound on the workspace's queues nor a
+    free-memory query of their own may reappear under ao/ or aov/, and the rule's arithmetic stands in pass_budget.h alone.
+    bump()'s arithmetic stands in k_shade and, restated, in k_aov -- in no third place. (One inlined device helper for both moved the registers of the textured k_shade
+    forms, so k_shade keeps its body and k_aov its copy, under a NOTE that says so: profiles/r6/NOTES.md section 15. With a helper this count would be one header.)"""
+    import glob
+    root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "pbrt-rust_amd")
+    text = lambda p: open(p, errors="replace").read()
+    side = sorted(glob.glob(os.path.join(root, "ao", "*")) + glob.glob(os.path.join(root, "aov", "*")))
+    assert any(p.endswith("ao_render.hip") for p in side) and any(p.endswith("aov_render.hip") for p in side)
+    for p in side:
+        if not os.path.isfile(p) or p.endswith((".so", ".o")):
+            continue
+        squeezed = re.sub(r"\s+", "", text(p))
+        assert "2*kNumClasses+2+2" not in squeezed, p
+        assert "hipMemGetInfo" not in squeezed, p
+    for name in ("ao_render.hip", "aov_render.hip"):
+        assert text([p for p in side if p.endswith(name)][0]).count("choose_pass_size(sc, ") == 1, name
+    native = [p for ext in ("h", "hip", "cpp") for p in glob.glob(os.path.join(root, "**", "*." + ext), recursive=True)]
+    assert sorted(os.path.basename(p) for p in native if "// passes of equal size" in text(p)) == ["pass_budget.h"]
+    bump = {os.path.basename(p): text(p).count("udisplace - displace") for p in native if "udisplace - displace" in text(p)}
+    assert bump == {"kern_shade.h": 1, "aov_kernels.h": 1}, bump
+    assert "NOTE: the body is k_shade's" in text(os.path.join(root, "aov", "aov_kernels.h"))
