@@ -7,17 +7,19 @@ import numpy as np
 from . import _abi as A
 from . import _abi_ao as AO
 from . import _abi_aov as AOV
+from . import _abi_dn as DN
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PT_LIB_PATH") or os.path.join(_HERE, "csrc", "libmi355pt.so")   # PT_LIB_PATH: kernel-variant experiments
 AO_LIB_PATH = os.path.join(_HERE, "ao", "libmi355ao.so")   # the ambient-occlusion integrator (include/mi355ao.h), linked against libmi355pt.so
 AOV_LIB_PATH = os.path.join(_HERE, "aov", "libmi355aov.so")   # the feature buffers for denoising (include/mi355aov.h), linked against libmi355pt.so
+DN_LIB_PATH = os.path.join(_HERE, "denoise", "libmi355dn.so")   # the a-trous denoiser over half films and feature buffers (include/mi355dn.h), linked against libmi355pt.so
 TABLES_PATH = os.path.join(_HERE, "data", "sobol_tables.bin")
 
 
 def build_library(verbose=False):
-    """Compile every HIP source for gfx950 (hipcc cross-compiles without a GPU): libmi355pt.so, then libmi355ao.so and libmi355aov.so, which link against it."""
-    for sub, name in (("csrc", "libmi355pt.so"), ("ao", "libmi355ao.so"), ("aov", "libmi355aov.so")):
+    """Compile every HIP source for gfx950 (hipcc cross-compiles without a GPU): libmi355pt.so, then libmi355ao.so, libmi355aov.so and libmi355dn.so, which link against it."""
+    for sub, name in (("csrc", "libmi355pt.so"), ("ao", "libmi355ao.so"), ("aov", "libmi355aov.so"), ("denoise", "libmi355dn.so")):
         r = subprocess.run(["make", "-C", os.path.join(_HERE, sub), "-j8"], capture_output=True, text=True)
         if verbose or r.returncode != 0:
             print(r.stdout[-4000:]); print(r.stderr[-4000:])
@@ -46,6 +48,7 @@ class Library:
         return self._side[path]
 
     aov = property(lambda self: self._side_library(AOV_LIB_PATH, AOV.ENTRY_POINTS), doc="libmi355aov.so (include/mi355aov.h), loaded on first use.")
+    dn = property(lambda self: self._side_library(DN_LIB_PATH, DN.ENTRY_POINTS), doc="libmi355dn.so (include/mi355dn.h), loaded on first use.")
     ao = property(lambda self: self._side_library(AO_LIB_PATH, AO.ENTRY_POINTS), doc="libmi355ao.so (include/mi355ao.h), loaded on first use.")
 
     def check(self, st, what=""):
@@ -73,6 +76,13 @@ def load_library():
 
 def _fptr(a):
     return a.ctypes.data_as(A.fp)
+
+
+def default_denoise_params(lib=None):
+    """pt_denoise_default_params: a PtDenoiseParams to adjust and hand to Scene.denoise / Scene.render_denoised."""
+    p = DN.PtDenoiseParams()
+    (lib or load_library()).dn.pt_denoise_default_params(C.byref(p))
+    return p
 
 
 def resolve_aov(sums, lib=None):
@@ -321,6 +331,52 @@ class Scene(Handle):
         s = C.c_uint32()
         self._call("aov_pass_size", self.h, C.byref(rp), C.byref(s), lib=self.L.aov)
         return int(s.value)
+
+    def denoise(self, film_a, film_b, sums, params=None, device_ptrs=None):
+        """pt_denoise of two half films (H, W, 4) -- XYZW sums of disjoint sample ranges, A + B is the film -- and the feature sums of the samples of A + B (the
+        dict render_aov returns, all three planes): the denoised image (H, W, 3). `params`: a PtDenoiseParams, else the library's defaults.
+        `device_ptrs` = (width, height, rgb_out): film_a, film_b, the values of `sums` and rgb_out are device pointers as integers; returns None."""
+        lib = self.L.dn
+        if params is None:
+            params = default_denoise_params(self.L)
+        if device_ptrs is not None:
+            w, h, out = device_ptrs
+            bufs = AOV.PtAOVBuffers(*[C.cast(C.c_void_p(sums[k]), A.fp) for k in AOV.PLANES])
+            self._call("denoise", self.h, C.byref(params), C.c_void_p(film_a), C.c_void_p(film_b), C.byref(bufs), w, h, C.c_void_p(out), 1, lib=lib); return None
+        film_a, film_b = (np.ascontiguousarray(f, dtype=np.float32) for f in (film_a, film_b))
+        sums = {k: np.ascontiguousarray(sums[k], dtype=np.float32) for k in AOV.PLANES}
+        h, w = film_a.shape[:2]
+        for name, arr, ch in [("film_a", film_a, 4), ("film_b", film_b, 4)] + [(k, sums[k], AOV.CHANNELS[k]) for k in AOV.PLANES]:
+            if arr.shape != (h, w, ch):
+                raise ValueError(f"denoise: {name} has shape {arr.shape}, expected {(h, w, ch)}")
+        out = np.zeros((h, w, 3), dtype=np.float32)
+        bufs = AOV.PtAOVBuffers(*[_fptr(sums[k]) for k in AOV.PLANES])
+        self._call("denoise", self.h, C.byref(params), film_a.ctypes.data_as(C.c_void_p), film_b.ctypes.data_as(C.c_void_p), C.byref(bufs), w, h, out.ctypes.data_as(C.c_void_p), 0, lib=lib)
+        return out
+
+    def render_denoised(self, rp, params=None, inputs=False):
+        """The job `rp` rendered and denoised without leaving the device: sample numbers [0, spp / 2) into half film A and [spp / 2, spp) into B (pt_render_samples),
+        the feature sums of [0, spp) (pt_aov_render), pt_denoise of the three. Returns (the denoised image (H, W, 3), A + B as a numpy film (H, W, 4)); `inputs`: and (A, B, the feature sums) as the filter read them, numpy copies.
+        counters() afterwards describes the feature render, kernel_stats() that render plus the denoiser's launches."""
+        import torch
+        if rp.spp < 2:
+            raise ValueError("render_denoised needs spp >= 2: two half films with samples in each")
+        cb = rp.cropped_pixel_bounds
+        w, h = cb[2] - cb[0], cb[3] - cb[1]
+        halves = [torch.zeros((h, w, 4), dtype=torch.float32, device="cuda") for _ in range(2)]
+        planes = {k: torch.zeros((h, w, AOV.CHANNELS[k]), dtype=torch.float32, device="cuda") for k in AOV.PLANES}
+        rgb = torch.zeros((h, w, 3), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()   # (the library renders on its own stream: the zeroed buffers must be there before it adds to them)
+        half = rp.spp // 2
+        self.render(rp, device_ptr=halves[0].data_ptr(), samples=(0, half))
+        self.render(rp, device_ptr=halves[1].data_ptr(), samples=(half, rp.spp - half))
+        ptrs = {k: v.data_ptr() for k, v in planes.items()}
+        self.render_aov(rp, device_ptrs=ptrs)
+        self.denoise(halves[0].data_ptr(), halves[1].data_ptr(), ptrs, params, device_ptrs=(w, h, rgb.data_ptr()))
+        out = (rgb.cpu().numpy(), (halves[0] + halves[1]).cpu().numpy())
+        if inputs:
+            out += ((halves[0].cpu().numpy(), halves[1].cpu().numpy(), {k: v.cpu().numpy() for k, v in planes.items()}),)
+        return out
 
     def ao_params(self):
         """The scene's PtAOParams (SceneBuilder.integ / the front end's "ambientocclusion" parameters)."""
