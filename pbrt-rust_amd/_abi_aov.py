@@ -11,6 +11,12 @@ class PtAOVBuffers(C.Structure):
     _fields_ = [("albedo_w", fp), ("normal_w", fp), ("depth_w", fp)]
 
 
+def buffers(planes, device=False):
+    """The PtAOVBuffers of {plane: a contiguous float32 array -- with `device`: a device pointer as an integer}; a plane that is not there is NULL."""
+    pointer = (lambda v: C.cast(C.c_void_p(v), fp)) if device else (lambda v: v.ctypes.data_as(fp))
+    return PtAOVBuffers(*[pointer(planes[k]) if k in planes else None for k in PLANES])
+
+
 # Every symbol include/mi355aov.h declares, with its signature (restype, argtypes).
 ENTRY_POINTS = {
     "pt_aov_render": (C.c_int, [VP, C.POINTER(PtRenderParams), C.POINTER(PtAOVBuffers), C.c_int]),

@@ -4,20 +4,12 @@ import os
 import subprocess
 from . import _abi as A
 from . import _abi_ao as AO
+from ._abi_front import ENTRY_POINTS, PTF_CHECKPOINT_MAGIC, PtfCheckpointHeader   # (re-exported: the mirror of include/mi355front.h)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SAN = bool(os.environ.get("PT_SAN"))   # ASan/UBSan build of the front end (tools/san_cpu_tests.sh)
 LIB_PATH = os.path.join(_HERE, "frontend", "libmi355front_san.so" if SAN else "libmi355front.so")
 CLI_PATH = os.path.join(_HERE, "frontend", "mi355pbrt")
-
-
-PTF_CHECKPOINT_MAGIC = 0x4b433550
-
-
-class PtfCheckpointHeader(C.Structure):
-    """include/mi355front.h: the header of a range render's checkpoint file (then width * height * 4 floats of XYZW sums)."""
-    _fields_ = [("magic", A.u32), ("version", A.u32), ("width", A.u32), ("height", A.u32), ("spp", A.u32), ("first_sample", A.u32), ("samples_done", A.u32),
-                ("reserved", A.u32), ("params_hash", A.u64)]
 
 
 def build(verbose=False):
@@ -37,23 +29,7 @@ def lib():
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             build()
-        L = C.CDLL(LIB_PATH)
-        L.ptf_parse_file.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
-        L.ptf_parse_string.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]
-        L.ptf_last_error.restype = C.c_char_p
-        L.ptf_scene_desc.restype = C.POINTER(A.PtSceneDesc); L.ptf_scene_desc.argtypes = [C.c_void_p]
-        L.ptf_render_params.restype = C.POINTER(A.PtRenderParams); L.ptf_render_params.argtypes = [C.c_void_p]
-        L.ptf_output_filename.restype = C.c_char_p; L.ptf_output_filename.argtypes = [C.c_void_p]
-        L.ptf_ao_params.argtypes = [C.c_void_p, C.POINTER(AO.PtAOParams)]
-        L.ptf_scene_destroy.argtypes = [C.c_void_p]
-        L.ptf_write_pfm.argtypes = [C.c_char_p, C.c_int, C.c_int, A.fp]
-        L.ptf_write_image.argtypes = [C.c_char_p, C.c_int, C.c_int, A.fp]
-        L.ptf_write_exr_channels.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(A.fp), A.u32p]
-        L.ptf_read_image.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), A.fp, C.c_size_t]
-        L.ptf_params_hash.restype = C.c_uint64; L.ptf_params_hash.argtypes = [C.POINTER(A.PtRenderParams), C.POINTER(AO.PtAOParams)]
-        L.ptf_checkpoint_write.argtypes = [C.c_char_p, C.POINTER(PtfCheckpointHeader), A.fp]
-        L.ptf_checkpoint_read.argtypes = [C.c_char_p, C.POINTER(PtfCheckpointHeader), A.u32p, A.fp]
-        _lib = L
+        _lib = A.bind(C.CDLL(LIB_PATH), table=ENTRY_POINTS)
     return _lib
 
 

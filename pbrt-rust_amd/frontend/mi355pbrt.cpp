@@ -1,6 +1,4 @@
-// mi355pbrt -- command-line renderer: the drop-in for `pbrt-rust scene.pbrt` on this back end (main.rs + api.rs:1715-1748).
-//   mi355pbrt scene.pbrt [--outfile out.pfm] [--device N] [--spp N] [--quiet] [--samples A:B] [--checkpoint FILE] [--preview-every N]
-//                        [--adaptive T [--adaptive-step N] [--adaptive-min N]] [--aov FILE.exr] [--denoise FILE [--denoise-iterations N]]
+// mi355pbrt -- command-line renderer: the drop-in for `pbrt-rust scene.pbrt` on this back end (main.rs + api.rs:1715-1748). The command line: kUsage below.
 // Parses with libmi355front.so, renders with libmi355pt.so (HIP; Integrator "ambientocclusion": libmi355ao.so), writes the film in the format the Film's "filename"
 // extension names (exr -- the reference's default "pbrt.exr" -- png, tga, pfm: core/imageio.rs:42-60).
 // The film lives on the device and is rendered in groups of samples (pt_render_samples); one group -- the whole job -- unless asked otherwise:
@@ -20,209 +18,192 @@
 //                        difference is the filter's noise estimate, so there must be two of them at least; the outfile's film is their sum. --denoise-iterations N: the
 //                        filter's levels, 0..5 (default 5). Not with --adaptive (tiles hold different sample counts), --checkpoint (it holds one film) or
 //                        --preview-every (the film so far is two halves).
-#include "../../include/mi355front.h"
+// What needs no device -- the flags, what they refuse, the sample numbers of a run and the render calls of its loop -- is cli_plan.h; this file is the device work.
+#include "cli_plan.h"
 #include "../../include/mi355aov.h"
 #include "../../include/mi355dn.h"
 #include <hip/hip_runtime_api.h>
 #include <chrono>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
 
 static const char *kUsage = "usage: mi355pbrt scene.pbrt [--outfile out.pfm] [--device N] [--spp N] [--quiet] [--samples A:B] [--checkpoint FILE] [--preview-every N]\n"
                             "                 [--adaptive T [--adaptive-step N] [--adaptive-min N]] [--aov FILE.exr] [--denoise FILE [--denoise-iterations N]]\n";
-static int usage(const std::string &why = "") { if (!why.empty()) std::fprintf(stderr, "mi355pbrt: %s\n", why.c_str()); std::fputs(kUsage, stderr); return 2; }
 
-// "A:B" with decimal A < B, both fitting 32 bits
-static bool parse_range(const std::string &a, long long &lo, long long &hi) {
-    const size_t c = a.find(':');
-    if (c == std::string::npos || c == 0 || c + 1 >= a.size() || a.size() > 21) return false;
-    for (size_t i = 0; i < a.size(); ++i) if (i != c && (a[i] < '0' || a[i] > '9')) return false;
-    lo = std::atoll(a.substr(0, c).c_str()); hi = std::atoll(a.substr(c + 1).c_str());
-    return lo < hi && hi <= 0xffffffffll;
+// The one failure path: the text on stderr, exit status 1. pt_ok, ptf_ok and hip_ok are false after they reported a failed call of their kind.
+static int die(const char *text) { std::fprintf(stderr, "mi355pbrt: %s\n", text); return 1; }
+static int usage(const std::string &why) { if (!why.empty()) die(why.c_str()); std::fputs(kUsage, stderr); return 2; }
+static bool pt_ok(int st) { return st == PT_OK || !die(pt_last_error()); }
+static bool ptf_ok(int st) { return st == PT_OK || !die(ptf_last_error()); }
+static bool hip_ok(hipError_t e, const char *text) { return e == hipSuccess || !die(text); }
+static bool hip_failed(const char *what) { return !die((std::string(what) + ": " + hipGetErrorString(hipGetLastError())).c_str()); }   // (false)
+static bool download(std::vector<float> &to, const float *d_from, const char *text) { return hip_ok(hipMemcpy(to.data(), d_from, to.size() * 4, hipMemcpyDeviceToHost), text); }
+
+// Owners: whatever path leaves main, the device buffers go first, then the scene, then the parsed file.
+struct Parsed { ptf_scene *p = nullptr; ~Parsed() { if (p) ptf_scene_destroy(p); } };
+struct Scene { pt_scene *p = nullptr; ~Scene() { if (p) pt_scene_destroy(p); } };
+struct DeviceBuffer {
+    float *p = nullptr;
+    ~DeviceBuffer() { if (p) (void)hipFree(p); }
+    // `zero`: cleared, and the device waited for (the library renders on its own stream: the zeros must be there before it adds to them)
+    bool alloc(const char *what, size_t bytes, bool zero) {
+        if (hipMalloc((void **)&p, bytes) != hipSuccess) p = nullptr;
+        return (p && (!zero || (hipMemset(p, 0, bytes) == hipSuccess && hipDeviceSynchronize() == hipSuccess))) || hip_failed(what);
+    }
+};
+
+struct Job {   // what the steps share
+    const Options &o; const Plan &p;
+    const PtAOParams *ao;                    // of Integrator "ambientocclusion" (libmi355ao.so), else null
+    size_t npix;
+    std::vector<float> film, rgb;            // on the host: the XYZW sums, a resolved image
+    Scene sc;
+    DeviceBuffer d_film, d_rgb, d_half_b;    // d_half_b: --adaptive and --denoise render two halves, and d_film is half A until sum_halves
+    unsigned long long camera_rays = 0;
+};
+
+// A += B: the film is the sum of the halves (host arithmetic on the read-back halves, element by element)
+static bool sum_halves(std::vector<float> &film, float *d_a, const float *d_b) {
+    std::vector<float> half_b(film.size());
+    if (!download(film, d_a, "reading the film back failed") || !download(half_b, d_b, "reading the film back failed")) return false;
+    for (size_t i = 0; i < film.size(); ++i) film[i] += half_b[i];
+    return hip_ok(hipMemcpy(d_a, film.data(), film.size() * 4, hipMemcpyHostToDevice), "writing the film back failed");
+}
+
+// the three planes in one array of feature sums: albedo and normal of 4 floats per pixel, depth of 2
+static PtAOVBuffers feature_planes(float *sums, size_t npix) { return {sums, sums + npix * 4, sums + npix * 8}; }
+
+// d_rgb -> an image file
+static bool write_rgb(Job &j, const std::string &path, const char *text) {
+    return download(j.rgb, j.d_rgb.p, text) && ptf_ok(ptf_write_image(path.c_str(), j.p.width, j.p.height, j.rgb.data()));
+}
+
+// the film so far -> outfile, resolved on the device
+static bool write_out(Job &j) {
+    return pt_ok(pt_film_resolve_device(j.sc.p, j.d_film.p, (uint32_t)j.npix, j.p.rp.scale, j.d_rgb.p, nullptr)) && write_rgb(j, j.o.outfile, "reading the image back failed");
+}
+
+// a checkpoint of this job: continue after its samples (host work: a file of another job is refused before the device is touched)
+static bool resume(Job &j, PtfCheckpointHeader &ck) {
+    const Options &o = j.o;
+    if (!ptf_ok(ptf_checkpoint_read(o.checkpoint.c_str(), &ck, &ck.samples_done, j.film.data()))) return false;
+    if (ck.samples_done > j.p.last - j.p.first) return !die(("checkpoint \"" + o.checkpoint + "\" holds more samples than --samples asks for").c_str());
+    if (ck.samples_done && !o.quiet) std::printf("resuming %s at sample %u of [%u, %u)\n", o.checkpoint.c_str(), j.p.first + ck.samples_done, j.p.first, j.p.last);
+    return true;
+}
+
+// runtime.Scene.render_adaptive's loop: d_film is half A, d_half_b half B, the active set only shrinks
+static bool render_adaptive(Job &j) {
+    const Options &o = j.o; const PtRenderParams &rp = j.p.rp; pt_scene *sc = j.sc.p;
+    uint32_t ntx = 0, nty = 0;
+    if (!pt_ok(pt_tile_grid(&rp, &ntx, &nty))) return false;
+    DeviceBuffer d_err;   // an error per 16x16 film tile
+    if (!d_err.alloc("device film", (size_t)((j.p.width + 15) / 16) * ((j.p.height + 15) / 16) * 4, false)) return false;
+    std::vector<uint32_t> active((size_t)ntx * nty), kept(active.size());
+    for (size_t i = 0; i < active.size(); ++i) active[i] = (uint32_t)i;
+    unsigned long long tile_samples = 0; unsigned rounds = 0;
+    for (uint32_t done = 0; done < rp.spp && !active.empty(); ++rounds) {
+        uint32_t n_b = 0;
+        for (float *half : {j.d_film.p, j.d_half_b.p}) {
+            const uint32_t n = (uint32_t)std::min<long long>(o.astep, rp.spp - done);
+            if (half == j.d_half_b.p) n_b = n;
+            if (n == 0) continue;
+            if (!pt_ok(pt_render_tiles(sc, &rp, done, n, active.data(), (uint32_t)active.size(), half, 1))) return false;
+            PtCounters c; pt_get_counters(sc, &c); j.camera_rays += c.camera_rays;
+            done += n; tile_samples += (unsigned long long)n * active.size();
+        }
+        if (n_b > 0 && done >= (uint32_t)o.amin) {
+            uint32_t n_kept = 0;
+            if (!pt_ok(pt_film_halves_error(sc, j.d_film.p, j.d_half_b.p, (uint32_t)j.p.width, (uint32_t)j.p.height, d_err.p, nullptr, nullptr)) ||
+                !pt_ok(pt_tiles_select(sc, &rp, d_err.p, o.threshold, active.data(), (uint32_t)active.size(), kept.data(), &n_kept))) return false;
+            active.assign(kept.begin(), kept.begin() + n_kept);
+        }
+    }
+    if (!sum_halves(j.film, j.d_film.p, j.d_half_b.p)) return false;
+    if (!o.quiet) std::printf("adaptive: %llu of %llu tile-samples, %u rounds\n", tile_samples, (unsigned long long)ntx * nty * rp.spp, rounds);
+    return true;
+}
+
+// The render calls groups() lists, of --preview-every N samples each, else (--checkpoint) of one wavefront pass, else the whole run in one; after each its counters,
+// the checkpoint and, unless it was the last, the preview.
+static bool render_groups(Job &j, PtfCheckpointHeader &ck) {
+    const Options &o = j.o; const Plan &p = j.p; pt_scene *sc = j.sc.p;
+    uint32_t group = p.last - p.first;   // samples per pt_render_samples call
+    if (o.preview > 0) group = (uint32_t)std::min<long long>(o.preview, group);
+    else if (!o.checkpoint.empty() && !pt_ok(j.ao ? pt_ao_pass_size(sc, &p.rp, j.ao, &group) : pt_pass_size(sc, &p.rp, &group))) return false;
+    for (const Group &g : groups(p, group, ck.samples_done)) {
+        float *const into = g.half ? j.d_half_b.p : j.d_film.p;
+        if (!pt_ok(j.ao ? pt_ao_render_samples(sc, &p.rp, j.ao, g.first, g.n, into, 1) : pt_render_samples(sc, &p.rp, g.first, g.n, into, 1))) return false;
+        PtCounters c; pt_get_counters(sc, &c); j.camera_rays += c.camera_rays;
+        ck.samples_done = g.first + g.n - p.first;
+        if (!o.checkpoint.empty() && !(download(j.film, j.d_film.p, "reading the film back failed") && ptf_ok(ptf_checkpoint_write(o.checkpoint.c_str(), &ck, j.film.data())))) return false;
+        if (o.preview > 0 && g.first + g.n < p.last && !write_out(j)) return false;
+    }
+    return true;
+}
+
+// the feature sums of sample numbers [first, last), whatever groups (or earlier runs, --checkpoint) rendered the image's: for --denoise and --aov
+static bool render_features(Job &j, DeviceBuffer &d_sums) {
+    if (!d_sums.alloc("feature buffers", j.npix * 40, true)) return false;
+    const PtAOVBuffers d_planes = feature_planes(d_sums.p, j.npix);
+    return pt_ok(pt_aov_render_samples(j.sc.p, &j.p.rp, j.p.first, j.p.last - j.p.first, &d_planes, 1));
+}
+
+// the filter reads the halves; then A += B: the outfile's film
+static bool write_denoised(Job &j, float *d_sums) {
+    const PtAOVBuffers d_planes = feature_planes(d_sums, j.npix);
+    PtDenoiseParams dp; pt_denoise_default_params(&dp);
+    if (j.o.dn_iterations >= 0) dp.iterations = (uint32_t)j.o.dn_iterations;
+    dp.scale = j.p.rp.scale;
+    return pt_ok(pt_denoise(j.sc.p, &dp, j.d_film.p, j.d_half_b.p, &d_planes, (uint32_t)j.p.width, (uint32_t)j.p.height, j.d_rgb.p, 1)) &&
+           write_rgb(j, j.o.denoise, "reading the denoised image back failed") && sum_halves(j.film, j.d_film.p, j.d_half_b.p);
+}
+
+static bool write_aov(Job &j, const float *d_sums) {
+    const size_t npix = j.npix;
+    std::vector<float> sums(npix * 10, 0.0f), res(npix * 7);
+    if (!download(sums, d_sums, "reading the feature buffers back failed")) return false;
+    const PtAOVBuffers planes = feature_planes(sums.data(), npix);
+    float *albedo = res.data(), *normal = res.data() + npix * 3, *depth = res.data() + npix * 6;
+    if (!pt_ok(pt_aov_resolve(&planes, (uint32_t)npix, albedo, normal, depth))) return false;
+    const char *names[7] = {"N.X", "N.Y", "N.Z", "Z", "albedo.B", "albedo.G", "albedo.R"};   // (byte-wise sorted, as the format stores them)
+    const float *data[7] = {normal, normal + 1, normal + 2, depth, albedo + 2, albedo + 1, albedo};
+    const uint32_t strides[7] = {3, 3, 3, 1, 3, 3, 3};
+    return ptf_ok(ptf_write_exr_channels(j.o.aov.c_str(), j.p.width, j.p.height, 7, names, data, strides));
 }
 
 int main(int argc, char **argv) {
-    std::string scene, outfile, samples, checkpoint, aov, denoise; long long dn_iterations = -1; int device = 0, spp = 0; long long preview = 0; bool quiet = false;
-    bool adaptive = false; float threshold = 0.0f; long long astep = 4, amin = 0;
-    for (int i = 1; i < argc; ++i) {
-        std::string a = argv[i];
-        if (a == "--outfile" && i + 1 < argc) outfile = argv[++i];
-        else if (a == "--device" && i + 1 < argc) device = std::atoi(argv[++i]);
-        else if (a == "--spp" && i + 1 < argc) spp = std::atoi(argv[++i]);
-        else if (a == "--samples" && i + 1 < argc) samples = argv[++i];
-        else if (a == "--checkpoint" && i + 1 < argc) checkpoint = argv[++i];
-        else if (a == "--aov" && i + 1 < argc) aov = argv[++i];
-        else if (a == "--denoise" && i + 1 < argc) denoise = argv[++i];
-        else if (a == "--denoise-iterations" && i + 1 < argc) {
-            char *end = nullptr; dn_iterations = std::strtoll(argv[++i], &end, 10);
-            if (end == argv[i] || *end || dn_iterations < 0 || dn_iterations > 5) return usage("--denoise-iterations takes a number of levels 0..5");
-        }
-        else if (a == "--preview-every" && i + 1 < argc) { preview = std::atoll(argv[++i]); if (preview <= 0 || preview > 0xffffffffll) return usage("--preview-every takes a number of samples > 0"); }
-        else if (a == "--adaptive" && i + 1 < argc) {
-            char *end = nullptr; threshold = std::strtof(argv[++i], &end);
-            if (end == argv[i] || *end || !(threshold >= 0.0f)) return usage("--adaptive takes an error threshold >= 0");
-            adaptive = true;
-        }
-        else if (a == "--adaptive-step" && i + 1 < argc) { astep = std::atoll(argv[++i]); if (astep <= 0 || astep > 0xffffffffll) return usage("--adaptive-step takes a number of samples > 0"); }
-        else if (a == "--adaptive-min" && i + 1 < argc) { amin = std::atoll(argv[++i]); if (amin < 0 || amin > 0xffffffffll) return usage("--adaptive-min takes a number of samples >= 0"); }
-        else if (a == "--quiet") quiet = true;
-        else if (a[0] != '-') scene = a;
-        else return usage();
-    }
-    if (scene.empty()) return usage();
-    if (adaptive && !samples.empty()) return usage("--adaptive with --samples: an adaptive render chooses its own sample ranges, tile by tile");
-    if (adaptive && !checkpoint.empty()) return usage("--adaptive with --checkpoint: a checkpoint holds one sample count for the frame, an adaptive render one per tile");
-    if (adaptive && !aov.empty()) return usage("--adaptive with --aov: the feature buffers have no tile-list render");
-    if (adaptive && !denoise.empty()) return usage("--adaptive with --denoise: the filter takes one sample count for the frame, an adaptive render's tiles hold different ones");
-    if (!checkpoint.empty() && !denoise.empty()) return usage("--checkpoint with --denoise: a checkpoint holds one film, a denoising run renders two halves");
-    if (preview > 0 && !denoise.empty()) return usage("--preview-every with --denoise: a preview shows the film so far, which a denoising run keeps as two halves");
-    if (dn_iterations >= 0 && denoise.empty()) return usage("--denoise-iterations without --denoise");
-    long long lo = 0, hi = 0;
-    if (!samples.empty() && !parse_range(samples, lo, hi)) return usage("--samples takes A:B with 0 <= A < B, got \"" + samples + "\"");
-    ptf_scene *fs = nullptr;
-    if (ptf_parse_file(scene.c_str(), &fs) != PT_OK) { std::fprintf(stderr, "mi355pbrt: %s\n", ptf_last_error()); return 1; }
-    PtRenderParams rp = *ptf_render_params(fs);
-    if (spp > 0) rp.spp = (uint32_t)spp;
-    if (samples.empty()) hi = rp.spp;
-    else if (hi > (long long)rp.spp) return usage("--samples " + samples + " goes beyond the job's " + std::to_string(rp.spp) + " samples per pixel");
-    const uint32_t first = (uint32_t)lo, last = (uint32_t)hi;
-    const bool dn = !denoise.empty();
-    if (dn && last - first < 2) return usage("--denoise needs two samples per pixel at least: it renders them as two halves");
-    const uint32_t mid = first + (last - first) / 2;   // --denoise: half A is [first, mid), half B [mid, last)
-    if (outfile.empty()) {
-        outfile = ptf_output_filename(fs);
-    }
-    const bool is_ao = rp.integrator == PT_INTEGRATOR_AO;   // Integrator "ambientocclusion" (libmi355ao.so)
-    PtAOParams ao{}; if (is_ao) ptf_ao_params(fs, &ao);
-    if (adaptive && is_ao) return usage("--adaptive with Integrator \"ambientocclusion\": the ambient-occlusion integrator has no tile-list render");
-    const int w = rp.cropped_pixel_bounds[2] - rp.cropped_pixel_bounds[0], h = rp.cropped_pixel_bounds[3] - rp.cropped_pixel_bounds[1];
-    if (w <= 0 || h <= 0) { std::fprintf(stderr, "mi355pbrt: empty film\n"); return 1; }
-    const size_t npix = (size_t)w * h;
-    std::vector<float> film(npix * 4, 0.0f), rgb(npix * 3);
-    // a checkpoint of this job: continue after its samples (host work: a file of another job is refused before the device is touched)
-    PtfCheckpointHeader ck{PTF_CHECKPOINT_MAGIC, 1u, (uint32_t)w, (uint32_t)h, rp.spp, first, 0u, 0u, ptf_params_hash(&rp, is_ao ? &ao : nullptr)};
-    if (!checkpoint.empty()) {
-        if (ptf_checkpoint_read(checkpoint.c_str(), &ck, &ck.samples_done, film.data()) != PT_OK) { std::fprintf(stderr, "mi355pbrt: %s\n", ptf_last_error()); return 1; }
-        if (ck.samples_done > last - first) { std::fprintf(stderr, "mi355pbrt: checkpoint \"%s\" holds more samples than --samples asks for\n", checkpoint.c_str()); return 1; }
-        if (ck.samples_done && !quiet) std::printf("resuming %s at sample %u of [%u, %u)\n", checkpoint.c_str(), first + ck.samples_done, first, last);
-    }
-    if (pt_init(device) != PT_OK) { std::fprintf(stderr, "mi355pbrt: %s\n", pt_last_error()); return 1; }
+    Options o; Plan plan; std::string why;
+    if (parse_options(argc, argv, o, why)) return usage(why);
+    Parsed fs;
+    if (!ptf_ok(ptf_parse_file(o.scene.c_str(), &fs.p))) return 1;
+    const bool is_ao = ptf_render_params(fs.p)->integrator == PT_INTEGRATOR_AO;
+    if (const int st = make_plan(o, *ptf_render_params(fs.p), is_ao, plan, why)) return st == 2 ? usage(why) : die(why.c_str());
+    if (o.outfile.empty()) o.outfile = ptf_output_filename(fs.p);
+    PtAOParams ao{}; if (is_ao) ptf_ao_params(fs.p, &ao);
+    const size_t npix = (size_t)plan.width * plan.height;
+    Job j{o, plan, is_ao ? &ao : nullptr, npix, std::vector<float>(npix * 4, 0.0f), std::vector<float>(npix * 3)};
+    PtfCheckpointHeader ck{PTF_CHECKPOINT_MAGIC, 1u, (uint32_t)plan.width, (uint32_t)plan.height, plan.rp.spp, plan.first, 0u, 0u, ptf_params_hash(&plan.rp, j.ao)};
+    if (!o.checkpoint.empty() && !resume(j, ck)) return 1;
+
+    if (!pt_ok(pt_init(o.device))) return 1;
     const auto t0 = std::chrono::steady_clock::now();
-    pt_scene *sc = nullptr;
-    if (pt_scene_create(ptf_scene_desc(fs), &sc) != PT_OK) { std::fprintf(stderr, "mi355pbrt: %s\n", pt_last_error()); return 1; }
+    if (!pt_ok(pt_scene_create(ptf_scene_desc(fs.p), &j.sc.p))) return 1;
     const auto t1 = std::chrono::steady_clock::now();
-    float *d_film = nullptr, *d_rgb = nullptr;
-    if (hipMalloc((void **)&d_film, npix * 16) != hipSuccess || hipMalloc((void **)&d_rgb, npix * 12) != hipSuccess ||
-        hipMemcpy(d_film, film.data(), npix * 16, hipMemcpyHostToDevice) != hipSuccess) { std::fprintf(stderr, "mi355pbrt: device film: %s\n", hipGetErrorString(hipGetLastError())); return 1; }
-    // the film so far -> outfile, resolved on the device
-    auto write_out = [&]() {
-        if (pt_film_resolve_device(sc, d_film, (uint32_t)npix, rp.scale, d_rgb, nullptr) != PT_OK) { std::fprintf(stderr, "mi355pbrt: %s\n", pt_last_error()); return false; }
-        if (hipMemcpy(rgb.data(), d_rgb, npix * 12, hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "mi355pbrt: reading the image back failed\n"); return false; }
-        if (ptf_write_image(outfile.c_str(), w, h, rgb.data()) != PT_OK) { std::fprintf(stderr, "mi355pbrt: %s\n", ptf_last_error()); return false; }
-        return true;
-    };
-    uint32_t group = last - first;   // samples per pt_render_samples call
-    if (preview > 0) group = (uint32_t)std::min<long long>(preview, group);
-    else if (!checkpoint.empty()) {
-        const int pst = is_ao ? pt_ao_pass_size(sc, &rp, &ao, &group) : pt_pass_size(sc, &rp, &group);
-        if (pst != PT_OK) { std::fprintf(stderr, "mi355pbrt: %s\n", pt_last_error()); return 1; }
-    }
-    unsigned long long camera_rays = 0;
-    float *d_half_b = nullptr;   // --denoise: half B (d_film is half A until the halves are summed)
-    if (dn && (hipMalloc((void **)&d_half_b, npix * 16) != hipSuccess || hipMemset(d_half_b, 0, npix * 16) != hipSuccess || hipDeviceSynchronize() != hipSuccess)) {
-        std::fprintf(stderr, "mi355pbrt: device film: %s\n", hipGetErrorString(hipGetLastError())); return 1;
-    }
-    if (adaptive) {   // runtime.Scene.render_adaptive's loop: d_film is half A, d_half half B, the active set only shrinks
-        const auto fail_pt = [&]() { std::fprintf(stderr, "mi355pbrt: %s\n", pt_last_error()); return 1; };
-        uint32_t ntx = 0, nty = 0;
-        if (pt_tile_grid(&rp, &ntx, &nty) != PT_OK) return fail_pt();
-        const size_t n_film_tiles = (size_t)((w + 15) / 16) * ((h + 15) / 16);
-        float *d_half = nullptr, *d_err = nullptr;
-        if (hipMalloc((void **)&d_half, npix * 16) != hipSuccess || hipMalloc((void **)&d_err, n_film_tiles * 4) != hipSuccess || hipMemset(d_half, 0, npix * 16) != hipSuccess ||
-            hipDeviceSynchronize() != hipSuccess) { std::fprintf(stderr, "mi355pbrt: device film: %s\n", hipGetErrorString(hipGetLastError())); return 1; }
-        std::vector<uint32_t> active((size_t)ntx * nty), kept(active.size());
-        for (size_t i = 0; i < active.size(); ++i) active[i] = (uint32_t)i;
-        unsigned long long tile_samples = 0; unsigned rounds = 0;
-        for (uint32_t done = 0; done < rp.spp && !active.empty(); ++rounds) {
-            uint32_t n_b = 0;
-            for (float *half : {d_film, d_half}) {
-                const uint32_t n = (uint32_t)std::min<long long>(astep, rp.spp - done);
-                if (half == d_half) n_b = n;
-                if (n == 0) continue;
-                if (pt_render_tiles(sc, &rp, done, n, active.data(), (uint32_t)active.size(), half, 1) != PT_OK) return fail_pt();
-                PtCounters c; pt_get_counters(sc, &c); camera_rays += c.camera_rays;
-                done += n; tile_samples += (unsigned long long)n * active.size();
-            }
-            if (n_b > 0 && done >= (uint32_t)amin) {
-                uint32_t n_kept = 0;
-                if (pt_film_halves_error(sc, d_film, d_half, (uint32_t)w, (uint32_t)h, d_err, nullptr, nullptr) != PT_OK ||
-                    pt_tiles_select(sc, &rp, d_err, threshold, active.data(), (uint32_t)active.size(), kept.data(), &n_kept) != PT_OK) return fail_pt();
-                active.assign(kept.begin(), kept.begin() + n_kept);
-            }
-        }
-        // A += B: the film is the sum of the halves (host arithmetic on the read-back halves, element by element)
-        std::vector<float> half_b(npix * 4);
-        if (hipMemcpy(film.data(), d_film, npix * 16, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(half_b.data(), d_half, npix * 16, hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "mi355pbrt: reading the film back failed\n"); return 1; }
-        for (size_t i = 0; i < film.size(); ++i) film[i] += half_b[i];
-        if (hipMemcpy(d_film, film.data(), npix * 16, hipMemcpyHostToDevice) != hipSuccess) { std::fprintf(stderr, "mi355pbrt: writing the film back failed\n"); return 1; }
-        (void)hipFree(d_half); (void)hipFree(d_err);
-        if (!quiet) std::printf("adaptive: %llu of %llu tile-samples, %u rounds\n", tile_samples, (unsigned long long)ntx * nty * rp.spp, rounds);
-    }
-    for (uint32_t s = first + ck.samples_done; s < last && !adaptive; ) {
-        const uint32_t n = std::min(group, (dn && s < mid ? mid : last) - s);
-        float *const into = dn && s >= mid ? d_half_b : d_film;
-        const int rst = is_ao ? pt_ao_render_samples(sc, &rp, &ao, s, n, into, 1) : pt_render_samples(sc, &rp, s, n, into, 1);
-        if (rst != PT_OK) { std::fprintf(stderr, "mi355pbrt: %s\n", pt_last_error()); return 1; }
-        PtCounters c; pt_get_counters(sc, &c); camera_rays += c.camera_rays;
-        s += n; ck.samples_done = s - first;
-        if (!checkpoint.empty()) {
-            if (hipMemcpy(film.data(), d_film, npix * 16, hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "mi355pbrt: reading the film back failed\n"); return 1; }
-            if (ptf_checkpoint_write(checkpoint.c_str(), &ck, film.data()) != PT_OK) { std::fprintf(stderr, "mi355pbrt: %s\n", ptf_last_error()); return 1; }
-        }
-        if (preview > 0 && s < last && !write_out()) return 1;
-    }
+    if (!j.d_film.alloc("device film", npix * 16, false) || !j.d_rgb.alloc("device film", npix * 12, false) ||
+        !(hipMemcpy(j.d_film.p, j.film.data(), npix * 16, hipMemcpyHostToDevice) == hipSuccess || hip_failed("device film"))) return 1;
+    if ((plan.denoise || o.adaptive) && !j.d_half_b.alloc("device film", npix * 16, true)) return 1;
+    if (!(o.adaptive ? render_adaptive(j) : render_groups(j, ck))) return 1;
     const auto t2 = std::chrono::steady_clock::now();
-    float *d_sums = nullptr;   // the feature sums of sample numbers [first, last), whatever groups (or earlier runs, --checkpoint) rendered the image's: for --denoise and --aov
-    if (dn || !aov.empty()) {
-        if (hipMalloc((void **)&d_sums, npix * 40) != hipSuccess || hipMemset(d_sums, 0, npix * 40) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { std::fprintf(stderr, "mi355pbrt: feature buffers: %s\n", hipGetErrorString(hipGetLastError())); return 1; }
-        const PtAOVBuffers d_planes{d_sums, d_sums + npix * 4, d_sums + npix * 8};
-        if (pt_aov_render_samples(sc, &rp, first, last - first, &d_planes, 1) != PT_OK) { std::fprintf(stderr, "mi355pbrt: %s\n", pt_last_error()); return 1; }
-    }
-    if (dn) {   // the filter reads the halves; then A += B: the outfile's film (host arithmetic on the read-back halves, element by element)
-        const PtAOVBuffers d_planes{d_sums, d_sums + npix * 4, d_sums + npix * 8};
-        PtDenoiseParams dp; pt_denoise_default_params(&dp);
-        if (dn_iterations >= 0) dp.iterations = (uint32_t)dn_iterations;
-        dp.scale = rp.scale;
-        if (pt_denoise(sc, &dp, d_film, d_half_b, &d_planes, (uint32_t)w, (uint32_t)h, d_rgb, 1) != PT_OK) { std::fprintf(stderr, "mi355pbrt: %s\n", pt_last_error()); return 1; }
-        if (hipMemcpy(rgb.data(), d_rgb, npix * 12, hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "mi355pbrt: reading the denoised image back failed\n"); return 1; }
-        if (ptf_write_image(denoise.c_str(), w, h, rgb.data()) != PT_OK) { std::fprintf(stderr, "mi355pbrt: %s\n", ptf_last_error()); return 1; }
-        std::vector<float> half_b(npix * 4);
-        if (hipMemcpy(film.data(), d_film, npix * 16, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(half_b.data(), d_half_b, npix * 16, hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "mi355pbrt: reading the film back failed\n"); return 1; }
-        for (size_t i = 0; i < film.size(); ++i) film[i] += half_b[i];
-        if (hipMemcpy(d_film, film.data(), npix * 16, hipMemcpyHostToDevice) != hipSuccess) { std::fprintf(stderr, "mi355pbrt: writing the film back failed\n"); return 1; }
-        (void)hipFree(d_half_b);
-    }
-    if (!write_out()) return 1;
-    if (!aov.empty()) {
-        std::vector<float> sums(npix * 10, 0.0f), res(npix * 7);
-        if (hipMemcpy(sums.data(), d_sums, npix * 40, hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "mi355pbrt: reading the feature buffers back failed\n"); return 1; }
-        const PtAOVBuffers planes{sums.data(), sums.data() + npix * 4, sums.data() + npix * 8};
-        float *albedo = res.data(), *normal = res.data() + npix * 3, *depth = res.data() + npix * 6;
-        if (pt_aov_resolve(&planes, (uint32_t)npix, albedo, normal, depth) != PT_OK) { std::fprintf(stderr, "mi355pbrt: %s\n", pt_last_error()); return 1; }
-        const char *names[7] = {"N.X", "N.Y", "N.Z", "Z", "albedo.B", "albedo.G", "albedo.R"};   // (byte-wise sorted, as the format stores them)
-        const float *data[7] = {normal, normal + 1, normal + 2, depth, albedo + 2, albedo + 1, albedo};
-        const uint32_t strides[7] = {3, 3, 3, 1, 3, 3, 3};
-        if (ptf_write_exr_channels(aov.c_str(), w, h, 7, names, data, strides) != PT_OK) { std::fprintf(stderr, "mi355pbrt: %s\n", ptf_last_error()); return 1; }
-    }
-    if (!quiet) {
+
+    DeviceBuffer d_sums;
+    if ((plan.denoise || !o.aov.empty()) && !render_features(j, d_sums)) return 1;
+    if (plan.denoise && !write_denoised(j, d_sums.p)) return 1;
+    if (!write_out(j)) return 1;
+    if (!o.aov.empty() && !write_aov(j, d_sums.p)) return 1;
+    if (!o.quiet) {
         const double ts = std::chrono::duration<double>(t1 - t0).count(), tr = std::chrono::duration<double>(t2 - t1).count();
-        std::printf("%s: %dx%d, %u spp, %llu camera rays, scene %.2f s, render %.3f s (%.1f Msamples/s) -> %s\n", scene.c_str(), w, h, rp.spp,
-                    camera_rays, ts, tr, (double)camera_rays / tr / 1e6, outfile.c_str());
+        std::printf("%s: %dx%d, %u spp, %llu camera rays, scene %.2f s, render %.3f s (%.1f Msamples/s) -> %s\n", o.scene.c_str(), plan.width, plan.height, plan.rp.spp,
+                    j.camera_rays, ts, tr, (double)j.camera_rays / tr / 1e6, o.outfile.c_str());
     }
-    (void)hipFree(d_film); (void)hipFree(d_rgb); (void)hipFree(d_sums);
-    pt_scene_destroy(sc); ptf_scene_destroy(fs);
     return 0;
 }

@@ -10,21 +10,28 @@ from . import _abi_aov as AOV
 from . import _abi_dn as DN
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("PT_LIB_PATH") or os.path.join(_HERE, "csrc", "libmi355pt.so")   # PT_LIB_PATH: kernel-variant experiments
-AO_LIB_PATH = os.path.join(_HERE, "ao", "libmi355ao.so")   # the ambient-occlusion integrator (include/mi355ao.h), linked against libmi355pt.so
-AOV_LIB_PATH = os.path.join(_HERE, "aov", "libmi355aov.so")   # the feature buffers for denoising (include/mi355aov.h), linked against libmi355pt.so
-DN_LIB_PATH = os.path.join(_HERE, "denoise", "libmi355dn.so")   # the a-trous denoiser over half films and feature buffers (include/mi355dn.h), linked against libmi355pt.so
+# The HIP libraries, in build order: the product library, then those linked against it. name: (directory, file, ctypes mirror, header under include/).
+# What builds them, finds them, loads them (Library) and checks their exports (__graft_entry__.build) reads this table.
+LIBRARIES = {
+    "pt": ("csrc", "libmi355pt.so", A, "mi355pt.h"),
+    "ao": ("ao", "libmi355ao.so", AO, "mi355ao.h"),          # the ambient-occlusion integrator
+    "aov": ("aov", "libmi355aov.so", AOV, "mi355aov.h"),     # the feature buffers for denoising
+    "dn": ("denoise", "libmi355dn.so", DN, "mi355dn.h"),     # the a-trous denoiser over half films and feature buffers
+}
+LIB_PATHS = {name: os.path.join(_HERE, sub, file) for name, (sub, file, _, _) in LIBRARIES.items()}
+LIB_PATHS["pt"] = os.environ.get("PT_LIB_PATH") or LIB_PATHS["pt"]   # PT_LIB_PATH: kernel-variant experiments
+LIB_PATH, AO_LIB_PATH, AOV_LIB_PATH, DN_LIB_PATH = (LIB_PATHS[name] for name in ("pt", "ao", "aov", "dn"))
 TABLES_PATH = os.path.join(_HERE, "data", "sobol_tables.bin")
 
 
 def build_library(verbose=False):
-    """Compile every HIP source for gfx950 (hipcc cross-compiles without a GPU): libmi355pt.so, then libmi355ao.so, libmi355aov.so and libmi355dn.so, which link against it."""
-    for sub, name in (("csrc", "libmi355pt.so"), ("ao", "libmi355ao.so"), ("aov", "libmi355aov.so"), ("denoise", "libmi355dn.so")):
+    """Compile every HIP source for gfx950 (hipcc cross-compiles without a GPU): the libraries of LIBRARIES, in its order."""
+    for sub, file, _, _ in LIBRARIES.values():
         r = subprocess.run(["make", "-C", os.path.join(_HERE, sub), "-j8"], capture_output=True, text=True)
         if verbose or r.returncode != 0:
             print(r.stdout[-4000:]); print(r.stderr[-4000:])
         if r.returncode != 0:
-            raise RuntimeError(f"building {name} failed")
+            raise RuntimeError(f"building {file} failed")
     return LIB_PATH
 
 
@@ -37,19 +44,16 @@ class Library:
         if not os.path.exists(path):
             raise PtError(f"{path} not found: build it with __graft_entry__.build() (no CPU fallback exists)")
         self.lib = A.bind(C.CDLL(path), strict=not os.environ.get("PT_LIB_PATH"))   # (PT_LIB_PATH: a kernel-variant library of an A/B run, possibly built from an older tree)
-        self._side = {}
 
-    def _side_library(self, path, table):
-        """An integrator library linked against libmi355pt.so, loaded and bound on first use."""
-        if path not in self._side:
-            if not os.path.exists(path):
-                raise PtError(f"{path} not found: build it with __graft_entry__.build() (no CPU fallback exists)")
-            self._side[path] = A.bind(C.CDLL(path), table=table)
-        return self._side[path]
-
-    aov = property(lambda self: self._side_library(AOV_LIB_PATH, AOV.ENTRY_POINTS), doc="libmi355aov.so (include/mi355aov.h), loaded on first use.")
-    dn = property(lambda self: self._side_library(DN_LIB_PATH, DN.ENTRY_POINTS), doc="libmi355dn.so (include/mi355dn.h), loaded on first use.")
-    ao = property(lambda self: self._side_library(AO_LIB_PATH, AO.ENTRY_POINTS), doc="libmi355ao.so (include/mi355ao.h), loaded on first use.")
+    def __getattr__(self, name):
+        """.ao, .aov, .dn: a library of LIBRARIES linked against the product library, loaded and bound on first use (and then an attribute like any other)."""
+        if name == "pt" or name not in LIBRARIES:
+            raise AttributeError(name)
+        path = LIB_PATHS[name]
+        if not os.path.exists(path):
+            raise PtError(f"{path} not found: build it with __graft_entry__.build() (no CPU fallback exists)")
+        setattr(self, name, A.bind(C.CDLL(path), table=LIBRARIES[name][2].ENTRY_POINTS))
+        return getattr(self, name)
 
     def check(self, st, what=""):
         if st != A.PT_OK:
@@ -78,6 +82,20 @@ def _fptr(a):
     return a.ctypes.data_as(A.fp)
 
 
+def film_shape(rp):
+    """(h, w) of the film of the job `rp`: its cropped pixel window."""
+    cb = rp.cropped_pixel_bounds
+    return cb[3] - cb[1], cb[2] - cb[0]
+
+
+def _device_zeros(*shapes):
+    """Zeroed float32 torch tensors of `shapes` on the device, there to be added to."""
+    import torch
+    out = [torch.zeros(s, dtype=torch.float32, device="cuda") for s in shapes]
+    torch.cuda.synchronize()   # (the library renders on its own stream: the zeroed buffers must be there before it adds to them)
+    return out
+
+
 def default_denoise_params(lib=None):
     """pt_denoise_default_params: a PtDenoiseParams to adjust and hand to Scene.denoise / Scene.render_denoised."""
     p = DN.PtDenoiseParams()
@@ -92,8 +110,7 @@ def resolve_aov(sums, lib=None):
     sums = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in sums.items()}
     shape = next(iter(sums.values())).shape[:2]
     out = {k: np.zeros(shape + ((3,) if k != "depth" else ()), dtype=np.float32) for k in sums}
-    bufs = AOV.PtAOVBuffers(*[_fptr(sums[k]) if k in sums else None for k in AOV.PLANES])
-    lib.check(lib.aov.pt_aov_resolve(C.byref(bufs), shape[0] * shape[1], *[_fptr(out[k]) if k in out else None for k in AOV.PLANES]), "pt_aov_resolve")
+    lib.check(lib.aov.pt_aov_resolve(C.byref(AOV.buffers(sums)), shape[0] * shape[1], *[_fptr(out[k]) if k in out else None for k in AOV.PLANES]), "pt_aov_resolve")
     return out
 
 
@@ -143,11 +160,14 @@ class Handle:
         if samples is not None:
             first, n = samples
             args += [first, n]; name += "_samples"
+        return self._film_call(name, args, rp, film, device_ptr, last, lib)
+
+    def _film_call(self, name, args, rp, film, device_ptr, last, lib):
+        """The tail of a render call that ADDS to a film: to the device film at `device_ptr` (returns None), else to the host array `film`, made when None and returned."""
         if device_ptr is not None:
             self._call(name, *args, C.c_void_p(device_ptr), 1, lib=lib); return None
         if film is None:
-            cb = rp.cropped_pixel_bounds
-            film = np.zeros((cb[3] - cb[1], cb[2] - cb[0], 4), dtype=np.float32)
+            film = np.zeros(film_shape(rp) + (4,), dtype=np.float32)
         film_type = getattr(lib, self.PREFIX + name).argtypes[-2]   # void* in the product library, float* in the oracle
         self._call(name, *args, film.ctypes.data_as(film_type), 0 if last is None else last, lib=lib)
         return film
@@ -194,13 +214,16 @@ class Scene(Handle):
 
     @property
     def _ao(self):
-        return self.L.ao   # libmi355ao.so, loaded on first use
+        return self.L.ao   # the AO integrator's library, loaded on first use
+
+    def _pass_size(self, name, *args, lib=None):
+        s = C.c_uint32()
+        self._call(name, self.h, *args, C.byref(s), lib=lib)
+        return int(s.value)
 
     def pass_size(self, rp):
         """Samples per pixel per wavefront pass pt_render would use for `rp` now (the library's choice from the free memory when rp.spp_per_pass == 0)."""
-        s = C.c_uint32()
-        self._call("pass_size", self.h, C.byref(rp), C.byref(s))
-        return int(s.value)
+        return self._pass_size("pass_size", C.byref(rp))
 
     def resolve_device(self, film_ptr, n_pixels, scale=1.0, rgb_ptr=None, srgb8_ptr=None):
         """pt_film_resolve_device: a film on the device -> rgb floats and / or 8-bit sRGB codes on the device (device pointers as integers)."""
@@ -216,13 +239,10 @@ class Scene(Handle):
         """The job `rp` in ranges of `step` samples, alternately into two torch films A and B on the device (A + B is the film). After each range:
         pt_film_halves_error of A and B, then on_step(done, mean_error, max_tile_error); nothing but those two numbers is read back. Stops when the job is done or,
         once both halves hold samples, when mean_error <= target_error. Returns (A + B as a numpy film (H, W, 4), samples rendered per pixel)."""
-        import torch
         if step <= 0:
             raise ValueError("step must be > 0")
-        cb = rp.cropped_pixel_bounds
-        w, h = cb[2] - cb[0], cb[3] - cb[1]
-        halves = [torch.zeros((h, w, 4), dtype=torch.float32, device="cuda") for _ in range(2)]
-        torch.cuda.synchronize()   # (the library renders on its own stream: the zeroed films must be there before it adds to them)
+        h, w = film_shape(rp)
+        halves = _device_zeros((h, w, 4), (h, w, 4))
         done = k = 0
         while done < rp.spp:
             n = min(step, rp.spp - done)
@@ -247,13 +267,7 @@ class Scene(Handle):
         first, n = samples
         tiles = np.ascontiguousarray(tiles, dtype=np.uint32)
         args = [self.h, C.byref(rp), first, n, tiles.ctypes.data_as(A.u32p), len(tiles)]
-        if device_ptr is not None:
-            self._call("render_tiles", *args, C.c_void_p(device_ptr), 1); return None
-        if film is None:
-            cb = rp.cropped_pixel_bounds
-            film = np.zeros((cb[3] - cb[1], cb[2] - cb[0], 4), dtype=np.float32)
-        self._call("render_tiles", *args, film.ctypes.data_as(C.c_void_p), 0)
-        return film
+        return self._film_call("render_tiles", args, rp, film, device_ptr, None, self._lib)
 
     def select_tiles(self, rp, tile_error_ptr, threshold, candidates=None):
         """pt_tiles_select: of `candidates` (ascending tile indices; None: every tile of the grid) those whose film footprint meets a film tile whose error -- the
@@ -278,15 +292,11 @@ class Scene(Handle):
         over the loop's render calls (counters() describes the last call alone).
         Caveat: the stopping rule reads the same samples it stops. A tile whose two halves happen to agree early stops early, so the estimate is biased (towards
         the values at which halves agree); min_samples bounds how early that can happen, it does not remove the bias."""
-        import torch
         if step <= 0:
             raise ValueError("step must be > 0")
-        cb = rp.cropped_pixel_bounds
-        w, h = cb[2] - cb[0], cb[3] - cb[1]
+        h, w = film_shape(rp)
         ntx, nty = self.tile_grid(rp)
-        halves = [torch.zeros((h, w, 4), dtype=torch.float32, device="cuda") for _ in range(2)]
-        tile_err = torch.zeros((-(-w // 16)) * (-(-h // 16)), dtype=torch.float32, device="cuda")
-        torch.cuda.synchronize()   # (the library renders on its own stream: the zeroed films must be there before it adds to them)
+        *halves, tile_err = _device_zeros((h, w, 4), (h, w, 4), (-(-w // 16)) * (-(-h // 16)))
         active = np.arange(ntx * nty, dtype=np.uint32)
         per_tile = np.zeros(ntx * nty, dtype=np.uint32)
         done, total = 0, None
@@ -317,20 +327,15 @@ class Scene(Handle):
         args = [self.h, C.byref(rp)] + ([] if samples is None else list(samples))
         name = "aov_render" if samples is None else "aov_render_samples"
         if device_ptrs is not None:
-            bufs = AOV.PtAOVBuffers(*[C.cast(C.c_void_p(device_ptrs[k]), A.fp) if k in device_ptrs else None for k in AOV.PLANES])
-            self._call(name, *args, C.byref(bufs), 1, lib=self.L.aov); return None
+            self._call(name, *args, C.byref(AOV.buffers(device_ptrs, device=True)), 1, lib=self.L.aov); return None
         if sums is None:
-            cb = rp.cropped_pixel_bounds
-            sums = {k: np.zeros((cb[3] - cb[1], cb[2] - cb[0], AOV.CHANNELS[k]), dtype=np.float32) for k in planes}
-        bufs = AOV.PtAOVBuffers(*[_fptr(sums[k]) if k in sums else None for k in AOV.PLANES])
-        self._call(name, *args, C.byref(bufs), 0, lib=self.L.aov)
+            sums = {k: np.zeros(film_shape(rp) + (AOV.CHANNELS[k],), dtype=np.float32) for k in planes}
+        self._call(name, *args, C.byref(AOV.buffers(sums)), 0, lib=self.L.aov)
         return sums
 
     def aov_pass_size(self, rp):
         """Samples per pixel per pass pt_aov_render would use for `rp` now."""
-        s = C.c_uint32()
-        self._call("aov_pass_size", self.h, C.byref(rp), C.byref(s), lib=self.L.aov)
-        return int(s.value)
+        return self._pass_size("aov_pass_size", C.byref(rp), lib=self.L.aov)
 
     def denoise(self, film_a, film_b, sums, params=None, device_ptrs=None):
         """pt_denoise of two half films (H, W, 4) -- XYZW sums of disjoint sample ranges, A + B is the film -- and the feature sums of the samples of A + B (the
@@ -341,8 +346,7 @@ class Scene(Handle):
             params = default_denoise_params(self.L)
         if device_ptrs is not None:
             w, h, out = device_ptrs
-            bufs = AOV.PtAOVBuffers(*[C.cast(C.c_void_p(sums[k]), A.fp) for k in AOV.PLANES])
-            self._call("denoise", self.h, C.byref(params), C.c_void_p(film_a), C.c_void_p(film_b), C.byref(bufs), w, h, C.c_void_p(out), 1, lib=lib); return None
+            self._call("denoise", self.h, C.byref(params), C.c_void_p(film_a), C.c_void_p(film_b), C.byref(AOV.buffers(sums, device=True)), w, h, C.c_void_p(out), 1, lib=lib); return None
         film_a, film_b = (np.ascontiguousarray(f, dtype=np.float32) for f in (film_a, film_b))
         sums = {k: np.ascontiguousarray(sums[k], dtype=np.float32) for k in AOV.PLANES}
         h, w = film_a.shape[:2]
@@ -350,23 +354,18 @@ class Scene(Handle):
             if arr.shape != (h, w, ch):
                 raise ValueError(f"denoise: {name} has shape {arr.shape}, expected {(h, w, ch)}")
         out = np.zeros((h, w, 3), dtype=np.float32)
-        bufs = AOV.PtAOVBuffers(*[_fptr(sums[k]) for k in AOV.PLANES])
-        self._call("denoise", self.h, C.byref(params), film_a.ctypes.data_as(C.c_void_p), film_b.ctypes.data_as(C.c_void_p), C.byref(bufs), w, h, out.ctypes.data_as(C.c_void_p), 0, lib=lib)
+        self._call("denoise", self.h, C.byref(params), film_a.ctypes.data_as(C.c_void_p), film_b.ctypes.data_as(C.c_void_p), C.byref(AOV.buffers(sums)), w, h, out.ctypes.data_as(C.c_void_p), 0, lib=lib)
         return out
 
     def render_denoised(self, rp, params=None, inputs=False):
         """The job `rp` rendered and denoised without leaving the device: sample numbers [0, spp / 2) into half film A and [spp / 2, spp) into B (pt_render_samples),
         the feature sums of [0, spp) (pt_aov_render), pt_denoise of the three. Returns (the denoised image (H, W, 3), A + B as a numpy film (H, W, 4)); `inputs`: and (A, B, the feature sums) as the filter read them, numpy copies.
         counters() afterwards describes the feature render, kernel_stats() that render plus the denoiser's launches."""
-        import torch
         if rp.spp < 2:
             raise ValueError("render_denoised needs spp >= 2: two half films with samples in each")
-        cb = rp.cropped_pixel_bounds
-        w, h = cb[2] - cb[0], cb[3] - cb[1]
-        halves = [torch.zeros((h, w, 4), dtype=torch.float32, device="cuda") for _ in range(2)]
-        planes = {k: torch.zeros((h, w, AOV.CHANNELS[k]), dtype=torch.float32, device="cuda") for k in AOV.PLANES}
-        rgb = torch.zeros((h, w, 3), dtype=torch.float32, device="cuda")
-        torch.cuda.synchronize()   # (the library renders on its own stream: the zeroed buffers must be there before it adds to them)
+        h, w = film_shape(rp)
+        a, b, rgb, *features = _device_zeros((h, w, 4), (h, w, 4), (h, w, 3), *[(h, w, AOV.CHANNELS[k]) for k in AOV.PLANES])
+        halves, planes = [a, b], dict(zip(AOV.PLANES, features))
         half = rp.spp // 2
         self.render(rp, device_ptr=halves[0].data_ptr(), samples=(0, half))
         self.render(rp, device_ptr=halves[1].data_ptr(), samples=(half, rp.spp - half))
@@ -384,10 +383,7 @@ class Scene(Handle):
 
     def ao_pass_size(self, rp, ao=None):
         """Samples per pixel per pass pt_ao_render would use for `rp` now."""
-        s = C.c_uint32()
-        ao = self.ao_params() if ao is None else ao
-        self._call("ao_pass_size", self.h, C.byref(rp), C.byref(ao), C.byref(s), lib=self.L.ao)
-        return int(s.value)
+        return self._pass_size("ao_pass_size", C.byref(rp), C.byref(self.ao_params() if ao is None else ao), lib=self.L.ao)
 
 
 class MultiScene(Handle):

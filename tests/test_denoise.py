@@ -223,3 +223,34 @@ def test_command_line_writes_the_library_image(pkg, gpu, tmp_path):
     # the two filter runs agree to rounding, not bit for bit)
     check(got, want, "mi355pbrt --denoise against Scene.denoise")
     assert np.abs(got - pkg.frontend.read_image(str(out))).max() > 0.01
+
+
+@pytest.mark.gpu
+def test_command_line_range_with_features_and_denoising_together(pkg, gpu, tmp_path):
+    """--samples 2:8 with --aov, --denoise and --outfile in one run: each file is what the flag gives without the other two."""
+    from test_aov_frontend import AOV_CHANNELS, read_exr_channels
+    scene = tmp_path / "scene.pbrt"; scene.write_text(SCENE % 8)
+    cli, common = pkg.frontend.CLI_PATH, [str(scene), "--samples", "2:8", "--quiet", "--outfile"]
+    for extra in (["plain.pfm"], ["alone.pfm", "--aov", "alone.exr"], ["o.pfm", "--aov", "f.exr", "--denoise", "d.pfm"]):
+        r = subprocess.run([cli] + common + extra, capture_output=True, text=True, timeout=300, env=trace_env(), cwd=tmp_path)
+        assert r.returncode == 0, r.stderr
+    read = lambda name: pkg.frontend.read_image(str(tmp_path / name))
+    # the outfile is the plain run's: the halves' sum adds a pixel's samples in another order, nothing else
+    np.testing.assert_allclose(read("o.pfm"), read("plain.pfm"), rtol=2e-6, atol=1e-7)
+    names, planes = read_exr_channels(str(tmp_path / "f.exr"))
+    alone = read_exr_channels(str(tmp_path / "alone.exr"))[1]
+    assert names == AOV_CHANNELS
+    for name in names:   # (test_aov_frontend's bounds: an atomic's place in a pixel's chain of additions varies between two renders)
+        np.testing.assert_allclose(planes[name], alone[name], rtol=2e-6, atol=2e-7 if name.startswith("N.") else 1e-7, err_msg=name)
+    fs = pkg.frontend.FrontScene(path=str(scene))
+    rp = fs.render_params()
+    g = pkg.Scene(gpu, fs)
+    try:
+        a, b = g.render(rp, samples=(2, 3)), g.render(rp, samples=(5, 3))
+        want = g.denoise(a, b, g.render_aov(rp, samples=(2, 6)), R.params_struct(pkg, scale=rp.scale))
+    finally:
+        g.close()
+    got = read("d.pfm")
+    assert got.shape == (24, 40, 3)
+    check(got, want, "mi355pbrt --samples 2:8 --aov --denoise against Scene.denoise")
+    assert np.abs(got - read("o.pfm")).max() > 0.01

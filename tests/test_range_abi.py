@@ -96,3 +96,47 @@ def test_checkpoint_round_trip_and_refusal(pkg, tmp_path):
     path.write_bytes(b"not a checkpoint" * 4)
     with pytest.raises(ValueError, match="not a checkpoint"):
         F.read_checkpoint(path, hdr)
+
+
+def test_front_end_table_names_what_the_header_declares(pkg):
+    import re
+    F = pkg._abi_front
+    header = open(os.path.join(INC, "mi355front.h")).read()
+    declared = set(re.findall(r"\b(ptf_\w+)\(", header))
+    assert declared == set(F.ENTRY_POINTS) and len(declared) == 15
+    for name, result in dict(ptf_last_error=C.c_char_p, ptf_output_filename=C.c_char_p, ptf_scene_desc=C.POINTER(pkg._abi.PtSceneDesc),
+                             ptf_render_params=C.POINTER(pkg._abi.PtRenderParams), ptf_params_hash=C.c_uint64, ptf_scene_destroy=None).items():
+        assert F.ENTRY_POINTS[name][0] is result, name
+    assert all(res is C.c_int for name, (res, _) in F.ENTRY_POINTS.items() if re.search(r"\bint %s\(" % name, header))
+    L = pkg.frontend.lib()   # bound through the table, and the names frontend.py had before it are still there
+    assert all(getattr(L, name).argtypes == args and getattr(L, name).restype is res for name, (res, args) in F.ENTRY_POINTS.items())
+    assert pkg.frontend.PtfCheckpointHeader is F.PtfCheckpointHeader and pkg.frontend.PTF_CHECKPOINT_MAGIC == F.PTF_CHECKPOINT_MAGIC and pkg.frontend.ENTRY_POINTS is F.ENTRY_POINTS
+
+
+def test_checkpoint_header_matches_the_ctypes_mirror(pkg, tmp_path):
+    H = pkg._abi_front.PtfCheckpointHeader
+    fields = [name for name, _ in H._fields_]
+    src = tmp_path / "probe.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "mi355front.h"\nint main(void) { printf("%u %d", PTF_CHECKPOINT_MAGIC, (int)sizeof(PtfCheckpointHeader));\n'
+                   + "".join('printf(" %%d", (int)offsetof(PtfCheckpointHeader, %s));\n' % f for f in fields) + "return 0; }\n")
+    exe = tmp_path / "probe"
+    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", INC, str(src), "-o", str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    out = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+    assert out == [pkg._abi_front.PTF_CHECKPOINT_MAGIC, C.sizeof(H)] + [getattr(H, f).offset for f in fields]
+    assert fields == ["magic", "version", "width", "height", "spp", "first_sample", "samples_done", "reserved", "params_hash"] and C.sizeof(H) == 40
+
+
+def test_one_table_of_libraries(pkg):
+    R = pkg.runtime
+    assert list(R.LIBRARIES) == ["pt", "ao", "aov", "dn"]
+    for name, (sub, file, abi, header) in R.LIBRARIES.items():
+        assert os.path.isfile(os.path.join(INC, header)) and os.path.isdir(os.path.join(os.path.dirname(R.__file__), sub)), name
+        assert abi.ENTRY_POINTS and R.LIB_PATHS[name].endswith(os.path.join(sub, file)) or (name == "pt" and os.environ.get("PT_LIB_PATH")), name
+    assert (R.LIB_PATH, R.AO_LIB_PATH, R.AOV_LIB_PATH, R.DN_LIB_PATH) == tuple(R.LIB_PATHS[k] for k in ("pt", "ao", "aov", "dn"))
+    # build()'s checks and Library's loaders read that table: nobody else spells the files' names
+    runtime = open(R.__file__).read()
+    entry = "\n".join(line.split("#")[0] for line in open(os.path.join(ROOT, "__graft_entry__.py")).read().splitlines())
+    for file in ("libmi355ao.so", "libmi355aov.so", "libmi355dn.so"):
+        assert runtime.count(file) == 1 and entry.count(file) == 0, file
+    assert "LIBRARIES" in entry and "ENTRY_POINTS" in entry
