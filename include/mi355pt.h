@@ -350,6 +350,14 @@ typedef struct PtSceneDesc {
 
 typedef enum PtIntegratorType { PT_INTEGRATOR_PATH = 0, PT_INTEGRATOR_VOLPATH = 1 } PtIntegratorType;
 typedef enum PtSamplerType { PT_SAMPLER_SOBOL = 0, PT_SAMPLER_HALTON = 1 } PtSamplerType;
+/* The projective and the environment camera (core/api.rs:832-836 minus "realistic"). What PtRenderParams carries for each:
+ *   PT_CAMERA_PERSPECTIVE   raster_to_camera = inverse(perspective(fov, .01, 1000)) * raster_to_screen (perspective.rs:40-86); lens_radius, focal_distance.
+ *   PT_CAMERA_ORTHOGRAPHIC  raster_to_camera = inverse(Transform::orthographic(0, 1)) * raster_to_screen (orthographic.rs:40-59); dx_camera / dy_camera are
+ *                           raster_to_camera applied to the VECTORS (1,0,0) and (0,1,0); lens_radius, focal_distance.
+ *   PT_CAMERA_ENVIRONMENT   lat-long panorama (environment.rs:36-51): theta = PI * pfilm.y / full_resolution.y, phi = 2 PI * pfilm.x / full_resolution.x;
+ *                           raster_to_camera, lens_radius and focal_distance are ignored, full_resolution is read. Its rays carry no differentials.
+ * Any other value is PT_ERR_INVALID_ARG from every entry point that takes PtRenderParams. */
+typedef enum PtCameraType { PT_CAMERA_PERSPECTIVE = 0, PT_CAMERA_ORTHOGRAPHIC = 1, PT_CAMERA_ENVIRONMENT = 2 } PtCameraType;
 /* "lightsamplestrategy" (path.rs:236, lightdistrib.rs:14-34). PT_LS_SPATIAL is SpatialLightDistribution (lightdistrib.rs:105-340): one
  * Distribution1D over ALL lights per voxel of a <= 64^3 grid. The reference fills a voxel on first touch (a lock-free hash,
  * lightdistrib.rs:249-337); a voxel's content is a pure function of the voxel, so WHEN it is filled cannot be observed. The library
@@ -400,6 +408,8 @@ typedef struct PtRenderParams {
      * sits in (CameraSample rays start in it, perspective.rs:114), PT_NONE for none; read only by PT_INTEGRATOR_VOLPATH. */
     uint32_t integrator;
     uint32_t camera_medium;
+    /* PtCameraType. 0 = perspective: a caller that zero-initialises the struct renders what it rendered before the field existed. */
+    uint32_t camera_type;
 } PtRenderParams;
 
 /* Device-side work counters: mirrors of the reference's stat counters
@@ -576,10 +586,15 @@ int pt_sobol_samples(const int32_t sample_bounds[4], uint32_t n, const int32_t *
 /* HaltonSampler (samplers/halton.rs:122-165): same contract, dimensions 0/1 are the offsets inside the pixel. */
 int pt_halton_samples(const int32_t sample_bounds[4], uint32_t sample_at_pixel_center, uint32_t n, const int32_t *pixel_xy,
                       const uint32_t *sample_num, uint32_t n_dims, float *out, uint64_t *out_index);
-/* PerspectiveCamera::generate_ray_differential main ray for n camera samples
- * (pfilm.xy, time, plens.xy) -> origin, direction (cameras/perspective.rs:120-179). */
+/* Camera::generate_ray_differential main ray of params->camera_type for n camera samples
+ * (pfilm.xy, time, plens.xy) -> origin, direction (cameras/perspective.rs:120-179, orthographic.rs:100-152, environment.rs:36-51). */
 int pt_camera_rays(const PtRenderParams *params, uint32_t n, const float *camera_samples,
                    float *out_origins, float *out_dirs);
+/* The auxiliary rays of the same camera samples as the shade kernels use them: after Transform::transform_ray and after
+ * Ray::scale_differential(1 / sqrt(spp)). out: 12 floats per sample (rx origin, rx direction, ry origin, ry direction);
+ * has[i] = 1 when the camera ray carries differentials (never under PT_CAMERA_ENVIRONMENT, whose 12 floats are 0). */
+int pt_camera_ray_differentials(const PtRenderParams *params, uint32_t n, const float *camera_samples,
+                                float *out, uint8_t *has);
 /* Distribution1D (core/sampling.rs:6-85) over func[n], built as the library builds the environment map's rows and the light
  * distributions; for each of n_u numbers u: discrete == 0: sample_continous (sampling.rs:38-64, the routine behind
  * InfiniteAreaLight::sample_li) -> out_x = the sampled value in [0,1), out_pdf, out_offset; discrete != 0: sample_discrete

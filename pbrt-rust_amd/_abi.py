@@ -26,6 +26,7 @@ PT_LS_UNIFORM, PT_LS_POWER, PT_LS_SPATIAL, PT_LS_SPATIAL_EAGER, PT_LS_SPATIAL_LA
 PT_SPLIT_SAH, PT_SPLIT_HLBVH = range(2)
 PT_SAMPLER_SOBOL, PT_SAMPLER_HALTON = range(2)
 PT_INTEGRATOR_PATH, PT_INTEGRATOR_VOLPATH = range(2)
+PT_CAMERA_PERSPECTIVE, PT_CAMERA_ORTHOGRAPHIC, PT_CAMERA_ENVIRONMENT = range(3)
 PT_QUADRIC_SPHERE, PT_QUADRIC_DISK = range(2)
 
 
@@ -126,7 +127,7 @@ class PtRenderParams(C.Structure):
                 ("raster_to_camera", f32 * 16), ("camera_to_world", f32 * 16), ("lens_radius", f32),
                 ("focal_distance", f32), ("shutter_open", f32), ("shutter_close", f32),
                 ("max_depth", u32), ("rr_threshold", f32), ("pixel_bounds", i32 * 4), ("light_strategy", u32),
-                ("tile_rank", u32), ("tile_world", u32), ("spp_per_pass", u32), ("profile", u32), ("sampler_type", u32), ("sample_at_pixel_center", u32), ("integrator", u32), ("camera_medium", u32)]
+                ("tile_rank", u32), ("tile_world", u32), ("spp_per_pass", u32), ("profile", u32), ("sampler_type", u32), ("sample_at_pixel_center", u32), ("integrator", u32), ("camera_medium", u32), ("camera_type", u32)]
 
 
 class PtCounters(C.Structure):
@@ -185,6 +186,7 @@ ENTRY_POINTS = {
     "pt_sobol_samples": (C.c_int, [i32p, u32, i32p, u32p, u32, fp, u64p]),
     "pt_halton_samples": (C.c_int, [i32p, u32, u32, i32p, u32p, u32, fp, u64p]),
     "pt_camera_rays": (C.c_int, [C.POINTER(PtRenderParams), u32, fp, fp, fp]),
+    "pt_camera_ray_differentials": (C.c_int, [C.POINTER(PtRenderParams), u32, fp, fp, C.POINTER(C.c_uint8)]),
     "pt_dist1d_sample": (C.c_int, [fp, u32, C.c_int, u32, fp, fp, fp, i32p]),
     "pt_test_ray_queue_push": (C.c_int, [u32, u32, u32, u8p, u32p, u32p, u32p, u32p]),
 }

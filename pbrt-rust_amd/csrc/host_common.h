@@ -218,6 +218,7 @@ void read_counters(pt_scene *sc);
 // The render frame: what pt_render_samples, pt_ao_render_samples (libmi355ao) and pt_multi_render_samples share. An integrator's geometry function is
 // frame_geometry, its own checks, its choice of a pass size, frame_pass_size -- and serves its render AND its pass-size query; its render is render_frame around its pass.
 using FrameStep = std::function<int()>;
+int check_camera(const PtRenderParams *rp);
 int check_spp(const PtRenderParams *rp);
 int check_sample_range(const PtRenderParams *rp, uint32_t first, uint32_t n);
 uint32_t tile_slots(const RenderConst &rc);

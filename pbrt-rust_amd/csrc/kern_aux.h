@@ -237,3 +237,15 @@ __global__ __launch_bounds__(256, PT_FILM_WAVES) void k_film_final(DeviceScene s
     counter_add(&counters->zero_num, zero_num);
     vertex_epilogue(s_hist, counters, &counters->shade_items[kMissClass], &counters->shade_bytes[kMissClass], n_final, n_bytes, n_assert);
 }
+// Parity entry (pt_camera_ray_differentials): the auxiliary rays the shade kernels compute for n camera samples (pfilm.xy, time, plens.xy), beside the main ray
+// they are scaled toward -- recomputed here by the same camera_ray_differentials. The main ray comes in as pt_camera_rays' kernel wrote it (main_o, main_d).
+__global__ void k_camera_ray_differentials(RenderConst rc, uint32_t n, const float *cs, const float *main_o, const float *main_d, float *out, uint8_t *has) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const RayDiff d = camera_ray_differentials(rc, cs[5 * i], cs[5 * i + 1], P2(cs[5 * i + 3], cs[5 * i + 4]),
+                                               V3(main_o[3 * i], main_o[3 * i + 1], main_o[3 * i + 2]), V3(main_d[3 * i], main_d[3 * i + 1], main_d[3 * i + 2]));
+    float *o = out + 12 * (size_t)i;
+    o[0] = d.rx_o.x; o[1] = d.rx_o.y; o[2] = d.rx_o.z; o[3] = d.rx_d.x; o[4] = d.rx_d.y; o[5] = d.rx_d.z;
+    o[6] = d.ry_o.x; o[7] = d.ry_o.y; o[8] = d.ry_o.z; o[9] = d.ry_d.x; o[10] = d.ry_d.y; o[11] = d.ry_d.z;
+    has[i] = d.has ? 1 : 0;
+}

@@ -17,6 +17,7 @@ __global__ void k_light_area(DeviceScene s, const uint32_t *head, float *area, f
 template <int NQ, int CAP> __global__ void k_route(DeviceScene s, const uint32_t *queue, const uint32_t *count_ptr, PathSoA ps, uint32_t *class_count, RouteJob rj);
 __global__ void k_split_rays(const uint32_t *rays, const uint32_t *count_ptr, uint32_t *mis, uint32_t *mis_count, uint32_t *shadow, uint32_t *shadow_count);
 __global__ void k_generate(RenderConst rc, SobolTables tabs, PathSoA ps, uint32_t *q_ext, uint32_t *q_ext_count, DevCounters *counters);
+template <int CAM> __global__ void k_generate_cam(RenderConst rc, SobolTables tabs, PathSoA ps, uint32_t *q_ext, uint32_t *q_ext_count, DevCounters *counters);
 __global__ void k_film(RenderConst rc, PathSoA ps, const float *filter_table, float *film_rgbw, DevCounters *counters);
 template <bool SPH> __global__ void k_film_final(DeviceScene s, RenderConst rc, PathSoA ps, const float *filter_table, float *film_rgbw, DevCounters *counters);
 __global__ void k_film_finish(const float *film_rgbw, float *film_xyzw, uint32_t npix);
@@ -33,4 +34,5 @@ __global__ void k_halton_samples(SobolTables tabs, HaltonParams hp, uint32_t n, 
 __global__ void k_sobol_samples(SobolTables tabs, SobolParams sp, uint32_t n, const int32_t *pixel_xy, const uint32_t *sample_num,
                                 uint32_t n_dims, float *out, uint64_t *out_index);
 __global__ void k_camera_rays(RenderConst rc, uint32_t n, const float *cs, float *out_o, float *out_d);
+__global__ void k_camera_ray_differentials(RenderConst rc, uint32_t n, const float *cs, const float *main_o, const float *main_d, float *out, uint8_t *has);   // kern_aux.h
 __global__ void k_dist1d_sample(const float *func, const float *cdf, float func_int, int n, int discrete, uint32_t n_u, const float *u, float *out_x, float *out_pdf, int32_t *out_off);

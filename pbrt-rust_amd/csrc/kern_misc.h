@@ -2,6 +2,7 @@
 #pragma once
 #include "kern_common.h"
 #include "kern_film.h"
+#include "kern_camera.h"
 // ---- scene preparation ---------------------------------------------------------------------------
 // Triangle packets in leaf order + the per-triangle "degenerate -> intersect() always fails" flag
 // (triangle.rs:254-261, evaluated once here instead of per accepted candidate).
@@ -132,125 +133,12 @@ __global__ __launch_bounds__(256) void k_split_rays(const uint32_t *rays, const 
     lq_flush_nosync(q_mis, mis_count, mis, 0u, true);
     lq_flush_nosync(q_sh, shadow_count, shadow, 0u, true);
 }
-// ---- camera rays -------------------------------------------------------------------------------------
-PT_DEV void camera_ray(const RenderConst &rc, float pfx, float pfy, float time_u, P2 plens_u, V3 &o, V3 &d) {  // perspective.rs:120-179
-    V3 pcamera = xf_point(rc.raster_to_camera, V3(pfx, pfy, 0.0f));
-    V3 ro(0.0f, 0.0f, 0.0f), rd = normalize(pcamera);
-    if (rc.lens_radius > 0.0f) {
-        P2 dsk = concentric_sample_disk(plens_u);
-        float lx = dsk.x * rc.lens_radius, ly = dsk.y * rc.lens_radius;
-        float ft = rc.focal_distance / rd.z;
-        V3 pfocus = ro + rd * ft;
-        ro = V3(lx, ly, 0.0f);
-        rd = normalize(pfocus - ro);
-    }
-    (void)time_u;  // ray.time = lerp(time, open, close) has no effect without animated transforms
-    // Transform::transform_ray (transform.rs:543-577)
-    V3 oerr;
-    V3 ow = xf_point_err(rc.camera_to_world, ro, oerr);
-    V3 dw = xf_vector(rc.camera_to_world, rd);
-    float l2 = length_squared(dw);
-    if (l2 > 0.0f) { float dt = dot(vabs(dw), oerr) / l2; ow = ow + dw * dt; }
-    o = ow; d = dw;
-}
-
-// A fresh path's core record (64 B) and ray record (32 B) are staged in LDS by the lane that computed them and written by the block
-// TRANSPOSED: thread t stores quad (t & 3) of path (t >> 2), so every store instruction of a wave covers 1 KB of consecutive HBM
-// (a lane writing its own record quad by quad strides 64 B between lanes: measured 2.5 TB/s against 3.6 TB/s for the old 4-byte arrays).
-// meta = dimension 5 after the camera sample, bounces 0, flags: camera ray.
-constexpr int kGenPlane = 257;   // quads per LDS plane (256 paths + 1: the four planes of a path land in different banks)
-struct GenStage { float4 core[4 * kGenPlane]; float4 ray[2 * kGenPlane]; uint32_t alive[256]; };
-PT_DEV void stage_path(GenStage &g, uint32_t t, float pfx, float pfy, V3 o, V3 d, uint64_t index, uint32_t medium) {
-    g.core[0 * kGenPlane + t] = make_float4(0.0f, 0.0f, 0.0f, 1.0f);                                               // L, etascale
-    g.core[1 * kGenPlane + t] = make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(5u | (PF_CAMERA_RAY << 24)));        // beta, meta
-    g.core[2 * kGenPlane + t] = make_float4(__uint_as_float((uint32_t)index), __uint_as_float((uint32_t)(index >> 32)), pfx, pfy);
-    g.core[3 * kGenPlane + t] = make_float4(__uint_as_float(medium), __uint_as_float(PT_NONE), 0.0f, 0.0f);        // medium (volpath: the camera's, perspective.rs:114), mis_medium
-    g.ray[0 * kGenPlane + t] = make_float4(o.x, o.y, o.z, d.x); g.ray[1 * kGenPlane + t] = make_float4(d.y, d.z, 0.0f, 0.0f);
-}
-PT_DEV void flush_paths(const GenStage &g, const PathSoA &ps, uint32_t pid0, uint32_t t) {   // all 256 threads; pid0 = first path id of the block's batch
-    float4 *core = reinterpret_cast<float4 *>(ps.core) + 4 * (size_t)pid0, *ray = reinterpret_cast<float4 *>(ps.ray) + 2 * (size_t)pid0;
-#pragma unroll
-    for (uint32_t j = 0; j < 4; ++j) { const uint32_t gq = j * 256u + t, p = gq >> 2, q = gq & 3u; if (g.alive[p]) core[gq] = g.core[q * kGenPlane + p]; }
-#pragma unroll
-    for (uint32_t j = 0; j < 2; ++j) { const uint32_t gq = j * 256u + t, p = gq >> 1, q = gq & 1u; if (g.alive[p]) ray[gq] = g.ray[q * kGenPlane + p]; }
-}
-
+// ---- camera rays: kern_camera.h (camera_ray<CAM>, stage_path / flush_paths, k_generate_cam<CAM>) -------------------------
+// The generate kernels: one body (kern_generate_body.h), one kernel per camera kind. The perspective job's kernel keeps its plain name and its instructions; the other
+// cameras run k_generate_cam<CAM> (render_loop.hip: generate_variant).
 __global__ __launch_bounds__(256) void k_generate(RenderConst rc, SobolTables tabs, PathSoA ps, uint32_t *q_ext, uint32_t *q_ext_count, DevCounters *counters) {
-    // LDS copies of what every lane needs, folded by NIBBLE of the word they are indexed with (the XORs of lowdiscrepancy.rs:512-569 regrouped, as in the shade
-    // kernels' Sobol' windows): the generator matrices of dimensions 0..4 (SobolTables::nib) and the two van-der-Corput matrices of m. A look-up per nibble
-    // replaces a count-trailing-zeros step per set bit -- the kernel issued vector instructions 99.7 % of its cycles, two thirds of them in those bit loops.
-    constexpr uint32_t kVdcNibbles = 13;   // 52 columns
-    __shared__ uint32_t s_nib[kSobolNibbles * 5 * 16];
-    __shared__ uint64_t s_vdc[2 * kVdcNibbles * 16];   // [M | MI][nibble][16]
-    __shared__ LdsQueue<1024> s_q;
-    __shared__ GenStage s_gen;
-    lq_init(s_q);
-    const uint32_t m = (uint32_t)rc.sobol.log2_resolution;
-    sobol_stage_lds(s_nib, tabs.nib, 5u, threadIdx.x, blockDim.x);
-    if (m > 0) for (uint32_t i = threadIdx.x; i < 2 * kVdcNibbles * 16; i += blockDim.x) {
-        const uint32_t which = i / (kVdcNibbles * 16), e = i - which * (kVdcNibbles * 16), j = e >> 4, n = e & 15u;
-        const uint64_t *col = (which ? tabs.vdc_inv : tabs.vdc) + (m - 1) * 52 + 4 * j;
-        uint64_t v = 0;
-        for (uint32_t b = 0; b < 4; ++b) if (n & (1u << b)) v ^= col[b];
-        s_vdc[i] = v;
-    }
-    __syncthreads();
-    const uint32_t total = rc.n_pix_slots * rc.s_count;
-    const uint32_t stride = gridDim.x * blockDim.x;
-    const uint32_t rounded = (total + 255u) & ~255u;   // whole blocks iterate together (block-level queue flushes)
-    unsigned long long n_alive = 0;
-    for (uint32_t pid = blockIdx.x * blockDim.x + threadIdx.x; pid < rounded; pid += stride) {
-        bool alive = false;
-        if (pid < total) {
-            const uint32_t slot = pid % rc.n_pix_slots, sl = pid / rc.n_pix_slots;
-            int32_t px, py;
-            if (slot_to_pixel(rc, slot, px, py)) {
-                const uint64_t sample = rc.s_begin + sl;
-                if (rc.halton.enabled) {   // HaltonSampler: same GlobalSampler bookkeeping, its own index and dimensions (halton.rs:122-165)
-                    const uint64_t index = halton_index_for_sample(rc.halton, px, py, sample);
-                    const float fx = halton_sample_dimension(tabs, rc.halton, index, 0u), fy = halton_sample_dimension(tabs, rc.halton, index, 1u);
-                    const float pfx = (float)px + fx, pfy = (float)py + fy;   // get_camera_sample: p_film = pixel + get_2d() (sampler.rs:170-180)
-                    const float tm = halton_sample_dimension(tabs, rc.halton, index, 2u);
-                    const P2 pl(halton_sample_dimension(tabs, rc.halton, index, 3u), halton_sample_dimension(tabs, rc.halton, index, 4u));
-                    V3 o, d;
-                    camera_ray(rc, pfx, pfy, tm, pl, o, d);
-                    stage_path(s_gen, threadIdx.x, pfx, pfy, o, d, index, rc.volpath ? rc.camera_medium : PT_NONE);
-                    alive = true;
-                } else {
-                // sobol_interval_to_index (lowdiscrepancy.rs:512-543) through the nibble tables
-                uint64_t index = 0;
-                if (m != 0) {
-                    index = sample << (m << 1);
-                    uint64_t delta = 0;
-                    for (uint64_t f = sample, j = 0; f != 0; f >>= 4, ++j) delta ^= s_vdc[j * 16 + (f & 15u)];
-                    uint64_t b = ((uint64_t)((uint32_t)(px - rc.sobol.sb_min[0]) << m) | (uint64_t)(uint32_t)(py - rc.sobol.sb_min[1])) ^ delta;
-                    for (uint32_t j = 0; b != 0; b >>= 4, ++j) index ^= s_vdc[kVdcNibbles * 16 + j * 16 + (b & 15u)];
-                }
-                // get_camera_sample (sampler.rs:170-180): pfilm = get_2d, time = get_1d, plens = get_2d
-                const uint32_t v0 = sobol_bits_nib(s_nib, 5u * 16u, tabs.m32, index), v1 = sobol_bits_nib(s_nib + 16, 5u * 16u, tabs.m32 + 52, index), v2 = sobol_bits_nib(s_nib + 32, 5u * 16u, tabs.m32 + 104, index),
-                               v3 = sobol_bits_nib(s_nib + 48, 5u * 16u, tabs.m32 + 156, index), v4 = sobol_bits_nib(s_nib + 64, 5u * 16u, tabs.m32 + 208, index);
-                // sobol.rs:77-81: film dimensions are remapped to the pixel
-                float fx = sobol_to_float(v0) * (float)rc.sobol.resolution + (float)rc.sobol.sb_min[0];
-                fx = clampf(fx - (float)px, 0.0f, kOneMinusEps);
-                float fy = sobol_to_float(v1) * (float)rc.sobol.resolution + (float)rc.sobol.sb_min[1];
-                fy = clampf(fy - (float)py, 0.0f, kOneMinusEps);
-                const float pfx = (float)px + fx, pfy = (float)py + fy;
-                V3 o, d;
-                camera_ray(rc, pfx, pfy, sobol_to_float(v2), P2(sobol_to_float(v3), sobol_to_float(v4)), o, d);
-                stage_path(s_gen, threadIdx.x, pfx, pfy, o, d, index, rc.volpath ? rc.camera_medium : PT_NONE);
-                alive = true;
-                }
-            }
-        }
-        s_gen.alive[threadIdx.x] = alive ? 1u : 0u;
-        __syncthreads();
-        flush_paths(s_gen, ps, pid - threadIdx.x, threadIdx.x);   // (the queue flush below holds the barrier that protects s_gen for the next round)
-        lq_push(s_q, pid, alive);
-        lq_sync_flush(s_q, q_ext_count, q_ext, 256u, false);
-        n_alive += alive ? 1ull : 0ull;
-    }
-    lq_sync_flush(s_q, q_ext_count, q_ext, 0u, true);
-    counter_add(&counters->camera_rays, n_alive);
+    constexpr int CAM = PT_CAMERA_PERSPECTIVE;
+#include "kern_generate_body.h"
 }
 // ---- film: kern_film.h (film_slot) -------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_film(RenderConst rc, PathSoA ps, const float *filter_table, float *film_rgbw, DevCounters *counters) {
@@ -386,7 +274,10 @@ __global__ void k_camera_rays(RenderConst rc, uint32_t n, const float *cs, float
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     V3 o, d;
-    camera_ray(rc, cs[5 * i], cs[5 * i + 1], cs[5 * i + 2], P2(cs[5 * i + 3], cs[5 * i + 4]), o, d);
+    const P2 pl(cs[5 * i + 3], cs[5 * i + 4]);
+    if (rc.camera_type == PT_CAMERA_ORTHOGRAPHIC) camera_ray<PT_CAMERA_ORTHOGRAPHIC>(rc, cs[5 * i], cs[5 * i + 1], cs[5 * i + 2], pl, o, d);
+    else if (rc.camera_type == PT_CAMERA_ENVIRONMENT) camera_ray<PT_CAMERA_ENVIRONMENT>(rc, cs[5 * i], cs[5 * i + 1], cs[5 * i + 2], pl, o, d);
+    else camera_ray<PT_CAMERA_PERSPECTIVE>(rc, cs[5 * i], cs[5 * i + 1], cs[5 * i + 2], pl, o, d);
     out_o[3 * i] = o.x; out_o[3 * i + 1] = o.y; out_o[3 * i + 2] = o.z;
     out_d[3 * i] = d.x; out_d[3 * i + 1] = d.y; out_d[3 * i + 2] = d.z;
 }

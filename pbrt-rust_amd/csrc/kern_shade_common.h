@@ -370,14 +370,42 @@ struct TexMatEval {
     PT_DEV RGB spec(const PtMaterial &m, int slot, const float *field) const { return m.tex[slot] >= 0 ? tex_eval(s, m.tex[slot], c) : RGB(field[0], field[1], field[2]); }
     PT_DEV float flt(const PtMaterial &m, int slot, float field) const { return m.tex[slot] >= 0 ? tex_eval(s, m.tex[slot], c).r : field; }
 };
-// The auxiliary rays of PerspectiveCamera::generate_ray_differential (perspective.rs:143-176) after transform_ray
-// (transform.rs:565-575) and Ray::scale_differential(1 / sqrt(spp)) (ray.rs:34-41, integrator.rs:340), recomputed from the
-// film position (and the lens sample, Sobol' dimensions 3 and 4) instead of being carried in the path state.
+// The auxiliary rays of the camera's generate_ray_differential after transform_ray (transform.rs:565-575: no error offset on the auxiliary
+// origins) and Ray::scale_differential(1 / sqrt(spp)) (ray.rs:34-41, integrator.rs:340), recomputed from the film position (and the lens
+// sample, dimensions 3 and 4) instead of being carried in the path state. rc.camera_type is uniform over the launch; the code runs in the
+// textured variants only, on camera rays.
+//   perspective (perspective.rs:143-176)   as before
+//   orthographic (orthographic.rs:123-152) no lens: both auxiliary origins are the main one shifted by dx_camera / dy_camera, both directions the main one.
+//       With a lens both origins are the lens point and the directions aim at pcamera + d{x,y}_camera + (0,0,z) * ft, where ft is taken from the ALREADY
+//       lens-modified direction's z (:130) and z is 1 for x but 0.1 for y (:135, as written there). Reproduced, not corrected.
+//   environment   none: EnvironmentCamera has no generate_ray_differential; the trait's default (core/camera.rs:43-97) writes into rd.diff only when
+//       generate_ray left one there, and it leaves None. has = false: the first vertex filters its textures as every later one does.
 PT_DEV RayDiff camera_ray_differentials(const RenderConst &rc, float pfx, float pfy, P2 plens_u, V3 ray_o, V3 ray_d) {
+    RayDiff d; d.has = true;
+    if (rc.camera_type == PT_CAMERA_ENVIRONMENT) {
+        d.has = false;
+        d.rx_o = d.rx_d = d.ry_o = d.ry_d = V3(0.0f, 0.0f, 0.0f);
+        return d;
+    }
     const V3 pcamera = xf_point(rc.raster_to_camera, V3(pfx, pfy, 0.0f));
     const V3 dxc(rc.dx_camera[0], rc.dx_camera[1], rc.dx_camera[2]), dyc(rc.dy_camera[0], rc.dy_camera[1], rc.dy_camera[2]);
-    RayDiff d; d.has = true;
-    if (rc.lens_radius > 0.0f) {
+    if (rc.camera_type == PT_CAMERA_ORTHOGRAPHIC) {
+        if (rc.lens_radius > 0.0f) {
+            const P2 dk = concentric_sample_disk(plens_u);
+            const V3 plens(dk.x * rc.lens_radius, dk.y * rc.lens_radius, 0.0f);
+            // the main ray's direction as generate_ray_differential has it by then (orthographic.rs:109-121)
+            const V3 pf0 = pcamera + V3(0.0f, 0.0f, 1.0f) * (rc.focal_distance / 1.0f);
+            const V3 dmain = normalize(pf0 - plens);
+            const float ft = rc.focal_distance / dmain.z;                          // orthographic.rs:130
+            V3 pfocus = pcamera + dxc + V3(0.0f, 0.0f, 1.0f) * ft;                 // orthographic.rs:131
+            d.rx_o = plens; d.rx_d = normalize(pfocus - plens);
+            pfocus = pcamera + dyc + V3(0.0f, 0.0f, 0.1f) * ft;                    // orthographic.rs:135
+            d.ry_o = plens; d.ry_d = normalize(pfocus - plens);
+        } else {
+            d.rx_o = pcamera + dxc; d.ry_o = pcamera + dyc;                        // orthographic.rs:140-143
+            d.rx_d = V3(0.0f, 0.0f, 1.0f); d.ry_d = V3(0.0f, 0.0f, 1.0f);
+        }
+    } else if (rc.lens_radius > 0.0f) {
         const P2 dk = concentric_sample_disk(plens_u);
         const float lx = dk.x * rc.lens_radius, ly = dk.y * rc.lens_radius;
         const V3 dx = normalize(pcamera + dxc);

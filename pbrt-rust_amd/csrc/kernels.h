@@ -166,14 +166,21 @@ struct RenderConst {
     SobolParams sobol;
     HaltonParams halton;
     M4 raster_to_camera, camera_to_world;
-    float lens_radius, focal_distance, shutter_open, shutter_close;
-    float dx_camera[3], dy_camera[3];  // perspective.rs:64-70
+    float lens_radius, focal_distance;
+    uint32_t camera_type;             // PtCameraType: which k_generate form runs (render_loop.hip: generate_variant); camera_ray_differentials switches on it
+    uint32_t reserved0;               // (camera_type and this word stand where the shutter times stood, which no kernel read: ray.time has no effect without animated
+                                      // transforms. The struct keeps its size and every other field its place, so the perspective job's kernels are the code they were.)
+    float dx_camera[3], dy_camera[3];  // perspective.rs:64-70: differences of two transformed points; orthographic.rs:55-56: raster_to_camera on the vectors (1,0,0) / (0,1,0).
+                                       // PT_CAMERA_ENVIRONMENT has neither: dx_camera[0..1] hold Film::full_resolution as floats (full_res below) -- its angles
+                                       // (environment.rs:38-39) are taken over the FULL frame, not the crop window. (Not a union: with one in it the struct is another type to
+                                       // the compiler, and k_generate came out as other instructions.)
     float inv_sqrt_spp;                // Ray::scale_differential factor (integrator.rs:340)
     uint32_t max_depth; float rr_threshold;
     uint32_t volpath, camera_medium;   // VolPathIntegrator (volpath.rs) instead of PathIntegrator; the camera's medium
     float filter_radius[2]; float max_sample_luminance;
     uint32_t film_w, film_h;
     const uint32_t *tile_list;        // pt_render_tiles: tile slot i renders tile tile_list[i] (device, n_tile_slots entries, ascending); NULL: tile_rank + i * tile_world
+    PT_HD float full_res(int i) const { return dx_camera[i]; }   // PT_CAMERA_ENVIRONMENT only
 };
 
 // One kind of ray of a traversal launch: where its rays come from and where its results go.

@@ -89,6 +89,7 @@ int pt_multi_render(pt_multi_scene *ms, const PtRenderParams *rp, float *film_xy
 // Every replica renders sample numbers [first, first + n) of its tiles (pt_render_samples)
 int pt_multi_render_samples(pt_multi_scene *ms, const PtRenderParams *rp, uint32_t first, uint32_t n_samples, float *film_xyzw, int film_is_device) {
     if (!ms || !rp || !film_xyzw || ms->sc.empty()) return fail(PT_ERR_INVALID_ARG, "null argument");
+    if (int cst = check_camera(rp)) return cst;
     if (int rst = check_sample_range(rp, first, n_samples)) return rst;   // (before a device is touched)
     const int home = g_device;
     const uint32_t n = (uint32_t)ms->sc.size();

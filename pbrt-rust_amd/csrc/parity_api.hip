@@ -110,7 +110,9 @@ int pt_halton_samples(const int32_t sb[4], uint32_t sample_at_pixel_center, uint
 int pt_camera_rays(const PtRenderParams *rp, uint32_t n, const float *cs, float *out_o, float *out_d) {
     DevTmp scratch;
     if (!rp || !cs || !out_o || !out_d) return fail(PT_ERR_INVALID_ARG, "null argument");
-    int st = ensure_device();
+    int st = check_camera(rp);
+    if (st) return st;
+    st = ensure_device();
     if (st || n == 0) return st;
     RenderConst rc; fill_render_const(rp, rc);
     float *dcs, *dout;
@@ -120,6 +122,26 @@ int pt_camera_rays(const PtRenderParams *rp, uint32_t n, const float *cs, float 
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out_o, dout, (size_t)n * 12, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(out_d, dout + 3 * (size_t)n, (size_t)n * 12, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+int pt_camera_ray_differentials(const PtRenderParams *rp, uint32_t n, const float *cs, float *out, uint8_t *has) {
+    DevTmp scratch;
+    if (!rp || !cs || !out || !has) return fail(PT_ERR_INVALID_ARG, "null argument");
+    int st = check_camera(rp);
+    if (st) return st;
+    if (rp->spp == 0) return fail(PT_ERR_INVALID_ARG, "spp must be > 0 (the differentials are scaled by 1 / sqrt(spp))");
+    st = ensure_device();
+    if (st || n == 0) return st;
+    RenderConst rc; fill_render_const(rp, rc);
+    float *dcs, *dmain, *dout; uint8_t *dhas;
+    HIP_TRY(scratch.alloc(&dcs, (size_t)n * 20)); HIP_TRY(scratch.alloc(&dmain, (size_t)n * 24)); HIP_TRY(scratch.alloc(&dout, (size_t)n * 48)); HIP_TRY(scratch.alloc(&dhas, (size_t)n + 4));
+    HIP_TRY(hipMemcpy(dcs, cs, (size_t)n * 20, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_camera_rays, dim3((n + 255) / 256), dim3(256), 0, 0, rc, n, dcs, dmain, dmain + 3 * (size_t)n);   // the main rays the differentials are scaled toward
+    hipLaunchKernelGGL(k_camera_ray_differentials, dim3((n + 255) / 256), dim3(256), 0, 0, rc, n, dcs, dmain, dmain + 3 * (size_t)n, dout, dhas);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, dout, (size_t)n * 48, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(has, dhas, (size_t)n, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 

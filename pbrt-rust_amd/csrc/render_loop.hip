@@ -65,6 +65,14 @@ static const FilmFinalVariant &film_final_variant(bool sph) { static const FilmF
 static const TouchVariant &touch_variant(bool sph) { static const TouchVariant t[2] = {touch_inst<false>(), touch_inst<true>()}; return t[sph]; }
 static const RouteVariant &route_variant(uint32_t n_slots) { static const RouteVariant t[2] = {route_inst<6, 2048>(), route_inst<12, 1024>()}; return t[n_slots > 6]; }
 
+// k_generate and, for the cameras beside the perspective one, k_generate_cam<CAM> (tu_misc.hip): one row per PtCameraType. The perspective job launches the plain kernel.
+using GenerateVariant = Variant<RenderConst, SobolTables, PathSoA, uint32_t *, uint32_t *, DevCounters *>;
+static const GenerateVariant &generate_variant(uint32_t camera_type) {
+    static const GenerateVariant t[3] = {{k_generate, "k_generate"}, {k_generate_cam<PT_CAMERA_ORTHOGRAPHIC>, symbol("k_generate_cam", (int)PT_CAMERA_ORTHOGRAPHIC)},
+                                         {k_generate_cam<PT_CAMERA_ENVIRONMENT>, symbol("k_generate_cam", (int)PT_CAMERA_ENVIRONMENT)}};
+    return t[camera_type];   // (check_camera: <= 2)
+}
+
 template <int MAXL, int DIFF> void launch_shade(pt_scene *sc, const RenderConst &rc, const LightGrid &grid, const ShadeJob &job, uint32_t upper) {
     const int mode = rc.volpath ? 3 : sc->ds.n_textures > 0 ? 2 : (general_geometry(sc) || rc.halton.enabled) ? 1 : 0;   // kern_shade.h: k_shade MODE
     launch(sc, shade_variant<MAXL, DIFF>(mode), blocks_for(upper, PT_SHADE_BLOCKS_PER_CU), dim3(256), sc->ds, rc, g_tabs, grid, sc->ps, job);   // persistent blocks: the LDS Sobol' table is staged once per block
@@ -311,14 +319,20 @@ void fill_render_const(const PtRenderParams *rp, RenderConst &rc) {
     std::memcpy(rc.raster_to_camera.m, rp->raster_to_camera, 64);
     std::memcpy(rc.camera_to_world.m, rp->camera_to_world, 64);
     rc.lens_radius = rp->lens_radius; rc.focal_distance = rp->focal_distance;
-    {   // PerspectiveCamera::new (perspective.rs:64-70): dx_camera / dy_camera
+    rc.camera_type = rp->camera_type;
+    rc.inv_sqrt_spp = 1.0f / std::sqrt((float)rp->spp);
+    if (rp->camera_type == PT_CAMERA_ENVIRONMENT) {   // no raster_to_camera (the field is not read), no dx_camera: RenderConst::full_res in its place. environment.rs:38-39: `full_resolution.x as Float`
+        rc.raster_to_camera = M4{};
+        rc.dx_camera[0] = (float)rp->full_resolution[0]; rc.dx_camera[1] = (float)rp->full_resolution[1];
+    } else {   // dx_camera / dy_camera. PerspectiveCamera::new (perspective.rs:64-70): differences of transformed POINTS; OrthographicCamera::new (orthographic.rs:55-56):
+               // raster_to_camera on the VECTORS (1,0,0) and (0,1,0)
+        const bool ortho = rp->camera_type == PT_CAMERA_ORTHOGRAPHIC;
         const V3 p2t = xf_point(rc.raster_to_camera, V3(0.0f, 0.0f, 0.0f));
-        const V3 dx = xf_point(rc.raster_to_camera, V3(1.0f, 0.0f, 0.0f)) - p2t, dy = xf_point(rc.raster_to_camera, V3(0.0f, 1.0f, 0.0f)) - p2t;
+        const V3 dx = ortho ? xf_vector(rc.raster_to_camera, V3(1.0f, 0.0f, 0.0f)) : xf_point(rc.raster_to_camera, V3(1.0f, 0.0f, 0.0f)) - p2t;
+        const V3 dy = ortho ? xf_vector(rc.raster_to_camera, V3(0.0f, 1.0f, 0.0f)) : xf_point(rc.raster_to_camera, V3(0.0f, 1.0f, 0.0f)) - p2t;
         rc.dx_camera[0] = dx.x; rc.dx_camera[1] = dx.y; rc.dx_camera[2] = dx.z;
         rc.dy_camera[0] = dy.x; rc.dy_camera[1] = dy.y; rc.dy_camera[2] = dy.z;
-        rc.inv_sqrt_spp = 1.0f / std::sqrt((float)rp->spp);
     }
-    rc.shutter_open = rp->shutter_open; rc.shutter_close = rp->shutter_close;
     rc.max_depth = rp->max_depth; rc.rr_threshold = rp->rr_threshold;
     rc.volpath = rp->integrator == PT_INTEGRATOR_VOLPATH ? 1u : 0u; rc.camera_medium = rc.volpath ? rp->camera_medium : PT_NONE;
     rc.filter_radius[0] = rp->filter_radius[0]; rc.filter_radius[1] = rp->filter_radius[1];
@@ -658,7 +672,13 @@ void read_counters(pt_scene *sc) {
 }
 
 // ---- the render frame (host_common.h): what every integrator's render does before, around and after its passes
-int check_spp(const PtRenderParams *rp) { return rp->spp == 0 ? fail(PT_ERR_INVALID_ARG, "spp must be > 0") : PT_OK; }
+// The camera of a PtRenderParams, for every entry point that takes one (the renders through check_spp, the parity entries themselves): host arithmetic, before the device is touched
+int check_camera(const PtRenderParams *rp) {
+    if (rp->camera_type > PT_CAMERA_ENVIRONMENT) return fail(PT_ERR_INVALID_ARG, "camera_type " + std::to_string(rp->camera_type) + ": PT_CAMERA_PERSPECTIVE (0), PT_CAMERA_ORTHOGRAPHIC (1) and PT_CAMERA_ENVIRONMENT (2) run here");
+    if (rp->camera_type == PT_CAMERA_ENVIRONMENT && (rp->full_resolution[0] <= 0 || rp->full_resolution[1] <= 0)) return fail(PT_ERR_INVALID_ARG, "the environment camera takes its angles over full_resolution, which must be > 0");
+    return PT_OK;
+}
+int check_spp(const PtRenderParams *rp) { if (int st = check_camera(rp)) return st; return rp->spp == 0 ? fail(PT_ERR_INVALID_ARG, "spp must be > 0") : PT_OK; }   // (every render's first check: the camera rides with it)
 // The range [first, first + n) of a job of rp->spp samples per pixel (pt_render_samples, pt_ao_render_samples, pt_multi_render_samples): host arithmetic, the sum in 64 bits
 int check_sample_range(const PtRenderParams *rp, uint32_t first, uint32_t n) {
     if (n == 0) return fail(PT_ERR_INVALID_ARG, "n_samples must be > 0");
@@ -742,7 +762,7 @@ int render_frame(pt_scene *sc, const PtRenderParams *rp, RenderConst &rc, uint32
         rc.s_begin = s0; rc.s_count = std::min(S, end - s0);
         HIP_TRY(hipMemsetAsync(sc->qc, 0, offsetof(QCounters, error), sc->stream));
         sc->begin("generate", (uint64_t)rc.n_pix_slots * rc.s_count);   // SamplerIntegrator::render's camera rays (integrator.rs:331-340): every integrator's pass starts from them
-        launch(sc, "k_generate", k_generate, blocks_for(rc.n_pix_slots * rc.s_count, PT_GEN_BLOCKS_PER_CU), dim3(256), rc, g_tabs, sc->ps, sc->q.ext[0], &sc->qc->ext[0], sc->dc);
+        launch(sc, generate_variant(rc.camera_type), blocks_for(rc.n_pix_slots * rc.s_count, PT_GEN_BLOCKS_PER_CU), dim3(256), rc, g_tabs, sc->ps, sc->q.ext[0], &sc->qc->ext[0], sc->dc);
         sc->end();
         if ((st = pass())) return st;
     }

@@ -115,6 +115,9 @@ struct Transform {
         c2w.m[0][2] = dir.x; c2w.m[1][2] = dir.y; c2w.m[2][2] = dir.z; c2w.m[3][2] = 0.0f;
         return Transform(mat_inverse(c2w), c2w);
     }
+    static Transform orthographic(float znear, float zfar) {  // transform.rs:395-397
+        return scale(1.0f, 1.0f, 1.0f / (zfar - znear)) * translate(Vec3{0.0f, 0.0f, -znear});
+    }
     static Transform perspective(float fov, float n, float f) {  // transform.rs:399-411
         Mat4 p;
         p.m[2][2] = f / (f - n); p.m[2][3] = -f * n / (f - n); p.m[3][2] = 1.0f; p.m[3][3] = 0.0f;

@@ -5,9 +5,9 @@
 //   coordinate systems), :1329-1460 (Camera/Film/Sampler/PixelFilter/Integrator options), :1462-1619 (LightSource,
 //   AreaLightSource, Shape: one GeometricPrimitive per triangle / sphere, one DiffuseAreaLight per emissive shape),
 //   :1630-1713 (ObjectBegin/End/Instance), :1715-1748 (WorldEnd), core/paramset.rs:500-600 (texture-or-constant lookups),
-//   cameras/perspective.rs:40-86,298-356, core/film.rs:55-112,364-398, filters/*.rs, lights/*.rs create_* functions,
+//   cameras/perspective.rs:40-86,298-356, cameras/orthographic.rs:40-59,154-207, cameras/environment.rs:54-100, core/film.rs:55-112,364-398, filters/*.rs, lights/*.rs create_* functions,
 //   materials/*.rs create_* functions, shapes/{triangle.rs:700-760, sphere.rs:424-431, plymesh.rs}.
-// Out of scope here (an error names the directive): other cameras / samplers / integrators than perspective / sobol, halton / path, volpath, ambientocclusion,
+// Out of scope here (an error names the directive): the "realistic" camera, other samplers / integrators than sobol, halton / path, volpath, ambientocclusion,
 // spectral (non-RGB) parameters, image formats other than those of fe_imageio.h (PFM, Radiance HDR, PNG, TGA, EXR), per-shape material parameter
 // overrides, animated transforms (ActiveTransform / TransformTimes are accepted and ignored for static scenes).
 #include "../../include/mi355pt.h"
@@ -570,7 +570,9 @@ static void filter_table(const std::string &name, const ParamSet &p, float radiu
 }
 
 static void finish(Scene &sc, const Api &api) {
-    if (sc.camera_name != "perspective") throw std::runtime_error("camera \"" + sc.camera_name + "\": only \"perspective\" runs on this back end");
+    // core/api.rs:832-836 minus "realistic" (lens files, exit-pupil tables and a lens-tracing loop of its own)
+    const uint32_t camera_type = sc.camera_name == "perspective" ? PT_CAMERA_PERSPECTIVE : sc.camera_name == "orthographic" ? PT_CAMERA_ORTHOGRAPHIC : sc.camera_name == "environment" ? PT_CAMERA_ENVIRONMENT : ~0u;
+    if (camera_type == ~0u) throw std::runtime_error("camera \"" + sc.camera_name + "\": \"perspective\", \"orthographic\" and \"environment\" run on this back end");
     if (sc.sampler != "sobol" && sc.sampler != "halton") throw std::runtime_error("sampler \"" + sc.sampler + "\": only \"sobol\" and \"halton\" run on this back end (the path depends on the GlobalSampler dimension bookkeeping)");
     PtSceneDesc &d = sc.desc; d = PtSceneDesc{};
     d.n_vertices = (uint32_t)(sc.P.size() / 3); d.P = sc.P.data();
@@ -608,15 +610,22 @@ static void finish(Scene &sc, const Api &api) {
     int sb[4] = {(int)std::floor((float)crop[0] + 0.5f - rx), (int)std::floor((float)crop[1] + 0.5f - ry), (int)std::ceil((float)crop[2] - 0.5f + rx), (int)std::ceil((float)crop[3] - 0.5f + ry)};   // film.rs:104-112
     for (int i = 0; i < 4; ++i) rp.sample_bounds[i] = sb[i];
     const ParamSet &cp = sc.camera_params;
-    float so = cp.one_float("shutteropen", 0.0f), scl = cp.one_float("shutterclose", 1.0f); if (scl < so) std::swap(so, scl);
+    // create_perspective_camera (perspective.rs:298-356), create_orthographic_camera (orthographic.rs:154-207), create_environment_camera (environment.rs:54-100): the
+    // same parameters, read the same way; the shutter defaults differ (0/1, 0/0, 1/1), and the environment camera reads everything after them only to ignore it.
+    const float so_default = camera_type == PT_CAMERA_ENVIRONMENT ? 1.0f : 0.0f, sc_default = camera_type == PT_CAMERA_PERSPECTIVE ? 1.0f : so_default;
+    float so = cp.one_float("shutteropen", so_default), scl = cp.one_float("shutterclose", sc_default); if (scl < so) std::swap(so, scl);
     const float frame = cp.one_float("frameaspectratio", (float)sc.xres / (float)sc.yres);
     float sw[4]; if (frame > 1.0f) { sw[0] = -frame; sw[1] = frame; sw[2] = -1.0f; sw[3] = 1.0f; } else { sw[0] = -1.0f; sw[1] = 1.0f; sw[2] = -1.0f / frame; sw[3] = 1.0f / frame; }
     if (const std::vector<float> *w = cp.floats("float", "screenwindow")) if (w->size() == 4) for (int i = 0; i < 4; ++i) sw[i] = (*w)[i];
-    float fov = cp.one_float("fov", 90.0f); const float halffov = cp.one_float("halffov", -1.0f); if (halffov > 0.5f) fov = 2.0f * halffov;
-    const Transform c2s = Transform::perspective(fov, 1e-2f, 1000.0f);
-    const Transform s2r = Transform::scale((float)sc.xres, (float)sc.yres, 1.0f) * Transform::scale(1.0f / (sw[1] - sw[0]), 1.0f / (sw[2] - sw[3]), 1.0f) * Transform::translate(v3(-sw[0], -sw[3], 0.0f));
-    const Transform r2c = c2s.inverse() * s2r.inverse();
-    r2c.flat(rp.raster_to_camera); sc.camera_to_world.flat(rp.camera_to_world);
+    rp.camera_type = camera_type;
+    if (camera_type != PT_CAMERA_ENVIRONMENT) {   // ProjectiveCamera: raster_to_camera = inverse(camera_to_screen) * raster_to_screen (perspective.rs:40-62, orthographic.rs:40-53)
+        float fov = cp.one_float("fov", 90.0f); const float halffov = cp.one_float("halffov", -1.0f); if (halffov > 0.5f) fov = 2.0f * halffov;
+        const Transform c2s = camera_type == PT_CAMERA_ORTHOGRAPHIC ? Transform::orthographic(0.0f, 1.0f) : Transform::perspective(fov, 1e-2f, 1000.0f);
+        const Transform s2r = Transform::scale((float)sc.xres, (float)sc.yres, 1.0f) * Transform::scale(1.0f / (sw[1] - sw[0]), 1.0f / (sw[2] - sw[3]), 1.0f) * Transform::translate(v3(-sw[0], -sw[3], 0.0f));
+        const Transform r2c = c2s.inverse() * s2r.inverse();
+        r2c.flat(rp.raster_to_camera);
+    }   // (the environment camera has no raster_to_camera: the field stays zero, the library does not read it)
+    sc.camera_to_world.flat(rp.camera_to_world);
     rp.lens_radius = cp.one_float("lensradius", 0.0f); rp.focal_distance = cp.one_float("focaldistance", 1.0e30f); rp.shutter_open = so; rp.shutter_close = scl;
     rp.max_depth = (uint32_t)sc.maxdepth; rp.rr_threshold = sc.rr_threshold;
     rp.integrator = sc.ao ? PT_INTEGRATOR_AO : sc.volpath ? PT_INTEGRATOR_VOLPATH : PT_INTEGRATOR_PATH; rp.camera_medium = sc.camera_medium < 0 ? PT_NONE : (uint32_t)sc.camera_medium;
@@ -697,6 +706,7 @@ int ptf_read_image(const char *path, int *width, int *height, float *rgb, size_t
     return PT_OK;
 }
 // ---- checkpoints of range renders (mi355front.h: PtfCheckpointHeader) ----
+// (the whole struct is hashed, camera_type with it: a checkpoint written under one camera refuses to resume under another)
 uint64_t ptf_params_hash(const PtRenderParams *params, const PtAOParams *ao) {
     uint64_t h = 1469598103934665603ull;
     auto eat = [&](const void *p, size_t n) { for (size_t i = 0; i < n; ++i) { h ^= ((const unsigned char *)p)[i]; h *= 1099511628211ull; } };

@@ -14,6 +14,7 @@ from . import _abi as A
 from . import _abi_ao as AO
 
 F = np.float32
+CAMERA_KINDS = {"perspective": A.PT_CAMERA_PERSPECTIVE, "orthographic": A.PT_CAMERA_ORTHOGRAPHIC, "environment": A.PT_CAMERA_ENVIRONMENT}
 
 
 class Transform:
@@ -97,6 +98,10 @@ class Transform:
         c2w = np.eye(4, dtype=F)
         c2w[:3, 0] = right; c2w[:3, 1] = new_up; c2w[:3, 2] = d; c2w[:3, 3] = pos
         return Transform(np.linalg.inv(c2w.astype(np.float64)).astype(F), c2w)
+
+    @staticmethod
+    def orthographic(znear, zfar):  # transform.rs:395-397
+        return Transform.scale(1, 1, F(1) / (F(zfar) - F(znear))) * Transform.translate((0, 0, -F(znear)))
 
     @staticmethod
     def perspective(fov, n, f):  # transform.rs:399-411
@@ -224,7 +229,7 @@ class SceneBuilder:
         # options block defaults (api.rs:215-241, film.rs:364-398, sobol.rs:120, path.rs:228-249)
         self.film = dict(xres=1280, yres=720, crop=(0.0, 1.0, 0.0, 1.0), scale=1.0, max_lum=float("inf"))
         self.filter = dict(kind="box", radius=(0.5, 0.5), alpha=2.0)
-        self.cam = dict(fov=90.0, lensradius=0.0, focaldistance=1e6, shutteropen=0.0, shutterclose=1.0, c2w=Transform())
+        self.cam = dict(kind="perspective", fov=90.0, lensradius=0.0, focaldistance=1e6, shutteropen=0.0, shutterclose=1.0, screenwindow=None, frameaspectratio=None, c2w=Transform())
         self.spp = 16
         self.sampler = "sobol"          # "sobol" | "halton" (Sampler directive; the reference's default is halton, api.rs:215-241)
         self.sample_at_pixel_center = False
@@ -291,8 +296,19 @@ class SceneBuilder:
         self.prim_med_out.append(np.full(n, none if mo is None else mo, dtype=np.uint32))
 
     # -- options
-    def camera(self, fov=90.0, lensradius=0.0, focaldistance=1e6):
-        self.cam.update(fov=fov, lensradius=lensradius, focaldistance=focaldistance, c2w=self.ctm.inverse())  # api.rs:1208
+    def camera(self, kind="perspective", fov=90.0, lensradius=0.0, focaldistance=None, screenwindow=None, frameaspectratio=None, shutteropen=None, shutterclose=None):
+        """Camera "perspective" | "orthographic" | "environment" (api.rs:832-836 minus "realistic"). What is not given takes the reference's default for the kind
+        (create_*_camera): shutter 0/1, 0/0, 1/1, swapped when reversed; focaldistance 1e30 for the two new kinds (this builder's perspective default stays 1e6);
+        screenwindow from frameaspectratio, that from the film. The environment camera takes all of them and uses none."""
+        if kind not in CAMERA_KINDS:
+            raise ValueError(f'camera "{kind}": "perspective", "orthographic" and "environment" run on this back end')
+        so_default = 1.0 if kind == "environment" else 0.0
+        so = so_default if shutteropen is None else shutteropen
+        sc = (1.0 if kind == "perspective" else so_default) if shutterclose is None else shutterclose
+        if sc < so: so, sc = sc, so
+        if focaldistance is None: focaldistance = 1e6 if kind == "perspective" else 1e30
+        self.cam.update(kind=kind, fov=fov, lensradius=lensradius, focaldistance=focaldistance, shutteropen=so, shutterclose=sc,
+                        screenwindow=screenwindow, frameaspectratio=frameaspectratio, c2w=self.ctm.inverse())  # api.rs:1208
         self.camera_medium = self._medium_index(self.medium_outside)   # provisional (what pbrt-v3 does); world_end() takes the state at WorldEnd as api.rs:1738-1741 does
 
     def world_begin(self): self.ctm = Transform()
@@ -609,15 +625,22 @@ class SceneBuilder:
         sb = [math.floor(F(crop[0]) + F(0.5) - F(rx)), math.floor(F(crop[1]) + F(0.5) - F(ry)),
               math.ceil(F(crop[2]) - F(0.5) + F(rx)), math.ceil(F(crop[3]) - F(0.5) + F(ry))]  # film.rs:104-112
         rp.sample_bounds = (C.c_int32 * 4)(*sb)
-        # PerspectiveCamera::new, perspective.rs:40-86 + create_perspective_camera :298-356
-        frame = F(xres) / F(yres)
+        # PerspectiveCamera::new, perspective.rs:40-86 + create_perspective_camera :298-356; OrthographicCamera::new, orthographic.rs:40-59 + create_orthographic_camera
+        # :154-207; the environment camera (environment.rs:54-100) has no raster_to_camera: the field stays zero
+        kind = self.cam["kind"]
+        rp.camera_type = CAMERA_KINDS[kind]
+        frame = F(xres) / F(yres) if self.cam["frameaspectratio"] is None else F(self.cam["frameaspectratio"])
         if frame > 1: sw = (-frame, frame, F(-1), F(1))
         else: sw = (F(-1), F(1), F(-1) / frame, F(1) / frame)
-        c2s = Transform.perspective(self.cam["fov"], 1e-2, 1000.0)
-        s2r = (Transform.scale(xres, yres, 1) * Transform.scale(F(1) / (sw[1] - sw[0]), F(1) / (sw[2] - sw[3]), 1) *
-               Transform.translate((-sw[0], -sw[3], 0)))
-        r2c = c2s.inverse() * s2r.inverse()
-        rp.raster_to_camera = _f16(r2c.m)
+        if self.cam["screenwindow"] is not None:
+            sw = tuple(F(v) for v in self.cam["screenwindow"])
+            if len(sw) != 4: raise ValueError('"screenwindow" should have four values')
+        if kind != "environment":
+            c2s = Transform.orthographic(0.0, 1.0) if kind == "orthographic" else Transform.perspective(self.cam["fov"], 1e-2, 1000.0)
+            s2r = (Transform.scale(xres, yres, 1) * Transform.scale(F(1) / (sw[1] - sw[0]), F(1) / (sw[2] - sw[3]), 1) *
+                   Transform.translate((-sw[0], -sw[3], 0)))
+            r2c = c2s.inverse() * s2r.inverse()
+            rp.raster_to_camera = _f16(r2c.m)
         rp.camera_to_world = _f16(self.cam["c2w"].m)
         rp.lens_radius = self.cam["lensradius"]; rp.focal_distance = self.cam["focaldistance"]
         rp.shutter_open = self.cam["shutteropen"]; rp.shutter_close = self.cam["shutterclose"]
