@@ -33,3 +33,9 @@ ENTRY_POINTS = {
     "ptf_checkpoint_write": (C.c_int, [C.c_char_p, C.POINTER(PtfCheckpointHeader), fp]),
     "ptf_checkpoint_read": (C.c_int, [C.c_char_p, C.POINTER(PtfCheckpointHeader), u32p, fp]),
 }
+
+# Every symbol include/mi355front_matte.h declares (the same library; what ID mattes need of a front end).
+MATTE_ENTRY_POINTS = {
+    "ptf_write_exr_channels_attrs": (C.c_int, [C.c_char_p, C.c_int, C.c_int, u32, C.POINTER(C.c_char_p), C.POINTER(fp), u32p, u32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)]),
+    "ptf_prim_shape_ordinals": (C.c_int, [VP, C.POINTER(u32p), u32p]),
+}

@@ -4,7 +4,7 @@ import os
 import subprocess
 from . import _abi as A
 from . import _abi_ao as AO
-from ._abi_front import ENTRY_POINTS, PTF_CHECKPOINT_MAGIC, PtfCheckpointHeader   # (re-exported: the mirror of include/mi355front.h)
+from ._abi_front import ENTRY_POINTS, MATTE_ENTRY_POINTS, PTF_CHECKPOINT_MAGIC, PtfCheckpointHeader   # (re-exported: the mirror of include/mi355front.h)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SAN = bool(os.environ.get("PT_SAN"))   # ASan/UBSan build of the front end (tools/san_cpu_tests.sh)
@@ -29,7 +29,7 @@ def lib():
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             build()
-        _lib = A.bind(C.CDLL(LIB_PATH), table=ENTRY_POINTS)
+        _lib = A.bind(A.bind(C.CDLL(LIB_PATH), table=ENTRY_POINTS), table=MATTE_ENTRY_POINTS)
     return _lib
 
 
@@ -65,6 +65,14 @@ class FrontScene:
     def output_filename(self):
         return lib().ptf_output_filename(self.h).decode()
 
+    @property
+    def prim_group(self):
+        """Per primitive, the ordinal of its Shape directive in file order (host.SceneData.prim_group's twin): a uint32 array, the `groups` of Scene.render_mattes."""
+        import numpy as np
+        p, n = A.u32p(), C.c_uint32()
+        if lib().ptf_prim_shape_ordinals(self.h, C.byref(p), C.byref(n)) != A.PT_OK: raise ValueError(lib().ptf_last_error().decode(errors="replace"))
+        return np.ctypeslib.as_array(p, shape=(n.value,)).copy() if n.value else np.zeros(0, np.uint32)
+
     def close(self):
         if self.h:
             lib().ptf_scene_destroy(self.h); self.h = C.c_void_p()
@@ -90,6 +98,23 @@ def write_image(path, rgb):
     rgb = np.ascontiguousarray(rgb, dtype=np.float32)
     L = lib()
     if L.ptf_write_image(os.fsencode(path), rgb.shape[1], rgb.shape[0], rgb.ctypes.data_as(A.fp)) != 0: raise ValueError(L.ptf_last_error().decode(errors="replace"))
+
+
+def write_exr_channels(path, channels, attributes=()):
+    """An EXR file of FLOAT channels: `channels` = {name: (h, w) float32 array}, written in the byte-wise sorted order of the names; `attributes` = (name, value)
+    pairs of strings, written as string attributes after the required ones."""
+    import numpy as np
+    names = sorted(channels, key=lambda s: s.encode())
+    arrs = [np.ascontiguousarray(channels[k], dtype=np.float32) for k in names]
+    h, w = arrs[0].shape
+    if any(a.shape != (h, w) for a in arrs): raise ValueError("write_exr_channels: the channels differ in shape")
+    n, m = len(names), len(attributes)
+    cn = (C.c_char_p * n)(*[s.encode() for s in names])
+    ptrs = (A.fp * n)(*[a.ctypes.data_as(A.fp) for a in arrs])
+    strides = (C.c_uint32 * n)(*([1] * n))
+    an = (C.c_char_p * max(m, 1))(*[k.encode() for k, _ in attributes]); av = (C.c_char_p * max(m, 1))(*[v.encode() for _, v in attributes])
+    L = lib()
+    if L.ptf_write_exr_channels_attrs(os.fsencode(path), w, h, n, cn, ptrs, strides, m, an, av) != A.PT_OK: raise ValueError(L.ptf_last_error().decode(errors="replace"))
 
 
 def checkpoint_header(rp, ao=None, first_sample=0, samples_done=0):

@@ -339,7 +339,9 @@ inline Image read_exr(const std::string &path) {
 struct ExrChannel { const char *name; const float *data; size_t stride; };
 // One part of FLOAT channels, scan lines in increasing y, no compression. The channel list is stored -- and each scan line's planes follow -- in the order given, which
 // must be the byte-wise sorted order of the names the format requires.
-inline void write_exr(const std::string &path, int w, int h, const std::vector<ExrChannel> &channels) {
+// A header attribute of type "string" to write after the required ones (e.g. a Cryptomatte layer's name, hash, conversion and manifest).
+struct ExrStringAttr { const char *name; const char *value; };
+inline void write_exr(const std::string &path, int w, int h, const std::vector<ExrChannel> &channels, const std::vector<ExrStringAttr> &strings = {}) {
     for (size_t i = 1; i < channels.size(); ++i) if (std::strcmp(channels[i - 1].name, channels[i].name) >= 0) throw std::runtime_error("EXR \"" + path + "\": channel names must be sorted and distinct");
     std::vector<unsigned char> o;
     auto put = [&](const void *q, size_t n) { o.insert(o.end(), (const unsigned char *)q, (const unsigned char *)q + n); };
@@ -360,6 +362,7 @@ inline void write_exr(const std::string &path, int w, int h, const std::vector<E
     attr("pixelAspectRatio", "float", 4); put(&one, 4);
     attr("screenWindowCenter", "v2f", 8); put(&zero, 4); put(&zero, 4);
     attr("screenWindowWidth", "float", 4); put(&one, 4);
+    for (const ExrStringAttr &a : strings) { const size_t n = std::strlen(a.value); attr(a.name, "string", (int32_t)n); put(a.value, n); }
     o.push_back(0);
     const size_t row = (size_t)w * 4 * channels.size(), line = 8 + row; uint64_t off = o.size() + 8 * (uint64_t)h;
     for (int y = 0; y < h; ++y) { put(&off, 8); off += line; }

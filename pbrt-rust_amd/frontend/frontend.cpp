@@ -13,6 +13,7 @@
 #include "../../include/mi355pt.h"
 #include "../../include/mi355ao.h"
 #include "../../include/mi355front.h"
+#include "../../include/mi355front_matte.h"
 #include "fe_bssrdf.h"
 #include "fe_image.h"
 #include "fe_imageio.h"
@@ -45,6 +46,7 @@ struct Scene {
     std::vector<uint32_t> indices; std::vector<uint8_t> tri_flags; std::vector<int32_t> tri_alpha, tri_shadow_alpha;
     std::vector<PtSphere> spheres;
     std::vector<uint32_t> prim_shape, prim_material, prim_light, prim_med_in, prim_med_out;
+    std::vector<uint32_t> prim_group; uint32_t n_shapes = 0;   // per primitive: the ordinal of its Shape directive, 0, 1, 2, ... in file order (shapes inside ObjectBegin count); not part of the PtSceneDesc
     std::vector<PtMedium> media; std::map<std::string, int> named_media; int camera_medium = -1; bool volpath = false;
     bool ao = false; PtAOParams ao_params{64u, 1u};   // Integrator "ambientocclusion" (include/mi355ao.h)
     std::vector<std::vector<float>> media_density; std::vector<int> media_density_of;   // grid media: density arrays and the medium each belongs to
@@ -471,7 +473,7 @@ private:
     }
     void add_prim(uint32_t shape_ref) {
         const uint32_t prim = (uint32_t)sc.prim_shape.size();
-        sc.prim_shape.push_back(shape_ref); sc.prim_material.push_back(gs.material < 0 ? PT_NONE : (uint32_t)gs.material);
+        sc.prim_shape.push_back(shape_ref); sc.prim_material.push_back(gs.material < 0 ? PT_NONE : (uint32_t)gs.material); sc.prim_group.push_back(sc.n_shapes);
         { const int mi = medium_index(gs.medium_inside), mo = medium_index(gs.medium_outside); sc.prim_med_in.push_back(mi < 0 ? PT_NONE : (uint32_t)mi); sc.prim_med_out.push_back(mo < 0 ? PT_NONE : (uint32_t)mo); }
         sc.prim_light.push_back((gs.has_area && !sc.in_object) ? new_area_light(prim) : PT_NONE);   // api.rs:1605-1608: area lights inside instances are dropped
         if (sc.in_object) sc.object_ranges[sc.current_object].second += 1; else sc.top_refs.push_back(prim);
@@ -525,6 +527,7 @@ private:
             sc.spheres.push_back(s);
             add_prim(((uint32_t)PT_SHAPE_SPHERE << 30) | ((uint32_t)sc.spheres.size() - 1));
         } else fail(d, "shape \"" + kind + "\" is not implemented on this back end");
+        sc.n_shapes++;
     }
     void object_instance(const Token &d, const std::string &name) {   // api.rs:1669-1713
         auto it = sc.object_ranges.find(name);
@@ -694,6 +697,25 @@ int ptf_write_exr_channels(const char *path, int width, int height, uint32_t n_c
     for (uint32_t i = 0; i < n_channels; ++i) if (!names[i] || !data[i] || strides[i] == 0) { fe::g_error = "ptf_write_exr_channels: channel " + std::to_string(i) + " has no name, no data or a stride of 0"; return PT_ERR_INVALID_ARG; }
     for (uint32_t i = 0; i < n_channels; ++i) ch.push_back(fe::ExrChannel{names[i], data[i], strides[i]});
     try { fe::write_exr(path, width, height, ch); } catch (const std::exception &e) { fe::g_error = e.what(); return PT_ERR_INVALID_ARG; }
+    return PT_OK;
+}
+int ptf_write_exr_channels_attrs(const char *path, int width, int height, uint32_t n_channels, const char *const *names, const float *const *data, const uint32_t *strides,
+                                 uint32_t n_attrs, const char *const *attr_names, const char *const *attr_values) {
+    if (!path || !names || !data || !strides || n_channels == 0 || width <= 0 || height <= 0 || (n_attrs && (!attr_names || !attr_values))) { fe::g_error = "ptf_write_exr_channels_attrs: bad argument"; return PT_ERR_INVALID_ARG; }
+    std::vector<fe::ExrChannel> ch;
+    for (uint32_t i = 0; i < n_channels; ++i) if (!names[i] || !data[i] || strides[i] == 0) { fe::g_error = "ptf_write_exr_channels_attrs: channel " + std::to_string(i) + " has no name, no data or a stride of 0"; return PT_ERR_INVALID_ARG; }
+    for (uint32_t i = 0; i < n_channels; ++i) ch.push_back(fe::ExrChannel{names[i], data[i], strides[i]});
+    std::vector<fe::ExrStringAttr> at;
+    for (uint32_t i = 0; i < n_attrs; ++i) {
+        if (!attr_names[i] || !attr_values[i] || !attr_names[i][0] || std::strlen(attr_names[i]) > 31) { fe::g_error = "ptf_write_exr_channels_attrs: attribute " + std::to_string(i) + " has no name, a name of more than 31 bytes (the file's version word promises short names) or no value"; return PT_ERR_INVALID_ARG; }
+        at.push_back(fe::ExrStringAttr{attr_names[i], attr_values[i]});
+    }
+    try { fe::write_exr(path, width, height, ch, at); } catch (const std::exception &e) { fe::g_error = e.what(); return PT_ERR_INVALID_ARG; }
+    return PT_OK;
+}
+int ptf_prim_shape_ordinals(const ptf_scene *s, const uint32_t **ordinals, uint32_t *n_prims) {
+    if (!s || !ordinals || !n_prims) { fe::g_error = "null argument"; return PT_ERR_INVALID_ARG; }
+    *ordinals = s->sc.prim_group.data(); *n_prims = (uint32_t)s->sc.prim_group.size();
     return PT_OK;
 }
 int ptf_read_image(const char *path, int *width, int *height, float *rgb, size_t capacity_floats) {

@@ -218,6 +218,7 @@ class SceneBuilder:
         self.ntris = 0
         self.spheres = []
         self.prim_shape, self.prim_material, self.prim_light = [], [], []
+        self.prim_group, self.nshapes = [], 0   # per primitive: the ordinal of its shape call, 0, 1, 2, ... (the .pbrt front end numbers the Shape directives alike)
         self.nprims = 0
         self.env = None
         self.top_refs = []            # RenderOptions.primitives: prim indices / PT_TOP_INSTANCE | instance
@@ -542,6 +543,7 @@ class SceneBuilder:
         first_prim = self.nprims
         self.prim_shape.append(shape_refs)
         self.prim_material.append(np.full(n, A.PT_NONE if self.material_id is None else self.material_id, dtype=np.uint32))
+        self.prim_group.append(np.full(n, self.nshapes, dtype=np.uint32)); self.nshapes += 1
         self._prim_media(n)
         if self.area_light is None or self.current_object is not None:  # api.rs:1605-1608: area lights inside instances are dropped
             self.prim_light.append(np.full(n, A.PT_NONE, dtype=np.uint32))
@@ -729,6 +731,7 @@ class SceneData:
             return np.ascontiguousarray(out)
         self.N, self.S, self.UV = opt(b.N, 3), opt(b.S, 3), opt(b.UV, 2)
         self.prim_shape, self.prim_material, self.prim_light = cat(b.prim_shape, np.uint32), cat(b.prim_material, np.uint32), cat(b.prim_light, np.uint32)
+        self.prim_group = cat(b.prim_group, np.uint32)   # not in the PtSceneDesc: the `groups` of Scene.render_mattes for per-shape mattes
         self.materials = (A.PtMaterial * max(1, len(b.materials)))(*b.materials)
         self.lights = (A.PtLight * max(1, len(b.lights)))(*b.lights)
         self.spheres = (A.PtSphere * max(1, len(b.spheres)))(*b.spheres)

@@ -114,6 +114,86 @@ def resolve_aov(sums, lib=None):
     return out
 
 
+def resolve_mattes(tables, ranks=6, lib=None):
+    """pt_matte_resolve of the tables Scene.render_mattes returns: {layer: (ids (H, W, ranks) uint32, coverage (H, W, ranks) float32)} -- per pixel the `ranks` (1 .. 8)
+    heaviest slots, by weight descending and ties to the lower id, coverage = w / w_total; id 0 and coverage 0 where a rank has no slot or the pixel no weight."""
+    lib = lib or load_library()
+    out = {}
+    for layer, table in tables.items():
+        table = np.ascontiguousarray(table, dtype=AOV.MATTE_DTYPE)
+        ids = np.zeros(table.shape + (max(ranks, 0),), np.uint32); cov = np.zeros(ids.shape, np.float32)
+        lib.check(lib.aov.pt_matte_resolve(table.ctypes.data_as(AOV.mp), table.size, ranks, ids.ctypes.data_as(A.u32p), _fptr(cov)), "pt_matte_resolve")
+        out[layer] = (ids, cov)
+    return out
+
+
+def murmur3_32(data, seed=0):
+    """MurmurHash3_x86_32 of a bytes object."""
+    c1, c2, M = 0xcc9e2d51, 0x1b873593, 0xffffffff
+    rotl = lambda v, r: ((v << r) | (v >> (32 - r))) & M
+    h, n = seed & M, len(data)
+    for i in range(0, n - n % 4, 4):
+        k = int.from_bytes(data[i:i + 4], "little")
+        k = (rotl((k * c1) & M, 15) * c2) & M
+        h = (rotl(h ^ k, 13) * 5 + 0xe6546b64) & M
+    tail = data[n - n % 4:]
+    if tail:
+        k = int.from_bytes(tail, "little")
+        h ^= (rotl((k * c1) & M, 15) * c2) & M
+    h ^= n
+    h ^= h >> 16; h = (h * 0x85ebca6b) & M
+    h ^= h >> 13; h = (h * 0xc2b2ae35) & M
+    return h ^ (h >> 16)
+
+
+def cryptomatte_id(name):
+    """The Cryptomatte id of a name: MurmurHash3_32 of its UTF-8 bytes (seed 0), and -- the id travels as a float32 bit pattern -- with bit 23 flipped where the
+    exponent bits are all 0 or all 1, so that it is neither a denormal nor an infinity or NaN."""
+    h = murmur3_32(name.encode("utf-8"))
+    return h ^ (1 << 23) if (h >> 23) & 255 in (0, 255) else h
+
+
+def default_matte_name(layer, raw_id):
+    """The name write_cryptomatte gives the raw id of a layer when the caller has none: material<i>; world for top-level geometry and instance<i> for the instance
+    layer's id i = 1 + the instance's index; group<i>."""
+    if layer == "instance":
+        return "world" if raw_id == 0 else "instance%d" % raw_id
+    return "%s%d" % (layer, raw_id)
+
+
+def write_cryptomatte(path, tables, names=None, ranks=6, lib=None):
+    """The tables of Scene.render_mattes as a Cryptomatte EXR. Per layer L (CryptoMaterial, CryptoInstance, CryptoGroup) the FLOAT channels L00.R/G/B/A, L01. ...: two
+    ranks per RGBA set, R and B the id's float32 bit pattern, G and A its coverage (pt_matte_resolve's ranks); and the string attributes cryptomatte/<key>/name, /hash
+    ("MurmurHash3_32"), /conversion ("uint32_to_float32") and /manifest (JSON {name: "%08x" of its id}), <key> the first 7 hex digits of the layer name's id.
+    `names` = {layer: {raw id: name}}; ids without a name get default_matte_name. The written id of a raw id is cryptomatte_id of its name."""
+    import json
+    from . import frontend
+    names = names or {}
+    channels, attributes = {}, []
+    for layer, (ids, cov) in resolve_mattes(tables, ranks, lib).items():
+        L = AOV.CRYPTO_LAYER_NAMES[layer]
+        table = np.asarray(tables[layer])
+        slot_used = np.arange(AOV.PT_MATTE_SLOTS)[None, None, :] < table["n_ids"][..., None]
+        raw = sorted(set(int(v) for v in np.unique(table["id"][slot_used])) | set(names.get(layer, {})))
+        name_of = {i: names.get(layer, {}).get(i, default_matte_name(layer, i)) for i in raw}
+        hashed = {i: cryptomatte_id(n) for i, n in name_of.items()}
+        lut_keys = np.array(raw, np.uint32); lut_vals = np.array([hashed[i] for i in raw], np.uint32)
+        ranked = cov != 0.0   # (a rank without a slot is id 0, coverage 0: it stays 0.0 in the file)
+        written = np.zeros(ids.shape, np.uint32)
+        if len(raw):
+            written[ranked] = lut_vals[np.searchsorted(lut_keys, ids[ranked])]
+        bits = written.view(np.float32)
+        for r in range(ranks + ranks % 2):
+            base = "%s%02d." % (L, r // 2)
+            zero = np.zeros(ids.shape[:2], np.float32)
+            channels[base + "RB"[r % 2]] = bits[..., r] if r < ranks else zero
+            channels[base + "GA"[r % 2]] = cov[..., r] if r < ranks else zero
+        key = "cryptomatte/%s/" % ("%08x" % cryptomatte_id(L))[:7]
+        attributes += [(key + "name", L), (key + "hash", "MurmurHash3_32"), (key + "conversion", "uint32_to_float32"),
+                       (key + "manifest", json.dumps({name_of[i]: "%08x" % hashed[i] for i in raw}, sort_keys=True))]
+    frontend.write_exr_channels(path, channels, attributes)
+
+
 class Handle:
     """A scene handle of a library whose C functions carry a prefix: `pt_` (Scene), `pt_multi_` (MultiScene), `orc_` (the CPU oracle's scene).
     `cdll` holds the functions, `check(status, what)` raises on a status other than PT_OK, `extra` goes between the description and the handle in
@@ -336,6 +416,44 @@ class Scene(Handle):
     def aov_pass_size(self, rp):
         """Samples per pixel per pass pt_aov_render would use for `rp` now."""
         return self._pass_size("aov_pass_size", C.byref(rp), lib=self.L.aov)
+
+    def render_mattes(self, rp, layers=("material", "instance"), groups=None, samples=None, tables=None, device_ptrs=None):
+        """The ID mattes of the job `rp` (pt_matte_render; `samples` = (first, n): pt_matte_render_samples): {layer: an (H, W) array of _abi_aov.MATTE_DTYPE} for the
+        wanted layers of "material", "instance", "group" -- per pixel up to eight ids in first-seen order with the filter weight of their samples, w_total and
+        w_other. `groups`: a uint32 array, the caller's id of every primitive (for per-shape mattes: the scene data's prim_group), needed by the "group" layer.
+        `tables` (a dict this method returned, for the same layers) is CONTINUED in place: ranges rendered in ascending order leave what the whole range leaves, bit
+        for bit. `device_ptrs` = {layer: device pointer as an integer}: those tables are continued, returns None."""
+        args = [self.h, C.byref(rp)] + ([] if samples is None else list(samples))
+        name = "matte_render" if samples is None else "matte_render_samples"
+        groups = None if groups is None else np.ascontiguousarray(groups, dtype=np.uint32)
+        if device_ptrs is not None:
+            self._call(name, *args, C.byref(AOV.matte_buffers(device_ptrs, groups, device=True)), 1, lib=self.L.aov); return None
+        if tables is None:
+            tables = {k: np.zeros(film_shape(rp), dtype=AOV.MATTE_DTYPE) for k in layers}
+        self._call(name, *args, C.byref(AOV.matte_buffers(tables, groups)), 0, lib=self.L.aov)
+        return tables
+
+    def matte_pass_size(self, rp):
+        """Samples per pixel per pass pt_matte_render would use for `rp` now."""
+        return self._pass_size("matte_pass_size", C.byref(rp), lib=self.L.aov)
+
+    def matte_mask(self, table, ids, n_pixels=None, mask_ptr=None):
+        """pt_matte_mask: per pixel of one layer's table, the share of the filter weight that the ids of `ids` hold -- the matte of those materials, instances or
+        groups, an (H, W) float32 array. `table`: an array of MATTE_DTYPE, or a device pointer as an integer to `n_pixels` tables (the result is then flat);
+        `mask_ptr`: the mask goes to that device buffer, returns None."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32).ravel()
+        on_device = isinstance(table, int)
+        if on_device:
+            shape, tp = (n_pixels,), C.cast(C.c_void_p(table), AOV.mp)
+        else:
+            table = np.ascontiguousarray(table, dtype=AOV.MATTE_DTYPE)
+            shape, tp = table.shape, table.ctypes.data_as(AOV.mp)
+        n = int(np.prod(shape))
+        if mask_ptr is not None:
+            self._call("matte_mask", self.h, tp, int(on_device), n, ids.ctypes.data_as(A.u32p), len(ids), C.cast(C.c_void_p(mask_ptr), A.fp), 1, lib=self.L.aov); return None
+        mask = np.zeros(shape, np.float32)
+        self._call("matte_mask", self.h, tp, int(on_device), n, ids.ctypes.data_as(A.u32p), len(ids), _fptr(mask), 0, lib=self.L.aov)
+        return mask
 
     def denoise(self, film_a, film_b, sums, params=None, device_ptrs=None):
         """pt_denoise of two half films (H, W, 4) -- XYZW sums of disjoint sample ranges, A + B is the film -- and the feature sums of the samples of A + B (the
