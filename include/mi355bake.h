@@ -1,0 +1,122 @@
+/* mi355bake.h -- C ABI of libmi355bake.so: ambient occlusion, bent normals, positions and shading normals of a UV-mapped mesh baked
+ * into its own texture space (a UV atlas) on the MI355X.
+ *
+ * A fifth library beside libmi355pt.so. It bakes scenes created with pt_scene_create (include/mi355pt.h) and reaches the any-hit
+ * traversal, the samplers' arrays and the pass budget through libmi355pt's driver. There is no camera, no path state and no film:
+ * the front of the pipe is its own -- which triangle owns which texel (k_bake_raster), the surface point there (k_bake_points), the
+ * AO rays from it (k_bake_rays), their any-hit walk (libmi355pt's k_trace, launch kind "shadow") and the sums (k_bake_accum).
+ *
+ * ---- the contract -----------------------------------------------------------------------------------------------------------------
+ *
+ * Texel centres. Texel (x, y) of a width x height atlas has index y * width + x and centre c = (u, v), u = (x + 0.5) / width,
+ * v = (y + 0.5) / height, in float32: ((float)x + 0.5f) / (float)width. Row 0 is at v = 0. Every sample of a texel starts at its
+ * centre: antialiasing in texture space is done by baking larger.
+ *
+ * Ownership. For a selected triangle with vertex UVs uv0, uv1, uv2 (TriangleMesh "uv", by the triangle's three indices), every
+ * operation in float32, unfused, in this order:
+ *     e0 = uv1 - uv0, e1 = uv2 - uv0, d = c - uv0
+ *     det = e0.x * e1.y - e0.y * e1.x
+ *     b1 = (d.x * e1.y - d.y * e1.x) / det,  b2 = (e0.x * d.y - e0.y * d.x) / det,  b0 = 1 - b1 - b2      ((1 - b1) - b2)
+ * A triangle with det == 0 owns nothing. It contains the centre when b0 >= 0, b1 >= 0 and b2 >= 0 (a NaN fails) AND the texel lies in
+ * the triangle's texel box, x0 <= x <= x1 and y0 <= y <= y1, in float32 (fminf / fmaxf: a NaN operand loses):
+ *     ulo = min(uv0.x, min(uv1.x, uv2.x)) * (float)width,   uhi = max(uv0.x, max(uv1.x, uv2.x)) * (float)width    (vlo, vhi alike with .y, height)
+ *     no box -- the triangle owns nothing -- unless ulo <= uhi, vlo <= vhi and all four are below 1e30 in magnitude
+ *     mx = 0.5625f + (float)width * 2.4e-7f                                                                       (my alike with height)
+ *     x0 = max(floor(ulo - mx), 0),   x1 = min(ceil((uhi - 1) + mx), width - 1);   no box when x0 > x1            (y0, y1 alike)
+ * The box holds every texel whose centre the UV bounds can hold, with a margin beyond what the roundings of the bounds and of the centres
+ * amount to: a well-conditioned triangle loses nothing to it. It is there for slivers: with a determinant of a few 1e-9 the rounded
+ * barycentrics of a nearly collinear triangle are >= 0 at centres far along its line, and without the box a low-numbered sliver would own
+ * texels anywhere on the atlas. The owner of a texel
+ * is the LOWEST-NUMBERED selected primitive that contains its centre (primitive numbers are PtSceneDesc's, as pt_trace_closest reports
+ * them): ownership is deterministic on shared edges and overlapping islands and does not depend on launch geometry. UVs outside
+ * [0, 1] are not wrapped: the part of a triangle outside the unit square owns nothing.
+ *
+ * The surface point. The interaction Triangle::intersect (shapes/triangle.rs:236-392) builds for the barycentrics (b0, b1, b2) of the
+ * owner: p = b0 p0 + b1 p1 + b2 p2 and its error bound p_error, the geometric normal n (flipped by ReverseOrientation xor a
+ * handedness-swapping transform, then faced toward the shading normal when the mesh has N or S), dpdu, and the shading normal from
+ * per-vertex N -- by the device function the shade and AO kernels use (tri_fill_interaction). `position` is p, `normal` the
+ * normalised shading normal. A triangle with area in UV space and none in space has no normal: its texels get NaN normals, rays and
+ * sums, as the interaction's arithmetic leaves them; leave such triangles out of the selection.
+ *
+ * AO rays, as AOIntegrator::li (integrators/ao.rs:77-98) with the surface point in place of the camera hit:
+ *     frame        s = normalize(dpdu), t = cross(n, s), and n itself: with no camera ray there is nothing to face n toward
+ *     sample       element k of sample s of a texel is the 2-D array value of sample number s * nsamples + k of pixel (x, y),
+ *                  dimensions 5 and 6, of a sampler set up for sample bounds [0, width) x [0, height) (sampler.rs:265-306)
+ *     direction    cos_sample != 0: cosine_sample_hemisphere(u), pdf = |wi.z| / pi;
+ *                  else uniform_sample_sphere(u), pdf = 1 / (4 pi); wi = s * wi.x + t * wi.y + n * wi.z
+ *     origin       offset_ray_origin(p, p_error, n, wi) (SurfaceInteraction::spawn_ray)
+ *     weight       w = dot(wi, n) / (pdf * nsamples);  t_max = max_distance
+ * The rays see the whole scene through libmi355pt's any-hit walk: spheres, instances, alpha masks and the baked mesh itself.
+ * ao_w of a texel gains, per unoccluded ray, wi.xyz and w, added in ascending (s, k) order to what the buffer holds. Disjoint sample
+ * ranges baked in ascending order into the same buffers leave what the whole range leaves, bit for bit; so do different pass sizes
+ * and repeated calls. spp * nsamples is limited as pt_ao_render limits it (the Sobol' tables' 52 columns, Halton's 64-bit index).
+ *
+ * Counters and kernel statistics of the last call are read through libmi355pt (pt_get_counters, pt_get_kernel_stats): shadow_tests
+ * = the AO rays, bvh_nodes_visited, triangle_tests, sphere_tests; the launch kinds are "bake_select", "bake_raster", "bake_points",
+ * "bake_rays", "shadow", "bake_accum" and "bake_dilate" ("bake_probe" for pt_bake_rays). */
+#ifndef MI355BAKE_H
+#define MI355BAKE_H
+#include <stdint.h>
+#include "mi355pt.h"
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct PtBakeParams {
+    uint32_t width, height;      /* the atlas, texels; width * height <= 2^28                         */
+    uint32_t spp;                /* the job's samples per texel, > 0                                  */
+    uint32_t nsamples;           /* AO rays per sample (ao.rs "nsamples"), > 0                        */
+    uint32_t cos_sample;         /* ao.rs "cossample"                                                 */
+    float    max_distance;       /* t_max of the AO rays, > 0; INFINITY is ao.rs                      */
+    uint32_t sampler_type;       /* PtSamplerType                                                     */
+    uint32_t spp_per_pass;       /* 0: the library chooses from the free memory                       */
+    uint32_t profile;            /* != 0: time every launch kind (pt_get_kernel_stats)                */
+} PtBakeParams;
+
+typedef struct PtBakeBuffers {   /* width * height entries, row-major; NULL = not wanted */
+    uint32_t *owner;             /* primitive that owns the texel, PT_NONE for none -- written        */
+    float *position;             /* 3 per texel: p; 0 where the texel has no owner -- written         */
+    float *normal;               /* 3 per texel: the normalised shading normal; 0 likewise -- written */
+    float *ao_w;                 /* 4 per texel: sum of unoccluded wi.xyz, sum of w -- ADDED to       */
+} PtBakeBuffers;
+
+/* Bakes params->spp samples per texel of the primitives selected by prim_select -- HOST memory, n_prims bytes, non-zero = a bake
+ * target -- into the wanted planes (device memory when buffers_are_device). Without ao_w no ray is traced.
+ * Errors. PT_ERR_INVALID_ARG, before the device is touched, for a NULL scene, params, prim_select or buffers; width or height 0 or
+ * more than 2^28 texels; spp or nsamples 0; all planes NULL; max_distance not positive, or NaN; a bad sample range; nothing selected;
+ * n_prims different from the scene's primitive count (the handle's host side). Then, with the device bound, for more sample numbers per
+ * texel than the sampler's tables serve.
+ * PT_ERR_UNSUPPORTED, the message naming the primitive, for a selected sphere or disk, a selected primitive that belongs to an
+ * instanced object, or a selected triangle of a mesh without UVs. Otherwise pt_render's statuses. Text: pt_last_error(). */
+int pt_bake_render(pt_scene *scene, const PtBakeParams *params, const uint8_t *prim_select, uint32_t n_prims, const PtBakeBuffers *buffers, int buffers_are_device);
+/* Samples [first_sample, first_sample + n_samples) of every texel; params->spp stays the job's sample count. n_samples == 0 or
+ * first_sample + n_samples > spp (in 64 bits): PT_ERR_INVALID_ARG before the device is touched. pt_bake_render is the call (0, spp). */
+int pt_bake_render_samples(pt_scene *scene, const PtBakeParams *params, const uint8_t *prim_select, uint32_t n_prims, uint32_t first_sample, uint32_t n_samples,
+                           const PtBakeBuffers *buffers, int buffers_are_device);
+/* Samples per texel per pass pt_bake_render would use: a pass holds width * height * spp_per_pass texel samples and their rays, traced
+ * in chunks of at most 64 per texel sample. With nsamples > 64 a pass is one sample, whatever spp_per_pass asks for: the additions to a
+ * texel stay in (s, k) order. */
+int pt_bake_pass_size(pt_scene *scene, const PtBakeParams *params, uint32_t *spp_per_pass);
+/* Host arithmetic: ao[n] = sum w / (spp * pi) -- sum w / spp is ao.rs's radiance, pi where nothing occludes under cosine sampling, so the
+ * map is 1 for an open surface --, bent_xyz[3 n] = normalize(sum wi); 0 where nothing was added (all four sums 0; the bent normal also
+ * where the sum's length is 0). A NULL output is skipped. PT_ERR_INVALID_ARG for a NULL ao_w, both outputs NULL, or spp == 0. */
+int pt_bake_resolve(const float *ao_w, uint32_t n_texels, uint32_t spp, float *ao, float *bent_xyz);
+/* Fills the gutter round the islands of a plane of `channels` (1 .. 4) floats per texel, in place. Per iteration every texel that is
+ * not covered and has at least one covered 8-neighbour inside the atlas gets the mean of its covered neighbours: per channel the sum
+ * in the order (-1,-1), (0,-1), (1,-1), (-1,0), (1,0), (-1,1), (0,1), (1,1) of (dx, dy), divided by their count as a float; it counts
+ * as covered from the next iteration on. Covered at the start: owner[texel] != PT_NONE. `owner` is not modified. Ping-pong buffers, no
+ * atomics: the result does not depend on launch geometry. iterations == 0 leaves the plane as it is. PT_ERR_INVALID_ARG for a NULL
+ * argument, width or height 0, more than 2^28 texels, or channels outside 1 .. 4. Unlike pt_bake_render, which starts the scene's kernel
+ * statistics afresh, this call ADDS its launches to the kind "bake_dilate" of the statistics it finds (timed when the last bake was
+ * profiled): the dilations that follow a bake are read with it, and their counts add up over calls until the next bake. */
+int pt_bake_dilate(pt_scene *scene, const uint32_t *owner, float *plane, uint32_t channels, uint32_t width, uint32_t height, uint32_t iterations, int buffers_are_device);
+/* Parity entry, in the style of pt_camera_rays: for n triples (texel index, sample number s, element k) -- host arrays -- the origin,
+ * direction and weight of that AO ray, by the device function the render uses; found[i] = 0 and zeros where the texel has no owner.
+ * The parameters, the selection and their checks are pt_bake_render's (spp_per_pass and profile are not read). */
+int pt_bake_rays(pt_scene *scene, const PtBakeParams *params, const uint8_t *prim_select, uint32_t n_prims, uint32_t n, const uint32_t *texel, const uint32_t *sample,
+                 const uint32_t *element, float *out_o, float *out_d, float *out_w, uint8_t *found);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -1,0 +1,38 @@
+"""ctypes mirror of include/mi355bake.h (libmi355bake.so: ambient occlusion, bent normals, positions and normals baked into a UV atlas). Kept apart from
+_abi.py, which mirrors include/mi355pt.h alone."""
+import ctypes as C
+from ._abi import VP, fp, u8p, u32, u32p
+
+PLANES = ("owner", "position", "normal", "ao_w")              # PtBakeBuffers' fields, in this order
+CHANNELS = {"owner": 1, "position": 3, "normal": 3, "ao_w": 4}   # entries per texel of a plane
+DTYPES = {"owner": "uint32", "position": "float32", "normal": "float32", "ao_w": "float32"}
+
+
+class PtBakeParams(C.Structure):
+    _fields_ = [("width", u32), ("height", u32), ("spp", u32), ("nsamples", u32), ("cos_sample", u32), ("max_distance", C.c_float), ("sampler_type", u32),
+                ("spp_per_pass", u32), ("profile", u32)]
+
+
+class PtBakeBuffers(C.Structure):
+    _fields_ = [("owner", u32p), ("position", fp), ("normal", fp), ("ao_w", fp)]
+
+
+def buffers(planes, device=False):
+    """The PtBakeBuffers of {plane: a contiguous array of its dtype -- with `device`: a device pointer as an integer}; a plane that is not there is NULL."""
+    b = PtBakeBuffers()
+    for k, (name, ctype) in enumerate(PtBakeBuffers._fields_):
+        if name in planes:
+            setattr(b, name, C.cast(C.c_void_p(planes[name]), ctype) if device else planes[name].ctypes.data_as(ctype))
+    return b
+
+
+# Every symbol include/mi355bake.h declares, with its signature (restype, argtypes).
+_bp, _bb = C.POINTER(PtBakeParams), C.POINTER(PtBakeBuffers)
+ENTRY_POINTS = {
+    "pt_bake_render": (C.c_int, [VP, _bp, u8p, u32, _bb, C.c_int]),
+    "pt_bake_render_samples": (C.c_int, [VP, _bp, u8p, u32, u32, u32, _bb, C.c_int]),
+    "pt_bake_pass_size": (C.c_int, [VP, _bp, u32p]),
+    "pt_bake_resolve": (C.c_int, [fp, u32, u32, fp, fp]),
+    "pt_bake_dilate": (C.c_int, [VP, u32p, fp, u32, u32, u32, u32, C.c_int]),
+    "pt_bake_rays": (C.c_int, [VP, _bp, u8p, u32, u32, u32p, u32p, u32p, fp, fp, fp, u8p]),
+}

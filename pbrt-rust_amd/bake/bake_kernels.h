@@ -1,0 +1,308 @@
+// bake_kernels.h -- the kernels of the texture-space bake (include/mi355bake.h, where the contract stands operation by operation). The any-hit walk of the AO
+// rays (k_trace) is libmi355pt's; this file is the front of the pipe and its end:
+//   k_bake_top      marks the primitives of the top-level accelerator (a primitive of an instanced object is no bake target)
+//   k_bake_raster   selected triangles -> atomicMin on the owner map
+//   k_bake_points   one thread per texel: the owner's interaction -> position and shading normal
+//   k_bake_rays     one texel sample per thread: one chunk of its AO rays (the direction sampling mirrors ao/ao_kernels.h:67-84)
+//   k_bake_accum    ao_w += the unoccluded rays' wi and w, in element order
+//   k_bake_dilate   one iteration of the gutter fill
+//   k_bake_probe    pt_bake_rays: single rays by bake_ray, the function k_bake_rays calls
+// No atomics other than the owner map's atomicMin and the per-wave ray-id reservation (wave_reserve).
+#pragma once
+#include "../csrc/kern_decl.h"
+
+namespace ptbake {
+using namespace ptd;
+
+constexpr float kInv4Pi = 0.07957747154594766788f;   // INV4_PI (pbrt.rs:30)
+constexpr uint32_t kBakeChunk = 64;                  // AO rays per texel sample per trace launch (the rays of one texel sample are consecutive ray ids)
+constexpr uint32_t kRasterOwnTexels = 16;            // k_bake_raster: a triangle whose texel box holds at most this many texels is walked by its own lane
+
+// `slots`: the texel samples of one sample number in the order the ray kernel walks them -- 8 x 8 texel tiles, one per wave, so that the rays of a wave start from a
+// square patch of the surface and not from a line of 64 texels (measured against raster order on a 2048^2 bake of a 4.3 M-triangle mesh: the any-hit launch 129.8 ms
+// against 139.4 ms, profiles/r6/NOTES.md). The tiles of the last column / row hang over the atlas: those slots have no texel.
+struct BakeAtlas { uint32_t width, height, n_texels, tiles_x, slots; };
+PT_HD BakeAtlas make_atlas(uint32_t width, uint32_t height) { return BakeAtlas{width, height, width * height, (width + 7u) / 8u, ((width + 7u) / 8u) * ((height + 7u) / 8u) * 64u}; }
+PT_DEV uint32_t slot_texel(const BakeAtlas &a, uint32_t slot) {   // PT_NONE: the slot hangs over the atlas
+    const uint32_t tile = slot >> 6, lane = slot & 63u;
+    const uint32_t x = (tile % a.tiles_x) * 8u + (lane & 7u), y = (tile / a.tiles_x) * 8u + (lane >> 3);
+    return (x < a.width && y < a.height) ? y * a.width + x : PT_NONE;
+}
+PT_DEV uint32_t texel_slot(const BakeAtlas &a, uint32_t texel) {
+    const uint32_t x = texel % a.width, y = texel / a.width;
+    return (((y >> 3) * a.tiles_x + (x >> 3)) << 6) | ((y & 7u) << 3) | (x & 7u);
+}
+
+// One chunk of AO rays: elements k0 .. k0 + kn - 1 of the texel samples [s_begin, s_begin + s_count) of every owned texel.
+struct BakeJob {
+    uint32_t nsamples, cos_sample;
+    uint32_t k0, kn;
+    uint32_t s_begin, s_count;
+    const uint32_t *owner;   // [texels]
+    float4 *ray;             // [rays][2]: {o.xyz, d.x} {d.yz, -, -} (k_trace's 32-byte ray record)
+    float *w;                // [rays]
+    uint32_t *base;          // [slots * s_count]: first ray id of the texel sample's chunk, PT_NONE for a texel without owner
+    uint32_t *ray_count;     // device count of ray ids handed out
+    const uint32_t *occluded;   // [rays]: k_trace's any-hit flags (k_bake_accum)
+    float4 *ao_w;            // [texels]
+};
+
+// Texel centre (mi355bake.h "Texel centres")
+PT_DEV P2 texel_centre(const BakeAtlas &a, uint32_t x, uint32_t y) { return P2(((float)x + 0.5f) / (float)a.width, ((float)y + 0.5f) / (float)a.height); }
+
+// The barycentrics of c in the UV triangle (mi355bake.h "Ownership"); false: the triangle does not contain c
+PT_DEV bool uv_barycentrics(P2 uv0, P2 uv1, P2 uv2, P2 c, float &b0, float &b1, float &b2) {
+    const float e0x = uv1.x - uv0.x, e0y = uv1.y - uv0.y, e1x = uv2.x - uv0.x, e1y = uv2.y - uv0.y, dx = c.x - uv0.x, dy = c.y - uv0.y;
+    const float det = e0x * e1y - e0y * e1x;
+    if (det == 0.0f) return false;
+    b1 = (dx * e1y - dy * e1x) / det;
+    b2 = (e0x * dy - e0y * dx) / det;
+    b0 = 1.0f - b1 - b2;
+    return b0 >= 0.0f && b1 >= 0.0f && b2 >= 0.0f;
+}
+
+PT_DEV void tri_vertex_uvs(const DeviceScene &s, uint32_t tri, P2 &uv0, P2 &uv1, P2 &uv2) {
+    const uint32_t i0 = s.indices[3 * tri], i1 = s.indices[3 * tri + 1], i2 = s.indices[3 * tri + 2];
+    uv0 = P2(s.UV[2 * i0], s.UV[2 * i0 + 1]); uv1 = P2(s.UV[2 * i1], s.UV[2 * i1 + 1]); uv2 = P2(s.UV[2 * i2], s.UV[2 * i2 + 1]);
+}
+
+// The interaction of a texel's owner at the texel's centre (mi355bake.h "The surface point"): Triangle::intersect's, by the function the shade and AO kernels rebuild
+// their hits with. The owner contains the centre (k_bake_raster decided so with the same arithmetic), so the barycentrics are the ones it saw.
+PT_DEV void texel_interaction(const DeviceScene &s, const BakeAtlas &a, uint32_t texel, uint32_t prim, SurfaceInteraction &si) {
+    const uint32_t tri = s.prim_shape[prim] & 0x3fffffffu;
+    P2 uv0, uv1, uv2; tri_vertex_uvs(s, tri, uv0, uv1, uv2);
+    float b0 = 0.0f, b1 = 0.0f, b2 = 0.0f;
+    uv_barycentrics(uv0, uv1, uv2, texel_centre(a, texel % a.width, texel / a.width), b0, b1, b2);
+    tri_fill_interaction(s, tri, V3(0.0f, 0.0f, 0.0f), b0, b1, b2, true, si);
+}
+
+// The 2-D array value of sample number j (GlobalSampler::start_pixel, sampler.rs:288-302): dimensions ARRAY_START_DIM = 5 and 6 (ao/ao_kernels.h:26-33)
+PT_DEV P2 bake_array_sample(const RenderConst &rc, const SobolTables &tabs, int32_t px, int32_t py, uint64_t j) {
+    if (rc.halton.enabled) {
+        const uint64_t index = halton_index_for_sample(rc.halton, px, py, j);
+        return P2(halton_sample_dimension(tabs, rc.halton, index, 5u), halton_sample_dimension(tabs, rc.halton, index, 6u));
+    }
+    const uint64_t index = sobol_interval_to_index(tabs, (uint32_t)rc.sobol.log2_resolution, j, (uint32_t)(px - rc.sobol.sb_min[0]), (uint32_t)(py - rc.sobol.sb_min[1]));
+    return P2(sobol_sample_float(tabs.m32, index, 5u), sobol_sample_float(tabs.m32, index, 6u));
+}
+
+// The frame of ao.rs:77-80 without the face-forward (there is no camera ray): s = normalize(dpdu), t = cross(n, s), n
+struct BakeFrame { V3 n, sv, tv; };
+PT_DEV BakeFrame bake_frame(const SurfaceInteraction &si) { BakeFrame f; f.n = si.n; f.sv = normalize(si.dpdu); f.tv = cross(si.n, f.sv); return f; }
+
+// Element k of sample s of texel (px, py): origin, direction and weight (ao.rs:82-95; the direction sampling mirrors ao/ao_kernels.h:67-84)
+PT_DEV void bake_ray(const RenderConst &rc, const SobolTables &tabs, const SurfaceInteraction &si, const BakeFrame &f, int32_t px, int32_t py, uint64_t number,
+                     uint32_t cos_sample, float nsf, V3 &o, V3 &wo, float &w) {
+    const P2 u = bake_array_sample(rc, tabs, px, py, number);
+    V3 wi; float pdf;
+    if (cos_sample) { wi = cosine_sample_hemisphere(u); pdf = fabsf(wi.z) * kInvPi; }   // cosine_hemisphere_pdf (sampling.rs:195-197)
+    else {   // uniform_sample_sphere (sampling.rs:212-218), uniform_sphere_pdf
+        const float z = 1.0f - 2.0f * u.x;
+        const float r = sqrtf(maxf(1.0f - z * z, 0.0f));
+        const float phi = 2.0f * kPi * u.y;
+        float sn, cs; dm_sincosf(phi, sn, cs);
+        wi = V3(r * cs, r * sn, z); pdf = kInv4Pi;
+    }
+    wo = V3(f.sv.x * wi.x + f.tv.x * wi.y + f.n.x * wi.z, f.sv.y * wi.x + f.tv.y * wi.y + f.n.y * wi.z, f.sv.z * wi.x + f.tv.z * wi.y + f.n.z * wi.z);
+    o = offset_ray_origin(si.p, si.p_error, si.n, wo);   // SurfaceInteraction::spawn_ray (interaction.rs:32-36)
+    w = dot(wo, f.n) / (pdf * nsf);
+}
+
+// The packets [0, n_top) are the top-level accelerator's, one per top-level primitive or instance (scene_plan.hip: the packet order of every accelerator)
+__global__ __launch_bounds__(256) void k_bake_top(DeviceScene s, uint32_t n_top, uint8_t *top) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_top) return;
+    const uint32_t prim = s.leaf[i].prim;
+    if (!(s.leaf[i].flags & TP_INSTANCE) && prim < s.n_prims) top[prim] = 1;
+}
+
+// Why a selected primitive is no bake target (0: it is one). One thread per selected primitive leaves its code; a block leaves whether any of its 256 has one, so that
+// the host reads a word per block and, only when a selection is refused, the codes of one block.
+enum { kBakeOk = 0, kBakeQuadric = 1, kBakeInstanced = 2, kBakeNoUV = 3 };
+__global__ __launch_bounds__(256) void k_bake_check(DeviceScene s, const uint8_t *top, const uint32_t *selected, uint32_t n_selected, uint8_t *code, uint32_t *block_refused) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t c = kBakeOk;
+    if (i < n_selected) {
+        const uint32_t prim = selected[i], sh = s.prim_shape[prim], tri = sh & 0x3fffffffu;
+        if ((sh >> 30) != PT_SHAPE_TRIANGLE) c = kBakeQuadric;
+        else if (!top[prim]) c = kBakeInstanced;
+        else if (tri >= s.n_triangles || !(s.tri_flags[tri] & PT_TRI_HAS_UV)) c = kBakeNoUV;
+        code[i] = (uint8_t)c;
+    }
+    const int any = __syncthreads_or(c != kBakeOk);
+    if (threadIdx.x == 0) block_refused[blockIdx.x] = any ? 1u : 0u;
+}
+
+// The texel box of a triangle (mi355bake.h "Ownership": part of the contract, every operation float32 in this order): the texels whose centres the UV bounds can hold,
+// with a margin of a sixteenth of a texel plus size * 2.4e-7 -- more than the roundings of the bounds and of the centres amount to, so a centre the barycentrics of a
+// well-conditioned triangle contain is never cut off. It is a second condition and not a mere speed-up: the barycentrics of a sliver with a tiny determinant round
+// without bound and "contain" centres far from the triangle; the box denies it those. false: the triangle owns nothing.
+PT_DEV bool texel_box(const BakeAtlas &a, P2 uv0, P2 uv1, P2 uv2, uint32_t &x0, uint32_t &x1, uint32_t &y0, uint32_t &y1) {
+    const float ulo = fminf(uv0.x, fminf(uv1.x, uv2.x)) * (float)a.width, uhi = fmaxf(uv0.x, fmaxf(uv1.x, uv2.x)) * (float)a.width;
+    const float vlo = fminf(uv0.y, fminf(uv1.y, uv2.y)) * (float)a.height, vhi = fmaxf(uv0.y, fmaxf(uv1.y, uv2.y)) * (float)a.height;
+    // (a NaN, an infinity or a bound of 1e30 texels and more: no box)
+    if (!(ulo <= uhi && vlo <= vhi && fabsf(ulo) < 1e30f && fabsf(uhi) < 1e30f && fabsf(vlo) < 1e30f && fabsf(vhi) < 1e30f)) return false;
+    const float mx = 0.5625f + (float)a.width * 2.4e-7f, my = 0.5625f + (float)a.height * 2.4e-7f;
+    const float fx0 = fmaxf(floorf(ulo - mx), 0.0f), fx1 = fminf(ceilf(uhi - 1.0f + mx), (float)(a.width - 1u));
+    const float fy0 = fmaxf(floorf(vlo - my), 0.0f), fy1 = fminf(ceilf(vhi - 1.0f + my), (float)(a.height - 1u));
+    if (!(fx0 <= fx1 && fy0 <= fy1)) return false;
+    x0 = (uint32_t)fx0; x1 = min((uint32_t)fx1, a.width - 1u); y0 = (uint32_t)fy0; y1 = min((uint32_t)fy1, a.height - 1u);   // ((float)(size - 1) rounds up beyond 2^24)
+    return true;
+}
+
+// What a lane knows of its triangle: the UVs and its texel box clipped to rows [row0, row1) of the atlas
+struct RasterTri { P2 uv0, uv1, uv2; uint32_t prim, x0, y0, nx, ny; };
+PT_DEV void raster_texels(const BakeAtlas &a, const RasterTri &t, uint32_t first, uint32_t step, uint32_t *owner) {
+    const uint32_t n = t.nx * t.ny;
+    for (uint32_t i = first; i < n; i += step) {
+        const uint32_t x = t.x0 + i % t.nx, y = t.y0 + i / t.nx;
+        float b0, b1, b2;
+        if (uv_barycentrics(t.uv0, t.uv1, t.uv2, texel_centre(a, x, y), b0, b1, b2)) atomicMin(&owner[(size_t)y * a.width + x], t.prim);
+    }
+}
+// Selected triangles -> owner map. blockIdx.y is a band of `band_rows` atlas rows: a lane sets its triangle up and clips its box to the band. A small box is walked by
+// the lane itself; the large ones of a wave are taken one after the other by all 64 lanes (the set-up travels by __shfl), so that a quad over the whole atlas is
+// rastered by every wave of every band and not by one thread. The host gives one band to a selection of many triangles and many bands to a selection of few.
+__global__ __launch_bounds__(256) void k_bake_raster(DeviceScene s, BakeAtlas a, const uint32_t *selected, uint32_t n_selected, uint32_t band_rows, uint32_t *owner) {
+    const uint32_t row0 = blockIdx.y * band_rows, row1 = min(a.height, row0 + band_rows);
+    const uint32_t rounded = (n_selected + 63u) & ~63u;   // whole waves iterate together (the large boxes are shared)
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < rounded; i += gridDim.x * blockDim.x) {
+        RasterTri t; t.nx = t.ny = 0; t.x0 = t.y0 = 0; t.prim = PT_NONE;
+        if (i < n_selected) {
+            t.prim = selected[i];
+            tri_vertex_uvs(s, s.prim_shape[t.prim] & 0x3fffffffu, t.uv0, t.uv1, t.uv2);
+            uint32_t x0, x1, y0, y1;
+            if (texel_box(a, t.uv0, t.uv1, t.uv2, x0, x1, y0, y1)) {
+                y0 = max(y0, row0); y1 = min(y1, row1 - 1u);
+                if (y0 <= y1) { t.x0 = x0; t.y0 = y0; t.nx = x1 - x0 + 1u; t.ny = y1 - y0 + 1u; }
+            }
+        }
+        const uint32_t n = t.nx * t.ny;   // (<= 2^28 texels)
+        if (n != 0 && n <= kRasterOwnTexels) raster_texels(a, t, 0u, 1u, owner);
+        unsigned long long large = __ballot(n > kRasterOwnTexels);
+        while (large) {
+            const int src = __ffsll((long long)large) - 1;
+            large &= large - 1ull;
+            RasterTri g;
+            g.uv0 = P2(__shfl(t.uv0.x, src), __shfl(t.uv0.y, src)); g.uv1 = P2(__shfl(t.uv1.x, src), __shfl(t.uv1.y, src)); g.uv2 = P2(__shfl(t.uv2.x, src), __shfl(t.uv2.y, src));
+            g.prim = __shfl(t.prim, src); g.x0 = __shfl(t.x0, src); g.y0 = __shfl(t.y0, src); g.nx = __shfl(t.nx, src); g.ny = __shfl(t.ny, src);
+            raster_texels(a, g, lane_id(), 64u, owner);
+        }
+    }
+}
+
+// position = p, normal = the normalised shading normal of the owner's interaction; zeros where the texel has no owner
+__global__ __launch_bounds__(256) void k_bake_points(DeviceScene s, BakeAtlas a, const uint32_t *owner, float *position, float *normal) {
+    const uint32_t texel = blockIdx.x * blockDim.x + threadIdx.x;
+    if (texel >= a.n_texels) return;
+    const uint32_t prim = owner[texel];
+    V3 p(0.0f, 0.0f, 0.0f), n(0.0f, 0.0f, 0.0f);
+    if (prim != PT_NONE) {
+        SurfaceInteraction si;
+        texel_interaction(s, a, texel, prim, si);
+        p = si.p; n = normalize(si.sh_n);
+    }
+    if (position) { position[3 * (size_t)texel] = p.x; position[3 * (size_t)texel + 1] = p.y; position[3 * (size_t)texel + 2] = p.z; }
+    if (normal) { normal[3 * (size_t)texel] = n.x; normal[3 * (size_t)texel + 1] = n.y; normal[3 * (size_t)texel + 2] = n.z; }
+}
+
+// Per texel sample of the pass (item = sample-in-pass * slots + slot: the lanes of a wave are neighbouring texels of one sample): this chunk's AO rays
+__global__ __launch_bounds__(256) void k_bake_rays(DeviceScene s, RenderConst rc, SobolTables tabs, BakeAtlas a, BakeJob job) {
+    const uint32_t total = a.slots * job.s_count;
+    const uint32_t rounded = (total + 63u) & ~63u;   // whole waves iterate together (one ray-id reservation per wave)
+    for (uint32_t item = blockIdx.x * blockDim.x + threadIdx.x; item < rounded; item += gridDim.x * blockDim.x) {
+        uint32_t texel = PT_NONE, sl = 0, prim = PT_NONE;
+        if (item < total) { texel = slot_texel(a, item % a.slots); sl = item / a.slots; if (texel != PT_NONE) prim = job.owner[texel]; }
+        const bool found = prim != PT_NONE;
+        // one atomic per wave: the wave's owned texels take consecutive blocks of kn ray ids, in lane order
+        const uint32_t first = wave_reserve(job.ray_count, found, job.kn);
+        if (item >= total) continue;
+        if (!found) { job.base[item] = PT_NONE; continue; }
+        job.base[item] = first;
+        SurfaceInteraction si;
+        texel_interaction(s, a, texel, prim, si);
+        const BakeFrame f = bake_frame(si);
+        const int32_t px = (int32_t)(texel % a.width), py = (int32_t)(texel / a.width);
+        const uint64_t sample = (uint64_t)job.s_begin + sl;
+        const float nsf = (float)job.nsamples;
+        for (uint32_t kk = 0; kk < job.kn; ++kk) {
+            V3 o, wo; float w;
+            bake_ray(rc, tabs, si, f, px, py, sample * job.nsamples + job.k0 + kk, job.cos_sample, nsf, o, wo, w);
+            const uint32_t id = first + kk;
+            job.ray[2 * (size_t)id] = make_float4(o.x, o.y, o.z, wo.x);
+            job.ray[2 * (size_t)id + 1] = make_float4(wo.y, wo.z, 0.0f, 0.0f);
+            job.w[id] = w;
+        }
+    }
+}
+
+// ao_w += the unoccluded rays' wi and w, in (sample, element) order (ao.rs:96-98): one thread per texel walks the pass's samples in order and, in each, this chunk's
+// elements. (A pass of more than one sample has ONE chunk -- the host sees to it --, so the chain of additions of a texel is (s, k) ascending however the job is cut.)
+__global__ __launch_bounds__(256) void k_bake_accum(BakeAtlas a, BakeJob job) {
+    const uint32_t texel = blockIdx.x * blockDim.x + threadIdx.x;
+    if (texel >= a.n_texels) return;
+    if (job.owner[texel] == PT_NONE) return;
+    const uint32_t slot = texel_slot(a, texel);
+    float4 acc = job.ao_w[texel];
+    for (uint32_t sl = 0; sl < job.s_count; ++sl) {
+        const uint32_t first = job.base[(size_t)sl * a.slots + slot];
+        for (uint32_t kk = 0; kk < job.kn; ++kk) {
+            const uint32_t id = first + kk;
+            if (job.occluded[id]) continue;
+            const float4 r0 = job.ray[2 * (size_t)id], r1 = job.ray[2 * (size_t)id + 1];
+            acc.x += r0.w; acc.y += r1.x; acc.z += r1.y; acc.w += job.w[id];
+        }
+    }
+    job.ao_w[texel] = acc;
+}
+
+// One iteration of pt_bake_dilate (mi355bake.h): src / covered -> dst / covered_next
+template <int CH>
+__global__ __launch_bounds__(256) void k_bake_dilate(BakeAtlas a, const float *src, const uint8_t *covered, float *dst, uint8_t *covered_next) {
+    const uint32_t texel = blockIdx.x * blockDim.x + threadIdx.x;
+    if (texel >= a.n_texels) return;
+    const int32_t x = (int32_t)(texel % a.width), y = (int32_t)(texel / a.width);
+    float sum[CH]; uint32_t n = 0;
+    for (int c = 0; c < CH; ++c) sum[c] = 0.0f;
+    const bool own = covered[texel] != 0;
+    if (!own) {
+        for (int32_t dy = -1; dy <= 1; ++dy) for (int32_t dx = -1; dx <= 1; ++dx) {
+            if (dx == 0 && dy == 0) continue;
+            const int32_t nx = x + dx, ny = y + dy;
+            if (nx < 0 || ny < 0 || nx >= (int32_t)a.width || ny >= (int32_t)a.height) continue;
+            const size_t q = (size_t)ny * a.width + (size_t)nx;
+            if (!covered[q]) continue;
+            for (int c = 0; c < CH; ++c) sum[c] += src[q * CH + c];
+            ++n;
+        }
+    }
+    const bool fill = !own && n > 0;
+    const float nf = (float)n;
+    for (int c = 0; c < CH; ++c) dst[(size_t)texel * CH + c] = fill ? sum[c] / nf : src[(size_t)texel * CH + c];
+    covered_next[texel] = (own || fill) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void k_bake_covered(BakeAtlas a, const uint32_t *owner, uint8_t *covered) {
+    const uint32_t texel = blockIdx.x * blockDim.x + threadIdx.x;
+    if (texel < a.n_texels) covered[texel] = owner[texel] != PT_NONE ? 1 : 0;
+}
+
+// pt_bake_rays: ray i = element[i] of sample[i] of texel[i], by bake_ray
+__global__ __launch_bounds__(256) void k_bake_probe(DeviceScene s, RenderConst rc, SobolTables tabs, BakeAtlas a, const uint32_t *owner, uint32_t nsamples, uint32_t cos_sample, uint32_t n,
+                                                    const uint32_t *texel, const uint32_t *sample, const uint32_t *element, float *out_o, float *out_d, float *out_w, uint8_t *found) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t tx = texel[i];
+    const uint32_t prim = tx < a.n_texels ? owner[tx] : PT_NONE;
+    V3 o(0.0f, 0.0f, 0.0f), wo(0.0f, 0.0f, 0.0f); float w = 0.0f;
+    if (prim != PT_NONE) {
+        SurfaceInteraction si;
+        texel_interaction(s, a, tx, prim, si);
+        bake_ray(rc, tabs, si, bake_frame(si), (int32_t)(tx % a.width), (int32_t)(tx / a.width), (uint64_t)sample[i] * nsamples + element[i], cos_sample, (float)nsamples, o, wo, w);
+    }
+    out_o[3 * (size_t)i] = o.x; out_o[3 * (size_t)i + 1] = o.y; out_o[3 * (size_t)i + 2] = o.z;
+    out_d[3 * (size_t)i] = wo.x; out_d[3 * (size_t)i + 1] = wo.y; out_d[3 * (size_t)i + 2] = wo.z;
+    out_w[i] = w; found[i] = prim != PT_NONE ? 1 : 0;
+}
+
+}  // namespace ptbake

@@ -1,0 +1,371 @@
+// bake_render.hip -- pt_bake_render / pt_bake_render_samples / pt_bake_pass_size / pt_bake_resolve / pt_bake_dilate / pt_bake_rays (include/mi355bake.h): ambient
+// occlusion, bent normals, positions and shading normals of a UV-mapped mesh in its own texture space. Per call:
+//   k_bake_top, k_bake_check       which primitives the top-level accelerator holds; why a selected primitive is no bake target (one word per 256 of them comes back)
+//   k_bake_raster                  the selected triangles' owner map
+//   k_bake_points                  position / normal planes, when wanted
+//   per pass of S samples of every texel, per chunk of <= 64 AO rays per texel sample (ao_w wanted):
+//     k_bake_rays                  the chunk's rays from each owned texel (dimensions 5 and 6 of sample numbers s * nsamples + k)
+//     k_trace<any>                 the rays' any-hit walk ("shadow", t_max = max_distance) -- libmi355pt's
+//     k_bake_accum                 ao_w += the unoccluded rays' wi and w, in order
+// There is no camera, no path state and no film, so the bake does not go through render_frame: the scene's stream, counters and traversal spill area come from
+// ensure_workspace with no paths and no film, the pass size from choose_pass_size with the bake's bytes per texel sample, the sampler set-up from fill_render_const
+// for a width x height image, the traversal through trace_job / trace_sub / traced as libmi355ao's AO rays go.
+#include "../csrc/host_common.h"
+#include "../../include/mi355bake.h"
+#include "bake_kernels.h"
+
+using namespace ptbake;
+
+namespace {
+
+constexpr double kBakeMemFraction = 0.5;           // of the device's free memory, for a pass the caller leaves to the library
+constexpr size_t kBakeMaxRays = (size_t)1 << 31;   // ray ids per chunk (32-bit ids, k_trace's queue index)
+constexpr size_t kBakeRayBytes = 32 + 4 + 4;       // ray record, weight, any-hit flag
+constexpr size_t kBakeMaxTexels = (size_t)1 << 28;
+constexpr uint32_t kRasterFewTriangles = 16384;    // a selection of fewer triangles is rastered in row bands (k_bake_raster)
+
+struct Geometry { RenderConst rc; BakeAtlas atlas; uint32_t S; uint32_t K; };
+
+int oom(const char *what, hipError_t e) { (void)hipGetLastError(); return fail(PT_ERR_OUT_OF_MEMORY, std::string("bake ") + what + ": " + hipGetErrorString(e)); }
+#define BAKE_ALLOC(tmp, ptr, bytes, what) do { if (hipError_t _a = (tmp).alloc(&(ptr), (bytes)); _a != hipSuccess) return oom(what, _a); } while (0)
+
+// ---- what is checked before the device is touched
+int check_atlas(uint32_t width, uint32_t height) {
+    if (width == 0 || height == 0) return fail(PT_ERR_INVALID_ARG, "bake: width and height must be > 0");
+    if ((size_t)width * height > kBakeMaxTexels) return fail(PT_ERR_INVALID_ARG, "bake: the atlas holds more than 2^28 texels");
+    return PT_OK;
+}
+int check_params(const PtBakeParams *bp) {
+    if (int st = check_atlas(bp->width, bp->height)) return st;
+    if (bp->spp == 0) return fail(PT_ERR_INVALID_ARG, "bake: spp must be > 0");
+    if (bp->nsamples == 0) return fail(PT_ERR_INVALID_ARG, "bake: nsamples must be > 0");
+    if (!(bp->max_distance > 0.0f)) return fail(PT_ERR_INVALID_ARG, "bake: max_distance must be > 0 (INFINITY: unbounded)");
+    if (bp->sampler_type != PT_SAMPLER_SOBOL && bp->sampler_type != PT_SAMPLER_HALTON) return fail(PT_ERR_INVALID_ARG, "bake: sampler_type must be PT_SAMPLER_SOBOL or PT_SAMPLER_HALTON");
+    return PT_OK;
+}
+int check_range(const PtBakeParams *bp, uint32_t first, uint32_t n) {
+    if (n == 0) return fail(PT_ERR_INVALID_ARG, "bake: n_samples must be > 0");
+    if ((uint64_t)first + n > bp->spp) return fail(PT_ERR_INVALID_ARG, "bake: sample range [" + std::to_string(first) + ", " + std::to_string((uint64_t)first + n) + ") exceeds the job's spp = " + std::to_string(bp->spp));
+    return PT_OK;
+}
+int check_selection(const uint8_t *prim_select, uint32_t n_prims) {
+    for (uint32_t i = 0; i < n_prims; ++i) if (prim_select[i]) return PT_OK;
+    return fail(PT_ERR_INVALID_ARG, "bake: no primitive is selected");
+}
+
+// (the scene's primitive count is the handle's host side)
+int check_prim_count(const pt_scene *sc, uint32_t n_prims) {
+    if (n_prims != sc->ds.n_prims) return fail(PT_ERR_INVALID_ARG, "bake: prim_select has " + std::to_string(n_prims) + " entries, the scene " + std::to_string(sc->ds.n_prims) + " primitives");
+    return PT_OK;
+}
+
+// The sampler of a width x height image (fill_render_const), the checks on its sample numbers (ao_render.hip: ao_geometry) and the pass size
+int bake_geometry(pt_scene *sc, const PtBakeParams *bp, uint32_t n_samples, Geometry &g) {
+    if (sc->device != g_device) { if (int st = bind_device(sc->device)) return st; }
+    PtRenderParams rp{};
+    rp.sample_bounds[2] = rp.pixel_bounds[2] = rp.cropped_pixel_bounds[2] = (int32_t)bp->width;
+    rp.sample_bounds[3] = rp.pixel_bounds[3] = rp.cropped_pixel_bounds[3] = (int32_t)bp->height;
+    rp.full_resolution[0] = (int32_t)bp->width; rp.full_resolution[1] = (int32_t)bp->height;
+    for (int i = 0; i < 4; ++i) rp.raster_to_camera[5 * i] = rp.camera_to_world[5 * i] = 1.0f;   // (not read: there is no camera)
+    rp.spp = bp->spp; rp.sampler_type = bp->sampler_type; rp.filter_radius[0] = rp.filter_radius[1] = 1.0f; rp.tile_world = 1;
+    RenderConst &rc = g.rc;
+    fill_render_const(&rp, rc);
+    if (rc.sobol.log2_resolution > 25) return fail(PT_ERR_INVALID_ARG, "bake: the atlas exceeds the 2^25 Sobol' pixel grid");
+    g.atlas = make_atlas(bp->width, bp->height);
+    // The array values of a texel are sample numbers 0 .. spp * nsamples - 1: the limits of ao_geometry (ao_render.hip:39-48) for both samplers
+    const uint64_t numbers = (uint64_t)bp->spp * bp->nsamples;
+    if (rc.halton.enabled) {
+        if (numbers > ~0ull / rc.halton.stride - 1) return fail(PT_ERR_INVALID_ARG, "bake: spp x nsamples sample numbers per texel exceed the Halton sampler's 64-bit index");
+    } else if (numbers - 1 >= (1ull << (52 - 2 * rc.sobol.log2_resolution))) {
+        return fail(PT_ERR_INVALID_ARG, "bake: spp x nsamples = " + std::to_string(numbers) + " sample numbers per texel exceed the 2^" + std::to_string(52 - 2 * rc.sobol.log2_resolution) +
+                                         " the Sobol' tables serve at this resolution");
+    }
+    g.K = std::min<uint32_t>(bp->nsamples, kBakeChunk);
+    uint32_t S = bp->spp_per_pass;
+    // (per texel sample: the ray id base and the chunk's rays. The rule counts libmi355pt's path workspace too, which the bake does not allocate: the choice errs small)
+    if (S == 0) S = choose_pass_size(sc, g.atlas.slots, n_samples, 1, false, PassBudget{4 + (size_t)g.K * kBakeRayBytes, kBakeMemFraction, kBakeMaxRays / g.K});
+    S = std::min(S, n_samples);
+    // The additions to a texel are in (sample, element) order: a pass of several samples is accumulated sample by sample within ONE chunk; with more than one chunk
+    // per sample a pass is one sample
+    if (bp->nsamples > kBakeChunk) S = 1;
+    if ((size_t)g.atlas.slots * S * g.K > kBakeMaxRays) return fail(PT_ERR_INVALID_ARG, "bake: pass too large: texels x samples per pass x min(nsamples, 64) AO rays per launch > 2^31 (lower spp_per_pass)");
+    g.S = S;
+    return PT_OK;
+}
+
+// The scene's stream, counters and traversal spill area (no paths, no film), and a clean slate for the call's statistics
+int begin_call(pt_scene *sc, bool profile) {
+    if (int st = ensure_workspace(sc, 0, 0)) return st;
+    sc->profile = profile;
+    sc->drop_timings();
+    sc->stats.clear();
+    sc->counters = PtCounters{};
+    HIP_TRY(hipMemsetAsync(sc->dc, 0, sizeof(DevCounters), sc->stream));
+    HIP_TRY(hipMemsetAsync(sc->qc, 0, sizeof(QCounters), sc->stream));
+    return PT_OK;
+}
+
+dim3 texel_grid(const BakeAtlas &a) { return dim3((unsigned)(((size_t)a.n_texels + 255) / 256)); }
+
+// The selection on the device: the ascending list of selected primitives, every one of which must be a top-level triangle of a mesh with UVs. The check runs on the
+// device (k_bake_top, k_bake_check); what comes back is one word per 256 selected primitives and, for a refused selection, the codes of the first refused block.
+// (prim_select itself is walked on the host, a byte per primitive, and the list uploaded, 4 bytes per selected primitive: on every call, a continuation's included.)
+int upload_selection(pt_scene *sc, const uint8_t *prim_select, uint32_t n_prims, DevTmp &tmp, uint32_t *&d_selected, uint32_t &n_selected) {
+    const DeviceScene &ds = sc->ds;
+    std::vector<uint32_t> selected;
+    for (uint32_t p = 0; p < n_prims; ++p) if (prim_select[p]) selected.push_back(p);
+    n_selected = (uint32_t)selected.size();
+    const uint32_t n_top = (uint32_t)sc->ordered.size(), n_blocks = (n_selected + 255) / 256;
+    uint8_t *d_top = nullptr, *d_code = nullptr; uint32_t *d_refused = nullptr;
+    BAKE_ALLOC(tmp, d_top, n_prims, "selection"); BAKE_ALLOC(tmp, d_selected, (size_t)n_selected * 4, "selection");
+    BAKE_ALLOC(tmp, d_code, n_selected, "selection"); BAKE_ALLOC(tmp, d_refused, (size_t)n_blocks * 4, "selection");
+    HIP_TRY(hipMemsetAsync(d_top, 0, n_prims, sc->stream));
+    HIP_TRY(hipMemcpyAsync(d_selected, selected.data(), (size_t)n_selected * 4, hipMemcpyHostToDevice, sc->stream));
+    sc->begin("bake_select", (uint64_t)n_top + n_selected);
+    if (n_top > 0 && ds.n_nodes > 0) launch(sc, "ptbake::k_bake_top", k_bake_top, dim3((n_top + 255) / 256), dim3(256), ds, n_top, d_top);
+    launch(sc, "ptbake::k_bake_check", k_bake_check, dim3(n_blocks), dim3(256), ds, (const uint8_t *)d_top, (const uint32_t *)d_selected, n_selected, d_code, d_refused);
+    sc->end();
+    HIP_TRY(hipGetLastError());
+    std::vector<uint32_t> refused(n_blocks);
+    HIP_TRY(hipMemcpyAsync(refused.data(), d_refused, (size_t)n_blocks * 4, hipMemcpyDeviceToHost, sc->stream));
+    HIP_TRY(hipStreamSynchronize(sc->stream));   // (`selected` is on the device by now, too)
+    for (uint32_t blk = 0; blk < n_blocks; ++blk) {
+        if (!refused[blk]) continue;
+        const uint32_t first = blk * 256u, n = std::min(256u, n_selected - first);
+        uint8_t code[256];
+        HIP_TRY(hipMemcpy(code, d_code + first, n, hipMemcpyDeviceToHost));
+        for (uint32_t k = 0; k < n; ++k) {
+            const std::string who = "bake: selected primitive " + std::to_string(selected[first + k]);
+            if (code[k] == kBakeQuadric) return fail(PT_ERR_UNSUPPORTED, who + " is a sphere or disk: only triangles have a UV atlas here");
+            if (code[k] == kBakeInstanced) return fail(PT_ERR_UNSUPPORTED, who + " belongs to an instanced object: instanced geometry is not baked");
+            if (code[k] == kBakeNoUV) return fail(PT_ERR_UNSUPPORTED, who + " is a triangle of a mesh without UVs");
+        }
+    }
+    return PT_OK;
+}
+
+// Owner map of the selection. Few triangles: row bands, so that a large triangle's box is shared among the waves of many blocks; many: one band, a triangle per lane.
+int raster(pt_scene *sc, const BakeAtlas &a, const uint32_t *d_selected, uint32_t n_selected, uint32_t *d_owner) {
+    HIP_TRY(hipMemsetAsync(d_owner, 0xff, (size_t)a.n_texels * 4, sc->stream));
+    // (a two-triangle quad over a 4096^2 atlas: one thread per triangle 3806 ms, one wave sharing each box 107.9 ms, bands of 64 rows 1.71 ms, of 16 rows 0.44 ms, of 8
+    // rows 0.24 ms; 4.3 M sub-texel triangles on 2048^2 in one band: 0.15 ms -- profiles/r6/NOTES.md)
+    const uint32_t band_rows = std::min(a.height, n_selected >= kRasterFewTriangles ? a.height : std::max<uint32_t>(4, (a.height + 511) / 512));
+    const uint32_t bands = (a.height + band_rows - 1) / band_rows;
+    const uint32_t blocks = std::max(1u, std::min<uint32_t>((n_selected + 255) / 256, (uint32_t)g_num_cus * 8u));
+    sc->begin("bake_raster", n_selected);
+    launch(sc, "ptbake::k_bake_raster", k_bake_raster, dim3(blocks, bands), dim3(256), sc->ds, a, d_selected, n_selected, band_rows, d_owner);
+    sc->end();
+    HIP_TRY(hipGetLastError());
+    return PT_OK;
+}
+
+// The rays of one pass: samples [s_begin, s_begin + s_count) of every texel, chunk by chunk
+struct RayBuffers { float4 *ray = nullptr; float *w = nullptr; uint32_t *occ = nullptr, *base = nullptr, *count = nullptr; };
+int bake_pass(pt_scene *sc, const Geometry &g, const PtBakeParams *bp, uint32_t s_begin, uint32_t s_count, const uint32_t *d_owner, float4 *d_ao, const RayBuffers &b) {
+    const uint32_t items = g.atlas.slots * s_count;
+    const dim3 blocks = blocks_for(items, 16u);
+    for (uint32_t k0 = 0; k0 < bp->nsamples; k0 += g.K) {
+        BakeJob job{};
+        job.nsamples = bp->nsamples; job.cos_sample = bp->cos_sample ? 1u : 0u;
+        job.k0 = k0; job.kn = std::min(g.K, bp->nsamples - k0);
+        job.s_begin = s_begin; job.s_count = s_count;
+        job.owner = d_owner; job.ray = b.ray; job.w = b.w; job.base = b.base; job.ray_count = b.count; job.occluded = b.occ; job.ao_w = d_ao;
+        HIP_TRY(hipMemsetAsync(b.count, 0, 4, sc->stream));
+        HIP_TRY(hipMemsetAsync(sc->qc->head, 0, sizeof sc->qc->head, sc->stream));
+        sc->begin("bake_rays", (uint64_t)items * job.kn);
+        launch(sc, "ptbake::k_bake_rays", k_bake_rays, blocks, dim3(256), sc->ds, g.rc, g_tabs, g.atlas, job);
+        sc->end();
+        HIP_TRY(hipGetLastError());
+        TraceJob tj = trace_job(sc, 2);   // ray ids, no queue: Scene::intersect_p of the spawned rays (ao.rs:94) with t_max = max_distance
+        tj.sub[0] = trace_sub(nullptr, b.count, (const float *)b.ray, 8, bp->max_distance, 2);
+        tj.sub[0].out_word = b.occ; tj.sub[0].out_word_stride = 1; tj.sub[0].any = 1;
+        if (int st = traced(sc, "shadow", 1, tj, items * job.kn)) return st;   // (an upper bound: the launch reads the count of rays spawned)
+        sc->begin("bake_accum", items);
+        launch(sc, "ptbake::k_bake_accum", k_bake_accum, texel_grid(g.atlas), dim3(256), g.atlas, job);
+        sc->end();
+        HIP_TRY(hipGetLastError());
+    }
+    return PT_OK;
+}
+
+int end_call(pt_scene *sc) {
+    QCounters h;
+    if (int st = sync_queue_counters(sc, h)) return st;   // (a status a kernel raised fails the call here)
+    sc->resolve_timings();
+    read_counters(sc);
+    return PT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+__attribute__((visibility("default"))) int pt_bake_pass_size(pt_scene *sc, const PtBakeParams *bp, uint32_t *spp_per_pass) {
+    if (!sc || !bp || !spp_per_pass) return fail(PT_ERR_INVALID_ARG, "null argument");
+    if (int st = check_params(bp)) return st;
+    Geometry g;
+    if (int st = bake_geometry(sc, bp, bp->spp, g)) return st;
+    *spp_per_pass = g.S;
+    return PT_OK;
+}
+
+__attribute__((visibility("default"))) int pt_bake_render(pt_scene *sc, const PtBakeParams *bp, const uint8_t *prim_select, uint32_t n_prims, const PtBakeBuffers *buffers, int buffers_are_device) {
+    if (!sc || !bp || !prim_select || !buffers) return fail(PT_ERR_INVALID_ARG, "null argument");
+    if (int st = check_params(bp)) return st;
+    return pt_bake_render_samples(sc, bp, prim_select, n_prims, 0, bp->spp, buffers, buffers_are_device);
+}
+
+__attribute__((visibility("default"))) int pt_bake_render_samples(pt_scene *sc, const PtBakeParams *bp, const uint8_t *prim_select, uint32_t n_prims, uint32_t first, uint32_t n_samples,
+                                                                  const PtBakeBuffers *buffers, int buffers_are_device) {
+    if (!sc || !bp || !prim_select || !buffers) return fail(PT_ERR_INVALID_ARG, "null argument");
+    if (int st = check_params(bp)) return st;
+    if (!buffers->owner && !buffers->position && !buffers->normal && !buffers->ao_w) return fail(PT_ERR_INVALID_ARG, "bake: all four planes are NULL");
+    if (int st = check_range(bp, first, n_samples)) return st;
+    if (int st = check_selection(prim_select, n_prims)) return st;
+    if (int st = check_prim_count(sc, n_prims)) return st;   // (all of the above before the device is touched)
+    Geometry g;
+    if (int st = bake_geometry(sc, bp, n_samples, g)) return st;
+    if (int st = begin_call(sc, bp->profile != 0)) return st;
+    const BakeAtlas &a = g.atlas;
+    const size_t n = a.n_texels;
+    DevTmp tmp;   // (freed when the call returns, however it ends: a bake leaves the device's free memory as it found it, apart from the scene's workspace)
+    uint32_t *d_selected = nullptr, n_selected = 0;
+    if (int st = upload_selection(sc, prim_select, n_prims, tmp, d_selected, n_selected)) return st;
+    const bool dev = buffers_are_device != 0;
+    uint32_t *d_owner = dev ? buffers->owner : nullptr;
+    if (!d_owner) BAKE_ALLOC(tmp, d_owner, n * 4, "owner map");
+    if (int st = raster(sc, a, d_selected, n_selected, d_owner)) return st;
+    float *d_pos = dev ? buffers->position : nullptr, *d_nrm = dev ? buffers->normal : nullptr;
+    if (buffers->position || buffers->normal) {
+        if (buffers->position && !d_pos) BAKE_ALLOC(tmp, d_pos, n * 12, "position plane");
+        if (buffers->normal && !d_nrm) BAKE_ALLOC(tmp, d_nrm, n * 12, "normal plane");
+        sc->begin("bake_points", n);
+        launch(sc, "ptbake::k_bake_points", k_bake_points, texel_grid(a), dim3(256), sc->ds, a, (const uint32_t *)d_owner, d_pos, d_nrm);
+        sc->end();
+        HIP_TRY(hipGetLastError());
+    }
+    float4 *d_ao = dev ? reinterpret_cast<float4 *>(buffers->ao_w) : nullptr;
+    if (buffers->ao_w) {
+        if (!d_ao) {
+            BAKE_ALLOC(tmp, d_ao, n * 16, "ao plane");
+            HIP_TRY(hipMemcpyAsync(d_ao, buffers->ao_w, n * 16, hipMemcpyHostToDevice, sc->stream));   // (added to)
+        }
+        RayBuffers b;
+        const size_t items = (size_t)a.slots * g.S, rays = items * g.K;
+        BAKE_ALLOC(tmp, b.ray, rays * 32, "rays"); BAKE_ALLOC(tmp, b.w, rays * 4, "rays"); BAKE_ALLOC(tmp, b.occ, rays * 4, "rays");
+        BAKE_ALLOC(tmp, b.base, items * 4, "rays"); BAKE_ALLOC(tmp, b.count, 4, "rays");
+        for (uint32_t s0 = first, end = first + n_samples; s0 < end; s0 += g.S)
+            if (int st = bake_pass(sc, g, bp, s0, std::min(g.S, end - s0), d_owner, d_ao, b)) return st;
+    }
+    if (int st = end_call(sc)) return st;
+    if (!dev) {   // (host planes are written once everything has succeeded)
+        if (buffers->owner) HIP_TRY(hipMemcpy(buffers->owner, d_owner, n * 4, hipMemcpyDeviceToHost));
+        if (buffers->position) HIP_TRY(hipMemcpy(buffers->position, d_pos, n * 12, hipMemcpyDeviceToHost));
+        if (buffers->normal) HIP_TRY(hipMemcpy(buffers->normal, d_nrm, n * 12, hipMemcpyDeviceToHost));
+        if (buffers->ao_w) HIP_TRY(hipMemcpy(buffers->ao_w, d_ao, n * 16, hipMemcpyDeviceToHost));
+    }
+    return PT_OK;
+}
+
+__attribute__((visibility("default"))) int pt_bake_resolve(const float *ao_w, uint32_t n_texels, uint32_t spp, float *ao, float *bent_xyz) {
+    if (!ao_w || (!ao && !bent_xyz)) return fail(PT_ERR_INVALID_ARG, "null argument");
+    if (spp == 0) return fail(PT_ERR_INVALID_ARG, "bake: spp must be > 0");
+    // (sum w / spp is ao.rs's radiance of the texel: pi where nothing occludes under cosine sampling. The map is that over pi: 1 for an open surface)
+    const float sf = (float)spp * ptd::kPi;
+    for (size_t i = 0; i < n_texels; ++i) {
+        const float x = ao_w[4 * i], y = ao_w[4 * i + 1], z = ao_w[4 * i + 2], w = ao_w[4 * i + 3];
+        const bool any = x != 0.0f || y != 0.0f || z != 0.0f || w != 0.0f;
+        if (ao) ao[i] = any ? w / sf : 0.0f;
+        if (bent_xyz) {
+            const float len = std::sqrt(x * x + y * y + z * z);
+            const bool ok = any && len > 0.0f;
+            const float inv = ok ? 1.0f / len : 0.0f;
+            bent_xyz[3 * i] = ok ? x * inv : 0.0f; bent_xyz[3 * i + 1] = ok ? y * inv : 0.0f; bent_xyz[3 * i + 2] = ok ? z * inv : 0.0f;
+        }
+    }
+    return PT_OK;
+}
+
+__attribute__((visibility("default"))) int pt_bake_dilate(pt_scene *sc, const uint32_t *owner, float *plane, uint32_t channels, uint32_t width, uint32_t height, uint32_t iterations, int buffers_are_device) {
+    if (!sc || !owner || !plane) return fail(PT_ERR_INVALID_ARG, "null argument");
+    if (int st = check_atlas(width, height)) return st;
+    if (channels < 1 || channels > 4) return fail(PT_ERR_INVALID_ARG, "bake: a plane has 1 .. 4 channels");
+    if (iterations == 0) return PT_OK;   // (all of the above before the device is touched)
+    if (sc->device != g_device) { if (int st = bind_device(sc->device)) return st; }
+    if (int st = ensure_workspace(sc, 0, 0)) return st;   // (the scene's stream; no paths, no film)
+    sc->drop_timings();
+    const BakeAtlas a = make_atlas(width, height);
+    const size_t n = a.n_texels, bytes = n * channels * 4;
+    DevTmp tmp;
+    const bool dev = buffers_are_device != 0;
+    const uint32_t *d_owner = owner;
+    float *buf[2] = {plane, nullptr};
+    uint8_t *cov[2] = {nullptr, nullptr};
+    if (!dev) {
+        uint32_t *up = nullptr;
+        BAKE_ALLOC(tmp, up, n * 4, "dilation"); BAKE_ALLOC(tmp, buf[0], bytes, "dilation");
+        HIP_TRY(hipMemcpyAsync(up, owner, n * 4, hipMemcpyHostToDevice, sc->stream));
+        HIP_TRY(hipMemcpyAsync(buf[0], plane, bytes, hipMemcpyHostToDevice, sc->stream));
+        d_owner = up;
+    }
+    BAKE_ALLOC(tmp, buf[1], bytes, "dilation"); BAKE_ALLOC(tmp, cov[0], n, "dilation"); BAKE_ALLOC(tmp, cov[1], n, "dilation");
+    sc->begin("bake_dilate", n);
+    launch(sc, "ptbake::k_bake_covered", k_bake_covered, texel_grid(a), dim3(256), a, d_owner, cov[0]);
+    sc->end();
+    int cur = 0;
+    for (uint32_t it = 0; it < iterations; ++it, cur ^= 1) {
+        sc->begin("bake_dilate", n);
+        const float *src = buf[cur]; const uint8_t *cs = cov[cur];
+        switch (channels) {
+        case 1: launch(sc, "ptbake::k_bake_dilate<1>", k_bake_dilate<1>, texel_grid(a), dim3(256), a, src, cs, buf[cur ^ 1], cov[cur ^ 1]); break;
+        case 2: launch(sc, "ptbake::k_bake_dilate<2>", k_bake_dilate<2>, texel_grid(a), dim3(256), a, src, cs, buf[cur ^ 1], cov[cur ^ 1]); break;
+        case 3: launch(sc, "ptbake::k_bake_dilate<3>", k_bake_dilate<3>, texel_grid(a), dim3(256), a, src, cs, buf[cur ^ 1], cov[cur ^ 1]); break;
+        default: launch(sc, "ptbake::k_bake_dilate<4>", k_bake_dilate<4>, texel_grid(a), dim3(256), a, src, cs, buf[cur ^ 1], cov[cur ^ 1]); break;
+        }
+        sc->end();
+    }
+    HIP_TRY(hipGetLastError());
+    if (dev) { if (buf[cur] != plane) HIP_TRY(hipMemcpyAsync(plane, buf[cur], bytes, hipMemcpyDeviceToDevice, sc->stream)); }
+    else HIP_TRY(hipMemcpyAsync(plane, buf[cur], bytes, hipMemcpyDeviceToHost, sc->stream));
+    HIP_TRY(hipStreamSynchronize(sc->stream));
+    sc->resolve_timings();
+    return PT_OK;
+}
+
+__attribute__((visibility("default"))) int pt_bake_rays(pt_scene *sc, const PtBakeParams *bp, const uint8_t *prim_select, uint32_t n_prims, uint32_t n, const uint32_t *texel, const uint32_t *sample,
+                                                        const uint32_t *element, float *out_o, float *out_d, float *out_w, uint8_t *found) {
+    if (!sc || !bp || !prim_select || !texel || !sample || !element || !out_o || !out_d || !out_w || !found) return fail(PT_ERR_INVALID_ARG, "null argument");
+    if (int st = check_params(bp)) return st;
+    if (int st = check_selection(prim_select, n_prims)) return st;
+    for (uint32_t i = 0; i < n; ++i)
+        if (sample[i] >= bp->spp || element[i] >= bp->nsamples) return fail(PT_ERR_INVALID_ARG, "bake: ray " + std::to_string(i) + " names a sample or element outside the job");
+    if (int st = check_prim_count(sc, n_prims)) return st;
+    Geometry g;
+    PtBakeParams one = *bp; one.spp_per_pass = 1;
+    if (int st = bake_geometry(sc, &one, bp->spp, g)) return st;
+    if (n == 0) return PT_OK;
+    if (int st = begin_call(sc, false)) return st;
+    DevTmp tmp;
+    uint32_t *d_selected = nullptr, n_selected = 0, *d_owner = nullptr, *d_in = nullptr; float *d_out = nullptr; uint8_t *d_found = nullptr;
+    if (int st = upload_selection(sc, prim_select, n_prims, tmp, d_selected, n_selected)) return st;
+    BAKE_ALLOC(tmp, d_owner, (size_t)g.atlas.n_texels * 4, "owner map");
+    if (int st = raster(sc, g.atlas, d_selected, n_selected, d_owner)) return st;
+    BAKE_ALLOC(tmp, d_in, (size_t)n * 12, "rays"); BAKE_ALLOC(tmp, d_out, (size_t)n * 28, "rays"); BAKE_ALLOC(tmp, d_found, n, "rays");
+    HIP_TRY(hipMemcpyAsync(d_in, texel, (size_t)n * 4, hipMemcpyHostToDevice, sc->stream));
+    HIP_TRY(hipMemcpyAsync(d_in + n, sample, (size_t)n * 4, hipMemcpyHostToDevice, sc->stream));
+    HIP_TRY(hipMemcpyAsync(d_in + 2 * (size_t)n, element, (size_t)n * 4, hipMemcpyHostToDevice, sc->stream));
+    sc->begin("bake_probe", n);
+    launch(sc, "ptbake::k_bake_probe", k_bake_probe, dim3((n + 255) / 256), dim3(256), sc->ds, g.rc, g_tabs, g.atlas, (const uint32_t *)d_owner, bp->nsamples, bp->cos_sample ? 1u : 0u, n,
+           (const uint32_t *)d_in, (const uint32_t *)(d_in + n), (const uint32_t *)(d_in + 2 * (size_t)n), d_out, d_out + 3 * (size_t)n, d_out + 6 * (size_t)n, d_found);
+    sc->end();
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(sc->stream));
+    sc->resolve_timings();
+    HIP_TRY(hipMemcpy(out_o, d_out, (size_t)n * 12, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_d, d_out + 3 * (size_t)n, (size_t)n * 12, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_w, d_out + 6 * (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(found, d_found, n, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+}  // extern "C"

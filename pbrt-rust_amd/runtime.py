@@ -8,25 +8,32 @@ from . import _abi as A
 from . import _abi_ao as AO
 from . import _abi_aov as AOV
 from . import _abi_dn as DN
+from . import _abi_bake as BAKE
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # The HIP libraries, in build order: the product library, then those linked against it. name: (directory, file, ctypes mirror, header under include/).
-# What builds them, finds them, loads them (Library) and checks their exports (__graft_entry__.build) reads this table.
+# What builds them, finds them, loads them (Library) and checks their exports (__graft_entry__.build) reads this table and the one below it.
 LIBRARIES = {
     "pt": ("csrc", "libmi355pt.so", A, "mi355pt.h"),
     "ao": ("ao", "libmi355ao.so", AO, "mi355ao.h"),          # the ambient-occlusion integrator
     "aov": ("aov", "libmi355aov.so", AOV, "mi355aov.h"),     # the feature buffers for denoising
     "dn": ("denoise", "libmi355dn.so", DN, "mi355dn.h"),     # the a-trous denoiser over half films and feature buffers
 }
-LIB_PATHS = {name: os.path.join(_HERE, sub, file) for name, (sub, file, _, _) in LIBRARIES.items()}
+# LIBRARIES holds what renders through a camera (a PtRenderParams, a film). The libraries that work in a mesh's texture space have their own table of the same rows,
+# built after the others; ALL_LIBRARIES is the two in build order, and what builds, finds, loads and checks libraries reads that.
+ATLAS_LIBRARIES = {
+    "bake": ("bake", "libmi355bake.so", BAKE, "mi355bake.h"),   # AO, bent normals, positions and normals baked into a UV atlas
+}
+ALL_LIBRARIES = {**LIBRARIES, **ATLAS_LIBRARIES}
+LIB_PATHS = {name: os.path.join(_HERE, sub, file) for name, (sub, file, _, _) in ALL_LIBRARIES.items()}
 LIB_PATHS["pt"] = os.environ.get("PT_LIB_PATH") or LIB_PATHS["pt"]   # PT_LIB_PATH: kernel-variant experiments
 LIB_PATH, AO_LIB_PATH, AOV_LIB_PATH, DN_LIB_PATH = (LIB_PATHS[name] for name in ("pt", "ao", "aov", "dn"))
 TABLES_PATH = os.path.join(_HERE, "data", "sobol_tables.bin")
 
 
 def build_library(verbose=False):
-    """Compile every HIP source for gfx950 (hipcc cross-compiles without a GPU): the libraries of LIBRARIES, in its order."""
-    for sub, file, _, _ in LIBRARIES.values():
+    """Compile every HIP source for gfx950 (hipcc cross-compiles without a GPU): the libraries of ALL_LIBRARIES, in its order."""
+    for sub, file, _, _ in ALL_LIBRARIES.values():
         r = subprocess.run(["make", "-C", os.path.join(_HERE, sub), "-j8"], capture_output=True, text=True)
         if verbose or r.returncode != 0:
             print(r.stdout[-4000:]); print(r.stderr[-4000:])
@@ -46,13 +53,13 @@ class Library:
         self.lib = A.bind(C.CDLL(path), strict=not os.environ.get("PT_LIB_PATH"))   # (PT_LIB_PATH: a kernel-variant library of an A/B run, possibly built from an older tree)
 
     def __getattr__(self, name):
-        """.ao, .aov, .dn: a library of LIBRARIES linked against the product library, loaded and bound on first use (and then an attribute like any other)."""
-        if name == "pt" or name not in LIBRARIES:
+        """.ao, .aov, .dn, .bake: a library of ALL_LIBRARIES linked against the product library, loaded and bound on first use (and then an attribute like any other)."""
+        if name == "pt" or name not in ALL_LIBRARIES:
             raise AttributeError(name)
         path = LIB_PATHS[name]
         if not os.path.exists(path):
             raise PtError(f"{path} not found: build it with __graft_entry__.build() (no CPU fallback exists)")
-        setattr(self, name, A.bind(C.CDLL(path), table=LIBRARIES[name][2].ENTRY_POINTS))
+        setattr(self, name, A.bind(C.CDLL(path), table=ALL_LIBRARIES[name][2].ENTRY_POINTS))
         return getattr(self, name)
 
     def check(self, st, what=""):
@@ -125,6 +132,17 @@ def resolve_mattes(tables, ranks=6, lib=None):
         lib.check(lib.aov.pt_matte_resolve(table.ctypes.data_as(AOV.mp), table.size, ranks, ids.ctypes.data_as(A.u32p), _fptr(cov)), "pt_matte_resolve")
         out[layer] = (ids, cov)
     return out
+
+
+def resolve_bake(ao_w, spp, lib=None):
+    """pt_bake_resolve of the ao_w sums Scene.bake returns, (H, W, 4): (ao (H, W) = sum w / (spp * pi): 1 for an open surface under cosine sampling, bent (H, W, 3) = the normalised sum of the unoccluded
+    directions), 0 where nothing was added."""
+    lib = lib or load_library()
+    ao_w = np.ascontiguousarray(ao_w, dtype=np.float32)
+    shape = ao_w.shape[:-1]
+    ao = np.zeros(shape, np.float32); bent = np.zeros(shape + (3,), np.float32)
+    lib.check(lib.bake.pt_bake_resolve(_fptr(ao_w), ao_w.size // 4, spp, _fptr(ao), _fptr(bent)), "pt_bake_resolve")
+    return ao, bent
 
 
 def murmur3_32(data, seed=0):
@@ -494,6 +512,74 @@ class Scene(Handle):
         if inputs:
             out += ((halves[0].cpu().numpy(), halves[1].cpu().numpy(), {k: v.cpu().numpy() for k, v in planes.items()}),)
         return out
+
+    def bake_select(self, select):
+        """The prim_select bytes of pt_bake_*: `select` is a shape ordinal or a list of them -- resolved through the scene data's prim_group, the ordinal of every
+        primitive's Shape call --, or a per-primitive array (bool or uint8, one entry per primitive) used as it is."""
+        n = self.data.desc().n_prims
+        if isinstance(select, np.ndarray) and select.dtype in (np.bool_, np.uint8):
+            if select.shape != (n,):
+                raise ValueError(f"bake: the selection has shape {select.shape}, the scene {n} primitives")
+            return np.ascontiguousarray(select, dtype=np.uint8)
+        ordinals = np.atleast_1d(np.asarray(select, dtype=np.int64))
+        group = np.asarray(self.data.prim_group)
+        return np.ascontiguousarray(np.isin(group, ordinals), dtype=np.uint8)
+
+    def bake_params(self, width, height, spp, nsamples=64, cos_sample=True, max_distance=float("inf"), sampler="sobol", spp_per_pass=0, profile=False):
+        return BAKE.PtBakeParams(width, height, spp, nsamples, 1 if cos_sample else 0, max_distance, {"sobol": A.PT_SAMPLER_SOBOL, "halton": A.PT_SAMPLER_HALTON}[sampler],
+                                 spp_per_pass, 1 if profile else 0)
+
+    def bake(self, select, width, height, spp, nsamples=64, cos_sample=True, max_distance=float("inf"), sampler="sobol", samples=None, sums=None, device_ptrs=None,
+             planes=BAKE.PLANES, spp_per_pass=0, profile=False):
+        """pt_bake_render of the primitives `select` names (bake_select) into a width x height UV atlas (`samples` = (first, n): pt_bake_render_samples): a dict of
+        the wanted planes -- "owner" (H, W) uint32, the primitive that owns the texel or PT_NONE; "position" and "normal" (H, W, 3); "ao_w" (H, W, 4) = the sums of
+        the unoccluded AO directions and of their weights (resolve_bake turns them into the AO and bent-normal maps). owner, position and normal are written; ao_w
+        is ADDED to the array of `sums` (a dict this method returned) when given, in place: sample ranges baked in ascending order leave what the whole range
+        leaves. `device_ptrs` = {plane: device pointer as an integer}: the planes go to those buffers, returns None."""
+        bp = self.bake_params(width, height, spp, nsamples, cos_sample, max_distance, sampler, spp_per_pass, profile)
+        sel = self.bake_select(select)
+        args = [self.h, C.byref(bp), sel.ctypes.data_as(A.u8p), len(sel)] + ([] if samples is None else list(samples))
+        name = "bake_render" if samples is None else "bake_render_samples"
+        if device_ptrs is not None:
+            self._call(name, *args, C.byref(BAKE.buffers(device_ptrs, device=True)), 1, lib=self.L.bake); return None
+        if sums is None:
+            sums = {}
+        for k in planes:
+            if k not in sums:
+                sums[k] = np.zeros((height, width) + ((BAKE.CHANNELS[k],) if k != "owner" else ()), dtype=BAKE.DTYPES[k])
+        self._call(name, *args, C.byref(BAKE.buffers(sums)), 0, lib=self.L.bake)
+        return sums
+
+    def bake_pass_size(self, width, height, spp, nsamples=64, sampler="sobol", spp_per_pass=0):
+        """Samples per texel per pass pt_bake_render would use now."""
+        return self._pass_size("bake_pass_size", C.byref(self.bake_params(width, height, spp, nsamples, sampler=sampler, spp_per_pass=spp_per_pass)), lib=self.L.bake)
+
+    def bake_dilate(self, owner, plane, iterations, device_ptrs=None):
+        """pt_bake_dilate: the gutter round the islands of `plane` ((H, W) or (H, W, channels) float32) filled over `iterations` rings from the texels `owner`
+        ((H, W) uint32, as Scene.bake returns it) covers; returns the dilated copy. `device_ptrs` = (width, height, channels): owner and plane are device
+        pointers as integers, the plane is dilated in place, returns None."""
+        if device_ptrs is not None:
+            w, h, ch = device_ptrs
+            self._call("bake_dilate", self.h, C.cast(C.c_void_p(owner), A.u32p), C.cast(C.c_void_p(plane), A.fp), ch, w, h, iterations, 1, lib=self.L.bake); return None
+        owner = np.ascontiguousarray(owner, dtype=np.uint32)
+        out = np.array(plane, dtype=np.float32, order="C")
+        h, w = owner.shape
+        ch = 1 if out.ndim == 2 else out.shape[2]
+        if out.shape[:2] != (h, w):
+            raise ValueError(f"bake_dilate: the plane has shape {out.shape}, the owner map {(h, w)}")
+        self._call("bake_dilate", self.h, owner.ctypes.data_as(A.u32p), _fptr(out), ch, w, h, iterations, 0, lib=self.L.bake)
+        return out
+
+    def bake_rays(self, select, width, height, spp, texel, sample, element, nsamples=64, cos_sample=True, max_distance=float("inf"), sampler="sobol"):
+        """pt_bake_rays: (origin (n, 3), direction (n, 3), weight (n,), found (n,) uint8) of the AO rays named by the arrays texel / sample / element."""
+        bp = self.bake_params(width, height, spp, nsamples, cos_sample, max_distance, sampler)
+        sel = self.bake_select(select)
+        texel, sample, element = (np.ascontiguousarray(v, dtype=np.uint32) for v in (texel, sample, element))
+        n = len(texel)
+        o = np.zeros((n, 3), np.float32); d = np.zeros((n, 3), np.float32); w = np.zeros(n, np.float32); found = np.zeros(n, np.uint8)
+        self._call("bake_rays", self.h, C.byref(bp), sel.ctypes.data_as(A.u8p), len(sel), n, texel.ctypes.data_as(A.u32p), sample.ctypes.data_as(A.u32p),
+                   element.ctypes.data_as(A.u32p), _fptr(o), _fptr(d), _fptr(w), found.ctypes.data_as(A.u8p), lib=self.L.bake)
+        return o, d, w, found
 
     def ao_params(self):
         """The scene's PtAOParams (SceneBuilder.integ / the front end's "ambientocclusion" parameters)."""
