@@ -4,33 +4,14 @@
 #pragma once
 #include "../csrc/kern_decl.h"
 #include "../csrc/kern_film.h"
+#include "../side/ao_rays.h"
 
 namespace ptao {
-using namespace ptd;
+using namespace ptside;
 
-constexpr float kInv4Pi = 0.07957747154594766788f;   // INV4_PI (pbrt.rs:30)
-constexpr uint32_t kAOChunk = 64;                    // AO rays per path per trace launch (the rays of one path are consecutive ray ids)
-
-// One chunk of AO rays: elements k0 .. k0 + kn - 1 of every camera hit's nsamples.
-struct AOJob {
-    uint32_t nsamples, cos_sample;
-    uint32_t k0, kn;
-    float4 *ray;            // [rays][2]: {o.xyz, d.x} {d.yz, -, -} (k_trace's 32-byte ray record)
-    float *w;               // [rays]: dot(wi, n) / (pdf * nsamples)
-    uint32_t *base;         // [paths]: first ray id of the path's chunk, PT_NONE when its camera ray missed
-    uint32_t *ray_count;    // device count of ray ids handed out
-    const uint32_t *occluded;   // [rays]: k_trace's any-hit flags (k_ao_accum)
-};
-
-// The 2-D array value of sample number j (GlobalSampler::start_pixel, sampler.rs:288-302): dimensions ARRAY_START_DIM = 5 and 6.
-PT_DEV P2 ao_array_sample(const RenderConst &rc, const SobolTables &tabs, int32_t px, int32_t py, uint64_t j) {
-    if (rc.halton.enabled) {
-        const uint64_t index = halton_index_for_sample(rc.halton, px, py, j);
-        return P2(halton_sample_dimension(tabs, rc.halton, index, 5u), halton_sample_dimension(tabs, rc.halton, index, 6u));
-    }
-    const uint64_t index = sobol_interval_to_index(tabs, (uint32_t)rc.sobol.log2_resolution, j, (uint32_t)(px - rc.sobol.sb_min[0]), (uint32_t)(py - rc.sobol.sb_min[1]));
-    return P2(sobol_sample_float(tabs.m32, index, 5u), sobol_sample_float(tabs.m32, index, 6u));
-}
+// One chunk of AO rays: elements k0 .. k0 + kn - 1 of every camera hit's nsamples; base: [paths], PT_NONE when the path's camera ray missed.
+// (A type of this namespace: the kernels' symbols name ptao::AOJob.)
+struct AOJob : AOChunk {};
 
 // Per alive path (the camera-ray queue of k_generate): rebuild the camera hit's interaction and write this chunk's AO rays.
 template <bool SPH>
@@ -64,6 +45,8 @@ __global__ __launch_bounds__(256) void k_ao_rays(DeviceScene s, RenderConst rc, 
         slot_to_pixel(rc, slot, px, py);   // (an alive path's slot is a pixel: k_generate queued it)
         const uint64_t sample = (uint64_t)rc.s_begin + sl;
         const float nsf = (float)job.nsamples;
+        // NOTE: the loop body is ao_ray's (side/ao_rays.h), restated here: called through that inlined helper, in any shape of it, k_ao_rays<false> came out of the compiler
+        // with 83 VGPRs for 79 -- five waves per SIMD for six (profiles/r6/NOTES.md section 21) --, so this kernel keeps its body. A fix to either belongs in both.
         for (uint32_t kk = 0; kk < job.kn; ++kk) {
             const P2 u = ao_array_sample(rc, tabs, px, py, sample * job.nsamples + job.k0 + kk);
             V3 wi; float pdf;

@@ -13,16 +13,13 @@
 // (blocks_for, general_geometry) and the k_film step (film_pass). This library adds AO's own checks and budget (ao_geometry), one pass (ao_pass), the kernels of
 // ao_kernels.h and the buffers of the AO rays, which live for one call.
 #include "../csrc/host_common.h"
+#include "../side/side_host.h"
 #include "../../include/mi355ao.h"
 #include "ao_kernels.h"
 
 using namespace ptao;
 
 namespace {
-
-constexpr double kAOMemFraction = 0.5;   // of the device's free memory, for a pass the caller leaves to the library
-constexpr size_t kAOMaxRays = (size_t)1 << 31;   // ray ids per chunk (32-bit ids, k_trace's queue index)
-constexpr size_t kAORayBytes = 32 + 4 + 4;       // ray record, weight, any-hit flag
 
 struct Geometry { RenderConst rc; uint32_t S; uint32_t K; };
 
@@ -36,41 +33,17 @@ int ao_geometry(pt_scene *sc, const PtRenderParams *rp, const PtAOParams *ao, ui
     PtRenderParams p = *rp;
     p.integrator = PT_INTEGRATOR_PATH;   // (no medium, no volpath state)
     if (int st = frame_geometry(sc, &p, rc)) return st;
-    // The array values of a pixel are sample numbers 0 .. spp * nsamples - 1 (sampler.rs:288-302). Sobol': the global index of
-    // sample number j is j << 2m plus the pixel's bits, and the generator matrices have 52 columns (lowdiscrepancy.rs:512-569).
-    // Halton: index = offset + j * stride must fit in 64 bits (halton.rs:122-155).
-    const uint64_t numbers = (uint64_t)rp->spp * ao->nsamples;
-    if (rc.halton.enabled) {
-        if (numbers > ~0ull / rc.halton.stride - 1) return fail(PT_ERR_INVALID_ARG, "ambientocclusion: spp x nsamples sample numbers per pixel exceed the Halton sampler's 64-bit index");
-    } else if (numbers - 1 >= (1ull << (52 - 2 * rc.sobol.log2_resolution))) {
-        return fail(PT_ERR_INVALID_ARG, "ambientocclusion: spp x nsamples = " + std::to_string(numbers) + " sample numbers per pixel exceed the 2^" +
-                                         std::to_string(52 - 2 * rc.sobol.log2_resolution) + " the Sobol' tables serve at this resolution");
-    }
+    if (int st = check_ao_sample_numbers(rc, rp->spp, ao->nsamples, "ambientocclusion", "pixel")) return st;
     g.K = std::min<uint32_t>(ao->nsamples, kAOChunk);
     uint32_t S = rp->spp_per_pass;
     // (per path besides libmi355pt's workspace: the ray id base and the chunk's rays)
-    if (S == 0 && rc.n_pix_slots > 0) S = choose_pass_size(sc, rc.n_pix_slots, n_samples, 1, false, PassBudget{4 + (size_t)g.K * kAORayBytes, kAOMemFraction, kAOMaxRays / g.K});
+    if (S == 0 && rc.n_pix_slots > 0) S = choose_pass_size(sc, rc.n_pix_slots, n_samples, 1, false, ao_ray_budget(g.K));
     if (int st = frame_pass_size(rc, S, n_samples, &g.S)) return st;
     if ((size_t)rc.n_pix_slots * g.S * g.K > kAOMaxRays) return fail(PT_ERR_INVALID_ARG, "pass too large: paths x min(nsamples, 64) AO rays per launch > 2^31 (lower spp_per_pass)");
     return PT_OK;
 }
 
-// Per-call buffers of the AO rays (freed on every exit path: a render leaves the device's free memory as it found it,
-// apart from libmi355pt's workspace, which lives with the scene).
-struct AOBuffers {
-    DevTmp tmp;
-    float4 *ray = nullptr; float *w = nullptr; uint32_t *occ = nullptr, *base = nullptr, *count = nullptr;
-    hipError_t alloc(size_t paths, size_t rays) {
-        hipError_t e;
-        if ((e = tmp.alloc(&ray, rays * 32)) != hipSuccess) return e;
-        if ((e = tmp.alloc(&w, rays * 4)) != hipSuccess) return e;
-        if ((e = tmp.alloc(&occ, rays * 4)) != hipSuccess) return e;
-        if ((e = tmp.alloc(&base, paths * 4)) != hipSuccess) return e;
-        return tmp.alloc(&count, 4);
-    }
-};
-
-int ao_pass(pt_scene *sc, const RenderConst &rc, const PtAOParams *ao, uint32_t K, AOBuffers &b) {
+int ao_pass(pt_scene *sc, const RenderConst &rc, const PtAOParams *ao, uint32_t K, const AORayBuffers &b) {
     const uint32_t total = rc.n_pix_slots * rc.s_count;
     QCounters *qc = sc->qc;
     TraceJob cam = trace_job(sc, 0);   // camera rays -> hit records (Scene::intersect, ao.rs:72)
@@ -79,27 +52,20 @@ int ao_pass(pt_scene *sc, const RenderConst &rc, const PtAOParams *ao, uint32_t 
     if ((st = traced(sc, "extend_camera", 0, cam, total))) return st;
     const bool sph = general_geometry(sc);
     const dim3 qblocks = blocks_for(total, 16u);
-    for (uint32_t k0 = 0; k0 < ao->nsamples; k0 += K) {
-        AOJob job{};
-        job.nsamples = ao->nsamples; job.cos_sample = ao->cos_sample ? 1u : 0u;
-        job.k0 = k0; job.kn = std::min(K, ao->nsamples - k0);
-        job.ray = b.ray; job.w = b.w; job.base = b.base; job.ray_count = b.count; job.occluded = b.occ;
-        HIP_TRY(hipMemsetAsync(b.count, 0, 4, sc->stream));
-        HIP_TRY(hipMemsetAsync(qc->head, 0, sizeof qc->head, sc->stream));
+    auto spawn = [&](const AOJob &job) {
         sc->begin("ao_rays", (uint64_t)total * job.kn);
         if (sph) launch(sc, "ptao::k_ao_rays<true>", k_ao_rays<true>, qblocks, dim3(256), sc->ds, rc, g_tabs, sc->ps, sc->q.ext[0], &qc->ext[0], job);
         else launch(sc, "ptao::k_ao_rays<false>", k_ao_rays<false>, qblocks, dim3(256), sc->ds, rc, g_tabs, sc->ps, sc->q.ext[0], &qc->ext[0], job);
         sc->end();
-        HIP_TRY(hipGetLastError());
-        TraceJob tj = trace_job(sc, 2);   // the AO rays: Scene::intersect_p of spawn_ray(wi) (ao.rs:94); ray ids, no queue
-        tj.sub[0] = trace_sub(nullptr, b.count, (const float *)b.ray, 8, INFINITY, 2);
-        tj.sub[0].out_word = b.occ; tj.sub[0].out_word_stride = 1; tj.sub[0].any = 1;
-        if ((st = traced(sc, "shadow", 1, tj, total * job.kn))) return st;   // (an upper bound: the launch reads the count of rays spawned)
+    };
+    auto accum = [&](const AOJob &job) {
         sc->begin("ao_accum", total);
         launch(sc, "ptao::k_ao_accum", k_ao_accum, qblocks, dim3(256), sc->ps, sc->q.ext[0], &qc->ext[0], job);
         sc->end();
-        HIP_TRY(hipGetLastError());
-    }
+    };
+    AOJob job{};
+    job.nsamples = ao->nsamples; job.cos_sample = ao->cos_sample ? 1u : 0u;
+    if ((st = ao_chunks<AOJob>(sc, job, K, total, INFINITY, b, spawn, accum))) return st;   // (Scene::intersect_p of spawn_ray(wi): t_max = infinity)
     if ((st = film_pass(sc, rc))) return st;
     QCounters h;
     return sync_queue_counters(sc, h);   // (a status a kernel raised fails the call here)
@@ -130,13 +96,9 @@ __attribute__((visibility("default"))) int pt_ao_render_samples(pt_scene *sc, co
     if (int rst = check_sample_range(rp, first, n_samples)) return rst;   // (before the device is touched)
     Geometry g;
     if (int gst = ao_geometry(sc, rp, ao, n_samples, g)) return gst;
-    AOBuffers b;   // (freed when the call returns, however it ends)
+    AORayBuffers b;   // (freed when the call returns, however it ends)
     // (the steps cross as std::function, FrameStep: render_frame launches libmi355pt's k_generate / k_film_finish, so it is one function there, not a header template compiled here too)
-    auto prepare = [&]() {
-        const size_t paths = (size_t)g.rc.n_pix_slots * g.S;
-        if (hipError_t e = b.alloc(paths, paths * g.K); e != hipSuccess) { (void)hipGetLastError(); return fail(PT_ERR_OUT_OF_MEMORY, std::string("ambientocclusion rays: ") + hipGetErrorString(e)); }
-        return (int)PT_OK;
-    };
+    auto prepare = [&]() { const size_t paths = (size_t)g.rc.n_pix_slots * g.S; return b.alloc(paths, paths * g.K, "ambientocclusion rays"); };
     return render_frame(sc, rp, g.rc, g.S, first, n_samples, film_xyzw, film_is_device, prepare, [&]() { return ao_pass(sc, g.rc, ao, g.K, b); });
 }
 

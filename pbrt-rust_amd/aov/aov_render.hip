@@ -16,6 +16,7 @@
 // pt_matte_render / pt_matte_render_samples / pt_matte_pass_size / pt_matte_resolve / pt_matte_mask (the ID mattes) follow below the feature buffers: the same pass with
 // k_matte and k_matte_film, the same geometry function with the mattes' record size.
 #include "../csrc/host_common.h"
+#include "../side/side_host.h"
 #include "../../include/mi355aov.h"
 #include "aov_kernels.h"
 #include <algorithm>
@@ -26,7 +27,6 @@ namespace {
 
 constexpr double kAovMemFraction = 0.5;   // of the device's free memory, for a pass the caller leaves to the library
 constexpr size_t kAovRecBytes = 32;       // the sample's record (aov_kernels.h: AovJob): what a path costs besides libmi355pt's workspace
-constexpr int kAovMaxRounds = 1 << 16;    // continuations of one camera ray: a scene's shells are finitely many
 
 struct Geometry { RenderConst rc; uint32_t S; };
 
@@ -63,15 +63,14 @@ struct AovCall {
 int aov_prepare(pt_scene *sc, const Geometry &g, const PtAOVBuffers *b, int on_device, AovCall &c) {
     const size_t film_px = (size_t)g.rc.film_w * g.rc.film_h, paths = (size_t)g.rc.n_pix_slots * g.S;
     float *const given[3] = {b->albedo_w, b->normal_w, b->depth_w};
-    auto oom = [](hipError_t e) { (void)hipGetLastError(); return fail(PT_ERR_OUT_OF_MEMORY, std::string("feature buffers: ") + hipGetErrorString(e)); };
-    if (hipError_t e = c.tmp.alloc(&c.rec, paths * kAovRecBytes); e != hipSuccess) return oom(e);
+    SIDE_ALLOC(c.tmp, c.rec, paths * kAovRecBytes, "feature buffers");
     for (int k = 0; k < 3; ++k) {
         if (!given[k]) continue;
         c.mask |= 1u << k;
         c.bytes[k] = film_px * (k < 2 ? 16 : 8);
         if (on_device) { *c.dev(k) = given[k]; continue; }
         c.host[k] = given[k];
-        if (hipError_t e = c.tmp.alloc(c.dev(k), c.bytes[k]); e != hipSuccess) return oom(e);
+        SIDE_ALLOC(c.tmp, *c.dev(k), c.bytes[k], "feature buffers");
         HIP_TRY(hipMemcpyAsync(*c.dev(k), given[k], c.bytes[k], hipMemcpyHostToDevice, sc->stream));
     }
     return PT_OK;
@@ -81,28 +80,16 @@ int aov_pass(pt_scene *sc, const RenderConst &rc, AovCall &c) {
     const uint32_t total = rc.n_pix_slots * rc.s_count;
     QCounters *qc = sc->qc;
     const bool sph = general_geometry(sc);
-    uint32_t n = total;   // rays of the round (round 0: an upper bound, the launches read the count of camera rays)
-    for (int round = 0, cur = 0; n > 0; ++round, cur = 1 - cur) {
-        if (round == kAovMaxRounds) return fail(PT_ERR_PROBE_CHAIN, "feature buffers: camera rays still going on behind material-less surfaces after " + std::to_string(round) + " continuations");
-        TraceJob tj = trace_job(sc, 0);   // Scene::intersect of the camera rays, then of the rays spawned behind shells
-        tj.sub[0] = extend_sub(sc, cur, round == 0);
-        if (round > 0) HIP_TRY(hipMemsetAsync(qc->head, 0, sizeof qc->head, sc->stream));
-        int st;
-        if ((st = traced(sc, round == 0 ? "extend_camera" : "extend", 0, tj, n))) return st;
+    auto record = [&](int cur, bool first_round, uint32_t n) {
         AovJob job{};
-        job.rec = c.rec; job.next = sc->q.ext[1 - cur]; job.next_count = &qc->ext[1 - cur]; job.mask = c.mask; job.first_round = round == 0 ? 1u : 0u;
-        HIP_TRY(hipMemsetAsync(&qc->ext[1 - cur], 0, 4, sc->stream));
+        job.rec = c.rec; job.next = sc->q.ext[1 - cur]; job.next_count = &qc->ext[1 - cur]; job.mask = c.mask; job.first_round = first_round ? 1u : 0u;
         const dim3 grid = blocks_for(n, 16u);
         sc->begin("aov", n);
         if (sph) launch(sc, "ptaov::k_aov<true>", k_aov<true>, grid, dim3(256), sc->ds, rc, g_tabs, sc->ps, sc->q.ext[cur], &qc->ext[cur], job);
         else launch(sc, "ptaov::k_aov<false>", k_aov<false>, grid, dim3(256), sc->ds, rc, g_tabs, sc->ps, sc->q.ext[cur], &qc->ext[cur], job);
         sc->end();
-        HIP_TRY(hipGetLastError());
-        if (!sc->has_null_material) break;   // every hit carries a material: nothing goes on, no count to wait for
-        QCounters h;
-        if ((st = sync_queue_counters(sc, h))) return st;
-        n = h.ext[1 - cur];
-    }
+    };
+    if (int st = first_hit_chase(sc, total, "feature buffers", record)) return st;
     sc->begin("film", total);
     launch(sc, "ptaov::k_aov_film", k_aov_film, film_grid(rc), dim3(256), rc, sc->ps, c.rec, sc->d_filter, c.planes, sc->dc);
     sc->end();
@@ -152,19 +139,18 @@ struct MatteCall {
 
 int matte_prepare(pt_scene *sc, const Geometry &g, const PtMatteBuffers *b, int on_device, MatteCall &c) {
     const size_t film_px = (size_t)g.rc.film_w * g.rc.film_h, paths = (size_t)g.rc.n_pix_slots * g.S;
-    auto oom = [](hipError_t e) { (void)hipGetLastError(); return fail(PT_ERR_OUT_OF_MEMORY, std::string("mattes: ") + hipGetErrorString(e)); };
-    if (hipError_t e = c.tmp.alloc(&c.rec, paths * kMatteRecBytes); e != hipSuccess) return oom(e);
+    SIDE_ALLOC(c.tmp, c.rec, paths * kMatteRecBytes, "mattes");
     c.bytes = film_px * sizeof(PtMattePixel);
     for (int k = 0; k < 3; ++k) {
         if (!b->layer[k]) continue;
         c.tabs.mask |= 1u << k;
         if (on_device) { c.tabs.layer[k] = reinterpret_cast<uint4 *>(b->layer[k]); continue; }
         c.host[k] = b->layer[k];
-        if (hipError_t e = c.tmp.alloc(&c.tabs.layer[k], c.bytes); e != hipSuccess) return oom(e);
+        SIDE_ALLOC(c.tmp, c.tabs.layer[k], c.bytes, "mattes");
         HIP_TRY(hipMemcpyAsync(c.tabs.layer[k], b->layer[k], c.bytes, hipMemcpyHostToDevice, sc->stream));
     }
     if (b->layer[PT_MATTE_GROUP]) {   // once per call
-        if (hipError_t e = c.tmp.alloc(&c.prim_group, (size_t)b->n_prims * 4); e != hipSuccess) return oom(e);
+        SIDE_ALLOC(c.tmp, c.prim_group, (size_t)b->n_prims * 4, "mattes");
         HIP_TRY(hipMemcpyAsync(c.prim_group, b->prim_group, (size_t)b->n_prims * 4, hipMemcpyHostToDevice, sc->stream));
     }
     return PT_OK;
@@ -174,27 +160,15 @@ int matte_pass(pt_scene *sc, const RenderConst &rc, MatteCall &c) {
     const uint32_t total = rc.n_pix_slots * rc.s_count;
     QCounters *qc = sc->qc;
     const bool sph = general_geometry(sc);
-    uint32_t n = total;
-    for (int round = 0, cur = 0; n > 0; ++round, cur = 1 - cur) {
-        if (round == kAovMaxRounds) return fail(PT_ERR_PROBE_CHAIN, "mattes: camera rays still going on behind material-less surfaces after " + std::to_string(round) + " continuations");
-        TraceJob tj = trace_job(sc, 0);
-        tj.sub[0] = extend_sub(sc, cur, round == 0);
-        if (round > 0) HIP_TRY(hipMemsetAsync(qc->head, 0, sizeof qc->head, sc->stream));
-        int st;
-        if ((st = traced(sc, round == 0 ? "extend_camera" : "extend", 0, tj, n))) return st;
+    auto record = [&](int cur, bool, uint32_t n) {
         MatteJob job{c.rec, sc->q.ext[1 - cur], &qc->ext[1 - cur], c.prim_group};
-        HIP_TRY(hipMemsetAsync(&qc->ext[1 - cur], 0, 4, sc->stream));
         const dim3 grid = blocks_for(n, 16u);
         sc->begin("matte", n);
         if (sph) launch(sc, "ptaov::k_matte<true>", k_matte<true>, grid, dim3(256), sc->ds, sc->ps, sc->q.ext[cur], &qc->ext[cur], job);
         else launch(sc, "ptaov::k_matte<false>", k_matte<false>, grid, dim3(256), sc->ds, sc->ps, sc->q.ext[cur], &qc->ext[cur], job);
         sc->end();
-        HIP_TRY(hipGetLastError());
-        if (!sc->has_null_material) break;
-        QCounters h;
-        if ((st = sync_queue_counters(sc, h))) return st;
-        n = h.ext[1 - cur];
-    }
+    };
+    if (int st = first_hit_chase(sc, total, "mattes", record)) return st;
     const size_t film_px = (size_t)rc.film_w * rc.film_h;
     sc->begin("matte_film", total);
     launch(sc, "ptaov::k_matte_film", k_matte_film, dim3((unsigned)((film_px + 255) / 256)), dim3(256), rc, sc->ps, c.rec, sc->d_filter, c.tabs, sc->dc);
@@ -238,7 +212,7 @@ __attribute__((visibility("default"))) int pt_matte_render_samples(pt_scene *sc,
     if (int gst = aov_geometry(sc, rp, n_samples, g, kMatteRecBytes)) return gst;
     if ((uint64_t)g.rc.film_w * g.rc.film_h > (1ull << 31)) return fail(PT_ERR_INVALID_ARG, "mattes: more than 2^31 film pixels");
     MatteCall c;   // (freed when the call returns, however it ends)
-    if (g.rc.n_pix_slots > 0) if (hipError_t e = c.tmp.alloc(&c.scratch_film, (size_t)g.rc.film_w * g.rc.film_h * 16); e != hipSuccess) { (void)hipGetLastError(); return fail(PT_ERR_OUT_OF_MEMORY, std::string("mattes: ") + hipGetErrorString(e)); }
+    if (g.rc.n_pix_slots > 0) SIDE_ALLOC(c.tmp, c.scratch_film, (size_t)g.rc.film_w * g.rc.film_h * 16, "mattes");
     return render_frame(sc, rp, g.rc, g.S, first, n_samples, c.scratch_film, 1,
                         [&]() { return matte_prepare(sc, g, buffers, buffers_are_device, c); }, [&]() { return matte_pass(sc, g.rc, c); }, [&]() { return matte_finish(sc, c); });
 }
@@ -270,19 +244,18 @@ __attribute__((visibility("default"))) int pt_matte_mask(pt_scene *sc, const PtM
     if (!sc->stream) HIP_TRY(hipStreamCreate(&sc->stream));
     sc->drop_timings();
     DevTmp tmp;
-    auto oom = [](hipError_t e) { (void)hipGetLastError(); return fail(PT_ERR_OUT_OF_MEMORY, std::string("mattes: ") + hipGetErrorString(e)); };
     const uint4 *d_table = reinterpret_cast<const uint4 *>(table);
     uint32_t *d_ids = nullptr;
     float *d_mask = mask;
-    if (hipError_t e = tmp.alloc(&d_ids, (size_t)n_ids * 4); e != hipSuccess) return oom(e);
+    SIDE_ALLOC(tmp, d_ids, (size_t)n_ids * 4, "mattes");
     HIP_TRY(hipMemcpyAsync(d_ids, ids, (size_t)n_ids * 4, hipMemcpyHostToDevice, sc->stream));
     if (!table_is_device) {
         uint4 *up = nullptr;
-        if (hipError_t e = tmp.alloc(&up, (size_t)n_pixels * sizeof(PtMattePixel)); e != hipSuccess) return oom(e);
+        SIDE_ALLOC(tmp, up, (size_t)n_pixels * sizeof(PtMattePixel), "mattes");
         HIP_TRY(hipMemcpyAsync(up, table, (size_t)n_pixels * sizeof(PtMattePixel), hipMemcpyHostToDevice, sc->stream));
         d_table = up;
     }
-    if (!mask_is_device) if (hipError_t e = tmp.alloc(&d_mask, (size_t)n_pixels * 4); e != hipSuccess) return oom(e);
+    if (!mask_is_device) SIDE_ALLOC(tmp, d_mask, (size_t)n_pixels * 4, "mattes");
     sc->begin("matte_mask", n_pixels);
     launch(sc, "ptaov::k_matte_mask", k_matte_mask, dim3((unsigned)(((size_t)n_pixels + 255) / 256)), dim3(256), d_table, n_pixels, (const uint32_t *)d_ids, n_ids, d_mask);
     sc->end();
@@ -316,7 +289,7 @@ __attribute__((visibility("default"))) int pt_aov_render_samples(pt_scene *sc, c
     if (int gst = aov_geometry(sc, rp, n_samples, g)) return gst;
     AovCall c;   // (freed when the call returns, however it ends)
     // the frame's film: nothing is splatted onto it, and a rank that owns no tile never delivers it
-    if (g.rc.n_pix_slots > 0) if (hipError_t e = c.tmp.alloc(&c.scratch_film, (size_t)g.rc.film_w * g.rc.film_h * 16); e != hipSuccess) { (void)hipGetLastError(); return fail(PT_ERR_OUT_OF_MEMORY, std::string("feature buffers: ") + hipGetErrorString(e)); }
+    if (g.rc.n_pix_slots > 0) SIDE_ALLOC(c.tmp, c.scratch_film, (size_t)g.rc.film_w * g.rc.film_h * 16, "feature buffers");
     return render_frame(sc, rp, g.rc, g.S, first, n_samples, c.scratch_film, 1,
                         [&]() { return aov_prepare(sc, g, buffers, buffers_are_device, c); }, [&]() { return aov_pass(sc, g.rc, c); }, [&]() { return aov_finish(sc, c); });
 }

@@ -3,19 +3,18 @@
 //   k_bake_top      marks the primitives of the top-level accelerator (a primitive of an instanced object is no bake target)
 //   k_bake_raster   selected triangles -> atomicMin on the owner map
 //   k_bake_points   one thread per texel: the owner's interaction -> position and shading normal
-//   k_bake_rays     one texel sample per thread: one chunk of its AO rays (the direction sampling mirrors ao/ao_kernels.h:67-84)
+//   k_bake_rays     one texel sample per thread: one chunk of its AO rays (side/ao_rays.h: the rays libmi355ao spawns from a camera hit)
 //   k_bake_accum    ao_w += the unoccluded rays' wi and w, in element order
 //   k_bake_dilate   one iteration of the gutter fill
-//   k_bake_probe    pt_bake_rays: single rays by bake_ray, the function k_bake_rays calls
+//   k_bake_probe    pt_bake_rays: single rays by ao_ray, the function k_bake_rays' rays come from
 // No atomics other than the owner map's atomicMin and the per-wave ray-id reservation (wave_reserve).
 #pragma once
 #include "../csrc/kern_decl.h"
+#include "../side/ao_rays.h"
 
 namespace ptbake {
-using namespace ptd;
+using namespace ptside;
 
-constexpr float kInv4Pi = 0.07957747154594766788f;   // INV4_PI (pbrt.rs:30)
-constexpr uint32_t kBakeChunk = 64;                  // AO rays per texel sample per trace launch (the rays of one texel sample are consecutive ray ids)
 constexpr uint32_t kRasterOwnTexels = 16;            // k_bake_raster: a triangle whose texel box holds at most this many texels is walked by its own lane
 
 // `slots`: the texel samples of one sample number in the order the ray kernel walks them -- 8 x 8 texel tiles, one per wave, so that the rays of a wave start from a
@@ -33,17 +32,10 @@ PT_DEV uint32_t texel_slot(const BakeAtlas &a, uint32_t texel) {
     return (((y >> 3) * a.tiles_x + (x >> 3)) << 6) | ((y & 7u) << 3) | (x & 7u);
 }
 
-// One chunk of AO rays: elements k0 .. k0 + kn - 1 of the texel samples [s_begin, s_begin + s_count) of every owned texel.
-struct BakeJob {
-    uint32_t nsamples, cos_sample;
-    uint32_t k0, kn;
+// One chunk of AO rays of the texel samples [s_begin, s_begin + s_count) of every owned texel; base: [slots * s_count], PT_NONE for a texel without owner
+struct BakeJob : AOChunk {
     uint32_t s_begin, s_count;
     const uint32_t *owner;   // [texels]
-    float4 *ray;             // [rays][2]: {o.xyz, d.x} {d.yz, -, -} (k_trace's 32-byte ray record)
-    float *w;                // [rays]
-    uint32_t *base;          // [slots * s_count]: first ray id of the texel sample's chunk, PT_NONE for a texel without owner
-    uint32_t *ray_count;     // device count of ray ids handed out
-    const uint32_t *occluded;   // [rays]: k_trace's any-hit flags (k_bake_accum)
     float4 *ao_w;            // [texels]
 };
 
@@ -76,37 +68,8 @@ PT_DEV void texel_interaction(const DeviceScene &s, const BakeAtlas &a, uint32_t
     tri_fill_interaction(s, tri, V3(0.0f, 0.0f, 0.0f), b0, b1, b2, true, si);
 }
 
-// The 2-D array value of sample number j (GlobalSampler::start_pixel, sampler.rs:288-302): dimensions ARRAY_START_DIM = 5 and 6 (ao/ao_kernels.h:26-33)
-PT_DEV P2 bake_array_sample(const RenderConst &rc, const SobolTables &tabs, int32_t px, int32_t py, uint64_t j) {
-    if (rc.halton.enabled) {
-        const uint64_t index = halton_index_for_sample(rc.halton, px, py, j);
-        return P2(halton_sample_dimension(tabs, rc.halton, index, 5u), halton_sample_dimension(tabs, rc.halton, index, 6u));
-    }
-    const uint64_t index = sobol_interval_to_index(tabs, (uint32_t)rc.sobol.log2_resolution, j, (uint32_t)(px - rc.sobol.sb_min[0]), (uint32_t)(py - rc.sobol.sb_min[1]));
-    return P2(sobol_sample_float(tabs.m32, index, 5u), sobol_sample_float(tabs.m32, index, 6u));
-}
-
 // The frame of ao.rs:77-80 without the face-forward (there is no camera ray): s = normalize(dpdu), t = cross(n, s), n
-struct BakeFrame { V3 n, sv, tv; };
-PT_DEV BakeFrame bake_frame(const SurfaceInteraction &si) { BakeFrame f; f.n = si.n; f.sv = normalize(si.dpdu); f.tv = cross(si.n, f.sv); return f; }
-
-// Element k of sample s of texel (px, py): origin, direction and weight (ao.rs:82-95; the direction sampling mirrors ao/ao_kernels.h:67-84)
-PT_DEV void bake_ray(const RenderConst &rc, const SobolTables &tabs, const SurfaceInteraction &si, const BakeFrame &f, int32_t px, int32_t py, uint64_t number,
-                     uint32_t cos_sample, float nsf, V3 &o, V3 &wo, float &w) {
-    const P2 u = bake_array_sample(rc, tabs, px, py, number);
-    V3 wi; float pdf;
-    if (cos_sample) { wi = cosine_sample_hemisphere(u); pdf = fabsf(wi.z) * kInvPi; }   // cosine_hemisphere_pdf (sampling.rs:195-197)
-    else {   // uniform_sample_sphere (sampling.rs:212-218), uniform_sphere_pdf
-        const float z = 1.0f - 2.0f * u.x;
-        const float r = sqrtf(maxf(1.0f - z * z, 0.0f));
-        const float phi = 2.0f * kPi * u.y;
-        float sn, cs; dm_sincosf(phi, sn, cs);
-        wi = V3(r * cs, r * sn, z); pdf = kInv4Pi;
-    }
-    wo = V3(f.sv.x * wi.x + f.tv.x * wi.y + f.n.x * wi.z, f.sv.y * wi.x + f.tv.y * wi.y + f.n.y * wi.z, f.sv.z * wi.x + f.tv.z * wi.y + f.n.z * wi.z);
-    o = offset_ray_origin(si.p, si.p_error, si.n, wo);   // SurfaceInteraction::spawn_ray (interaction.rs:32-36)
-    w = dot(wo, f.n) / (pdf * nsf);
-}
+PT_DEV AOFrame bake_frame(const SurfaceInteraction &si) { AOFrame f; f.n = si.n; f.sv = normalize(si.dpdu); f.tv = cross(si.n, f.sv); return f; }
 
 // The packets [0, n_top) are the top-level accelerator's, one per top-level primitive or instance (scene_plan.hip: the packet order of every accelerator)
 __global__ __launch_bounds__(256) void k_bake_top(DeviceScene s, uint32_t n_top, uint8_t *top) {
@@ -221,13 +184,13 @@ __global__ __launch_bounds__(256) void k_bake_rays(DeviceScene s, RenderConst rc
         job.base[item] = first;
         SurfaceInteraction si;
         texel_interaction(s, a, texel, prim, si);
-        const BakeFrame f = bake_frame(si);
+        const AOFrame f = bake_frame(si);
         const int32_t px = (int32_t)(texel % a.width), py = (int32_t)(texel / a.width);
         const uint64_t sample = (uint64_t)job.s_begin + sl;
         const float nsf = (float)job.nsamples;
         for (uint32_t kk = 0; kk < job.kn; ++kk) {
             V3 o, wo; float w;
-            bake_ray(rc, tabs, si, f, px, py, sample * job.nsamples + job.k0 + kk, job.cos_sample, nsf, o, wo, w);
+            ao_ray(rc, tabs, si, f, px, py, sample * job.nsamples + job.k0 + kk, job.cos_sample, nsf, o, wo, w);
             const uint32_t id = first + kk;
             job.ray[2 * (size_t)id] = make_float4(o.x, o.y, o.z, wo.x);
             job.ray[2 * (size_t)id + 1] = make_float4(wo.y, wo.z, 0.0f, 0.0f);
@@ -287,7 +250,7 @@ __global__ __launch_bounds__(256) void k_bake_covered(BakeAtlas a, const uint32_
     if (texel < a.n_texels) covered[texel] = owner[texel] != PT_NONE ? 1 : 0;
 }
 
-// pt_bake_rays: ray i = element[i] of sample[i] of texel[i], by bake_ray
+// pt_bake_rays: ray i = element[i] of sample[i] of texel[i], by ao_ray
 __global__ __launch_bounds__(256) void k_bake_probe(DeviceScene s, RenderConst rc, SobolTables tabs, BakeAtlas a, const uint32_t *owner, uint32_t nsamples, uint32_t cos_sample, uint32_t n,
                                                     const uint32_t *texel, const uint32_t *sample, const uint32_t *element, float *out_o, float *out_d, float *out_w, uint8_t *found) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -298,7 +261,7 @@ __global__ __launch_bounds__(256) void k_bake_probe(DeviceScene s, RenderConst r
     if (prim != PT_NONE) {
         SurfaceInteraction si;
         texel_interaction(s, a, tx, prim, si);
-        bake_ray(rc, tabs, si, bake_frame(si), (int32_t)(tx % a.width), (int32_t)(tx / a.width), (uint64_t)sample[i] * nsamples + element[i], cos_sample, (float)nsamples, o, wo, w);
+        ao_ray(rc, tabs, si, bake_frame(si), (int32_t)(tx % a.width), (int32_t)(tx / a.width), (uint64_t)sample[i] * nsamples + element[i], cos_sample, (float)nsamples, o, wo, w);
     }
     out_o[3 * (size_t)i] = o.x; out_o[3 * (size_t)i + 1] = o.y; out_o[3 * (size_t)i + 2] = o.z;
     out_d[3 * (size_t)i] = wo.x; out_d[3 * (size_t)i + 1] = wo.y; out_d[3 * (size_t)i + 2] = wo.z;

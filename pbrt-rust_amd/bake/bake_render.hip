@@ -11,6 +11,7 @@
 // ensure_workspace with no paths and no film, the pass size from choose_pass_size with the bake's bytes per texel sample, the sampler set-up from fill_render_const
 // for a width x height image, the traversal through trace_job / trace_sub / traced as libmi355ao's AO rays go.
 #include "../csrc/host_common.h"
+#include "../side/side_host.h"
 #include "../../include/mi355bake.h"
 #include "bake_kernels.h"
 
@@ -18,16 +19,10 @@ using namespace ptbake;
 
 namespace {
 
-constexpr double kBakeMemFraction = 0.5;           // of the device's free memory, for a pass the caller leaves to the library
-constexpr size_t kBakeMaxRays = (size_t)1 << 31;   // ray ids per chunk (32-bit ids, k_trace's queue index)
-constexpr size_t kBakeRayBytes = 32 + 4 + 4;       // ray record, weight, any-hit flag
 constexpr size_t kBakeMaxTexels = (size_t)1 << 28;
 constexpr uint32_t kRasterFewTriangles = 16384;    // a selection of fewer triangles is rastered in row bands (k_bake_raster)
 
 struct Geometry { RenderConst rc; BakeAtlas atlas; uint32_t S; uint32_t K; };
-
-int oom(const char *what, hipError_t e) { (void)hipGetLastError(); return fail(PT_ERR_OUT_OF_MEMORY, std::string("bake ") + what + ": " + hipGetErrorString(e)); }
-#define BAKE_ALLOC(tmp, ptr, bytes, what) do { if (hipError_t _a = (tmp).alloc(&(ptr), (bytes)); _a != hipSuccess) return oom(what, _a); } while (0)
 
 // ---- what is checked before the device is touched
 int check_atlas(uint32_t width, uint32_t height) {
@@ -59,7 +54,7 @@ int check_prim_count(const pt_scene *sc, uint32_t n_prims) {
     return PT_OK;
 }
 
-// The sampler of a width x height image (fill_render_const), the checks on its sample numbers (ao_render.hip: ao_geometry) and the pass size
+// The sampler of a width x height image (fill_render_const), the checks on its sample numbers and the pass size
 int bake_geometry(pt_scene *sc, const PtBakeParams *bp, uint32_t n_samples, Geometry &g) {
     if (sc->device != g_device) { if (int st = bind_device(sc->device)) return st; }
     PtRenderParams rp{};
@@ -72,23 +67,16 @@ int bake_geometry(pt_scene *sc, const PtBakeParams *bp, uint32_t n_samples, Geom
     fill_render_const(&rp, rc);
     if (rc.sobol.log2_resolution > 25) return fail(PT_ERR_INVALID_ARG, "bake: the atlas exceeds the 2^25 Sobol' pixel grid");
     g.atlas = make_atlas(bp->width, bp->height);
-    // The array values of a texel are sample numbers 0 .. spp * nsamples - 1: the limits of ao_geometry (ao_render.hip:39-48) for both samplers
-    const uint64_t numbers = (uint64_t)bp->spp * bp->nsamples;
-    if (rc.halton.enabled) {
-        if (numbers > ~0ull / rc.halton.stride - 1) return fail(PT_ERR_INVALID_ARG, "bake: spp x nsamples sample numbers per texel exceed the Halton sampler's 64-bit index");
-    } else if (numbers - 1 >= (1ull << (52 - 2 * rc.sobol.log2_resolution))) {
-        return fail(PT_ERR_INVALID_ARG, "bake: spp x nsamples = " + std::to_string(numbers) + " sample numbers per texel exceed the 2^" + std::to_string(52 - 2 * rc.sobol.log2_resolution) +
-                                         " the Sobol' tables serve at this resolution");
-    }
-    g.K = std::min<uint32_t>(bp->nsamples, kBakeChunk);
+    if (int st = check_ao_sample_numbers(rc, bp->spp, bp->nsamples, "bake", "texel")) return st;
+    g.K = std::min<uint32_t>(bp->nsamples, kAOChunk);
     uint32_t S = bp->spp_per_pass;
     // (per texel sample: the ray id base and the chunk's rays. The rule counts libmi355pt's path workspace too, which the bake does not allocate: the choice errs small)
-    if (S == 0) S = choose_pass_size(sc, g.atlas.slots, n_samples, 1, false, PassBudget{4 + (size_t)g.K * kBakeRayBytes, kBakeMemFraction, kBakeMaxRays / g.K});
+    if (S == 0) S = choose_pass_size(sc, g.atlas.slots, n_samples, 1, false, ao_ray_budget(g.K));
     S = std::min(S, n_samples);
     // The additions to a texel are in (sample, element) order: a pass of several samples is accumulated sample by sample within ONE chunk; with more than one chunk
     // per sample a pass is one sample
-    if (bp->nsamples > kBakeChunk) S = 1;
-    if ((size_t)g.atlas.slots * S * g.K > kBakeMaxRays) return fail(PT_ERR_INVALID_ARG, "bake: pass too large: texels x samples per pass x min(nsamples, 64) AO rays per launch > 2^31 (lower spp_per_pass)");
+    if (bp->nsamples > kAOChunk) S = 1;
+    if ((size_t)g.atlas.slots * S * g.K > kAOMaxRays) return fail(PT_ERR_INVALID_ARG, "bake: pass too large: texels x samples per pass x min(nsamples, 64) AO rays per launch > 2^31 (lower spp_per_pass)");
     g.S = S;
     return PT_OK;
 }
@@ -117,8 +105,8 @@ int upload_selection(pt_scene *sc, const uint8_t *prim_select, uint32_t n_prims,
     n_selected = (uint32_t)selected.size();
     const uint32_t n_top = (uint32_t)sc->ordered.size(), n_blocks = (n_selected + 255) / 256;
     uint8_t *d_top = nullptr, *d_code = nullptr; uint32_t *d_refused = nullptr;
-    BAKE_ALLOC(tmp, d_top, n_prims, "selection"); BAKE_ALLOC(tmp, d_selected, (size_t)n_selected * 4, "selection");
-    BAKE_ALLOC(tmp, d_code, n_selected, "selection"); BAKE_ALLOC(tmp, d_refused, (size_t)n_blocks * 4, "selection");
+    SIDE_ALLOC(tmp, d_top, n_prims, "bake selection"); SIDE_ALLOC(tmp, d_selected, (size_t)n_selected * 4, "bake selection");
+    SIDE_ALLOC(tmp, d_code, n_selected, "bake selection"); SIDE_ALLOC(tmp, d_refused, (size_t)n_blocks * 4, "bake selection");
     HIP_TRY(hipMemsetAsync(d_top, 0, n_prims, sc->stream));
     HIP_TRY(hipMemcpyAsync(d_selected, selected.data(), (size_t)n_selected * 4, hipMemcpyHostToDevice, sc->stream));
     sc->begin("bake_select", (uint64_t)n_top + n_selected);
@@ -160,32 +148,23 @@ int raster(pt_scene *sc, const BakeAtlas &a, const uint32_t *d_selected, uint32_
 }
 
 // The rays of one pass: samples [s_begin, s_begin + s_count) of every texel, chunk by chunk
-struct RayBuffers { float4 *ray = nullptr; float *w = nullptr; uint32_t *occ = nullptr, *base = nullptr, *count = nullptr; };
-int bake_pass(pt_scene *sc, const Geometry &g, const PtBakeParams *bp, uint32_t s_begin, uint32_t s_count, const uint32_t *d_owner, float4 *d_ao, const RayBuffers &b) {
+int bake_pass(pt_scene *sc, const Geometry &g, const PtBakeParams *bp, uint32_t s_begin, uint32_t s_count, const uint32_t *d_owner, float4 *d_ao, const AORayBuffers &b) {
     const uint32_t items = g.atlas.slots * s_count;
     const dim3 blocks = blocks_for(items, 16u);
-    for (uint32_t k0 = 0; k0 < bp->nsamples; k0 += g.K) {
-        BakeJob job{};
-        job.nsamples = bp->nsamples; job.cos_sample = bp->cos_sample ? 1u : 0u;
-        job.k0 = k0; job.kn = std::min(g.K, bp->nsamples - k0);
-        job.s_begin = s_begin; job.s_count = s_count;
-        job.owner = d_owner; job.ray = b.ray; job.w = b.w; job.base = b.base; job.ray_count = b.count; job.occluded = b.occ; job.ao_w = d_ao;
-        HIP_TRY(hipMemsetAsync(b.count, 0, 4, sc->stream));
-        HIP_TRY(hipMemsetAsync(sc->qc->head, 0, sizeof sc->qc->head, sc->stream));
+    auto spawn = [&](const BakeJob &job) {
         sc->begin("bake_rays", (uint64_t)items * job.kn);
         launch(sc, "ptbake::k_bake_rays", k_bake_rays, blocks, dim3(256), sc->ds, g.rc, g_tabs, g.atlas, job);
         sc->end();
-        HIP_TRY(hipGetLastError());
-        TraceJob tj = trace_job(sc, 2);   // ray ids, no queue: Scene::intersect_p of the spawned rays (ao.rs:94) with t_max = max_distance
-        tj.sub[0] = trace_sub(nullptr, b.count, (const float *)b.ray, 8, bp->max_distance, 2);
-        tj.sub[0].out_word = b.occ; tj.sub[0].out_word_stride = 1; tj.sub[0].any = 1;
-        if (int st = traced(sc, "shadow", 1, tj, items * job.kn)) return st;   // (an upper bound: the launch reads the count of rays spawned)
+    };
+    auto accum = [&](const BakeJob &job) {
         sc->begin("bake_accum", items);
         launch(sc, "ptbake::k_bake_accum", k_bake_accum, texel_grid(g.atlas), dim3(256), g.atlas, job);
         sc->end();
-        HIP_TRY(hipGetLastError());
-    }
-    return PT_OK;
+    };
+    BakeJob job{};
+    job.nsamples = bp->nsamples; job.cos_sample = bp->cos_sample ? 1u : 0u;
+    job.s_begin = s_begin; job.s_count = s_count; job.owner = d_owner; job.ao_w = d_ao;
+    return ao_chunks<BakeJob>(sc, job, g.K, items, bp->max_distance, b, spawn, accum);   // (t_max = max_distance)
 }
 
 int end_call(pt_scene *sc) {
@@ -233,12 +212,12 @@ __attribute__((visibility("default"))) int pt_bake_render_samples(pt_scene *sc, 
     if (int st = upload_selection(sc, prim_select, n_prims, tmp, d_selected, n_selected)) return st;
     const bool dev = buffers_are_device != 0;
     uint32_t *d_owner = dev ? buffers->owner : nullptr;
-    if (!d_owner) BAKE_ALLOC(tmp, d_owner, n * 4, "owner map");
+    if (!d_owner) SIDE_ALLOC(tmp, d_owner, n * 4, "bake owner map");
     if (int st = raster(sc, a, d_selected, n_selected, d_owner)) return st;
     float *d_pos = dev ? buffers->position : nullptr, *d_nrm = dev ? buffers->normal : nullptr;
     if (buffers->position || buffers->normal) {
-        if (buffers->position && !d_pos) BAKE_ALLOC(tmp, d_pos, n * 12, "position plane");
-        if (buffers->normal && !d_nrm) BAKE_ALLOC(tmp, d_nrm, n * 12, "normal plane");
+        if (buffers->position && !d_pos) SIDE_ALLOC(tmp, d_pos, n * 12, "bake position plane");
+        if (buffers->normal && !d_nrm) SIDE_ALLOC(tmp, d_nrm, n * 12, "bake normal plane");
         sc->begin("bake_points", n);
         launch(sc, "ptbake::k_bake_points", k_bake_points, texel_grid(a), dim3(256), sc->ds, a, (const uint32_t *)d_owner, d_pos, d_nrm);
         sc->end();
@@ -247,13 +226,12 @@ __attribute__((visibility("default"))) int pt_bake_render_samples(pt_scene *sc, 
     float4 *d_ao = dev ? reinterpret_cast<float4 *>(buffers->ao_w) : nullptr;
     if (buffers->ao_w) {
         if (!d_ao) {
-            BAKE_ALLOC(tmp, d_ao, n * 16, "ao plane");
+            SIDE_ALLOC(tmp, d_ao, n * 16, "bake ao plane");
             HIP_TRY(hipMemcpyAsync(d_ao, buffers->ao_w, n * 16, hipMemcpyHostToDevice, sc->stream));   // (added to)
         }
-        RayBuffers b;
-        const size_t items = (size_t)a.slots * g.S, rays = items * g.K;
-        BAKE_ALLOC(tmp, b.ray, rays * 32, "rays"); BAKE_ALLOC(tmp, b.w, rays * 4, "rays"); BAKE_ALLOC(tmp, b.occ, rays * 4, "rays");
-        BAKE_ALLOC(tmp, b.base, items * 4, "rays"); BAKE_ALLOC(tmp, b.count, 4, "rays");
+        AORayBuffers b;
+        const size_t items = (size_t)a.slots * g.S;
+        if (int st = b.alloc(items, items * g.K, "bake rays")) return st;
         for (uint32_t s0 = first, end = first + n_samples; s0 < end; s0 += g.S)
             if (int st = bake_pass(sc, g, bp, s0, std::min(g.S, end - s0), d_owner, d_ao, b)) return st;
     }
@@ -303,12 +281,12 @@ __attribute__((visibility("default"))) int pt_bake_dilate(pt_scene *sc, const ui
     uint8_t *cov[2] = {nullptr, nullptr};
     if (!dev) {
         uint32_t *up = nullptr;
-        BAKE_ALLOC(tmp, up, n * 4, "dilation"); BAKE_ALLOC(tmp, buf[0], bytes, "dilation");
+        SIDE_ALLOC(tmp, up, n * 4, "bake dilation"); SIDE_ALLOC(tmp, buf[0], bytes, "bake dilation");
         HIP_TRY(hipMemcpyAsync(up, owner, n * 4, hipMemcpyHostToDevice, sc->stream));
         HIP_TRY(hipMemcpyAsync(buf[0], plane, bytes, hipMemcpyHostToDevice, sc->stream));
         d_owner = up;
     }
-    BAKE_ALLOC(tmp, buf[1], bytes, "dilation"); BAKE_ALLOC(tmp, cov[0], n, "dilation"); BAKE_ALLOC(tmp, cov[1], n, "dilation");
+    SIDE_ALLOC(tmp, buf[1], bytes, "bake dilation"); SIDE_ALLOC(tmp, cov[0], n, "bake dilation"); SIDE_ALLOC(tmp, cov[1], n, "bake dilation");
     sc->begin("bake_dilate", n);
     launch(sc, "ptbake::k_bake_covered", k_bake_covered, texel_grid(a), dim3(256), a, d_owner, cov[0]);
     sc->end();
@@ -348,9 +326,9 @@ __attribute__((visibility("default"))) int pt_bake_rays(pt_scene *sc, const PtBa
     DevTmp tmp;
     uint32_t *d_selected = nullptr, n_selected = 0, *d_owner = nullptr, *d_in = nullptr; float *d_out = nullptr; uint8_t *d_found = nullptr;
     if (int st = upload_selection(sc, prim_select, n_prims, tmp, d_selected, n_selected)) return st;
-    BAKE_ALLOC(tmp, d_owner, (size_t)g.atlas.n_texels * 4, "owner map");
+    SIDE_ALLOC(tmp, d_owner, (size_t)g.atlas.n_texels * 4, "bake owner map");
     if (int st = raster(sc, g.atlas, d_selected, n_selected, d_owner)) return st;
-    BAKE_ALLOC(tmp, d_in, (size_t)n * 12, "rays"); BAKE_ALLOC(tmp, d_out, (size_t)n * 28, "rays"); BAKE_ALLOC(tmp, d_found, n, "rays");
+    SIDE_ALLOC(tmp, d_in, (size_t)n * 12, "bake rays"); SIDE_ALLOC(tmp, d_out, (size_t)n * 28, "bake rays"); SIDE_ALLOC(tmp, d_found, n, "bake rays");
     HIP_TRY(hipMemcpyAsync(d_in, texel, (size_t)n * 4, hipMemcpyHostToDevice, sc->stream));
     HIP_TRY(hipMemcpyAsync(d_in + n, sample, (size_t)n * 4, hipMemcpyHostToDevice, sc->stream));
     HIP_TRY(hipMemcpyAsync(d_in + 2 * (size_t)n, element, (size_t)n * 4, hipMemcpyHostToDevice, sc->stream));

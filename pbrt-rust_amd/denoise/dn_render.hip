@@ -7,6 +7,7 @@
 // restate its film_tool_begin / film_tool_end), and ADDS the launch kinds "denoise_prepare", "denoise_variance" and "denoise_atrous" to the kernel statistics of the last render; the
 // counters are not touched. The workspace lives for the call.
 #include "../csrc/host_common.h"
+#include "../side/side_host.h"
 #include "../../include/mi355dn.h"
 #include "dn_kernels.h"
 #include <cmath>
@@ -63,23 +64,22 @@ __attribute__((visibility("default"))) int pt_denoise(pt_scene *sc, const PtDeno
     const DnImage im{width, height};
     const DnParams p{dp->sigma_l, dp->sigma_z, dp->sigma_n * dp->sigma_n, dp->albedo_floor, dp->scale};
     DevTmp tmp;
-    auto oom = [](hipError_t e) { (void)hipGetLastError(); return fail(PT_ERR_OUT_OF_MEMORY, std::string("pt_denoise: ") + hipGetErrorString(e)); };
     float4 *img[2] = {nullptr, nullptr}, *guide = nullptr;
     float *noise = nullptr;
-    for (float4 *&q : img) if (hipError_t e = tmp.alloc(&q, n_pix * 16); e != hipSuccess) return oom(e);
-    if (hipError_t e = tmp.alloc(&guide, n_pix * 32); e != hipSuccess) return oom(e);
-    if (hipError_t e = tmp.alloc(&noise, n_pix * 4); e != hipSuccess) return oom(e);
+    for (float4 *&q : img) SIDE_ALLOC(tmp, q, n_pix * 16, "pt_denoise");
+    SIDE_ALLOC(tmp, guide, n_pix * 32, "pt_denoise");
+    SIDE_ALLOC(tmp, noise, n_pix * 4, "pt_denoise");
     const float *in[5] = {film_a, film_b, sums->albedo_w, sums->normal_w, sums->depth_w};
     float *out = rgb_out;
     if (!buffers_are_device) {
         const size_t bytes[5] = {n_pix * 16, n_pix * 16, n_pix * 16, n_pix * 16, n_pix * 8};
         for (int k = 0; k < 5; ++k) {
             float *d = nullptr;
-            if (hipError_t e = tmp.alloc(&d, bytes[k]); e != hipSuccess) return oom(e);
+            SIDE_ALLOC(tmp, d, bytes[k], "pt_denoise");
             HIP_TRY(hipMemcpyAsync(d, in[k], bytes[k], hipMemcpyHostToDevice, sc->stream));
             in[k] = d;
         }
-        if (hipError_t e = tmp.alloc(&out, n_pix * 12); e != hipSuccess) return oom(e);
+        SIDE_ALLOC(tmp, out, n_pix * 12, "pt_denoise");
     }
     const DnSums s{(const float4 *)in[2], (const float4 *)in[3], (const float2 *)in[4]};
     sc->begin("denoise_prepare", n_pix);

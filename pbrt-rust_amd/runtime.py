@@ -12,28 +12,23 @@ from . import _abi_bake as BAKE
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # The HIP libraries, in build order: the product library, then those linked against it. name: (directory, file, ctypes mirror, header under include/).
-# What builds them, finds them, loads them (Library) and checks their exports (__graft_entry__.build) reads this table and the one below it.
+# What builds them, finds them, loads them (Library) and checks their exports (__graft_entry__.build) reads this table.
 LIBRARIES = {
     "pt": ("csrc", "libmi355pt.so", A, "mi355pt.h"),
     "ao": ("ao", "libmi355ao.so", AO, "mi355ao.h"),          # the ambient-occlusion integrator
     "aov": ("aov", "libmi355aov.so", AOV, "mi355aov.h"),     # the feature buffers for denoising
     "dn": ("denoise", "libmi355dn.so", DN, "mi355dn.h"),     # the a-trous denoiser over half films and feature buffers
-}
-# LIBRARIES holds what renders through a camera (a PtRenderParams, a film). The libraries that work in a mesh's texture space have their own table of the same rows,
-# built after the others; ALL_LIBRARIES is the two in build order, and what builds, finds, loads and checks libraries reads that.
-ATLAS_LIBRARIES = {
     "bake": ("bake", "libmi355bake.so", BAKE, "mi355bake.h"),   # AO, bent normals, positions and normals baked into a UV atlas
 }
-ALL_LIBRARIES = {**LIBRARIES, **ATLAS_LIBRARIES}
-LIB_PATHS = {name: os.path.join(_HERE, sub, file) for name, (sub, file, _, _) in ALL_LIBRARIES.items()}
+LIB_PATHS = {name: os.path.join(_HERE, sub, file) for name, (sub, file, _, _) in LIBRARIES.items()}
 LIB_PATHS["pt"] = os.environ.get("PT_LIB_PATH") or LIB_PATHS["pt"]   # PT_LIB_PATH: kernel-variant experiments
 LIB_PATH, AO_LIB_PATH, AOV_LIB_PATH, DN_LIB_PATH = (LIB_PATHS[name] for name in ("pt", "ao", "aov", "dn"))
 TABLES_PATH = os.path.join(_HERE, "data", "sobol_tables.bin")
 
 
 def build_library(verbose=False):
-    """Compile every HIP source for gfx950 (hipcc cross-compiles without a GPU): the libraries of ALL_LIBRARIES, in its order."""
-    for sub, file, _, _ in ALL_LIBRARIES.values():
+    """Compile every HIP source for gfx950 (hipcc cross-compiles without a GPU): the libraries of LIBRARIES, in its order."""
+    for sub, file, _, _ in LIBRARIES.values():
         r = subprocess.run(["make", "-C", os.path.join(_HERE, sub), "-j8"], capture_output=True, text=True)
         if verbose or r.returncode != 0:
             print(r.stdout[-4000:]); print(r.stderr[-4000:])
@@ -53,13 +48,13 @@ class Library:
         self.lib = A.bind(C.CDLL(path), strict=not os.environ.get("PT_LIB_PATH"))   # (PT_LIB_PATH: a kernel-variant library of an A/B run, possibly built from an older tree)
 
     def __getattr__(self, name):
-        """.ao, .aov, .dn, .bake: a library of ALL_LIBRARIES linked against the product library, loaded and bound on first use (and then an attribute like any other)."""
-        if name == "pt" or name not in ALL_LIBRARIES:
+        """.ao, .aov, .dn, .bake: a library of LIBRARIES linked against the product library, loaded and bound on first use (and then an attribute like any other)."""
+        if name == "pt" or name not in LIBRARIES:
             raise AttributeError(name)
         path = LIB_PATHS[name]
         if not os.path.exists(path):
             raise PtError(f"{path} not found: build it with __graft_entry__.build() (no CPU fallback exists)")
-        setattr(self, name, A.bind(C.CDLL(path), table=ALL_LIBRARIES[name][2].ENTRY_POINTS))
+        setattr(self, name, A.bind(C.CDLL(path), table=LIBRARIES[name][2].ENTRY_POINTS))
         return getattr(self, name)
 
     def check(self, st, what=""):

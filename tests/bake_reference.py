@@ -226,7 +226,7 @@ def array_samples(oracle, pkg, sampler, width, height, px, py, numbers):
 
 
 def directions(oracle, u, cos_sample):
-    """(wi (m, 3), pdf (m,)) of the array values u (m, 2): cosine_sample_hemisphere or uniform_sample_sphere (ao/ao_kernels.h:67-77)."""
+    """(wi (m, 3), pdf (m,)) of the array values u (m, 2): cosine_sample_hemisphere or uniform_sample_sphere (side/ao_rays.h: ao_ray)."""
     sin = np.frompyfunc(lambda x: oracle.lib.orc_dm_sin(float(x)), 1, 1)
     cos = np.frompyfunc(lambda x: oracle.lib.orc_dm_cos(float(x)), 1, 1)
     ux, uy = u[:, 0].astype(F), u[:, 1].astype(F)

@@ -236,3 +236,22 @@ def test_the_pass_budget_and_bump_are_not_restated():
     bump = {os.path.basename(p): text(p).count("udisplace - displace") for p in native if "udisplace - displace" in text(p)}
     assert bump == {"kern_shade.h": 1, "aov_kernels.h": 1}, bump
     assert "NOTE: the body is k_shade's" in text(os.path.join(root, "aov", "aov_kernels.h"))
+
+
+def test_what_the_side_libraries_share_is_not_restated():
+    """What the libraries beside libmi355pt share among themselves stands once, under side/: the AO ray (side/ao_rays.h) and, on the host (side/side_host.h), the
+    sample-number limits of an AO job, the first-hit chase and the out-of-memory failure of a call's scratch allocations.
+    The AO direction sampling stands in ao_ray and, restated, in k_ao_rays -- in no third place. (Through the inlined helper k_ao_rays<false> took 83 VGPRs for 79, so
+    the kernel keeps its body under a NOTE that says so: profiles/r6/NOTES.md section 21. With the helper this count would be one header.)"""
+    import glob
+    root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "pbrt-rust_amd")
+    text = lambda p: open(p, errors="replace").read()
+    native = [p for ext in ("h", "hip", "cpp") for p in glob.glob(os.path.join(root, "**", "*." + ext), recursive=True)]
+    where = lambda phrase: {os.path.relpath(p, root).replace(os.sep, "/"): text(p).count(phrase) for p in native if phrase in text(p)}
+    # (csrc/ has the uniform-sphere line twice more, in its light and phase-function sampling: other functions, libmi355pt's)
+    assert {p: n for p, n in where("1.0f - 2.0f * u.x").items() if not p.startswith("csrc/")} == {"side/ao_rays.h": 1, "ao/ao_kernels.h": 1}
+    assert "NOTE: the loop body is ao_ray's" in text(os.path.join(root, "ao", "ao_kernels.h"))
+    for phrase in ("the Sobol' tables serve at this resolution", "Halton sampler's 64-bit index", "still going on behind material-less surfaces"):
+        assert where(phrase) == {"side/side_host.h": 1}, phrase
+    strings = where("hipGetErrorString")
+    assert "side/side_host.h" in strings and not [p for p in strings if p.split("/")[0] in ("ao", "aov", "bake", "denoise")], strings

@@ -169,6 +169,11 @@ def test_ao_errors_are_returned_with_their_text(pkg, gpu):
     assert b"Sobol" in gpu.lib.pt_last_error()
     s = C.c_uint32()
     assert gpu.ao.pt_ao_pass_size(sc.h, C.byref(rp), C.byref(ao), C.byref(s)) == A.PT_ERR_INVALID_ARG
+    rp.sampler_type = A.PT_SAMPLER_HALTON; rp.spp = 1 << 31   # 2^62 sample numbers per pixel; the Halton stride of a 16 x 16 grid is 2^4 * 3^3 = 432: 64-bit indices reach 4.3e16 of them
+    assert gpu.ao.pt_ao_render(sc.h, C.byref(rp), C.byref(ao), film.ctypes.data_as(C.c_void_p), 0) == A.PT_ERR_INVALID_ARG
+    assert b"Halton" in gpu.lib.pt_last_error()
+    assert gpu.ao.pt_ao_pass_size(sc.h, C.byref(rp), C.byref(ao), C.byref(s)) == A.PT_ERR_INVALID_ARG
+    assert b"Halton" in gpu.lib.pt_last_error()
     assert not film.any()
 
 

@@ -223,6 +223,9 @@ def test_refusals_that_read_the_scene(pkg, gpu):
     with pytest.raises(pkg.runtime.PtError) as e:
         sc.bake(0, 8, 8, 1 << 20, nsamples=1 << 31, planes=("ao_w",))
     assert "Sobol" in str(e.value)
+    with pytest.raises(pkg.runtime.PtError) as e:   # (the Halton stride of an 8 x 8 grid is 2^3 * 3^2 = 72: 64-bit indices reach 2.6e17 sample numbers, not 2^62)
+        sc.bake(0, 8, 8, 1 << 31, nsamples=1 << 31, sampler="halton", planes=("ao_w",))
+    assert "Halton" in str(e.value)
     assert (sc.bake(0, 8, 8, 1, planes=("owner",))["owner"] != NONE).all()   # the scene bakes after the refusals
 
 

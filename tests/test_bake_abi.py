@@ -36,7 +36,7 @@ def test_the_library_exports_what_its_map_names_and_the_header_declares(pkg):
     if not os.path.exists(path):
         pytest.fail(f"{path} missing: __graft_entry__.build() builds it")
     R = pkg.runtime
-    assert R.ATLAS_LIBRARIES["bake"] == ("bake", "libmi355bake.so", pkg._abi_bake, "mi355bake.h") and list(R.ALL_LIBRARIES) == list(R.LIBRARIES) + list(R.ATLAS_LIBRARIES)
+    assert R.LIBRARIES["bake"] == ("bake", "libmi355bake.so", pkg._abi_bake, "mi355bake.h") and not hasattr(R, "ATLAS_LIBRARIES") and not hasattr(R, "ALL_LIBRARIES")
     r = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True)
     names = {line.split()[-1] for line in r.stdout.splitlines() if line.strip()}
     assert names == set(pkg._abi_bake.ENTRY_POINTS)

@@ -129,7 +129,7 @@ def test_checkpoint_header_matches_the_ctypes_mirror(pkg, tmp_path):
 
 def test_one_table_of_libraries(pkg):
     R = pkg.runtime
-    assert list(R.LIBRARIES) == ["pt", "ao", "aov", "dn"]
+    assert list(R.LIBRARIES) == ["pt", "ao", "aov", "dn", "bake"]
     for name, (sub, file, abi, header) in R.LIBRARIES.items():
         assert os.path.isfile(os.path.join(INC, header)) and os.path.isdir(os.path.join(os.path.dirname(R.__file__), sub)), name
         assert abi.ENTRY_POINTS and R.LIB_PATHS[name].endswith(os.path.join(sub, file)) or (name == "pt" and os.environ.get("PT_LIB_PATH")), name
@@ -137,6 +137,6 @@ def test_one_table_of_libraries(pkg):
     # build()'s checks and Library's loaders read that table: nobody else spells the files' names
     runtime = open(R.__file__).read()
     entry = "\n".join(line.split("#")[0] for line in open(os.path.join(ROOT, "__graft_entry__.py")).read().splitlines())
-    for file in ("libmi355ao.so", "libmi355aov.so", "libmi355dn.so"):
+    for file in ("libmi355ao.so", "libmi355aov.so", "libmi355dn.so", "libmi355bake.so"):
         assert runtime.count(file) == 1 and entry.count(file) == 0, file
     assert "LIBRARIES" in entry and "ENTRY_POINTS" in entry
