@@ -5,6 +5,8 @@
  * traversal, the samplers' arrays and the pass budget through libmi355pt's driver. There is no camera, no path state and no film:
  * the front of the pipe is its own -- which triangle owns which texel (k_bake_raster), the surface point there (k_bake_points), the
  * AO rays from it (k_bake_rays), their any-hit walk (libmi355pt's k_trace, launch kind "shadow") and the sums (k_bake_accum).
+ * pt_bake_transfer (below, "Transfer") fills the atlas of one scene's mesh with what rays from its surface hit in ANOTHER scene: the
+ * height, position, world- and tangent-space normal of a detailed mesh, and the AO there.
  *
  * ---- the contract -----------------------------------------------------------------------------------------------------------------
  *
@@ -115,6 +117,90 @@ int pt_bake_dilate(pt_scene *scene, const uint32_t *owner, float *plane, uint32_
  * The parameters, the selection and their checks are pt_bake_render's (spp_per_pass and profile are not read). */
 int pt_bake_rays(pt_scene *scene, const PtBakeParams *params, const uint8_t *prim_select, uint32_t n_prims, uint32_t n, const uint32_t *texel, const uint32_t *sample,
                  const uint32_t *element, float *out_o, float *out_d, float *out_w, uint8_t *found);
+
+/* ---- Transfer: another scene projected onto the atlas ------------------------------------------------------------------------------
+ *
+ * The other half of a baker's job: a low-polygon mesh with UVs (the TARGET scene, whose atlas is filled) and a detailed mesh without
+ * them (the SOURCE scene, which the rays see). Per owned texel one projection ray goes from above the target's surface straight down
+ * through the source; what it hits first leaves a height, a position, a world-space and a tangent-space normal, and the ambient
+ * occlusion of the source at that point. The two handles may be the same: the target is then part of what the rays see and every
+ * projection ray hits it at t = front or sooner -- rarely what one wants. Both must live on the same device. The target is only read:
+ * every launch runs on the source scene's stream, and the counters and kernel statistics of the call are the SOURCE scene's.
+ *
+ * Every operation float32, unfused, in this order; cross, dot, normalize, coordinate_system and face_forward are dev_math.h's
+ * (vector.rs): cross in float64 products rounded once, normalize(a) = a * (1 / sqrt(dot(a, a))).
+ *
+ * 1. Texel and owner. As above: texel centres, ownership with the texel box, and the owner's interaction si at the centre -- on the
+ *    target scene. ns = normalize(si.sh_n).
+ * 2. Projection ray. d = -ns, o = si.p + ns * front (no error-bound offset), t_max = front + back. A closest-hit query, Scene::intersect,
+ *    through the source scene (libmi355pt's k_trace, launch kind "extend"; intersect_tests counts them). It is the same ray for every
+ *    sample of the texel: one ray per owned texel per call.
+ * 3. Hit. hit_prim = the source primitive (as pt_trace_closest reports it) or PT_NONE; height = front - t. A DETAIL HIT is a hit on a
+ *    top-level triangle of the source: hs = the interaction Triangle::intersect builds for the hit's primitive and barycentrics, as
+ *    pt_trace_closest reports them (tri_fill_interaction); src_position = hs.p; src_normal = nh = normalize(hs.sh_n), negated when
+ *    dot(nh, d) > 0. A hit on a sphere, a disk or a primitive of an instanced object writes hit_prim and height only: the other planes
+ *    are 0 there and no AO ray starts. A miss or a texel without owner: 0 everywhere, PT_NONE in hit_prim.
+ * 4. Tangent frame of the target texel. sv = si.dpdu - ns * dot(ns, si.dpdu). If dot(sv, sv) > 0: sv = normalize(sv), tv = cross(ns, sv),
+ *    and tv = -tv when dot(tv, si.dpdv) < 0 -- a mirrored UV island keeps its handedness; else (sv, tv) = coordinate_system(ns).
+ *    dpdu and dpdv are Triangle::intersect's (triangle.rs:236-265; for degenerate UVs coordinate_system of the geometric normal).
+ *    tangent_normal = (dot(nh, sv), dot(nh, tv), dot(nh, ns)).
+ * 5. AO at a detail hit: AOIntegrator::li (ao.rs:78-107) with the projection ray as its camera ray. Frame n = face_forward(hs.n, -d),
+ *    s = normalize(hs.dpdu), t = cross(hs.n, s). Element k of sample s of texel (x, y): the array value of sample number
+ *    s * nsamples + k, dimensions 5 and 6, sample bounds [0, width) x [0, height); direction, origin (offset_ray_origin(hs.p, hs.p_error,
+ *    hs.n, wi)) and weight as under "AO rays" above, by the same device function. The any-hit walk goes through the source scene with
+ *    t_max = max_distance. ao_w gains the unoccluded rays' wi and w in ascending (s, k) order, onto what the buffer holds: sample
+ *    ranges baked in ascending order, any spp_per_pass and repeated calls leave the same bytes. pt_bake_resolve and pt_bake_dilate
+ *    serve the planes unchanged; hit_prim is a valid coverage map for pt_bake_dilate.
+ *
+ * Launch kinds (the source scene's pt_get_kernel_stats): "bake_select", "bake_raster", "bake_project" (the projection rays), "extend"
+ * (their closest-hit walk), "bake_transfer_points", and with ao_w "bake_transfer_rays", "shadow", "bake_accum" ("bake_probe" for
+ * pt_bake_transfer_rays). The projection rays are traced in slices of 8 x 8-texel tiles sized by the pass budget. */
+typedef struct PtBakeTransferParams {
+    uint32_t width, height;      /* the target's atlas; width * height <= 2^28                                            */
+    float    front, back;        /* the projection ray starts `front` above the target's surface along its shading normal */
+                                 /* and ends `back` below it; both >= 0 and finite, front + back > 0                      */
+    uint32_t spp;                /* the AO at the source hit: PtBakeParams' meaning. spp, nsamples, max_distance and       */
+    uint32_t nsamples;           /* sampler_type are read -- and checked -- only when ao_w is wanted                      */
+    uint32_t cos_sample;
+    float    max_distance;
+    uint32_t sampler_type;
+    uint32_t spp_per_pass;       /* 0: the library chooses from the free memory                                           */
+    uint32_t profile;            /* != 0: time every launch kind                                                          */
+} PtBakeTransferParams;
+
+typedef struct PtBakeTransferBuffers {   /* width * height entries, row-major; NULL = not wanted */
+    uint32_t *owner;             /* target primitive that owns the texel (pt_bake_render's owner map) -- written          */
+    uint32_t *hit_prim;          /* source primitive the projection ray hits first, PT_NONE for none -- written           */
+    float *height;               /* 1: front - t of that hit, 0 without one -- written                                    */
+    float *src_position;         /* 3: the source hit point -- written                                                    */
+    float *src_normal;           /* 3: the source's normalised shading normal there, world space -- written               */
+    float *tangent_normal;       /* 3: the same vector in the target texel's tangent frame -- written                     */
+    float *ao_w;                 /* 4: sums of the unoccluded AO directions and weights at the source hit -- ADDED to     */
+} PtBakeTransferBuffers;
+
+/* Projects the source scene onto the atlas of the target's primitives selected by prim_select (HOST memory, n_prims bytes: the TARGET's
+ * primitives) and bakes params->spp AO samples per detail hit. Without ao_w no AO ray is traced and no sample number is drawn.
+ * Errors. PT_ERR_INVALID_ARG, before the device is touched and in this order, for a NULL target, source, params, prim_select or buffers;
+ * width or height 0 or more than 2^28 texels; front or back negative, infinite or NaN, or front + back == 0; all seven planes NULL; with
+ * ao_w wanted: spp or nsamples 0, max_distance not positive, an unknown sampler_type, a bad sample range; nothing selected; n_prims
+ * different from the target's primitive count. Then, with the source's device bound: the two scenes on different devices; more sample
+ * numbers per texel than the sampler's tables serve. PT_ERR_UNSUPPORTED as pt_bake_render, for the selection. Host planes are written
+ * only after everything has succeeded. */
+int pt_bake_transfer(pt_scene *target, pt_scene *source, const PtBakeTransferParams *params, const uint8_t *prim_select, uint32_t n_prims,
+                     const PtBakeTransferBuffers *buffers, int buffers_are_device);
+/* AO samples [first_sample, first_sample + n_samples) of every detail hit (the range is read only when ao_w is wanted); the written planes
+ * are written again, the same. pt_bake_transfer is the call (0, spp). */
+int pt_bake_transfer_samples(pt_scene *target, pt_scene *source, const PtBakeTransferParams *params, const uint8_t *prim_select, uint32_t n_prims,
+                             uint32_t first_sample, uint32_t n_samples, const PtBakeTransferBuffers *buffers, int buffers_are_device);
+/* AO samples per texel per pass pt_bake_transfer would use (pt_bake_pass_size's rule, on the source scene); spp and nsamples are checked. */
+int pt_bake_transfer_pass_size(pt_scene *target, pt_scene *source, const PtBakeTransferParams *params, uint32_t *spp_per_pass);
+/* Parity entry, in the style of pt_bake_rays: for n triples (texel index, sample number s, element k) -- host arrays -- the texel's
+ * projection ray (proj_o, proj_d, proj_tmax) and the AO ray (ao_o, ao_d, ao_w) from its detail hit, by the device functions the bake
+ * uses. found[i]: bit 0 = the texel has an owner (else the projection ray is zeros), bit 1 = its ray made a detail hit (else the AO ray
+ * is zeros). The parameters, the selection and their checks are pt_bake_transfer's with ao_w wanted (spp_per_pass and profile are not read). */
+int pt_bake_transfer_rays(pt_scene *target, pt_scene *source, const PtBakeTransferParams *params, const uint8_t *prim_select, uint32_t n_prims, uint32_t n,
+                          const uint32_t *texel, const uint32_t *sample, const uint32_t *element, float *proj_o, float *proj_d, float *proj_tmax,
+                          float *ao_o, float *ao_d, float *ao_w, uint8_t *found);
 
 #ifdef __cplusplus
 }

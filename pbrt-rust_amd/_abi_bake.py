@@ -17,17 +17,38 @@ class PtBakeBuffers(C.Structure):
     _fields_ = [("owner", u32p), ("position", fp), ("normal", fp), ("ao_w", fp)]
 
 
-def buffers(planes, device=False):
+def buffers(planes, device=False, struct=PtBakeBuffers):
     """The PtBakeBuffers of {plane: a contiguous array of its dtype -- with `device`: a device pointer as an integer}; a plane that is not there is NULL."""
-    b = PtBakeBuffers()
-    for k, (name, ctype) in enumerate(PtBakeBuffers._fields_):
+    b = struct()
+    for k, (name, ctype) in enumerate(struct._fields_):
         if name in planes:
             setattr(b, name, C.cast(C.c_void_p(planes[name]), ctype) if device else planes[name].ctypes.data_as(ctype))
     return b
 
 
+# pt_bake_transfer: PtBakeTransferBuffers' fields, in this order
+TRANSFER_PLANES = ("owner", "hit_prim", "height", "src_position", "src_normal", "tangent_normal", "ao_w")
+TRANSFER_CHANNELS = {"owner": 1, "hit_prim": 1, "height": 1, "src_position": 3, "src_normal": 3, "tangent_normal": 3, "ao_w": 4}
+TRANSFER_DTYPES = {k: ("uint32" if k in ("owner", "hit_prim") else "float32") for k in TRANSFER_PLANES}
+
+
+class PtBakeTransferParams(C.Structure):
+    _fields_ = [("width", u32), ("height", u32), ("front", C.c_float), ("back", C.c_float), ("spp", u32), ("nsamples", u32), ("cos_sample", u32), ("max_distance", C.c_float),
+                ("sampler_type", u32), ("spp_per_pass", u32), ("profile", u32)]
+
+
+class PtBakeTransferBuffers(C.Structure):
+    _fields_ = [("owner", u32p), ("hit_prim", u32p), ("height", fp), ("src_position", fp), ("src_normal", fp), ("tangent_normal", fp), ("ao_w", fp)]
+
+
+def transfer_buffers(planes, device=False):
+    """The PtBakeTransferBuffers of {plane: array or device pointer}, as buffers()."""
+    return buffers(planes, device, PtBakeTransferBuffers)
+
+
 # Every symbol include/mi355bake.h declares, with its signature (restype, argtypes).
 _bp, _bb = C.POINTER(PtBakeParams), C.POINTER(PtBakeBuffers)
+_tp, _tb = C.POINTER(PtBakeTransferParams), C.POINTER(PtBakeTransferBuffers)
 ENTRY_POINTS = {
     "pt_bake_render": (C.c_int, [VP, _bp, u8p, u32, _bb, C.c_int]),
     "pt_bake_render_samples": (C.c_int, [VP, _bp, u8p, u32, u32, u32, _bb, C.c_int]),
@@ -35,4 +56,8 @@ ENTRY_POINTS = {
     "pt_bake_resolve": (C.c_int, [fp, u32, u32, fp, fp]),
     "pt_bake_dilate": (C.c_int, [VP, u32p, fp, u32, u32, u32, u32, C.c_int]),
     "pt_bake_rays": (C.c_int, [VP, _bp, u8p, u32, u32, u32p, u32p, u32p, fp, fp, fp, u8p]),
+    "pt_bake_transfer": (C.c_int, [VP, VP, _tp, u8p, u32, _tb, C.c_int]),
+    "pt_bake_transfer_samples": (C.c_int, [VP, VP, _tp, u8p, u32, u32, u32, _tb, C.c_int]),
+    "pt_bake_transfer_pass_size": (C.c_int, [VP, VP, _tp, u32p]),
+    "pt_bake_transfer_rays": (C.c_int, [VP, VP, _tp, u8p, u32, u32, u32p, u32p, u32p, fp, fp, fp, fp, fp, fp, u8p]),
 }

@@ -7,6 +7,11 @@
 //   k_bake_accum    ao_w += the unoccluded rays' wi and w, in element order
 //   k_bake_dilate   one iteration of the gutter fill
 //   k_bake_probe    pt_bake_rays: single rays by ao_ray, the function k_bake_rays' rays come from
+// and, for the transfer bake (pt_bake_transfer: another scene projected onto the atlas; the closest-hit walk of the projection rays is libmi355pt's k_trace too):
+//   k_bake_project          one lane per slot of a slice of the tile order: the projection ray of an owned texel
+//   k_bake_transfer_points  one thread per texel of the slice: the hit classified -> hit_prim, height, the three vector planes, the hit record of the AO passes
+//   k_bake_transfer_rays    k_bake_rays from the source hit (k_bake_accum adds them, with the detail-hit map in the owner map's place)
+//   k_bake_transfer_probe   pt_bake_transfer_rays: single projection and AO rays by the functions the kernels above use
 // No atomics other than the owner map's atomicMin and the per-wave ray-id reservation (wave_reserve).
 #pragma once
 #include "../csrc/kern_decl.h"
@@ -266,6 +271,155 @@ __global__ __launch_bounds__(256) void k_bake_probe(DeviceScene s, RenderConst r
     out_o[3 * (size_t)i] = o.x; out_o[3 * (size_t)i + 1] = o.y; out_o[3 * (size_t)i + 2] = o.z;
     out_d[3 * (size_t)i] = wo.x; out_d[3 * (size_t)i + 1] = wo.y; out_d[3 * (size_t)i + 2] = wo.z;
     out_w[i] = w; found[i] = prim != PT_NONE ? 1 : 0;
+}
+
+// ---- the transfer bake (mi355bake.h "Transfer"): `t` is the scene whose atlas is filled, `s` the scene the rays see
+
+// The projection ray of an owned texel (contract step 2): from `front` above the target's surface along its normalised shading normal, straight down
+PT_DEV void projection_ray(const SurfaceInteraction &si, float front, V3 &ns, V3 &o, V3 &d) { ns = normalize(si.sh_n); d = -ns; o = si.p + ns * front; }
+
+// The tangent frame of a target texel (step 4): dpdu made orthogonal to ns, its partner on dpdv's side (a mirrored island keeps its handedness)
+PT_DEV void tangent_frame(const SurfaceInteraction &si, V3 ns, V3 &sv, V3 &tv) {
+    sv = si.dpdu - ns * dot(ns, si.dpdu);
+    if (dot(sv, sv) > 0.0f) {
+        sv = normalize(sv); tv = cross(ns, sv);
+        if (dot(tv, si.dpdv) < 0.0f) tv = -tv;
+    } else coordinate_system(ns, sv, tv);
+}
+
+// The interaction of a detail hit and the frame of its AO rays (step 5): ao.rs:77-80 with the projection ray as the camera ray. `flip`: face_forward(hs.n, -d) turned n round
+PT_DEV AOFrame transfer_hit(const DeviceScene &s, float4 rec, bool flip, SurfaceInteraction &hs) {
+    tri_fill_interaction(s, s.prim_shape[__float_as_uint(rec.x)] & 0x3fffffffu, V3(0.0f, 0.0f, 0.0f), rec.y, rec.z, rec.w, true, hs);
+    AOFrame f; f.n = flip ? -hs.n : hs.n; f.sv = normalize(hs.dpdu); f.tv = cross(hs.n, f.sv); return f;
+}
+
+// Slots [slot0, slot0 + n_slots) of the tile order (slot0 a multiple of 64: a wave is a tile): ray ids in lane order, base[slot - slot0] = the texel's ray id or PT_NONE
+__global__ __launch_bounds__(256) void k_bake_project(DeviceScene t, BakeAtlas a, const uint32_t *owner, uint32_t slot0, uint32_t n_slots, float front, float t_max, float4 *ray, uint32_t *base,
+                                                      uint32_t *ray_count) {
+    const uint32_t rounded = (n_slots + 63u) & ~63u;   // whole waves iterate together (one ray-id reservation per wave)
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < rounded; i += gridDim.x * blockDim.x) {
+        uint32_t texel = PT_NONE, prim = PT_NONE;
+        if (i < n_slots) { texel = slot_texel(a, slot0 + i); if (texel != PT_NONE) prim = owner[texel]; }
+        const bool found = prim != PT_NONE;
+        const uint32_t id = wave_reserve(ray_count, found, 1u);
+        if (i >= n_slots) continue;
+        if (!found) { base[i] = PT_NONE; continue; }
+        base[i] = id;
+        SurfaceInteraction si;
+        texel_interaction(t, a, texel, prim, si);
+        V3 ns, o, d; projection_ray(si, front, ns, o, d);
+        ray[2 * (size_t)id] = make_float4(o.x, o.y, o.z, d.x);
+        ray[2 * (size_t)id + 1] = make_float4(d.y, d.z, t_max, 0.0f);   // (per-ray t_max: k_trace reads it from the record)
+    }
+}
+
+// The planes pt_bake_transfer writes (NULL: not wanted) and what the AO passes read: detail[texel] = PT_NONE, or -- a detail hit -- whether n was turned round;
+// rec[texel] = {source primitive, b0, b1, b2} of a detail hit (both NULL when no AO is wanted)
+struct TransferOut { uint32_t *hit_prim; float *height, *src_position, *src_normal, *tangent_normal; uint32_t *detail; float4 *rec; };
+PT_DEV void store3(float *plane, uint32_t texel, V3 v) { if (plane) { plane[3 * (size_t)texel] = v.x; plane[3 * (size_t)texel + 1] = v.y; plane[3 * (size_t)texel + 2] = v.z; } }
+
+// One thread per slot of the slice: the hit of the texel's projection ray (hit: {prim, b0, b1, b2}, hit_t, by ray id), classified (steps 3 and 4). `top`: k_bake_top's
+// marks of the source scene
+__global__ __launch_bounds__(256) void k_bake_transfer_points(DeviceScene t, DeviceScene s, BakeAtlas a, const uint32_t *owner, const uint8_t *top, uint32_t slot0, uint32_t n_slots,
+                                                              const uint32_t *base, const float4 *hit, const float *hit_t, float front, TransferOut out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_slots) return;
+    const uint32_t texel = slot_texel(a, slot0 + i);
+    if (texel == PT_NONE) return;
+    uint32_t hit_prim = PT_NONE, detail = PT_NONE;
+    float height = 0.0f;
+    V3 p(0.0f, 0.0f, 0.0f), nh(0.0f, 0.0f, 0.0f), tn(0.0f, 0.0f, 0.0f);
+    float4 rec = make_float4(__uint_as_float(PT_NONE), 0.0f, 0.0f, 0.0f);
+    const uint32_t id = base[i];
+    if (id != PT_NONE) {
+        const float4 h = hit[id];
+        hit_prim = __float_as_uint(h.x);
+        if (hit_prim != PT_NONE) {
+            height = front - hit_t[id];
+            if ((s.prim_shape[hit_prim] >> 30) == PT_SHAPE_TRIANGLE && top[hit_prim]) {
+                V3 ns, sv, tv;
+                {   // the target texel: its normal and tangent frame
+                    SurfaceInteraction si;
+                    texel_interaction(t, a, texel, owner[texel], si);
+                    ns = normalize(si.sh_n);
+                    tangent_frame(si, ns, sv, tv);
+                }
+                SurfaceInteraction hs;
+                tri_fill_interaction(s, s.prim_shape[hit_prim] & 0x3fffffffu, -ns, h.y, h.z, h.w, true, hs);
+                p = hs.p;
+                nh = normalize(hs.sh_n);
+                if (dot(nh, -ns) > 0.0f) nh = -nh;
+                tn = V3(dot(nh, sv), dot(nh, tv), dot(nh, ns));
+                detail = dot(hs.n, ns) < 0.0f ? 1u : 0u;   // face_forward(hs.n, -d)
+                rec = h;
+            }
+        }
+    }
+    if (out.hit_prim) out.hit_prim[texel] = hit_prim;
+    if (out.height) out.height[texel] = height;
+    store3(out.src_position, texel, p); store3(out.src_normal, texel, nh); store3(out.tangent_normal, texel, tn);
+    if (out.detail) { out.detail[texel] = detail; out.rec[texel] = rec; }
+}
+
+// k_bake_rays from the source hits: job.owner is the detail-hit map, rec the hits
+struct TransferJob : BakeJob { const float4 *rec; };
+__global__ __launch_bounds__(256) void k_bake_transfer_rays(DeviceScene s, RenderConst rc, SobolTables tabs, BakeAtlas a, TransferJob job) {
+    const uint32_t total = a.slots * job.s_count;
+    const uint32_t rounded = (total + 63u) & ~63u;   // whole waves iterate together (one ray-id reservation per wave)
+    for (uint32_t item = blockIdx.x * blockDim.x + threadIdx.x; item < rounded; item += gridDim.x * blockDim.x) {
+        uint32_t texel = PT_NONE, sl = 0, detail = PT_NONE;
+        if (item < total) { texel = slot_texel(a, item % a.slots); sl = item / a.slots; if (texel != PT_NONE) detail = job.owner[texel]; }
+        const bool found = detail != PT_NONE;
+        const uint32_t first = wave_reserve(job.ray_count, found, job.kn);
+        if (item >= total) continue;
+        if (!found) { job.base[item] = PT_NONE; continue; }
+        job.base[item] = first;
+        SurfaceInteraction hs;
+        const AOFrame f = transfer_hit(s, job.rec[texel], detail != 0u, hs);
+        const int32_t px = (int32_t)(texel % a.width), py = (int32_t)(texel / a.width);
+        const uint64_t sample = (uint64_t)job.s_begin + sl;
+        const float nsf = (float)job.nsamples;
+        for (uint32_t kk = 0; kk < job.kn; ++kk) {
+            V3 o, wo; float w;
+            ao_ray(rc, tabs, hs, f, px, py, sample * job.nsamples + job.k0 + kk, job.cos_sample, nsf, o, wo, w);
+            const uint32_t id = first + kk;
+            job.ray[2 * (size_t)id] = make_float4(o.x, o.y, o.z, wo.x);
+            job.ray[2 * (size_t)id + 1] = make_float4(wo.y, wo.z, 0.0f, 0.0f);
+            job.w[id] = w;
+        }
+    }
+}
+
+// pt_bake_transfer_rays: the projection ray of texel[i] and the AO ray (sample[i], element[i]) from its detail hit. found[i]: bit 0 the texel has an owner, bit 1 a detail hit
+__global__ __launch_bounds__(256) void k_bake_transfer_probe(DeviceScene t, DeviceScene s, RenderConst rc, SobolTables tabs, BakeAtlas a, const uint32_t *owner, const uint32_t *detail,
+                                                             const float4 *rec, float front, float t_max, uint32_t nsamples, uint32_t cos_sample, uint32_t n, const uint32_t *texel,
+                                                             const uint32_t *sample, const uint32_t *element, float *out, uint8_t *found) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t tx = texel[i];
+    const uint32_t prim = tx < a.n_texels ? owner[tx] : PT_NONE;
+    V3 po(0.0f, 0.0f, 0.0f), pd(0.0f, 0.0f, 0.0f), o(0.0f, 0.0f, 0.0f), wo(0.0f, 0.0f, 0.0f);
+    float pt = 0.0f, w = 0.0f;
+    uint32_t bits = 0;
+    if (prim != PT_NONE) {
+        bits = 1u; pt = t_max;
+        {
+            SurfaceInteraction si;
+            texel_interaction(t, a, tx, prim, si);
+            V3 ns; projection_ray(si, front, ns, po, pd);
+        }
+        const uint32_t dt = detail[tx];
+        if (dt != PT_NONE) {
+            bits = 3u;
+            SurfaceInteraction hs;
+            const AOFrame f = transfer_hit(s, rec[tx], dt != 0u, hs);
+            ao_ray(rc, tabs, hs, f, (int32_t)(tx % a.width), (int32_t)(tx / a.width), (uint64_t)sample[i] * nsamples + element[i], cos_sample, (float)nsamples, o, wo, w);
+        }
+    }
+    float *r = out + 14 * (size_t)i;   // {projection o, d, t_max, AO o, d, w}
+    r[0] = po.x; r[1] = po.y; r[2] = po.z; r[3] = pd.x; r[4] = pd.y; r[5] = pd.z; r[6] = pt;
+    r[7] = o.x; r[8] = o.y; r[9] = o.z; r[10] = wo.x; r[11] = wo.y; r[12] = wo.z; r[13] = w;
+    found[i] = (uint8_t)bits;
 }
 
 }  // namespace ptbake

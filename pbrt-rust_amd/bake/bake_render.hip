@@ -10,6 +10,13 @@
 // There is no camera, no path state and no film, so the bake does not go through render_frame: the scene's stream, counters and traversal spill area come from
 // ensure_workspace with no paths and no film, the pass size from choose_pass_size with the bake's bytes per texel sample, the sampler set-up from fill_render_const
 // for a width x height image, the traversal through trace_job / trace_sub / traced as libmi355ao's AO rays go.
+// pt_bake_transfer / _samples / _pass_size / _rays project a SOURCE scene onto the atlas of a TARGET scene's mesh. Per call, after the target's selection and owner map:
+//   k_bake_top (source)            which source primitives are top-level: only their triangles are detail hits
+//   per slice of 8 x 8-texel tiles sized by the pass budget:
+//     k_bake_project               the projection ray of every owned texel
+//     k_trace<closest>             their closest-hit walk through the source ("extend", per-ray t_max = front + back) -- libmi355pt's
+//     k_bake_transfer_points       hit_prim, height, source position, world- and tangent-space normal; the hit records of the AO passes
+//   per pass and chunk (ao_w wanted): k_bake_transfer_rays, k_trace<any> through the source ("shadow"), k_bake_accum over the detail-hit map
 #include "../csrc/host_common.h"
 #include "../side/side_host.h"
 #include "../../include/mi355bake.h"
@@ -95,22 +102,30 @@ int begin_call(pt_scene *sc, bool profile) {
 
 dim3 texel_grid(const BakeAtlas &a) { return dim3((unsigned)(((size_t)a.n_texels + 255) / 256)); }
 
+// In the three functions below `of` is the scene whose primitives are read and `sc` the scene whose stream and statistics the launches run under (pt_bake_render: the
+// same scene; pt_bake_transfer: the target and the source). `of` is only read.
+// The marks of the top-level accelerator's primitives (d_top: zeroed, of->ds.n_prims bytes), inside the launch kind the caller has opened
+void launch_top(pt_scene *sc, const pt_scene *of, uint8_t *d_top) {
+    const uint32_t n_top = (uint32_t)of->ordered.size();
+    if (n_top > 0 && of->ds.n_nodes > 0) launch(sc, "ptbake::k_bake_top", k_bake_top, dim3((n_top + 255) / 256), dim3(256), of->ds, n_top, d_top);
+}
+
 // The selection on the device: the ascending list of selected primitives, every one of which must be a top-level triangle of a mesh with UVs. The check runs on the
 // device (k_bake_top, k_bake_check); what comes back is one word per 256 selected primitives and, for a refused selection, the codes of the first refused block.
 // (prim_select itself is walked on the host, a byte per primitive, and the list uploaded, 4 bytes per selected primitive: on every call, a continuation's included.)
-int upload_selection(pt_scene *sc, const uint8_t *prim_select, uint32_t n_prims, DevTmp &tmp, uint32_t *&d_selected, uint32_t &n_selected) {
-    const DeviceScene &ds = sc->ds;
+int upload_selection(pt_scene *sc, const pt_scene *of, const uint8_t *prim_select, uint32_t n_prims, DevTmp &tmp, uint32_t *&d_selected, uint32_t &n_selected) {
+    const DeviceScene &ds = of->ds;
     std::vector<uint32_t> selected;
     for (uint32_t p = 0; p < n_prims; ++p) if (prim_select[p]) selected.push_back(p);
     n_selected = (uint32_t)selected.size();
-    const uint32_t n_top = (uint32_t)sc->ordered.size(), n_blocks = (n_selected + 255) / 256;
+    const uint32_t n_top = (uint32_t)of->ordered.size(), n_blocks = (n_selected + 255) / 256;
     uint8_t *d_top = nullptr, *d_code = nullptr; uint32_t *d_refused = nullptr;
     SIDE_ALLOC(tmp, d_top, n_prims, "bake selection"); SIDE_ALLOC(tmp, d_selected, (size_t)n_selected * 4, "bake selection");
     SIDE_ALLOC(tmp, d_code, n_selected, "bake selection"); SIDE_ALLOC(tmp, d_refused, (size_t)n_blocks * 4, "bake selection");
     HIP_TRY(hipMemsetAsync(d_top, 0, n_prims, sc->stream));
     HIP_TRY(hipMemcpyAsync(d_selected, selected.data(), (size_t)n_selected * 4, hipMemcpyHostToDevice, sc->stream));
     sc->begin("bake_select", (uint64_t)n_top + n_selected);
-    if (n_top > 0 && ds.n_nodes > 0) launch(sc, "ptbake::k_bake_top", k_bake_top, dim3((n_top + 255) / 256), dim3(256), ds, n_top, d_top);
+    launch_top(sc, of, d_top);
     launch(sc, "ptbake::k_bake_check", k_bake_check, dim3(n_blocks), dim3(256), ds, (const uint8_t *)d_top, (const uint32_t *)d_selected, n_selected, d_code, d_refused);
     sc->end();
     HIP_TRY(hipGetLastError());
@@ -133,7 +148,7 @@ int upload_selection(pt_scene *sc, const uint8_t *prim_select, uint32_t n_prims,
 }
 
 // Owner map of the selection. Few triangles: row bands, so that a large triangle's box is shared among the waves of many blocks; many: one band, a triangle per lane.
-int raster(pt_scene *sc, const BakeAtlas &a, const uint32_t *d_selected, uint32_t n_selected, uint32_t *d_owner) {
+int raster(pt_scene *sc, const pt_scene *of, const BakeAtlas &a, const uint32_t *d_selected, uint32_t n_selected, uint32_t *d_owner) {
     HIP_TRY(hipMemsetAsync(d_owner, 0xff, (size_t)a.n_texels * 4, sc->stream));
     // (a two-triangle quad over a 4096^2 atlas: one thread per triangle 3806 ms, one wave sharing each box 107.9 ms, bands of 64 rows 1.71 ms, of 16 rows 0.44 ms, of 8
     // rows 0.24 ms; 4.3 M sub-texel triangles on 2048^2 in one band: 0.15 ms -- profiles/r6/NOTES.md)
@@ -141,7 +156,7 @@ int raster(pt_scene *sc, const BakeAtlas &a, const uint32_t *d_selected, uint32_
     const uint32_t bands = (a.height + band_rows - 1) / band_rows;
     const uint32_t blocks = std::max(1u, std::min<uint32_t>((n_selected + 255) / 256, (uint32_t)g_num_cus * 8u));
     sc->begin("bake_raster", n_selected);
-    launch(sc, "ptbake::k_bake_raster", k_bake_raster, dim3(blocks, bands), dim3(256), sc->ds, a, d_selected, n_selected, band_rows, d_owner);
+    launch(sc, "ptbake::k_bake_raster", k_bake_raster, dim3(blocks, bands), dim3(256), of->ds, a, d_selected, n_selected, band_rows, d_owner);
     sc->end();
     HIP_TRY(hipGetLastError());
     return PT_OK;
@@ -173,6 +188,86 @@ int end_call(pt_scene *sc) {
     sc->resolve_timings();
     read_counters(sc);
     return PT_OK;
+}
+
+// ---- the transfer bake: `target` is the scene whose atlas is filled and is only read, `source` the scene the rays see -- every launch runs on its stream, under its
+// statistics and counters
+int check_transfer(const PtBakeTransferParams *tp) {
+    if (int st = check_atlas(tp->width, tp->height)) return st;
+    if (!(tp->front >= 0.0f && tp->back >= 0.0f && std::isfinite(tp->front) && std::isfinite(tp->back) && tp->front + tp->back > 0.0f))
+        return fail(PT_ERR_INVALID_ARG, "bake transfer: front and back must be >= 0 and finite, front + back > 0");
+    return PT_OK;
+}
+// The AO at the source hit as a bake's parameters. Without ao_w no sample number is drawn: spp and nsamples are not read (and not checked)
+PtBakeParams ao_params(const PtBakeTransferParams *tp, bool want_ao) {
+    PtBakeParams bp{};
+    bp.width = tp->width; bp.height = tp->height; bp.spp = want_ao ? tp->spp : 1u; bp.nsamples = want_ao ? tp->nsamples : 1u; bp.cos_sample = tp->cos_sample;
+    bp.max_distance = want_ao ? tp->max_distance : INFINITY; bp.sampler_type = want_ao ? tp->sampler_type : (uint32_t)PT_SAMPLER_SOBOL; bp.spp_per_pass = tp->spp_per_pass; bp.profile = tp->profile;
+    return bp;
+}
+int same_device(pt_scene *target, pt_scene *source) {
+    if (source->device != g_device) { if (int st = bind_device(source->device)) return st; }
+    if (target->device != source->device) return fail(PT_ERR_INVALID_ARG, "bake transfer: the target scene lives on device " + std::to_string(target->device) + ", the source scene on device " + std::to_string(source->device));
+    return PT_OK;
+}
+
+// Steps 1 to 4 of the contract over the whole atlas: the projection rays of the owned texels through the source scene, in slices of whole tiles sized by the pass budget
+// (per slot the ray id, the ray record, the hit quad and t: a 2^28-texel atlas does not hold them all at once), and what each hit leaves in the planes
+int project(pt_scene *target, pt_scene *source, const PtBakeTransferParams *tp, const BakeAtlas &a, const uint32_t *d_owner, const TransferOut &out) {
+    DevTmp tmp;   // (the slices' records: freed before the AO passes allocate theirs)
+    uint8_t *d_top = nullptr;
+    SIDE_ALLOC(tmp, d_top, source->ds.n_prims, "bake transfer marks");
+    HIP_TRY(hipMemsetAsync(d_top, 0, source->ds.n_prims, source->stream));
+    source->begin("bake_select", source->ordered.size());
+    launch_top(source, source, d_top);
+    source->end();
+    const uint32_t n_tiles = a.slots / 64u;
+    const uint32_t tiles = choose_pass_size(source, 64u, n_tiles, 1, false, PassBudget{4 + 32 + 16 + 4, 0.5, kAOMaxRays});
+    const uint32_t cap = tiles * 64u;
+    float4 *d_ray = nullptr, *d_hit = nullptr; float *d_t = nullptr; uint32_t *d_base = nullptr, *d_count = nullptr;
+    SIDE_ALLOC(tmp, d_ray, (size_t)cap * 32, "bake transfer rays"); SIDE_ALLOC(tmp, d_hit, (size_t)cap * 16, "bake transfer rays"); SIDE_ALLOC(tmp, d_t, (size_t)cap * 4, "bake transfer rays");
+    SIDE_ALLOC(tmp, d_base, (size_t)cap * 4, "bake transfer rays"); SIDE_ALLOC(tmp, d_count, 4, "bake transfer rays");
+    const float t_max = tp->front + tp->back;
+    for (uint32_t slot0 = 0; slot0 < a.slots; slot0 += cap) {
+        const uint32_t n_slots = std::min(cap, a.slots - slot0);
+        HIP_TRY(hipMemsetAsync(d_count, 0, 4, source->stream));
+        HIP_TRY(hipMemsetAsync(source->qc->head, 0, sizeof source->qc->head, source->stream));
+        source->begin("bake_project", n_slots);
+        launch(source, "ptbake::k_bake_project", k_bake_project, blocks_for(n_slots, 16u), dim3(256), target->ds, a, d_owner, slot0, n_slots, tp->front, t_max, d_ray, d_base, d_count);
+        source->end();
+        HIP_TRY(hipGetLastError());
+        TraceJob tj = trace_job(source, 0);   // ray ids, no queue
+        tj.sub[0] = trace_sub(nullptr, d_count, (const float *)d_ray, 8, t_max, 0);
+        tj.sub[0].per_ray_tmax = 1; tj.sub[0].out_hit = d_hit; tj.sub[0].out_hit_stride = 1; tj.sub[0].out_t = d_t; tj.sub[0].out_t_stride = 1;
+        if (int st = traced(source, "extend", 0, tj, n_slots)) return st;   // (an upper bound: the launch reads the count of rays spawned)
+        source->begin("bake_transfer_points", n_slots);
+        launch(source, "ptbake::k_bake_transfer_points", k_bake_transfer_points, dim3((n_slots + 255) / 256), dim3(256), target->ds, source->ds, a, d_owner, (const uint8_t *)d_top, slot0, n_slots,
+               (const uint32_t *)d_base, (const float4 *)d_hit, (const float *)d_t, tp->front, out);
+        source->end();
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(source->stream));   // (the records are freed on return)
+    return PT_OK;
+}
+
+// The AO rays of one pass from the detail hits (bake_pass with the source hits in the owners' place)
+int transfer_pass(pt_scene *sc, const Geometry &g, const PtBakeParams *bp, uint32_t s_begin, uint32_t s_count, const uint32_t *d_detail, const float4 *d_rec, float4 *d_ao, const AORayBuffers &b) {
+    const uint32_t items = g.atlas.slots * s_count;
+    const dim3 blocks = blocks_for(items, 16u);
+    auto spawn = [&](const TransferJob &job) {
+        sc->begin("bake_transfer_rays", (uint64_t)items * job.kn);
+        launch(sc, "ptbake::k_bake_transfer_rays", k_bake_transfer_rays, blocks, dim3(256), sc->ds, g.rc, g_tabs, g.atlas, job);
+        sc->end();
+    };
+    auto accum = [&](const TransferJob &job) {
+        sc->begin("bake_accum", items);
+        launch(sc, "ptbake::k_bake_accum", k_bake_accum, texel_grid(g.atlas), dim3(256), g.atlas, static_cast<const BakeJob &>(job));
+        sc->end();
+    };
+    TransferJob job{};
+    job.nsamples = bp->nsamples; job.cos_sample = bp->cos_sample ? 1u : 0u;
+    job.s_begin = s_begin; job.s_count = s_count; job.owner = d_detail; job.ao_w = d_ao; job.rec = d_rec;
+    return ao_chunks<TransferJob>(sc, job, g.K, items, bp->max_distance, b, spawn, accum);   // (t_max = max_distance)
 }
 
 }  // namespace
@@ -209,11 +304,11 @@ __attribute__((visibility("default"))) int pt_bake_render_samples(pt_scene *sc, 
     const size_t n = a.n_texels;
     DevTmp tmp;   // (freed when the call returns, however it ends: a bake leaves the device's free memory as it found it, apart from the scene's workspace)
     uint32_t *d_selected = nullptr, n_selected = 0;
-    if (int st = upload_selection(sc, prim_select, n_prims, tmp, d_selected, n_selected)) return st;
+    if (int st = upload_selection(sc, sc, prim_select, n_prims, tmp, d_selected, n_selected)) return st;
     const bool dev = buffers_are_device != 0;
     uint32_t *d_owner = dev ? buffers->owner : nullptr;
     if (!d_owner) SIDE_ALLOC(tmp, d_owner, n * 4, "bake owner map");
-    if (int st = raster(sc, a, d_selected, n_selected, d_owner)) return st;
+    if (int st = raster(sc, sc, a, d_selected, n_selected, d_owner)) return st;
     float *d_pos = dev ? buffers->position : nullptr, *d_nrm = dev ? buffers->normal : nullptr;
     if (buffers->position || buffers->normal) {
         if (buffers->position && !d_pos) SIDE_ALLOC(tmp, d_pos, n * 12, "bake position plane");
@@ -325,9 +420,9 @@ __attribute__((visibility("default"))) int pt_bake_rays(pt_scene *sc, const PtBa
     if (int st = begin_call(sc, false)) return st;
     DevTmp tmp;
     uint32_t *d_selected = nullptr, n_selected = 0, *d_owner = nullptr, *d_in = nullptr; float *d_out = nullptr; uint8_t *d_found = nullptr;
-    if (int st = upload_selection(sc, prim_select, n_prims, tmp, d_selected, n_selected)) return st;
+    if (int st = upload_selection(sc, sc, prim_select, n_prims, tmp, d_selected, n_selected)) return st;
     SIDE_ALLOC(tmp, d_owner, (size_t)g.atlas.n_texels * 4, "bake owner map");
-    if (int st = raster(sc, g.atlas, d_selected, n_selected, d_owner)) return st;
+    if (int st = raster(sc, sc, g.atlas, d_selected, n_selected, d_owner)) return st;
     SIDE_ALLOC(tmp, d_in, (size_t)n * 12, "bake rays"); SIDE_ALLOC(tmp, d_out, (size_t)n * 28, "bake rays"); SIDE_ALLOC(tmp, d_found, n, "bake rays");
     HIP_TRY(hipMemcpyAsync(d_in, texel, (size_t)n * 4, hipMemcpyHostToDevice, sc->stream));
     HIP_TRY(hipMemcpyAsync(d_in + n, sample, (size_t)n * 4, hipMemcpyHostToDevice, sc->stream));
@@ -343,6 +438,136 @@ __attribute__((visibility("default"))) int pt_bake_rays(pt_scene *sc, const PtBa
     HIP_TRY(hipMemcpy(out_d, d_out + 3 * (size_t)n, (size_t)n * 12, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(out_w, d_out + 6 * (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(found, d_found, n, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+__attribute__((visibility("default"))) int pt_bake_transfer_pass_size(pt_scene *target, pt_scene *source, const PtBakeTransferParams *tp, uint32_t *spp_per_pass) {
+    if (!target || !source || !tp || !spp_per_pass) return fail(PT_ERR_INVALID_ARG, "null argument");
+    if (int st = check_transfer(tp)) return st;
+    const PtBakeParams bp = ao_params(tp, true);
+    if (int st = check_params(&bp)) return st;
+    if (int st = same_device(target, source)) return st;
+    Geometry g;
+    if (int st = bake_geometry(source, &bp, bp.spp, g)) return st;
+    *spp_per_pass = g.S;
+    return PT_OK;
+}
+
+__attribute__((visibility("default"))) int pt_bake_transfer(pt_scene *target, pt_scene *source, const PtBakeTransferParams *tp, const uint8_t *prim_select, uint32_t n_prims,
+                                                            const PtBakeTransferBuffers *buffers, int buffers_are_device) {
+    if (!target || !source || !tp || !prim_select || !buffers) return fail(PT_ERR_INVALID_ARG, "null argument");
+    return pt_bake_transfer_samples(target, source, tp, prim_select, n_prims, 0, tp->spp, buffers, buffers_are_device);
+}
+
+__attribute__((visibility("default"))) int pt_bake_transfer_samples(pt_scene *target, pt_scene *source, const PtBakeTransferParams *tp, const uint8_t *prim_select, uint32_t n_prims, uint32_t first,
+                                                                    uint32_t n_samples, const PtBakeTransferBuffers *buffers, int buffers_are_device) {
+    if (!target || !source || !tp || !prim_select || !buffers) return fail(PT_ERR_INVALID_ARG, "null argument");
+    if (int st = check_transfer(tp)) return st;
+    const PtBakeTransferBuffers &B = *buffers;
+    if (!B.owner && !B.hit_prim && !B.height && !B.src_position && !B.src_normal && !B.tangent_normal && !B.ao_w) return fail(PT_ERR_INVALID_ARG, "bake transfer: all seven planes are NULL");
+    const bool want_ao = B.ao_w != nullptr;
+    const PtBakeParams bp = ao_params(tp, want_ao);
+    if (want_ao) {   // (without ao_w the sample range is not read either)
+        if (int st = check_params(&bp)) return st;
+        if (int st = check_range(&bp, first, n_samples)) return st;
+    } else { first = 0; n_samples = 1; }
+    if (int st = check_selection(prim_select, n_prims)) return st;
+    if (int st = check_prim_count(target, n_prims)) return st;   // (all of the above before the device is touched)
+    if (int st = same_device(target, source)) return st;
+    Geometry g;
+    if (int st = bake_geometry(source, &bp, n_samples, g)) return st;
+    if (int st = begin_call(source, tp->profile != 0)) return st;
+    const BakeAtlas &a = g.atlas;
+    const size_t n = a.n_texels;
+    DevTmp tmp;   // (freed when the call returns, however it ends)
+    uint32_t *d_selected = nullptr, n_selected = 0;
+    if (int st = upload_selection(source, target, prim_select, n_prims, tmp, d_selected, n_selected)) return st;
+    const bool dev = buffers_are_device != 0;
+    uint32_t *d_owner = dev ? B.owner : nullptr;
+    if (!d_owner) SIDE_ALLOC(tmp, d_owner, n * 4, "bake owner map");
+    if (int st = raster(source, target, a, d_selected, n_selected, d_owner)) return st;
+    TransferOut out{};
+    if (dev) { out.hit_prim = B.hit_prim; out.height = B.height; out.src_position = B.src_position; out.src_normal = B.src_normal; out.tangent_normal = B.tangent_normal; }
+    else {
+        if (B.hit_prim) SIDE_ALLOC(tmp, out.hit_prim, n * 4, "bake transfer planes");
+        if (B.height) SIDE_ALLOC(tmp, out.height, n * 4, "bake transfer planes");
+        if (B.src_position) SIDE_ALLOC(tmp, out.src_position, n * 12, "bake transfer planes");
+        if (B.src_normal) SIDE_ALLOC(tmp, out.src_normal, n * 12, "bake transfer planes");
+        if (B.tangent_normal) SIDE_ALLOC(tmp, out.tangent_normal, n * 12, "bake transfer planes");
+    }
+    if (want_ao) { SIDE_ALLOC(tmp, out.detail, n * 4, "bake transfer hits"); SIDE_ALLOC(tmp, out.rec, n * 16, "bake transfer hits"); }
+    if (out.hit_prim || out.height || out.src_position || out.src_normal || out.tangent_normal || want_ao)
+        if (int st = project(target, source, tp, a, d_owner, out)) return st;
+    float4 *d_ao = dev ? reinterpret_cast<float4 *>(B.ao_w) : nullptr;
+    if (want_ao) {
+        if (!d_ao) {
+            SIDE_ALLOC(tmp, d_ao, n * 16, "bake ao plane");
+            HIP_TRY(hipMemcpyAsync(d_ao, B.ao_w, n * 16, hipMemcpyHostToDevice, source->stream));   // (added to)
+        }
+        AORayBuffers b;
+        const size_t items = (size_t)a.slots * g.S;
+        if (int st = b.alloc(items, items * g.K, "bake rays")) return st;
+        for (uint32_t s0 = first, end = first + n_samples; s0 < end; s0 += g.S)
+            if (int st = transfer_pass(source, g, &bp, s0, std::min(g.S, end - s0), out.detail, out.rec, d_ao, b)) return st;
+    }
+    if (int st = end_call(source)) return st;
+    if (!dev) {   // (host planes are written once everything has succeeded)
+        if (B.owner) HIP_TRY(hipMemcpy(B.owner, d_owner, n * 4, hipMemcpyDeviceToHost));
+        if (B.hit_prim) HIP_TRY(hipMemcpy(B.hit_prim, out.hit_prim, n * 4, hipMemcpyDeviceToHost));
+        if (B.height) HIP_TRY(hipMemcpy(B.height, out.height, n * 4, hipMemcpyDeviceToHost));
+        if (B.src_position) HIP_TRY(hipMemcpy(B.src_position, out.src_position, n * 12, hipMemcpyDeviceToHost));
+        if (B.src_normal) HIP_TRY(hipMemcpy(B.src_normal, out.src_normal, n * 12, hipMemcpyDeviceToHost));
+        if (B.tangent_normal) HIP_TRY(hipMemcpy(B.tangent_normal, out.tangent_normal, n * 12, hipMemcpyDeviceToHost));
+        if (B.ao_w) HIP_TRY(hipMemcpy(B.ao_w, d_ao, n * 16, hipMemcpyDeviceToHost));
+    }
+    return PT_OK;
+}
+
+__attribute__((visibility("default"))) int pt_bake_transfer_rays(pt_scene *target, pt_scene *source, const PtBakeTransferParams *tp, const uint8_t *prim_select, uint32_t n_prims, uint32_t n,
+                                                                 const uint32_t *texel, const uint32_t *sample, const uint32_t *element, float *proj_o, float *proj_d, float *proj_tmax, float *ao_o,
+                                                                 float *ao_d, float *ao_w, uint8_t *found) {
+    if (!target || !source || !tp || !prim_select || !texel || !sample || !element || !proj_o || !proj_d || !proj_tmax || !ao_o || !ao_d || !ao_w || !found) return fail(PT_ERR_INVALID_ARG, "null argument");
+    if (int st = check_transfer(tp)) return st;
+    PtBakeParams bp = ao_params(tp, true);
+    if (int st = check_params(&bp)) return st;
+    if (int st = check_selection(prim_select, n_prims)) return st;
+    for (uint32_t i = 0; i < n; ++i)
+        if (sample[i] >= bp.spp || element[i] >= bp.nsamples) return fail(PT_ERR_INVALID_ARG, "bake: ray " + std::to_string(i) + " names a sample or element outside the job");
+    if (int st = check_prim_count(target, n_prims)) return st;
+    if (int st = same_device(target, source)) return st;
+    Geometry g;
+    bp.spp_per_pass = 1;
+    if (int st = bake_geometry(source, &bp, bp.spp, g)) return st;
+    if (n == 0) return PT_OK;
+    if (int st = begin_call(source, false)) return st;
+    const BakeAtlas &a = g.atlas;
+    DevTmp tmp;
+    uint32_t *d_selected = nullptr, n_selected = 0, *d_owner = nullptr, *d_in = nullptr; float *d_out = nullptr; uint8_t *d_found = nullptr;
+    if (int st = upload_selection(source, target, prim_select, n_prims, tmp, d_selected, n_selected)) return st;
+    SIDE_ALLOC(tmp, d_owner, (size_t)a.n_texels * 4, "bake owner map");
+    if (int st = raster(source, target, a, d_selected, n_selected, d_owner)) return st;
+    TransferOut out{};
+    SIDE_ALLOC(tmp, out.detail, (size_t)a.n_texels * 4, "bake transfer hits"); SIDE_ALLOC(tmp, out.rec, (size_t)a.n_texels * 16, "bake transfer hits");
+    if (int st = project(target, source, tp, a, d_owner, out)) return st;
+    SIDE_ALLOC(tmp, d_in, (size_t)n * 12, "bake rays"); SIDE_ALLOC(tmp, d_out, (size_t)n * 56, "bake rays"); SIDE_ALLOC(tmp, d_found, n, "bake rays");
+    HIP_TRY(hipMemcpyAsync(d_in, texel, (size_t)n * 4, hipMemcpyHostToDevice, source->stream));
+    HIP_TRY(hipMemcpyAsync(d_in + n, sample, (size_t)n * 4, hipMemcpyHostToDevice, source->stream));
+    HIP_TRY(hipMemcpyAsync(d_in + 2 * (size_t)n, element, (size_t)n * 4, hipMemcpyHostToDevice, source->stream));
+    source->begin("bake_probe", n);
+    launch(source, "ptbake::k_bake_transfer_probe", k_bake_transfer_probe, dim3((n + 255) / 256), dim3(256), target->ds, source->ds, g.rc, g_tabs, a, (const uint32_t *)d_owner,
+           (const uint32_t *)out.detail, (const float4 *)out.rec, tp->front, tp->front + tp->back, bp.nsamples, bp.cos_sample ? 1u : 0u, n, (const uint32_t *)d_in, (const uint32_t *)(d_in + n),
+           (const uint32_t *)(d_in + 2 * (size_t)n), d_out, d_found);
+    source->end();
+    HIP_TRY(hipGetLastError());
+    if (int st = end_call(source)) return st;
+    std::vector<float> rows((size_t)n * 14);
+    HIP_TRY(hipMemcpy(rows.data(), d_out, rows.size() * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(found, d_found, n, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) {
+        const float *r = rows.data() + 14 * i;
+        for (int k = 0; k < 3; ++k) { proj_o[3 * i + k] = r[k]; proj_d[3 * i + k] = r[3 + k]; ao_o[3 * i + k] = r[7 + k]; ao_d[3 * i + k] = r[10 + k]; }
+        proj_tmax[i] = r[6]; ao_w[i] = r[13];
+    }
     return PT_OK;
 }
 

@@ -140,6 +140,14 @@ def resolve_bake(ao_w, spp, lib=None):
     return ao, bent
 
 
+def encode_normal_map(tangent_normal, covered):
+    """The tangent_normal plane of Scene.bake_transfer, (H, W, 3), as a normal-map image: n * 0.5 + 0.5 where `covered` ((H, W) bool: the texels with a detail hit, or
+    those a dilation filled), the flat normal (0.5, 0.5, 1) elsewhere. float32."""
+    n = np.asarray(tangent_normal, dtype=np.float32)
+    flat = np.array([0.5, 0.5, 1.0], np.float32)
+    return np.where(np.asarray(covered, bool)[..., None], n * np.float32(0.5) + np.float32(0.5), flat).astype(np.float32)
+
+
 def murmur3_32(data, seed=0):
     """MurmurHash3_x86_32 of a bytes object."""
     c1, c2, M = 0xcc9e2d51, 0x1b873593, 0xffffffff
@@ -575,6 +583,48 @@ class Scene(Handle):
         self._call("bake_rays", self.h, C.byref(bp), sel.ctypes.data_as(A.u8p), len(sel), n, texel.ctypes.data_as(A.u32p), sample.ctypes.data_as(A.u32p),
                    element.ctypes.data_as(A.u32p), _fptr(o), _fptr(d), _fptr(w), found.ctypes.data_as(A.u8p), lib=self.L.bake)
         return o, d, w, found
+
+    def bake_transfer_params(self, width, height, front, back, spp=1, nsamples=64, cos_sample=True, max_distance=float("inf"), sampler="sobol", spp_per_pass=0, profile=False):
+        return BAKE.PtBakeTransferParams(width, height, front, back, spp, nsamples, 1 if cos_sample else 0, max_distance, {"sobol": A.PT_SAMPLER_SOBOL, "halton": A.PT_SAMPLER_HALTON}[sampler],
+                                         spp_per_pass, 1 if profile else 0)
+
+    def bake_transfer(self, source, select, width, height, front, back, spp=1, nsamples=64, cos_sample=True, max_distance=float("inf"), sampler="sobol", spp_per_pass=0, profile=False,
+                      planes=BAKE.TRANSFER_PLANES, samples=None, sums=None, device_ptrs=None):
+        """pt_bake_transfer: the Scene `source` projected onto the width x height UV atlas of this scene's primitives `select` names (bake_select), by rays from `front`
+        above this scene's surface to `back` below it (`samples` = (first, n): pt_bake_transfer_samples). A dict of the wanted planes -- "owner" and "hit_prim" (H, W)
+        uint32, "height" (H, W), "src_position", "src_normal" and "tangent_normal" (H, W, 3), "ao_w" (H, W, 4) = the AO sums at the source hit (resolve_bake) --, ADDED
+        to the array of `sums` as Scene.bake does. Counters and kernel statistics of the call are `source`'s. `device_ptrs` = {plane: device pointer}: returns None."""
+        tp = self.bake_transfer_params(width, height, front, back, spp, nsamples, cos_sample, max_distance, sampler, spp_per_pass, profile)
+        sel = self.bake_select(select)
+        args = [self.h, source.h, C.byref(tp), sel.ctypes.data_as(A.u8p), len(sel)] + ([] if samples is None else list(samples))
+        name = "bake_transfer" if samples is None else "bake_transfer_samples"
+        if device_ptrs is not None:
+            self._call(name, *args, C.byref(BAKE.transfer_buffers(device_ptrs, device=True)), 1, lib=self.L.bake); return None
+        if sums is None:
+            sums = {}
+        for k in planes:
+            if k not in sums:
+                sums[k] = np.zeros((height, width) + ((BAKE.TRANSFER_CHANNELS[k],) if BAKE.TRANSFER_CHANNELS[k] > 1 else ()), dtype=BAKE.TRANSFER_DTYPES[k])
+        self._call(name, *args, C.byref(BAKE.transfer_buffers({k: sums[k] for k in planes})), 0, lib=self.L.bake)
+        return sums
+
+    def bake_transfer_pass_size(self, source, width, height, front, back, spp, nsamples=64, sampler="sobol", spp_per_pass=0):
+        """AO samples per texel per pass pt_bake_transfer would use now."""
+        tp = self.bake_transfer_params(width, height, front, back, spp, nsamples, sampler=sampler, spp_per_pass=spp_per_pass)
+        return self._pass_size("bake_transfer_pass_size", source.h, C.byref(tp), lib=self.L.bake)
+
+    def bake_transfer_rays(self, source, select, width, height, front, back, spp, texel, sample, element, nsamples=64, cos_sample=True, max_distance=float("inf"), sampler="sobol"):
+        """pt_bake_transfer_rays: dict(o, d, t_max: the projection rays of the texels; ao_o, ao_d, ao_w: the AO rays (sample, element) from their detail hits; found (n,)
+        uint8: bit 0 the texel has an owner, bit 1 a detail hit)."""
+        tp = self.bake_transfer_params(width, height, front, back, spp, nsamples, cos_sample, max_distance, sampler)
+        sel = self.bake_select(select)
+        texel, sample, element = (np.ascontiguousarray(v, dtype=np.uint32) for v in (texel, sample, element))
+        n = len(texel)
+        r = dict(o=np.zeros((n, 3), np.float32), d=np.zeros((n, 3), np.float32), t_max=np.zeros(n, np.float32), ao_o=np.zeros((n, 3), np.float32), ao_d=np.zeros((n, 3), np.float32),
+                 ao_w=np.zeros(n, np.float32), found=np.zeros(n, np.uint8))
+        self._call("bake_transfer_rays", self.h, source.h, C.byref(tp), sel.ctypes.data_as(A.u8p), len(sel), n, texel.ctypes.data_as(A.u32p), sample.ctypes.data_as(A.u32p),
+                   element.ctypes.data_as(A.u32p), *[_fptr(r[k]) for k in ("o", "d", "t_max", "ao_o", "ao_d", "ao_w")], r["found"].ctypes.data_as(A.u8p), lib=self.L.bake)
+        return r
 
     def ao_params(self):
         """The scene's PtAOParams (SceneBuilder.integ / the front end's "ambientocclusion" parameters)."""
