@@ -6,7 +6,8 @@
  * the front of the pipe is its own -- which triangle owns which texel (k_bake_raster), the surface point there (k_bake_points), the
  * AO rays from it (k_bake_rays), their any-hit walk (libmi355pt's k_trace, launch kind "shadow") and the sums (k_bake_accum).
  * pt_bake_transfer (below, "Transfer") fills the atlas of one scene's mesh with what rays from its surface hit in ANOTHER scene: the
- * height, position, world- and tangent-space normal of a detailed mesh, and the AO there.
+ * height, position, world- and tangent-space normal of a detailed mesh, and the AO there. pt_bake_light (below, "Lightmap") bakes the
+ * scene's lights into the atlas: the irradiance every texel receives directly from them.
  *
  * ---- the contract -----------------------------------------------------------------------------------------------------------------
  *
@@ -201,6 +202,82 @@ int pt_bake_transfer_pass_size(pt_scene *target, pt_scene *source, const PtBakeT
 int pt_bake_transfer_rays(pt_scene *target, pt_scene *source, const PtBakeTransferParams *params, const uint8_t *prim_select, uint32_t n_prims, uint32_t n,
                           const uint32_t *texel, const uint32_t *sample, const uint32_t *element, float *proj_o, float *proj_d, float *proj_tmax,
                           float *ao_o, float *ao_d, float *ao_w, uint8_t *found);
+
+/* ---- Lightmap: the scene's lights baked into the atlas -------------------------------------------------------------------------------
+ *
+ * The irradiance every owned texel receives DIRECTLY from the scene's lights, on the side its normal faces: the direct-lighting estimate
+ * of integrators/directlighting.rs with the surface's BSDF left out (a lightmap is multiplied with the albedo where it is used), no
+ * indirect light, no emission of the baked surface itself. Every light type the renderer knows is served, by the device function the
+ * render samples its lights with. Every operation float32, unfused, in this order:
+ *
+ * 1. Texel, owner, surface point. The atlas bake's, unchanged: texel centres, ownership with the texel box, the owner's interaction si at
+ *    the centre. The reference point of the light samples is ref = {si.p, si.p_error, si.n}; ns = normalize(si.sh_n).
+ * 2. Which light. sel[0 .. n_sel) are the selected lights in ascending index (light_select; NULL: all of the scene's). Sample number
+ *    j = s * nsamples + k of a texel -- element k of sample s -- samples light sel[j mod n_sel], in 64-bit arithmetic. spp * nsamples
+ *    must be a multiple of n_sel, so that every light gets exactly spp * nsamples / n_sel samples per texel. nsamples == n_sel is
+ *    directlighting.rs's "all lights, one sample each"; a smaller nsamples serves scenes with many emissive triangles. The light of a
+ *    sample does NOT depend on the texel: the 64 texels a wave works on sample the same light (see k_bake_light_rays).
+ * 3. Light sample. u = the 2-D array value of sample number j of pixel (x, y), dimensions 5 and 6, of a sampler set up for sample bounds
+ *    [0, width) x [0, height), as under "AO rays". (Li, wi, pdf, p1) = Light::sample_li(ref, u) (lights/point.rs, spot.rs, distant.rs,
+ *    diffuse.rs with Triangle / Sphere / Disk::sample, infinite.rs), p1 being the far end of its visibility segment: the light's
+ *    position, the sampled point of an area light with its error bound and normal, or ref.p + wi * (2 * world radius).
+ * 4. Contribution. A sample contributes only if pdf > 0, Li is not black (all three channels 0), c = dot(wi, ns) > 0 and
+ *    dot(wi, si.n) > 0 (a NaN fails each): a lightmap is one-sided, light from behind the surface adds nothing. Then
+ *        w = (c * ((float)n_sel / (float)nsamples)) / pdf,      E = Li * w   per channel.
+ * 5. Shadow ray. VisibilityTester::unoccluded's ray: Interaction::spawn_ray_to(ref, p1) (interaction.rs:45-52) --
+ *        o = offset_ray_origin(ref.p, ref.p_error, ref.n, p1.p - ref.p),  d = offset_ray_origin(p1.p, p1.p_error, p1.n, o - p1.p) - o
+ *    -- an any-hit query through the whole scene (spheres, instances, alpha masks, the baked mesh itself) with t_max = 1 - 0.0001f: the
+ *    render's shadow ray. A sample that does not contribute spawns no ray. Media are NOT consulted: there is no transmittance along the
+ *    segment, as under Integrator "path" -- a scene's participating media do not dim its lightmap.
+ * 6. Sums. light_w[texel] += (E.r, E.g, E.b, 1.0f) for every unoccluded contributing sample, in ascending (s, k), onto what the buffer
+ *    holds. Sample ranges baked in ascending order, any spp_per_pass, repeated calls and device or host buffers leave the same bytes.
+ * 7. Resolve (pt_bake_light_resolve). irradiance = rgb / (float)spp; reached = w / ((float)spp * (float)nsamples), the fraction of
+ *    the light samples that arrived; both 0 where nothing was added (all four sums 0).
+ *
+ * spp * nsamples is limited as under "AO rays". PtCounters.shadow_tests = the shadow rays traced = the contributing samples. Launch
+ * kinds: "bake_select", "bake_raster", "bake_points", "bake_light_rays", "shadow", "bake_light_accum" ("bake_probe" for
+ * pt_bake_light_rays). The samples of a pass are taken in chunks of at most 64 elements per texel sample; with nsamples > 64 a pass is one
+ * sample, as for the AO bake. */
+typedef struct PtBakeLightParams {
+    uint32_t width, height;      /* the atlas, texels; width * height <= 2^28                         */
+    uint32_t spp;                /* the job's samples per texel, > 0                                  */
+    uint32_t nsamples;           /* light samples per sample, > 0; spp * nsamples a multiple of n_sel */
+    uint32_t sampler_type;       /* PtSamplerType                                                     */
+    uint32_t spp_per_pass;       /* 0: the library chooses from the free memory                       */
+    uint32_t profile;            /* != 0: time every launch kind (pt_get_kernel_stats)                */
+} PtBakeLightParams;
+
+typedef struct PtBakeLightBuffers {   /* width * height entries, row-major; NULL = not wanted */
+    uint32_t *owner;             /* primitive that owns the texel, PT_NONE for none -- written        */
+    float *position;             /* 3 per texel: p; 0 where the texel has no owner -- written         */
+    float *normal;               /* 3 per texel: the normalised shading normal; 0 likewise -- written */
+    float *light_w;              /* 4 per texel: sum of E.rgb, count of arrived samples -- ADDED to   */
+} PtBakeLightBuffers;
+
+/* Bakes params->spp samples of params->nsamples light samples each per texel of the primitives selected by prim_select (pt_bake_render's)
+ * under the lights selected by light_select -- HOST memory, n_lights bytes in PtSceneDesc's light order, non-zero = the light is baked;
+ * NULL = all n_lights lights: static lights only, or one map per light. Without light_w no ray is traced.
+ * Errors. PT_ERR_INVALID_ARG, before the device is touched and in this order, for a NULL scene, params, prim_select or buffers; width or
+ * height 0 or more than 2^28 texels; spp or nsamples 0; an unknown sampler_type; all four planes NULL; a bad sample range; no primitive
+ * selected; no light selected (n_lights == 0 included); spp * nsamples no multiple of the number of selected lights (the message names both
+ * numbers); n_prims different from the scene's primitive count; n_lights different from the scene's light count. Then as pt_bake_render:
+ * the sampler's limits, PT_ERR_UNSUPPORTED for the selection. Host planes are written only after everything has succeeded. */
+int pt_bake_light(pt_scene *scene, const PtBakeLightParams *params, const uint8_t *prim_select, uint32_t n_prims, const uint8_t *light_select, uint32_t n_lights,
+                  const PtBakeLightBuffers *buffers, int buffers_are_device);
+/* Samples [first_sample, first_sample + n_samples) of every texel; params->spp stays the job's sample count. pt_bake_light is the call (0, spp). */
+int pt_bake_light_samples(pt_scene *scene, const PtBakeLightParams *params, const uint8_t *prim_select, uint32_t n_prims, const uint8_t *light_select, uint32_t n_lights,
+                          uint32_t first_sample, uint32_t n_samples, const PtBakeLightBuffers *buffers, int buffers_are_device);
+/* Samples per texel per pass pt_bake_light would use: pt_bake_pass_size's rule with 20 more bytes per ray (what it adds, its id). */
+int pt_bake_light_pass_size(pt_scene *scene, const PtBakeLightParams *params, const uint8_t *light_select, uint32_t n_lights, uint32_t *spp_per_pass);
+/* Host arithmetic: step 7. A NULL output is skipped. PT_ERR_INVALID_ARG for a NULL light_w, both outputs NULL, spp or nsamples 0. */
+int pt_bake_light_resolve(const float *light_w, uint32_t n_texels, uint32_t spp, uint32_t nsamples, float *irradiance_rgb, float *reached);
+/* Parity entry, in the style of pt_bake_rays: for n triples (texel index, sample number s, element k) -- host arrays -- the light that
+ * sample is taken on, Light::sample_li's wi, pdf and Li, E and the shadow ray (out_o, out_d), by the device function the bake uses.
+ * found[i]: bit 0 = the texel has an owner (else everything but out_light is zeros), bit 1 = the sample contributes (else E and the ray are
+ * zeros). The parameters, the selections and their checks are pt_bake_light's (spp_per_pass and profile are not read). */
+int pt_bake_light_rays(pt_scene *scene, const PtBakeLightParams *params, const uint8_t *prim_select, uint32_t n_prims, const uint8_t *light_select, uint32_t n_lights,
+                       uint32_t n, const uint32_t *texel, const uint32_t *sample, const uint32_t *element, uint32_t *out_light, float *out_wi, float *out_pdf,
+                       float *out_li, float *out_e, float *out_o, float *out_d, uint8_t *found);
 
 #ifdef __cplusplus
 }

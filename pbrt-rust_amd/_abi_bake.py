@@ -46,9 +46,29 @@ def transfer_buffers(planes, device=False):
     return buffers(planes, device, PtBakeTransferBuffers)
 
 
+# pt_bake_light: PtBakeLightBuffers' fields, in this order
+LIGHT_PLANES = ("owner", "position", "normal", "light_w")
+LIGHT_CHANNELS = {"owner": 1, "position": 3, "normal": 3, "light_w": 4}
+LIGHT_DTYPES = {"owner": "uint32", "position": "float32", "normal": "float32", "light_w": "float32"}
+
+
+class PtBakeLightParams(C.Structure):
+    _fields_ = [("width", u32), ("height", u32), ("spp", u32), ("nsamples", u32), ("sampler_type", u32), ("spp_per_pass", u32), ("profile", u32)]
+
+
+class PtBakeLightBuffers(C.Structure):
+    _fields_ = [("owner", u32p), ("position", fp), ("normal", fp), ("light_w", fp)]
+
+
+def light_buffers(planes, device=False):
+    """The PtBakeLightBuffers of {plane: array or device pointer}, as buffers()."""
+    return buffers(planes, device, PtBakeLightBuffers)
+
+
 # Every symbol include/mi355bake.h declares, with its signature (restype, argtypes).
 _bp, _bb = C.POINTER(PtBakeParams), C.POINTER(PtBakeBuffers)
 _tp, _tb = C.POINTER(PtBakeTransferParams), C.POINTER(PtBakeTransferBuffers)
+_lp, _lb = C.POINTER(PtBakeLightParams), C.POINTER(PtBakeLightBuffers)
 ENTRY_POINTS = {
     "pt_bake_render": (C.c_int, [VP, _bp, u8p, u32, _bb, C.c_int]),
     "pt_bake_render_samples": (C.c_int, [VP, _bp, u8p, u32, u32, u32, _bb, C.c_int]),
@@ -60,4 +80,9 @@ ENTRY_POINTS = {
     "pt_bake_transfer_samples": (C.c_int, [VP, VP, _tp, u8p, u32, u32, u32, _tb, C.c_int]),
     "pt_bake_transfer_pass_size": (C.c_int, [VP, VP, _tp, u32p]),
     "pt_bake_transfer_rays": (C.c_int, [VP, VP, _tp, u8p, u32, u32, u32p, u32p, u32p, fp, fp, fp, fp, fp, fp, u8p]),
+    "pt_bake_light": (C.c_int, [VP, _lp, u8p, u32, u8p, u32, _lb, C.c_int]),
+    "pt_bake_light_samples": (C.c_int, [VP, _lp, u8p, u32, u8p, u32, u32, u32, _lb, C.c_int]),
+    "pt_bake_light_pass_size": (C.c_int, [VP, _lp, u8p, u32, u32p]),
+    "pt_bake_light_resolve": (C.c_int, [fp, u32, u32, u32, fp, fp]),
+    "pt_bake_light_rays": (C.c_int, [VP, _lp, u8p, u32, u8p, u32, u32, u32p, u32p, u32p, u32p, fp, fp, fp, fp, fp, fp, u8p]),
 }

@@ -12,7 +12,11 @@
 //   k_bake_transfer_points  one thread per texel of the slice: the hit classified -> hit_prim, height, the three vector planes, the hit record of the AO passes
 //   k_bake_transfer_rays    k_bake_rays from the source hit (k_bake_accum adds them, with the detail-hit map in the owner map's place)
 //   k_bake_transfer_probe   pt_bake_transfer_rays: single projection and AO rays by the functions the kernels above use
-// No atomics other than the owner map's atomicMin and the per-wave ray-id reservation (wave_reserve).
+// and, for the lightmap (pt_bake_light: the scene's lights sampled from every texel; the any-hit walk of the shadow rays is libmi355pt's k_trace once more):
+//   k_bake_light_rays<SPH>   one texel sample per lane: one chunk of its light samples -> the shadow rays of those that contribute, and what each would add
+//   k_bake_light_accum       light_w += the unoccluded samples' E and 1, in element order
+//   k_bake_light_probe<SPH>  pt_bake_light_rays: single light samples by light_ray, the function k_bake_light_rays' rays come from
+// No atomics other than the owner map's atomicMin and the per-wave ray-id reservation (wave_reserve; k_bake_light_rays' own, one for several elements).
 #pragma once
 #include "../csrc/kern_decl.h"
 #include "../side/ao_rays.h"
@@ -20,6 +24,7 @@
 namespace ptbake {
 using namespace ptside;
 
+constexpr uint32_t kLightGroup = 4;                  // k_bake_light_rays: light samples of a texel sample whose rays share one ray-id reservation
 constexpr uint32_t kRasterOwnTexels = 16;            // k_bake_raster: a triangle whose texel box holds at most this many texels is walked by its own lane
 
 // `slots`: the texel samples of one sample number in the order the ray kernel walks them -- 8 x 8 texel tiles, one per wave, so that the rays of a wave start from a
@@ -420,6 +425,147 @@ __global__ __launch_bounds__(256) void k_bake_transfer_probe(DeviceScene t, Devi
     r[0] = po.x; r[1] = po.y; r[2] = po.z; r[3] = pd.x; r[4] = pd.y; r[5] = pd.z; r[6] = pt;
     r[7] = o.x; r[8] = o.y; r[9] = o.z; r[10] = wo.x; r[11] = wo.y; r[12] = wo.z; r[13] = w;
     found[i] = (uint8_t)bits;
+}
+
+// ---- the lightmap (mi355bake.h "Lightmap")
+
+// One chunk of light samples of the texel samples [s_begin, s_begin + s_count): AOChunk's ray records and flags (w is not used), and per ray what it adds when it
+// arrives. Not every sample spawns a ray: id[kk * items + item] is the ray id of element k0 + kk of the item, PT_NONE for a sample that contributes nothing.
+struct LightJob : AOChunk {
+    uint32_t s_begin, s_count;
+    const uint32_t *owner;   // [texels]
+    float4 *light_w;         // [texels]
+    const uint32_t *sel;     // [n_sel]: the selected lights, ascending
+    uint32_t n_sel;
+    float scale;             // (float)n_sel / (float)nsamples
+    uint32_t *id;            // [kn][items]
+    float4 *e;               // [rays]: {E.rgb, 1}
+};
+
+// The reference point of a texel's light samples (contract step 1) and the normalised shading normal
+PT_DEV IData light_ref(const SurfaceInteraction &si, V3 &ns) { IData ref; ref.p = si.p; ref.p_error = si.p_error; ref.n = si.n; ns = normalize(si.sh_n); return ref; }
+
+// Sample number j of texel (px, py) on light li (contract steps 3 to 5): Light::sample_li, the contribution test, E and the shadow ray. false: the sample adds
+// nothing and spawns no ray (E, o and d are zeros then).
+template <bool SPH>
+PT_DEV bool light_ray(const DeviceScene &s, const RenderConst &rc, const SobolTables &tabs, const IData &ref, V3 ns, int32_t px, int32_t py, uint64_t j, uint32_t li, float scale,
+                      V3 &wi, float &pdf, RGB &Li, RGB &E, V3 &o, V3 &d) {
+    const P2 u = ao_array_sample(rc, tabs, px, py, j);
+    wi = V3(0.0f, 0.0f, 0.0f); pdf = 0.0f;
+    IData p1;
+    Li = light_sample_li<SPH>(s, li, ref, u, wi, pdf, p1);
+    E = RGB(0.0f); o = V3(0.0f, 0.0f, 0.0f); d = V3(0.0f, 0.0f, 0.0f);
+    const float c = dot(wi, ns);
+    if (!(pdf > 0.0f) || (Li.r == 0.0f && Li.g == 0.0f && Li.b == 0.0f) || !(c > 0.0f) || !(dot(wi, ref.n) > 0.0f)) return false;
+    const float w = (c * scale) / pdf;
+    E = Li * w;
+    spawn_ray_to(ref, p1, o, d);
+    return true;
+}
+
+// Per texel sample of the pass (item = sample-in-pass * slots + slot, as k_bake_rays): this chunk's light samples. A wave is one 8 x 8 tile of ONE sample number, so the
+// sample number j of an element, and with it the light sel[j mod n_sel], is the same for all 64 lanes: the index goes through readfirstlane and the light's record and
+// PtLight are fetched by scalar loads, once per wave. One ray-id reservation per wave per kLightGroup elements, for the lanes whose samples contribute.
+template <bool SPH>
+__global__ __launch_bounds__(256) void k_bake_light_rays(DeviceScene s, RenderConst rc, SobolTables tabs, BakeAtlas a, LightJob job) {
+    const uint32_t total = a.slots * job.s_count;   // (a multiple of 64: whole waves)
+    for (uint32_t item = blockIdx.x * blockDim.x + threadIdx.x; item < total; item += gridDim.x * blockDim.x) {
+        const uint32_t texel = slot_texel(a, item % a.slots);
+        const uint32_t sl = (uint32_t)__builtin_amdgcn_readfirstlane((int)(item / a.slots));
+        const uint32_t prim = texel != PT_NONE ? job.owner[texel] : PT_NONE;
+        const bool found = prim != PT_NONE;
+        IData ref; V3 ns(0.0f, 0.0f, 0.0f);
+        ref.p = ref.p_error = ref.n = V3(0.0f, 0.0f, 0.0f);
+        if (found) {
+            SurfaceInteraction si;
+            texel_interaction(s, a, texel, prim, si);
+            ref = light_ref(si, ns);
+        }
+        const int32_t px = found ? (int32_t)(texel % a.width) : 0, py = found ? (int32_t)(texel / a.width) : 0;
+        const uint64_t j0 = ((uint64_t)job.s_begin + sl) * job.nsamples + job.k0;
+        uint32_t r = (uint32_t)(j0 % job.n_sel);
+        // kLightGroup elements at a time: their rays wait in registers for ONE reservation of the wave -- a single counter sustains ~88 returning atomics per microsecond
+        // (MI355X_MICROARCH.md), and one per element made the kernel wait for the counter (2048^2 x 16 x 3 samples: 30.3 ms; k_bake_rays, one per item, 13.2 ms)
+        for (uint32_t kk = 0; kk < job.kn; kk += kLightGroup) {
+            V3 o[kLightGroup], d[kLightGroup]; RGB E[kLightGroup];
+            unsigned long long rays[kLightGroup];   // per element: the lanes whose sample contributes
+            uint32_t n_rays = 0;
+#pragma unroll
+            for (uint32_t g = 0; g < kLightGroup; ++g) {
+                bool ray = false;
+                if (kk + g < job.kn) {
+                    const uint32_t li = (uint32_t)__builtin_amdgcn_readfirstlane((int)job.sel[r]);
+                    r = r + 1u == job.n_sel ? 0u : r + 1u;
+                    V3 wi; float pdf; RGB Li;
+                    if (found) ray = light_ray<SPH>(s, rc, tabs, ref, ns, px, py, j0 + kk + g, li, job.scale, wi, pdf, Li, E[g], o[g], d[g]);
+                }
+                rays[g] = __ballot(ray);
+                n_rays += (uint32_t)__popcll(rays[g]);
+            }
+            // ids: the group's elements one after the other, each in lane order (every lane of the wave is here: lane 0 asks)
+            uint32_t base = 0;
+            if (n_rays != 0u) {
+                if (lane_id() == 0u) base = atomicAdd(job.ray_count, n_rays);
+                base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+            }
+            const unsigned long long below = (1ull << lane_id()) - 1ull;
+#pragma unroll
+            for (uint32_t g = 0; g < kLightGroup; ++g) {
+                if (kk + g >= job.kn) break;
+                const bool ray = ((rays[g] >> lane_id()) & 1ull) != 0ull;
+                const uint32_t id = base + (uint32_t)__popcll(rays[g] & below);
+                base += (uint32_t)__popcll(rays[g]);
+                job.id[(size_t)(kk + g) * total + item] = ray ? id : PT_NONE;
+                if (!ray) continue;
+                job.ray[2 * (size_t)id] = make_float4(o[g].x, o[g].y, o[g].z, d[g].x);
+                job.ray[2 * (size_t)id + 1] = make_float4(d[g].y, d[g].z, 0.0f, 0.0f);
+                job.e[id] = make_float4(E[g].r, E[g].g, E[g].b, 1.0f);
+            }
+        }
+    }
+}
+
+// light_w += {E, 1} of the unoccluded contributing samples, in (sample, element) order: k_bake_accum's walk over the id table (a pass of more than one sample has ONE chunk)
+__global__ __launch_bounds__(256) void k_bake_light_accum(BakeAtlas a, LightJob job) {
+    const uint32_t texel = blockIdx.x * blockDim.x + threadIdx.x;
+    if (texel >= a.n_texels) return;
+    if (job.owner[texel] == PT_NONE) return;
+    const uint32_t slot = texel_slot(a, texel), total = a.slots * job.s_count;
+    float4 acc = job.light_w[texel];
+    for (uint32_t sl = 0; sl < job.s_count; ++sl) {
+        for (uint32_t kk = 0; kk < job.kn; ++kk) {
+            const uint32_t id = job.id[(size_t)kk * total + (size_t)sl * a.slots + slot];
+            if (id == PT_NONE || job.occluded[id]) continue;
+            const float4 e = job.e[id];
+            acc.x += e.x; acc.y += e.y; acc.z += e.z; acc.w += e.w;
+        }
+    }
+    job.light_w[texel] = acc;
+}
+
+// pt_bake_light_rays: query i = element[i] of sample[i] of texel[i], by light_ray. out: 16 floats per query {wi, pdf, Li, E, o, d}; found: bit 0 the texel has
+// an owner, bit 1 the sample contributes (its shadow ray is {o, d})
+template <bool SPH>
+__global__ __launch_bounds__(256) void k_bake_light_probe(DeviceScene s, RenderConst rc, SobolTables tabs, BakeAtlas a, const uint32_t *owner, uint32_t nsamples, const uint32_t *sel, uint32_t n_sel,
+                                                          float scale, uint32_t n, const uint32_t *texel, const uint32_t *sample, const uint32_t *element, uint32_t *out_light, float *out, uint8_t *found) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t tx = texel[i];
+    const uint32_t prim = tx < a.n_texels ? owner[tx] : PT_NONE;
+    const uint64_t j = (uint64_t)sample[i] * nsamples + element[i];
+    const uint32_t li = sel[j % n_sel];
+    V3 wi(0.0f, 0.0f, 0.0f), o(0.0f, 0.0f, 0.0f), d(0.0f, 0.0f, 0.0f); float pdf = 0.0f; RGB Li(0.0f), E(0.0f);
+    uint32_t bits = 0;
+    if (prim != PT_NONE) {
+        SurfaceInteraction si;
+        texel_interaction(s, a, tx, prim, si);
+        V3 ns; const IData ref = light_ref(si, ns);
+        bits = light_ray<SPH>(s, rc, tabs, ref, ns, (int32_t)(tx % a.width), (int32_t)(tx / a.width), j, li, scale, wi, pdf, Li, E, o, d) ? 3u : 1u;
+    }
+    float *r = out + 16 * (size_t)i;
+    r[0] = wi.x; r[1] = wi.y; r[2] = wi.z; r[3] = pdf; r[4] = Li.r; r[5] = Li.g; r[6] = Li.b; r[7] = E.r; r[8] = E.g; r[9] = E.b;
+    r[10] = o.x; r[11] = o.y; r[12] = o.z; r[13] = d.x; r[14] = d.y; r[15] = d.z;
+    out_light[i] = li; found[i] = (uint8_t)bits;
 }
 
 }  // namespace ptbake

@@ -17,6 +17,12 @@
 //     k_trace<closest>             their closest-hit walk through the source ("extend", per-ray t_max = front + back) -- libmi355pt's
 //     k_bake_transfer_points       hit_prim, height, source position, world- and tangent-space normal; the hit records of the AO passes
 //   per pass and chunk (ao_w wanted): k_bake_transfer_rays, k_trace<any> through the source ("shadow"), k_bake_accum over the detail-hit map
+// pt_bake_light / _samples / _pass_size / _resolve / _rays bake the scene's lights into the atlas (mi355bake.h "Lightmap"). Per call, after the selection, the owner map and
+// the position / normal planes, per pass and chunk of <= 64 light samples per texel sample (light_w wanted):
+//     k_bake_light_rays<SPH>       Light::sample_li of the chunk's samples, the contribution test, the shadow rays of the samples that contribute and what each adds
+//     k_trace<any>                 the shadow rays' any-hit walk ("shadow", t_max = 1 - 0.0001: the render's) -- libmi355pt's
+//     k_bake_light_accum           light_w += {E, 1} of the samples that arrived, in order
+// The chunk loop is ao_chunks (LightJob begins with an AOChunk), the budget ao_ray_budget's plus 20 bytes per ray, SPH general_geometry's as the render chooses it.
 #include "../csrc/host_common.h"
 #include "../side/side_host.h"
 #include "../../include/mi355bake.h"
@@ -62,7 +68,7 @@ int check_prim_count(const pt_scene *sc, uint32_t n_prims) {
 }
 
 // The sampler of a width x height image (fill_render_const), the checks on its sample numbers and the pass size
-int bake_geometry(pt_scene *sc, const PtBakeParams *bp, uint32_t n_samples, Geometry &g) {
+int bake_geometry(pt_scene *sc, const PtBakeParams *bp, uint32_t n_samples, Geometry &g, size_t extra_bytes_per_ray = 0) {
     if (sc->device != g_device) { if (int st = bind_device(sc->device)) return st; }
     PtRenderParams rp{};
     rp.sample_bounds[2] = rp.pixel_bounds[2] = rp.cropped_pixel_bounds[2] = (int32_t)bp->width;
@@ -78,7 +84,9 @@ int bake_geometry(pt_scene *sc, const PtBakeParams *bp, uint32_t n_samples, Geom
     g.K = std::min<uint32_t>(bp->nsamples, kAOChunk);
     uint32_t S = bp->spp_per_pass;
     // (per texel sample: the ray id base and the chunk's rays. The rule counts libmi355pt's path workspace too, which the bake does not allocate: the choice errs small)
-    if (S == 0) S = choose_pass_size(sc, g.atlas.slots, n_samples, 1, false, ao_ray_budget(g.K));
+    PassBudget budget = ao_ray_budget(g.K);
+    budget.extra_bytes_per_path += (size_t)g.K * extra_bytes_per_ray;   // (the lightmap: what a ray adds and its entry of the id table)
+    if (S == 0) S = choose_pass_size(sc, g.atlas.slots, n_samples, 1, false, budget);
     S = std::min(S, n_samples);
     // The additions to a texel are in (sample, element) order: a pass of several samples is accumulated sample by sample within ONE chunk; with more than one chunk
     // per sample a pass is one sample
@@ -268,6 +276,61 @@ int transfer_pass(pt_scene *sc, const Geometry &g, const PtBakeParams *bp, uint3
     job.nsamples = bp->nsamples; job.cos_sample = bp->cos_sample ? 1u : 0u;
     job.s_begin = s_begin; job.s_count = s_count; job.owner = d_detail; job.ao_w = d_ao; job.rec = d_rec;
     return ao_chunks<TransferJob>(sc, job, g.K, items, bp->max_distance, b, spawn, accum);   // (t_max = max_distance)
+}
+
+// ---- the lightmap (mi355bake.h "Lightmap")
+constexpr float kShadowTMax = 1.0f - 0.0001f;     // the render's shadow ray (render_loop.hip: the scalar t_max of its "shadow" launches)
+constexpr size_t kLightBytesPerRay = 16 + 4;      // besides ao_ray_budget's: the E record and the id table's entry
+
+// A lightmap job as a bake's parameters: the sampler, the atlas and the checks on them are the AO bake's (cos_sample and max_distance are not read)
+PtBakeParams light_params(const PtBakeLightParams *lp) {
+    PtBakeParams bp{};
+    bp.width = lp->width; bp.height = lp->height; bp.spp = lp->spp; bp.nsamples = lp->nsamples; bp.cos_sample = 0; bp.max_distance = INFINITY;
+    bp.sampler_type = lp->sampler_type; bp.spp_per_pass = lp->spp_per_pass; bp.profile = lp->profile;
+    return bp;
+}
+// The selected lights in ascending order (light_select NULL: all n_lights), and the rule that gives every light the same number of samples
+int check_lights(const PtBakeLightParams *lp, const uint8_t *light_select, uint32_t n_lights, std::vector<uint32_t> &sel) {
+    sel.clear();
+    for (uint32_t i = 0; i < n_lights; ++i) if (!light_select || light_select[i]) sel.push_back(i);
+    if (sel.empty()) return fail(PT_ERR_INVALID_ARG, "bake light: no light is selected");
+    const uint64_t numbers = (uint64_t)lp->spp * lp->nsamples;
+    if (numbers % sel.size() != 0)
+        return fail(PT_ERR_INVALID_ARG, "bake light: spp x nsamples = " + std::to_string(numbers) + " light samples per texel are no multiple of the " + std::to_string(sel.size()) + " selected lights");
+    return PT_OK;
+}
+int check_light_count(const pt_scene *sc, uint32_t n_lights) {
+    if (n_lights != sc->n_lights) return fail(PT_ERR_INVALID_ARG, "bake light: light_select has " + std::to_string(n_lights) + " entries, the scene " + std::to_string(sc->n_lights) + " lights");
+    return PT_OK;
+}
+int upload_lights(pt_scene *sc, const std::vector<uint32_t> &sel, DevTmp &tmp, uint32_t *&d_sel) {
+    SIDE_ALLOC(tmp, d_sel, sel.size() * 4, "bake light selection");
+    HIP_TRY(hipMemcpyAsync(d_sel, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, sc->stream));   // (`sel` outlives the call's last synchronisation)
+    return PT_OK;
+}
+
+// The light samples of one pass: samples [s_begin, s_begin + s_count) of every texel, chunk by chunk (bake_pass with the shadow ray's t_max)
+int light_pass(pt_scene *sc, const Geometry &g, const PtBakeParams *bp, uint32_t s_begin, uint32_t s_count, const uint32_t *d_owner, float4 *d_light, const uint32_t *d_sel, uint32_t n_sel,
+               uint32_t *d_id, float4 *d_e, const AORayBuffers &b) {
+    const uint32_t items = g.atlas.slots * s_count;
+    const dim3 blocks = blocks_for(items, 16u);
+    const bool sph = general_geometry(sc);   // light_sample_li<SPH> as the render chooses it
+    auto spawn = [&](const LightJob &job) {
+        sc->begin("bake_light_rays", (uint64_t)items * job.kn);
+        if (sph) launch(sc, "ptbake::k_bake_light_rays<true>", k_bake_light_rays<true>, blocks, dim3(256), sc->ds, g.rc, g_tabs, g.atlas, job);
+        else launch(sc, "ptbake::k_bake_light_rays<false>", k_bake_light_rays<false>, blocks, dim3(256), sc->ds, g.rc, g_tabs, g.atlas, job);
+        sc->end();
+    };
+    auto accum = [&](const LightJob &job) {
+        sc->begin("bake_light_accum", items);
+        launch(sc, "ptbake::k_bake_light_accum", k_bake_light_accum, texel_grid(g.atlas), dim3(256), g.atlas, job);
+        sc->end();
+    };
+    LightJob job{};
+    job.nsamples = bp->nsamples; job.cos_sample = 0;
+    job.s_begin = s_begin; job.s_count = s_count; job.owner = d_owner; job.light_w = d_light;
+    job.sel = d_sel; job.n_sel = n_sel; job.scale = (float)n_sel / (float)bp->nsamples; job.id = d_id; job.e = d_e;
+    return ao_chunks<LightJob>(sc, job, g.K, items, kShadowTMax, b, spawn, accum);
 }
 
 }  // namespace
@@ -567,6 +630,151 @@ __attribute__((visibility("default"))) int pt_bake_transfer_rays(pt_scene *targe
         const float *r = rows.data() + 14 * i;
         for (int k = 0; k < 3; ++k) { proj_o[3 * i + k] = r[k]; proj_d[3 * i + k] = r[3 + k]; ao_o[3 * i + k] = r[7 + k]; ao_d[3 * i + k] = r[10 + k]; }
         proj_tmax[i] = r[6]; ao_w[i] = r[13];
+    }
+    return PT_OK;
+}
+
+// ---- the lightmap
+__attribute__((visibility("default"))) int pt_bake_light_pass_size(pt_scene *sc, const PtBakeLightParams *lp, const uint8_t *light_select, uint32_t n_lights, uint32_t *spp_per_pass) {
+    if (!sc || !lp || !spp_per_pass) return fail(PT_ERR_INVALID_ARG, "null argument");
+    const PtBakeParams bp = light_params(lp);
+    if (int st = check_params(&bp)) return st;
+    std::vector<uint32_t> sel;
+    if (int st = check_lights(lp, light_select, n_lights, sel)) return st;
+    if (int st = check_light_count(sc, n_lights)) return st;
+    Geometry g;
+    if (int st = bake_geometry(sc, &bp, bp.spp, g, kLightBytesPerRay)) return st;
+    *spp_per_pass = g.S;
+    return PT_OK;
+}
+
+__attribute__((visibility("default"))) int pt_bake_light(pt_scene *sc, const PtBakeLightParams *lp, const uint8_t *prim_select, uint32_t n_prims, const uint8_t *light_select, uint32_t n_lights,
+                                                         const PtBakeLightBuffers *buffers, int buffers_are_device) {
+    if (!sc || !lp || !prim_select || !buffers) return fail(PT_ERR_INVALID_ARG, "null argument");
+    return pt_bake_light_samples(sc, lp, prim_select, n_prims, light_select, n_lights, 0, lp->spp, buffers, buffers_are_device);
+}
+
+__attribute__((visibility("default"))) int pt_bake_light_samples(pt_scene *sc, const PtBakeLightParams *lp, const uint8_t *prim_select, uint32_t n_prims, const uint8_t *light_select, uint32_t n_lights,
+                                                                 uint32_t first, uint32_t n_samples, const PtBakeLightBuffers *buffers, int buffers_are_device) {
+    if (!sc || !lp || !prim_select || !buffers) return fail(PT_ERR_INVALID_ARG, "null argument");
+    const PtBakeParams bp = light_params(lp);
+    if (int st = check_params(&bp)) return st;
+    if (!buffers->owner && !buffers->position && !buffers->normal && !buffers->light_w) return fail(PT_ERR_INVALID_ARG, "bake: all four planes are NULL");
+    if (int st = check_range(&bp, first, n_samples)) return st;
+    if (int st = check_selection(prim_select, n_prims)) return st;
+    std::vector<uint32_t> sel;
+    if (int st = check_lights(lp, light_select, n_lights, sel)) return st;
+    if (int st = check_prim_count(sc, n_prims)) return st;
+    if (int st = check_light_count(sc, n_lights)) return st;   // (all of the above before the device is touched)
+    Geometry g;
+    if (int st = bake_geometry(sc, &bp, n_samples, g, kLightBytesPerRay)) return st;
+    if (int st = begin_call(sc, bp.profile != 0)) return st;
+    const BakeAtlas &a = g.atlas;
+    const size_t n = a.n_texels;
+    DevTmp tmp;   // (freed when the call returns, however it ends)
+    uint32_t *d_selected = nullptr, n_selected = 0;
+    if (int st = upload_selection(sc, sc, prim_select, n_prims, tmp, d_selected, n_selected)) return st;
+    const bool dev = buffers_are_device != 0;
+    uint32_t *d_owner = dev ? buffers->owner : nullptr;
+    if (!d_owner) SIDE_ALLOC(tmp, d_owner, n * 4, "bake owner map");
+    if (int st = raster(sc, sc, a, d_selected, n_selected, d_owner)) return st;
+    float *d_pos = dev ? buffers->position : nullptr, *d_nrm = dev ? buffers->normal : nullptr;
+    if (buffers->position || buffers->normal) {
+        if (buffers->position && !d_pos) SIDE_ALLOC(tmp, d_pos, n * 12, "bake position plane");
+        if (buffers->normal && !d_nrm) SIDE_ALLOC(tmp, d_nrm, n * 12, "bake normal plane");
+        sc->begin("bake_points", n);
+        launch(sc, "ptbake::k_bake_points", k_bake_points, texel_grid(a), dim3(256), sc->ds, a, (const uint32_t *)d_owner, d_pos, d_nrm);
+        sc->end();
+        HIP_TRY(hipGetLastError());
+    }
+    float4 *d_light = dev ? reinterpret_cast<float4 *>(buffers->light_w) : nullptr;
+    if (buffers->light_w) {
+        if (!d_light) {
+            SIDE_ALLOC(tmp, d_light, n * 16, "bake light plane");
+            HIP_TRY(hipMemcpyAsync(d_light, buffers->light_w, n * 16, hipMemcpyHostToDevice, sc->stream));   // (added to)
+        }
+        uint32_t *d_sel = nullptr, *d_id = nullptr; float4 *d_e = nullptr;
+        if (int st = upload_lights(sc, sel, tmp, d_sel)) return st;
+        AORayBuffers b;
+        const size_t items = (size_t)a.slots * g.S;
+        if (int st = b.alloc(items, items * g.K, "bake light rays")) return st;
+        SIDE_ALLOC(tmp, d_id, items * g.K * 4, "bake light rays"); SIDE_ALLOC(tmp, d_e, items * g.K * 16, "bake light rays");
+        for (uint32_t s0 = first, end = first + n_samples; s0 < end; s0 += g.S)
+            if (int st = light_pass(sc, g, &bp, s0, std::min(g.S, end - s0), d_owner, d_light, d_sel, (uint32_t)sel.size(), d_id, d_e, b)) return st;
+    }
+    if (int st = end_call(sc)) return st;
+    if (!dev) {   // (host planes are written once everything has succeeded)
+        if (buffers->owner) HIP_TRY(hipMemcpy(buffers->owner, d_owner, n * 4, hipMemcpyDeviceToHost));
+        if (buffers->position) HIP_TRY(hipMemcpy(buffers->position, d_pos, n * 12, hipMemcpyDeviceToHost));
+        if (buffers->normal) HIP_TRY(hipMemcpy(buffers->normal, d_nrm, n * 12, hipMemcpyDeviceToHost));
+        if (buffers->light_w) HIP_TRY(hipMemcpy(buffers->light_w, d_light, n * 16, hipMemcpyDeviceToHost));
+    }
+    return PT_OK;
+}
+
+__attribute__((visibility("default"))) int pt_bake_light_resolve(const float *light_w, uint32_t n_texels, uint32_t spp, uint32_t nsamples, float *irradiance_rgb, float *reached) {
+    if (!light_w || (!irradiance_rgb && !reached)) return fail(PT_ERR_INVALID_ARG, "null argument");
+    if (spp == 0) return fail(PT_ERR_INVALID_ARG, "bake: spp must be > 0");
+    if (nsamples == 0) return fail(PT_ERR_INVALID_ARG, "bake: nsamples must be > 0");
+    const float sf = (float)spp, nf = (float)spp * (float)nsamples;
+    for (size_t i = 0; i < n_texels; ++i) {
+        const float r = light_w[4 * i], g = light_w[4 * i + 1], b = light_w[4 * i + 2], w = light_w[4 * i + 3];
+        const bool any = r != 0.0f || g != 0.0f || b != 0.0f || w != 0.0f;
+        if (irradiance_rgb) { irradiance_rgb[3 * i] = any ? r / sf : 0.0f; irradiance_rgb[3 * i + 1] = any ? g / sf : 0.0f; irradiance_rgb[3 * i + 2] = any ? b / sf : 0.0f; }
+        if (reached) reached[i] = any ? w / nf : 0.0f;
+    }
+    return PT_OK;
+}
+
+__attribute__((visibility("default"))) int pt_bake_light_rays(pt_scene *sc, const PtBakeLightParams *lp, const uint8_t *prim_select, uint32_t n_prims, const uint8_t *light_select, uint32_t n_lights,
+                                                              uint32_t n, const uint32_t *texel, const uint32_t *sample, const uint32_t *element, uint32_t *out_light, float *out_wi, float *out_pdf,
+                                                              float *out_li, float *out_e, float *out_o, float *out_d, uint8_t *found) {
+    if (!sc || !lp || !prim_select || !texel || !sample || !element || !out_light || !out_wi || !out_pdf || !out_li || !out_e || !out_o || !out_d || !found) return fail(PT_ERR_INVALID_ARG, "null argument");
+    PtBakeParams bp = light_params(lp);
+    if (int st = check_params(&bp)) return st;
+    if (int st = check_selection(prim_select, n_prims)) return st;
+    std::vector<uint32_t> sel;
+    if (int st = check_lights(lp, light_select, n_lights, sel)) return st;
+    for (uint32_t i = 0; i < n; ++i)
+        if (sample[i] >= bp.spp || element[i] >= bp.nsamples) return fail(PT_ERR_INVALID_ARG, "bake: ray " + std::to_string(i) + " names a sample or element outside the job");
+    if (int st = check_prim_count(sc, n_prims)) return st;
+    if (int st = check_light_count(sc, n_lights)) return st;
+    Geometry g;
+    bp.spp_per_pass = 1;
+    if (int st = bake_geometry(sc, &bp, bp.spp, g, kLightBytesPerRay)) return st;
+    if (n == 0) return PT_OK;
+    if (int st = begin_call(sc, false)) return st;
+    DevTmp tmp;
+    uint32_t *d_selected = nullptr, n_selected = 0, *d_owner = nullptr, *d_in = nullptr, *d_sel = nullptr, *d_light = nullptr; float *d_out = nullptr; uint8_t *d_found = nullptr;
+    if (int st = upload_selection(sc, sc, prim_select, n_prims, tmp, d_selected, n_selected)) return st;
+    SIDE_ALLOC(tmp, d_owner, (size_t)g.atlas.n_texels * 4, "bake owner map");
+    if (int st = raster(sc, sc, g.atlas, d_selected, n_selected, d_owner)) return st;
+    if (int st = upload_lights(sc, sel, tmp, d_sel)) return st;
+    SIDE_ALLOC(tmp, d_in, (size_t)n * 12, "bake light rays"); SIDE_ALLOC(tmp, d_out, (size_t)n * 64, "bake light rays"); SIDE_ALLOC(tmp, d_light, (size_t)n * 4, "bake light rays");
+    SIDE_ALLOC(tmp, d_found, n, "bake light rays");
+    HIP_TRY(hipMemcpyAsync(d_in, texel, (size_t)n * 4, hipMemcpyHostToDevice, sc->stream));
+    HIP_TRY(hipMemcpyAsync(d_in + n, sample, (size_t)n * 4, hipMemcpyHostToDevice, sc->stream));
+    HIP_TRY(hipMemcpyAsync(d_in + 2 * (size_t)n, element, (size_t)n * 4, hipMemcpyHostToDevice, sc->stream));
+    const uint32_t n_sel = (uint32_t)sel.size();
+    const float scale = (float)n_sel / (float)bp.nsamples;
+    sc->begin("bake_probe", n);
+    if (general_geometry(sc))
+        launch(sc, "ptbake::k_bake_light_probe<true>", k_bake_light_probe<true>, dim3((n + 255) / 256), dim3(256), sc->ds, g.rc, g_tabs, g.atlas, (const uint32_t *)d_owner, bp.nsamples, (const uint32_t *)d_sel,
+               n_sel, scale, n, (const uint32_t *)d_in, (const uint32_t *)(d_in + n), (const uint32_t *)(d_in + 2 * (size_t)n), d_light, d_out, d_found);
+    else
+        launch(sc, "ptbake::k_bake_light_probe<false>", k_bake_light_probe<false>, dim3((n + 255) / 256), dim3(256), sc->ds, g.rc, g_tabs, g.atlas, (const uint32_t *)d_owner, bp.nsamples, (const uint32_t *)d_sel,
+               n_sel, scale, n, (const uint32_t *)d_in, (const uint32_t *)(d_in + n), (const uint32_t *)(d_in + 2 * (size_t)n), d_light, d_out, d_found);
+    sc->end();
+    HIP_TRY(hipGetLastError());
+    if (int st = end_call(sc)) return st;
+    std::vector<float> rows((size_t)n * 16);
+    HIP_TRY(hipMemcpy(rows.data(), d_out, rows.size() * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_light, d_light, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(found, d_found, n, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) {
+        const float *r = rows.data() + 16 * i;
+        for (int k = 0; k < 3; ++k) { out_wi[3 * i + k] = r[k]; out_li[3 * i + k] = r[4 + k]; out_e[3 * i + k] = r[7 + k]; out_o[3 * i + k] = r[10 + k]; out_d[3 * i + k] = r[13 + k]; }
+        out_pdf[i] = r[3];
     }
     return PT_OK;
 }

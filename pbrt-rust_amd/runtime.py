@@ -140,6 +140,17 @@ def resolve_bake(ao_w, spp, lib=None):
     return ao, bent
 
 
+def resolve_lightmap(light_w, spp, nsamples, lib=None):
+    """pt_bake_light_resolve of the light_w sums Scene.bake_light returns, (H, W, 4): (irradiance (H, W, 3) = sum E / spp, reached (H, W) = the fraction of the
+    spp * nsamples light samples of a texel that arrived), 0 where nothing was added."""
+    lib = lib or load_library()
+    light_w = np.ascontiguousarray(light_w, dtype=np.float32)
+    shape = light_w.shape[:-1]
+    irradiance = np.zeros(shape + (3,), np.float32); reached = np.zeros(shape, np.float32)
+    lib.check(lib.bake.pt_bake_light_resolve(_fptr(light_w), light_w.size // 4, spp, nsamples, _fptr(irradiance), _fptr(reached)), "pt_bake_light_resolve")
+    return irradiance, reached
+
+
 def encode_normal_map(tangent_normal, covered):
     """The tangent_normal plane of Scene.bake_transfer, (H, W, 3), as a normal-map image: n * 0.5 + 0.5 where `covered` ((H, W) bool: the texels with a detail hit, or
     those a dilation filled), the flat normal (0.5, 0.5, 1) elsewhere. float32."""
@@ -583,6 +594,64 @@ class Scene(Handle):
         self._call("bake_rays", self.h, C.byref(bp), sel.ctypes.data_as(A.u8p), len(sel), n, texel.ctypes.data_as(A.u32p), sample.ctypes.data_as(A.u32p),
                    element.ctypes.data_as(A.u32p), _fptr(o), _fptr(d), _fptr(w), found.ctypes.data_as(A.u8p), lib=self.L.bake)
         return o, d, w, found
+
+    def bake_light_select(self, lights):
+        """(light_select bytes or None, n_lights, n_sel) of pt_bake_light*: `lights` is None (all of the scene's lights), a list of light indices in the scene's
+        light order, or a per-light array (bool or uint8, one entry per light) used as it is."""
+        n = self.data.desc().n_lights
+        if lights is None:
+            return None, n, n
+        if isinstance(lights, np.ndarray) and lights.dtype in (np.bool_, np.uint8):
+            sel = np.ascontiguousarray(lights, dtype=np.uint8)
+        else:
+            sel = np.zeros(n, np.uint8)
+            sel[np.atleast_1d(np.asarray(lights, dtype=np.int64))] = 1
+        return sel, len(sel), int(np.count_nonzero(sel))
+
+    def bake_light_params(self, width, height, spp, nsamples, sampler="sobol", spp_per_pass=0, profile=False):
+        return BAKE.PtBakeLightParams(width, height, spp, nsamples, {"sobol": A.PT_SAMPLER_SOBOL, "halton": A.PT_SAMPLER_HALTON}[sampler], spp_per_pass, 1 if profile else 0)
+
+    def bake_light(self, select, width, height, spp, nsamples=None, lights=None, sampler="sobol", samples=None, sums=None, device_ptrs=None, planes=BAKE.LIGHT_PLANES,
+                   spp_per_pass=0, profile=False):
+        """pt_bake_light of the primitives `select` names (bake_select) under the lights `lights` names (bake_light_select; None: all) into a width x height UV atlas
+        (`samples` = (first, n): pt_bake_light_samples): a dict of the wanted planes -- "owner", "position" and "normal" as Scene.bake, "light_w" (H, W, 4) = the sums
+        of what the unoccluded light samples add and their count (resolve_lightmap turns them into the irradiance map). `nsamples` light samples per sample, None: one
+        per selected light. light_w is ADDED to the array of `sums` as Scene.bake does. `device_ptrs` = {plane: device pointer}: returns None."""
+        sel = self.bake_select(select)
+        lsel, n_lights, n_sel = self.bake_light_select(lights)
+        lp = self.bake_light_params(width, height, spp, n_sel if nsamples is None else nsamples, sampler, spp_per_pass, profile)
+        args = [self.h, C.byref(lp), sel.ctypes.data_as(A.u8p), len(sel), None if lsel is None else lsel.ctypes.data_as(A.u8p), n_lights] + ([] if samples is None else list(samples))
+        name = "bake_light" if samples is None else "bake_light_samples"
+        if device_ptrs is not None:
+            self._call(name, *args, C.byref(BAKE.light_buffers(device_ptrs, device=True)), 1, lib=self.L.bake); return None
+        if sums is None:
+            sums = {}
+        for k in planes:
+            if k not in sums:
+                sums[k] = np.zeros((height, width) + ((BAKE.LIGHT_CHANNELS[k],) if k != "owner" else ()), dtype=BAKE.LIGHT_DTYPES[k])
+        self._call(name, *args, C.byref(BAKE.light_buffers({k: sums[k] for k in planes})), 0, lib=self.L.bake)
+        return sums
+
+    def bake_light_pass_size(self, width, height, spp, nsamples=None, lights=None, sampler="sobol", spp_per_pass=0):
+        """Samples per texel per pass pt_bake_light would use now."""
+        lsel, n_lights, n_sel = self.bake_light_select(lights)
+        lp = self.bake_light_params(width, height, spp, n_sel if nsamples is None else nsamples, sampler, spp_per_pass)
+        return self._pass_size("bake_light_pass_size", C.byref(lp), None if lsel is None else lsel.ctypes.data_as(A.u8p), n_lights, lib=self.L.bake)
+
+    def bake_light_rays(self, select, width, height, spp, texel, sample, element, nsamples=None, lights=None, sampler="sobol"):
+        """pt_bake_light_rays: dict(light (n,) uint32, wi (n, 3), pdf (n,), Li (n, 3), E (n, 3), o (n, 3), d (n, 3), found (n,) uint8: bit 0 the texel has an owner,
+        bit 1 the sample contributes and (o, d) is its shadow ray) of the light samples named by the arrays texel / sample / element."""
+        sel = self.bake_select(select)
+        lsel, n_lights, n_sel = self.bake_light_select(lights)
+        lp = self.bake_light_params(width, height, spp, n_sel if nsamples is None else nsamples, sampler)
+        texel, sample, element = (np.ascontiguousarray(v, dtype=np.uint32) for v in (texel, sample, element))
+        n = len(texel)
+        r = {k: np.zeros((n, 3), np.float32) for k in ("wi", "Li", "E", "o", "d")}
+        r.update(light=np.zeros(n, np.uint32), pdf=np.zeros(n, np.float32), found=np.zeros(n, np.uint8))
+        self._call("bake_light_rays", self.h, C.byref(lp), sel.ctypes.data_as(A.u8p), len(sel), None if lsel is None else lsel.ctypes.data_as(A.u8p), n_lights, n,
+                   texel.ctypes.data_as(A.u32p), sample.ctypes.data_as(A.u32p), element.ctypes.data_as(A.u32p), r["light"].ctypes.data_as(A.u32p),
+                   *[_fptr(r[k]) for k in ("wi", "pdf", "Li", "E", "o", "d")], r["found"].ctypes.data_as(A.u8p), lib=self.L.bake)
+        return r
 
     def bake_transfer_params(self, width, height, front, back, spp=1, nsamples=64, cos_sample=True, max_distance=float("inf"), sampler="sobol", spp_per_pass=0, profile=False):
         return BAKE.PtBakeTransferParams(width, height, front, back, spp, nsamples, 1 if cos_sample else 0, max_distance, {"sobol": A.PT_SAMPLER_SOBOL, "halton": A.PT_SAMPLER_HALTON}[sampler],
