@@ -279,6 +279,83 @@ int pt_bake_light_rays(pt_scene *scene, const PtBakeLightParams *params, const u
                        uint32_t n, const uint32_t *texel, const uint32_t *sample, const uint32_t *element, uint32_t *out_light, float *out_wi, float *out_pdf,
                        float *out_li, float *out_e, float *out_o, float *out_d, uint8_t *found);
 
+/* ---- SH points: the scene's lights baked at free points into order-2 spherical harmonics ("light probes") -----------------------------
+ *
+ * What has no UV atlas -- a character, a prop, a particle, a point in the air -- gets its direct light from points in space: the incident
+ * radiance at a point, projected onto the nine real spherical harmonics of orders 0 to 2, per colour channel. A dynamic object evaluates
+ * them with its own normal (pt_bake_sh_irradiance). The light samples, the shadow rays and the sums are the lightmap's; the reference point
+ * has no surface and an SH projection stands where the cosine stood. Every operation float32, unfused, in this order:
+ *
+ * 1. Points. n_points points p_i, HOST memory, three floats each, all finite. Point i is pixel (x, y) = (i mod row, i / row) of a sampler
+ *    set up for sample bounds [0, row) x [0, rows), rows = ceil(n_points / row). The reference point of its light samples is
+ *    ref = {p_i, p_error = 0, n = 0}: a medium interaction's, as estimate_direct gets one from integrators/volpath.rs. With n = 0
+ *    offset_ray_origin adds nothing: every shadow ray starts at p_i exactly.
+ * 2. Which light. The lightmap's step 2: sel[] ascending, sample number j = s * nsamples + k samples light sel[j mod n_sel] in 64-bit
+ *    arithmetic, spp * nsamples a multiple of n_sel. The light of a sample does NOT depend on the point (see k_bake_sh_rays).
+ * 3. Light sample. The lightmap's step 3: u = the 2-D array value of sample number j of pixel (x, y), dimensions 5 and 6;
+ *    (Li, wi, pdf, p1) = Light::sample_li(ref, u), by the device function the render samples its lights with.
+ * 4. Contribution. A sample contributes if pdf > 0 (a NaN fails) and Li is not black. There is no cosine and no side test: a point
+ *    receives light from the whole sphere. Then
+ *        w = ((float)n_sel / (float)nsamples) / pdf,      E = Li * w   per channel.
+ * 5. Shadow ray. The lightmap's step 5: Interaction::spawn_ray_to(ref, p1), an any-hit query through the whole scene with
+ *    t_max = 1 - 0.0001f. Media are NOT consulted. A sample that does not contribute spawns no ray.
+ * 6. Basis. With (x, y, z) = wi -- sample_li's wi, not the normalised ray direction -- and float32 literals:
+ *        Y0 = 0.282095f                  Y1 = 0.488603f * y              Y2 = 0.488603f * z
+ *        Y3 = 0.488603f * x              Y4 = 1.092548f * (x * y)        Y5 = 1.092548f * (y * z)
+ *        Y6 = 0.315392f * ((3.0f * (z * z)) - 1.0f)                      Y7 = 1.092548f * (x * z)
+ *        Y8 = 0.546274f * ((x * x) - (y * y))
+ * 7. Sums. sh_w holds 28 floats per point. For every unoccluded contributing sample sh_w[28 i + 3 q + c] += E.c * Y_q for q in 0 .. 8 and
+ *    c in r, g, b, and sh_w[28 i + 27] += 1.0f, in ascending (s, k), onto what the buffer holds. Sample ranges baked in ascending order,
+ *    any spp_per_pass, repeated calls and device or host buffers leave the same bytes.
+ * 8. Resolve (pt_bake_sh_resolve). sh[27 i + m] = sh_w[28 i + m] / (float)spp: the SH coefficients of the direct incident radiance;
+ *    reached[i] = sh_w[28 i + 27] / ((float)spp * (float)nsamples). Both 0 where all 28 sums are 0.
+ * 9. Irradiance (pt_bake_sh_irradiance). For a unit normal nrm, E_c = the sum over q ascending, from 0.0f, of (A_q * sh[3 q + c]) *
+ *    Y_q(nrm), with A_0 = 3.141593f, A_1..3 = 2.094395f, A_4..8 = 0.785398f: Ramamoorthi and Hanrahan's cosine-lobe factors. The sum is
+ *    NOT clamped: an order-2 fit can go slightly negative, and the caller decides what to do with that.
+ *
+ * Where the arithmetic produces NaN or infinity the sums hold what it leaves: a point on a point light's position (wi = 0 / 0, pdf = 1
+ * contributes), or in an emissive triangle's plane. Keep points off the lights. spp * nsamples is limited as under "AO rays"; under Sobol'
+ * row and rows are limited to the 2^25 pixel grid. PtCounters.shadow_tests = the shadow rays traced = the contributing samples. Launch
+ * kinds: "bake_sh_rays", "shadow", "bake_sh_accum" ("bake_probe" for pt_bake_sh_rays). Chunks and passes as for the lightmap. */
+typedef struct PtBakeShParams {
+    uint32_t n_points;           /* 1 .. 2^28                                                          */
+    uint32_t row;                /* points per sampler row, 1 .. 2^28                                  */
+    uint32_t spp;                /* the job's samples per point, > 0                                   */
+    uint32_t nsamples;           /* light samples per sample, > 0; spp * nsamples a multiple of n_sel  */
+    uint32_t sampler_type;       /* PtSamplerType                                                      */
+    uint32_t spp_per_pass;       /* 0: the library chooses from the free memory                        */
+    uint32_t profile;            /* != 0: time every launch kind (pt_get_kernel_stats)                 */
+} PtBakeShParams;
+
+/* Bakes params->spp samples of params->nsamples light samples each at every point under the lights selected by light_select
+ * (pt_bake_light's). points and light_select are HOST memory; sh_w -- 28 floats per point, device or host memory -- is ADDED to.
+ * Errors. PT_ERR_INVALID_ARG, before the device is touched and before the scene handle is read, in this order: a NULL scene, params, points
+ * or sh_w; n_points 0 or above 2^28; row 0 or above 2^28; spp or nsamples 0; an unknown sampler_type; a bad sample range; a point with a
+ * coordinate that is not finite (the message names the point); no light selected (n_lights == 0 included); spp * nsamples no multiple of
+ * the number of selected lights (the message names both numbers). Then, reading the handle's host side: n_lights different from the
+ * scene's light count. Then, with the device bound: the sampler's limits. A host sh_w is written only after everything has succeeded. */
+int pt_bake_sh(pt_scene *scene, const PtBakeShParams *params, const float *points, const uint8_t *light_select, uint32_t n_lights, float *sh_w, int buffers_are_device);
+/* Samples [first_sample, first_sample + n_samples) of every point; params->spp stays the job's sample count. pt_bake_sh is the call (0, spp). */
+int pt_bake_sh_samples(pt_scene *scene, const PtBakeShParams *params, const float *points, const uint8_t *light_select, uint32_t n_lights, uint32_t first_sample,
+                       uint32_t n_samples, float *sh_w, int buffers_are_device);
+/* Samples per point per pass pt_bake_sh would use: pt_bake_light_pass_size's rule over the points padded to a multiple of 64, with 36 more
+ * bytes per ray (what it adds, its wi, its id). */
+int pt_bake_sh_pass_size(pt_scene *scene, const PtBakeShParams *params, const uint8_t *light_select, uint32_t n_lights, uint32_t *spp_per_pass);
+/* Host arithmetic: step 8. sh: 27 floats per point (coefficient q, channel c at 3 q + c). A NULL output is skipped. PT_ERR_INVALID_ARG for
+ * a NULL sh_w, both outputs NULL, spp or nsamples 0. */
+int pt_bake_sh_resolve(const float *sh_w, uint32_t n_points, uint32_t spp, uint32_t nsamples, float *sh, float *reached);
+/* Host arithmetic: step 9 for n pairs -- entry i of sh (27 floats) goes with normal i (3 floats, unit length; not checked).
+ * PT_ERR_INVALID_ARG for a NULL argument. */
+int pt_bake_sh_irradiance(const float *sh, const float *normals, uint32_t n, float *irradiance_rgb);
+/* Parity entry, in the style of pt_bake_light_rays: for n triples (point index, sample number s, element k) -- host arrays -- the light
+ * that sample is taken on, Light::sample_li's wi, pdf and Li, E and the shadow ray (out_o, out_d), by the device function the bake uses.
+ * found[i]: bit 0 = the point index is below n_points (else everything but out_light is zeros), bit 1 = the sample contributes (else E and
+ * the ray are zeros). The parameters, the points, the selection and their checks are pt_bake_sh's (spp_per_pass and profile are not read);
+ * a sample or element outside the job is refused after them. */
+int pt_bake_sh_rays(pt_scene *scene, const PtBakeShParams *params, const float *points, const uint8_t *light_select, uint32_t n_lights, uint32_t n, const uint32_t *point,
+                    const uint32_t *sample, const uint32_t *element, uint32_t *out_light, float *out_wi, float *out_pdf, float *out_li, float *out_e, float *out_o,
+                    float *out_d, uint8_t *found);
+
 #ifdef __cplusplus
 }
 #endif

@@ -65,10 +65,20 @@ def light_buffers(planes, device=False):
     return buffers(planes, device, PtBakeLightBuffers)
 
 
+# pt_bake_sh: 28 sums per point in sh_w (27 = coefficient q, channel c at 3 q + c; the count of arrived samples), 27 coefficients per point resolved
+SH_SUMS = 28
+SH_COEFFICIENTS = 9
+
+
+class PtBakeShParams(C.Structure):
+    _fields_ = [("n_points", u32), ("row", u32), ("spp", u32), ("nsamples", u32), ("sampler_type", u32), ("spp_per_pass", u32), ("profile", u32)]
+
+
 # Every symbol include/mi355bake.h declares, with its signature (restype, argtypes).
 _bp, _bb = C.POINTER(PtBakeParams), C.POINTER(PtBakeBuffers)
 _tp, _tb = C.POINTER(PtBakeTransferParams), C.POINTER(PtBakeTransferBuffers)
 _lp, _lb = C.POINTER(PtBakeLightParams), C.POINTER(PtBakeLightBuffers)
+_hp = C.POINTER(PtBakeShParams)
 ENTRY_POINTS = {
     "pt_bake_render": (C.c_int, [VP, _bp, u8p, u32, _bb, C.c_int]),
     "pt_bake_render_samples": (C.c_int, [VP, _bp, u8p, u32, u32, u32, _bb, C.c_int]),
@@ -85,4 +95,10 @@ ENTRY_POINTS = {
     "pt_bake_light_pass_size": (C.c_int, [VP, _lp, u8p, u32, u32p]),
     "pt_bake_light_resolve": (C.c_int, [fp, u32, u32, u32, fp, fp]),
     "pt_bake_light_rays": (C.c_int, [VP, _lp, u8p, u32, u8p, u32, u32, u32p, u32p, u32p, u32p, fp, fp, fp, fp, fp, fp, u8p]),
+    "pt_bake_sh": (C.c_int, [VP, _hp, fp, u8p, u32, fp, C.c_int]),
+    "pt_bake_sh_samples": (C.c_int, [VP, _hp, fp, u8p, u32, u32, u32, fp, C.c_int]),
+    "pt_bake_sh_pass_size": (C.c_int, [VP, _hp, u8p, u32, u32p]),
+    "pt_bake_sh_resolve": (C.c_int, [fp, u32, u32, u32, fp, fp]),
+    "pt_bake_sh_irradiance": (C.c_int, [fp, fp, u32, fp]),
+    "pt_bake_sh_rays": (C.c_int, [VP, _hp, fp, u8p, u32, u32, u32p, u32p, u32p, u32p, fp, fp, fp, fp, fp, fp, u8p]),
 }

@@ -16,7 +16,11 @@
 //   k_bake_light_rays<SPH>   one texel sample per lane: one chunk of its light samples -> the shadow rays of those that contribute, and what each would add
 //   k_bake_light_accum       light_w += the unoccluded samples' E and 1, in element order
 //   k_bake_light_probe<SPH>  pt_bake_light_rays: single light samples by light_ray, the function k_bake_light_rays' rays come from
-// No atomics other than the owner map's atomicMin and the per-wave ray-id reservation (wave_reserve; k_bake_light_rays' own, one for several elements).
+// and, for the SH points (pt_bake_sh: the lights sampled from free points in space and projected onto the nine order-2 spherical harmonics):
+//   k_bake_sh_rays<SPH>      one point sample per lane: k_bake_light_rays from a point without surface -> the shadow rays, what each would add, and its wi
+//   k_bake_sh_accum          sh_w += E * Y_q(wi) and 1 of the unoccluded samples, in element order
+//   k_bake_sh_probe<SPH>     pt_bake_sh_rays: single light samples by sh_ray, the function k_bake_sh_rays' rays come from
+// No atomics other than the owner map's atomicMin and the per-wave ray-id reservation (wave_reserve; k_bake_light_rays' and k_bake_sh_rays' own, one for several elements).
 #pragma once
 #include "../csrc/kern_decl.h"
 #include "../side/ao_rays.h"
@@ -25,7 +29,8 @@ namespace ptbake {
 using namespace ptside;
 
 constexpr uint32_t kLightGroup = 4;                  // k_bake_light_rays: light samples of a texel sample whose rays share one ray-id reservation
-constexpr uint32_t kRasterOwnTexels = 16;            // k_bake_raster: a triangle whose texel box holds at most this many texels is walked by its own lane
+constexpr uint32_t kShAhead = 4;                     // k_bake_sh_accum: steps of a point's walk whose loads are in flight together
+constexpr uint32_t kRasterOwnTexels = 16;           // k_bake_raster: a triangle whose texel box holds at most this many texels is walked by its own lane
 
 // `slots`: the texel samples of one sample number in the order the ray kernel walks them -- 8 x 8 texel tiles, one per wave, so that the rays of a wave start from a
 // square patch of the surface and not from a line of 64 texels (measured against raster order on a 2048^2 bake of a 4.3 M-triangle mesh: the any-hit launch 129.8 ms
@@ -561,6 +566,173 @@ __global__ __launch_bounds__(256) void k_bake_light_probe(DeviceScene s, RenderC
         texel_interaction(s, a, tx, prim, si);
         V3 ns; const IData ref = light_ref(si, ns);
         bits = light_ray<SPH>(s, rc, tabs, ref, ns, (int32_t)(tx % a.width), (int32_t)(tx / a.width), j, li, scale, wi, pdf, Li, E, o, d) ? 3u : 1u;
+    }
+    float *r = out + 16 * (size_t)i;
+    r[0] = wi.x; r[1] = wi.y; r[2] = wi.z; r[3] = pdf; r[4] = Li.r; r[5] = Li.g; r[6] = Li.b; r[7] = E.r; r[8] = E.g; r[9] = E.b;
+    r[10] = o.x; r[11] = o.y; r[12] = o.z; r[13] = d.x; r[14] = d.y; r[15] = d.z;
+    out_light[i] = li; found[i] = (uint8_t)bits;
+}
+
+// ---- the SH points (mi355bake.h "SH points")
+
+// One chunk of light samples of the point samples [s_begin, s_begin + s_count) of n_points points. A sample number's items are the points padded to whole waves
+// (`padded`, a multiple of 64): item = sample-in-pass * padded + point. LightJob's records, and per ray the wi its basis is evaluated with where the sums are made.
+struct ShJob : AOChunk {
+    uint32_t s_begin, s_count;
+    uint32_t n_points, padded, row;
+    const float *points;     // [n_points][3]
+    float4 *sh_w;            // [n_points][7]: 27 sums (coefficient q, channel c at 3 q + c) and the count of arrived samples
+    const uint32_t *sel;     // [n_sel]: the selected lights, ascending
+    uint32_t n_sel;
+    float scale;             // (float)n_sel / (float)nsamples
+    uint32_t *id;            // [kn][items]
+    float4 *e;               // [rays]: {E.rgb, 1}
+    float4 *wi;              // [rays]: {wi.xyz, -}
+};
+
+// Sample number j of point p, pixel (px, py), on light li (contract steps 1 and 3 to 5): light_ray from a reference point without surface -- a medium interaction's,
+// p_error = n = 0, so the shadow ray starts at p exactly --, without cosine and side test. false: the sample adds nothing and spawns no ray (E, o and d are zeros then).
+// (light_ray stands as it was: the two share ao_array_sample, light_sample_li and spawn_ray_to, and the lightmap's kernels keep their code.)
+template <bool SPH>
+PT_DEV bool sh_ray(const DeviceScene &s, const RenderConst &rc, const SobolTables &tabs, V3 p, int32_t px, int32_t py, uint64_t j, uint32_t li, float scale,
+                   V3 &wi, float &pdf, RGB &Li, RGB &E, V3 &o, V3 &d) {
+    IData ref; ref.p = p; ref.p_error = ref.n = V3(0.0f, 0.0f, 0.0f);
+    const P2 u = ao_array_sample(rc, tabs, px, py, j);
+    wi = V3(0.0f, 0.0f, 0.0f); pdf = 0.0f;
+    IData p1;
+    Li = light_sample_li<SPH>(s, li, ref, u, wi, pdf, p1);
+    E = RGB(0.0f); o = V3(0.0f, 0.0f, 0.0f); d = V3(0.0f, 0.0f, 0.0f);
+    if (!(pdf > 0.0f) || (Li.r == 0.0f && Li.g == 0.0f && Li.b == 0.0f)) return false;
+    const float w = scale / pdf;
+    E = Li * w;
+    spawn_ray_to(ref, p1, o, d);
+    return true;
+}
+
+// The nine real SH basis functions of orders 0 to 2 at (x, y, z) (contract step 6)
+PT_HD void sh_basis(float x, float y, float z, float Y[9]) {
+    Y[0] = 0.282095f;
+    Y[1] = 0.488603f * y;
+    Y[2] = 0.488603f * z;
+    Y[3] = 0.488603f * x;
+    Y[4] = 1.092548f * (x * y);
+    Y[5] = 1.092548f * (y * z);
+    Y[6] = 0.315392f * ((3.0f * (z * z)) - 1.0f);
+    Y[7] = 1.092548f * (x * z);
+    Y[8] = 0.546274f * ((x * x) - (y * y));
+}
+
+// Per point sample of the pass: this chunk's light samples. k_bake_light_rays with a wave of 64 consecutive points of ONE sample number in the tile's place: the light
+// index is wave-uniform and goes through readfirstlane, one ray-id reservation per wave per kLightGroup elements. Lanes beyond n_points take part in the ballots and
+// spawn nothing.
+template <bool SPH>
+__global__ __launch_bounds__(256) void k_bake_sh_rays(DeviceScene s, RenderConst rc, SobolTables tabs, ShJob job) {
+    const uint32_t total = job.padded * job.s_count;   // (a multiple of 64: whole waves)
+    for (uint32_t item = blockIdx.x * blockDim.x + threadIdx.x; item < total; item += gridDim.x * blockDim.x) {
+        const uint32_t point = item % job.padded;
+        const uint32_t sl = (uint32_t)__builtin_amdgcn_readfirstlane((int)(item / job.padded));
+        const bool found = point < job.n_points;
+        V3 p(0.0f, 0.0f, 0.0f);
+        if (found) p = V3(job.points[3 * (size_t)point], job.points[3 * (size_t)point + 1], job.points[3 * (size_t)point + 2]);
+        const int32_t px = found ? (int32_t)(point % job.row) : 0, py = found ? (int32_t)(point / job.row) : 0;
+        const uint64_t j0 = ((uint64_t)job.s_begin + sl) * job.nsamples + job.k0;
+        uint32_t r = (uint32_t)(j0 % job.n_sel);
+        for (uint32_t kk = 0; kk < job.kn; kk += kLightGroup) {   // (one reservation per group: see k_bake_light_rays)
+            V3 o[kLightGroup], d[kLightGroup], wi[kLightGroup]; RGB E[kLightGroup];
+            unsigned long long rays[kLightGroup];   // per element: the lanes whose sample contributes
+            uint32_t n_rays = 0;
+#pragma unroll
+            for (uint32_t g = 0; g < kLightGroup; ++g) {
+                bool ray = false;
+                if (kk + g < job.kn) {
+                    const uint32_t li = (uint32_t)__builtin_amdgcn_readfirstlane((int)job.sel[r]);
+                    r = r + 1u == job.n_sel ? 0u : r + 1u;
+                    float pdf; RGB Li;
+                    if (found) ray = sh_ray<SPH>(s, rc, tabs, p, px, py, j0 + kk + g, li, job.scale, wi[g], pdf, Li, E[g], o[g], d[g]);
+                }
+                rays[g] = __ballot(ray);
+                n_rays += (uint32_t)__popcll(rays[g]);
+            }
+            uint32_t base = 0;
+            if (n_rays != 0u) {
+                if (lane_id() == 0u) base = atomicAdd(job.ray_count, n_rays);
+                base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+            }
+            const unsigned long long below = (1ull << lane_id()) - 1ull;
+#pragma unroll
+            for (uint32_t g = 0; g < kLightGroup; ++g) {
+                if (kk + g >= job.kn) break;
+                const bool ray = ((rays[g] >> lane_id()) & 1ull) != 0ull;
+                const uint32_t id = base + (uint32_t)__popcll(rays[g] & below);
+                base += (uint32_t)__popcll(rays[g]);
+                job.id[(size_t)(kk + g) * total + item] = ray ? id : PT_NONE;
+                if (!ray) continue;
+                job.ray[2 * (size_t)id] = make_float4(o[g].x, o[g].y, o[g].z, d[g].x);
+                job.ray[2 * (size_t)id + 1] = make_float4(d[g].y, d[g].z, 0.0f, 0.0f);
+                job.e[id] = make_float4(E[g].r, E[g].g, E[g].b, 1.0f);
+                job.wi[id] = make_float4(wi[g].x, wi[g].y, wi[g].z, 0.0f);
+            }
+        }
+    }
+}
+
+// sh_w += {E * Y_q(wi), 1} of the unoccluded contributing samples, in (sample, element) order through the id table: one lane per point, its 28 sums in registers, the
+// basis evaluated here from the ray's wi. (One lane per float4 of a point's seven was measured beside it and lost: DESIGN section 5, "SH points".)
+__global__ __launch_bounds__(256) void k_bake_sh_accum(ShJob job) {
+    const uint32_t point = blockIdx.x * blockDim.x + threadIdx.x;
+    if (point >= job.n_points) return;
+    const uint32_t total = job.padded * job.s_count;
+    float4 *out = job.sh_w + 7 * (size_t)point;
+    float acc[28];
+#pragma unroll
+    for (uint32_t g = 0; g < 7; ++g) { const float4 v = out[g]; acc[4 * g] = v.x; acc[4 * g + 1] = v.y; acc[4 * g + 2] = v.z; acc[4 * g + 3] = v.w; }
+    // The walk is a chain of dependent loads per step (id, flag, records), and a point's additions have one order: kShAhead steps' loads are issued together, stage by
+    // stage, and their sums are added one after the other (step = sl * kn + kk)
+    const uint32_t steps = job.s_count * job.kn;
+    uint32_t sl = 0, kk = 0;
+    for (uint32_t t0 = 0; t0 < steps; t0 += kShAhead) {
+        uint32_t id[kShAhead]; bool arrived[kShAhead]; float4 e[kShAhead], w[kShAhead];
+#pragma unroll
+        for (uint32_t g = 0; g < kShAhead; ++g) {
+            id[g] = t0 + g < steps ? job.id[(size_t)kk * total + (size_t)sl * job.padded + point] : PT_NONE;
+            if (++kk == job.kn) { kk = 0; ++sl; }
+        }
+#pragma unroll
+        for (uint32_t g = 0; g < kShAhead; ++g) arrived[g] = id[g] != PT_NONE && job.occluded[id[g]] == 0u;
+#pragma unroll
+        for (uint32_t g = 0; g < kShAhead; ++g) {
+            e[g] = w[g] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (arrived[g]) { e[g] = job.e[id[g]]; w[g] = job.wi[id[g]]; }
+        }
+#pragma unroll
+        for (uint32_t g = 0; g < kShAhead; ++g) {
+            if (!arrived[g]) continue;
+            float Y[9]; sh_basis(w[g].x, w[g].y, w[g].z, Y);
+#pragma unroll
+            for (uint32_t k = 0; k < 9; ++k) { acc[3 * k] += e[g].x * Y[k]; acc[3 * k + 1] += e[g].y * Y[k]; acc[3 * k + 2] += e[g].z * Y[k]; }
+            acc[27] += 1.0f;
+        }
+    }
+#pragma unroll
+    for (uint32_t g = 0; g < 7; ++g) out[g] = make_float4(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]);
+}
+
+// pt_bake_sh_rays: query i = element[i] of sample[i] of point[i], by sh_ray. out: 16 floats per query {wi, pdf, Li, E, o, d}; found: bit 0 the point index is
+// below n_points, bit 1 the sample contributes (its shadow ray is {o, d})
+template <bool SPH>
+__global__ __launch_bounds__(256) void k_bake_sh_probe(DeviceScene s, RenderConst rc, SobolTables tabs, const float *points, uint32_t n_points, uint32_t row, uint32_t nsamples,
+                                                       const uint32_t *sel, uint32_t n_sel, float scale, uint32_t n, const uint32_t *point, const uint32_t *sample, const uint32_t *element,
+                                                       uint32_t *out_light, float *out, uint8_t *found) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t pt = point[i];
+    const uint64_t j = (uint64_t)sample[i] * nsamples + element[i];
+    const uint32_t li = sel[j % n_sel];
+    V3 wi(0.0f, 0.0f, 0.0f), o(0.0f, 0.0f, 0.0f), d(0.0f, 0.0f, 0.0f); float pdf = 0.0f; RGB Li(0.0f), E(0.0f);
+    uint32_t bits = 0;
+    if (pt < n_points) {
+        const V3 p(points[3 * (size_t)pt], points[3 * (size_t)pt + 1], points[3 * (size_t)pt + 2]);
+        bits = sh_ray<SPH>(s, rc, tabs, p, (int32_t)(pt % row), (int32_t)(pt / row), j, li, scale, wi, pdf, Li, E, o, d) ? 3u : 1u;
     }
     float *r = out + 16 * (size_t)i;
     r[0] = wi.x; r[1] = wi.y; r[2] = wi.z; r[3] = pdf; r[4] = Li.r; r[5] = Li.g; r[6] = Li.b; r[7] = E.r; r[8] = E.g; r[9] = E.b;

@@ -23,6 +23,12 @@
 //     k_trace<any>                 the shadow rays' any-hit walk ("shadow", t_max = 1 - 0.0001: the render's) -- libmi355pt's
 //     k_bake_light_accum           light_w += {E, 1} of the samples that arrived, in order
 // The chunk loop is ao_chunks (LightJob begins with an AOChunk), the budget ao_ray_budget's plus 20 bytes per ray, SPH general_geometry's as the render chooses it.
+// pt_bake_sh / _samples / _pass_size / _resolve / _irradiance / _rays bake the scene's lights at free points into order-2 spherical harmonics (mi355bake.h "SH points").
+// There is no atlas, no selection and no owner map: the points are uploaded, a sample number's items are the points padded to whole waves. Per pass and chunk:
+//     k_bake_sh_rays<SPH>          the lightmap's light samples from a reference point without surface: the shadow rays, what each adds, and its wi
+//     k_trace<any>                 the same "shadow" walk
+//     k_bake_sh_accum              sh_w += {E * Y_q(wi), 1} of the samples that arrived, in order
+// The budget is ao_ray_budget's plus 36 bytes per ray.
 #include "../csrc/host_common.h"
 #include "../side/side_host.h"
 #include "../../include/mi355bake.h"
@@ -68,7 +74,8 @@ int check_prim_count(const pt_scene *sc, uint32_t n_prims) {
 }
 
 // The sampler of a width x height image (fill_render_const), the checks on its sample numbers and the pass size
-int bake_geometry(pt_scene *sc, const PtBakeParams *bp, uint32_t n_samples, Geometry &g, size_t extra_bytes_per_ray = 0) {
+// (`slots`: the items of one sample number, 0: the atlas's tile slots; the SH points have no atlas and pass their padded point count)
+int bake_geometry(pt_scene *sc, const PtBakeParams *bp, uint32_t n_samples, Geometry &g, size_t extra_bytes_per_ray = 0, uint32_t slots = 0) {
     if (sc->device != g_device) { if (int st = bind_device(sc->device)) return st; }
     PtRenderParams rp{};
     rp.sample_bounds[2] = rp.pixel_bounds[2] = rp.cropped_pixel_bounds[2] = (int32_t)bp->width;
@@ -80,18 +87,19 @@ int bake_geometry(pt_scene *sc, const PtBakeParams *bp, uint32_t n_samples, Geom
     fill_render_const(&rp, rc);
     if (rc.sobol.log2_resolution > 25) return fail(PT_ERR_INVALID_ARG, "bake: the atlas exceeds the 2^25 Sobol' pixel grid");
     g.atlas = make_atlas(bp->width, bp->height);
+    if (slots == 0) slots = g.atlas.slots;
     if (int st = check_ao_sample_numbers(rc, bp->spp, bp->nsamples, "bake", "texel")) return st;
     g.K = std::min<uint32_t>(bp->nsamples, kAOChunk);
     uint32_t S = bp->spp_per_pass;
     // (per texel sample: the ray id base and the chunk's rays. The rule counts libmi355pt's path workspace too, which the bake does not allocate: the choice errs small)
     PassBudget budget = ao_ray_budget(g.K);
     budget.extra_bytes_per_path += (size_t)g.K * extra_bytes_per_ray;   // (the lightmap: what a ray adds and its entry of the id table)
-    if (S == 0) S = choose_pass_size(sc, g.atlas.slots, n_samples, 1, false, budget);
+    if (S == 0) S = choose_pass_size(sc, slots, n_samples, 1, false, budget);
     S = std::min(S, n_samples);
     // The additions to a texel are in (sample, element) order: a pass of several samples is accumulated sample by sample within ONE chunk; with more than one chunk
     // per sample a pass is one sample
     if (bp->nsamples > kAOChunk) S = 1;
-    if ((size_t)g.atlas.slots * S * g.K > kAOMaxRays) return fail(PT_ERR_INVALID_ARG, "bake: pass too large: texels x samples per pass x min(nsamples, 64) AO rays per launch > 2^31 (lower spp_per_pass)");
+    if ((size_t)slots * S * g.K > kAOMaxRays) return fail(PT_ERR_INVALID_ARG, "bake: pass too large: texels x samples per pass x min(nsamples, 64) AO rays per launch > 2^31 (lower spp_per_pass)");
     g.S = S;
     return PT_OK;
 }
@@ -290,13 +298,13 @@ PtBakeParams light_params(const PtBakeLightParams *lp) {
     return bp;
 }
 // The selected lights in ascending order (light_select NULL: all n_lights), and the rule that gives every light the same number of samples
-int check_lights(const PtBakeLightParams *lp, const uint8_t *light_select, uint32_t n_lights, std::vector<uint32_t> &sel) {
+int check_lights(const PtBakeLightParams *lp, const uint8_t *light_select, uint32_t n_lights, std::vector<uint32_t> &sel, const char *per = "texel") {
     sel.clear();
     for (uint32_t i = 0; i < n_lights; ++i) if (!light_select || light_select[i]) sel.push_back(i);
     if (sel.empty()) return fail(PT_ERR_INVALID_ARG, "bake light: no light is selected");
     const uint64_t numbers = (uint64_t)lp->spp * lp->nsamples;
     if (numbers % sel.size() != 0)
-        return fail(PT_ERR_INVALID_ARG, "bake light: spp x nsamples = " + std::to_string(numbers) + " light samples per texel are no multiple of the " + std::to_string(sel.size()) + " selected lights");
+        return fail(PT_ERR_INVALID_ARG, "bake light: spp x nsamples = " + std::to_string(numbers) + " light samples per " + per + " are no multiple of the " + std::to_string(sel.size()) + " selected lights");
     return PT_OK;
 }
 int check_light_count(const pt_scene *sc, uint32_t n_lights) {
@@ -331,6 +339,72 @@ int light_pass(pt_scene *sc, const Geometry &g, const PtBakeParams *bp, uint32_t
     job.s_begin = s_begin; job.s_count = s_count; job.owner = d_owner; job.light_w = d_light;
     job.sel = d_sel; job.n_sel = n_sel; job.scale = (float)n_sel / (float)bp->nsamples; job.id = d_id; job.e = d_e;
     return ao_chunks<LightJob>(sc, job, g.K, items, kShadowTMax, b, spawn, accum);
+}
+
+// ---- the SH points (mi355bake.h "SH points")
+constexpr uint32_t kShMaxPoints = 1u << 28;
+constexpr size_t kShBytesPerRay = 16 + 16 + 4;    // besides ao_ray_budget's: the E record, wi and the id table's entry
+
+uint32_t sh_rows(const PtBakeShParams *hp) { return (hp->n_points + hp->row - 1) / hp->row; }
+uint32_t sh_padded(const PtBakeShParams *hp) { return (hp->n_points + 63u) / 64u * 64u; }
+// An SH job as a bake's parameters: the sampler is that of a row x rows image (cos_sample and max_distance are not read)
+PtBakeParams sh_params(const PtBakeShParams *hp) {
+    PtBakeParams bp{};
+    bp.width = hp->row; bp.height = sh_rows(hp); bp.spp = hp->spp; bp.nsamples = hp->nsamples; bp.cos_sample = 0; bp.max_distance = INFINITY;
+    bp.sampler_type = hp->sampler_type; bp.spp_per_pass = hp->spp_per_pass; bp.profile = hp->profile;
+    return bp;
+}
+// Errors 2 to 5 of the header's list
+int check_sh(const PtBakeShParams *hp) {
+    if (hp->n_points == 0) return fail(PT_ERR_INVALID_ARG, "bake sh: n_points must be > 0");
+    if (hp->n_points > kShMaxPoints) return fail(PT_ERR_INVALID_ARG, "bake sh: more than 2^28 points");
+    if (hp->row == 0) return fail(PT_ERR_INVALID_ARG, "bake sh: row must be > 0");
+    if (hp->row > kShMaxPoints) return fail(PT_ERR_INVALID_ARG, "bake sh: row exceeds 2^28");
+    if (hp->spp == 0) return fail(PT_ERR_INVALID_ARG, "bake: spp must be > 0");
+    if (hp->nsamples == 0) return fail(PT_ERR_INVALID_ARG, "bake: nsamples must be > 0");
+    if (hp->sampler_type != PT_SAMPLER_SOBOL && hp->sampler_type != PT_SAMPLER_HALTON) return fail(PT_ERR_INVALID_ARG, "bake: sampler_type must be PT_SAMPLER_SOBOL or PT_SAMPLER_HALTON");
+    return PT_OK;
+}
+// Errors 7 to 9
+int check_sh_points_and_lights(const PtBakeShParams *hp, const float *points, const uint8_t *light_select, uint32_t n_lights, std::vector<uint32_t> &sel) {
+    for (size_t i = 0; i < (size_t)hp->n_points * 3; ++i)
+        if (!std::isfinite(points[i])) return fail(PT_ERR_INVALID_ARG, "bake sh: point " + std::to_string(i / 3) + " has a coordinate that is not finite");
+    PtBakeLightParams lp{};
+    lp.spp = hp->spp; lp.nsamples = hp->nsamples;
+    return check_lights(&lp, light_select, n_lights, sel, "point");
+}
+int sh_geometry(pt_scene *sc, const PtBakeShParams *hp, uint32_t n_samples, Geometry &g) {
+    const PtBakeParams bp = sh_params(hp);
+    return bake_geometry(sc, &bp, n_samples, g, kShBytesPerRay, sh_padded(hp));
+}
+int upload_points(pt_scene *sc, const PtBakeShParams *hp, const float *points, DevTmp &tmp, float *&d_points) {
+    SIDE_ALLOC(tmp, d_points, (size_t)hp->n_points * 12, "bake sh points");
+    HIP_TRY(hipMemcpyAsync(d_points, points, (size_t)hp->n_points * 12, hipMemcpyHostToDevice, sc->stream));   // (the caller's array outlives the call's last synchronisation)
+    return PT_OK;
+}
+
+// The light samples of one pass: samples [s_begin, s_begin + s_count) of every point, chunk by chunk (light_pass without atlas)
+int sh_pass(pt_scene *sc, const Geometry &g, const PtBakeShParams *hp, uint32_t s_begin, uint32_t s_count, const float *d_points, float4 *d_sh, const uint32_t *d_sel, uint32_t n_sel,
+            uint32_t *d_id, float4 *d_e, float4 *d_wi, const AORayBuffers &b) {
+    const uint32_t padded = sh_padded(hp), items = padded * s_count;
+    const dim3 blocks = blocks_for(items, 16u);
+    const bool sph = general_geometry(sc);   // light_sample_li<SPH> as the render chooses it
+    auto spawn = [&](const ShJob &job) {
+        sc->begin("bake_sh_rays", (uint64_t)items * job.kn);
+        if (sph) launch(sc, "ptbake::k_bake_sh_rays<true>", k_bake_sh_rays<true>, blocks, dim3(256), sc->ds, g.rc, g_tabs, job);
+        else launch(sc, "ptbake::k_bake_sh_rays<false>", k_bake_sh_rays<false>, blocks, dim3(256), sc->ds, g.rc, g_tabs, job);
+        sc->end();
+    };
+    auto accum = [&](const ShJob &job) {
+        sc->begin("bake_sh_accum", items);
+        launch(sc, "ptbake::k_bake_sh_accum", k_bake_sh_accum, dim3((hp->n_points + 255) / 256), dim3(256), job);
+        sc->end();
+    };
+    ShJob job{};
+    job.nsamples = hp->nsamples; job.cos_sample = 0;
+    job.s_begin = s_begin; job.s_count = s_count; job.n_points = hp->n_points; job.padded = padded; job.row = hp->row; job.points = d_points; job.sh_w = d_sh;
+    job.sel = d_sel; job.n_sel = n_sel; job.scale = (float)n_sel / (float)hp->nsamples; job.id = d_id; job.e = d_e; job.wi = d_wi;
+    return ao_chunks<ShJob>(sc, job, g.K, items, kShadowTMax, b, spawn, accum);
 }
 
 }  // namespace
@@ -764,6 +838,138 @@ __attribute__((visibility("default"))) int pt_bake_light_rays(pt_scene *sc, cons
     else
         launch(sc, "ptbake::k_bake_light_probe<false>", k_bake_light_probe<false>, dim3((n + 255) / 256), dim3(256), sc->ds, g.rc, g_tabs, g.atlas, (const uint32_t *)d_owner, bp.nsamples, (const uint32_t *)d_sel,
                n_sel, scale, n, (const uint32_t *)d_in, (const uint32_t *)(d_in + n), (const uint32_t *)(d_in + 2 * (size_t)n), d_light, d_out, d_found);
+    sc->end();
+    HIP_TRY(hipGetLastError());
+    if (int st = end_call(sc)) return st;
+    std::vector<float> rows((size_t)n * 16);
+    HIP_TRY(hipMemcpy(rows.data(), d_out, rows.size() * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_light, d_light, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(found, d_found, n, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) {
+        const float *r = rows.data() + 16 * i;
+        for (int k = 0; k < 3; ++k) { out_wi[3 * i + k] = r[k]; out_li[3 * i + k] = r[4 + k]; out_e[3 * i + k] = r[7 + k]; out_o[3 * i + k] = r[10 + k]; out_d[3 * i + k] = r[13 + k]; }
+        out_pdf[i] = r[3];
+    }
+    return PT_OK;
+}
+
+// ---- the SH points
+__attribute__((visibility("default"))) int pt_bake_sh_pass_size(pt_scene *sc, const PtBakeShParams *hp, const uint8_t *light_select, uint32_t n_lights, uint32_t *spp_per_pass) {
+    if (!sc || !hp || !spp_per_pass) return fail(PT_ERR_INVALID_ARG, "null argument");
+    if (int st = check_sh(hp)) return st;
+    std::vector<uint32_t> sel;
+    PtBakeLightParams lp{};
+    lp.spp = hp->spp; lp.nsamples = hp->nsamples;
+    if (int st = check_lights(&lp, light_select, n_lights, sel, "point")) return st;
+    if (int st = check_light_count(sc, n_lights)) return st;
+    Geometry g;
+    if (int st = sh_geometry(sc, hp, hp->spp, g)) return st;
+    *spp_per_pass = g.S;
+    return PT_OK;
+}
+
+__attribute__((visibility("default"))) int pt_bake_sh(pt_scene *sc, const PtBakeShParams *hp, const float *points, const uint8_t *light_select, uint32_t n_lights, float *sh_w, int buffers_are_device) {
+    if (!sc || !hp || !points || !sh_w) return fail(PT_ERR_INVALID_ARG, "null argument");
+    return pt_bake_sh_samples(sc, hp, points, light_select, n_lights, 0, hp->spp, sh_w, buffers_are_device);
+}
+
+__attribute__((visibility("default"))) int pt_bake_sh_samples(pt_scene *sc, const PtBakeShParams *hp, const float *points, const uint8_t *light_select, uint32_t n_lights, uint32_t first,
+                                                              uint32_t n_samples, float *sh_w, int buffers_are_device) {
+    if (!sc || !hp || !points || !sh_w) return fail(PT_ERR_INVALID_ARG, "null argument");
+    if (int st = check_sh(hp)) return st;
+    const PtBakeParams bp = sh_params(hp);
+    if (int st = check_range(&bp, first, n_samples)) return st;
+    std::vector<uint32_t> sel;
+    if (int st = check_sh_points_and_lights(hp, points, light_select, n_lights, sel)) return st;
+    if (int st = check_light_count(sc, n_lights)) return st;   // (all of the above before the device is touched)
+    Geometry g;
+    if (int st = sh_geometry(sc, hp, n_samples, g)) return st;
+    if (int st = begin_call(sc, hp->profile != 0)) return st;
+    const size_t n = hp->n_points;
+    DevTmp tmp;   // (freed when the call returns, however it ends)
+    const bool dev = buffers_are_device != 0;
+    float4 *d_sh = dev ? reinterpret_cast<float4 *>(sh_w) : nullptr;
+    if (!d_sh) {
+        SIDE_ALLOC(tmp, d_sh, n * 112, "bake sh sums");
+        HIP_TRY(hipMemcpyAsync(d_sh, sh_w, n * 112, hipMemcpyHostToDevice, sc->stream));   // (added to)
+    }
+    float *d_points = nullptr; uint32_t *d_sel = nullptr, *d_id = nullptr; float4 *d_e = nullptr, *d_wi = nullptr;
+    if (int st = upload_points(sc, hp, points, tmp, d_points)) return st;
+    if (int st = upload_lights(sc, sel, tmp, d_sel)) return st;
+    AORayBuffers b;
+    const size_t items = (size_t)sh_padded(hp) * g.S;
+    if (int st = b.alloc(items, items * g.K, "bake sh rays")) return st;
+    SIDE_ALLOC(tmp, d_id, items * g.K * 4, "bake sh rays"); SIDE_ALLOC(tmp, d_e, items * g.K * 16, "bake sh rays"); SIDE_ALLOC(tmp, d_wi, items * g.K * 16, "bake sh rays");
+    for (uint32_t s0 = first, end = first + n_samples; s0 < end; s0 += g.S)
+        if (int st = sh_pass(sc, g, hp, s0, std::min(g.S, end - s0), d_points, d_sh, d_sel, (uint32_t)sel.size(), d_id, d_e, d_wi, b)) return st;
+    if (int st = end_call(sc)) return st;
+    if (!dev) HIP_TRY(hipMemcpy(sh_w, d_sh, n * 112, hipMemcpyDeviceToHost));   // (a host buffer is written once everything has succeeded)
+    return PT_OK;
+}
+
+__attribute__((visibility("default"))) int pt_bake_sh_resolve(const float *sh_w, uint32_t n_points, uint32_t spp, uint32_t nsamples, float *sh, float *reached) {
+    if (!sh_w || (!sh && !reached)) return fail(PT_ERR_INVALID_ARG, "null argument");
+    if (spp == 0) return fail(PT_ERR_INVALID_ARG, "bake: spp must be > 0");
+    if (nsamples == 0) return fail(PT_ERR_INVALID_ARG, "bake: nsamples must be > 0");
+    const float sf = (float)spp, nf = (float)spp * (float)nsamples;
+    for (size_t i = 0; i < n_points; ++i) {
+        const float *w = sh_w + 28 * i;
+        bool any = false;
+        for (int m = 0; m < 28; ++m) any = any || w[m] != 0.0f;
+        if (sh) for (int m = 0; m < 27; ++m) sh[27 * i + m] = any ? w[m] / sf : 0.0f;
+        if (reached) reached[i] = any ? w[27] / nf : 0.0f;
+    }
+    return PT_OK;
+}
+
+__attribute__((visibility("default"))) int pt_bake_sh_irradiance(const float *sh, const float *normals, uint32_t n, float *irradiance_rgb) {
+    if (!sh || !normals || !irradiance_rgb) return fail(PT_ERR_INVALID_ARG, "null argument");
+    // (Ramamoorthi and Hanrahan's cosine-lobe factors: pi, 2 pi / 3, pi / 4)
+    const float A[9] = {3.141593f, 2.094395f, 2.094395f, 2.094395f, 0.785398f, 0.785398f, 0.785398f, 0.785398f, 0.785398f};
+    for (size_t i = 0; i < n; ++i) {
+        float Y[9]; sh_basis(normals[3 * i], normals[3 * i + 1], normals[3 * i + 2], Y);
+        for (int c = 0; c < 3; ++c) {
+            float e = 0.0f;
+            for (int q = 0; q < 9; ++q) e += (A[q] * sh[27 * i + 3 * q + c]) * Y[q];
+            irradiance_rgb[3 * i + c] = e;
+        }
+    }
+    return PT_OK;
+}
+
+__attribute__((visibility("default"))) int pt_bake_sh_rays(pt_scene *sc, const PtBakeShParams *hp, const float *points, const uint8_t *light_select, uint32_t n_lights, uint32_t n, const uint32_t *point,
+                                                           const uint32_t *sample, const uint32_t *element, uint32_t *out_light, float *out_wi, float *out_pdf, float *out_li, float *out_e,
+                                                           float *out_o, float *out_d, uint8_t *found) {
+    if (!sc || !hp || !points || !point || !sample || !element || !out_light || !out_wi || !out_pdf || !out_li || !out_e || !out_o || !out_d || !found) return fail(PT_ERR_INVALID_ARG, "null argument");
+    if (int st = check_sh(hp)) return st;
+    std::vector<uint32_t> sel;
+    if (int st = check_sh_points_and_lights(hp, points, light_select, n_lights, sel)) return st;
+    for (uint32_t i = 0; i < n; ++i)
+        if (sample[i] >= hp->spp || element[i] >= hp->nsamples) return fail(PT_ERR_INVALID_ARG, "bake: ray " + std::to_string(i) + " names a sample or element outside the job");
+    if (int st = check_light_count(sc, n_lights)) return st;
+    Geometry g;
+    PtBakeShParams one = *hp; one.spp_per_pass = 1;
+    if (int st = sh_geometry(sc, &one, hp->spp, g)) return st;
+    if (n == 0) return PT_OK;
+    if (int st = begin_call(sc, false)) return st;
+    DevTmp tmp;
+    float *d_points = nullptr, *d_out = nullptr; uint32_t *d_in = nullptr, *d_sel = nullptr, *d_light = nullptr; uint8_t *d_found = nullptr;
+    if (int st = upload_points(sc, hp, points, tmp, d_points)) return st;
+    if (int st = upload_lights(sc, sel, tmp, d_sel)) return st;
+    SIDE_ALLOC(tmp, d_in, (size_t)n * 12, "bake sh rays"); SIDE_ALLOC(tmp, d_out, (size_t)n * 64, "bake sh rays"); SIDE_ALLOC(tmp, d_light, (size_t)n * 4, "bake sh rays");
+    SIDE_ALLOC(tmp, d_found, n, "bake sh rays");
+    HIP_TRY(hipMemcpyAsync(d_in, point, (size_t)n * 4, hipMemcpyHostToDevice, sc->stream));
+    HIP_TRY(hipMemcpyAsync(d_in + n, sample, (size_t)n * 4, hipMemcpyHostToDevice, sc->stream));
+    HIP_TRY(hipMemcpyAsync(d_in + 2 * (size_t)n, element, (size_t)n * 4, hipMemcpyHostToDevice, sc->stream));
+    const uint32_t n_sel = (uint32_t)sel.size();
+    const float scale = (float)n_sel / (float)hp->nsamples;
+    sc->begin("bake_probe", n);
+    if (general_geometry(sc))
+        launch(sc, "ptbake::k_bake_sh_probe<true>", k_bake_sh_probe<true>, dim3((n + 255) / 256), dim3(256), sc->ds, g.rc, g_tabs, (const float *)d_points, hp->n_points, hp->row, hp->nsamples,
+               (const uint32_t *)d_sel, n_sel, scale, n, (const uint32_t *)d_in, (const uint32_t *)(d_in + n), (const uint32_t *)(d_in + 2 * (size_t)n), d_light, d_out, d_found);
+    else
+        launch(sc, "ptbake::k_bake_sh_probe<false>", k_bake_sh_probe<false>, dim3((n + 255) / 256), dim3(256), sc->ds, g.rc, g_tabs, (const float *)d_points, hp->n_points, hp->row, hp->nsamples,
+               (const uint32_t *)d_sel, n_sel, scale, n, (const uint32_t *)d_in, (const uint32_t *)(d_in + n), (const uint32_t *)(d_in + 2 * (size_t)n), d_light, d_out, d_found);
     sc->end();
     HIP_TRY(hipGetLastError());
     if (int st = end_call(sc)) return st;

@@ -1,6 +1,7 @@
 """ctypes binding of libmi355pt.so (the HIP product library).  Fails loudly when the
 extension is missing: there is NO CPU fallback behind this module."""
 import ctypes as C
+import math
 import os
 import subprocess
 import numpy as np
@@ -149,6 +150,33 @@ def resolve_lightmap(light_w, spp, nsamples, lib=None):
     irradiance = np.zeros(shape + (3,), np.float32); reached = np.zeros(shape, np.float32)
     lib.check(lib.bake.pt_bake_light_resolve(_fptr(light_w), light_w.size // 4, spp, nsamples, _fptr(irradiance), _fptr(reached)), "pt_bake_light_resolve")
     return irradiance, reached
+
+
+def resolve_sh(sh_w, spp, nsamples, lib=None):
+    """pt_bake_sh_resolve of the sh_w sums Scene.bake_sh returns, (n, 28): (sh (n, 9, 3) = the order-2 SH coefficients of the direct incident radiance per
+    colour channel, reached (n,) = the fraction of the spp * nsamples light samples of a point that arrived), 0 where nothing was added."""
+    lib = lib or load_library()
+    sh_w = np.ascontiguousarray(sh_w, dtype=np.float32)
+    n = sh_w.size // BAKE.SH_SUMS
+    sh = np.zeros((n, BAKE.SH_COEFFICIENTS, 3), np.float32); reached = np.zeros(n, np.float32)
+    lib.check(lib.bake.pt_bake_sh_resolve(_fptr(sh_w), n, spp, nsamples, _fptr(sh), _fptr(reached)), "pt_bake_sh_resolve")
+    return sh, reached
+
+
+def sh_irradiance(sh, normals, lib=None):
+    """pt_bake_sh_irradiance: the irradiance (n, 3) a surface of unit normal normals[i] receives under the coefficients sh[i] ((n, 9, 3), as resolve_sh returns
+    them; one entry is used for every normal). Not clamped: an order-2 fit can go slightly negative."""
+    lib = lib or load_library()
+    normals = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+    sh = np.asarray(sh, dtype=np.float32).reshape(-1, BAKE.SH_COEFFICIENTS, 3)
+    if len(sh) == 1 and len(normals) != 1:
+        sh = np.broadcast_to(sh, (len(normals), BAKE.SH_COEFFICIENTS, 3))
+    if len(sh) != len(normals):
+        raise ValueError(f"sh_irradiance: {len(sh)} sets of coefficients, {len(normals)} normals")
+    sh = np.ascontiguousarray(sh)
+    out = np.zeros((len(normals), 3), np.float32)
+    lib.check(lib.bake.pt_bake_sh_irradiance(_fptr(sh), _fptr(normals), len(normals), _fptr(out)), "pt_bake_sh_irradiance")
+    return out
 
 
 def encode_normal_map(tangent_normal, covered):
@@ -650,6 +678,54 @@ class Scene(Handle):
         r.update(light=np.zeros(n, np.uint32), pdf=np.zeros(n, np.float32), found=np.zeros(n, np.uint8))
         self._call("bake_light_rays", self.h, C.byref(lp), sel.ctypes.data_as(A.u8p), len(sel), None if lsel is None else lsel.ctypes.data_as(A.u8p), n_lights, n,
                    texel.ctypes.data_as(A.u32p), sample.ctypes.data_as(A.u32p), element.ctypes.data_as(A.u32p), r["light"].ctypes.data_as(A.u32p),
+                   *[_fptr(r[k]) for k in ("wi", "pdf", "Li", "E", "o", "d")], r["found"].ctypes.data_as(A.u8p), lib=self.L.bake)
+        return r
+
+    def bake_sh_params(self, points, spp, nsamples, sampler="sobol", row=None, spp_per_pass=0, profile=False):
+        """(the points as a contiguous (n, 3) float32 array, the PtBakeShParams): `row` None = ceil(sqrt(n))."""
+        points = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        n = len(points)
+        if row is None:
+            row = max(1, math.isqrt(n))
+            row += row * row < n
+        return points, BAKE.PtBakeShParams(n, row, spp, nsamples, {"sobol": A.PT_SAMPLER_SOBOL, "halton": A.PT_SAMPLER_HALTON}[sampler], spp_per_pass, 1 if profile else 0)
+
+    def bake_sh(self, points, spp, nsamples=None, lights=None, sampler="sobol", row=None, samples=None, sums=None, device_ptr=None, spp_per_pass=0, profile=False):
+        """pt_bake_sh: the direct light of the lights `lights` names (bake_light_select; None: all) at the free points `points` (n, 3), as sums over the nine order-2
+        spherical harmonics (`samples` = (first, n): pt_bake_sh_samples). Returns sh_w (n, 28) = per point the 27 sums (coefficient q, channel c at 3 q + c) and the
+        count of light samples that arrived (resolve_sh turns them into the coefficients, sh_irradiance evaluates those for a normal). `nsamples` light samples per
+        sample, None: one per selected light. Point i is pixel (i mod row, i / row) of the sampler. The sums are ADDED to the array `sums` (what this method
+        returned) when given, in place. `device_ptr`: sh_w is a device pointer as an integer, returns None."""
+        lsel, n_lights, n_sel = self.bake_light_select(lights)
+        points, hp = self.bake_sh_params(points, spp, n_sel if nsamples is None else nsamples, sampler, row, spp_per_pass, profile)
+        args = [self.h, C.byref(hp), _fptr(points), None if lsel is None else lsel.ctypes.data_as(A.u8p), n_lights] + ([] if samples is None else list(samples))
+        name = "bake_sh" if samples is None else "bake_sh_samples"
+        if device_ptr is not None:
+            self._call(name, *args, C.cast(C.c_void_p(device_ptr), A.fp), 1, lib=self.L.bake); return None
+        if sums is None:
+            sums = np.zeros((len(points), BAKE.SH_SUMS), np.float32)
+        if sums.shape != (len(points), BAKE.SH_SUMS) or sums.dtype != np.float32 or not sums.flags.c_contiguous:
+            raise ValueError(f"bake_sh: sums must be a contiguous float32 array of shape {(len(points), BAKE.SH_SUMS)}")
+        self._call(name, *args, _fptr(sums), 0, lib=self.L.bake)
+        return sums
+
+    def bake_sh_pass_size(self, n_points, spp, nsamples=None, lights=None, sampler="sobol", row=None, spp_per_pass=0):
+        """Samples per point per pass pt_bake_sh would use now."""
+        lsel, n_lights, n_sel = self.bake_light_select(lights)
+        _, hp = self.bake_sh_params(np.zeros((n_points, 3), np.float32), spp, n_sel if nsamples is None else nsamples, sampler, row, spp_per_pass)
+        return self._pass_size("bake_sh_pass_size", C.byref(hp), None if lsel is None else lsel.ctypes.data_as(A.u8p), n_lights, lib=self.L.bake)
+
+    def bake_sh_rays(self, points, spp, point, sample, element, nsamples=None, lights=None, sampler="sobol", row=None):
+        """pt_bake_sh_rays: dict(light (n,) uint32, wi (n, 3), pdf (n,), Li (n, 3), E (n, 3), o (n, 3), d (n, 3), found (n,) uint8: bit 0 the point index is below
+        the point count, bit 1 the sample contributes and (o, d) is its shadow ray) of the light samples named by the arrays point / sample / element."""
+        lsel, n_lights, n_sel = self.bake_light_select(lights)
+        points, hp = self.bake_sh_params(points, spp, n_sel if nsamples is None else nsamples, sampler, row)
+        point, sample, element = (np.ascontiguousarray(v, dtype=np.uint32) for v in (point, sample, element))
+        n = len(point)
+        r = {k: np.zeros((n, 3), np.float32) for k in ("wi", "Li", "E", "o", "d")}
+        r.update(light=np.zeros(n, np.uint32), pdf=np.zeros(n, np.float32), found=np.zeros(n, np.uint8))
+        self._call("bake_sh_rays", self.h, C.byref(hp), _fptr(points), None if lsel is None else lsel.ctypes.data_as(A.u8p), n_lights, n,
+                   point.ctypes.data_as(A.u32p), sample.ctypes.data_as(A.u32p), element.ctypes.data_as(A.u32p), r["light"].ctypes.data_as(A.u32p),
                    *[_fptr(r[k]) for k in ("wi", "pdf", "Li", "E", "o", "d")], r["found"].ctypes.data_as(A.u8p), lib=self.L.bake)
         return r
 
