@@ -3,9 +3,24 @@ _abi.py, which mirrors include/mi355pt.h alone."""
 import ctypes as C
 from ._abi import VP, fp, u8p, u32, u32p
 
-PLANES = ("owner", "position", "normal", "ao_w")              # PtBakeBuffers' fields, in this order
-CHANNELS = {"owner": 1, "position": 3, "normal": 3, "ao_w": 4}   # entries per texel of a plane
-DTYPES = {"owner": "uint32", "position": "float32", "normal": "float32", "ao_w": "float32"}
+# Per job kind {plane: (entries per texel, dtype)}, in the order of the fields of its buffer struct (BUFFERS)
+_ID, _SCALAR, _VECTOR, _SUMS = (1, "uint32"), (1, "float32"), (3, "float32"), (4, "float32")
+PLANE_TABLES = {
+    "bake": {"owner": _ID, "position": _VECTOR, "normal": _VECTOR, "ao_w": _SUMS},
+    "transfer": {"owner": _ID, "hit_prim": _ID, "height": _SCALAR, "src_position": _VECTOR, "src_normal": _VECTOR, "tangent_normal": _VECTOR, "ao_w": _SUMS},
+    "light": {"owner": _ID, "position": _VECTOR, "normal": _VECTOR, "light_w": _SUMS},
+}
+
+
+def _columns(kind):
+    """(planes, {plane: channels}, {plane: dtype}) of a job kind"""
+    table = PLANE_TABLES[kind]
+    return tuple(table), {k: c for k, (c, _) in table.items()}, {k: d for k, (_, d) in table.items()}
+
+
+PLANES, CHANNELS, DTYPES = _columns("bake")
+TRANSFER_PLANES, TRANSFER_CHANNELS, TRANSFER_DTYPES = _columns("transfer")
+LIGHT_PLANES, LIGHT_CHANNELS, LIGHT_DTYPES = _columns("light")
 
 
 class PtBakeParams(C.Structure):
@@ -26,12 +41,6 @@ def buffers(planes, device=False, struct=PtBakeBuffers):
     return b
 
 
-# pt_bake_transfer: PtBakeTransferBuffers' fields, in this order
-TRANSFER_PLANES = ("owner", "hit_prim", "height", "src_position", "src_normal", "tangent_normal", "ao_w")
-TRANSFER_CHANNELS = {"owner": 1, "hit_prim": 1, "height": 1, "src_position": 3, "src_normal": 3, "tangent_normal": 3, "ao_w": 4}
-TRANSFER_DTYPES = {k: ("uint32" if k in ("owner", "hit_prim") else "float32") for k in TRANSFER_PLANES}
-
-
 class PtBakeTransferParams(C.Structure):
     _fields_ = [("width", u32), ("height", u32), ("front", C.c_float), ("back", C.c_float), ("spp", u32), ("nsamples", u32), ("cos_sample", u32), ("max_distance", C.c_float),
                 ("sampler_type", u32), ("spp_per_pass", u32), ("profile", u32)]
@@ -46,12 +55,6 @@ def transfer_buffers(planes, device=False):
     return buffers(planes, device, PtBakeTransferBuffers)
 
 
-# pt_bake_light: PtBakeLightBuffers' fields, in this order
-LIGHT_PLANES = ("owner", "position", "normal", "light_w")
-LIGHT_CHANNELS = {"owner": 1, "position": 3, "normal": 3, "light_w": 4}
-LIGHT_DTYPES = {"owner": "uint32", "position": "float32", "normal": "float32", "light_w": "float32"}
-
-
 class PtBakeLightParams(C.Structure):
     _fields_ = [("width", u32), ("height", u32), ("spp", u32), ("nsamples", u32), ("sampler_type", u32), ("spp_per_pass", u32), ("profile", u32)]
 
@@ -64,6 +67,8 @@ def light_buffers(planes, device=False):
     """The PtBakeLightBuffers of {plane: array or device pointer}, as buffers()."""
     return buffers(planes, device, PtBakeLightBuffers)
 
+
+BUFFERS = {"bake": PtBakeBuffers, "transfer": PtBakeTransferBuffers, "light": PtBakeLightBuffers}
 
 # pt_bake_sh: 28 sums per point in sh_w (27 = coefficient q, channel c at 3 q + c; the count of arrived samples), 27 coefficients per point resolved
 SH_SUMS = 28

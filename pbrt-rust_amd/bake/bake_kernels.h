@@ -1,26 +1,23 @@
-// bake_kernels.h -- the kernels of the texture-space bake (include/mi355bake.h, where the contract stands operation by operation). The any-hit walk of the AO
-// rays (k_trace) is libmi355pt's; this file is the front of the pipe and its end:
-//   k_bake_top      marks the primitives of the top-level accelerator (a primitive of an instanced object is no bake target)
-//   k_bake_raster   selected triangles -> atomicMin on the owner map
-//   k_bake_points   one thread per texel: the owner's interaction -> position and shading normal
-//   k_bake_rays     one texel sample per thread: one chunk of its AO rays (side/ao_rays.h: the rays libmi355ao spawns from a camera hit)
-//   k_bake_accum    ao_w += the unoccluded rays' wi and w, in element order
-//   k_bake_dilate   one iteration of the gutter fill
-//   k_bake_probe    pt_bake_rays: single rays by ao_ray, the function k_bake_rays' rays come from
-// and, for the transfer bake (pt_bake_transfer: another scene projected onto the atlas; the closest-hit walk of the projection rays is libmi355pt's k_trace too):
-//   k_bake_project          one lane per slot of a slice of the tile order: the projection ray of an owned texel
-//   k_bake_transfer_points  one thread per texel of the slice: the hit classified -> hit_prim, height, the three vector planes, the hit record of the AO passes
-//   k_bake_transfer_rays    k_bake_rays from the source hit (k_bake_accum adds them, with the detail-hit map in the owner map's place)
-//   k_bake_transfer_probe   pt_bake_transfer_rays: single projection and AO rays by the functions the kernels above use
-// and, for the lightmap (pt_bake_light: the scene's lights sampled from every texel; the any-hit walk of the shadow rays is libmi355pt's k_trace once more):
-//   k_bake_light_rays<SPH>   one texel sample per lane: one chunk of its light samples -> the shadow rays of those that contribute, and what each would add
-//   k_bake_light_accum       light_w += the unoccluded samples' E and 1, in element order
-//   k_bake_light_probe<SPH>  pt_bake_light_rays: single light samples by light_ray, the function k_bake_light_rays' rays come from
-// and, for the SH points (pt_bake_sh: the lights sampled from free points in space and projected onto the nine order-2 spherical harmonics):
-//   k_bake_sh_rays<SPH>      one point sample per lane: k_bake_light_rays from a point without surface -> the shadow rays, what each would add, and its wi
-//   k_bake_sh_accum          sh_w += E * Y_q(wi) and 1 of the unoccluded samples, in element order
-//   k_bake_sh_probe<SPH>     pt_bake_sh_rays: single light samples by sh_ray, the function k_bake_sh_rays' rays come from
-// No atomics other than the owner map's atomicMin and the per-wave ray-id reservation (wave_reserve; k_bake_light_rays' and k_bake_sh_rays' own, one for several elements).
+// bake_kernels.h -- the kernels of libmi355bake.so (include/mi355bake.h, where the contract stands operation by operation). The walks of their rays (k_trace, any-hit
+// and closest-hit) are libmi355pt's; this file is the front of the pipe and its end. Kernels are thin: what two of them do alike is a force-inlined body, written once.
+// Every atlas call:
+//   k_bake_top, k_bake_check  the primitives of the top-level accelerator (a primitive of an instanced object is no bake target); why a selected primitive is none
+//   k_bake_raster             selected triangles -> atomicMin on the owner map
+//   k_bake_points             one thread per texel: the owner's interaction (texel_interaction) -> position and shading normal
+//   k_bake_covered, k_bake_dilate<CH>   pt_bake_dilate: the gutter fill, one iteration per launch
+// The ray kernels, one item (a texel sample, a point sample) per lane, a wave = an 8 x 8 tile or 64 points of ONE sample number:
+//   ao_chunk_rays      the body of k_bake_rays (from the owner's interaction) and k_bake_transfer_rays (from the source hit; ray_surface tells them apart): one
+//                      reservation of kn ray ids per wave (wave_reserve), the base, ao_ray (side/ao_rays.h: the rays libmi355ao spawns from a camera hit) per element
+//   light_group_rays   the body of k_bake_light_rays<SPH> (light_ray: Light::sample_li, cosine and side test) and k_bake_sh_rays<SPH> (sh_ray: from a point without
+//                      surface; the ray's wi is kept): the wave-uniform light index, kLightGroup samples in registers, ONE reservation per group, the id table
+// The accumulate kernels, one thread per texel or point, additions in (sample, element) order:
+//   k_bake_accum       ao_w += the unoccluded rays' wi and w (the transfer bake's too, with the detail-hit map in the owner map's place)
+//   k_bake_light_accum light_w += {E, 1}        k_bake_sh_accum   sh_w += {E * Y_q(wi), 1}, the basis evaluated here
+// The transfer bake's projection (`t`: the scene whose atlas is filled, `s`: the scene the rays see):
+//   k_bake_project, k_bake_transfer_points   the projection ray of an owned texel; its hit classified -> hit_prim, height, the three vector planes, the hit record
+// The probes (pt_bake_*_rays), single queries by the functions the ray kernels call:
+//   k_bake_probe, k_bake_transfer_probe, k_bake_light_probe<SPH>, k_bake_sh_probe<SPH>; the two light probes leave one row (store_light_row)
+// No atomics other than the owner map's atomicMin and the per-wave ray-id reservations.
 #pragma once
 #include "../csrc/kern_decl.h"
 #include "../side/ao_rays.h"
@@ -184,33 +181,43 @@ __global__ __launch_bounds__(256) void k_bake_points(DeviceScene s, BakeAtlas a,
     if (normal) { normal[3 * (size_t)texel] = n.x; normal[3 * (size_t)texel + 1] = n.y; normal[3 * (size_t)texel + 2] = n.z; }
 }
 
-// Per texel sample of the pass (item = sample-in-pass * slots + slot: the lanes of a wave are neighbouring texels of one sample): this chunk's AO rays
+// Where a texel's AO rays leave: the owner's interaction at the texel's centre
+PT_DEV AOFrame ray_surface(const DeviceScene &s, const BakeAtlas &a, const BakeJob &, uint32_t texel, uint32_t prim, SurfaceInteraction &si) { texel_interaction(s, a, texel, prim, si); return bake_frame(si); }
+
+// The body of k_bake_rays and k_bake_transfer_rays, per texel sample of the pass (item = sample-in-pass * slots + slot: the lanes of a wave are neighbouring texels of
+// one sample; the kernels round the items up to whole waves, since there is one ray-id reservation per wave): this chunk's AO rays of sample `sl` of `texel`, whose
+// job.owner entry `mark` is PT_NONE where it has no surface point. ray_surface(s, a, job, texel, mark, si) -- the job type's -- fills the interaction the rays leave
+// and returns their frame. (The item loop stays in the kernels: under a kernel's launch bounds the index arithmetic compiles as it did.)
+template <class Job>
+PT_DEV void ao_chunk_rays(const DeviceScene &s, const RenderConst &rc, const SobolTables &tabs, const BakeAtlas &a, const Job &job, uint32_t total, uint32_t item, uint32_t texel, uint32_t sl, uint32_t mark) {
+    const bool found = mark != PT_NONE;
+    // one atomic per wave: the wave's owned texels take consecutive blocks of kn ray ids, in lane order
+    const uint32_t first = wave_reserve(job.ray_count, found, job.kn);
+    if (item >= total) return;
+    if (!found) { job.base[item] = PT_NONE; return; }
+    job.base[item] = first;
+    SurfaceInteraction si;
+    const AOFrame f = ray_surface(s, a, job, texel, mark, si);
+    const int32_t px = (int32_t)(texel % a.width), py = (int32_t)(texel / a.width);
+    const uint64_t sample = (uint64_t)job.s_begin + sl;
+    const float nsf = (float)job.nsamples;
+    for (uint32_t kk = 0; kk < job.kn; ++kk) {
+        V3 o, wo; float w;
+        ao_ray(rc, tabs, si, f, px, py, sample * job.nsamples + job.k0 + kk, job.cos_sample, nsf, o, wo, w);
+        const uint32_t id = first + kk;
+        job.ray[2 * (size_t)id] = make_float4(o.x, o.y, o.z, wo.x);
+        job.ray[2 * (size_t)id + 1] = make_float4(wo.y, wo.z, 0.0f, 0.0f);
+        job.w[id] = w;
+    }
+}
+
 __global__ __launch_bounds__(256) void k_bake_rays(DeviceScene s, RenderConst rc, SobolTables tabs, BakeAtlas a, BakeJob job) {
     const uint32_t total = a.slots * job.s_count;
-    const uint32_t rounded = (total + 63u) & ~63u;   // whole waves iterate together (one ray-id reservation per wave)
+    const uint32_t rounded = (total + 63u) & ~63u;
     for (uint32_t item = blockIdx.x * blockDim.x + threadIdx.x; item < rounded; item += gridDim.x * blockDim.x) {
         uint32_t texel = PT_NONE, sl = 0, prim = PT_NONE;
         if (item < total) { texel = slot_texel(a, item % a.slots); sl = item / a.slots; if (texel != PT_NONE) prim = job.owner[texel]; }
-        const bool found = prim != PT_NONE;
-        // one atomic per wave: the wave's owned texels take consecutive blocks of kn ray ids, in lane order
-        const uint32_t first = wave_reserve(job.ray_count, found, job.kn);
-        if (item >= total) continue;
-        if (!found) { job.base[item] = PT_NONE; continue; }
-        job.base[item] = first;
-        SurfaceInteraction si;
-        texel_interaction(s, a, texel, prim, si);
-        const AOFrame f = bake_frame(si);
-        const int32_t px = (int32_t)(texel % a.width), py = (int32_t)(texel / a.width);
-        const uint64_t sample = (uint64_t)job.s_begin + sl;
-        const float nsf = (float)job.nsamples;
-        for (uint32_t kk = 0; kk < job.kn; ++kk) {
-            V3 o, wo; float w;
-            ao_ray(rc, tabs, si, f, px, py, sample * job.nsamples + job.k0 + kk, job.cos_sample, nsf, o, wo, w);
-            const uint32_t id = first + kk;
-            job.ray[2 * (size_t)id] = make_float4(o.x, o.y, o.z, wo.x);
-            job.ray[2 * (size_t)id + 1] = make_float4(wo.y, wo.z, 0.0f, 0.0f);
-            job.w[id] = w;
-        }
+        ao_chunk_rays(s, rc, tabs, a, job, total, item, texel, sl, prim);
     }
 }
 
@@ -373,30 +380,14 @@ __global__ __launch_bounds__(256) void k_bake_transfer_points(DeviceScene t, Dev
 
 // k_bake_rays from the source hits: job.owner is the detail-hit map, rec the hits
 struct TransferJob : BakeJob { const float4 *rec; };
+PT_DEV AOFrame ray_surface(const DeviceScene &s, const BakeAtlas &, const TransferJob &job, uint32_t texel, uint32_t detail, SurfaceInteraction &hs) { return transfer_hit(s, job.rec[texel], detail != 0u, hs); }
 __global__ __launch_bounds__(256) void k_bake_transfer_rays(DeviceScene s, RenderConst rc, SobolTables tabs, BakeAtlas a, TransferJob job) {
     const uint32_t total = a.slots * job.s_count;
-    const uint32_t rounded = (total + 63u) & ~63u;   // whole waves iterate together (one ray-id reservation per wave)
+    const uint32_t rounded = (total + 63u) & ~63u;
     for (uint32_t item = blockIdx.x * blockDim.x + threadIdx.x; item < rounded; item += gridDim.x * blockDim.x) {
         uint32_t texel = PT_NONE, sl = 0, detail = PT_NONE;
         if (item < total) { texel = slot_texel(a, item % a.slots); sl = item / a.slots; if (texel != PT_NONE) detail = job.owner[texel]; }
-        const bool found = detail != PT_NONE;
-        const uint32_t first = wave_reserve(job.ray_count, found, job.kn);
-        if (item >= total) continue;
-        if (!found) { job.base[item] = PT_NONE; continue; }
-        job.base[item] = first;
-        SurfaceInteraction hs;
-        const AOFrame f = transfer_hit(s, job.rec[texel], detail != 0u, hs);
-        const int32_t px = (int32_t)(texel % a.width), py = (int32_t)(texel / a.width);
-        const uint64_t sample = (uint64_t)job.s_begin + sl;
-        const float nsf = (float)job.nsamples;
-        for (uint32_t kk = 0; kk < job.kn; ++kk) {
-            V3 o, wo; float w;
-            ao_ray(rc, tabs, hs, f, px, py, sample * job.nsamples + job.k0 + kk, job.cos_sample, nsf, o, wo, w);
-            const uint32_t id = first + kk;
-            job.ray[2 * (size_t)id] = make_float4(o.x, o.y, o.z, wo.x);
-            job.ray[2 * (size_t)id + 1] = make_float4(wo.y, wo.z, 0.0f, 0.0f);
-            job.w[id] = w;
-        }
+        ao_chunk_rays(s, rc, tabs, a, job, total, item, texel, sl, detail);
     }
 }
 
@@ -434,17 +425,22 @@ __global__ __launch_bounds__(256) void k_bake_transfer_probe(DeviceScene t, Devi
 
 // ---- the lightmap (mi355bake.h "Lightmap")
 
-// One chunk of light samples of the texel samples [s_begin, s_begin + s_count): AOChunk's ray records and flags (w is not used), and per ray what it adds when it
-// arrives. Not every sample spawns a ray: id[kk * items + item] is the ray id of element k0 + kk of the item, PT_NONE for a sample that contributes nothing.
-struct LightJob : AOChunk {
-    uint32_t s_begin, s_count;
-    const uint32_t *owner;   // [texels]
-    float4 *light_w;         // [texels]
+// One chunk of light samples of the samples [s_begin, s_begin + s_count) of every item (a texel, a point): AOChunk's ray records and flags (w is not used), and per
+// ray what it adds when it arrives. Not every sample spawns a ray: id[kk * items + item] is the ray id of element k0 + kk of the item, PT_NONE for a sample that
+// contributes nothing. `LightSamples light` is what the lightmap's and the SH points' jobs hold alike: a member, since as a base ahead of the other fields it moved the
+// kernel arguments and with them k_bake_light_rays' register traffic (profiles/r6/NOTES.md section 23).
+struct LightSamples {
     const uint32_t *sel;     // [n_sel]: the selected lights, ascending
     uint32_t n_sel;
     float scale;             // (float)n_sel / (float)nsamples
     uint32_t *id;            // [kn][items]
     float4 *e;               // [rays]: {E.rgb, 1}
+};
+struct LightJob : AOChunk {
+    uint32_t s_begin, s_count;
+    const uint32_t *owner;   // [texels]
+    float4 *light_w;         // [texels]
+    LightSamples light;
 };
 
 // The reference point of a texel's light samples (contract step 1) and the normalised shading normal
@@ -468,9 +464,57 @@ PT_DEV bool light_ray(const DeviceScene &s, const RenderConst &rc, const SobolTa
     return true;
 }
 
-// Per texel sample of the pass (item = sample-in-pass * slots + slot, as k_bake_rays): this chunk's light samples. A wave is one 8 x 8 tile of ONE sample number, so the
-// sample number j of an element, and with it the light sel[j mod n_sel], is the same for all 64 lanes: the index goes through readfirstlane and the light's record and
-// PtLight are fetched by scalar loads, once per wave. One ray-id reservation per wave per kLightGroup elements, for the lanes whose samples contribute.
+// The body of k_bake_light_rays and k_bake_sh_rays: this chunk's light samples of item `item` of `total`, sample `sl` of the pass. A wave is 64 items (an 8 x 8 tile,
+// 64 consecutive points) of ONE sample number, so the sample number j of an element, and with it the light sel[j mod n_sel], is the same for all 64 lanes: the index
+// goes through readfirstlane and the light's record and PtLight are fetched by scalar loads, once per wave. Every lane of the wave is here; one without surface or
+// point (`found` false) takes part in the ballots and spawns nothing. `sample(j, li, wi, E, o, d)` is sample number j of the item on light li (light_ray, sh_ray);
+// `store(id, wi)` writes what the caller keeps of ray `id` besides the records here (the SH points: wi; the lightmap: nothing, and its wi registers are dead).
+// kLightGroup elements at a time: their rays wait in registers for ONE reservation of the wave, for the lanes whose samples contribute -- a single counter sustains
+// ~88 returning atomics per microsecond (MI355X_MICROARCH.md), and one per element made the kernel wait for the counter (2048^2 x 16 x 3 samples: 30.3 ms;
+// k_bake_rays, one per item, 13.2 ms)
+template <class Job, class Sample, class Store>
+PT_DEV void light_group_rays(const Job &job, uint32_t total, uint32_t item, uint32_t sl, bool found, const Sample &sample, const Store &store) {
+    const uint64_t j0 = ((uint64_t)job.s_begin + sl) * job.nsamples + job.k0;
+    uint32_t r = (uint32_t)(j0 % job.light.n_sel);
+    for (uint32_t kk = 0; kk < job.kn; kk += kLightGroup) {
+        V3 o[kLightGroup], d[kLightGroup], wi[kLightGroup]; RGB E[kLightGroup];
+        unsigned long long rays[kLightGroup];   // per element: the lanes whose sample contributes
+        uint32_t n_rays = 0;
+#pragma unroll
+        for (uint32_t g = 0; g < kLightGroup; ++g) {
+            bool ray = false;
+            if (kk + g < job.kn) {
+                const uint32_t li = (uint32_t)__builtin_amdgcn_readfirstlane((int)job.light.sel[r]);
+                r = r + 1u == job.light.n_sel ? 0u : r + 1u;
+                if (found) ray = sample(j0 + kk + g, li, wi[g], E[g], o[g], d[g]);
+            }
+            rays[g] = __ballot(ray);
+            n_rays += (uint32_t)__popcll(rays[g]);
+        }
+        // ids: the group's elements one after the other, each in lane order (lane 0 asks)
+        uint32_t base = 0;
+        if (n_rays != 0u) {
+            if (lane_id() == 0u) base = atomicAdd(job.ray_count, n_rays);
+            base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+        }
+        const unsigned long long below = (1ull << lane_id()) - 1ull;
+#pragma unroll
+        for (uint32_t g = 0; g < kLightGroup; ++g) {
+            if (kk + g >= job.kn) break;
+            const bool ray = ((rays[g] >> lane_id()) & 1ull) != 0ull;
+            const uint32_t id = base + (uint32_t)__popcll(rays[g] & below);
+            base += (uint32_t)__popcll(rays[g]);
+            job.light.id[(size_t)(kk + g) * total + item] = ray ? id : PT_NONE;
+            if (!ray) continue;
+            job.ray[2 * (size_t)id] = make_float4(o[g].x, o[g].y, o[g].z, d[g].x);
+            job.ray[2 * (size_t)id + 1] = make_float4(d[g].y, d[g].z, 0.0f, 0.0f);
+            job.light.e[id] = make_float4(E[g].r, E[g].g, E[g].b, 1.0f);
+            store(id, wi[g]);
+        }
+    }
+}
+
+// Per texel sample of the pass (item = sample-in-pass * slots + slot, as k_bake_rays): this chunk's light samples from the owner's interaction at the texel's centre
 template <bool SPH>
 __global__ __launch_bounds__(256) void k_bake_light_rays(DeviceScene s, RenderConst rc, SobolTables tabs, BakeAtlas a, LightJob job) {
     const uint32_t total = a.slots * job.s_count;   // (a multiple of 64: whole waves)
@@ -487,46 +531,9 @@ __global__ __launch_bounds__(256) void k_bake_light_rays(DeviceScene s, RenderCo
             ref = light_ref(si, ns);
         }
         const int32_t px = found ? (int32_t)(texel % a.width) : 0, py = found ? (int32_t)(texel / a.width) : 0;
-        const uint64_t j0 = ((uint64_t)job.s_begin + sl) * job.nsamples + job.k0;
-        uint32_t r = (uint32_t)(j0 % job.n_sel);
-        // kLightGroup elements at a time: their rays wait in registers for ONE reservation of the wave -- a single counter sustains ~88 returning atomics per microsecond
-        // (MI355X_MICROARCH.md), and one per element made the kernel wait for the counter (2048^2 x 16 x 3 samples: 30.3 ms; k_bake_rays, one per item, 13.2 ms)
-        for (uint32_t kk = 0; kk < job.kn; kk += kLightGroup) {
-            V3 o[kLightGroup], d[kLightGroup]; RGB E[kLightGroup];
-            unsigned long long rays[kLightGroup];   // per element: the lanes whose sample contributes
-            uint32_t n_rays = 0;
-#pragma unroll
-            for (uint32_t g = 0; g < kLightGroup; ++g) {
-                bool ray = false;
-                if (kk + g < job.kn) {
-                    const uint32_t li = (uint32_t)__builtin_amdgcn_readfirstlane((int)job.sel[r]);
-                    r = r + 1u == job.n_sel ? 0u : r + 1u;
-                    V3 wi; float pdf; RGB Li;
-                    if (found) ray = light_ray<SPH>(s, rc, tabs, ref, ns, px, py, j0 + kk + g, li, job.scale, wi, pdf, Li, E[g], o[g], d[g]);
-                }
-                rays[g] = __ballot(ray);
-                n_rays += (uint32_t)__popcll(rays[g]);
-            }
-            // ids: the group's elements one after the other, each in lane order (every lane of the wave is here: lane 0 asks)
-            uint32_t base = 0;
-            if (n_rays != 0u) {
-                if (lane_id() == 0u) base = atomicAdd(job.ray_count, n_rays);
-                base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-            }
-            const unsigned long long below = (1ull << lane_id()) - 1ull;
-#pragma unroll
-            for (uint32_t g = 0; g < kLightGroup; ++g) {
-                if (kk + g >= job.kn) break;
-                const bool ray = ((rays[g] >> lane_id()) & 1ull) != 0ull;
-                const uint32_t id = base + (uint32_t)__popcll(rays[g] & below);
-                base += (uint32_t)__popcll(rays[g]);
-                job.id[(size_t)(kk + g) * total + item] = ray ? id : PT_NONE;
-                if (!ray) continue;
-                job.ray[2 * (size_t)id] = make_float4(o[g].x, o[g].y, o[g].z, d[g].x);
-                job.ray[2 * (size_t)id + 1] = make_float4(d[g].y, d[g].z, 0.0f, 0.0f);
-                job.e[id] = make_float4(E[g].r, E[g].g, E[g].b, 1.0f);
-            }
-        }
+        light_group_rays(job, total, item, sl, found,
+                         [&](uint64_t j, uint32_t li, V3 &wi, RGB &E, V3 &o, V3 &d) { float pdf; RGB Li; return light_ray<SPH>(s, rc, tabs, ref, ns, px, py, j, li, job.light.scale, wi, pdf, Li, E, o, d); },
+                         [](uint32_t, V3) {});
     }
 }
 
@@ -539,17 +546,24 @@ __global__ __launch_bounds__(256) void k_bake_light_accum(BakeAtlas a, LightJob 
     float4 acc = job.light_w[texel];
     for (uint32_t sl = 0; sl < job.s_count; ++sl) {
         for (uint32_t kk = 0; kk < job.kn; ++kk) {
-            const uint32_t id = job.id[(size_t)kk * total + (size_t)sl * a.slots + slot];
+            const uint32_t id = job.light.id[(size_t)kk * total + (size_t)sl * a.slots + slot];
             if (id == PT_NONE || job.occluded[id]) continue;
-            const float4 e = job.e[id];
+            const float4 e = job.light.e[id];
             acc.x += e.x; acc.y += e.y; acc.z += e.z; acc.w += e.w;
         }
     }
     job.light_w[texel] = acc;
 }
 
-// pt_bake_light_rays: query i = element[i] of sample[i] of texel[i], by light_ray. out: 16 floats per query {wi, pdf, Li, E, o, d}; found: bit 0 the texel has
-// an owner, bit 1 the sample contributes (its shadow ray is {o, d})
+// What a light probe leaves of query i: 16 floats {wi, pdf, Li, E, o, d}, the light, and found -- bit 0 the item exists, bit 1 the sample contributes (its shadow ray is {o, d})
+PT_DEV void store_light_row(uint32_t i, uint32_t li, uint32_t bits, V3 wi, float pdf, RGB Li, RGB E, V3 o, V3 d, uint32_t *out_light, float *out, uint8_t *found) {
+    float *r = out + 16 * (size_t)i;
+    r[0] = wi.x; r[1] = wi.y; r[2] = wi.z; r[3] = pdf; r[4] = Li.r; r[5] = Li.g; r[6] = Li.b; r[7] = E.r; r[8] = E.g; r[9] = E.b;
+    r[10] = o.x; r[11] = o.y; r[12] = o.z; r[13] = d.x; r[14] = d.y; r[15] = d.z;
+    out_light[i] = li; found[i] = (uint8_t)bits;
+}
+
+// pt_bake_light_rays: query i = element[i] of sample[i] of texel[i], by light_ray (store_light_row; bit 0: the texel has an owner)
 template <bool SPH>
 __global__ __launch_bounds__(256) void k_bake_light_probe(DeviceScene s, RenderConst rc, SobolTables tabs, BakeAtlas a, const uint32_t *owner, uint32_t nsamples, const uint32_t *sel, uint32_t n_sel,
                                                           float scale, uint32_t n, const uint32_t *texel, const uint32_t *sample, const uint32_t *element, uint32_t *out_light, float *out, uint8_t *found) {
@@ -567,32 +581,27 @@ __global__ __launch_bounds__(256) void k_bake_light_probe(DeviceScene s, RenderC
         V3 ns; const IData ref = light_ref(si, ns);
         bits = light_ray<SPH>(s, rc, tabs, ref, ns, (int32_t)(tx % a.width), (int32_t)(tx / a.width), j, li, scale, wi, pdf, Li, E, o, d) ? 3u : 1u;
     }
-    float *r = out + 16 * (size_t)i;
-    r[0] = wi.x; r[1] = wi.y; r[2] = wi.z; r[3] = pdf; r[4] = Li.r; r[5] = Li.g; r[6] = Li.b; r[7] = E.r; r[8] = E.g; r[9] = E.b;
-    r[10] = o.x; r[11] = o.y; r[12] = o.z; r[13] = d.x; r[14] = d.y; r[15] = d.z;
-    out_light[i] = li; found[i] = (uint8_t)bits;
+    store_light_row(i, li, bits, wi, pdf, Li, E, o, d, out_light, out, found);
 }
 
 // ---- the SH points (mi355bake.h "SH points")
 
 // One chunk of light samples of the point samples [s_begin, s_begin + s_count) of n_points points. A sample number's items are the points padded to whole waves
-// (`padded`, a multiple of 64): item = sample-in-pass * padded + point. LightJob's records, and per ray the wi its basis is evaluated with where the sums are made.
+// (`padded`, a multiple of 64): item = sample-in-pass * padded + point. LightSamples' records, and per ray the wi its basis is evaluated with where the sums are made.
 struct ShJob : AOChunk {
     uint32_t s_begin, s_count;
     uint32_t n_points, padded, row;
     const float *points;     // [n_points][3]
     float4 *sh_w;            // [n_points][7]: 27 sums (coefficient q, channel c at 3 q + c) and the count of arrived samples
-    const uint32_t *sel;     // [n_sel]: the selected lights, ascending
-    uint32_t n_sel;
-    float scale;             // (float)n_sel / (float)nsamples
-    uint32_t *id;            // [kn][items]
-    float4 *e;               // [rays]: {E.rgb, 1}
+    LightSamples light;
     float4 *wi;              // [rays]: {wi.xyz, -}
 };
 
 // Sample number j of point p, pixel (px, py), on light li (contract steps 1 and 3 to 5): light_ray from a reference point without surface -- a medium interaction's,
 // p_error = n = 0, so the shadow ray starts at p exactly --, without cosine and side test. false: the sample adds nothing and spawns no ray (E, o and d are zeros then).
-// (light_ray stands as it was: the two share ao_array_sample, light_sample_li and spawn_ray_to, and the lightmap's kernels keep their code.)
+// (Two functions on purpose. They share ao_array_sample, light_sample_li and spawn_ray_to; one light_sample<SPH, SURFACE> with the cosine ahead of the same || chain
+// was tried and left the four lightmap kernels as they are, but changed the code of all four SH kernels -- k_bake_sh_rays<false> 147 -> 149 VGPRs, the <true> probe
+// 79 -> 83 --, which the rule of profiles/r6/NOTES.md section 23 does not allow without timing them anew.)
 template <bool SPH>
 PT_DEV bool sh_ray(const DeviceScene &s, const RenderConst &rc, const SobolTables &tabs, V3 p, int32_t px, int32_t py, uint64_t j, uint32_t li, float scale,
                    V3 &wi, float &pdf, RGB &Li, RGB &E, V3 &o, V3 &d) {
@@ -622,9 +631,8 @@ PT_HD void sh_basis(float x, float y, float z, float Y[9]) {
     Y[8] = 0.546274f * ((x * x) - (y * y));
 }
 
-// Per point sample of the pass: this chunk's light samples. k_bake_light_rays with a wave of 64 consecutive points of ONE sample number in the tile's place: the light
-// index is wave-uniform and goes through readfirstlane, one ray-id reservation per wave per kLightGroup elements. Lanes beyond n_points take part in the ballots and
-// spawn nothing.
+// Per point sample of the pass: this chunk's light samples, with a wave of 64 consecutive points of ONE sample number in the tile's place; a ray's wi is kept beside
+// what it adds. Lanes beyond n_points have no point.
 template <bool SPH>
 __global__ __launch_bounds__(256) void k_bake_sh_rays(DeviceScene s, RenderConst rc, SobolTables tabs, ShJob job) {
     const uint32_t total = job.padded * job.s_count;   // (a multiple of 64: whole waves)
@@ -635,44 +643,9 @@ __global__ __launch_bounds__(256) void k_bake_sh_rays(DeviceScene s, RenderConst
         V3 p(0.0f, 0.0f, 0.0f);
         if (found) p = V3(job.points[3 * (size_t)point], job.points[3 * (size_t)point + 1], job.points[3 * (size_t)point + 2]);
         const int32_t px = found ? (int32_t)(point % job.row) : 0, py = found ? (int32_t)(point / job.row) : 0;
-        const uint64_t j0 = ((uint64_t)job.s_begin + sl) * job.nsamples + job.k0;
-        uint32_t r = (uint32_t)(j0 % job.n_sel);
-        for (uint32_t kk = 0; kk < job.kn; kk += kLightGroup) {   // (one reservation per group: see k_bake_light_rays)
-            V3 o[kLightGroup], d[kLightGroup], wi[kLightGroup]; RGB E[kLightGroup];
-            unsigned long long rays[kLightGroup];   // per element: the lanes whose sample contributes
-            uint32_t n_rays = 0;
-#pragma unroll
-            for (uint32_t g = 0; g < kLightGroup; ++g) {
-                bool ray = false;
-                if (kk + g < job.kn) {
-                    const uint32_t li = (uint32_t)__builtin_amdgcn_readfirstlane((int)job.sel[r]);
-                    r = r + 1u == job.n_sel ? 0u : r + 1u;
-                    float pdf; RGB Li;
-                    if (found) ray = sh_ray<SPH>(s, rc, tabs, p, px, py, j0 + kk + g, li, job.scale, wi[g], pdf, Li, E[g], o[g], d[g]);
-                }
-                rays[g] = __ballot(ray);
-                n_rays += (uint32_t)__popcll(rays[g]);
-            }
-            uint32_t base = 0;
-            if (n_rays != 0u) {
-                if (lane_id() == 0u) base = atomicAdd(job.ray_count, n_rays);
-                base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-            }
-            const unsigned long long below = (1ull << lane_id()) - 1ull;
-#pragma unroll
-            for (uint32_t g = 0; g < kLightGroup; ++g) {
-                if (kk + g >= job.kn) break;
-                const bool ray = ((rays[g] >> lane_id()) & 1ull) != 0ull;
-                const uint32_t id = base + (uint32_t)__popcll(rays[g] & below);
-                base += (uint32_t)__popcll(rays[g]);
-                job.id[(size_t)(kk + g) * total + item] = ray ? id : PT_NONE;
-                if (!ray) continue;
-                job.ray[2 * (size_t)id] = make_float4(o[g].x, o[g].y, o[g].z, d[g].x);
-                job.ray[2 * (size_t)id + 1] = make_float4(d[g].y, d[g].z, 0.0f, 0.0f);
-                job.e[id] = make_float4(E[g].r, E[g].g, E[g].b, 1.0f);
-                job.wi[id] = make_float4(wi[g].x, wi[g].y, wi[g].z, 0.0f);
-            }
-        }
+        light_group_rays(job, total, item, sl, found,
+                         [&](uint64_t j, uint32_t li, V3 &wi, RGB &E, V3 &o, V3 &d) { float pdf; RGB Li; return sh_ray<SPH>(s, rc, tabs, p, px, py, j, li, job.light.scale, wi, pdf, Li, E, o, d); },
+                         [&](uint32_t id, V3 wi) { job.wi[id] = make_float4(wi.x, wi.y, wi.z, 0.0f); });
     }
 }
 
@@ -694,7 +667,7 @@ __global__ __launch_bounds__(256) void k_bake_sh_accum(ShJob job) {
         uint32_t id[kShAhead]; bool arrived[kShAhead]; float4 e[kShAhead], w[kShAhead];
 #pragma unroll
         for (uint32_t g = 0; g < kShAhead; ++g) {
-            id[g] = t0 + g < steps ? job.id[(size_t)kk * total + (size_t)sl * job.padded + point] : PT_NONE;
+            id[g] = t0 + g < steps ? job.light.id[(size_t)kk * total + (size_t)sl * job.padded + point] : PT_NONE;
             if (++kk == job.kn) { kk = 0; ++sl; }
         }
 #pragma unroll
@@ -702,7 +675,7 @@ __global__ __launch_bounds__(256) void k_bake_sh_accum(ShJob job) {
 #pragma unroll
         for (uint32_t g = 0; g < kShAhead; ++g) {
             e[g] = w[g] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (arrived[g]) { e[g] = job.e[id[g]]; w[g] = job.wi[id[g]]; }
+            if (arrived[g]) { e[g] = job.light.e[id[g]]; w[g] = job.wi[id[g]]; }
         }
 #pragma unroll
         for (uint32_t g = 0; g < kShAhead; ++g) {
@@ -717,8 +690,7 @@ __global__ __launch_bounds__(256) void k_bake_sh_accum(ShJob job) {
     for (uint32_t g = 0; g < 7; ++g) out[g] = make_float4(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]);
 }
 
-// pt_bake_sh_rays: query i = element[i] of sample[i] of point[i], by sh_ray. out: 16 floats per query {wi, pdf, Li, E, o, d}; found: bit 0 the point index is
-// below n_points, bit 1 the sample contributes (its shadow ray is {o, d})
+// pt_bake_sh_rays: query i = element[i] of sample[i] of point[i], by sh_ray (store_light_row; bit 0: the point index is below n_points)
 template <bool SPH>
 __global__ __launch_bounds__(256) void k_bake_sh_probe(DeviceScene s, RenderConst rc, SobolTables tabs, const float *points, uint32_t n_points, uint32_t row, uint32_t nsamples,
                                                        const uint32_t *sel, uint32_t n_sel, float scale, uint32_t n, const uint32_t *point, const uint32_t *sample, const uint32_t *element,
@@ -734,10 +706,7 @@ __global__ __launch_bounds__(256) void k_bake_sh_probe(DeviceScene s, RenderCons
         const V3 p(points[3 * (size_t)pt], points[3 * (size_t)pt + 1], points[3 * (size_t)pt + 2]);
         bits = sh_ray<SPH>(s, rc, tabs, p, (int32_t)(pt % row), (int32_t)(pt / row), j, li, scale, wi, pdf, Li, E, o, d) ? 3u : 1u;
     }
-    float *r = out + 16 * (size_t)i;
-    r[0] = wi.x; r[1] = wi.y; r[2] = wi.z; r[3] = pdf; r[4] = Li.r; r[5] = Li.g; r[6] = Li.b; r[7] = E.r; r[8] = E.g; r[9] = E.b;
-    r[10] = o.x; r[11] = o.y; r[12] = o.z; r[13] = d.x; r[14] = d.y; r[15] = d.z;
-    out_light[i] = li; found[i] = (uint8_t)bits;
+    store_light_row(i, li, bits, wi, pdf, Li, E, o, d, out_light, out, found);
 }
 
 }  // namespace ptbake

@@ -1,34 +1,29 @@
-// bake_render.hip -- pt_bake_render / pt_bake_render_samples / pt_bake_pass_size / pt_bake_resolve / pt_bake_dilate / pt_bake_rays (include/mi355bake.h): ambient
-// occlusion, bent normals, positions and shading normals of a UV-mapped mesh in its own texture space. Per call:
-//   k_bake_top, k_bake_check       which primitives the top-level accelerator holds; why a selected primitive is no bake target (one word per 256 of them comes back)
-//   k_bake_raster                  the selected triangles' owner map
-//   k_bake_points                  position / normal planes, when wanted
-//   per pass of S samples of every texel, per chunk of <= 64 AO rays per texel sample (ao_w wanted):
-//     k_bake_rays                  the chunk's rays from each owned texel (dimensions 5 and 6 of sample numbers s * nsamples + k)
-//     k_trace<any>                 the rays' any-hit walk ("shadow", t_max = max_distance) -- libmi355pt's
-//     k_bake_accum                 ao_w += the unoccluded rays' wi and w, in order
-// There is no camera, no path state and no film, so the bake does not go through render_frame: the scene's stream, counters and traversal spill area come from
-// ensure_workspace with no paths and no film, the pass size from choose_pass_size with the bake's bytes per texel sample, the sampler set-up from fill_render_const
-// for a width x height image, the traversal through trace_job / trace_sub / traced as libmi355ao's AO rays go.
-// pt_bake_transfer / _samples / _pass_size / _rays project a SOURCE scene onto the atlas of a TARGET scene's mesh. Per call, after the target's selection and owner map:
-//   k_bake_top (source)            which source primitives are top-level: only their triangles are detail hits
-//   per slice of 8 x 8-texel tiles sized by the pass budget:
-//     k_bake_project               the projection ray of every owned texel
-//     k_trace<closest>             their closest-hit walk through the source ("extend", per-ray t_max = front + back) -- libmi355pt's
-//     k_bake_transfer_points       hit_prim, height, source position, world- and tangent-space normal; the hit records of the AO passes
-//   per pass and chunk (ao_w wanted): k_bake_transfer_rays, k_trace<any> through the source ("shadow"), k_bake_accum over the detail-hit map
-// pt_bake_light / _samples / _pass_size / _resolve / _rays bake the scene's lights into the atlas (mi355bake.h "Lightmap"). Per call, after the selection, the owner map and
-// the position / normal planes, per pass and chunk of <= 64 light samples per texel sample (light_w wanted):
-//     k_bake_light_rays<SPH>       Light::sample_li of the chunk's samples, the contribution test, the shadow rays of the samples that contribute and what each adds
-//     k_trace<any>                 the shadow rays' any-hit walk ("shadow", t_max = 1 - 0.0001: the render's) -- libmi355pt's
-//     k_bake_light_accum           light_w += {E, 1} of the samples that arrived, in order
-// The chunk loop is ao_chunks (LightJob begins with an AOChunk), the budget ao_ray_budget's plus 20 bytes per ray, SPH general_geometry's as the render chooses it.
-// pt_bake_sh / _samples / _pass_size / _resolve / _irradiance / _rays bake the scene's lights at free points into order-2 spherical harmonics (mi355bake.h "SH points").
-// There is no atlas, no selection and no owner map: the points are uploaded, a sample number's items are the points padded to whole waves. Per pass and chunk:
-//     k_bake_sh_rays<SPH>          the lightmap's light samples from a reference point without surface: the shadow rays, what each adds, and its wi
-//     k_trace<any>                 the same "shadow" walk
-//     k_bake_sh_accum              sh_w += {E * Y_q(wi), 1} of the samples that arrived, in order
-// The budget is ao_ray_budget's plus 36 bytes per ray.
+// bake_render.hip -- the entry points of include/mi355bake.h: four bakes (pt_bake_render: AO and bent normals, pt_bake_transfer: another scene projected onto the atlas,
+// pt_bake_light: the lightmap, pt_bake_sh: the lights at free points in order-2 spherical harmonics), each with its _samples, _pass_size and _rays (probe) forms, the
+// resolves and pt_bake_dilate. There is no camera, no path state and no film, so a bake does not go through render_frame: the scene's stream, counters and traversal spill
+// area come from ensure_workspace with no paths and no film, the sampler from fill_render_const for a width x height image (bake_geometry), the traversal goes through
+// trace_job / trace_sub / traced as libmi355ao's AO rays do. Every call is made of the same steps, each written once:
+//   the refusals          check_*: before the device or a handle is touched, in the header's order; then bake_geometry (bind_device, sampler, pass size), begin_call
+//   Staging               a plane on the device: the caller's device pointer, or a temporary that is uploaded where it is added to (the *_w sums) and copied home by
+//                         finish() -- after end_call, so a call that fails midway writes no host plane; the temporaries go when the call returns
+//   atlas_frame           upload_selection (k_bake_top, k_bake_check: why a selected primitive is no bake target), the owner map (k_bake_raster), the position / normal
+//                         planes where wanted (k_bake_points). It takes the scene that is read and the scene the launches run on: a transfer's are target and source.
+//                         The SH points have no atlas: their points are uploaded instead (upload_points)
+//   for_passes            samples [first, first + n) in passes of S; a pass of several samples has ONE chunk (bake_geometry), so a texel's additions are in (s, k) order
+//   pass_chunks           one pass through ao_chunks (side_host.h), <= 64 rays per item and chunk: the bake's ray kernel, k_trace<any> ("shadow", libmi355pt's), the
+//                         bake's accumulate kernel -- bake_pass, transfer_pass, light_pass and sh_pass fill in their job and their two launches
+//   light_samples         the light-sample fields of the lightmap's and the SH points' jobs: selection, scale, id table, E records
+//   launch_sph            the <true> / <false> pair of the kernels that sample lights, SPH as the render chooses it
+//   upload_queries, check_queries, LightRows    a probe's three index arrays, their range check, and the 16-float row the two light probes leave
+// What is a bake's own:
+//   AO         k_bake_rays (dimensions 5 and 6 of sample numbers s * nsamples + k), t_max = max_distance, k_bake_accum: ao_w += the unoccluded rays' wi and w
+//   transfer   project(): k_bake_top of the source, then per slice of 8 x 8-texel tiles sized by the pass budget k_bake_project, k_trace<closest> ("extend", per-ray t_max =
+//              front + back), k_bake_transfer_points (hit_prim, height, source position, world- and tangent-space normal, the hit records); its slice records are freed
+//              before the AO passes allocate theirs. Then k_bake_transfer_rays and k_bake_accum over the detail-hit map. Counters and statistics are the source's
+//   lightmap   k_bake_light_rays<SPH> (Light::sample_li, the contribution test, the shadow rays of the samples that contribute and what each adds), t_max = 1 - 0.0001 as the
+//              render's shadow rays, k_bake_light_accum: light_w += {E, 1}. The budget is ao_ray_budget's plus 20 bytes per ray
+//   SH points  k_bake_sh_rays<SPH> (those samples from a point without surface, and each ray's wi), k_bake_sh_accum: sh_w += {E * Y_q(wi), 1}. A sample number's items are
+//              the points padded to whole waves; the budget is ao_ray_budget's plus 36 bytes per ray
 #include "../csrc/host_common.h"
 #include "../side/side_host.h"
 #include "../../include/mi355bake.h"
@@ -49,17 +44,28 @@ int check_atlas(uint32_t width, uint32_t height) {
     if ((size_t)width * height > kBakeMaxTexels) return fail(PT_ERR_INVALID_ARG, "bake: the atlas holds more than 2^28 texels");
     return PT_OK;
 }
+int check_spp(uint32_t spp) { return spp == 0 ? fail(PT_ERR_INVALID_ARG, "bake: spp must be > 0") : PT_OK; }
+int check_nsamples(uint32_t nsamples) { return nsamples == 0 ? fail(PT_ERR_INVALID_ARG, "bake: nsamples must be > 0") : PT_OK; }
+int check_sampler(uint32_t type) {
+    if (type != PT_SAMPLER_SOBOL && type != PT_SAMPLER_HALTON) return fail(PT_ERR_INVALID_ARG, "bake: sampler_type must be PT_SAMPLER_SOBOL or PT_SAMPLER_HALTON");
+    return PT_OK;
+}
 int check_params(const PtBakeParams *bp) {
     if (int st = check_atlas(bp->width, bp->height)) return st;
-    if (bp->spp == 0) return fail(PT_ERR_INVALID_ARG, "bake: spp must be > 0");
-    if (bp->nsamples == 0) return fail(PT_ERR_INVALID_ARG, "bake: nsamples must be > 0");
+    if (int st = check_spp(bp->spp)) return st;
+    if (int st = check_nsamples(bp->nsamples)) return st;
     if (!(bp->max_distance > 0.0f)) return fail(PT_ERR_INVALID_ARG, "bake: max_distance must be > 0 (INFINITY: unbounded)");
-    if (bp->sampler_type != PT_SAMPLER_SOBOL && bp->sampler_type != PT_SAMPLER_HALTON) return fail(PT_ERR_INVALID_ARG, "bake: sampler_type must be PT_SAMPLER_SOBOL or PT_SAMPLER_HALTON");
-    return PT_OK;
+    return check_sampler(bp->sampler_type);
 }
 int check_range(const PtBakeParams *bp, uint32_t first, uint32_t n) {
     if (n == 0) return fail(PT_ERR_INVALID_ARG, "bake: n_samples must be > 0");
     if ((uint64_t)first + n > bp->spp) return fail(PT_ERR_INVALID_ARG, "bake: sample range [" + std::to_string(first) + ", " + std::to_string((uint64_t)first + n) + ") exceeds the job's spp = " + std::to_string(bp->spp));
+    return PT_OK;
+}
+// The queries of a probe: every one names a sample and an element of the job
+int check_queries(uint32_t n, const uint32_t *sample, const uint32_t *element, uint32_t spp, uint32_t nsamples) {
+    for (uint32_t i = 0; i < n; ++i)
+        if (sample[i] >= spp || element[i] >= nsamples) return fail(PT_ERR_INVALID_ARG, "bake: ray " + std::to_string(i) + " names a sample or element outside the job");
     return PT_OK;
 }
 int check_selection(const uint8_t *prim_select, uint32_t n_prims) {
@@ -178,32 +184,106 @@ int raster(pt_scene *sc, const pt_scene *of, const BakeAtlas &a, const uint32_t 
     return PT_OK;
 }
 
-// The rays of one pass: samples [s_begin, s_begin + s_count) of every texel, chunk by chunk
-int bake_pass(pt_scene *sc, const Geometry &g, const PtBakeParams *bp, uint32_t s_begin, uint32_t s_count, const uint32_t *d_owner, float4 *d_ao, const AORayBuffers &b) {
-    const uint32_t items = g.atlas.slots * s_count;
-    const dim3 blocks = blocks_for(items, 16u);
-    auto spawn = [&](const BakeJob &job) {
-        sc->begin("bake_rays", (uint64_t)items * job.kn);
-        launch(sc, "ptbake::k_bake_rays", k_bake_rays, blocks, dim3(256), sc->ds, g.rc, g_tabs, g.atlas, job);
-        sc->end();
-    };
-    auto accum = [&](const BakeJob &job) {
-        sc->begin("bake_accum", items);
-        launch(sc, "ptbake::k_bake_accum", k_bake_accum, texel_grid(g.atlas), dim3(256), g.atlas, job);
-        sc->end();
-    };
-    BakeJob job{};
-    job.nsamples = bp->nsamples; job.cos_sample = bp->cos_sample ? 1u : 0u;
-    job.s_begin = s_begin; job.s_count = s_count; job.owner = d_owner; job.ao_w = d_ao;
-    return ao_chunks<BakeJob>(sc, job, g.K, items, bp->max_distance, b, spawn, accum);   // (t_max = max_distance)
-}
-
 int end_call(pt_scene *sc) {
     QCounters h;
     if (int st = sync_queue_counters(sc, h)) return st;   // (a status a kernel raised fails the call here)
     sc->resolve_timings();
     read_counters(sc);
     return PT_OK;
+}
+
+// ---- the call frame: what every bake and every probe is made of
+
+// The planes of a call on the device. A plane the caller did not ask for is NULL; one of a call with device buffers is the caller's pointer; one of a call with host
+// buffers is a temporary of `tmp` (freed when the call returns, however it ends: a bake leaves the device's free memory as it found it, apart from the scene's
+// workspace) that finish() copies home -- after end_call has succeeded, so a call that fails midway writes no host plane.
+struct Staging {
+    DevTmp &tmp; hipStream_t stream; bool dev;
+    struct Home { void *host; const void *device; size_t bytes; };
+    std::vector<Home> home;
+    // `upload`: the plane is added to (the *_w sums), so the temporary starts from what the caller's array holds
+    template <class D, class T> int plane(T *user, size_t bytes, const char *what, bool upload, D *&d) {
+        d = dev ? reinterpret_cast<D *>(user) : nullptr;
+        if (!user || dev) return PT_OK;
+        SIDE_ALLOC(tmp, d, bytes, what);
+        if (upload) HIP_TRY(hipMemcpyAsync(d, user, bytes, hipMemcpyHostToDevice, stream));
+        home.push_back(Home{user, d, bytes});
+        return PT_OK;
+    }
+    int finish(pt_scene *sc) {
+        if (int st = end_call(sc)) return st;
+        for (const Home &h : home) HIP_TRY(hipMemcpy(h.host, h.device, h.bytes, hipMemcpyDeviceToHost));
+        return PT_OK;
+    }
+};
+
+// The atlas part of a call: the selection of `of`'s primitives on the device, their owner map -- the caller's plane (Staging) or a temporary nobody reads back -- and,
+// where asked for, the position and normal planes. `of` is the scene that is read, `sc` the scene the launches run on (upload_selection).
+int atlas_frame(pt_scene *sc, const pt_scene *of, const BakeAtlas &a, const uint8_t *prim_select, uint32_t n_prims, Staging &out, uint32_t *owner, float *position, float *normal, uint32_t *&d_owner) {
+    const size_t n = a.n_texels;
+    uint32_t *d_selected = nullptr, n_selected = 0;
+    if (int st = upload_selection(sc, of, prim_select, n_prims, out.tmp, d_selected, n_selected)) return st;
+    if (int st = out.plane(owner, n * 4, "bake owner map", false, d_owner)) return st;
+    if (!d_owner) SIDE_ALLOC(out.tmp, d_owner, n * 4, "bake owner map");
+    if (int st = raster(sc, of, a, d_selected, n_selected, d_owner)) return st;
+    if (!position && !normal) return PT_OK;
+    float *d_pos = nullptr, *d_nrm = nullptr;
+    if (int st = out.plane(position, n * 12, "bake position plane", false, d_pos)) return st;
+    if (int st = out.plane(normal, n * 12, "bake normal plane", false, d_nrm)) return st;
+    sc->begin("bake_points", n);
+    launch(sc, "ptbake::k_bake_points", k_bake_points, texel_grid(a), dim3(256), of->ds, a, d_owner, d_pos, d_nrm);
+    sc->end();
+    HIP_TRY(hipGetLastError());
+    return PT_OK;
+}
+
+// The ray buffers of the largest pass (`slots` items per sample number), and the passes of the samples [first, first + n_samples): pass(s_begin, s_count)
+int alloc_pass_rays(const Geometry &g, uint32_t slots, const char *what, AORayBuffers &b, size_t &rays) {
+    const size_t items = (size_t)slots * g.S;
+    rays = items * g.K;
+    return b.alloc(items, rays, what);
+}
+template <class Pass> int for_passes(const Geometry &g, uint32_t first, uint32_t n_samples, const Pass &pass) {
+    for (uint32_t s0 = first, end = first + n_samples; s0 < end; s0 += g.S)
+        if (int st = pass(s0, std::min(g.S, end - s0))) return st;
+    return PT_OK;
+}
+
+// One pass chunk by chunk (ao_chunks): `job` comes with what its bake adds and gets the samples here; spawn(job, blocks) and accum(job) launch under their launch kinds
+template <class Job, class Spawn, class Accum>
+int pass_chunks(pt_scene *sc, const Geometry &g, Job job, uint32_t nsamples, uint32_t cos_sample, uint32_t s_begin, uint32_t s_count, uint32_t items, float t_max, const AORayBuffers &b,
+                const char *spawn_kind, const Spawn &spawn, const char *accum_kind, const Accum &accum) {
+    job.nsamples = nsamples; job.cos_sample = cos_sample ? 1u : 0u; job.s_begin = s_begin; job.s_count = s_count;
+    const dim3 blocks = blocks_for(items, 16u);
+    return ao_chunks<Job>(sc, job, g.K, items, t_max, b,
+                          [&](const Job &j) { sc->begin(spawn_kind, (uint64_t)items * j.kn); spawn(j, blocks); sc->end(); },
+                          [&](const Job &j) { sc->begin(accum_kind, items); accum(j); sc->end(); });
+}
+
+// A kernel's <true> / <false> pair under the launch kind the caller has opened: SPH as the render chooses it (light_sample_li<SPH>)
+template <class K, class... A> void launch_sph(pt_scene *sc, const char *name_true, K k_true, const char *name_false, K k_false, dim3 blocks, const A &...args) {
+    if (general_geometry(sc)) launch(sc, name_true, k_true, blocks, dim3(256), args...);
+    else launch(sc, name_false, k_false, blocks, dim3(256), args...);
+}
+
+// The queries of a probe on the device: three index arrays in one allocation
+struct Queries { const uint32_t *item, *sample, *element; };
+int upload_queries(pt_scene *sc, uint32_t n, const uint32_t *item, const uint32_t *sample, const uint32_t *element, const char *what, DevTmp &tmp, Queries &q) {
+    uint32_t *d = nullptr;
+    SIDE_ALLOC(tmp, d, (size_t)n * 12, what);
+    const uint32_t *from[3] = {item, sample, element};
+    for (size_t k = 0; k < 3; ++k) HIP_TRY(hipMemcpyAsync(d + k * n, from[k], (size_t)n * 4, hipMemcpyHostToDevice, sc->stream));
+    q = Queries{d, d + n, d + 2 * (size_t)n};
+    return PT_OK;
+}
+
+// The rays of one pass: samples [s_begin, s_begin + s_count) of every texel (t_max = max_distance)
+int bake_pass(pt_scene *sc, const Geometry &g, const PtBakeParams *bp, uint32_t s_begin, uint32_t s_count, const uint32_t *d_owner, float4 *d_ao, const AORayBuffers &b) {
+    BakeJob job{};
+    job.owner = d_owner; job.ao_w = d_ao;
+    return pass_chunks(sc, g, job, bp->nsamples, bp->cos_sample, s_begin, s_count, g.atlas.slots * s_count, bp->max_distance, b,
+                       "bake_rays", [&](const BakeJob &j, dim3 blocks) { launch(sc, "ptbake::k_bake_rays", k_bake_rays, blocks, dim3(256), sc->ds, g.rc, g_tabs, g.atlas, j); },
+                       "bake_accum", [&](const BakeJob &j) { launch(sc, "ptbake::k_bake_accum", k_bake_accum, texel_grid(g.atlas), dim3(256), g.atlas, j); });
 }
 
 // ---- the transfer bake: `target` is the scene whose atlas is filled and is only read, `source` the scene the rays see -- every launch runs on its stream, under its
@@ -268,22 +348,11 @@ int project(pt_scene *target, pt_scene *source, const PtBakeTransferParams *tp, 
 
 // The AO rays of one pass from the detail hits (bake_pass with the source hits in the owners' place)
 int transfer_pass(pt_scene *sc, const Geometry &g, const PtBakeParams *bp, uint32_t s_begin, uint32_t s_count, const uint32_t *d_detail, const float4 *d_rec, float4 *d_ao, const AORayBuffers &b) {
-    const uint32_t items = g.atlas.slots * s_count;
-    const dim3 blocks = blocks_for(items, 16u);
-    auto spawn = [&](const TransferJob &job) {
-        sc->begin("bake_transfer_rays", (uint64_t)items * job.kn);
-        launch(sc, "ptbake::k_bake_transfer_rays", k_bake_transfer_rays, blocks, dim3(256), sc->ds, g.rc, g_tabs, g.atlas, job);
-        sc->end();
-    };
-    auto accum = [&](const TransferJob &job) {
-        sc->begin("bake_accum", items);
-        launch(sc, "ptbake::k_bake_accum", k_bake_accum, texel_grid(g.atlas), dim3(256), g.atlas, static_cast<const BakeJob &>(job));
-        sc->end();
-    };
     TransferJob job{};
-    job.nsamples = bp->nsamples; job.cos_sample = bp->cos_sample ? 1u : 0u;
-    job.s_begin = s_begin; job.s_count = s_count; job.owner = d_detail; job.ao_w = d_ao; job.rec = d_rec;
-    return ao_chunks<TransferJob>(sc, job, g.K, items, bp->max_distance, b, spawn, accum);   // (t_max = max_distance)
+    job.owner = d_detail; job.ao_w = d_ao; job.rec = d_rec;
+    return pass_chunks(sc, g, job, bp->nsamples, bp->cos_sample, s_begin, s_count, g.atlas.slots * s_count, bp->max_distance, b,
+                       "bake_transfer_rays", [&](const TransferJob &j, dim3 blocks) { launch(sc, "ptbake::k_bake_transfer_rays", k_bake_transfer_rays, blocks, dim3(256), sc->ds, g.rc, g_tabs, g.atlas, j); },
+                       "bake_accum", [&](const TransferJob &j) { launch(sc, "ptbake::k_bake_accum", k_bake_accum, texel_grid(g.atlas), dim3(256), g.atlas, static_cast<const BakeJob &>(j)); });
 }
 
 // ---- the lightmap (mi355bake.h "Lightmap")
@@ -298,11 +367,11 @@ PtBakeParams light_params(const PtBakeLightParams *lp) {
     return bp;
 }
 // The selected lights in ascending order (light_select NULL: all n_lights), and the rule that gives every light the same number of samples
-int check_lights(const PtBakeLightParams *lp, const uint8_t *light_select, uint32_t n_lights, std::vector<uint32_t> &sel, const char *per = "texel") {
+int check_lights(uint32_t spp, uint32_t nsamples, const uint8_t *light_select, uint32_t n_lights, std::vector<uint32_t> &sel, const char *per = "texel") {
     sel.clear();
     for (uint32_t i = 0; i < n_lights; ++i) if (!light_select || light_select[i]) sel.push_back(i);
     if (sel.empty()) return fail(PT_ERR_INVALID_ARG, "bake light: no light is selected");
-    const uint64_t numbers = (uint64_t)lp->spp * lp->nsamples;
+    const uint64_t numbers = (uint64_t)spp * nsamples;
     if (numbers % sel.size() != 0)
         return fail(PT_ERR_INVALID_ARG, "bake light: spp x nsamples = " + std::to_string(numbers) + " light samples per " + per + " are no multiple of the " + std::to_string(sel.size()) + " selected lights");
     return PT_OK;
@@ -311,34 +380,65 @@ int check_light_count(const pt_scene *sc, uint32_t n_lights) {
     if (n_lights != sc->n_lights) return fail(PT_ERR_INVALID_ARG, "bake light: light_select has " + std::to_string(n_lights) + " entries, the scene " + std::to_string(sc->n_lights) + " lights");
     return PT_OK;
 }
-int upload_lights(pt_scene *sc, const std::vector<uint32_t> &sel, DevTmp &tmp, uint32_t *&d_sel) {
+// The light-sample fields of a lightmap or SH job: the selection on the device (`sel` outlives the call's last synchronisation), the rule's scale and, for `rays`
+// rays in flight at the most (a probe: none), the id table and the E records
+int light_samples(pt_scene *sc, const std::vector<uint32_t> &sel, uint32_t nsamples, size_t rays, const char *what, DevTmp &tmp, LightSamples &ls) {
+    uint32_t *d_sel = nullptr;
     SIDE_ALLOC(tmp, d_sel, sel.size() * 4, "bake light selection");
-    HIP_TRY(hipMemcpyAsync(d_sel, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, sc->stream));   // (`sel` outlives the call's last synchronisation)
+    HIP_TRY(hipMemcpyAsync(d_sel, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, sc->stream));
+    ls = LightSamples{};
+    ls.sel = d_sel; ls.n_sel = (uint32_t)sel.size(); ls.scale = (float)ls.n_sel / (float)nsamples;
+    if (rays) { SIDE_ALLOC(tmp, ls.id, rays * 4, what); SIDE_ALLOC(tmp, ls.e, rays * 16, what); }
     return PT_OK;
 }
 
-// The light samples of one pass: samples [s_begin, s_begin + s_count) of every texel, chunk by chunk (bake_pass with the shadow ray's t_max)
-int light_pass(pt_scene *sc, const Geometry &g, const PtBakeParams *bp, uint32_t s_begin, uint32_t s_count, const uint32_t *d_owner, float4 *d_light, const uint32_t *d_sel, uint32_t n_sel,
-               uint32_t *d_id, float4 *d_e, const AORayBuffers &b) {
-    const uint32_t items = g.atlas.slots * s_count;
-    const dim3 blocks = blocks_for(items, 16u);
-    const bool sph = general_geometry(sc);   // light_sample_li<SPH> as the render chooses it
-    auto spawn = [&](const LightJob &job) {
-        sc->begin("bake_light_rays", (uint64_t)items * job.kn);
-        if (sph) launch(sc, "ptbake::k_bake_light_rays<true>", k_bake_light_rays<true>, blocks, dim3(256), sc->ds, g.rc, g_tabs, g.atlas, job);
-        else launch(sc, "ptbake::k_bake_light_rays<false>", k_bake_light_rays<false>, blocks, dim3(256), sc->ds, g.rc, g_tabs, g.atlas, job);
-        sc->end();
-    };
-    auto accum = [&](const LightJob &job) {
-        sc->begin("bake_light_accum", items);
-        launch(sc, "ptbake::k_bake_light_accum", k_bake_light_accum, texel_grid(g.atlas), dim3(256), g.atlas, job);
-        sc->end();
-    };
+// The light samples of one pass: samples [s_begin, s_begin + s_count) of every texel (the shadow ray's t_max)
+int light_pass(pt_scene *sc, const Geometry &g, uint32_t nsamples, uint32_t s_begin, uint32_t s_count, const uint32_t *d_owner, float4 *d_light, const LightSamples &ls, const AORayBuffers &b) {
     LightJob job{};
-    job.nsamples = bp->nsamples; job.cos_sample = 0;
-    job.s_begin = s_begin; job.s_count = s_count; job.owner = d_owner; job.light_w = d_light;
-    job.sel = d_sel; job.n_sel = n_sel; job.scale = (float)n_sel / (float)bp->nsamples; job.id = d_id; job.e = d_e;
-    return ao_chunks<LightJob>(sc, job, g.K, items, kShadowTMax, b, spawn, accum);
+    job.owner = d_owner; job.light_w = d_light; job.light = ls;
+    return pass_chunks(sc, g, job, nsamples, 0, s_begin, s_count, g.atlas.slots * s_count, kShadowTMax, b,
+                       "bake_light_rays", [&](const LightJob &j, dim3 blocks) {
+                           launch_sph(sc, "ptbake::k_bake_light_rays<true>", k_bake_light_rays<true>, "ptbake::k_bake_light_rays<false>", k_bake_light_rays<false>, blocks, sc->ds, g.rc, g_tabs, g.atlas, j);
+                       },
+                       "bake_light_accum", [&](const LightJob &j) { launch(sc, "ptbake::k_bake_light_accum", k_bake_light_accum, texel_grid(g.atlas), dim3(256), g.atlas, j); });
+}
+
+// What a light probe leaves per query on the device (store_light_row), and its way into the caller's arrays
+struct LightRows {
+    float *d_out = nullptr; uint32_t *d_light = nullptr; uint8_t *d_found = nullptr;
+    int alloc(DevTmp &tmp, uint32_t n, const char *what) {
+        SIDE_ALLOC(tmp, d_out, (size_t)n * 64, what); SIDE_ALLOC(tmp, d_light, (size_t)n * 4, what); SIDE_ALLOC(tmp, d_found, n, what);
+        return PT_OK;
+    }
+    int read(uint32_t n, uint32_t *out_light, float *out_wi, float *out_pdf, float *out_li, float *out_e, float *out_o, float *out_d, uint8_t *found) const {
+        std::vector<float> rows((size_t)n * 16);
+        HIP_TRY(hipMemcpy(rows.data(), d_out, rows.size() * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out_light, d_light, (size_t)n * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(found, d_found, n, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n; ++i) {
+            const float *r = rows.data() + 16 * i;
+            for (int k = 0; k < 3; ++k) { out_wi[3 * i + k] = r[k]; out_li[3 * i + k] = r[4 + k]; out_e[3 * i + k] = r[7 + k]; out_o[3 * i + k] = r[10 + k]; out_d[3 * i + k] = r[13 + k]; }
+            out_pdf[i] = r[3];
+        }
+        return PT_OK;
+    }
+};
+
+// What the light and SH resolves share: per item `width` sums, the last of them the count of arrived samples -- the others / spp, the count / (spp * nsamples), zeros
+// where nothing arrived and nothing was added
+int resolve_light_sums(const float *sums, size_t n, size_t width, uint32_t spp, uint32_t nsamples, float *mean, float *reached) {
+    if (!sums || (!mean && !reached)) return fail(PT_ERR_INVALID_ARG, "null argument");
+    if (int st = check_spp(spp)) return st;
+    if (int st = check_nsamples(nsamples)) return st;
+    const float sf = (float)spp, nf = (float)spp * (float)nsamples;
+    for (size_t i = 0; i < n; ++i) {
+        const float *w = sums + width * i;
+        bool any = false;
+        for (size_t m = 0; m < width; ++m) any = any || w[m] != 0.0f;
+        if (mean) for (size_t m = 0; m + 1 < width; ++m) mean[(width - 1) * i + m] = any ? w[m] / sf : 0.0f;
+        if (reached) reached[i] = any ? w[width - 1] / nf : 0.0f;
+    }
+    return PT_OK;
 }
 
 // ---- the SH points (mi355bake.h "SH points")
@@ -360,18 +460,15 @@ int check_sh(const PtBakeShParams *hp) {
     if (hp->n_points > kShMaxPoints) return fail(PT_ERR_INVALID_ARG, "bake sh: more than 2^28 points");
     if (hp->row == 0) return fail(PT_ERR_INVALID_ARG, "bake sh: row must be > 0");
     if (hp->row > kShMaxPoints) return fail(PT_ERR_INVALID_ARG, "bake sh: row exceeds 2^28");
-    if (hp->spp == 0) return fail(PT_ERR_INVALID_ARG, "bake: spp must be > 0");
-    if (hp->nsamples == 0) return fail(PT_ERR_INVALID_ARG, "bake: nsamples must be > 0");
-    if (hp->sampler_type != PT_SAMPLER_SOBOL && hp->sampler_type != PT_SAMPLER_HALTON) return fail(PT_ERR_INVALID_ARG, "bake: sampler_type must be PT_SAMPLER_SOBOL or PT_SAMPLER_HALTON");
-    return PT_OK;
+    if (int st = check_spp(hp->spp)) return st;
+    if (int st = check_nsamples(hp->nsamples)) return st;
+    return check_sampler(hp->sampler_type);
 }
 // Errors 7 to 9
 int check_sh_points_and_lights(const PtBakeShParams *hp, const float *points, const uint8_t *light_select, uint32_t n_lights, std::vector<uint32_t> &sel) {
     for (size_t i = 0; i < (size_t)hp->n_points * 3; ++i)
         if (!std::isfinite(points[i])) return fail(PT_ERR_INVALID_ARG, "bake sh: point " + std::to_string(i / 3) + " has a coordinate that is not finite");
-    PtBakeLightParams lp{};
-    lp.spp = hp->spp; lp.nsamples = hp->nsamples;
-    return check_lights(&lp, light_select, n_lights, sel, "point");
+    return check_lights(hp->spp, hp->nsamples, light_select, n_lights, sel, "point");
 }
 int sh_geometry(pt_scene *sc, const PtBakeShParams *hp, uint32_t n_samples, Geometry &g) {
     const PtBakeParams bp = sh_params(hp);
@@ -383,28 +480,16 @@ int upload_points(pt_scene *sc, const PtBakeShParams *hp, const float *points, D
     return PT_OK;
 }
 
-// The light samples of one pass: samples [s_begin, s_begin + s_count) of every point, chunk by chunk (light_pass without atlas)
-int sh_pass(pt_scene *sc, const Geometry &g, const PtBakeShParams *hp, uint32_t s_begin, uint32_t s_count, const float *d_points, float4 *d_sh, const uint32_t *d_sel, uint32_t n_sel,
-            uint32_t *d_id, float4 *d_e, float4 *d_wi, const AORayBuffers &b) {
-    const uint32_t padded = sh_padded(hp), items = padded * s_count;
-    const dim3 blocks = blocks_for(items, 16u);
-    const bool sph = general_geometry(sc);   // light_sample_li<SPH> as the render chooses it
-    auto spawn = [&](const ShJob &job) {
-        sc->begin("bake_sh_rays", (uint64_t)items * job.kn);
-        if (sph) launch(sc, "ptbake::k_bake_sh_rays<true>", k_bake_sh_rays<true>, blocks, dim3(256), sc->ds, g.rc, g_tabs, job);
-        else launch(sc, "ptbake::k_bake_sh_rays<false>", k_bake_sh_rays<false>, blocks, dim3(256), sc->ds, g.rc, g_tabs, job);
-        sc->end();
-    };
-    auto accum = [&](const ShJob &job) {
-        sc->begin("bake_sh_accum", items);
-        launch(sc, "ptbake::k_bake_sh_accum", k_bake_sh_accum, dim3((hp->n_points + 255) / 256), dim3(256), job);
-        sc->end();
-    };
+// The light samples of one pass: samples [s_begin, s_begin + s_count) of every point (light_pass without atlas)
+int sh_pass(pt_scene *sc, const Geometry &g, const PtBakeShParams *hp, uint32_t s_begin, uint32_t s_count, const float *d_points, float4 *d_sh, const LightSamples &ls, float4 *d_wi,
+            const AORayBuffers &b) {
     ShJob job{};
-    job.nsamples = hp->nsamples; job.cos_sample = 0;
-    job.s_begin = s_begin; job.s_count = s_count; job.n_points = hp->n_points; job.padded = padded; job.row = hp->row; job.points = d_points; job.sh_w = d_sh;
-    job.sel = d_sel; job.n_sel = n_sel; job.scale = (float)n_sel / (float)hp->nsamples; job.id = d_id; job.e = d_e; job.wi = d_wi;
-    return ao_chunks<ShJob>(sc, job, g.K, items, kShadowTMax, b, spawn, accum);
+    job.n_points = hp->n_points; job.padded = sh_padded(hp); job.row = hp->row; job.points = d_points; job.sh_w = d_sh; job.light = ls; job.wi = d_wi;
+    return pass_chunks(sc, g, job, hp->nsamples, 0, s_begin, s_count, job.padded * s_count, kShadowTMax, b,
+                       "bake_sh_rays", [&](const ShJob &j, dim3 blocks) {
+                           launch_sph(sc, "ptbake::k_bake_sh_rays<true>", k_bake_sh_rays<true>, "ptbake::k_bake_sh_rays<false>", k_bake_sh_rays<false>, blocks, sc->ds, g.rc, g_tabs, j);
+                       },
+                       "bake_sh_accum", [&](const ShJob &j) { launch(sc, "ptbake::k_bake_sh_accum", k_bake_sh_accum, dim3((hp->n_points + 255) / 256), dim3(256), j); });
 }
 
 }  // namespace
@@ -437,49 +522,22 @@ __attribute__((visibility("default"))) int pt_bake_render_samples(pt_scene *sc, 
     Geometry g;
     if (int st = bake_geometry(sc, bp, n_samples, g)) return st;
     if (int st = begin_call(sc, bp->profile != 0)) return st;
-    const BakeAtlas &a = g.atlas;
-    const size_t n = a.n_texels;
-    DevTmp tmp;   // (freed when the call returns, however it ends: a bake leaves the device's free memory as it found it, apart from the scene's workspace)
-    uint32_t *d_selected = nullptr, n_selected = 0;
-    if (int st = upload_selection(sc, sc, prim_select, n_prims, tmp, d_selected, n_selected)) return st;
-    const bool dev = buffers_are_device != 0;
-    uint32_t *d_owner = dev ? buffers->owner : nullptr;
-    if (!d_owner) SIDE_ALLOC(tmp, d_owner, n * 4, "bake owner map");
-    if (int st = raster(sc, sc, a, d_selected, n_selected, d_owner)) return st;
-    float *d_pos = dev ? buffers->position : nullptr, *d_nrm = dev ? buffers->normal : nullptr;
-    if (buffers->position || buffers->normal) {
-        if (buffers->position && !d_pos) SIDE_ALLOC(tmp, d_pos, n * 12, "bake position plane");
-        if (buffers->normal && !d_nrm) SIDE_ALLOC(tmp, d_nrm, n * 12, "bake normal plane");
-        sc->begin("bake_points", n);
-        launch(sc, "ptbake::k_bake_points", k_bake_points, texel_grid(a), dim3(256), sc->ds, a, (const uint32_t *)d_owner, d_pos, d_nrm);
-        sc->end();
-        HIP_TRY(hipGetLastError());
+    DevTmp tmp;
+    Staging out{tmp, sc->stream, buffers_are_device != 0};
+    uint32_t *d_owner = nullptr; float4 *d_ao = nullptr;
+    if (int st = atlas_frame(sc, sc, g.atlas, prim_select, n_prims, out, buffers->owner, buffers->position, buffers->normal, d_owner)) return st;
+    if (int st = out.plane(buffers->ao_w, (size_t)g.atlas.n_texels * 16, "bake ao plane", true, d_ao)) return st;
+    if (d_ao) {
+        AORayBuffers b; size_t rays;
+        if (int st = alloc_pass_rays(g, g.atlas.slots, "bake rays", b, rays)) return st;
+        if (int st = for_passes(g, first, n_samples, [&](uint32_t s0, uint32_t sn) { return bake_pass(sc, g, bp, s0, sn, d_owner, d_ao, b); })) return st;
     }
-    float4 *d_ao = dev ? reinterpret_cast<float4 *>(buffers->ao_w) : nullptr;
-    if (buffers->ao_w) {
-        if (!d_ao) {
-            SIDE_ALLOC(tmp, d_ao, n * 16, "bake ao plane");
-            HIP_TRY(hipMemcpyAsync(d_ao, buffers->ao_w, n * 16, hipMemcpyHostToDevice, sc->stream));   // (added to)
-        }
-        AORayBuffers b;
-        const size_t items = (size_t)a.slots * g.S;
-        if (int st = b.alloc(items, items * g.K, "bake rays")) return st;
-        for (uint32_t s0 = first, end = first + n_samples; s0 < end; s0 += g.S)
-            if (int st = bake_pass(sc, g, bp, s0, std::min(g.S, end - s0), d_owner, d_ao, b)) return st;
-    }
-    if (int st = end_call(sc)) return st;
-    if (!dev) {   // (host planes are written once everything has succeeded)
-        if (buffers->owner) HIP_TRY(hipMemcpy(buffers->owner, d_owner, n * 4, hipMemcpyDeviceToHost));
-        if (buffers->position) HIP_TRY(hipMemcpy(buffers->position, d_pos, n * 12, hipMemcpyDeviceToHost));
-        if (buffers->normal) HIP_TRY(hipMemcpy(buffers->normal, d_nrm, n * 12, hipMemcpyDeviceToHost));
-        if (buffers->ao_w) HIP_TRY(hipMemcpy(buffers->ao_w, d_ao, n * 16, hipMemcpyDeviceToHost));
-    }
-    return PT_OK;
+    return out.finish(sc);
 }
 
 __attribute__((visibility("default"))) int pt_bake_resolve(const float *ao_w, uint32_t n_texels, uint32_t spp, float *ao, float *bent_xyz) {
     if (!ao_w || (!ao && !bent_xyz)) return fail(PT_ERR_INVALID_ARG, "null argument");
-    if (spp == 0) return fail(PT_ERR_INVALID_ARG, "bake: spp must be > 0");
+    if (int st = check_spp(spp)) return st;
     // (sum w / spp is ao.rs's radiance of the texel: pi where nothing occludes under cosine sampling. The map is that over pi: 1 for an open surface)
     const float sf = (float)spp * ptd::kPi;
     for (size_t i = 0; i < n_texels; ++i) {
@@ -547,8 +605,7 @@ __attribute__((visibility("default"))) int pt_bake_rays(pt_scene *sc, const PtBa
     if (!sc || !bp || !prim_select || !texel || !sample || !element || !out_o || !out_d || !out_w || !found) return fail(PT_ERR_INVALID_ARG, "null argument");
     if (int st = check_params(bp)) return st;
     if (int st = check_selection(prim_select, n_prims)) return st;
-    for (uint32_t i = 0; i < n; ++i)
-        if (sample[i] >= bp->spp || element[i] >= bp->nsamples) return fail(PT_ERR_INVALID_ARG, "bake: ray " + std::to_string(i) + " names a sample or element outside the job");
+    if (int st = check_queries(n, sample, element, bp->spp, bp->nsamples)) return st;
     if (int st = check_prim_count(sc, n_prims)) return st;
     Geometry g;
     PtBakeParams one = *bp; one.spp_per_pass = 1;
@@ -556,17 +613,14 @@ __attribute__((visibility("default"))) int pt_bake_rays(pt_scene *sc, const PtBa
     if (n == 0) return PT_OK;
     if (int st = begin_call(sc, false)) return st;
     DevTmp tmp;
-    uint32_t *d_selected = nullptr, n_selected = 0, *d_owner = nullptr, *d_in = nullptr; float *d_out = nullptr; uint8_t *d_found = nullptr;
-    if (int st = upload_selection(sc, sc, prim_select, n_prims, tmp, d_selected, n_selected)) return st;
-    SIDE_ALLOC(tmp, d_owner, (size_t)g.atlas.n_texels * 4, "bake owner map");
-    if (int st = raster(sc, sc, g.atlas, d_selected, n_selected, d_owner)) return st;
-    SIDE_ALLOC(tmp, d_in, (size_t)n * 12, "bake rays"); SIDE_ALLOC(tmp, d_out, (size_t)n * 28, "bake rays"); SIDE_ALLOC(tmp, d_found, n, "bake rays");
-    HIP_TRY(hipMemcpyAsync(d_in, texel, (size_t)n * 4, hipMemcpyHostToDevice, sc->stream));
-    HIP_TRY(hipMemcpyAsync(d_in + n, sample, (size_t)n * 4, hipMemcpyHostToDevice, sc->stream));
-    HIP_TRY(hipMemcpyAsync(d_in + 2 * (size_t)n, element, (size_t)n * 4, hipMemcpyHostToDevice, sc->stream));
+    Staging none{tmp, sc->stream, false};
+    uint32_t *d_owner = nullptr; float *d_out = nullptr; uint8_t *d_found = nullptr; Queries q;
+    if (int st = atlas_frame(sc, sc, g.atlas, prim_select, n_prims, none, nullptr, nullptr, nullptr, d_owner)) return st;
+    if (int st = upload_queries(sc, n, texel, sample, element, "bake rays", tmp, q)) return st;
+    SIDE_ALLOC(tmp, d_out, (size_t)n * 28, "bake rays"); SIDE_ALLOC(tmp, d_found, n, "bake rays");
     sc->begin("bake_probe", n);
-    launch(sc, "ptbake::k_bake_probe", k_bake_probe, dim3((n + 255) / 256), dim3(256), sc->ds, g.rc, g_tabs, g.atlas, (const uint32_t *)d_owner, bp->nsamples, bp->cos_sample ? 1u : 0u, n,
-           (const uint32_t *)d_in, (const uint32_t *)(d_in + n), (const uint32_t *)(d_in + 2 * (size_t)n), d_out, d_out + 3 * (size_t)n, d_out + 6 * (size_t)n, d_found);
+    launch(sc, "ptbake::k_bake_probe", k_bake_probe, dim3((n + 255) / 256), dim3(256), sc->ds, g.rc, g_tabs, g.atlas, d_owner, bp->nsamples, bp->cos_sample ? 1u : 0u, n, q.item, q.sample, q.element,
+           d_out, d_out + 3 * (size_t)n, d_out + 6 * (size_t)n, d_found);
     sc->end();
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(sc->stream));
@@ -613,51 +667,29 @@ __attribute__((visibility("default"))) int pt_bake_transfer_samples(pt_scene *ta
     if (int st = same_device(target, source)) return st;
     Geometry g;
     if (int st = bake_geometry(source, &bp, n_samples, g)) return st;
-    if (int st = begin_call(source, tp->profile != 0)) return st;
+    if (int st = begin_call(source, tp->profile != 0)) return st;   // (counters and statistics of a transfer are the source's)
     const BakeAtlas &a = g.atlas;
     const size_t n = a.n_texels;
-    DevTmp tmp;   // (freed when the call returns, however it ends)
-    uint32_t *d_selected = nullptr, n_selected = 0;
-    if (int st = upload_selection(source, target, prim_select, n_prims, tmp, d_selected, n_selected)) return st;
-    const bool dev = buffers_are_device != 0;
-    uint32_t *d_owner = dev ? B.owner : nullptr;
-    if (!d_owner) SIDE_ALLOC(tmp, d_owner, n * 4, "bake owner map");
-    if (int st = raster(source, target, a, d_selected, n_selected, d_owner)) return st;
+    DevTmp tmp;
+    Staging planes{tmp, source->stream, buffers_are_device != 0};
+    uint32_t *d_owner = nullptr; float4 *d_ao = nullptr;
+    if (int st = atlas_frame(source, target, a, prim_select, n_prims, planes, B.owner, nullptr, nullptr, d_owner)) return st;
     TransferOut out{};
-    if (dev) { out.hit_prim = B.hit_prim; out.height = B.height; out.src_position = B.src_position; out.src_normal = B.src_normal; out.tangent_normal = B.tangent_normal; }
-    else {
-        if (B.hit_prim) SIDE_ALLOC(tmp, out.hit_prim, n * 4, "bake transfer planes");
-        if (B.height) SIDE_ALLOC(tmp, out.height, n * 4, "bake transfer planes");
-        if (B.src_position) SIDE_ALLOC(tmp, out.src_position, n * 12, "bake transfer planes");
-        if (B.src_normal) SIDE_ALLOC(tmp, out.src_normal, n * 12, "bake transfer planes");
-        if (B.tangent_normal) SIDE_ALLOC(tmp, out.tangent_normal, n * 12, "bake transfer planes");
-    }
+    if (int st = planes.plane(B.hit_prim, n * 4, "bake transfer planes", false, out.hit_prim)) return st;
+    if (int st = planes.plane(B.height, n * 4, "bake transfer planes", false, out.height)) return st;
+    if (int st = planes.plane(B.src_position, n * 12, "bake transfer planes", false, out.src_position)) return st;
+    if (int st = planes.plane(B.src_normal, n * 12, "bake transfer planes", false, out.src_normal)) return st;
+    if (int st = planes.plane(B.tangent_normal, n * 12, "bake transfer planes", false, out.tangent_normal)) return st;
     if (want_ao) { SIDE_ALLOC(tmp, out.detail, n * 4, "bake transfer hits"); SIDE_ALLOC(tmp, out.rec, n * 16, "bake transfer hits"); }
     if (out.hit_prim || out.height || out.src_position || out.src_normal || out.tangent_normal || want_ao)
         if (int st = project(target, source, tp, a, d_owner, out)) return st;
-    float4 *d_ao = dev ? reinterpret_cast<float4 *>(B.ao_w) : nullptr;
+    if (int st = planes.plane(B.ao_w, n * 16, "bake ao plane", true, d_ao)) return st;
     if (want_ao) {
-        if (!d_ao) {
-            SIDE_ALLOC(tmp, d_ao, n * 16, "bake ao plane");
-            HIP_TRY(hipMemcpyAsync(d_ao, B.ao_w, n * 16, hipMemcpyHostToDevice, source->stream));   // (added to)
-        }
-        AORayBuffers b;
-        const size_t items = (size_t)a.slots * g.S;
-        if (int st = b.alloc(items, items * g.K, "bake rays")) return st;
-        for (uint32_t s0 = first, end = first + n_samples; s0 < end; s0 += g.S)
-            if (int st = transfer_pass(source, g, &bp, s0, std::min(g.S, end - s0), out.detail, out.rec, d_ao, b)) return st;
+        AORayBuffers b; size_t rays;
+        if (int st = alloc_pass_rays(g, a.slots, "bake rays", b, rays)) return st;
+        if (int st = for_passes(g, first, n_samples, [&](uint32_t s0, uint32_t sn) { return transfer_pass(source, g, &bp, s0, sn, out.detail, out.rec, d_ao, b); })) return st;
     }
-    if (int st = end_call(source)) return st;
-    if (!dev) {   // (host planes are written once everything has succeeded)
-        if (B.owner) HIP_TRY(hipMemcpy(B.owner, d_owner, n * 4, hipMemcpyDeviceToHost));
-        if (B.hit_prim) HIP_TRY(hipMemcpy(B.hit_prim, out.hit_prim, n * 4, hipMemcpyDeviceToHost));
-        if (B.height) HIP_TRY(hipMemcpy(B.height, out.height, n * 4, hipMemcpyDeviceToHost));
-        if (B.src_position) HIP_TRY(hipMemcpy(B.src_position, out.src_position, n * 12, hipMemcpyDeviceToHost));
-        if (B.src_normal) HIP_TRY(hipMemcpy(B.src_normal, out.src_normal, n * 12, hipMemcpyDeviceToHost));
-        if (B.tangent_normal) HIP_TRY(hipMemcpy(B.tangent_normal, out.tangent_normal, n * 12, hipMemcpyDeviceToHost));
-        if (B.ao_w) HIP_TRY(hipMemcpy(B.ao_w, d_ao, n * 16, hipMemcpyDeviceToHost));
-    }
-    return PT_OK;
+    return planes.finish(source);
 }
 
 __attribute__((visibility("default"))) int pt_bake_transfer_rays(pt_scene *target, pt_scene *source, const PtBakeTransferParams *tp, const uint8_t *prim_select, uint32_t n_prims, uint32_t n,
@@ -668,8 +700,7 @@ __attribute__((visibility("default"))) int pt_bake_transfer_rays(pt_scene *targe
     PtBakeParams bp = ao_params(tp, true);
     if (int st = check_params(&bp)) return st;
     if (int st = check_selection(prim_select, n_prims)) return st;
-    for (uint32_t i = 0; i < n; ++i)
-        if (sample[i] >= bp.spp || element[i] >= bp.nsamples) return fail(PT_ERR_INVALID_ARG, "bake: ray " + std::to_string(i) + " names a sample or element outside the job");
+    if (int st = check_queries(n, sample, element, bp.spp, bp.nsamples)) return st;
     if (int st = check_prim_count(target, n_prims)) return st;
     if (int st = same_device(target, source)) return st;
     Geometry g;
@@ -679,21 +710,17 @@ __attribute__((visibility("default"))) int pt_bake_transfer_rays(pt_scene *targe
     if (int st = begin_call(source, false)) return st;
     const BakeAtlas &a = g.atlas;
     DevTmp tmp;
-    uint32_t *d_selected = nullptr, n_selected = 0, *d_owner = nullptr, *d_in = nullptr; float *d_out = nullptr; uint8_t *d_found = nullptr;
-    if (int st = upload_selection(source, target, prim_select, n_prims, tmp, d_selected, n_selected)) return st;
-    SIDE_ALLOC(tmp, d_owner, (size_t)a.n_texels * 4, "bake owner map");
-    if (int st = raster(source, target, a, d_selected, n_selected, d_owner)) return st;
+    Staging none{tmp, source->stream, false};
+    uint32_t *d_owner = nullptr; float *d_out = nullptr; uint8_t *d_found = nullptr; Queries q;
+    if (int st = atlas_frame(source, target, a, prim_select, n_prims, none, nullptr, nullptr, nullptr, d_owner)) return st;
     TransferOut out{};
     SIDE_ALLOC(tmp, out.detail, (size_t)a.n_texels * 4, "bake transfer hits"); SIDE_ALLOC(tmp, out.rec, (size_t)a.n_texels * 16, "bake transfer hits");
     if (int st = project(target, source, tp, a, d_owner, out)) return st;
-    SIDE_ALLOC(tmp, d_in, (size_t)n * 12, "bake rays"); SIDE_ALLOC(tmp, d_out, (size_t)n * 56, "bake rays"); SIDE_ALLOC(tmp, d_found, n, "bake rays");
-    HIP_TRY(hipMemcpyAsync(d_in, texel, (size_t)n * 4, hipMemcpyHostToDevice, source->stream));
-    HIP_TRY(hipMemcpyAsync(d_in + n, sample, (size_t)n * 4, hipMemcpyHostToDevice, source->stream));
-    HIP_TRY(hipMemcpyAsync(d_in + 2 * (size_t)n, element, (size_t)n * 4, hipMemcpyHostToDevice, source->stream));
+    if (int st = upload_queries(source, n, texel, sample, element, "bake rays", tmp, q)) return st;
+    SIDE_ALLOC(tmp, d_out, (size_t)n * 56, "bake rays"); SIDE_ALLOC(tmp, d_found, n, "bake rays");
     source->begin("bake_probe", n);
-    launch(source, "ptbake::k_bake_transfer_probe", k_bake_transfer_probe, dim3((n + 255) / 256), dim3(256), target->ds, source->ds, g.rc, g_tabs, a, (const uint32_t *)d_owner,
-           (const uint32_t *)out.detail, (const float4 *)out.rec, tp->front, tp->front + tp->back, bp.nsamples, bp.cos_sample ? 1u : 0u, n, (const uint32_t *)d_in, (const uint32_t *)(d_in + n),
-           (const uint32_t *)(d_in + 2 * (size_t)n), d_out, d_found);
+    launch(source, "ptbake::k_bake_transfer_probe", k_bake_transfer_probe, dim3((n + 255) / 256), dim3(256), target->ds, source->ds, g.rc, g_tabs, a, d_owner, out.detail, out.rec, tp->front,
+           tp->front + tp->back, bp.nsamples, bp.cos_sample ? 1u : 0u, n, q.item, q.sample, q.element, d_out, d_found);
     source->end();
     HIP_TRY(hipGetLastError());
     if (int st = end_call(source)) return st;
@@ -714,7 +741,7 @@ __attribute__((visibility("default"))) int pt_bake_light_pass_size(pt_scene *sc,
     const PtBakeParams bp = light_params(lp);
     if (int st = check_params(&bp)) return st;
     std::vector<uint32_t> sel;
-    if (int st = check_lights(lp, light_select, n_lights, sel)) return st;
+    if (int st = check_lights(lp->spp, lp->nsamples, light_select, n_lights, sel)) return st;
     if (int st = check_light_count(sc, n_lights)) return st;
     Geometry g;
     if (int st = bake_geometry(sc, &bp, bp.spp, g, kLightBytesPerRay)) return st;
@@ -737,67 +764,28 @@ __attribute__((visibility("default"))) int pt_bake_light_samples(pt_scene *sc, c
     if (int st = check_range(&bp, first, n_samples)) return st;
     if (int st = check_selection(prim_select, n_prims)) return st;
     std::vector<uint32_t> sel;
-    if (int st = check_lights(lp, light_select, n_lights, sel)) return st;
+    if (int st = check_lights(lp->spp, lp->nsamples, light_select, n_lights, sel)) return st;
     if (int st = check_prim_count(sc, n_prims)) return st;
     if (int st = check_light_count(sc, n_lights)) return st;   // (all of the above before the device is touched)
     Geometry g;
     if (int st = bake_geometry(sc, &bp, n_samples, g, kLightBytesPerRay)) return st;
     if (int st = begin_call(sc, bp.profile != 0)) return st;
-    const BakeAtlas &a = g.atlas;
-    const size_t n = a.n_texels;
-    DevTmp tmp;   // (freed when the call returns, however it ends)
-    uint32_t *d_selected = nullptr, n_selected = 0;
-    if (int st = upload_selection(sc, sc, prim_select, n_prims, tmp, d_selected, n_selected)) return st;
-    const bool dev = buffers_are_device != 0;
-    uint32_t *d_owner = dev ? buffers->owner : nullptr;
-    if (!d_owner) SIDE_ALLOC(tmp, d_owner, n * 4, "bake owner map");
-    if (int st = raster(sc, sc, a, d_selected, n_selected, d_owner)) return st;
-    float *d_pos = dev ? buffers->position : nullptr, *d_nrm = dev ? buffers->normal : nullptr;
-    if (buffers->position || buffers->normal) {
-        if (buffers->position && !d_pos) SIDE_ALLOC(tmp, d_pos, n * 12, "bake position plane");
-        if (buffers->normal && !d_nrm) SIDE_ALLOC(tmp, d_nrm, n * 12, "bake normal plane");
-        sc->begin("bake_points", n);
-        launch(sc, "ptbake::k_bake_points", k_bake_points, texel_grid(a), dim3(256), sc->ds, a, (const uint32_t *)d_owner, d_pos, d_nrm);
-        sc->end();
-        HIP_TRY(hipGetLastError());
+    DevTmp tmp;
+    Staging out{tmp, sc->stream, buffers_are_device != 0};
+    uint32_t *d_owner = nullptr; float4 *d_light = nullptr;
+    if (int st = atlas_frame(sc, sc, g.atlas, prim_select, n_prims, out, buffers->owner, buffers->position, buffers->normal, d_owner)) return st;
+    if (int st = out.plane(buffers->light_w, (size_t)g.atlas.n_texels * 16, "bake light plane", true, d_light)) return st;
+    if (d_light) {
+        AORayBuffers b; size_t rays; LightSamples ls;
+        if (int st = alloc_pass_rays(g, g.atlas.slots, "bake light rays", b, rays)) return st;
+        if (int st = light_samples(sc, sel, bp.nsamples, rays, "bake light rays", tmp, ls)) return st;
+        if (int st = for_passes(g, first, n_samples, [&](uint32_t s0, uint32_t sn) { return light_pass(sc, g, bp.nsamples, s0, sn, d_owner, d_light, ls, b); })) return st;
     }
-    float4 *d_light = dev ? reinterpret_cast<float4 *>(buffers->light_w) : nullptr;
-    if (buffers->light_w) {
-        if (!d_light) {
-            SIDE_ALLOC(tmp, d_light, n * 16, "bake light plane");
-            HIP_TRY(hipMemcpyAsync(d_light, buffers->light_w, n * 16, hipMemcpyHostToDevice, sc->stream));   // (added to)
-        }
-        uint32_t *d_sel = nullptr, *d_id = nullptr; float4 *d_e = nullptr;
-        if (int st = upload_lights(sc, sel, tmp, d_sel)) return st;
-        AORayBuffers b;
-        const size_t items = (size_t)a.slots * g.S;
-        if (int st = b.alloc(items, items * g.K, "bake light rays")) return st;
-        SIDE_ALLOC(tmp, d_id, items * g.K * 4, "bake light rays"); SIDE_ALLOC(tmp, d_e, items * g.K * 16, "bake light rays");
-        for (uint32_t s0 = first, end = first + n_samples; s0 < end; s0 += g.S)
-            if (int st = light_pass(sc, g, &bp, s0, std::min(g.S, end - s0), d_owner, d_light, d_sel, (uint32_t)sel.size(), d_id, d_e, b)) return st;
-    }
-    if (int st = end_call(sc)) return st;
-    if (!dev) {   // (host planes are written once everything has succeeded)
-        if (buffers->owner) HIP_TRY(hipMemcpy(buffers->owner, d_owner, n * 4, hipMemcpyDeviceToHost));
-        if (buffers->position) HIP_TRY(hipMemcpy(buffers->position, d_pos, n * 12, hipMemcpyDeviceToHost));
-        if (buffers->normal) HIP_TRY(hipMemcpy(buffers->normal, d_nrm, n * 12, hipMemcpyDeviceToHost));
-        if (buffers->light_w) HIP_TRY(hipMemcpy(buffers->light_w, d_light, n * 16, hipMemcpyDeviceToHost));
-    }
-    return PT_OK;
+    return out.finish(sc);
 }
 
 __attribute__((visibility("default"))) int pt_bake_light_resolve(const float *light_w, uint32_t n_texels, uint32_t spp, uint32_t nsamples, float *irradiance_rgb, float *reached) {
-    if (!light_w || (!irradiance_rgb && !reached)) return fail(PT_ERR_INVALID_ARG, "null argument");
-    if (spp == 0) return fail(PT_ERR_INVALID_ARG, "bake: spp must be > 0");
-    if (nsamples == 0) return fail(PT_ERR_INVALID_ARG, "bake: nsamples must be > 0");
-    const float sf = (float)spp, nf = (float)spp * (float)nsamples;
-    for (size_t i = 0; i < n_texels; ++i) {
-        const float r = light_w[4 * i], g = light_w[4 * i + 1], b = light_w[4 * i + 2], w = light_w[4 * i + 3];
-        const bool any = r != 0.0f || g != 0.0f || b != 0.0f || w != 0.0f;
-        if (irradiance_rgb) { irradiance_rgb[3 * i] = any ? r / sf : 0.0f; irradiance_rgb[3 * i + 1] = any ? g / sf : 0.0f; irradiance_rgb[3 * i + 2] = any ? b / sf : 0.0f; }
-        if (reached) reached[i] = any ? w / nf : 0.0f;
-    }
-    return PT_OK;
+    return resolve_light_sums(light_w, n_texels, 4, spp, nsamples, irradiance_rgb, reached);
 }
 
 __attribute__((visibility("default"))) int pt_bake_light_rays(pt_scene *sc, const PtBakeLightParams *lp, const uint8_t *prim_select, uint32_t n_prims, const uint8_t *light_select, uint32_t n_lights,
@@ -808,9 +796,8 @@ __attribute__((visibility("default"))) int pt_bake_light_rays(pt_scene *sc, cons
     if (int st = check_params(&bp)) return st;
     if (int st = check_selection(prim_select, n_prims)) return st;
     std::vector<uint32_t> sel;
-    if (int st = check_lights(lp, light_select, n_lights, sel)) return st;
-    for (uint32_t i = 0; i < n; ++i)
-        if (sample[i] >= bp.spp || element[i] >= bp.nsamples) return fail(PT_ERR_INVALID_ARG, "bake: ray " + std::to_string(i) + " names a sample or element outside the job");
+    if (int st = check_lights(lp->spp, lp->nsamples, light_select, n_lights, sel)) return st;
+    if (int st = check_queries(n, sample, element, bp.spp, bp.nsamples)) return st;
     if (int st = check_prim_count(sc, n_prims)) return st;
     if (int st = check_light_count(sc, n_lights)) return st;
     Geometry g;
@@ -819,38 +806,19 @@ __attribute__((visibility("default"))) int pt_bake_light_rays(pt_scene *sc, cons
     if (n == 0) return PT_OK;
     if (int st = begin_call(sc, false)) return st;
     DevTmp tmp;
-    uint32_t *d_selected = nullptr, n_selected = 0, *d_owner = nullptr, *d_in = nullptr, *d_sel = nullptr, *d_light = nullptr; float *d_out = nullptr; uint8_t *d_found = nullptr;
-    if (int st = upload_selection(sc, sc, prim_select, n_prims, tmp, d_selected, n_selected)) return st;
-    SIDE_ALLOC(tmp, d_owner, (size_t)g.atlas.n_texels * 4, "bake owner map");
-    if (int st = raster(sc, sc, g.atlas, d_selected, n_selected, d_owner)) return st;
-    if (int st = upload_lights(sc, sel, tmp, d_sel)) return st;
-    SIDE_ALLOC(tmp, d_in, (size_t)n * 12, "bake light rays"); SIDE_ALLOC(tmp, d_out, (size_t)n * 64, "bake light rays"); SIDE_ALLOC(tmp, d_light, (size_t)n * 4, "bake light rays");
-    SIDE_ALLOC(tmp, d_found, n, "bake light rays");
-    HIP_TRY(hipMemcpyAsync(d_in, texel, (size_t)n * 4, hipMemcpyHostToDevice, sc->stream));
-    HIP_TRY(hipMemcpyAsync(d_in + n, sample, (size_t)n * 4, hipMemcpyHostToDevice, sc->stream));
-    HIP_TRY(hipMemcpyAsync(d_in + 2 * (size_t)n, element, (size_t)n * 4, hipMemcpyHostToDevice, sc->stream));
-    const uint32_t n_sel = (uint32_t)sel.size();
-    const float scale = (float)n_sel / (float)bp.nsamples;
+    Staging none{tmp, sc->stream, false};
+    uint32_t *d_owner = nullptr; LightSamples ls; Queries q; LightRows rows;
+    if (int st = atlas_frame(sc, sc, g.atlas, prim_select, n_prims, none, nullptr, nullptr, nullptr, d_owner)) return st;
+    if (int st = light_samples(sc, sel, bp.nsamples, 0, "bake light rays", tmp, ls)) return st;
+    if (int st = upload_queries(sc, n, texel, sample, element, "bake light rays", tmp, q)) return st;
+    if (int st = rows.alloc(tmp, n, "bake light rays")) return st;
     sc->begin("bake_probe", n);
-    if (general_geometry(sc))
-        launch(sc, "ptbake::k_bake_light_probe<true>", k_bake_light_probe<true>, dim3((n + 255) / 256), dim3(256), sc->ds, g.rc, g_tabs, g.atlas, (const uint32_t *)d_owner, bp.nsamples, (const uint32_t *)d_sel,
-               n_sel, scale, n, (const uint32_t *)d_in, (const uint32_t *)(d_in + n), (const uint32_t *)(d_in + 2 * (size_t)n), d_light, d_out, d_found);
-    else
-        launch(sc, "ptbake::k_bake_light_probe<false>", k_bake_light_probe<false>, dim3((n + 255) / 256), dim3(256), sc->ds, g.rc, g_tabs, g.atlas, (const uint32_t *)d_owner, bp.nsamples, (const uint32_t *)d_sel,
-               n_sel, scale, n, (const uint32_t *)d_in, (const uint32_t *)(d_in + n), (const uint32_t *)(d_in + 2 * (size_t)n), d_light, d_out, d_found);
+    launch_sph(sc, "ptbake::k_bake_light_probe<true>", k_bake_light_probe<true>, "ptbake::k_bake_light_probe<false>", k_bake_light_probe<false>, dim3((n + 255) / 256), sc->ds, g.rc, g_tabs, g.atlas,
+               d_owner, bp.nsamples, ls.sel, ls.n_sel, ls.scale, n, q.item, q.sample, q.element, rows.d_light, rows.d_out, rows.d_found);
     sc->end();
     HIP_TRY(hipGetLastError());
     if (int st = end_call(sc)) return st;
-    std::vector<float> rows((size_t)n * 16);
-    HIP_TRY(hipMemcpy(rows.data(), d_out, rows.size() * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_light, d_light, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(found, d_found, n, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < n; ++i) {
-        const float *r = rows.data() + 16 * i;
-        for (int k = 0; k < 3; ++k) { out_wi[3 * i + k] = r[k]; out_li[3 * i + k] = r[4 + k]; out_e[3 * i + k] = r[7 + k]; out_o[3 * i + k] = r[10 + k]; out_d[3 * i + k] = r[13 + k]; }
-        out_pdf[i] = r[3];
-    }
-    return PT_OK;
+    return rows.read(n, out_light, out_wi, out_pdf, out_li, out_e, out_o, out_d, found);
 }
 
 // ---- the SH points
@@ -858,9 +826,7 @@ __attribute__((visibility("default"))) int pt_bake_sh_pass_size(pt_scene *sc, co
     if (!sc || !hp || !spp_per_pass) return fail(PT_ERR_INVALID_ARG, "null argument");
     if (int st = check_sh(hp)) return st;
     std::vector<uint32_t> sel;
-    PtBakeLightParams lp{};
-    lp.spp = hp->spp; lp.nsamples = hp->nsamples;
-    if (int st = check_lights(&lp, light_select, n_lights, sel, "point")) return st;
+    if (int st = check_lights(hp->spp, hp->nsamples, light_select, n_lights, sel, "point")) return st;
     if (int st = check_light_count(sc, n_lights)) return st;
     Geometry g;
     if (int st = sh_geometry(sc, hp, hp->spp, g)) return st;
@@ -885,41 +851,21 @@ __attribute__((visibility("default"))) int pt_bake_sh_samples(pt_scene *sc, cons
     Geometry g;
     if (int st = sh_geometry(sc, hp, n_samples, g)) return st;
     if (int st = begin_call(sc, hp->profile != 0)) return st;
-    const size_t n = hp->n_points;
-    DevTmp tmp;   // (freed when the call returns, however it ends)
-    const bool dev = buffers_are_device != 0;
-    float4 *d_sh = dev ? reinterpret_cast<float4 *>(sh_w) : nullptr;
-    if (!d_sh) {
-        SIDE_ALLOC(tmp, d_sh, n * 112, "bake sh sums");
-        HIP_TRY(hipMemcpyAsync(d_sh, sh_w, n * 112, hipMemcpyHostToDevice, sc->stream));   // (added to)
-    }
-    float *d_points = nullptr; uint32_t *d_sel = nullptr, *d_id = nullptr; float4 *d_e = nullptr, *d_wi = nullptr;
+    DevTmp tmp;
+    Staging out{tmp, sc->stream, buffers_are_device != 0};
+    float4 *d_sh = nullptr, *d_wi = nullptr; float *d_points = nullptr;
+    if (int st = out.plane(sh_w, (size_t)hp->n_points * 112, "bake sh sums", true, d_sh)) return st;
     if (int st = upload_points(sc, hp, points, tmp, d_points)) return st;
-    if (int st = upload_lights(sc, sel, tmp, d_sel)) return st;
-    AORayBuffers b;
-    const size_t items = (size_t)sh_padded(hp) * g.S;
-    if (int st = b.alloc(items, items * g.K, "bake sh rays")) return st;
-    SIDE_ALLOC(tmp, d_id, items * g.K * 4, "bake sh rays"); SIDE_ALLOC(tmp, d_e, items * g.K * 16, "bake sh rays"); SIDE_ALLOC(tmp, d_wi, items * g.K * 16, "bake sh rays");
-    for (uint32_t s0 = first, end = first + n_samples; s0 < end; s0 += g.S)
-        if (int st = sh_pass(sc, g, hp, s0, std::min(g.S, end - s0), d_points, d_sh, d_sel, (uint32_t)sel.size(), d_id, d_e, d_wi, b)) return st;
-    if (int st = end_call(sc)) return st;
-    if (!dev) HIP_TRY(hipMemcpy(sh_w, d_sh, n * 112, hipMemcpyDeviceToHost));   // (a host buffer is written once everything has succeeded)
-    return PT_OK;
+    AORayBuffers b; size_t rays; LightSamples ls;
+    if (int st = alloc_pass_rays(g, sh_padded(hp), "bake sh rays", b, rays)) return st;
+    if (int st = light_samples(sc, sel, hp->nsamples, rays, "bake sh rays", tmp, ls)) return st;
+    SIDE_ALLOC(tmp, d_wi, rays * 16, "bake sh rays");
+    if (int st = for_passes(g, first, n_samples, [&](uint32_t s0, uint32_t sn) { return sh_pass(sc, g, hp, s0, sn, d_points, d_sh, ls, d_wi, b); })) return st;
+    return out.finish(sc);
 }
 
 __attribute__((visibility("default"))) int pt_bake_sh_resolve(const float *sh_w, uint32_t n_points, uint32_t spp, uint32_t nsamples, float *sh, float *reached) {
-    if (!sh_w || (!sh && !reached)) return fail(PT_ERR_INVALID_ARG, "null argument");
-    if (spp == 0) return fail(PT_ERR_INVALID_ARG, "bake: spp must be > 0");
-    if (nsamples == 0) return fail(PT_ERR_INVALID_ARG, "bake: nsamples must be > 0");
-    const float sf = (float)spp, nf = (float)spp * (float)nsamples;
-    for (size_t i = 0; i < n_points; ++i) {
-        const float *w = sh_w + 28 * i;
-        bool any = false;
-        for (int m = 0; m < 28; ++m) any = any || w[m] != 0.0f;
-        if (sh) for (int m = 0; m < 27; ++m) sh[27 * i + m] = any ? w[m] / sf : 0.0f;
-        if (reached) reached[i] = any ? w[27] / nf : 0.0f;
-    }
-    return PT_OK;
+    return resolve_light_sums(sh_w, n_points, 28, spp, nsamples, sh, reached);
 }
 
 __attribute__((visibility("default"))) int pt_bake_sh_irradiance(const float *sh, const float *normals, uint32_t n, float *irradiance_rgb) {
@@ -944,8 +890,7 @@ __attribute__((visibility("default"))) int pt_bake_sh_rays(pt_scene *sc, const P
     if (int st = check_sh(hp)) return st;
     std::vector<uint32_t> sel;
     if (int st = check_sh_points_and_lights(hp, points, light_select, n_lights, sel)) return st;
-    for (uint32_t i = 0; i < n; ++i)
-        if (sample[i] >= hp->spp || element[i] >= hp->nsamples) return fail(PT_ERR_INVALID_ARG, "bake: ray " + std::to_string(i) + " names a sample or element outside the job");
+    if (int st = check_queries(n, sample, element, hp->spp, hp->nsamples)) return st;
     if (int st = check_light_count(sc, n_lights)) return st;
     Geometry g;
     PtBakeShParams one = *hp; one.spp_per_pass = 1;
@@ -953,36 +898,18 @@ __attribute__((visibility("default"))) int pt_bake_sh_rays(pt_scene *sc, const P
     if (n == 0) return PT_OK;
     if (int st = begin_call(sc, false)) return st;
     DevTmp tmp;
-    float *d_points = nullptr, *d_out = nullptr; uint32_t *d_in = nullptr, *d_sel = nullptr, *d_light = nullptr; uint8_t *d_found = nullptr;
+    float *d_points = nullptr; LightSamples ls; Queries q; LightRows rows;
     if (int st = upload_points(sc, hp, points, tmp, d_points)) return st;
-    if (int st = upload_lights(sc, sel, tmp, d_sel)) return st;
-    SIDE_ALLOC(tmp, d_in, (size_t)n * 12, "bake sh rays"); SIDE_ALLOC(tmp, d_out, (size_t)n * 64, "bake sh rays"); SIDE_ALLOC(tmp, d_light, (size_t)n * 4, "bake sh rays");
-    SIDE_ALLOC(tmp, d_found, n, "bake sh rays");
-    HIP_TRY(hipMemcpyAsync(d_in, point, (size_t)n * 4, hipMemcpyHostToDevice, sc->stream));
-    HIP_TRY(hipMemcpyAsync(d_in + n, sample, (size_t)n * 4, hipMemcpyHostToDevice, sc->stream));
-    HIP_TRY(hipMemcpyAsync(d_in + 2 * (size_t)n, element, (size_t)n * 4, hipMemcpyHostToDevice, sc->stream));
-    const uint32_t n_sel = (uint32_t)sel.size();
-    const float scale = (float)n_sel / (float)hp->nsamples;
+    if (int st = light_samples(sc, sel, hp->nsamples, 0, "bake sh rays", tmp, ls)) return st;
+    if (int st = upload_queries(sc, n, point, sample, element, "bake sh rays", tmp, q)) return st;
+    if (int st = rows.alloc(tmp, n, "bake sh rays")) return st;
     sc->begin("bake_probe", n);
-    if (general_geometry(sc))
-        launch(sc, "ptbake::k_bake_sh_probe<true>", k_bake_sh_probe<true>, dim3((n + 255) / 256), dim3(256), sc->ds, g.rc, g_tabs, (const float *)d_points, hp->n_points, hp->row, hp->nsamples,
-               (const uint32_t *)d_sel, n_sel, scale, n, (const uint32_t *)d_in, (const uint32_t *)(d_in + n), (const uint32_t *)(d_in + 2 * (size_t)n), d_light, d_out, d_found);
-    else
-        launch(sc, "ptbake::k_bake_sh_probe<false>", k_bake_sh_probe<false>, dim3((n + 255) / 256), dim3(256), sc->ds, g.rc, g_tabs, (const float *)d_points, hp->n_points, hp->row, hp->nsamples,
-               (const uint32_t *)d_sel, n_sel, scale, n, (const uint32_t *)d_in, (const uint32_t *)(d_in + n), (const uint32_t *)(d_in + 2 * (size_t)n), d_light, d_out, d_found);
+    launch_sph(sc, "ptbake::k_bake_sh_probe<true>", k_bake_sh_probe<true>, "ptbake::k_bake_sh_probe<false>", k_bake_sh_probe<false>, dim3((n + 255) / 256), sc->ds, g.rc, g_tabs, d_points, hp->n_points,
+               hp->row, hp->nsamples, ls.sel, ls.n_sel, ls.scale, n, q.item, q.sample, q.element, rows.d_light, rows.d_out, rows.d_found);
     sc->end();
     HIP_TRY(hipGetLastError());
     if (int st = end_call(sc)) return st;
-    std::vector<float> rows((size_t)n * 16);
-    HIP_TRY(hipMemcpy(rows.data(), d_out, rows.size() * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_light, d_light, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(found, d_found, n, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < n; ++i) {
-        const float *r = rows.data() + 16 * i;
-        for (int k = 0; k < 3; ++k) { out_wi[3 * i + k] = r[k]; out_li[3 * i + k] = r[4 + k]; out_e[3 * i + k] = r[7 + k]; out_o[3 * i + k] = r[10 + k]; out_d[3 * i + k] = r[13 + k]; }
-        out_pdf[i] = r[3];
-    }
-    return PT_OK;
+    return rows.read(n, out_light, out_wi, out_pdf, out_li, out_e, out_o, out_d, found);
 }
 
 }  // extern "C"

@@ -85,6 +85,14 @@ def _fptr(a):
     return a.ctypes.data_as(A.fp)
 
 
+def _sampler_code(sampler):
+    return {"sobol": A.PT_SAMPLER_SOBOL, "halton": A.PT_SAMPLER_HALTON}[sampler]
+
+
+# what pt_bake_light_rays and pt_bake_sh_rays return per light sample, in their order: (key, is a 3-vector)
+_LIGHT_SAMPLE = (("wi", True), ("pdf", False), ("Li", True), ("E", True), ("o", True), ("d", True))
+
+
 def film_shape(rp):
     """(h, w) of the film of the job `rp`: its cropped pixel window."""
     cb = rp.cropped_pixel_bounds
@@ -567,9 +575,44 @@ class Scene(Handle):
         group = np.asarray(self.data.prim_group)
         return np.ascontiguousarray(np.isin(group, ordinals), dtype=np.uint8)
 
+    def _bake_planes(self, kind, name, head, width, height, planes, samples, sums, device_ptrs):
+        """What bake, bake_light and bake_transfer share: pt_<name> -- with `samples` = (first, n): pt_<name>_samples -- of the arguments `head` into the planes
+        `planes` of BAKE.PLANE_TABLES[kind], each (H, W, channels) or, with one channel, (H, W). A plane `sums` does not hold yet starts from zeros; `device_ptrs` =
+        {plane: device pointer as an integer}: the planes go to those buffers, returns None."""
+        args = list(head) + ([] if samples is None else list(samples))
+        name = name if samples is None else name + "_samples"
+        struct = BAKE.BUFFERS[kind]
+        if device_ptrs is not None:
+            self._call(name, *args, C.byref(BAKE.buffers(device_ptrs, True, struct)), 1, lib=self.L.bake); return None
+        if sums is None:
+            sums = {}
+        for k in planes:
+            if k not in sums:
+                channels, dtype = BAKE.PLANE_TABLES[kind][k]
+                sums[k] = np.zeros((height, width) + ((channels,) if channels > 1 else ()), dtype=dtype)
+        self._call(name, *args, C.byref(BAKE.buffers({k: sums[k] for k in planes}, False, struct)), 0, lib=self.L.bake)
+        return sums
+
+    def _bake_probe(self, name, head, queries, floats, light=False):
+        """What the four *_rays methods share: pt_<name> of the arguments `head` for the queries named by the three index arrays `queries`. Returns a dict of the
+        outputs: `floats` = ((key, is a 3-vector), ...) in the entry point's order, "found" (n,) uint8 and, with `light`, "light" (n,) uint32 ahead of them."""
+        queries = [np.ascontiguousarray(v, dtype=np.uint32) for v in queries]
+        n = len(queries[0])
+        r = {k: np.zeros((n, 3) if vector else n, np.float32) for k, vector in floats}
+        r["found"] = np.zeros(n, np.uint8)
+        if light:
+            r["light"] = np.zeros(n, np.uint32)
+        self._call(name, *head, n, *[v.ctypes.data_as(A.u32p) for v in queries], *([r["light"].ctypes.data_as(A.u32p)] if light else []), *[_fptr(r[k]) for k, _ in floats],
+                   r["found"].ctypes.data_as(A.u8p), lib=self.L.bake)
+        return r
+
+    def _light_selection(self, lights, nsamples):
+        """((light_select pointer or None, n_lights) as pt_bake_light* and pt_bake_sh* take them, the light samples per sample: `nsamples`, None = one per selected light)"""
+        lsel, n_lights, n_sel = self.bake_light_select(lights)
+        return (None if lsel is None else lsel.ctypes.data_as(A.u8p), n_lights), n_sel if nsamples is None else nsamples
+
     def bake_params(self, width, height, spp, nsamples=64, cos_sample=True, max_distance=float("inf"), sampler="sobol", spp_per_pass=0, profile=False):
-        return BAKE.PtBakeParams(width, height, spp, nsamples, 1 if cos_sample else 0, max_distance, {"sobol": A.PT_SAMPLER_SOBOL, "halton": A.PT_SAMPLER_HALTON}[sampler],
-                                 spp_per_pass, 1 if profile else 0)
+        return BAKE.PtBakeParams(width, height, spp, nsamples, 1 if cos_sample else 0, max_distance, _sampler_code(sampler), spp_per_pass, 1 if profile else 0)
 
     def bake(self, select, width, height, spp, nsamples=64, cos_sample=True, max_distance=float("inf"), sampler="sobol", samples=None, sums=None, device_ptrs=None,
              planes=BAKE.PLANES, spp_per_pass=0, profile=False):
@@ -580,17 +623,8 @@ class Scene(Handle):
         leaves. `device_ptrs` = {plane: device pointer as an integer}: the planes go to those buffers, returns None."""
         bp = self.bake_params(width, height, spp, nsamples, cos_sample, max_distance, sampler, spp_per_pass, profile)
         sel = self.bake_select(select)
-        args = [self.h, C.byref(bp), sel.ctypes.data_as(A.u8p), len(sel)] + ([] if samples is None else list(samples))
-        name = "bake_render" if samples is None else "bake_render_samples"
-        if device_ptrs is not None:
-            self._call(name, *args, C.byref(BAKE.buffers(device_ptrs, device=True)), 1, lib=self.L.bake); return None
-        if sums is None:
-            sums = {}
-        for k in planes:
-            if k not in sums:
-                sums[k] = np.zeros((height, width) + ((BAKE.CHANNELS[k],) if k != "owner" else ()), dtype=BAKE.DTYPES[k])
-        self._call(name, *args, C.byref(BAKE.buffers(sums)), 0, lib=self.L.bake)
-        return sums
+        planes = tuple(planes) + tuple(k for k in (sums or {}) if k not in planes)   # (every plane `sums` holds is baked, as it always was)
+        return self._bake_planes("bake", "bake_render", [self.h, C.byref(bp), sel.ctypes.data_as(A.u8p), len(sel)], width, height, planes, samples, sums, device_ptrs)
 
     def bake_pass_size(self, width, height, spp, nsamples=64, sampler="sobol", spp_per_pass=0):
         """Samples per texel per pass pt_bake_render would use now."""
@@ -616,12 +650,8 @@ class Scene(Handle):
         """pt_bake_rays: (origin (n, 3), direction (n, 3), weight (n,), found (n,) uint8) of the AO rays named by the arrays texel / sample / element."""
         bp = self.bake_params(width, height, spp, nsamples, cos_sample, max_distance, sampler)
         sel = self.bake_select(select)
-        texel, sample, element = (np.ascontiguousarray(v, dtype=np.uint32) for v in (texel, sample, element))
-        n = len(texel)
-        o = np.zeros((n, 3), np.float32); d = np.zeros((n, 3), np.float32); w = np.zeros(n, np.float32); found = np.zeros(n, np.uint8)
-        self._call("bake_rays", self.h, C.byref(bp), sel.ctypes.data_as(A.u8p), len(sel), n, texel.ctypes.data_as(A.u32p), sample.ctypes.data_as(A.u32p),
-                   element.ctypes.data_as(A.u32p), _fptr(o), _fptr(d), _fptr(w), found.ctypes.data_as(A.u8p), lib=self.L.bake)
-        return o, d, w, found
+        r = self._bake_probe("bake_rays", [self.h, C.byref(bp), sel.ctypes.data_as(A.u8p), len(sel)], (texel, sample, element), (("o", True), ("d", True), ("w", False)))
+        return r["o"], r["d"], r["w"], r["found"]
 
     def bake_light_select(self, lights):
         """(light_select bytes or None, n_lights, n_sel) of pt_bake_light*: `lights` is None (all of the scene's lights), a list of light indices in the scene's
@@ -637,7 +667,7 @@ class Scene(Handle):
         return sel, len(sel), int(np.count_nonzero(sel))
 
     def bake_light_params(self, width, height, spp, nsamples, sampler="sobol", spp_per_pass=0, profile=False):
-        return BAKE.PtBakeLightParams(width, height, spp, nsamples, {"sobol": A.PT_SAMPLER_SOBOL, "halton": A.PT_SAMPLER_HALTON}[sampler], spp_per_pass, 1 if profile else 0)
+        return BAKE.PtBakeLightParams(width, height, spp, nsamples, _sampler_code(sampler), spp_per_pass, 1 if profile else 0)
 
     def bake_light(self, select, width, height, spp, nsamples=None, lights=None, sampler="sobol", samples=None, sums=None, device_ptrs=None, planes=BAKE.LIGHT_PLANES,
                    spp_per_pass=0, profile=False):
@@ -646,40 +676,22 @@ class Scene(Handle):
         of what the unoccluded light samples add and their count (resolve_lightmap turns them into the irradiance map). `nsamples` light samples per sample, None: one
         per selected light. light_w is ADDED to the array of `sums` as Scene.bake does. `device_ptrs` = {plane: device pointer}: returns None."""
         sel = self.bake_select(select)
-        lsel, n_lights, n_sel = self.bake_light_select(lights)
-        lp = self.bake_light_params(width, height, spp, n_sel if nsamples is None else nsamples, sampler, spp_per_pass, profile)
-        args = [self.h, C.byref(lp), sel.ctypes.data_as(A.u8p), len(sel), None if lsel is None else lsel.ctypes.data_as(A.u8p), n_lights] + ([] if samples is None else list(samples))
-        name = "bake_light" if samples is None else "bake_light_samples"
-        if device_ptrs is not None:
-            self._call(name, *args, C.byref(BAKE.light_buffers(device_ptrs, device=True)), 1, lib=self.L.bake); return None
-        if sums is None:
-            sums = {}
-        for k in planes:
-            if k not in sums:
-                sums[k] = np.zeros((height, width) + ((BAKE.LIGHT_CHANNELS[k],) if k != "owner" else ()), dtype=BAKE.LIGHT_DTYPES[k])
-        self._call(name, *args, C.byref(BAKE.light_buffers({k: sums[k] for k in planes})), 0, lib=self.L.bake)
-        return sums
+        light_args, nsamples = self._light_selection(lights, nsamples)
+        lp = self.bake_light_params(width, height, spp, nsamples, sampler, spp_per_pass, profile)
+        return self._bake_planes("light", "bake_light", [self.h, C.byref(lp), sel.ctypes.data_as(A.u8p), len(sel), *light_args], width, height, planes, samples, sums, device_ptrs)
 
     def bake_light_pass_size(self, width, height, spp, nsamples=None, lights=None, sampler="sobol", spp_per_pass=0):
         """Samples per texel per pass pt_bake_light would use now."""
-        lsel, n_lights, n_sel = self.bake_light_select(lights)
-        lp = self.bake_light_params(width, height, spp, n_sel if nsamples is None else nsamples, sampler, spp_per_pass)
-        return self._pass_size("bake_light_pass_size", C.byref(lp), None if lsel is None else lsel.ctypes.data_as(A.u8p), n_lights, lib=self.L.bake)
+        light_args, nsamples = self._light_selection(lights, nsamples)
+        return self._pass_size("bake_light_pass_size", C.byref(self.bake_light_params(width, height, spp, nsamples, sampler, spp_per_pass)), *light_args, lib=self.L.bake)
 
     def bake_light_rays(self, select, width, height, spp, texel, sample, element, nsamples=None, lights=None, sampler="sobol"):
         """pt_bake_light_rays: dict(light (n,) uint32, wi (n, 3), pdf (n,), Li (n, 3), E (n, 3), o (n, 3), d (n, 3), found (n,) uint8: bit 0 the texel has an owner,
         bit 1 the sample contributes and (o, d) is its shadow ray) of the light samples named by the arrays texel / sample / element."""
         sel = self.bake_select(select)
-        lsel, n_lights, n_sel = self.bake_light_select(lights)
-        lp = self.bake_light_params(width, height, spp, n_sel if nsamples is None else nsamples, sampler)
-        texel, sample, element = (np.ascontiguousarray(v, dtype=np.uint32) for v in (texel, sample, element))
-        n = len(texel)
-        r = {k: np.zeros((n, 3), np.float32) for k in ("wi", "Li", "E", "o", "d")}
-        r.update(light=np.zeros(n, np.uint32), pdf=np.zeros(n, np.float32), found=np.zeros(n, np.uint8))
-        self._call("bake_light_rays", self.h, C.byref(lp), sel.ctypes.data_as(A.u8p), len(sel), None if lsel is None else lsel.ctypes.data_as(A.u8p), n_lights, n,
-                   texel.ctypes.data_as(A.u32p), sample.ctypes.data_as(A.u32p), element.ctypes.data_as(A.u32p), r["light"].ctypes.data_as(A.u32p),
-                   *[_fptr(r[k]) for k in ("wi", "pdf", "Li", "E", "o", "d")], r["found"].ctypes.data_as(A.u8p), lib=self.L.bake)
-        return r
+        light_args, nsamples = self._light_selection(lights, nsamples)
+        lp = self.bake_light_params(width, height, spp, nsamples, sampler)
+        return self._bake_probe("bake_light_rays", [self.h, C.byref(lp), sel.ctypes.data_as(A.u8p), len(sel), *light_args], (texel, sample, element), _LIGHT_SAMPLE, light=True)
 
     def bake_sh_params(self, points, spp, nsamples, sampler="sobol", row=None, spp_per_pass=0, profile=False):
         """(the points as a contiguous (n, 3) float32 array, the PtBakeShParams): `row` None = ceil(sqrt(n))."""
@@ -688,7 +700,7 @@ class Scene(Handle):
         if row is None:
             row = max(1, math.isqrt(n))
             row += row * row < n
-        return points, BAKE.PtBakeShParams(n, row, spp, nsamples, {"sobol": A.PT_SAMPLER_SOBOL, "halton": A.PT_SAMPLER_HALTON}[sampler], spp_per_pass, 1 if profile else 0)
+        return points, BAKE.PtBakeShParams(n, row, spp, nsamples, _sampler_code(sampler), spp_per_pass, 1 if profile else 0)
 
     def bake_sh(self, points, spp, nsamples=None, lights=None, sampler="sobol", row=None, samples=None, sums=None, device_ptr=None, spp_per_pass=0, profile=False):
         """pt_bake_sh: the direct light of the lights `lights` names (bake_light_select; None: all) at the free points `points` (n, 3), as sums over the nine order-2
@@ -696,9 +708,9 @@ class Scene(Handle):
         count of light samples that arrived (resolve_sh turns them into the coefficients, sh_irradiance evaluates those for a normal). `nsamples` light samples per
         sample, None: one per selected light. Point i is pixel (i mod row, i / row) of the sampler. The sums are ADDED to the array `sums` (what this method
         returned) when given, in place. `device_ptr`: sh_w is a device pointer as an integer, returns None."""
-        lsel, n_lights, n_sel = self.bake_light_select(lights)
-        points, hp = self.bake_sh_params(points, spp, n_sel if nsamples is None else nsamples, sampler, row, spp_per_pass, profile)
-        args = [self.h, C.byref(hp), _fptr(points), None if lsel is None else lsel.ctypes.data_as(A.u8p), n_lights] + ([] if samples is None else list(samples))
+        light_args, nsamples = self._light_selection(lights, nsamples)
+        points, hp = self.bake_sh_params(points, spp, nsamples, sampler, row, spp_per_pass, profile)
+        args = [self.h, C.byref(hp), _fptr(points), *light_args] + ([] if samples is None else list(samples))
         name = "bake_sh" if samples is None else "bake_sh_samples"
         if device_ptr is not None:
             self._call(name, *args, C.cast(C.c_void_p(device_ptr), A.fp), 1, lib=self.L.bake); return None
@@ -711,27 +723,19 @@ class Scene(Handle):
 
     def bake_sh_pass_size(self, n_points, spp, nsamples=None, lights=None, sampler="sobol", row=None, spp_per_pass=0):
         """Samples per point per pass pt_bake_sh would use now."""
-        lsel, n_lights, n_sel = self.bake_light_select(lights)
-        _, hp = self.bake_sh_params(np.zeros((n_points, 3), np.float32), spp, n_sel if nsamples is None else nsamples, sampler, row, spp_per_pass)
-        return self._pass_size("bake_sh_pass_size", C.byref(hp), None if lsel is None else lsel.ctypes.data_as(A.u8p), n_lights, lib=self.L.bake)
+        light_args, nsamples = self._light_selection(lights, nsamples)
+        _, hp = self.bake_sh_params(np.zeros((n_points, 3), np.float32), spp, nsamples, sampler, row, spp_per_pass)
+        return self._pass_size("bake_sh_pass_size", C.byref(hp), *light_args, lib=self.L.bake)
 
     def bake_sh_rays(self, points, spp, point, sample, element, nsamples=None, lights=None, sampler="sobol", row=None):
         """pt_bake_sh_rays: dict(light (n,) uint32, wi (n, 3), pdf (n,), Li (n, 3), E (n, 3), o (n, 3), d (n, 3), found (n,) uint8: bit 0 the point index is below
         the point count, bit 1 the sample contributes and (o, d) is its shadow ray) of the light samples named by the arrays point / sample / element."""
-        lsel, n_lights, n_sel = self.bake_light_select(lights)
-        points, hp = self.bake_sh_params(points, spp, n_sel if nsamples is None else nsamples, sampler, row)
-        point, sample, element = (np.ascontiguousarray(v, dtype=np.uint32) for v in (point, sample, element))
-        n = len(point)
-        r = {k: np.zeros((n, 3), np.float32) for k in ("wi", "Li", "E", "o", "d")}
-        r.update(light=np.zeros(n, np.uint32), pdf=np.zeros(n, np.float32), found=np.zeros(n, np.uint8))
-        self._call("bake_sh_rays", self.h, C.byref(hp), _fptr(points), None if lsel is None else lsel.ctypes.data_as(A.u8p), n_lights, n,
-                   point.ctypes.data_as(A.u32p), sample.ctypes.data_as(A.u32p), element.ctypes.data_as(A.u32p), r["light"].ctypes.data_as(A.u32p),
-                   *[_fptr(r[k]) for k in ("wi", "pdf", "Li", "E", "o", "d")], r["found"].ctypes.data_as(A.u8p), lib=self.L.bake)
-        return r
+        light_args, nsamples = self._light_selection(lights, nsamples)
+        points, hp = self.bake_sh_params(points, spp, nsamples, sampler, row)
+        return self._bake_probe("bake_sh_rays", [self.h, C.byref(hp), _fptr(points), *light_args], (point, sample, element), _LIGHT_SAMPLE, light=True)
 
     def bake_transfer_params(self, width, height, front, back, spp=1, nsamples=64, cos_sample=True, max_distance=float("inf"), sampler="sobol", spp_per_pass=0, profile=False):
-        return BAKE.PtBakeTransferParams(width, height, front, back, spp, nsamples, 1 if cos_sample else 0, max_distance, {"sobol": A.PT_SAMPLER_SOBOL, "halton": A.PT_SAMPLER_HALTON}[sampler],
-                                         spp_per_pass, 1 if profile else 0)
+        return BAKE.PtBakeTransferParams(width, height, front, back, spp, nsamples, 1 if cos_sample else 0, max_distance, _sampler_code(sampler), spp_per_pass, 1 if profile else 0)
 
     def bake_transfer(self, source, select, width, height, front, back, spp=1, nsamples=64, cos_sample=True, max_distance=float("inf"), sampler="sobol", spp_per_pass=0, profile=False,
                       planes=BAKE.TRANSFER_PLANES, samples=None, sums=None, device_ptrs=None):
@@ -741,17 +745,7 @@ class Scene(Handle):
         to the array of `sums` as Scene.bake does. Counters and kernel statistics of the call are `source`'s. `device_ptrs` = {plane: device pointer}: returns None."""
         tp = self.bake_transfer_params(width, height, front, back, spp, nsamples, cos_sample, max_distance, sampler, spp_per_pass, profile)
         sel = self.bake_select(select)
-        args = [self.h, source.h, C.byref(tp), sel.ctypes.data_as(A.u8p), len(sel)] + ([] if samples is None else list(samples))
-        name = "bake_transfer" if samples is None else "bake_transfer_samples"
-        if device_ptrs is not None:
-            self._call(name, *args, C.byref(BAKE.transfer_buffers(device_ptrs, device=True)), 1, lib=self.L.bake); return None
-        if sums is None:
-            sums = {}
-        for k in planes:
-            if k not in sums:
-                sums[k] = np.zeros((height, width) + ((BAKE.TRANSFER_CHANNELS[k],) if BAKE.TRANSFER_CHANNELS[k] > 1 else ()), dtype=BAKE.TRANSFER_DTYPES[k])
-        self._call(name, *args, C.byref(BAKE.transfer_buffers({k: sums[k] for k in planes})), 0, lib=self.L.bake)
-        return sums
+        return self._bake_planes("transfer", "bake_transfer", [self.h, source.h, C.byref(tp), sel.ctypes.data_as(A.u8p), len(sel)], width, height, planes, samples, sums, device_ptrs)
 
     def bake_transfer_pass_size(self, source, width, height, front, back, spp, nsamples=64, sampler="sobol", spp_per_pass=0):
         """AO samples per texel per pass pt_bake_transfer would use now."""
@@ -763,13 +757,8 @@ class Scene(Handle):
         uint8: bit 0 the texel has an owner, bit 1 a detail hit)."""
         tp = self.bake_transfer_params(width, height, front, back, spp, nsamples, cos_sample, max_distance, sampler)
         sel = self.bake_select(select)
-        texel, sample, element = (np.ascontiguousarray(v, dtype=np.uint32) for v in (texel, sample, element))
-        n = len(texel)
-        r = dict(o=np.zeros((n, 3), np.float32), d=np.zeros((n, 3), np.float32), t_max=np.zeros(n, np.float32), ao_o=np.zeros((n, 3), np.float32), ao_d=np.zeros((n, 3), np.float32),
-                 ao_w=np.zeros(n, np.float32), found=np.zeros(n, np.uint8))
-        self._call("bake_transfer_rays", self.h, source.h, C.byref(tp), sel.ctypes.data_as(A.u8p), len(sel), n, texel.ctypes.data_as(A.u32p), sample.ctypes.data_as(A.u32p),
-                   element.ctypes.data_as(A.u32p), *[_fptr(r[k]) for k in ("o", "d", "t_max", "ao_o", "ao_d", "ao_w")], r["found"].ctypes.data_as(A.u8p), lib=self.L.bake)
-        return r
+        return self._bake_probe("bake_transfer_rays", [self.h, source.h, C.byref(tp), sel.ctypes.data_as(A.u8p), len(sel)], (texel, sample, element),
+                                (("o", True), ("d", True), ("t_max", False), ("ao_o", True), ("ao_d", True), ("ao_w", False)))
 
     def ao_params(self):
         """The scene's PtAOParams (SceneBuilder.integ / the front end's "ambientocclusion" parameters)."""
