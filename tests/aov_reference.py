@@ -9,9 +9,9 @@ import ctypes as C
 import math
 
 import numpy as np
+import camera_model
+from model_math import F, NONE, cross, dm_map, dm_sin, dot, normalize, transform_ray, xf_normal_inv
 
-F = np.float32
-NONE = 0xFFFFFFFF
 XRES, YRES, SPP = 32, 24, 4
 _norm = lambda v: tuple(float(x) for x in np.asarray(v, np.float64) / np.linalg.norm(v))
 LIGHTS = (_norm((0.3, 1.0, 0.1)), _norm((-0.2, 1.0, 0.25)), _norm((0.05, 1.0, -0.3)))
@@ -101,29 +101,17 @@ def film_rgb_sums(pkg, film):
 
 # ---- identity 3: the oracle's first hits -> numpy sums ------------------------------------------------------------------------------------------------------------
 
+def oracle_rays(oracle, rp, cs):
+    """orc_camera_rays: the oracle's own (perspective) camera for the camera samples cs (N, 5)."""
+    fp = oracle.A.fp
+    o = np.zeros((len(cs), 3), F); d = np.zeros((len(cs), 3), F)
+    assert oracle.lib.orc_camera_rays(C.byref(rp), len(cs), cs.ctypes.data_as(fp), o.ctypes.data_as(fp), d.ctypes.data_as(fp)) == 0
+    return o, d
+
+
 def camera_hits(pkg, oracle, orc, rp, first=0, n=None):
-    """The camera samples [first, first + n) of every pixel of rp's sample bounds, in the oracle's words: dict(pix (N, 2), pfilm (N, 2), o, d (N, 3), prim, t, b), pixel
-    major and sample minor. `orc`: the oracle's scene."""
-    A = pkg._abi
-    n = rp.spp - first if n is None else n
-    sb = rp.sample_bounds
-    xs, ys = np.meshgrid(np.arange(sb[0], sb[2]), np.arange(sb[1], sb[3]), indexing="xy")
-    pix = np.repeat(np.stack([xs.ravel(), ys.ravel()], 1).astype(np.int32), n, axis=0)
-    sn = np.tile(np.arange(first, first + n, dtype=np.uint32), len(pix) // n)
-    N = len(pix)
-    pix = np.ascontiguousarray(pix); sn = np.ascontiguousarray(sn)
-    dims = np.zeros((N, 5), F)
-    sbc = (C.c_int32 * 4)(*sb)
-    if rp.sampler_type == A.PT_SAMPLER_HALTON:
-        assert oracle.lib.orc_halton_samples(sbc, rp.sample_at_pixel_center, N, pix.ctypes.data_as(A.i32p), sn.ctypes.data_as(A.u32p), 5, dims.ctypes.data_as(A.fp), None) == 0
-    else:
-        assert oracle.lib.orc_sobol_samples(sbc, N, pix.ctypes.data_as(A.i32p), sn.ctypes.data_as(A.u32p), 5, dims.ctypes.data_as(A.fp), None) == 0
-    cs = dims.copy()
-    cs[:, :2] = pix.astype(F) + dims[:, :2]   # get_camera_sample: p_film = pixel + get_2d() (sampler.rs:170-180)
-    o = np.zeros((N, 3), F); d = np.zeros((N, 3), F)
-    assert oracle.lib.orc_camera_rays(C.byref(rp), N, cs.ctypes.data_as(A.fp), o.ctypes.data_as(A.fp), d.ctypes.data_as(A.fp)) == 0
-    prim, t, b = orc.trace_closest(o, d, np.full(N, np.inf, F))
-    return dict(pix=pix, pfilm=cs[:, :2].copy(), o=o, d=d, prim=prim, t=t, b=b, n=n)
+    """camera_model.camera_hits in the oracle's words throughout: its samplers' camera samples, its camera's rays, its first hits."""
+    return camera_model.camera_hits(pkg, oracle, orc, rp, first, n, oracle_rays)
 
 
 def hit_fractions(h):
@@ -171,62 +159,9 @@ def leaf_albedo(pkg, sd, mi):
     return None if tex(A.PT_MP_KD) else v(m.kd)
 
 
-# float32 arithmetic as the device and the oracle write it (dev_math.h / ref_math.h): products and sums left to right, cross products through double, a vector divided
-# by its length multiplied by the reciprocal. A normal formed this way is the device's bit for bit -- a sphere's, near its poles, is many ulps from the radial direction
-# (sphere.rs:160-176 forms it from sin(acos(z / r))), which is the reference's normal all the same.
-_G3 = F(3 * 2.0 ** -24) / (F(1.0) - F(3 * 2.0 ** -24))   # gamma(3)
-
-
-def _xf_point_err32(m, p):
-    x, y, z = p[:, 0], p[:, 1], p[:, 2]
-    M = lambda k: m[..., k]
-    out = np.stack([x * M(0) + y * M(1) + z * M(2) + M(3), x * M(4) + y * M(5) + z * M(6) + M(7), x * M(8) + y * M(9) + z * M(10) + M(11)], 1)
-    err = np.stack([np.abs(x * M(0)) + np.abs(y * M(1)) + np.abs(z * M(2)) + np.abs(M(3)), np.abs(x * M(4)) + np.abs(y * M(5)) + np.abs(z * M(6)) + np.abs(M(7)),
-                    np.abs(x * M(8)) + np.abs(y * M(9)) + np.abs(z * M(10)) + np.abs(M(11))], 1) * _G3
-    return out.astype(F), err.astype(F)
-
-
-def _xf_vector32(m, v):
-    x, y, z = v[:, 0], v[:, 1], v[:, 2]
-    M = lambda k: m[..., k]
-    return np.stack([x * M(0) + y * M(1) + z * M(2), x * M(4) + y * M(5) + z * M(6), x * M(8) + y * M(9) + z * M(10)], 1).astype(F)
-
-
-def _xf_normal_inv32(minv, n):
-    x, y, z = n[:, 0], n[:, 1], n[:, 2]
-    M = lambda k: minv[..., k]
-    return np.stack([x * M(0) + y * M(4) + z * M(8), x * M(1) + y * M(5) + z * M(9), x * M(2) + y * M(6) + z * M(10)], 1).astype(F)
-
-
-def _dot32(a, b):
-    return a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1] + a[:, 2] * b[:, 2]
-
-
-def _normalize32(a):
-    return (a * (F(1.0) / np.sqrt(_dot32(a, a)))[:, None]).astype(F)
-
-
-def _cross32(a, b):
-    a, b = a.astype(np.float64), b.astype(np.float64)
-    return np.stack([a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1], a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2], a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]], 1).astype(F)
-
-
-def _ray_into32(m, o, d):
-    """A ray into the space of the transform m (Transform::transform_ray, transform.rs:565-575): the origin moved along the ray by its error bound."""
-    o2, oerr = _xf_point_err32(m, o)
-    d2 = _xf_vector32(m, d)
-    l2 = _dot32(d2, d2)
-    dt = np.where(l2 > 0, _dot32(np.abs(d2), oerr) / np.where(l2 > 0, l2, F(1.0)), F(0.0)).astype(F)
-    return (o2 + d2 * dt[:, None]).astype(F), d2
-
-
-def _map32(fn, x):
-    return np.array([fn(float(v)) for v in x], F)
-
-
 def sample_values(pkg, oracle, sd, h):
     """Per camera sample of camera_hits: hit (bool), albedo (N, 3; NaN where the material's parameters are textured), the shading normal facing the camera (N, 3) and
-    smooth (bool). The normal of a flat triangle, a sphere or a disk is formed in the device's own float32 arithmetic (above), through the instance the hit lies in --
+    smooth (bool). The normal of a flat triangle, a sphere or a disk is formed in the device's own float32 arithmetic (tests/model_math.py), through the instance the hit lies in --
     the one of the primitive's object that maps the hit point back onto the primitive. A triangle with vertex normals (smooth) gets normalize(sum of b_i N_i) in
     float64: its shading normal is that direction renormalised three times over (triangle.rs:300-345), which identity 2 holds against the oracle."""
     A = pkg._abi
@@ -278,16 +213,16 @@ def sample_values(pkg, oracle, sd, h):
             best = res.argmin(axis=0)
             w2i[sel] = np.stack([np.array(list(I.world_to_instance), F) for I in cands])[best]
             through[sel] = np.array([not np.array_equal(np.array(list(I.instance_to_world), F), eye) for I in cands])[best]
-    lo, ld = _ray_into32(w2i, o32, d32)   # TransformedPrimitive::intersect (primitive.rs:58-80)
+    lo, ld = transform_ray(w2i, o32, d32)   # TransformedPrimitive::intersect (primitive.rs:58-80)
     lo, ld = np.where(through[:, None], lo, o32), np.where(through[:, None], ld, d32)
     n32 = np.zeros((n, 3), F)
     if tri.any():
         P32 = sd.P
-        n32[tri] = _normalize32(_cross32(P32[vid[:, 0]] - P32[vid[:, 2]], P32[vid[:, 1]] - P32[vid[:, 2]]))   # triangle.rs:283
+        n32[tri] = normalize(cross(P32[vid[:, 0]] - P32[vid[:, 2]], P32[vid[:, 1]] - P32[vid[:, 2]]))   # triangle.rs:283
     for k, (S, _) in quadrics.items():
         m = (~tri) & (index == k)
         w2o = np.array(list(S.world_to_object), F)
-        so, sdir = _ray_into32(w2o, lo[m], ld[m])
+        so, sdir = transform_ray(w2o, lo[m], ld[m])
         ph = (so + sdir * t32[m][:, None]).astype(F)
         r, phi_max = F(S.radius), F(S.phi_max)
         if S.kind == A.PT_QUADRIC_DISK:   # disk.rs:78-96
@@ -295,18 +230,18 @@ def sample_values(pkg, oracle, sd, h):
             dpdu = np.stack([-phi_max * ph[:, 1], phi_max * ph[:, 0], np.zeros_like(r_hit)], 1)
             flat = np.stack([ph[:, 0], ph[:, 1], np.zeros_like(r_hit)], 1)
             dpdv = (flat * (F(S.inner_radius) - r)).astype(F) * (F(1.0) / r_hit)[:, None]
-        else:   # sphere.rs:130-176
-            ph = (ph * (r / np.sqrt(_dot32(ph, ph)))[:, None]).astype(F)
+        else:   # sphere.rs:130-176: near the poles many ulps from the radial direction (:160-176 form it from sin(acos(z / r))) -- the reference's normal all the same
+            ph = (ph * (r / np.sqrt(dot(ph, ph)))[:, None]).astype(F)
             ph[:, 0] = np.where((ph[:, 0] == 0) & (ph[:, 1] == 0), F(1e-5) * r, ph[:, 0])
-            theta = _map32(oracle.lib.orc_dm_acos, np.clip(ph[:, 2] / r, F(-1.0), F(1.0)))
+            theta = dm_map(oracle.lib.orc_dm_acos, np.clip(ph[:, 2] / r, F(-1.0), F(1.0)))
             inv = F(1.0) / np.sqrt(ph[:, 0] * ph[:, 0] + ph[:, 1] * ph[:, 1])
             cos_phi, sin_phi = ph[:, 0] * inv, ph[:, 1] * inv
             dpdu = np.stack([-phi_max * ph[:, 1], phi_max * ph[:, 0], np.zeros_like(inv)], 1)
-            dpdv = np.stack([ph[:, 2] * cos_phi, ph[:, 2] * sin_phi, -r * _map32(oracle.lib.orc_dm_sin, theta)], 1) * (F(S.theta_max) - F(S.theta_min))
-        nq = _normalize32(_cross32(dpdu.astype(F), dpdv.astype(F)))
-        n32[m] = _normalize32(_xf_normal_inv32(w2o, nq))
-    n32 = np.where(through[:, None], _normalize32(_xf_normal_inv32(w2i, n32)), n32)   # transform_surface_interaction (transform.rs:607-636)
-    n32 = np.where((_dot32(n32, -d32) < 0)[:, None], -n32, n32)
+            dpdv = np.stack([ph[:, 2] * cos_phi, ph[:, 2] * sin_phi, -r * dm_sin(oracle, theta)], 1) * (F(S.theta_max) - F(S.theta_min))
+        nq = normalize(cross(dpdu.astype(F), dpdv.astype(F)))
+        n32[m] = normalize(xf_normal_inv(w2o, nq))
+    n32 = np.where(through[:, None], normalize(xf_normal_inv(w2i, n32)), n32)   # transform_surface_interaction (transform.rs:607-636)
+    n32 = np.where((dot(n32, -d32) < 0)[:, None], -n32, n32)
     nw = n32.astype(np.float64)
     if tri.any() and sd.N is not None:
         smooth = np.zeros(n, bool)

@@ -1,19 +1,11 @@
 """A float32 numpy model of the texture-space bake's contract (include/mi355bake.h): ownership, the surface point, the AO rays, the sums and the dilation,
-every operation in the header's order. numpy's float32 +, -, *, / and sqrt round as the device's do (no fusing on either side); what numpy has no twin of comes
-from the oracle's probes: dm_sincosf (orc_dm_sin / orc_dm_cos), the samplers' array values (orc_sobol_samples / orc_halton_samples), and the occlusion of the
-model's rays (orc_trace_any)."""
+every operation in the header's order, in the float32 arithmetic of tests/model_math.py (which also lends the oracle's dm_sincosf and the samplers' array values);
+the occlusion of the model's rays is the oracle's (orc_trace_any)."""
 import numpy as np
+from model_math import F, INV_4PI, INV_PI, NONE, PI, concentric_sample_disk, coordinate_system, cross, dm_cos, dm_sin, dot, gamma, normalize, offset_ray_origin, sampler_values
 
-F = np.float32
-NONE = np.uint32(0xFFFFFFFF)
-PI, PI_OVER_2, PI_OVER_4, INV_PI, INV_4PI = F(3.14159265358979323846), F(1.57079632679489661923), F(0.78539816339744830961), F(0.31830988618379067154), F(0.07957747154594766788)
-MACH_EPS = F(5.9604644775390625e-08)
 TRI_REVERSE, TRI_SWAPS, TRI_HAS_N, TRI_HAS_S, TRI_HAS_UV = 1, 2, 4, 8, 16
 NEIGHBOURS = [(-1, -1), (0, -1), (1, -1), (-1, 0), (1, 0), (-1, 1), (0, 1), (1, 1)]   # (dx, dy): the dilation's order of summation
-
-
-def gamma(n):
-    return (F(n) * MACH_EPS) / (F(1) - F(n) * MACH_EPS)
 
 
 # ---- ownership ----
@@ -85,28 +77,6 @@ def scene_triangles(sd, select):
 # ---- the surface point: Triangle::intersect's interaction for given barycentrics (dev_scene.h: tri_partials, tri_fill_from) ----
 def v3(a):
     return np.asarray(a, F).reshape(3)
-
-
-def cross(a, b):   # vector.rs:339-352: f64 products, one rounding
-    a, b = a.astype(np.float64), b.astype(np.float64)
-    return np.array([a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]]).astype(F)
-
-
-def dot(a, b):
-    return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]
-
-
-def normalize(a):
-    with np.errstate(all="ignore"):
-        return a * (F(1) / np.sqrt(dot(a, a)))
-
-
-def coordinate_system(v1):
-    if abs(v1[0]) > abs(v1[1]):
-        v2 = np.array([-v1[2], F(0), v1[0]], F) * (F(1) / np.sqrt(v1[0] * v1[0] + v1[2] * v1[2]))
-    else:
-        v2 = np.array([F(0), v1[2], -v1[1]], F) * (F(1) / np.sqrt(v1[1] * v1[1] + v1[2] * v1[2]))
-    return v2, cross(v1, v2)
 
 
 def interaction(sd, prim, b0, b1, b2):
@@ -186,84 +156,47 @@ def planes(sd, owner):
 
 
 # ---- the AO rays ----
-def next_up(v):
-    v = np.where(v == 0, F(0), v).astype(F)   # -0 -> +0
-    bits = v.view(np.uint32)
-    out = np.where(v >= 0, bits + np.uint32(1), bits - np.uint32(1)).astype(np.uint32).view(F)
-    return np.where(np.isposinf(v), v, out)
-
-
-def next_down(v):
-    v = np.where(v == 0, F(-0.0), v).astype(F)
-    bits = v.view(np.uint32)
-    out = np.where(v > 0, bits - np.uint32(1), bits + np.uint32(1)).astype(np.uint32).view(F)
-    return np.where(np.isneginf(v), v, out)
-
-
-def offset_ray_origin(p, perr, n, w):
-    """dev_math.h: offset_ray_origin, rows of (m, 3) arrays."""
-    d = np.abs(n[:, 0]) * perr[:, 0] + np.abs(n[:, 1]) * perr[:, 1] + np.abs(n[:, 2]) * perr[:, 2]
-    offset = n * d[:, None]
-    neg = (w[:, 0] * n[:, 0] + w[:, 1] * n[:, 1] + w[:, 2] * n[:, 2]) < 0
-    offset = np.where(neg[:, None], -offset, offset)
-    po = (p + offset).astype(F)
-    return np.where(offset > 0, next_up(po), np.where(offset < 0, next_down(po), po)).astype(F)
-
-
 def array_samples(oracle, pkg, sampler, width, height, px, py, numbers):
     """The 2-D array values (m, 2) of sample numbers `numbers` of pixels (px, py): dimensions 5 and 6 of a sampler for sample bounds [0, width) x [0, height)."""
-    import ctypes as C
-    A = pkg._abi
-    m = len(numbers)
-    sb = (C.c_int32 * 4)(0, 0, width, height)
-    xy = np.ascontiguousarray(np.stack([px, py], axis=1), dtype=np.int32)
-    num = np.ascontiguousarray(numbers, dtype=np.uint32)
-    out = np.zeros((m, 7), F)
-    args = (m, xy.ctypes.data_as(A.i32p), num.ctypes.data_as(A.u32p), 7, out.ctypes.data_as(A.fp), None)
-    st = oracle.lib.orc_sobol_samples(sb, *args) if sampler == "sobol" else oracle.lib.orc_halton_samples(sb, 0, *args)
-    assert st == 0, st
-    return out[:, 5:7].copy()
+    return sampler_values(oracle, pkg, sampler, (0, 0, width, height), np.stack([px, py], axis=1), numbers, 7)[:, 5:7].copy()
 
 
 def directions(oracle, u, cos_sample):
     """(wi (m, 3), pdf (m,)) of the array values u (m, 2): cosine_sample_hemisphere or uniform_sample_sphere (side/ao_rays.h: ao_ray)."""
-    sin = np.frompyfunc(lambda x: oracle.lib.orc_dm_sin(float(x)), 1, 1)
-    cos = np.frompyfunc(lambda x: oracle.lib.orc_dm_cos(float(x)), 1, 1)
     ux, uy = u[:, 0].astype(F), u[:, 1].astype(F)
     with np.errstate(all="ignore"):
         if cos_sample:
-            ox, oy = ux * F(2) - F(1), uy * F(2) - F(1)
-            first = np.abs(ox) > np.abs(oy)
-            r = np.where(first, ox, oy).astype(F)
-            theta = np.where(first, PI_OVER_4 * (oy / ox), PI_OVER_2 - PI_OVER_4 * (ox / oy)).astype(F)
-            theta = np.where((ox == 0) & (oy == 0), F(0), theta).astype(F)
-            s, c = sin(theta).astype(F), cos(theta).astype(F)
-            dx, dy = c * r, s * r
-            zero = (ox == 0) & (oy == 0)
-            dx, dy = np.where(zero, F(0), dx).astype(F), np.where(zero, F(0), dy).astype(F)
+            dsk = concentric_sample_disk(oracle, u)
+            dx, dy = dsk[:, 0], dsk[:, 1]
             z = np.sqrt(np.maximum(F(0), F(1) - dx * dx - dy * dy)).astype(F)
             return np.stack([dx, dy, z], axis=1).astype(F), (np.abs(z) * INV_PI).astype(F)
         z = F(1) - F(2) * ux
         r = np.sqrt(np.maximum(F(1) - z * z, F(0))).astype(F)
         phi = (F(2) * PI) * uy
-        s, c = sin(phi).astype(F), cos(phi).astype(F)
+        s, c = dm_sin(oracle, phi), dm_cos(oracle, phi)
         return np.stack([r * c, r * s, z], axis=1).astype(F), np.full(len(ux), INV_4PI, F)
+
+
+def sample_list(items, spp, nsamples, samples=None):
+    """(item, s, k) of every sample of the items (texels, points: ascending numbers), for sample numbers `samples` = (first, n) of the job (default: all spp), ordered
+    by item, then (s, k): arrays of int64."""
+    first, count = (0, spp) if samples is None else samples
+    items = np.asarray(items, dtype=np.int64)
+    return (np.repeat(items, count * nsamples), np.tile(np.repeat(np.arange(first, first + count, dtype=np.int64), nsamples), len(items)),
+            np.tile(np.arange(nsamples, dtype=np.int64), len(items) * count))
 
 
 def rays(oracle, pkg, sd, owner, spp, nsamples, cos_sample, sampler, samples=None):
     """The AO rays of the owned texels of an owner map, for sample numbers `samples` = (first, n) of the job (default: all spp): dict(texel, s, k, o, d, w) of
     arrays over the rays, ordered by texel, then (s, k)."""
     height, width = owner.shape
-    first, count = (0, spp) if samples is None else samples
     sis = texel_interactions(sd, owner)
     texels = np.array(sorted(sis), dtype=np.int64)
-    per = count * nsamples
-    tx = np.repeat(texels, per)
-    s = np.tile(np.repeat(np.arange(first, first + count, dtype=np.int64), nsamples), len(texels))
-    k = np.tile(np.arange(nsamples, dtype=np.int64), len(texels) * count)
+    tx, s, k = sample_list(texels, spp, nsamples, samples)
     if len(tx) == 0:
         z3 = np.zeros((0, 3), F)
         return dict(texel=tx, s=s, k=k, o=z3, d=z3, w=np.zeros(0, F))
+    per = len(tx) // len(texels)
     u = array_samples(oracle, pkg, sampler, width, height, tx % width, tx // width, s * nsamples + k)
     wi, pdf = directions(oracle, u, cos_sample)
     with np.errstate(all="ignore"):
@@ -275,20 +208,23 @@ def rays(oracle, pkg, sd, owner, spp, nsamples, cos_sample, sampler, samples=Non
         perr = np.repeat(np.array([sis[t]["p_error"] for t in texels], F), per, axis=0)
         wo = (sv * wi[:, 0:1] + tv * wi[:, 1:2] + n * wi[:, 2:3]).astype(F)
         o = offset_ray_origin(p, perr, n, wo)
-        w = ((wo[:, 0] * n[:, 0] + wo[:, 1] * n[:, 1] + wo[:, 2] * n[:, 2]) / (pdf * F(nsamples))).astype(F)
+        w = (dot(wo, n) / (pdf * F(nsamples))).astype(F)
     return dict(texel=tx, s=s, k=k, o=o, d=wo, w=w)
 
 
-def accumulate(ao_w, r, occluded, nsamples):
-    """ao_w (H, W, 4) += the unoccluded rays' direction and weight, per texel in ascending (s, k) order. Returns ao_w (modified in place)."""
-    flat = ao_w.reshape(-1, 4)
+def accumulate(sums, item, r, nsamples, rows, take):
+    """sums (n, c) += rows (m, c) of the samples `take` (m,) of r = dict(s, k, ..), per item (m,) in ascending (s, k) order. Returns sums (modified in place)."""
     order = r["s"] * nsamples + r["k"]
-    free = ~np.asarray(occluded, bool)
-    for j in np.unique(order):   # one (s, k) at a time: every texel has at most one ray of it
-        m = (order == j) & free
-        t = r["texel"][m]
-        flat[t, 0:3] = flat[t, 0:3] + r["d"][m]
-        flat[t, 3] = flat[t, 3] + r["w"][m]
+    for j in np.unique(order):   # one (s, k) at a time: every item has at most one sample of it
+        m = (order == j) & take
+        t = item[m]
+        sums[t] = (sums[t] + rows[m]).astype(F)
+    return sums
+
+
+def add_ao_rays(ao_w, r, occluded, nsamples):
+    """ao_w (H, W, 4) += the unoccluded rays' direction and weight, per texel in ascending (s, k) order. Returns ao_w (modified in place)."""
+    accumulate(ao_w.reshape(-1, 4), r["texel"], r, nsamples, np.concatenate([r["d"], r["w"][:, None]], axis=1), ~np.asarray(occluded, bool))
     return ao_w
 
 
@@ -301,7 +237,7 @@ def bake(oracle, pkg, sd, select, width, height, spp, nsamples, cos_sample=True,
     orc_scene = orc_scene or oracle.scene(sd)
     occ = orc_scene.trace_any(r["o"], r["d"], np.full(len(r["w"]), max_distance, F)) if len(r["w"]) else np.zeros(0, np.uint8)
     ao_w = np.zeros((height, width, 4), F) if ao_w is None else ao_w
-    accumulate(ao_w, r, occ, nsamples)
+    add_ao_rays(ao_w, r, occ, nsamples)
     return dict(owner=owner, position=pos, normal=nrm, ao_w=ao_w, n_rays=len(r["w"]), rays=r, occluded=occ)
 
 

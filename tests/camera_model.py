@@ -4,99 +4,24 @@ The oracle renders the perspective camera only, so the orthographic and the envi
 the camera (this file), proved where an oracle exists -- rays() of the perspective camera equals orc_camera_rays bit for bit -- and identities that hold the device
 against the unchanged oracle's pieces: the model's rays -> orc_trace_closest give the primitive, t and barycentrics of every camera sample.
 
-All arithmetic is float32 with nothing fused, products and sums left to right as dev_math.h writes them (the device is built with -ffp-contract=off and correctly
-rounded division and square root); a vector divided by a number is multiplied by the reciprocal (vector.rs:481-495). Sine and cosine are the oracle's orc_dm_sin /
-orc_dm_cos, called element by element: the functions the device uses.
+All arithmetic is tests/model_math.py's: float32 with nothing fused, as dev_math.h writes it, sine and cosine the oracle's orc_dm_sin / orc_dm_cos (the functions the
+device uses), the camera samples the oracle's samplers'.
 
 The reference's behaviours the model reproduces (cameras/orthographic.rs, cameras/environment.rs, core/camera.rs):
   * orthographic, lens: the differentials take ft from the ALREADY lens-modified direction's z (orthographic.rs:130), and the y focus point is
     pcamera + dy_camera + (0, 0, 0.1) * ft (:135) where x has (0, 0, 1). `corrected=True` gives the variant a well-meant fix would compute.
   * transform_ray moves the main ray's origin by its error bound, not the auxiliary origins (transform.rs:565-575); no direction is normalised after camera_to_world.
   * environment: theta = PI * pfilm.y / full_resolution.y, phi = 2 PI * pfilm.x / full_resolution.x over the FULL resolution; no differentials at all."""
-import ctypes as C
-import math
-
 import numpy as np
-
-from aov_reference import F, NONE, _G3   # gamma(3) in float32
+from model_math import F, PI, concentric_sample_disk, dm_cos, dm_sin, normalize, sampler_values, transform_ray, xf_point, xf_vector
 
 PERSPECTIVE, ORTHOGRAPHIC, ENVIRONMENT = 0, 1, 2
-PI = F(3.14159265358979323846)
-PI_OVER_2 = F(1.57079632679489661923)
-PI_OVER_4 = F(0.78539816339744830961)
-
-
-def _m(a):
-    return [F(v) for v in a]
-
-
-def xf_point(m, p):
-    """Transform::transform_point (transform.rs:413-432) with the divide by w. p: (N, 3) float32; m: 16 float32, row major."""
-    x, y, z = p[:, 0], p[:, 1], p[:, 2]
-    xp = x * m[0] + y * m[1] + z * m[2] + m[3]
-    yp = x * m[4] + y * m[5] + z * m[6] + m[7]
-    zp = x * m[8] + y * m[9] + z * m[10] + m[11]
-    wp = x * m[12] + y * m[13] + z * m[14] + m[15]
-    q = np.stack([xp, yp, zp], 1).astype(F)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        inv = (F(1.0) / wp).astype(F)
-        return np.where((wp == F(1.0))[:, None], q, (q * inv[:, None]).astype(F)).astype(F)
-
-
-def xf_point_err(m, p):
-    """transform_point_with_error (transform.rs:434-459): the point and its absolute error bound."""
-    x, y, z = p[:, 0], p[:, 1], p[:, 2]
-    err = np.stack([np.abs(x * m[0]) + np.abs(y * m[1]) + np.abs(z * m[2]) + np.abs(m[3]), np.abs(x * m[4]) + np.abs(y * m[5]) + np.abs(z * m[6]) + np.abs(m[7]),
-                    np.abs(x * m[8]) + np.abs(y * m[9]) + np.abs(z * m[10]) + np.abs(m[11])], 1).astype(F) * _G3
-    return xf_point(m, p), err.astype(F)
-
-
-def xf_vector(m, v):
-    x, y, z = v[:, 0], v[:, 1], v[:, 2]
-    return np.stack([x * m[0] + y * m[1] + z * m[2], x * m[4] + y * m[5] + z * m[6], x * m[8] + y * m[9] + z * m[10]], 1).astype(F)
-
-
-def dot(a, b):
-    return (a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1] + a[:, 2] * b[:, 2]).astype(F)
-
-
-def normalize(a):
-    with np.errstate(divide="ignore", invalid="ignore"):
-        return (a * (F(1.0) / np.sqrt(dot(a, a)))[:, None]).astype(F)
-
-
-def _map(fn, x):
-    return np.array([fn(float(v)) for v in x], F)
-
-
-def concentric_sample_disk(oracle, u):
-    """sampling.rs:153-176. u: (N, 2)."""
-    ox, oy = (u[:, 0] * F(2.0) - F(1.0)).astype(F), (u[:, 1] * F(2.0) - F(1.0)).astype(F)
-    wide = np.abs(ox) > np.abs(oy)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        theta = np.where(wide, PI_OVER_4 * (oy / ox), PI_OVER_2 - PI_OVER_4 * (ox / oy)).astype(F)
-    r = np.where(wide, ox, oy).astype(F)
-    zero = (ox == 0) & (oy == 0)
-    theta = np.where(zero, F(0.0), theta).astype(F)
-    s, c = _map(oracle.lib.orc_dm_sin, theta), _map(oracle.lib.orc_dm_cos, theta)
-    return np.where(zero[:, None], F(0.0), np.stack([c * r, s * r], 1)).astype(F)
-
-
-def transform_ray(m, o, d):
-    """Transform::transform_ray (transform.rs:543-577): the origin moved along the direction by its error bound; the direction as it comes out."""
-    ow, oerr = xf_point_err(m, o)
-    dw = xf_vector(m, d)
-    l2 = dot(dw, dw)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        dt = (dot(np.abs(dw), oerr) / l2).astype(F)
-    ow = np.where((l2 > 0)[:, None], (ow + dw * dt[:, None]).astype(F), ow)
-    return ow.astype(F), dw
 
 
 def _camera_space(oracle, rp, cs, kind):
     """(pcamera, ray origin, ray direction, lens point or None) in camera space, before transform_ray."""
     N = len(cs)
-    r2c = _m(rp.raster_to_camera)
+    r2c = rp.raster_to_camera
     pfilm = np.stack([cs[:, 0], cs[:, 1], np.zeros(N, F)], 1).astype(F)
     pcamera = xf_point(r2c, pfilm)
     if kind == ORTHOGRAPHIC:   # orthographic.rs:104-106
@@ -121,17 +46,17 @@ def rays(oracle, rp, cs):
     if kind == ENVIRONMENT:   # environment.rs:36-51
         theta = (PI * cs[:, 1] / F(rp.full_resolution[1])).astype(F)
         phi = (F(2.0) * PI * cs[:, 0] / F(rp.full_resolution[0])).astype(F)
-        st, ct = _map(oracle.lib.orc_dm_sin, theta), _map(oracle.lib.orc_dm_cos, theta)
-        sp, cp = _map(oracle.lib.orc_dm_sin, phi), _map(oracle.lib.orc_dm_cos, phi)
+        st, ct = dm_sin(oracle, theta), dm_cos(oracle, theta)
+        sp, cp = dm_sin(oracle, phi), dm_cos(oracle, phi)
         ro, rd = np.zeros((N, 3), F), np.stack([st * cp, ct, st * sp], 1).astype(F)
     else:
         _, ro, rd, _ = _camera_space(oracle, rp, cs, kind)
-    return transform_ray(_m(rp.camera_to_world), ro, rd)
+    return transform_ray(rp.camera_to_world, ro, rd)
 
 
 def dxdy_camera(rp):
     """dx_camera, dy_camera: perspective.rs:64-70 (differences of transformed points), orthographic.rs:55-56 (raster_to_camera on the vectors)."""
-    r2c = _m(rp.raster_to_camera)
+    r2c = rp.raster_to_camera
     e = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0]], F)
     if rp.camera_type == ORTHOGRAPHIC:
         v = xf_vector(r2c, e)
@@ -172,7 +97,7 @@ def differentials(oracle, rp, cs, corrected=False):
     else:                       # perspective.rs:167-172
         rx_o = ry_o = np.zeros((N, 3), F)
         rx_d, ry_d = normalize((pcamera + dxc).astype(F)), normalize((pcamera + dyc).astype(F))
-    c2w = _m(rp.camera_to_world)
+    c2w = rp.camera_to_world
     sc = F(1.0) / np.sqrt(F(rp.spp))
     scale = lambda main, aux: (main + ((aux - main).astype(F) * sc).astype(F)).astype(F)   # ray.rs:34-41
     out = np.concatenate([scale(o, xf_point(c2w, rx_o)), scale(d, xf_vector(c2w, rx_d)), scale(o, xf_point(c2w, ry_o)), scale(d, xf_vector(c2w, ry_d))], 1)
@@ -182,28 +107,22 @@ def differentials(oracle, rp, cs, corrected=False):
 def camera_samples(pkg, oracle, rp, first=0, n=None):
     """(pix (N, 2) int32, cs (N, 5)) of the camera samples [first, first + n) of every pixel of rp's sample bounds, pixel major and sample minor, from the oracle's
     orc_sobol_samples / orc_halton_samples: get_camera_sample's p_film = pixel + get_2d(), time, p_lens (sampler.rs:170-180)."""
-    A = pkg._abi
     n = rp.spp - first if n is None else n
     sb = rp.sample_bounds
     xs, ys = np.meshgrid(np.arange(sb[0], sb[2]), np.arange(sb[1], sb[3]), indexing="xy")
     pix = np.ascontiguousarray(np.repeat(np.stack([xs.ravel(), ys.ravel()], 1).astype(np.int32), n, axis=0))
-    sn = np.ascontiguousarray(np.tile(np.arange(first, first + n, dtype=np.uint32), len(pix) // n))
-    N = len(pix)
-    dims = np.zeros((N, 5), F)
-    sbc = (C.c_int32 * 4)(*sb)
-    if rp.sampler_type == A.PT_SAMPLER_HALTON:
-        assert oracle.lib.orc_halton_samples(sbc, rp.sample_at_pixel_center, N, pix.ctypes.data_as(A.i32p), sn.ctypes.data_as(A.u32p), 5, dims.ctypes.data_as(A.fp), None) == 0
-    else:
-        assert oracle.lib.orc_sobol_samples(sbc, N, pix.ctypes.data_as(A.i32p), sn.ctypes.data_as(A.u32p), 5, dims.ctypes.data_as(A.fp), None) == 0
-    cs = dims.copy()
-    cs[:, :2] = pix.astype(F) + dims[:, :2]
+    sn = np.tile(np.arange(first, first + n, dtype=np.uint32), len(pix) // n)
+    cs = sampler_values(oracle, pkg, rp.sampler_type, sb, pix, sn, 5, rp.sample_at_pixel_center)
+    cs[:, :2] = pix.astype(F) + cs[:, :2]
     return pix, cs
 
 
-def camera_hits(pkg, oracle, orc, rp, first=0, n=None):
-    """aov_reference.camera_hits with the model's rays in place of orc_camera_rays: dict(pix, pfilm, cs, o, d, prim, t, b, n). `orc`: the oracle's scene."""
+def camera_hits(pkg, oracle, orc, rp, first=0, n=None, ray_source=None):
+    """The camera samples [first, first + n) of every pixel of rp's sample bounds and their first hits by orc_trace_closest: dict(pix (N, 2), pfilm (N, 2), cs (N, 5),
+    o, d (N, 3), prim, t, b, n), pixel major and sample minor. `orc`: the oracle's scene. ray_source(oracle, rp, cs) -> (o, d): where the rays come from -- the
+    model's rays (the default) or aov_reference.oracle_rays (orc_camera_rays: the perspective camera's)."""
     pix, cs = camera_samples(pkg, oracle, rp, first, n)
-    o, d = rays(oracle, rp, cs)
+    o, d = (ray_source or rays)(oracle, rp, cs)
     prim, t, b = orc.trace_closest(o, d, np.full(len(cs), np.inf, F))
     return dict(pix=pix, pfilm=cs[:, :2].copy(), cs=cs, o=o, d=d, prim=prim, t=t, b=b, n=rp.spp - first if n is None else n)
 

@@ -8,7 +8,8 @@ the weights table lookups of bit-exact pfilm values, so the device's tables are 
 import types
 
 import numpy as np
-from aov_reference import F, GROUND_I, GROUND_P, NONE, _builder, undulating_mesh
+from aov_reference import GROUND_I, GROUND_P, _builder, undulating_mesh
+from model_math import F, NONE
 
 SLOTS = 8
 LAYERS = ("material", "instance", "group")

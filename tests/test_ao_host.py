@@ -3,13 +3,10 @@ answer, the .pbrt front end's "ambientocclusion" parameters against the Python s
 mirror."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi_checks import assert_mirror, c99_probe, exported_names
 
 
 def _builder(pkg, nsamples=16, cossample=True, spp=2, res=8):
@@ -121,23 +118,10 @@ def test_front_end_path_scenes_are_unchanged_and_others_refused(pkg):
         pkg.frontend.FrontScene(text='Integrator "ambientocclusion" "integer nsamples" 0\n')
 
 
-def test_mi355ao_header_is_c99_and_matches_the_ctypes_mirror(pkg, tmp_path):
+def test_mi355ao_header_is_c99_and_matches_the_ctypes_mirror(pkg):
     A = pkg._abi_ao
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "mi355ao.h"\n'
-                   'int main(void) { printf("%d %d %d %d\\n", (int)sizeof(PtAOParams), (int)offsetof(PtAOParams, nsamples), '
-                   '(int)offsetof(PtAOParams, cos_sample), PT_INTEGRATOR_AO); return 0; }\n')
-    exe = tmp_path / "probe"
-    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    out = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()
-    assert [int(v) for v in out] == [C.sizeof(A.PtAOParams), A.PtAOParams.nsamples.offset, A.PtAOParams.cos_sample.offset, A.PT_INTEGRATOR_AO]
-
+    assert_mirror("mi355ao.h", {A.PtAOParams: ("nsamples", "cos_sample")})
+    assert [int(v) for v in c99_probe("mi355ao.h", 'printf("%d", PT_INTEGRATOR_AO);')] == [A.PT_INTEGRATOR_AO]
 
 def test_ao_library_exports_only_its_entry_points(pkg):
-    path = pkg.runtime.AO_LIB_PATH
-    if not os.path.exists(path):
-        pytest.fail(f"{path} missing: __graft_entry__.build() builds it")
-    r = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True)
-    names = {line.split()[-1] for line in r.stdout.splitlines() if line.strip()}
-    assert names == set(pkg._abi_ao.ENTRY_POINTS)
+    assert exported_names(pkg.runtime.AO_LIB_PATH) == set(pkg._abi_ao.ENTRY_POINTS)

@@ -2,36 +2,18 @@
 (host arithmetic) and the argument errors that return before the device is touched."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi_checks import ROOT, assert_mirror, exported_names
 
 
-def test_mi355aov_header_is_c99_and_matches_the_ctypes_mirror(pkg, tmp_path):
+def test_mi355aov_header_is_c99_and_matches_the_ctypes_mirror(pkg):
     A = pkg._abi_aov
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "mi355aov.h"\n'
-                   'int main(void) { printf("%d %d %d %d\\n", (int)sizeof(PtAOVBuffers), (int)offsetof(PtAOVBuffers, albedo_w), '
-                   '(int)offsetof(PtAOVBuffers, normal_w), (int)offsetof(PtAOVBuffers, depth_w)); return 0; }\n')
-    exe = tmp_path / "probe"
-    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    out = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()
-    B = A.PtAOVBuffers
-    assert [int(v) for v in out] == [C.sizeof(B), B.albedo_w.offset, B.normal_w.offset, B.depth_w.offset]
-    assert [name for name, _ in B._fields_] == [p + "_w" for p in A.PLANES]
-
+    assert_mirror("mi355aov.h", {A.PtAOVBuffers: [p + "_w" for p in A.PLANES]})
+    assert A.PLANES == ("albedo", "normal", "depth")
 
 def test_aov_library_exports_only_its_entry_points(pkg):
-    path = pkg.runtime.AOV_LIB_PATH
-    if not os.path.exists(path):
-        pytest.fail(f"{path} missing: __graft_entry__.build() builds it")
-    r = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True)
-    names = {line.split()[-1] for line in r.stdout.splitlines() if line.strip()}
-    assert names == set(pkg._abi_aov.ENTRY_POINTS)
+    assert exported_names(pkg.runtime.AOV_LIB_PATH) == set(pkg._abi_aov.ENTRY_POINTS)
     header = open(os.path.join(ROOT, "include", "mi355aov.h")).read()
     for name in pkg._abi_aov.ENTRY_POINTS:
         assert f"int {name}(" in header, name

@@ -1,78 +1,38 @@
 """The bake's C ABI without a GPU (include/mi355bake.h, libmi355bake.so): the header under C99, the structs against the ctypes mirror, the export list, the refusals
 that return before the device is touched, and pt_bake_resolve (host arithmetic) against the model."""
-import ctypes as C
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
-import pytest
 import bake_reference as M
+from abi_checks import ROOT, assert_bound, assert_mirror, embedded_kernel_names, exported_names, run_without_device
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P_FIELDS = ("width", "height", "spp", "nsamples", "cos_sample", "max_distance", "sampler_type", "spp_per_pass", "profile")
 B_FIELDS = ("owner", "position", "normal", "ao_w")
 
 
-def test_the_header_is_c99_and_the_structs_match_the_ctypes_mirror(pkg, tmp_path):
+def test_the_header_is_c99_and_the_structs_match_the_ctypes_mirror(pkg):
     K = pkg._abi_bake
-    fmt = lambda t, fields: "".join('printf("%%d ", (int)offsetof(%s, %s));' % (t, f) for f in fields)
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "mi355bake.h"\nint main(void) {\n'
-                   'printf("%d %d ", (int)sizeof(PtBakeParams), (int)sizeof(PtBakeBuffers));\n' + fmt("PtBakeParams", P_FIELDS) + fmt("PtBakeBuffers", B_FIELDS) + '\nreturn 0; }\n')
-    exe = tmp_path / "probe"
-    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    out = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    P, B = K.PtBakeParams, K.PtBakeBuffers
-    assert [n for n, _ in P._fields_] == list(P_FIELDS) and [n for n, _ in B._fields_] == list(B_FIELDS) == list(K.PLANES)
-    assert out == [C.sizeof(P), C.sizeof(B)] + [getattr(P, f).offset for f in P_FIELDS] + [getattr(B, f).offset for f in B_FIELDS]
-    assert out[:2] == [36, 32]
+    assert assert_mirror("mi355bake.h", {K.PtBakeParams: P_FIELDS, K.PtBakeBuffers: B_FIELDS}) == [36, 32]
+    assert list(B_FIELDS) == list(K.PLANES)
 
 
 def test_the_library_exports_what_its_map_names_and_the_header_declares(pkg):
-    path = pkg.runtime.LIB_PATHS["bake"]
-    if not os.path.exists(path):
-        pytest.fail(f"{path} missing: __graft_entry__.build() builds it")
     R = pkg.runtime
     assert R.LIBRARIES["bake"] == ("bake", "libmi355bake.so", pkg._abi_bake, "mi355bake.h") and not hasattr(R, "ATLAS_LIBRARIES") and not hasattr(R, "ALL_LIBRARIES")
-    r = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True)
-    names = {line.split()[-1] for line in r.stdout.splitlines() if line.strip()}
+    names = exported_names(R.LIB_PATHS["bake"])
     assert names == set(pkg._abi_bake.ENTRY_POINTS)
     pattern = re.search(r"global:\s*([^;]+);", open(os.path.join(ROOT, "pbrt-rust_amd", "bake", "exports.map")).read()).group(1).strip()
     assert pattern == "pt_bake_*" and all(n.startswith("pt_bake_") for n in names)
     header = open(os.path.join(ROOT, "include", "mi355bake.h")).read()
     declared = set(re.findall(r"^int (pt_\w+)\(", header, re.M))
     assert declared == names
-    lib = pkg.load_library().bake
-    for name, (res, args) in pkg._abi_bake.ENTRY_POINTS.items():
-        assert getattr(lib, name).restype is res and getattr(lib, name).argtypes == args
+    assert_bound(pkg.load_library().bake, pkg._abi_bake.ENTRY_POINTS)
 
 
-def test_no_bake_kernel_uses_scratch(pkg, tmp_path):
+def test_no_bake_kernel_uses_scratch(pkg):
     """The gfx950 code objects inside the built library: every kernel's .private_segment_fixed_size is 0, and the kernels are the ones the sources name."""
-    import shutil
-    import struct
-    readelf = next((p for p in ("/opt/rocm/lib/llvm/bin/llvm-readelf", "/opt/rocm/llvm/bin/llvm-readelf", shutil.which("llvm-readelf")) if p and os.path.exists(p)), None)
-    if readelf is None:
-        pytest.fail("llvm-readelf (ROCm's LLVM) not found: the kernels' metadata cannot be read")
-    data = open(pkg.runtime.LIB_PATHS["bake"], "rb").read()
-    kernels, pos = {}, 0
-    while True:   # every embedded code object is an ELF for EM_AMDGPU (machine 0xE0); its size: section header offset + the section headers
-        i = data.find(b"\x7fELF", pos)
-        if i < 0:
-            break
-        pos = i + 4
-        if data[i + 18:i + 20] != b"\xe0\x00":
-            continue
-        shoff = struct.unpack_from("<Q", data, i + 0x28)[0]; shentsize, shnum = struct.unpack_from("<HH", data, i + 0x3A)
-        co = tmp_path / ("co%d.elf" % len(kernels))
-        co.write_bytes(data[i:i + shoff + shentsize * shnum])
-        notes = subprocess.run([readelf, "--notes", str(co)], capture_output=True, text=True, check=True).stdout
-        for block in notes.split("- .agpr_count:")[1:]:
-            name = re.search(r"\.name:\s+(\S+)", block).group(1)
-            kernels[name] = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", block).group(1))
+    kernels = embedded_kernel_names(pkg.runtime.LIB_PATHS["bake"])
     want = ["k_bake_top", "k_bake_check", "k_bake_raster", "k_bake_points", "k_bake_rays", "k_bake_accum", "k_bake_dilate", "k_bake_covered", "k_bake_probe"]
     assert kernels and all("6ptbake" in n for n in kernels), sorted(kernels)
     for k in want:
@@ -83,16 +43,9 @@ def test_no_bake_kernel_uses_scratch(pkg, tmp_path):
 
 def test_refusals_return_before_the_device_is_touched(pkg):
     """Run in a child process with no visible device: a call that reached the device would fail with another status (or not return)."""
-    code = r'''
-import ctypes as C, sys
-import numpy as np
-sys.path.insert(0, %r)
-from _pkg import import_pkg
-pkg = import_pkg()
-A, K = pkg._abi, pkg._abi_bake
-lib = pkg.load_library(); bake = lib.bake
+    n = run_without_device(r'''
+K = pkg._abi_bake; bake = lib.bake
 scene = C.c_void_p(8)   # never looked at
-bad = A.PT_ERR_INVALID_ARG
 def params(**kw):
     d = dict(width=8, height=8, spp=4, nsamples=8, cos_sample=1, max_distance=float("inf"), sampler_type=0, spp_per_pass=0, profile=0); d.update(kw)
     return K.PtBakeParams(*[d[k] for k, _ in K.PtBakeParams._fields_])
@@ -101,9 +54,6 @@ kept = {k: v.copy() for k, v in planes.items()}
 ok, none = K.buffers(planes), K.buffers({})
 sel = np.ones(5, np.uint8); nosel = np.zeros(5, np.uint8)
 sp, np_ = sel.ctypes.data_as(A.u8p), nosel.ctypes.data_as(A.u8p)
-def refused(st, text):
-    assert st == bad, (st, text)
-    assert text in lib.lib.pt_last_error(), (text, lib.lib.pt_last_error())
 p = params()
 refused(bake.pt_bake_render(None, C.byref(p), sp, 5, C.byref(ok), 0), b"null")
 refused(bake.pt_bake_render(scene, None, sp, 5, C.byref(ok), 0), b"null")
@@ -144,11 +94,8 @@ refused(bake.pt_bake_resolve(aw, 64, 0, ao.ctypes.data_as(A.fp), bent.ctypes.dat
 for k in planes:
     assert planes[k].tobytes() == kept[k].tobytes(), k
 assert not ao.any() and not bent.any()
-print("refused")
-''' % ROOT
-    env = dict(os.environ, HIP_VISIBLE_DEVICES="")
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0 and "refused" in r.stdout, r.stderr[-3000:]
+''')
+    assert n == 56
 
 
 def test_resolve_is_the_models(pkg):

@@ -73,7 +73,7 @@ def model(pkg, oracle, sc, name):
     def make():
         owner = M.owner_map(M.scene_triangles(sd, select)[1], M.scene_triangles(sd, select)[0], w, h)
         n = len(LM.selected_lights(int(sd.desc().n_lights), subset)) if ns is None else ns
-        tx, s, k = LM.sample_list(owner, spp, n)
+        tx, s, k = M.sample_list(LM.owned_texels(owner), spp, n)
         dev = device_samples(sc, select, w, h, spp, n, subset, sampler, tx, s, k)
         return LM.bake(oracle, pkg, sd, select, w, h, spp, n, subset, sampler, device=dev)
     return cached(("model", name), make), sd, select

@@ -13,6 +13,7 @@ import sys
 
 import numpy as np
 import pytest
+import bake_reference as M
 import lightmap_reference as LM
 import lightmap_scenes as LS
 import sh_reference as SR
@@ -74,7 +75,7 @@ def model(pkg, oracle, sc, name):
 
     def make():
         n = len(LM.selected_lights(int(sd.desc().n_lights), subset)) if ns is None else ns
-        pt, s, k = SR.sample_list(n_points, spp, n)
+        pt, s, k = M.sample_list(np.arange(n_points), spp, n)
         dev = sc.bake_sh_rays(points(n_points), spp, pt, s, k, nsamples=n, lights=subset, sampler=sampler, row=row)
         return SR.bake(oracle, pkg, sd, points(n_points), spp, n, subset, sampler, row, device=dev)
     return cached(("model", name), make), sd

@@ -1,6 +1,7 @@
 """The SH points' model (tests/sh_reference.py) against what is known in closed form, without a GPU: the model is what the device is held against bit for bit
 (tests/test_bake_sh.py), so it has to be right on its own account."""
 import numpy as np
+import bake_reference as M
 import lightmap_reference as LM
 import lightmap_scenes as LS
 import sh_reference as SR
@@ -68,7 +69,7 @@ def test_behind_the_box_it_is_dark(pkg, oracle):
 def test_the_round_robin_gives_every_light_the_same_number_of_samples_at_every_point():
     for n_lights, lights, spp, ns in ((8, None, 2, 8), (8, None, 4, 2), (8, [1, 4, 6], 3, 1), (3, None, 2, 6), (5, [0, 2], 1, 70)):
         sel = LM.selected_lights(n_lights, lights)
-        pt, s, k = SR.sample_list(3, spp, ns)
+        pt, s, k = M.sample_list(np.arange(3), spp, ns)
         light = LM.light_of(sel, s * ns + k, ns)
         for t in range(3):
             mine = light[pt == t]

@@ -1,60 +1,25 @@
 """The transfer bake's C ABI without a GPU (include/mi355bake.h "Transfer", libmi355bake.so): the header under C99, the structs against the ctypes mirror, the
 refusals that return before the device is touched, the kernels in the built library, and encode_normal_map."""
-import ctypes as C
-import os
-import subprocess
-import sys
-
 import numpy as np
+from abi_checks import assert_mirror, embedded_kernel_names, run_without_device
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P_FIELDS = ("width", "height", "front", "back", "spp", "nsamples", "cos_sample", "max_distance", "sampler_type", "spp_per_pass", "profile")
 B_FIELDS = ("owner", "hit_prim", "height", "src_position", "src_normal", "tangent_normal", "ao_w")
 
 
-def test_the_header_is_c99_and_the_transfer_structs_match_the_ctypes_mirror(pkg, tmp_path):
+def test_the_header_is_c99_and_the_transfer_structs_match_the_ctypes_mirror(pkg):
     K = pkg._abi_bake
-    fmt = lambda t, fields: "".join('printf("%%d ", (int)offsetof(%s, %s));' % (t, f) for f in fields)
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "mi355bake.h"\nint main(void) {\n'
-                   'printf("%d %d %d %d ", (int)sizeof(PtBakeTransferParams), (int)sizeof(PtBakeTransferBuffers), (int)sizeof(PtBakeParams), (int)sizeof(PtBakeBuffers));\n'
-                   + fmt("PtBakeTransferParams", P_FIELDS) + fmt("PtBakeTransferBuffers", B_FIELDS) + '\nreturn 0; }\n')
-    exe = tmp_path / "probe"
-    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    out = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    P, B = K.PtBakeTransferParams, K.PtBakeTransferBuffers
-    assert [n for n, _ in P._fields_] == list(P_FIELDS) and [n for n, _ in B._fields_] == list(B_FIELDS) == list(K.TRANSFER_PLANES)
-    assert out == [C.sizeof(P), C.sizeof(B), C.sizeof(K.PtBakeParams), C.sizeof(K.PtBakeBuffers)] + [getattr(P, f).offset for f in P_FIELDS] + [getattr(B, f).offset for f in B_FIELDS]
-    assert out[:4] == [44, 56, 36, 32]
+    assert assert_mirror("mi355bake.h", {K.PtBakeTransferParams: P_FIELDS, K.PtBakeTransferBuffers: B_FIELDS, K.PtBakeParams: [n for n, _ in K.PtBakeParams._fields_],
+                                         K.PtBakeBuffers: K.PLANES}) == [44, 56, 36, 32]
+    assert list(B_FIELDS) == list(K.TRANSFER_PLANES)
     assert set(K.TRANSFER_CHANNELS) == set(K.TRANSFER_DTYPES) == set(B_FIELDS) and K.PLANES == ("owner", "position", "normal", "ao_w")
     for name in ("pt_bake_transfer", "pt_bake_transfer_samples", "pt_bake_transfer_pass_size", "pt_bake_transfer_rays"):
         assert name in K.ENTRY_POINTS
     assert len(pkg.runtime.LIBRARIES) == 5
 
 
-def test_the_transfer_kernels_are_in_the_library_and_use_no_scratch(pkg, tmp_path):
-    import re
-    import shutil
-    import struct
-    readelf = next((p for p in ("/opt/rocm/lib/llvm/bin/llvm-readelf", "/opt/rocm/llvm/bin/llvm-readelf", shutil.which("llvm-readelf")) if p and os.path.exists(p)), None)
-    assert readelf is not None, "llvm-readelf (ROCm's LLVM) not found: the kernels' metadata cannot be read"
-    data = open(pkg.runtime.LIB_PATHS["bake"], "rb").read()
-    kernels, pos = {}, 0
-    while True:   # every embedded code object is an ELF for EM_AMDGPU (machine 0xE0)
-        i = data.find(b"\x7fELF", pos)
-        if i < 0:
-            break
-        pos = i + 4
-        if data[i + 18:i + 20] != b"\xe0\x00":
-            continue
-        shoff = struct.unpack_from("<Q", data, i + 0x28)[0]; shentsize, shnum = struct.unpack_from("<HH", data, i + 0x3A)
-        co = tmp_path / ("co%d.elf" % len(kernels))
-        co.write_bytes(data[i:i + shoff + shentsize * shnum])
-        notes = subprocess.run([readelf, "--notes", str(co)], capture_output=True, text=True, check=True).stdout
-        for block in notes.split("- .agpr_count:")[1:]:
-            name = re.search(r"\.name:\s+(\S+)", block).group(1)
-            kernels[name] = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", block).group(1))
+def test_the_transfer_kernels_are_in_the_library_and_use_no_scratch(pkg):
+    kernels = embedded_kernel_names(pkg.runtime.LIB_PATHS["bake"])
     for k in ("k_bake_project", "k_bake_transfer_points", "k_bake_transfer_rays", "k_bake_transfer_probe"):
         mine = {n: v for n, v in kernels.items() if k in n}
         assert len(mine) == 1 and list(mine.values()) == [0] and "6ptbake" in list(mine)[0], (k, sorted(kernels))
@@ -63,16 +28,9 @@ def test_the_transfer_kernels_are_in_the_library_and_use_no_scratch(pkg, tmp_pat
 def test_transfer_refusals_return_before_the_device_is_touched(pkg):
     """Run in a child process with no visible device: a call that reached the device would fail with another status (or not return). The scene handles are never looked
     at; the check of n_prims against the target, which reads the handle, is tests/test_bake_transfer.py's."""
-    code = r'''
-import ctypes as C, sys
-import numpy as np
-sys.path.insert(0, %r)
-from _pkg import import_pkg
-pkg = import_pkg()
-A, K = pkg._abi, pkg._abi_bake
-lib = pkg.load_library(); bake = lib.bake
+    n = run_without_device(r'''
+K = pkg._abi_bake; bake = lib.bake
 tg, src = C.c_void_p(8), C.c_void_p(16)   # never looked at
-bad = A.PT_ERR_INVALID_ARG
 def params(**kw):
     d = dict(width=8, height=8, front=0.5, back=0.5, spp=4, nsamples=8, cos_sample=1, max_distance=float("inf"), sampler_type=0, spp_per_pass=0, profile=0); d.update(kw)
     return K.PtBakeTransferParams(*[d[k] for k, _ in K.PtBakeTransferParams._fields_])
@@ -82,9 +40,6 @@ ok, none = K.transfer_buffers(planes), K.transfer_buffers({})
 no_ao = K.transfer_buffers({k: v for k, v in planes.items() if k != "ao_w"})
 sel = np.ones(5, np.uint8); nosel = np.zeros(5, np.uint8)
 sp, np_ = sel.ctypes.data_as(A.u8p), nosel.ctypes.data_as(A.u8p)
-def refused(st, text):
-    assert st == bad, (st, text, lib.lib.pt_last_error())
-    assert text in lib.lib.pt_last_error(), (text, lib.lib.pt_last_error())
 p = params()
 size = C.c_uint32(5)
 # NULL arguments
@@ -139,11 +94,8 @@ refused(rays(p, sp, smp=four.ctypes.data_as(A.u32p)), b"outside the job")
 for k in planes:
     assert planes[k].tobytes() == kept[k].tobytes(), k
 assert not f3.any() and not f1.any() and not u8.any()
-print("refused")
-''' % ROOT
-    env = dict(os.environ, HIP_VISIBLE_DEVICES="")
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0 and "refused" in r.stdout, r.stderr[-3000:]
+''')
+    assert n == 103
 
 
 def test_encode_normal_map(pkg):

@@ -8,40 +8,33 @@ import re
 import subprocess
 import numpy as np
 import pytest
+from abi_checks import INC, ROOT, c99_probe
 from parity import assert_same_film, assert_same_render
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INC = os.path.join(ROOT, "include")
 
 
 def _structs(A):
     return [(n, t) for n, t in vars(A).items() if isinstance(t, type) and issubclass(t, C.Structure) and t is not C.Structure and n.startswith("Pt")]
 
 
-def test_struct_layouts_and_constants_equal_what_a_c_compiler_sees(pkg, tmp_path):
+def test_struct_layouts_and_constants_equal_what_a_c_compiler_sees(pkg):
     A = pkg._abi
     structs = _structs(A)
     assert {"PtSceneDesc", "PtRenderParams", "PtCounters", "PtKernelStat", "PtMaterial", "PtLight", "PtSphere", "PtBVHNode", "PtInstance", "PtTexture", "PtImage", "PtMedium",
             "PtObject", "PtBSSRDFTable"} <= {n for n, _ in structs}
     consts = sorted(n for n, v in vars(A).items() if re.fullmatch(r"PT_[A-Z0-9_]+", n) and isinstance(v, int))
     assert len(consts) > 60
-    src = ['#include <stdio.h>', '#include <stddef.h>', '#include "mi355pt.h"', 'int main(void) {']
+    src = []
     for name, t in structs:
         src.append(f'    printf("S {name} %zu\\n", sizeof({name}));')
         for f in t._fields_:
             src.append(f'    printf("F {name}.{f[0]} %zu %zu\\n", offsetof({name}, {f[0]}), sizeof((({name} *)0)->{f[0]}));')
     for c in consts:
         src.append(f'    printf("C {c} %lld\\n", (long long){c});')
-    src += ['    return 0;', '}']
-    cfile = tmp_path / "probe.c"; cfile.write_text("\n".join(src))
-    exe = tmp_path / "probe"
-    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", INC, str(cfile), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]          # (a field or constant the mirror has and the header lacks fails here, by name)
-    out = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split("\n")
-    seen = {}
-    for line in out:
-        if line:
-            p = line.split(); seen[(p[0], p[1])] = [int(x) for x in p[2:]]
+    words = c99_probe("mi355pt.h", "\n".join(src))   # (a field or constant the mirror has and the header lacks fails here, by name)
+    seen, pos = {}, 0
+    while pos < len(words):   # S name size | F name offset size | C name value
+        n = 2 if words[pos] == "F" else 1
+        seen[(words[pos], words[pos + 1])] = [int(x) for x in words[pos + 2:pos + 2 + n]]; pos += 2 + n
     for name, t in structs:
         assert seen[("S", name)] == [C.sizeof(t)], name
         for f in t._fields_:

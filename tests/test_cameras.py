@@ -13,6 +13,7 @@ import pytest
 
 import camera_model as cm
 from aov_reference import GROUND_I, GROUND_P, GROUND_UV, NONE, UP, _light, box_sums, film_rgb_sums, sample_values
+from model_math import concentric_sample_disk
 from parity import assert_same_film, assert_same_render
 
 pytestmark = pytest.mark.gpu
@@ -116,7 +117,7 @@ def _parent_perspective_differentials(oracle, rp, cs, o, d):
     dxc, dyc = sub(point(m, [F(1.0), F(0.0), F(0.0)]), p2t), sub(point(m, [F(0.0), F(1.0), F(0.0)]), p2t)
     sc = F(1.0) / np.sqrt(F(rp.spp))
     lens_r, focal = F(rp.lens_radius), F(rp.focal_distance)
-    dsk = cm.concentric_sample_disk(oracle, cs[:, 3:5]) if lens_r > 0 else None
+    dsk = concentric_sample_disk(oracle, cs[:, 3:5]) if lens_r > 0 else None
     out = np.zeros((len(cs), 12), F)
     for i in range(len(cs)):
         pc = point(m, [cs[i, 0], cs[i, 1], F(0.0)])

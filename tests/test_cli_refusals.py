@@ -6,6 +6,7 @@ import os
 import subprocess
 
 import pytest
+from abi_checks import no_device_env
 
 SCENE = ('LookAt 0 0 -1  0 0 0  0 1 0\nCamera "perspective" "float fov" 30\nFilm "image" "integer xresolution" 16 "integer yresolution" 16\n'
          'Sampler "sobol" "integer pixelsamples" 4\n%sWorldBegin\n'
@@ -64,8 +65,7 @@ REFUSALS = [
 
 
 def run(args, cwd):
-    env = dict(os.environ, HIP_VISIBLE_DEVICES="", ROCR_VISIBLE_DEVICES="")   # no device to touch: a refusal must come first
-    return subprocess.run(args, capture_output=True, text=True, timeout=60, env=env, cwd=cwd)
+    return subprocess.run(args, capture_output=True, text=True, timeout=60, env=no_device_env(), cwd=cwd)   # a refusal must come first
 
 
 @pytest.mark.parametrize("extra,scene,message", REFUSALS, ids=lambda v: " ".join(v) if isinstance(v, list) else None)

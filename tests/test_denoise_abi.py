@@ -2,37 +2,18 @@
 the argument errors that return before the device is touched."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi_checks import ROOT, assert_mirror, exported_names
 FIELDS = ["iterations", "sigma_l", "sigma_z", "sigma_n", "albedo_floor", "scale"]
 
 
-def test_mi355dn_header_is_c99_and_matches_the_ctypes_mirror(pkg, tmp_path):
+def test_mi355dn_header_is_c99_and_matches_the_ctypes_mirror(pkg):
     D = pkg._abi_dn
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "mi355dn.h"\n'
-                   'int main(void) { PtAOVBuffers b = {0, 0, 0}; (void)b; printf("%d", (int)sizeof(PtDenoiseParams));\n'
-                   + "".join('printf(" %%d", (int)offsetof(PtDenoiseParams, %s));\n' % f for f in FIELDS) + 'printf("\\n"); return 0; }\n')
-    exe = tmp_path / "probe"
-    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    out = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()
-    P = D.PtDenoiseParams
-    assert [int(v) for v in out] == [C.sizeof(P)] + [getattr(P, f).offset for f in FIELDS]
-    assert [name for name, _ in P._fields_] == FIELDS
-
+    assert_mirror("mi355dn.h", {D.PtDenoiseParams: FIELDS}, prelude="PtAOVBuffers b = {0, 0, 0}; (void)b;\n")   # (the header brings mi355aov.h's buffers along)
 
 def test_denoise_library_exports_only_its_entry_points(pkg):
-    path = pkg.runtime.DN_LIB_PATH
-    if not os.path.exists(path):
-        pytest.fail(f"{path} missing: __graft_entry__.build() builds it")
-    r = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True)
-    names = {line.split()[-1] for line in r.stdout.splitlines() if line.strip()}
-    assert names == set(pkg._abi_dn.ENTRY_POINTS)
+    assert exported_names(pkg.runtime.DN_LIB_PATH) == set(pkg._abi_dn.ENTRY_POINTS)
     header = open(os.path.join(ROOT, "include", "mi355dn.h")).read()
     for name in pkg._abi_dn.ENTRY_POINTS:
         assert f" {name}(" in header, name

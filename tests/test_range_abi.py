@@ -5,9 +5,7 @@ import subprocess
 
 import numpy as np
 import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INC = os.path.join(ROOT, "include")
+from abi_checks import INC, ROOT, assert_mirror, c99_probe, no_device_env
 
 # the prototypes as the feature defines them: C type of the function, and the ctypes signature the mirrors must carry
 PROTOTYPES = {
@@ -56,8 +54,7 @@ SCENE = ('LookAt 0 0 -1  0 0 0  0 1 0\nCamera "perspective" "float fov" 30\nFilm
 def test_mi355pbrt_refuses_malformed_sample_ranges_before_any_gpu_call(pkg, tmp_path, arg):
     scene = tmp_path / "s.pbrt"; scene.write_text(SCENE)
     out = tmp_path / "o.pfm"
-    env = dict(os.environ, HIP_VISIBLE_DEVICES="", ROCR_VISIBLE_DEVICES="")   # no device to touch: a usage error must come first
-    r = subprocess.run([pkg.frontend.CLI_PATH, str(scene), "--outfile", str(out), "--samples", arg], capture_output=True, text=True, timeout=60, env=env)
+    r = subprocess.run([pkg.frontend.CLI_PATH, str(scene), "--outfile", str(out), "--samples", arg], capture_output=True, text=True, timeout=60, env=no_device_env())   # a usage error must come first
     assert r.returncode == 2, (r.returncode, r.stderr)
     assert "usage:" in r.stderr and "--samples" in r.stderr and not out.exists()
 
@@ -113,17 +110,11 @@ def test_front_end_table_names_what_the_header_declares(pkg):
     assert pkg.frontend.PtfCheckpointHeader is F.PtfCheckpointHeader and pkg.frontend.PTF_CHECKPOINT_MAGIC == F.PTF_CHECKPOINT_MAGIC and pkg.frontend.ENTRY_POINTS is F.ENTRY_POINTS
 
 
-def test_checkpoint_header_matches_the_ctypes_mirror(pkg, tmp_path):
+def test_checkpoint_header_matches_the_ctypes_mirror(pkg):
     H = pkg._abi_front.PtfCheckpointHeader
     fields = [name for name, _ in H._fields_]
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "mi355front.h"\nint main(void) { printf("%u %d", PTF_CHECKPOINT_MAGIC, (int)sizeof(PtfCheckpointHeader));\n'
-                   + "".join('printf(" %%d", (int)offsetof(PtfCheckpointHeader, %s));\n' % f for f in fields) + "return 0; }\n")
-    exe = tmp_path / "probe"
-    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", INC, str(src), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    out = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    assert out == [pkg._abi_front.PTF_CHECKPOINT_MAGIC, C.sizeof(H)] + [getattr(H, f).offset for f in fields]
+    assert_mirror("mi355front.h", {H: fields})
+    assert [int(v) for v in c99_probe("mi355front.h", 'printf("%u", PTF_CHECKPOINT_MAGIC);')] == [pkg._abi_front.PTF_CHECKPOINT_MAGIC]
     assert fields == ["magic", "version", "width", "height", "spp", "first_sample", "samples_done", "reserved", "params_hash"] and C.sizeof(H) == 40
 
 

@@ -1,10 +1,10 @@
 """No GPU: pt_tile_grid is the arithmetic of integrator.rs:277-279 on the sample bounds -- the grid the tile lists of pt_render_tiles / pt_tiles_select index --, and
 mi355pbrt's usage errors for --adaptive."""
 import ctypes as C
-import os
 import subprocess
 
 import pytest
+from abi_checks import no_device_env
 from range_scene import range_scene
 from tile_scene import BACKGROUND_PBRT, grid_of, with_filter
 
@@ -57,7 +57,7 @@ def test_mi355pbrt_refuses_adaptive_with_what_it_cannot_keep_before_any_gpu_call
     assert extra or "ambientocclusion" in text
     scene = tmp_path / "adaptive.pbrt"; scene.write_text(text)
     out = tmp_path / "o.pfm"
-    env = dict(os.environ, HIP_VISIBLE_DEVICES="", ROCR_VISIBLE_DEVICES="")   # no device to touch: the usage error must come first
+    env = no_device_env()   # the usage error must come first
     r = subprocess.run([pkg.frontend.CLI_PATH, str(scene), "--outfile", str(out), "--adaptive", "0.1", *extra], capture_output=True, text=True, timeout=60, env=env, cwd=str(tmp_path))
     assert r.returncode == 2, (r.returncode, r.stderr)
     assert "usage:" in r.stderr and "--adaptive with " + why in r.stderr and not out.exists() and not (tmp_path / "job.ckpt").exists()

@@ -1,14 +1,12 @@
 """A float32 numpy model of the transfer bake's contract (include/mi355bake.h "Transfer"): the projection ray of every owned texel of the target, the source hit
 classified, height, position, world- and tangent-space normal, and the AO at the hit -- every operation in the header's order. It builds on bake_reference (owner
-map, Triangle::intersect's interaction, array values, directions, offset_ray_origin, accumulate); the hits and the occlusion come from the oracle's closest-hit and
-any-hit queries over the SOURCE scene."""
+map, Triangle::intersect's interaction, array values, directions, sample_list, add_ao_rays) and on model_math's float32 arithmetic; the hits and the occlusion
+come from the oracle's closest-hit and any-hit queries over the SOURCE scene."""
 import types
 
 import numpy as np
 import bake_reference as M
-
-F = M.F
-NONE = M.NONE
+from model_math import F, NONE, coordinate_system, cross, dot, normalize, offset_ray_origin
 
 
 def partials(sd, prim):
@@ -28,11 +26,11 @@ def partials(sd, prim):
             inv = F(1) / det
             dpdu = (dp02 * duv12[1] - dp12 * duv02[1]) * inv
             dpdv = (dp02 * (-duv12[0]) + dp12 * duv02[0]) * inv
-        c = M.cross(dpdu, dpdv)
-        if degenerate or M.dot(c, c) == 0:
-            ng = M.cross(p2 - p0, p1 - p0)
-            if M.dot(ng, ng) != 0:
-                dpdu, dpdv = M.coordinate_system(M.normalize(ng))
+        c = cross(dpdu, dpdv)
+        if degenerate or dot(c, c) == 0:
+            ng = cross(p2 - p0, p1 - p0)
+            if dot(ng, ng) != 0:
+                dpdu, dpdv = coordinate_system(normalize(ng))
     return dpdu, dpdv
 
 
@@ -58,14 +56,14 @@ def top_level_triangles(sd):
 def tangent_frame(si, dpdv, ns):
     """(sv, tv) of a target texel (step 4)."""
     with np.errstate(all="ignore"):
-        sv = si["dpdu"] - ns * M.dot(ns, si["dpdu"])
-        if M.dot(sv, sv) > 0:
-            sv = M.normalize(sv)
-            tv = M.cross(ns, sv)
-            if M.dot(tv, dpdv) < 0:
+        sv = si["dpdu"] - ns * dot(ns, si["dpdu"])
+        if dot(sv, sv) > 0:
+            sv = normalize(sv)
+            tv = cross(ns, sv)
+            if dot(tv, dpdv) < 0:
                 tv = -tv
             return sv, tv, False
-        sv, tv = M.coordinate_system(ns)
+        sv, tv = coordinate_system(ns)
         return sv, tv, True
 
 
@@ -75,7 +73,7 @@ def projection(sd_t, owner, front, back):
     sis = M.texel_interactions(sd_t, owner)
     texels = np.array(sorted(sis), dtype=np.int64)
     with np.errstate(all="ignore"):
-        ns = np.array([M.normalize(sis[t]["sh_n"]) for t in texels], F).reshape(-1, 3)
+        ns = np.array([normalize(sis[t]["sh_n"]) for t in texels], F).reshape(-1, 3)
         p = np.array([sis[t]["p"] for t in texels], F).reshape(-1, 3)
         o = (p + ns * F(front)).astype(F)
     return dict(texel=texels, o=o, d=(-ns).astype(F), t_max=np.full(len(texels), F(front) + F(back), F), si=[sis[t] for t in texels], ns=ns)
@@ -83,27 +81,23 @@ def projection(sd_t, owner, front, back):
 
 def ao_rays(oracle, pkg, hits, width, height, spp, nsamples, cos_sample, sampler, samples=None):
     """The AO rays of the detail hits (step 5), ordered by texel, then (s, k): dict(texel, s, k, o, d, w). hits: [(texel, hs, ns)]."""
-    first, count = (0, spp) if samples is None else samples
-    per = count * nsamples
-    texels = np.array([h[0] for h in hits], dtype=np.int64)
-    tx = np.repeat(texels, per)
-    s = np.tile(np.repeat(np.arange(first, first + count, dtype=np.int64), nsamples), len(texels))
-    k = np.tile(np.arange(nsamples, dtype=np.int64), len(texels) * count)
+    tx, s, k = M.sample_list([h[0] for h in hits], spp, nsamples, samples)
     if len(tx) == 0:
         z3 = np.zeros((0, 3), F)
         return dict(texel=tx, s=s, k=k, o=z3, d=z3, w=np.zeros(0, F))
+    per = len(tx) // len(hits)
     u = M.array_samples(oracle, pkg, sampler, width, height, tx % width, tx // width, s * nsamples + k)
     wi, pdf = M.directions(oracle, u, cos_sample)
     with np.errstate(all="ignore"):
         rep = lambda rows: np.repeat(np.array(rows, F).reshape(-1, 3), per, axis=0)
         ng = rep([hs["n"] for _, hs, _ in hits])                                                       # hs.n: the origin's offset and t
-        n = rep([(-hs["n"] if M.dot(hs["n"], ns) < 0 else hs["n"]) for _, hs, ns in hits])             # face_forward(hs.n, -d), -d = ns
-        sv = rep([M.normalize(hs["dpdu"]) for _, hs, _ in hits])
-        tv = rep([M.cross(hs["n"], M.normalize(hs["dpdu"])) for _, hs, _ in hits])
+        n = rep([(-hs["n"] if dot(hs["n"], ns) < 0 else hs["n"]) for _, hs, ns in hits])             # face_forward(hs.n, -d), -d = ns
+        sv = rep([normalize(hs["dpdu"]) for _, hs, _ in hits])
+        tv = rep([cross(hs["n"], normalize(hs["dpdu"])) for _, hs, _ in hits])
         p, perr = rep([hs["p"] for _, hs, _ in hits]), rep([hs["p_error"] for _, hs, _ in hits])
         wo = (sv * wi[:, 0:1] + tv * wi[:, 1:2] + n * wi[:, 2:3]).astype(F)
-        o = M.offset_ray_origin(p, perr, ng, wo)
-        w = ((wo[:, 0] * n[:, 0] + wo[:, 1] * n[:, 1] + wo[:, 2] * n[:, 2]) / (pdf * F(nsamples))).astype(F)
+        o = offset_ray_origin(p, perr, ng, wo)
+        w = (dot(wo, n) / (pdf * F(nsamples))).astype(F)
     return dict(texel=tx, s=s, k=k, o=o, d=wo, w=w)
 
 
@@ -134,11 +128,11 @@ def transfer(oracle, pkg, sd_t, sd_s, select, width, height, front, back, spp=1,
         si, ns = pr["si"][j], pr["ns"][j]
         hs = source_interaction(sd_s, int(hp[j]), hb[j, 0], hb[j, 1], hb[j, 2])
         with np.errstate(all="ignore"):
-            nh = M.normalize(hs["sh_n"])
-            if M.dot(nh, -ns) > 0:
+            nh = normalize(hs["sh_n"])
+            if dot(nh, -ns) > 0:
                 nh = -nh
             sv, tv, fell = tangent_frame(si, partials(sd_t, int(owner.reshape(-1)[texel]))[1], ns)
-            pos[texel] = hs["p"]; nrm[texel] = nh; tn[texel] = np.array([M.dot(nh, sv), M.dot(nh, tv), M.dot(nh, ns)], F)
+            pos[texel] = hs["p"]; nrm[texel] = nh; tn[texel] = np.array([dot(nh, sv), dot(nh, tv), dot(nh, ns)], F)
         if fell:
             fallback.append(texel)
         hits.append((texel, hs, ns))
@@ -149,7 +143,7 @@ def transfer(oracle, pkg, sd_t, sd_s, select, width, height, front, back, spp=1,
     if nsamples:
         r = ao_rays(oracle, pkg, hits, width, height, spp, nsamples, cos_sample, sampler, samples)
         occ = orc_source.trace_any(r["o"], r["d"], np.full(len(r["w"]), max_distance, F)) if len(r["w"]) else np.zeros(0, np.uint8)
-        M.accumulate(ao_w, r, occ, nsamples)
+        M.add_ao_rays(ao_w, r, occ, nsamples)
         out.update(ao_rays=r, occluded=occ, n_rays=len(r["w"]))
     out["ao_w"] = ao_w
     return out
