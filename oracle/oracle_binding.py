@@ -5,6 +5,8 @@ import importlib
 import os
 import subprocess
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SAN = bool(os.environ.get("PT_SAN"))   # ASan/UBSan build of the oracle (tools/san_cpu_tests.sh preloads the sanitizer runtimes)
 LIB_PATH = os.path.join(_HERE, "liboracle_san.so" if SAN else "liboracle.so")
@@ -22,6 +24,14 @@ def build(verbose=False):
 # orc_* functions that mirror a pt_* entry point of include/mi355pt.h: their signature is the one _abi.ENTRY_POINTS declares
 _MIRRORED = ("pt_scene_create", "pt_scene_destroy", "pt_scene_bvh_info", "pt_scene_bvh_read", "pt_get_counters", "pt_film_resolve",
              "pt_trace_closest", "pt_trace_any", "pt_sobol_samples", "pt_halton_samples", "pt_camera_rays")
+
+
+# orc_intersect's words per ray (ref_kats_shapes.cpp): name -> (first word, words, is float)
+INTERSECT_FIELDS = {"hit": (0, 1, False), "prim": (1, 1, False), "inst": (2, 1, False), "t": (3, 1, True), "b": (4, 3, True), "p": (7, 3, True), "p_error": (10, 3, True),
+                    "n": (13, 3, True), "wo": (16, 3, True), "uv": (19, 2, True), "dpdu": (21, 3, True), "dpdv": (24, 3, True), "sh_n": (27, 3, True),
+                    "sh_dpdu": (30, 3, True), "sh_dpdv": (33, 3, True), "sh_dndu": (36, 3, True), "sh_dndv": (39, 3, True), "has_shape": (42, 1, False),
+                    "shape_flip": (43, 1, False)}
+INTERSECT_WORDS = 44
 
 
 def signatures(A, AO):
@@ -85,6 +95,7 @@ def signatures(A, AO):
         "orc_test_sphere_reintersect": (i, [i, i, i, ip]),
         "orc_tri_intersect": (i, [vp, u32, fp, fp, f, fp, fp, fp, fp, fp]),
         "orc_tri_intersect_p": (i, [vp, u32, fp, fp, f]),
+        "orc_intersect": (i, [vp, u32, fp, fp, fp, u32p]),
     })
     return sig
 
@@ -128,5 +139,14 @@ def _scene_class(handle):
 
         def seconds(self):
             return self.O.lib.orc_last_render_seconds(self.h)
+
+        def intersect(self, o, d, tmax):
+            """orc_intersect: Scene::intersect of the rays, (n, INTERSECT_WORDS) uint32 -- the hit record and the whole SurfaceInteraction (INTERSECT_FIELDS);
+            a miss leaves its row zero. counters() afterwards as after trace_closest."""
+            o, d, tmax = (np.ascontiguousarray(x, dtype=np.float32) for x in (o, d, tmax))
+            out = np.zeros((len(tmax), INTERSECT_WORDS), np.uint32)
+            self._call("intersect", self.h, len(tmax), o.ctypes.data_as(self.O.A.fp), d.ctypes.data_as(self.O.A.fp), tmax.ctypes.data_as(self.O.A.fp),
+                       out.ctypes.data_as(self.O.A.u32p))
+            return out
 
     return OracleScene

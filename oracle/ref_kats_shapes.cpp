@@ -324,6 +324,30 @@ int orc_tri_intersect(orc_scene *h, uint32_t tri, const float *o, const float *d
     n[0] = si.n.x; n[1] = si.n.y; n[2] = si.n.z;
     return 1;
 }
+// Scene::intersect of n rays (o, d: 3n floats, tmax: n) with everything it leaves behind, for tests/test_interaction_probe.py to compare the device's
+// fill_hit / fill_hit_pkt with, field by field. Per ray 44 words of out: 0 hit flag, 1 prim, 2 inst, 3 t, 4-6 b, then the SurfaceInteraction:
+// 7-9 p, 10-12 p_error, 13-15 n, 16-18 wo, 19-20 uv, 21-23 dpdu, 24-26 dpdv, 27-29 sh_n, 30-32 sh_dpdu, 33-35 sh_dpdv, 36-38 sh_dndu, 39-41 sh_dndv, 42 has_shape,
+// 43 shape_flip. A miss leaves the ray's words zero. Counters as orc_trace_closest leaves them.
+int orc_intersect(orc_scene *h, uint32_t n, const float *o, const float *d, const float *tmax, uint32_t *out) {
+    constexpr size_t kWords = 44;
+    if (!h || !o || !d || !tmax || !out) return PT_ERR_INVALID_ARG;
+    Counters c;
+    for (uint32_t i = 0; i < n; ++i) {
+        Ray r(V3(o[3 * i], o[3 * i + 1], o[3 * i + 2]), V3(d[3 * i], d[3 * i + 1], d[3 * i + 2]), tmax[i]);
+        uint32_t *w = out + kWords * i;
+        std::memset(w, 0, kWords * sizeof(uint32_t));
+        SurfaceInteraction si;
+        if (!h->scene.intersect(r, si, c)) continue;
+        const float f[39] = {si.t, si.b[0], si.b[1], si.b[2], si.p.x, si.p.y, si.p.z, si.p_error.x, si.p_error.y, si.p_error.z, si.n.x, si.n.y, si.n.z, si.wo.x, si.wo.y, si.wo.z,
+                             si.uv.x, si.uv.y, si.dpdu.x, si.dpdu.y, si.dpdu.z, si.dpdv.x, si.dpdv.y, si.dpdv.z, si.sh_n.x, si.sh_n.y, si.sh_n.z,
+                             si.sh_dpdu.x, si.sh_dpdu.y, si.sh_dpdu.z, si.sh_dpdv.x, si.sh_dpdv.y, si.sh_dpdv.z, si.sh_dndu.x, si.sh_dndu.y, si.sh_dndu.z, si.sh_dndv.x, si.sh_dndv.y, si.sh_dndv.z};
+        w[0] = 1u; w[1] = si.prim; w[2] = si.inst;
+        std::memcpy(w + 3, f, sizeof f);   // words 3 .. 41
+        w[42] = si.has_shape ? 1u : 0u; w[43] = si.shape_flip ? 1u : 0u;
+    }
+    h->counters = c;
+    return PT_OK;
+}
 int orc_tri_intersect_p(orc_scene *h, uint32_t tri, const float *o, const float *d, float tmax) {
     Ray r(V3(o[0], o[1], o[2]), V3(d[0], d[1], d[2]), tmax);
     Float tt, bb[3];

@@ -21,61 +21,25 @@ A test must not pass by comparing nothing: per material the shares of random que
 share of random queries with a non-zero sampled pdf."""
 import ctypes as C
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
+from probe_build import probe_library
 
 pytestmark = pytest.mark.gpu
 
 if os.environ.get("PT_LIB_PATH"):   # a kernel-variant library: its pt_scene layout may differ from the one the probe is compiled against
     pytest.skip("PT_LIB_PATH names a variant library; the probe reads pt_scene of the tree's own headers", allow_module_level=True)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "pbrt-rust_amd", "csrc")
-PROBE_SRC = os.path.join(ROOT, "tests", "device_probe")
 F = np.float32
 U_TOP = float(np.float32(1.0) - np.float32(2.0 ** -24))   # the largest float below 1
 
 
 # ---- the probe library ------------------------------------------------------------------------------------------------------------------------------
-def makefile_hipflags():
-    """(hipcc, flags) as pbrt-rust_amd/csrc/Makefile holds them: the HIPFLAGS line with $(ARCH) expanded and $(EXTRA_HIPFLAGS) empty."""
-    text = open(os.path.join(CSRC, "Makefile")).read()
-    var = lambda name: re.search(r"^%s\s*\??=\s*(.*)$" % name, text, re.M).group(1).strip()
-    flags = var("HIPFLAGS").replace("$(ARCH)", var("ARCH")).replace("$(EXTRA_HIPFLAGS)", "")
-    assert "$(" not in flags and "-ffp-contract=off" in flags, flags
-    return os.environ.get("HIPCC") or var("HIPCC"), flags.split(), var("ARCH")
-
-
 @pytest.fixture(scope="module")
 def probe(pkg, gpu, tmp_path_factory):
-    """libdevprobe.so, built here from tests/device_probe/*.hip and linked against libmi355pt.so (pth::material_class) the way libmi355ao.so is."""
-    out = tmp_path_factory.mktemp("device_probe")
-    hipcc, flags, arch = makefile_hipflags()
-    names = ("bsdf_probe", "light_probe")
-    jobs = [subprocess.Popen([hipcc] + flags + ["-fvisibility=hidden", "-c", "-o", str(out / (n + ".o")), os.path.join(PROBE_SRC, n + ".hip")],
-                             stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for n in names]
-    for n, j in zip(names, jobs):
-        log = j.communicate()[0]
-        assert j.returncode == 0, f"hipcc {n}.hip failed:\n{log[-4000:]}"
-    so = str(out / "libdevprobe.so")
-    libdir = os.path.dirname(pkg.runtime.LIB_PATH)
-    r = subprocess.run([hipcc, "-shared", "-fPIC", f"--offload-arch={arch}", "-o", so] + [str(out / (n + ".o")) for n in names] +
-                       ["-L" + libdir, "-lmi355pt", "-Wl,-rpath," + libdir], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    A = pkg._abi
-    lib = C.CDLL(so)
-    u32, i32, vp, u32p, i32p, fp = C.c_uint32, C.c_int32, C.c_void_p, A.u32p, A.i32p, A.fp
-    for name, res, args in (("probe_bsdf_words", u32, []), ("probe_light_words", u32, []),
-                            ("probe_material_class", C.c_int, [C.POINTER(A.PtMaterial), u32, u32, i32p, i32p]),
-                            ("probe_bsdf", C.c_int, [vp, C.c_int, C.c_int, u32, u32, fp, fp, fp, u32p]),
-                            ("probe_light_count", C.c_int, [vp, u32p, i32p]),
-                            ("probe_light", C.c_int, [vp, u32, u32, fp, fp, fp, fp, fp, u32p])):
-        fn = getattr(lib, name); fn.restype = res; fn.argtypes = args
-    assert lib.probe_bsdf_words() == 18 and lib.probe_light_words() == 8
-    return lib
+    """libdevprobe.so of tests/device_probe/*.hip: built once per session by tests/probe_build.py, shared with tests/test_interaction_probe.py."""
+    return probe_library(pkg, tmp_path_factory.mktemp("device_probe"))
 
 
 def _fp(a):
