@@ -84,6 +84,7 @@ def signatures(A, AO):
         "orc_light_sample_li": (i, [vp, u32, fp, fp, fp, u32, fp, fp, fp, fp]),
         "orc_light_pdf_li": (i, [vp, u32, fp, fp, fp, u32, fp, fp]),
         "orc_bsdf_eval": (i, [vp, u32, u32, fp, fp, fp, fp, fp, fp, fp, fp, i32p, i32p]),
+        "orc_bssrdf_eval": (i, [vp, u32, fp, fp, u32, fp, fp, u32, fp, fp, u32, fp, fp, u32, fp, u32p, fp, u32, fp, i32p, u32p, u32, fp, fp]),
         # shape loops and probes (ref_kats_shapes.cpp)
         "orc_test_triangle_sampling": (i, [i, i, dp]),
         "orc_test_triangle_solid_angle": (i, [i, i, dp]),

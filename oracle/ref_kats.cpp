@@ -4,7 +4,8 @@
 // tests/fp.rs:46-57 (float_bits), tests/bitops.rs:7-64 (log2_int, round_up_pow2), tests/sampling.rs:24-97 (scrambled radical inverse,
 // generator matrices, Gray-code samples), tests/hg.rs (HenyeyGreenstein::p / sample_p); then the function probes that
 // tests/test_oracle_kats.py and tests/test_oracle_bsdf.py call per query: Sobol / Halton / radical inverse, next_float, find_interval,
-// PCG32, Distribution1D, the deterministic math, offset_ray_origin, the BSSRDF tables, light sample_li / pdf_li and a material's BSDF.
+// PCG32, Distribution1D, the deterministic math, offset_ray_origin, the BSSRDF tables, light sample_li / pdf_li, a material's BSDF and (for
+// tests/test_bssrdf_probe.py and tests/test_bssrdf_zoo.py) a material's BSSRDF, section by section.
 #include "ref_efloat.h"
 #include "ref_bssrdf.h"
 #include <cmath>
@@ -338,6 +339,84 @@ int orc_bsdf_eval(orc_scene *h, uint32_t mi, uint32_t n, const float *wo, const 
             for (int c = 0; c < 3; ++c) s_f_out[3 * i + c] = f.c[c];
             if (s_type_out) s_type_out[i] = sampled;
         }
+    }
+    return 0;
+}
+
+// A material's BSSRDF, call by call, for tests/test_bssrdf_probe.py (the device's dev_bssrdf.h answers the same words) and tests/test_bssrdf_zoo.py.
+// scattering_functions_of(material mi) at the interaction `frame` gives (15 floats: p, n, sh_n, sh_dpdu, sh_dpdv; uv = (0.5, 0.5), no shape, no textures);
+// status 1: a bad argument, 2: the material leaves no BSSRDF there -- nothing is written in either case. Every section is optional: a null output (or a
+// count of zero) skips it. Words are floats unless said otherwise.
+//   state (19):          sigma_t.rgb, rho.rgb (DisneyBSSRDF: d.rgb, R.rgb), eta, ns, ss, ts, po_p
+//   radii (6 per r):     sr(r).rgb, pdf_sr(ch, r) for ch = 0, 1, 2
+//   samples (3 per u):   sample_sr(ch, u) for ch = 0, 1, 2
+//   exits (4 per point): pdf_sp(pi_p, pi_n), sr(length(po_p - pi_p)).rgb  -- in: 6 floats (pi_p, pi_n); the two values subsurface_step takes
+//   segments (8 per):    probe_segment's boolean (a uint32), start, target, u1n -- in: 3 floats (u1, u2.x, u2.y); start / target stay 0 where it returns false
+//   adapter (12 per):    f.rgb, pdf, sample_f's wi, f.rgb, pdf and sampled type (an int32) of BSDF(pi, 1.0) with the one BX_BSSRDF lobe, built as subsurface_step
+//                        builds it, at the exit interaction `exit_frame` (15 floats as `frame`) -- in: 8 floats (wo, wi, u) and one int32 of flags; pdf and wi are 0 on entry
+//   conversion (6 per):  subsurface_from_diffuse(kd, mfp) on the material's table: sigma_a.rgb, sigma_s.rgb -- in: 6 floats; a tabulated material only (else status 1)
+static SurfaceInteraction bssrdf_probe_interaction(const float *f) {
+    SurfaceInteraction si{};
+    si.p = V3(f[0], f[1], f[2]); si.p_error = V3(0, 0, 0); si.n = V3(f[3], f[4], f[5]); si.sh_n = V3(f[6], f[7], f[8]); si.wo = si.sh_n;
+    si.sh_dpdu = V3(f[9], f[10], f[11]); si.sh_dpdv = V3(f[12], f[13], f[14]); si.dpdu = si.sh_dpdu; si.dpdv = si.sh_dpdv;
+    si.uv = P2(0.5f, 0.5f); si.has_shape = false; si.shape_flip = false; si.prim = 0;
+    return si;
+}
+int orc_bssrdf_eval(orc_scene *h, uint32_t mi, const float *frame, float *state,
+                    uint32_t n_r, const float *r, float *r_out, uint32_t n_u, const float *u, float *u_out,
+                    uint32_t n_x, const float *x, float *x_out, uint32_t n_s, const float *s, uint32_t *s_out,
+                    const float *exit_frame, uint32_t n_a, const float *a, const int32_t *a_flags, uint32_t *a_out,
+                    uint32_t n_c, const float *c, float *c_out) {
+    if (!h || !frame || mi >= h->scene.materials.size()) return 1;
+    if ((n_r && r_out && !r) || (n_u && u_out && !u) || (n_x && x_out && !x) || (n_s && s_out && !s) || (n_a && a_out && (!a || !a_flags || !exit_frame)) || (n_c && c_out && !c)) return 1;
+    SurfaceInteraction si = bssrdf_probe_interaction(frame);
+    BSDF bsdf; TabulatedBSSRDF b; bool has = false;
+    if (!scattering_functions_of(h->scene, mi, si, bsdf, &b, &has, nullptr) || !has) return 2;
+    if (n_c && c_out && b.disney) return 1;
+    auto put3 = [](float *o, V3 v) { o[0] = v.x; o[1] = v.y; o[2] = v.z; };
+    auto word = [](Float v) { return float_to_bits(v); };
+    if (state) {
+        for (int k = 0; k < 3; ++k) { state[k] = b.disney ? b.dD.c[k] : b.sigma_t.c[k]; state[3 + k] = b.disney ? b.dR.c[k] : b.rho.c[k]; }
+        state[6] = b.eta; put3(state + 7, b.ns); put3(state + 10, b.ss); put3(state + 13, b.ts); put3(state + 16, b.po_p);
+    }
+    if (r_out) for (uint32_t i = 0; i < n_r; ++i) {
+        const RGB v = b.sr(r[i]);
+        for (int k = 0; k < 3; ++k) { r_out[6 * i + k] = v.c[k]; r_out[6 * i + 3 + k] = b.pdf_sr(k, r[i]); }
+    }
+    if (u_out) for (uint32_t i = 0; i < n_u; ++i) for (int k = 0; k < 3; ++k) u_out[3 * i + k] = b.sample_sr(k, u[i]);
+    if (x_out) for (uint32_t i = 0; i < n_x; ++i) {
+        const V3 pp(x[6 * i], x[6 * i + 1], x[6 * i + 2]), pn(x[6 * i + 3], x[6 * i + 4], x[6 * i + 5]);
+        x_out[4 * i] = b.pdf_sp(pp, pn);
+        const RGB v = b.sr(length(b.po_p - pp));
+        for (int k = 0; k < 3; ++k) x_out[4 * i + 1 + k] = v.c[k];
+    }
+    if (s_out) for (uint32_t i = 0; i < n_s; ++i) {
+        V3 start(0, 0, 0), target(0, 0, 0); Float u1n = 0.0f;
+        const bool ok = b.probe_segment(s[3 * i], P2(s[3 * i + 1], s[3 * i + 2]), start, target, u1n);
+        uint32_t *o = s_out + 8 * (size_t)i;
+        o[0] = ok ? 1u : 0u; o[1] = word(start.x); o[2] = word(start.y); o[3] = word(start.z);
+        o[4] = word(target.x); o[5] = word(target.y); o[6] = word(target.z); o[7] = word(u1n);
+    }
+    if (a_out && n_a) {
+        SurfaceInteraction pi = bssrdf_probe_interaction(exit_frame);
+        BSDF pibsdf; pibsdf.init(pi, 1.0f);   // ref_render.cpp subsurface_step: sample_s (bssrdf.rs:559-574)
+        { Bxdf bx; bx.kind = BX_BSSRDF; bx.type = BSDF_REFLECTION | BSDF_DIFFUSE; bx.etab = b.eta; pibsdf.add(bx); }
+        for (uint32_t i = 0; i < n_a; ++i) {
+            const float *q = a + 8 * (size_t)i;
+            const V3 wo(q[0], q[1], q[2]), wi(q[3], q[4], q[5]);
+            const RGB f = pibsdf.f(wo, wi, a_flags[i]);
+            const Float pdf = pibsdf.pdf(wo, wi, a_flags[i]);
+            V3 w(0, 0, 0); Float spdf = 0.0f; int sampled = 0;
+            const RGB sf = pibsdf.sample_f(wo, w, P2(q[6], q[7]), spdf, a_flags[i], sampled);
+            uint32_t *o = a_out + 12 * (size_t)i;
+            o[0] = word(f.c[0]); o[1] = word(f.c[1]); o[2] = word(f.c[2]); o[3] = word(pdf);
+            o[4] = word(w.x); o[5] = word(w.y); o[6] = word(w.z); o[7] = word(sf.c[0]); o[8] = word(sf.c[1]); o[9] = word(sf.c[2]); o[10] = word(spdf); o[11] = (uint32_t)sampled;
+        }
+    }
+    if (c_out) for (uint32_t i = 0; i < n_c; ++i) {
+        RGB sa(0.0f), ss(0.0f);
+        subsurface_from_diffuse(*b.table, RGB(c[6 * i], c[6 * i + 1], c[6 * i + 2]), RGB(c[6 * i + 3], c[6 * i + 4], c[6 * i + 5]), sa, ss);
+        for (int k = 0; k < 3; ++k) { c_out[6 * i + k] = sa.c[k]; c_out[6 * i + 3 + k] = ss.c[k]; }
     }
     return 0;
 }

@@ -10,8 +10,10 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "pbrt-rust_amd", "csrc")
 PROBE_SRC = os.path.join(ROOT, "tests", "device_probe")
-UNITS = ("bsdf_probe", "light_probe", "interaction_probe")
+UNITS = ("bsdf_probe", "light_probe", "interaction_probe", "bssrdf_probe")
 BSDF_WORDS, LIGHT_WORDS, INTERACTION_WORDS = 18, 8, 45
+# bssrdf_probe.hip's sections in order, each with its words in and out per query: the layout of the oracle's orc_bssrdf_eval
+BSSRDF_SECTIONS = (("state", 0, 19), ("radii", 1, 6), ("samples", 1, 3), ("exits", 6, 4), ("segments", 3, 8), ("adapter", 9, 12), ("conversion", 6, 6))
 _BUILT = {}
 
 
@@ -59,8 +61,12 @@ def probe_library(pkg, out=None):
                             ("probe_bsdf", C.c_int, [vp, C.c_int, C.c_int, u32, u32, fp, fp, fp, u32p]),
                             ("probe_light_count", C.c_int, [vp, u32p, i32p]),
                             ("probe_light", C.c_int, [vp, u32, u32, fp, fp, fp, fp, fp, u32p]),
-                            ("probe_interaction", C.c_int, [vp, C.c_int, u32, fp, fp, fp, u32p])):
+                            ("probe_interaction", C.c_int, [vp, C.c_int, u32, fp, fp, fp, u32p]),
+                            ("probe_bssrdf_sections", u32, []), ("probe_bssrdf_words_in", u32, [u32]), ("probe_bssrdf_words", u32, [u32]),
+                            ("probe_bssrdf", C.c_int, [vp, u32, C.c_int, C.c_int, fp, u32, fp, u32p])):
         fn = getattr(lib, name); fn.restype = res; fn.argtypes = args
     assert lib.probe_bsdf_words() == BSDF_WORDS and lib.probe_light_words() == LIGHT_WORDS and lib.probe_interaction_words() == INTERACTION_WORDS
+    assert lib.probe_bssrdf_sections() == len(BSSRDF_SECTIONS)
+    assert [(lib.probe_bssrdf_words_in(k), lib.probe_bssrdf_words(k)) for k in range(len(BSSRDF_SECTIONS))] == [(a, b) for _, a, b in BSSRDF_SECTIONS]
     _BUILT["lib"] = lib
     return lib

@@ -54,13 +54,15 @@ def bits(a):
     return b
 
 
-def assert_same_bits(dev, ref, what):
+def assert_same_bits(dev, ref, what, tags=None):
+    """`tags`: per query, the name of the family it belongs to (tests/bssrdf_zoo.py): the message then names the first one's and every family that differs."""
     d, r = bits(dev), bits(ref)
     if np.array_equal(d, r):
         return
     bad = np.argwhere(d != r)
     q = int(bad[0][0])
-    raise AssertionError(f"{what}: {len(np.unique(bad[:, 0]))} of {len(d)} queries differ; first at query {q}: device {np.atleast_1d(d[q])} "
+    family = "" if tags is None else f" [{tags[q]}; families that differ: {sorted({str(t) for t in np.asarray(tags)[np.unique(bad[:, 0])]})[:8]}]"
+    raise AssertionError(f"{what}: {len(np.unique(bad[:, 0]))} of {len(d)} queries differ; first at query {q}{family}: device {np.atleast_1d(d[q])} "
                          f"({np.atleast_1d(np.asarray(dev, F)[q])}) != reference {np.atleast_1d(r[q])} ({np.atleast_1d(np.asarray(ref, F)[q])})")
 
 

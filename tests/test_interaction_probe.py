@@ -3,7 +3,7 @@ sphere_fill_interaction (dev_sphere.h) and the instance branch that carries an o
 the quadrics of sphere_hit traced with rays aimed at their edges. Renders reach this stage with generic hits only: never a vertex, a zero interpolated normal,
 S parallel to N, a UV determinant below 1e-8, a pole, a disk's centre, a mirrored or non-uniformly scaled instance.
 
-tests/device_probe/interaction_probe.hip is test code beside bsdf_probe.hip / light_probe.hip (tests/probe_build.py builds the three once per session): it traces the
+tests/device_probe/interaction_probe.hip is test code beside bsdf_probe.hip / light_probe.hip (tests/probe_build.py builds them all once per session): it traces the
 rays with the library's own pth::launch_trace, receives the two quads of the hit record as k_trace writes them for the render, and calls the UNMODIFIED fill functions once
 per ray. Scenes, queries, the float64 model and the conditions under which a comparison compares something: tests/interaction_zoo.py; what holds of the oracle alone:
 tests/test_interaction_zoo.py.
